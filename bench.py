@@ -15,9 +15,11 @@ No PyTorch anywhere: kernels, streams, events and the RCCL exchange all go throu
 bench.py --gpus N` (RANK / LOCAL_RANK / WORLD_SIZE in the environment) it runs as one of them.  Either way rank 0
 prints ONE JSON line (see the task contract).
 
-At N = 1 the line also carries, measured after the timed region: the roofline of the dominant kernel, the CPU baseline
-(C oracle on a bounded sample, with the live parity check incl. the ill-posed windows), the other two single-GPU
-BASELINE configs (`config.other_configs`: C3 64x64 @ 75 %, C4 4K) and the host-fed (PCIe-inclusive) rates.
+A plain run sets up, warms up, times the --steps steps, writes the last step's results if --dump-outputs DIR is given and
+prints the line.  Everything else is measured after the timed region with --full only: the roofline of the dominant kernel
+and the sustained loop; at N = 1 the CPU baseline (C oracle on a bounded sample, with the live parity check incl. the
+ill-posed windows), the other two single-GPU BASELINE configs (`config.other_configs`: C3 64x64 @ 75 %, C4 4K) and the
+host-fed (PCIe-inclusive) rates; at N > 1 the gather on its own, one strong pass and the bit check of the gathered block.
 """
 
 from __future__ import annotations
@@ -63,6 +65,12 @@ def parse():
                     help="N > 1: cut a FIXED total of --strong-pairs over the N ranks (north_star's 'strong scaling', literally) "
                          "instead of --pairs per rank (the default, 'weak')")
     ap.add_argument("--strong-pairs", type=int, default=8000, help="total frame pairs of --strong (BASELINE.json configs[4]: 8000)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run every other measurement and check of the line (roofline, sustained loop, CPU "
+                         "baseline and parity, other configs, host-fed rates; N > 1: gather alone, strong pass, bit check)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's results as DIR/<name>.npy (u, v, corr, s2n: float32, NaN / inf as 0; <name>_nonfinite: "
+                         "0 finite, 1 NaN, 2 +inf, 3 -inf; a fixed sample of pairs above 48 MiB)")
     return ap.parse_args()
 
 
@@ -171,6 +179,49 @@ def time_kernel_only(lib, launch, reps: int):
         _lib.set_option("time_kernel", 0)
     ms = [float(buf[i]) for i in range(n.value)]
     return (sum(ms) / len(ms) if ms else None), ms
+
+
+def kernel_timings(lib, launch_all, reps: int):
+    """Live kernel timing with HIP events on the launch stream (roofline leg, N-independent): (launch_ms, kernel_ms, kernel_ms_each,
+    kernel_ms_rescue_off).  Leaves the result block as a full launch (with the rescue pass) produces it."""
+    launch_ms = time_launches(lib, launch_all, reps)          # PIV kernel + the two rescue kernels: what a step issues
+    # the dominant kernel alone (what roofline.achieved and the rocprofv3 per-kernel average are about): the same launch with
+    # the rescue pass switched off -- the kernel still evaluates its flags, it just appends nothing and no rescue kernel follows
+    _lib.set_option("rescue", 0)
+    try:
+        kernel_ms_rescue_off = time_launches(lib, launch_all, reps)
+    finally:
+        _lib.set_option("rescue", 1)
+    # ... and the dominant kernel INSIDE the launch as issued (rescue on: it appends its records), by the library's events right
+    # around it: what rocprofv3 --kernel-trace reports for it, and what roofline.achieved is computed from (VERDICT r04: the
+    # rescue-off figure was ~3 % kinder than the profile the line cites)
+    kernel_ms, kernel_ms_each = time_kernel_only(lib, launch_all, reps)
+    if kernel_ms is None:
+        kernel_ms = launch_ms
+    launch_all()
+    return launch_ms, kernel_ms, kernel_ms_each, kernel_ms_rescue_off
+
+
+DUMP_BUDGET_BYTES = 48 << 20   # --dump-outputs stays under 64 MB in all
+
+
+def dump_outputs(out_dir: str, block: np.ndarray) -> None:
+    """--dump-outputs: the last timed step's (4, pairs, n_rows, n_cols) float32 result block as out_dir/{u,v,corr,s2n}.npy, each
+    (pairs, n_rows, n_cols).  Windows without a valid peak are NaN in the result (as in the reference), and a NaN never compares
+    equal, so a file holding one cannot be compared value for value with another build's: every array is written finite --
+    non-finite entries as 0 -- next to out_dir/<name>_nonfinite.npy, which codes each entry 0 finite, 1 NaN, 2 +inf, 3 -inf.
+    The pair decodes to the result exactly, and a change of the NaN mask shows as a change of the code file.  A block above DUMP_BUDGET_BYTES keeps a fixed, seeded sample of its pairs (in
+    order): the same pairs for every run with the same arguments, so that two builds can be compared output for output."""
+    os.makedirs(out_dir, exist_ok=True)
+    n_pairs = block.shape[1]
+    keep = max(1, DUMP_BUDGET_BYTES // (8 * block.shape[2] * block.shape[3] * 4))    # 4 arrays + 4 codes, float32
+    if n_pairs > keep:
+        block = block[:, np.sort(np.random.default_rng(0).choice(n_pairs, keep, replace=False))]
+    for k, name in enumerate(("u", "v", "corr", "s2n")):
+        a = np.ascontiguousarray(block[k], dtype=np.float32)
+        code = np.select([np.isnan(a), a == np.inf, a == -np.inf], [1, 2, 3], 0).astype(np.float32)
+        np.save(os.path.join(out_dir, name + ".npy"), np.where(code == 0, a, np.float32(0)))
+        np.save(os.path.join(out_dir, name + "_nonfinite.npy"), code)
 
 
 class SmiSampler:
@@ -592,6 +643,22 @@ def c_oracle_uv(sample, ws, ov, cores):
     return u, v
 
 
+def numpy_pocketfft_in_child(sample, ws, ov, check) -> dict:
+    """cpu_baseline.numpy_pocketfft, run in a fresh interpreter: it forks one worker per core, and workers forked from this process
+    would inherit its open GPU device."""
+    code = ("import json, sys; import numpy as np; sys.path.insert(0, sys.argv[1]); from oracle import cpu_baseline as cb; "
+            "d, ws, ov = sys.argv[2], *json.loads(sys.argv[3]); "
+            "r = cb.numpy_pocketfft(np.load(d + '/sample.npy'), ws, ov, check=(np.load(d + '/u.npy'), np.load(d + '/v.npy'))); "
+            "sys.stdout.write(json.dumps(r))")
+    with tempfile.TemporaryDirectory(prefix="lspiv_np_") as d:
+        for name, arr in (("sample", sample), ("u", check[0]), ("v", check[1])):
+            np.save(os.path.join(d, name + ".npy"), arr)
+        r = subprocess.run([sys.executable, "-c", code, ROOT, d, json.dumps([list(ws), list(ov)])], stdout=subprocess.PIPE, text=True)
+    if r.returncode != 0:
+        raise RuntimeError(f"numpy baseline process exited with {r.returncode}")
+    return json.loads(r.stdout)
+
+
 def rows_block(lib) -> list:
     """The HBM-bound rows around the path, each with its own roofline block: tools/rows_launch.py."""
     import importlib.util
@@ -803,39 +870,32 @@ def main():
         dt = float(comm.allreduce(np.array([dt], dtype=np.float64), 1)[0])   # MAX over ranks
     step_marks = plan.timings() if plan is not None else None
 
-    # ---- live kernel timing with HIP events on the launch stream (roofline leg, N-independent) --
-    reps = max(3, min(a.steps, 10))
-    launch_ms = time_launches(lib, launch_all, reps)          # PIV kernel + the two rescue kernels: what a step issues
-    # the dominant kernel alone (what roofline.achieved and the rocprofv3 per-kernel average are about): the same launch with
-    # the rescue pass switched off -- the kernel still evaluates its flags, it just appends nothing and no rescue kernel follows
-    _lib.set_option("rescue", 0)
-    try:
-        kernel_ms_rescue_off = time_launches(lib, launch_all, reps)
-    finally:
-        _lib.set_option("rescue", 1)
-    # ... and the dominant kernel INSIDE the launch as issued (rescue on: it appends its records), by the library's events right
-    # around it: what rocprofv3 --kernel-trace reports for it, and what roofline.achieved is computed from (the
-    # rescue-off figure was ~3 % kinder than the profile the line cites)
-    kernel_ms, kernel_ms_each = time_kernel_only(lib, launch_all, reps)
-    if kernel_ms is None:
-        kernel_ms = launch_ms
-    launch_all()                                              # leave d_out as a full launch (with the rescue pass) produces it
-    sustained = None
-    if world == 1 and a.sustained_s > 0:
-        sustained = sustained_run(lib, step, sync, total_pairs, a.sustained_s)
-        launch_all()
+    if a.dump_outputs and rank == 0:
+        if plan is None:
+            block = np.empty((4, my_pairs, n_rows, n_cols), dtype=np.float32)
+            _lib.check(lib.lspiv_memcpy_d2h(_lib.ptr(block), d_out, block.nbytes))
+        else:
+            block = plan.gathered_host()                      # what the sharded path hands its caller: every rank's pairs
+        dump_outputs(a.dump_outputs, block)
+        del block
+
+    launch_ms = kernel_ms = None
+    sustained = rescue = gather_ms = strong = dist_check = None
+    if a.full:
+        launch_ms, kernel_ms, kernel_ms_each, kernel_ms_rescue_off = kernel_timings(lib, launch_all, max(3, min(a.steps, 10)))
+        if world == 1 and a.sustained_s > 0:
+            sustained = sustained_run(lib, step, sync, total_pairs, a.sustained_s)
+            launch_all()
 
     # float64 rescue pass: how many windows of one launch the kernels flagged (the launches above ran on the library's stream)
-    rescue = None
-    if hasattr(lib, "lspiv_rescue_stats"):
+    if a.full and hasattr(lib, "lspiv_rescue_stats"):
         st = (C.c_int64 * 5)()
         _lib.check(lib.lspiv_rescue_stats(None, st))
         rescue = {"enabled": bool(_lib.get_option("rescue")), "fit_windows_per_launch": int(st[0]), "amb_windows_per_launch": int(st[1]),
                   "share_of_windows": round((st[0] + st[1]) / max(n_tiles, 1), 6),
                   "note": "windows whose float32 peak fit the kernel flags as ill-conditioned are re-evaluated from the frames in "
                           "float64 (csrc/piv_rescue.hip); the two rescue kernels run inside the timed region and inside kernel_ms"}
-    gather_ms = None
-    if plan is not None and plan.k > 0:
+    if a.full and plan is not None and plan.k > 0:
         # one all-gather of a result block on its own, by events on the gather stream (outside the timed region)
         e0, e1 = C.c_void_p(), C.c_void_p()
         _lib.check(lib.lspiv_event_create(C.byref(e0)))
@@ -852,8 +912,7 @@ def main():
         _lib.check(lib.lspiv_event_destroy(e1))
 
     # ---- one STRONG pass next to the weak one (north_star says "strong scaling"; the driver runs the default) ----
-    strong = None
-    if plan is not None and not a.strong and a.strong_pairs > 0:
+    if a.full and plan is not None and not a.strong and a.strong_pairs > 0:
         from pyorc_amd import shard
 
         plan_s = shard.ShardedPivDev(comm, a.strong_pairs, (H, W), ws, ov, align=None)
@@ -880,8 +939,7 @@ def main():
         plan_s.close()
         del block_s
 
-    dist_check = None
-    if plan is not None and plan.k > 0:
+    if a.full and plan is not None and plan.k > 0:
         # this rank's slice of the all-gathered block must equal its own single-launch result bit for bit; cheap, outside the
         # timed region (launch_all above wrote the same pairs, at the same absolute pair index, into d_out)
         plan.step(frames)
@@ -931,12 +989,13 @@ def main():
                                     "(north_star's >= 6.5x at 8 GPUs = 8000 pairs on 8 GPUs vs 1000 pairs on 1); `--strong` cuts a "
                                     "fixed 8000-pair total over the ranks instead"),
         },
-        "roofline": roofline_block(lib, kernel_ms, a.pairs, H, W, a.window, a.overlap, n_win, launch_ms),
     }
-    out["roofline"]["kernel_timing"] = ("mean of HIP-event pairs recorded by the library right around the dominant kernel in " + str(len(kernel_ms_each)) +
-                                        " launches issued as a caller issues them (rescue pass on), on the launch stream -- the per-kernel "
-                                        "duration of `rocprofv3 --kernel-trace`; profiles/*_summary.json hold the trace's own mean")
-    out["roofline"]["kernel_ms_same_launch_rescue_off"] = round(kernel_ms_rescue_off, 4)
+    if a.full:
+        out["roofline"] = roofline_block(lib, kernel_ms, a.pairs, H, W, a.window, a.overlap, n_win, launch_ms)
+        out["roofline"]["kernel_timing"] = ("mean of HIP-event pairs recorded by the library right around the dominant kernel in " + str(len(kernel_ms_each)) +
+                                            " launches issued as a caller issues them (rescue pass on), on the launch stream -- the per-kernel "
+                                            "duration of `rocprofv3 --kernel-trace`; profiles/*_summary.json hold the trace's own mean")
+        out["roofline"]["kernel_ms_same_launch_rescue_off"] = round(kernel_ms_rescue_off, 4)
     if sustained is not None:
         # value / ms_per_step time a burst of --steps launches (0.12 s); this is the same step loop held for >= 10 s
         out["sustained_pairs_per_s"] = sustained["pairs_per_s"]
@@ -956,19 +1015,17 @@ def main():
                                                   "(results cross the host) -- a diagnosis, not the xGMI figure"} if rccl_error else {}),
             "path": "pyorc_amd.shard.ShardedPivDev (the library's device-resident sharded path; bench.py only times it)",
             "mode": "strong" if a.strong else "weak", "pairs_total": total_pairs, "pairs_rank0": my_pairs,
-            "allgather_matches_single_launch": dist_check,
             "allgather_bytes_per_rank_per_step": 4 * plan.p_max * n_win * 4,
             "allgather_bytes_received_per_rank_per_step": (world - 1) * 4 * plan.p_max * n_win * 4,
             "survey_8e_bytes_per_rank": "SURVEY.md section 8e: 1000 pairs x 7854 vectors x 16 B = 125.7 MB per rank and step at the C5 shape",
-            "allgather_ms_alone": gather_ms,
             # rank 0, by HIP events per timed step: this rank's kernels (PIV + rescue) while the previous step's gather is in
             # flight on the other stream, that gather itself, and what of the step is not covered by the kernels
             "kernel_ms_while_gather_in_flight": mean(km), "gather_ms_overlapped": mean(gm),
             "gather_end_after_kernel_end_ms": mean(lag),
             "exposed_comm_ms": round(dt / a.steps * 1e3 - float(np.mean(km)), 4) if len(km) else None,
-            "kernel_ms_alone": round(launch_ms, 4),
             "gather_stream_priority": "high" if plan.gather_priority > 0 else ("low" if plan.gather_priority < 0 else "default"),
-            **(strong or {}),
+            **({"allgather_matches_single_launch": dist_check, "allgather_ms_alone": gather_ms, "kernel_ms_alone": round(launch_ms, 4),
+                **(strong or {})} if a.full else {}),
             # NCCL_MAX_NCHANNELS: what was in force when the RCCL communicator was created (pyorc_amd.comm sets its default only
             # around ncclCommInitRank and restores the environment afterwards)
             "rccl_env": {**{k: os.environ.get(k) for k in ("NCCL_MIN_NCHANNELS", "LSPIV_RCCL_MAX_NCHANNELS", "NCCL_ALGO", "NCCL_PROTO")
@@ -976,7 +1033,7 @@ def main():
                          **({"NCCL_MAX_NCHANNELS": _comm_mod._rccl_channel_cap.applied} if _comm_mod._rccl_channel_cap.applied else {})},
             **({"same_device_plumbing_test": True} if same_device else {})}
     # ---- CPU baseline on a bounded sample of the same stack (rank 0, N = 1 only) --------------
-    if world == 1 and a.cpu_pairs != 0:
+    if a.full and world == 1 and a.cpu_pairs != 0:
         from oracle import cpu_baseline as cb   # test infrastructure: baseline / parity leg only
 
         n_s = cb.default_sample_pairs(H, W, ws) if a.cpu_pairs < 0 else a.cpu_pairs
@@ -1001,14 +1058,14 @@ def main():
             # the numpy / pocketfft reading of the same sample beside the C port (one process per core)
             try:
                 ref_uv = c_oracle_uv(sample, ws, ov, base["cores"])
-                base["numpy_pocketfft"] = cb.numpy_pocketfft(sample, ws, ov, check=ref_uv)
+                base["numpy_pocketfft"] = numpy_pocketfft_in_child(sample, ws, ov, ref_uv)
             except Exception as exc:   # a baseline leg must not take the line down
                 base["numpy_pocketfft"] = {"error": f"{type(exc).__name__}: {exc}"}
         out["cpu_baseline"] = base
         if base.get("value"):
             out["config"]["speedup_vs_cpu_baseline"] = round(pairs_per_s / base["value"], 1)
     # ---- the other single-GPU BASELINE configs + host-fed rates (N = 1, default shape only) ----
-    if world == 1 and is_c2 and not a.no_extras:
+    if a.full and world == 1 and is_c2 and not a.no_extras:
         others = [other_config(lib, "BASELINE.json configs[2]: 1080p, 64x64 windows @ 75 % overlap, same stack",
                                d_frames, a.pairs, H, W, 64, 48, parity_pairs=a.parity_pairs if a.cpu_pairs != 0 else 0)]
         ensembles = [ensemble_config(lib, "ensemble correlation (ensemble_corr=True), 1080p, 32x32 @ 50 %, same stack", d_frames, a.pairs, H, W, 32, 16),

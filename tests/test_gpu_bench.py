@@ -5,6 +5,7 @@ import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -21,9 +22,34 @@ def run_bench(args, env_extra=None):
     return json.loads(lines[0])
 
 
+def one_launch(lib, seed, pairs, pair_offset=0, H=256, W=384):
+    """(4, pairs, n_rows, n_cols): ONE launch over bench.py's synthetic stack of `seed` (its --seed + rank), as a rank issues it."""
+    from pyorc_amd import DeviceFrames, _lib, window
+
+    n_rows, n_cols = window.get_array_shape((H, W), (32, 32), (16, 16))
+    frames = DeviceFrames.empty((pairs + 1, H, W), np.uint8)
+    _lib.check(lib.lspiv_synth_particles_dev(frames.c_ptr, pairs + 1, H, W, seed, 0.02))
+    _lib.check(lib.lspiv_synchronize())
+    out = DeviceFrames.empty((4 * pairs, n_rows, n_cols), np.float32)
+    _lib.check(lib.lspiv_piv_pairs_dev_at(frames.c_ptr, 0, pairs + 1, H, W, 32, 32, 16, 16, -1.0, pair_offset, out.c_ptr, None, None))
+    _lib.check(lib.lspiv_synchronize())
+    return out.to_host().reshape(4, pairs, n_rows, n_cols)
+
+
+def load_dump(d):
+    """The four arrays of a --dump-outputs directory, decoded: finite values + their <name>_nonfinite codes."""
+    out = []
+    for name in ("u", "v", "corr", "s2n"):
+        val, code = np.load(os.path.join(d, f"{name}.npy")), np.load(os.path.join(d, f"{name}_nonfinite.npy"))
+        assert val.dtype == code.dtype == np.float32 and val.shape == code.shape, name
+        assert np.isfinite(val).all() and np.isin(code, (0, 1, 2, 3)).all() and np.all(val[code != 0] == 0), name
+        out.append(np.select([code == 1, code == 2, code == 3], [np.nan, np.inf, -np.inf], val))
+    return np.stack(out)
+
+
 @pytest.mark.gpu
 def test_bench_json_contract_single_gpu(gpu):
-    d = run_bench(SMALL + ["--cpu-pairs", "4"])
+    d = run_bench(SMALL + ["--cpu-pairs", "4", "--full"])
     for key in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling", "vs_baseline",
                 "dtype", "data", "config", "roofline", "cpu_baseline"):
         assert key in d, key
@@ -42,11 +68,34 @@ def test_bench_json_contract_single_gpu(gpu):
 
 
 @pytest.mark.gpu
-def test_bench_launches_its_own_ranks_and_gathers_over_the_native_comm(gpu):
+def test_bench_plain_run_times_the_steps_and_dumps_the_last_one(gpu, tmp_path):
+    """A run without --full: the headline keys and nothing measured after the timed steps; --dump-outputs writes the last step's
+    u, v, corr, s2n (float32, one plane per pair) as finite arrays plus their non-finite codes, the same bits from run to run, and
+    decoded they are what one launch over the same stack returns."""
+    args = ["--pairs", "60", "--height", "256", "--width", "384", "--steps", "3", "--warmup", "1", "--dump-outputs"]
+    d = run_bench(args + [str(tmp_path / "a")])
+    for key in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+        assert key in d, key
+    assert d["steps"] == 3 and d["warmup"] == 1 and d["unit"] == "frame-pairs/s" and d["dtype"] == "f32"
+    # ms_per_step is rounded to 1e-4 ms: allow for that rounding
+    assert abs(d["value"] - 60 / (d["ms_per_step"] * 1e-3)) / d["value"] < 1e-4 / d["ms_per_step"] + 1e-4
+    assert not {"roofline", "cpu_baseline", "sustained_pairs_per_s"} & set(d) and "other_configs" not in d["config"]
+    run_bench(args + [str(tmp_path / "b")])
+    a, b = load_dump(tmp_path / "a"), load_dump(tmp_path / "b")
+    ref = one_launch(gpu, 20260927 + 2, 60)
+    assert a.shape == ref.shape and np.array_equal(a, b, equal_nan=True) and np.array_equal(a, ref, equal_nan=True)
+
+
+@pytest.mark.gpu
+def test_bench_launches_its_own_ranks_and_gathers_over_the_native_comm(gpu, tmp_path):
     """`python bench.py --gpus 2` starts two ranks itself; on a 1-GPU box they share the device over the shared-memory
     transport (LSPIV_BENCH_SAME_DEVICE): sharding, pipelined all-gather, max-over-ranks timing and the bit check."""
-    d = run_bench(SMALL + ["--gpus", "2", "--strong-pairs", "300"], {"LSPIV_BENCH_SAME_DEVICE": "1"})
+    d = run_bench(SMALL + ["--gpus", "2", "--strong-pairs", "300", "--full", "--dump-outputs", str(tmp_path)], {"LSPIV_BENCH_SAME_DEVICE": "1"})
     assert d["n_gpus"] == 2 and d["scaling"] == "weak" and "cpu_baseline" not in d
+    # rank 0 dumps the gathered block its caller receives: every rank's 60 pairs (rank r: stack seed --seed + r, pairs 60 r ...)
+    ref = np.concatenate([one_launch(gpu, 20260927 + 2 + r, 60, pair_offset=60 * r) for r in range(2)], axis=1)
+    got = load_dump(tmp_path)
+    assert got.shape == ref.shape and np.array_equal(got, ref, equal_nan=True)
     comm = d["config"]["comm"]
     assert comm["transport"] == "shm" and comm["ranks_reported_by_transport"] == 2
     assert comm["allgather_matches_single_launch"] is True and comm["same_device_plumbing_test"] is True
@@ -68,10 +117,18 @@ def test_bench_launches_its_own_ranks_and_gathers_over_the_native_comm(gpu):
 @pytest.mark.gpu
 @pytest.mark.parametrize("n", [4, 8])
 def test_bench_at_the_rank_counts_of_the_scaling_run(gpu, n):
-    """The driver's N = 4 and 8, as far as one GPU goes: n self-launched ranks share device 0 over the shared-memory transport --
-    block sizes, the gathered (n, 4, pairs, windows) result against ONE launch, the max-over-ranks clock and the weak-scaling value."""
-    d = run_bench(["--pairs", "25", "--height", "256", "--width", "384", "--steps", "2", "--warmup", "1", "--gpus", str(n)],
-                  {"LSPIV_BENCH_SAME_DEVICE": "1"})
+    """The driver's N = 4 and 8: n self-launched ranks -- block sizes, the gathered (n, 4, pairs, windows) result against ONE launch,
+    the max-over-ranks clock and the weak-scaling value.  4 ranks share device 0 over the shared-memory transport (5 processes with
+    the device open, this one included); 8 ranks get one device each: on one device they would be 9 processes holding it at once,
+    more than a shared GPU node lets one job open.  The 8-rank sharding of pyorc_amd.shard over the native shared-memory
+    communicator runs on CPU ranks in tests/test_shard_gloo.py (world 8)."""
+    from pyorc_amd import _lib
+
+    found = _lib.device_count()
+    if n > 4 and found < n:
+        pytest.skip(f"needs {n} GPUs (one rank per device), found {found}")
+    d = run_bench(["--pairs", "25", "--height", "256", "--width", "384", "--steps", "2", "--warmup", "1", "--gpus", str(n), "--full"],
+                  {"LSPIV_BENCH_SAME_DEVICE": "1"} if n <= 4 else {})
     comm = d["config"]["comm"]
     assert d["n_gpus"] == n and d["scaling"] == "weak" and comm["ranks_reported_by_transport"] == n
     assert comm["pairs_total"] == 25 * n and comm["pairs_rank0"] == 25 and comm["allgather_matches_single_launch"] is True
@@ -82,7 +139,7 @@ def test_bench_at_the_rank_counts_of_the_scaling_run(gpu, n):
 @pytest.mark.gpu
 def test_bench_strong_mode_cuts_a_fixed_total(gpu):
     """`--strong`: a fixed total (here 150 pairs) cut over the ranks on the walking kernels' anchors (75 + 75), value = total / time."""
-    d = run_bench(SMALL + ["--gpus", "2", "--strong", "--strong-pairs", "150"], {"LSPIV_BENCH_SAME_DEVICE": "1"})
+    d = run_bench(SMALL + ["--gpus", "2", "--strong", "--strong-pairs", "150", "--full"], {"LSPIV_BENCH_SAME_DEVICE": "1"})
     comm = d["config"]["comm"]
     assert d["scaling"] == "strong" and comm["mode"] == "strong" and comm["pairs_total"] == 150 and comm["pairs_rank0"] == 75
     assert comm["allgather_matches_single_launch"] is True
@@ -93,7 +150,7 @@ def test_bench_strong_mode_cuts_a_fixed_total(gpu):
 def test_bench_over_rccl_with_one_rank(gpu):
     """The RCCL transport itself (librccl.so dlopen'ed by the C library, ncclCommInitRank, ncclAllGather on a second
     stream, all-reduce for the timing), with the one rank a 1-GPU box allows."""
-    d = run_bench(SMALL + ["--gpus", "1", "--cpu-pairs", "0", "--no-extras"], {"LSPIV_BENCH_FORCE_COMM": "1"})
+    d = run_bench(SMALL + ["--gpus", "1", "--cpu-pairs", "0", "--no-extras", "--full"], {"LSPIV_BENCH_FORCE_COMM": "1"})
     comm = d["config"]["comm"]
     assert comm["transport"] == "rccl" and comm["ranks_reported_by_transport"] == 1
     assert comm["allgather_matches_single_launch"] is True
@@ -105,7 +162,7 @@ def test_bench_falls_back_to_shared_memory_when_rccl_cannot_be_brought_up(gpu):
     """Round 6: RCCL has never met two ranks on the boxes this was built on.  A node on which it cannot be brought up must still yield a
     line that says so: the ranks vote on their communicator and, unless all of them succeeded, all of them fall back to the shared-memory
     transport and the line carries the error.  Provoked here with two ranks on ONE device, which RCCL refuses ("Duplicate GPU")."""
-    d = run_bench(SMALL + ["--gpus", "2", "--strong-pairs", "300"], {"LSPIV_BENCH_SAME_DEVICE": "1", "LSPIV_COMM": "rccl"})
+    d = run_bench(SMALL + ["--gpus", "2", "--strong-pairs", "300", "--full"], {"LSPIV_BENCH_SAME_DEVICE": "1", "LSPIV_COMM": "rccl"})
     comm = d["config"]["comm"]
     assert d["n_gpus"] == 2 and comm["transport"] == "shm" and comm["ranks_reported_by_transport"] == 2
     assert "rccl_error" in comm and "rank" in comm["rccl_error"] and "diagnosis" in comm["note"]

@@ -26,10 +26,10 @@ for f in sorted(glob.glob(f'profiles/{sys.argv[1]}_*_summary.json')):
         if 'walk' not in k: continue
         print(f.split('/')[-1], k[12:70], {kk: (round(vv, 3) if isinstance(vv, float) else vv) for kk, vv in v.items() if kk in ('hbm_traffic_bytes', 'hbm_fetch_bytes', 'hbm_write_bytes', 'valu_inst_per_simd_per_4cyc')}, v.get('trace'))
 PY
-timeout 600 python bench.py --gpus 1 --steps 20 --warmup 5 2> gpurun_out/${TAG}_out/bench.err > gpurun_out/${TAG}_out/bench.json
+mkdir -p build && timeout 600 python bench.py --gpus 1 --steps 20 --warmup 5 --full > build/${TAG}_bench.json 2> build/${TAG}_bench.err
 python - "$TAG" <<'PY'
 import json, sys
-d = json.load(open(f'gpurun_out/{sys.argv[1]}_out/bench.json')); c = d.get('cpu_baseline', {})
+d = json.load(open(f'build/{sys.argv[1]}_bench.json')); c = d.get('cpu_baseline', {})
 print('bench', d['value'], d['ms_per_step'], d['roofline']['kernel_ms_per_launch'], d['roofline'].get('traffic'), d['roofline']['frac'], d['config']['binary']['binary_hash_matches'])
 print(c.get('value'), c.get('cores'), {k: v for k, v in c.items() if k.startswith('parity') and not isinstance(v, dict)})
 print('ensemble parity', c.get('ensemble_parity'))

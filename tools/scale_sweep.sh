@@ -7,7 +7,7 @@ N=${1:-8}; STEPS=${2:-20}
 R=$(cd "$(dirname "$0")/.." && pwd)
 for ch in 8 16 32; do
   for prio in 0 1; do
-    line=$(LSPIV_RCCL_MAX_NCHANNELS=$ch LSPIV_GATHER_STREAM_PRIORITY=$prio python "$R/bench.py" --gpus "$N" --steps "$STEPS" --warmup 5 --no-extras --cpu-pairs 0 --sustained-s 0 2>/dev/null | tail -1)
+    line=$(LSPIV_RCCL_MAX_NCHANNELS=$ch LSPIV_GATHER_STREAM_PRIORITY=$prio python "$R/bench.py" --gpus "$N" --steps "$STEPS" --warmup 5 --full --no-extras --cpu-pairs 0 --sustained-s 0 2>/dev/null | tail -1)
     echo "{\"nchannels\": $ch, \"gather_priority\": \"$([ $prio = 1 ] && echo high || echo default)\", \"line\": $line}"
   done
 done

@@ -9,11 +9,11 @@ cd $R
 case $NAME in
   tests)        # the GPU suite as the driver runs it, then the default bench line
     timeout 1500 python -m pytest tests -m gpu -x -q > $OUT/pytest.log 2>&1; echo "pytest rc $?" >> $OUT/pytest.log; tail -5 $OUT/pytest.log
-    timeout 900 python bench.py --gpus 1 --steps 20 --warmup 5 > $OUT/bench.json 2> $OUT/bench.err; echo "bench rc $?"; head -c 600 $OUT/bench.json;;
+    timeout 900 python bench.py --gpus 1 --steps 20 --warmup 5 --full > $OUT/bench.json 2> $OUT/bench.err; echo "bench rc $?"; head -c 600 $OUT/bench.json;;
   new-tests)    # only this round's GPU tests (fast iteration)
     timeout 900 python -m pytest tests/test_gpu_round6.py tests/test_gpu_round5.py -m gpu -x -q 2>&1 | tail -30 | tee $OUT/pytest.log;;
   bench)
-    timeout 900 python bench.py --gpus 1 --steps 20 --warmup 5 > $OUT/bench.json 2> $OUT/bench.err; echo "bench rc $?"; tail -3 $OUT/bench.err; head -c 400 $OUT/bench.json;;
+    timeout 900 python bench.py --gpus 1 --steps 20 --warmup 5 --full > $OUT/bench.json 2> $OUT/bench.err; echo "bench rc $?"; tail -3 $OUT/bench.err; head -c 400 $OUT/bench.json;;
   rows)         # the HBM-bound rows: timings, then rocprofv3 passes per row (tools/profile.sh with another kernel filter)
     for row in project project_nn project_u8 project_f32 project_cv project_cv_f32 time_diff normalize smooth edge_detect edge_detect_6_10 smooth_f32 edge_detect_f32; do
       python tools/rows_launch.py $row 30 201 | tee -a $OUT/rows.log
