@@ -1,0 +1,507 @@
+// C ABI of liblspiv_hip.so, ensemble correlation (api_core.hip has the overview): the summed correlation planes of a video, their
+// fit, and the float64 rescue of that fit in stages (piv_rescue.hip, ens_*).
+#include "api_internal.h"
+
+#include <algorithm>
+#include <cstdlib>
+#include <cstring>
+
+using namespace lspiv_api;
+
+struct lspiv_ensemble {
+  int64_t H, W;
+  int wy, wx, oy, ox;
+  Grid g;
+  int device;
+  float* d_sum;    // n_win * wy * wx
+  float* d_count;  // n_win
+  float* d_part;   // walking kernels: per-segment partial sums + counts (grow-only workspace)
+  size_t part_cap;
+  int64_t pairs_done;   // pairs accumulated so far = absolute index of the next chunk's first pair (segment anchoring)
+  // float64 rescue of the final fit (piv_rescue.hip, ens_*): the chunks' frames and masked corr_max stay reachable until
+  // lspiv_ensemble_finish -- owned copies (host entry point: the upload buffer itself; "_dev": a device copy, LSPIV_RETAIN_COPY)
+  // or the caller's pointer (LSPIV_RETAIN_BORROW)
+  struct Kept { void* d_frames; bool owned; int dtype; int64_t T; float* d_cmax; };
+  std::vector<Kept> kept;
+  int retain_mode;          // "_dev" entry point: LSPIV_RETAIN_*; the host entry point always keeps its upload buffers
+  size_t kept_bytes;        // HBM held BECAUSE of this handle: owned frame copies, the corr_max records, and the borrowed chunks too
+                            // (they are the caller's allocations, but it keeps them alive for the handle): all against the budget
+  // the chunks' masked corr_max records live in a few large blocks (geometric growth) instead of one hipMalloc per accumulate
+  struct CmaxBlock { char* base; size_t cap, used; };
+  std::vector<CmaxBlock> cmax_blocks;
+  // accumulate_dev may run on caller streams while flag / partials / finish run on the context's stream: one event per stream
+  // that accumulated, recorded after each accumulate, waited for by every reader of the sums and of the kept records
+  struct AccEvent { hipStream_t stream; hipEvent_t ev; };
+  std::vector<AccEvent> acc_events;
+  bool retain_complete;     // false: some chunk could not be kept (budget, mode NONE, imported state) -> float32 fits stay
+  void* d_rescue; size_t rescue_cap;     // EnsRescueHdr (256 B) + records
+  double* d_partial; size_t partial_cap;
+  double* d_totals; size_t totals_cap;   // (n_rec, kEnsMaxCand * 5): the partial sums merged over this handle's pair-blocks
+  int64_t last_flagged, last_rescued, last_skipped;
+  bool foreign;             // the sums were replaced by lspiv_ensemble_import: they hold other handles' pairs as well
+  uint32_t n_rec;           // records of the last lspiv_ensemble_flag (sorted by window), 0 if none
+  uint64_t rec_digest;      // FNV-1a over (w, ncand, pos[0 .. ncand-1]) of those records: what ranks compare before they sum partials
+  float flag_min_count;     // count_min * n_frames of that call
+};
+
+// HBM the retained chunks of one ensemble may occupy: LSPIV_ENSEMBLE_RETAIN_BYTES, default a quarter of the device
+static size_t ensemble_retain_budget() {
+  if (const char* e = getenv("LSPIV_ENSEMBLE_RETAIN_BYTES")) return (size_t)atoll(e);
+  size_t f = 0, t = 0;
+  if (hipMemGetInfo(&f, &t) != hipSuccess) { (void)hipGetLastError(); return (size_t)16 << 30; }
+  return t / 4;
+}
+static void ensemble_drop_kept(lspiv_ensemble* h) {
+  for (auto& k : h->kept)
+    if (k.owned && k.d_frames) (void)hipFree(k.d_frames);
+  for (auto& b : h->cmax_blocks) (void)hipFree(b.base);
+  h->kept.clear();
+  h->cmax_blocks.clear();
+  h->kept_bytes = 0;
+}
+// n bytes (256-byte granules) from the handle's record blocks; a new block is twice the last one (>= 1 MiB, >= n, <= 1 GiB unless n
+// is larger): a handle that takes hundreds of chunks calls hipMalloc a dozen times, not hundreds
+static void* ensemble_cmax_alloc(lspiv_ensemble* h, size_t n) {
+  n = (n + 255) & ~(size_t)255;
+  if (!h->cmax_blocks.empty()) {
+    auto& b = h->cmax_blocks.back();
+    if (b.used + n <= b.cap) { void* p = b.base + b.used; b.used += n; return p; }
+  }
+  const size_t last = h->cmax_blocks.empty() ? 0 : h->cmax_blocks.back().cap;
+  const size_t cap = std::max(n, std::min<size_t>(std::max<size_t>(2 * last, (size_t)1 << 20), (size_t)1 << 30));
+  void* base = nullptr;
+  if (hipMalloc(&base, cap) != hipSuccess) { (void)hipGetLastError(); return nullptr; }
+  h->cmax_blocks.push_back({(char*)base, cap, n});
+  h->kept_bytes += cap;
+  return base;
+}
+// the handle stops being rescuable: what it kept is of no use any more (the float32 fits stay, lspiv_ensemble_stats says so)
+static void ensemble_give_up_retention(lspiv_ensemble* h) {
+  h->retain_complete = false;
+  ensemble_drop_kept(h);
+}
+// keep the masked corr_max of a chunk (the kernels' keep decisions) next to its frames (`frame_bytes` of them: counted against
+// the budget whether the handle owns them or borrows them); on any failure -- budget, allocation, copy -- the ensemble simply stops
+// being rescuable, the accumulation itself is not affected.  Takes ownership of an `owned` buffer either way.
+static void ensemble_keep(lspiv_ensemble* h, void* d_frames, bool owned, size_t frame_bytes, int dtype, int64_t T, const float* d_cmax,
+                          hipStream_t s) {
+  const size_t n_tiles = (size_t)(T - 1) * h->g.n_rows * h->g.n_cols;
+  void* cm = nullptr;
+  if (h->kept_bytes + frame_bytes + n_tiles * sizeof(float) > ensemble_retain_budget() ||
+      !(cm = ensemble_cmax_alloc(h, n_tiles * sizeof(float))) ||
+      hipMemcpyAsync(cm, d_cmax, n_tiles * sizeof(float), hipMemcpyDeviceToDevice, s) != hipSuccess) {
+    (void)hipGetLastError();
+    if (owned) (void)hipFree(d_frames);
+    ensemble_give_up_retention(h);
+    return;
+  }
+  h->kept.push_back({d_frames, owned, dtype, T, (float*)cm});
+  h->kept_bytes += frame_bytes;
+}
+// accumulate_dev ran on stream `s`: note where that stream stands; readers on another stream wait for it
+static void ensemble_mark_accumulated(lspiv_ensemble* h, hipStream_t s) {
+  lspiv_ensemble::AccEvent* a = nullptr;
+  for (auto& e : h->acc_events) if (e.stream == s) a = &e;
+  if (!a) {
+    hipEvent_t ev = nullptr;
+    if (hipEventCreateWithFlags(&ev, hipEventDisableTiming) != hipSuccess) { (void)hipGetLastError(); (void)hipStreamSynchronize(s); return; }
+    h->acc_events.push_back({s, ev});
+    a = &h->acc_events.back();
+  }
+  if (hipEventRecord(a->ev, s) != hipSuccess) { (void)hipGetLastError(); (void)hipStreamSynchronize(s); }
+}
+static void ensemble_wait_accumulated(lspiv_ensemble* h, hipStream_t reader) {
+  for (auto& e : h->acc_events)
+    if (e.stream != reader && hipStreamWaitEvent(reader, e.ev, 0) != hipSuccess) { (void)hipGetLastError(); (void)hipStreamSynchronize(e.stream); }
+}
+
+extern "C" {
+
+// ---- ensemble -------------------------------------------------------------------------------
+int lspiv_ensemble_begin(int64_t H, int64_t W, int wy, int wx, int oy, int ox, lspiv_ensemble** handle) {
+  if (!handle) return fail(LSPIV_EINVAL, "handle is NULL");
+  Grid g;
+  LSPIV_TRY(make_grid(H, W, wy, wx, oy, ox, &g));
+  DeviceCtx* c;
+  LSPIV_TRY(get_ctx(&c));
+  lspiv_ensemble* h = new lspiv_ensemble();
+  h->H = H; h->W = W; h->wy = wy; h->wx = wx; h->oy = oy; h->ox = ox; h->g = g;
+  h->retain_mode = LSPIV_RETAIN_NONE; h->retain_complete = true;   // (the rest value-initialised: zeros, nullptr)
+  HIP_TRY(hipGetDevice(&h->device));
+  const size_t n_win = (size_t)g.n_rows * g.n_cols;
+  void* p = nullptr;
+  hipError_t e = hipMalloc(&p, n_win * wy * wx * sizeof(float));
+  if (e != hipSuccess) { delete h; return fail(LSPIV_ENOMEM, "hipMalloc corr_sum: %s", hipGetErrorString(e)); }
+  h->d_sum = (float*)p;
+  e = hipMalloc(&p, n_win * sizeof(float));
+  if (e != hipSuccess) { hipFree(h->d_sum); delete h; return fail(LSPIV_ENOMEM, "hipMalloc corr_count: %s", hipGetErrorString(e)); }
+  h->d_count = (float*)p;
+  HIP_TRY(hipMemsetAsync(h->d_sum, 0, n_win * wy * wx * sizeof(float), c->stream));
+  HIP_TRY(hipMemsetAsync(h->d_count, 0, n_win * sizeof(float), c->stream));
+  HIP_TRY(hipStreamSynchronize(c->stream));  // lspiv_ensemble_accumulate_dev may be given another stream
+  *handle = h;
+  return LSPIV_OK;
+}
+
+static int ensemble_launch(lspiv_ensemble* h, DeviceCtx* c, const void* d_frames, int dtype, int64_t T, float corr_min,
+                           float s2n_min, float signal_threshold, float* d_cmax, float* d_s2n, hipStream_t s) {
+  lspiv::PivParams p;
+  LSPIV_TRY(fill_params(&p, d_frames, dtype, T, h->H, h->W, h->wy, h->wx, h->oy, h->ox, signal_threshold, h->g));
+  p.cmax = d_cmax;
+  p.s2n = d_s2n;
+  p.corr_min = corr_min;
+  p.s2n_min = s2n_min;
+  p.corr_sum = h->d_sum;
+  p.corr_count = h->d_count;
+  const int kind = lspiv_kernel_kind(h->wy, h->wx);
+  const int walk = lspiv::walk_setting();
+  p.pair_offset = h->pairs_done;   // advanced only once the launch has been issued (a failed accumulate changes nothing)
+  if (kind_walks(kind) && walk != 0) {
+    // segments anchored at multiples of the anchor length of the absolute pair index (common.h): the partial sums, and
+    // the order they are merged in, are the same for every chunking whose boundaries are multiples of that length
+    const lspiv::WalkSegments w = lspiv::walk_segments(p.n_pairs, p.pair_offset, walk > 1 ? (uint32_t)walk : lspiv::walk_anchor(h->wy, p.n_win));
+    p.seg_len = w.seg_len; p.seg_first = w.seg_first; p.n_seg = w.n_seg;
+    const size_t plane = (size_t)h->wy * h->wx;
+    const size_t need = (size_t)p.n_seg * p.n_win * (plane + 1) * sizeof(float);
+    LSPIV_TRY(ensure(&h->d_part, &h->part_cap, need));
+    // not zeroed: every (segment, window) job writes its whole slot and its count (first iteration stores, later ones add)
+    p.part_sum = h->d_part;
+    p.part_cnt = h->d_part + (size_t)p.n_seg * p.n_win * plane;
+  }
+  LSPIV_TRY(apply_signal_mode(c, &p, dtype, s));
+  LSPIV_TRY(dispatch(p, dtype, true, s));
+  h->pairs_done += p.n_pairs;
+  return LSPIV_OK;
+}
+
+int lspiv_ensemble_accumulate_dev(lspiv_ensemble* h, const void* d_frames, int dtype, int64_t T, float corr_min,
+                                  float s2n_min, float signal_threshold, float* d_corr_s2n, void* stream) {
+  if (!h || !d_frames || !d_corr_s2n) return fail(LSPIV_EINVAL, "NULL argument");
+  if (T < 2) return fail(LSPIV_ESHAPE, "need at least 2 frames, got %lld", (long long)T);
+  DeviceCtx* c;
+  LSPIV_TRY(get_ctx(&c));
+  const size_t n_tiles = (size_t)(T - 1) * h->g.n_rows * h->g.n_cols;
+  hipStream_t s = on_stream(c, stream);
+  LSPIV_TRY(ensemble_launch(h, c, d_frames, dtype, T, corr_min, s2n_min, signal_threshold, d_corr_s2n, d_corr_s2n + n_tiles, s));
+  // retention for the float64 rescue of the final fit (lspiv_ensemble_set_retain)
+  const size_t fbytes = (size_t)T * h->H * h->W * elem_size(dtype);
+  if (h->retain_mode == LSPIV_RETAIN_NONE || !h->retain_complete || !g_opt_rescue.load()) {
+    if (h->retain_complete) ensemble_give_up_retention(h);
+  } else if (h->retain_mode == LSPIV_RETAIN_BORROW) {
+    ensemble_keep(h, const_cast<void*>(d_frames), false, fbytes, dtype, T, d_corr_s2n, s);
+  } else {
+    void* copy = nullptr;
+    if (h->kept_bytes + fbytes > ensemble_retain_budget() || hipMalloc(&copy, fbytes) != hipSuccess) {
+      (void)hipGetLastError();
+      ensemble_give_up_retention(h);
+    } else if (hipMemcpyAsync(copy, d_frames, fbytes, hipMemcpyDeviceToDevice, s) != hipSuccess) {
+      (void)hipGetLastError(); (void)hipFree(copy);
+      ensemble_give_up_retention(h);
+    } else {
+      ensemble_keep(h, copy, true, fbytes, dtype, T, d_corr_s2n, s);
+    }
+  }
+  ensemble_mark_accumulated(h, s);   // flag / partials / finish (context stream) wait for the sums, the records and the copies
+  return LSPIV_OK;
+}
+
+int lspiv_ensemble_accumulate(lspiv_ensemble* h, const void* frames, int dtype, int64_t T, float corr_min,
+                              float s2n_min, float signal_threshold, float* corr_max, float* s2n) {
+  std::lock_guard<std::mutex> host_lock(locks_here().host);
+  if (!h || !frames || !corr_max || !s2n) return fail(LSPIV_EINVAL, "NULL argument");
+  DeviceCtx* c;
+  LSPIV_TRY(get_ctx(&c));
+  if (dtype < 0 || dtype > 2) return fail(LSPIV_EINVAL, "dtype %d not in {0:u8, 1:f32, 2:f64}", dtype);
+  if (T < 2) return fail(LSPIV_ESHAPE, "need at least 2 frames, got %lld", (long long)T);
+  const size_t n_win = (size_t)h->g.n_rows * h->g.n_cols, n_tiles = (size_t)(T - 1) * n_win;
+  LSPIV_TRY(ensure(&c->d_out, &c->out_cap, 2 * n_tiles * sizeof(float)));
+  // Pipelined like lspiv_piv_pairs: the ensemble sums are additive over pairs, so the pairs of sub-batch k are
+  // accumulated (in order, on one stream) while sub-batch k+1 is staged and DMA'd.  float64 is narrowed while staged.
+  const int dev_dtype = dtype == LSPIV_F64 ? LSPIV_F32 : dtype;
+  const size_t frame_elems = (size_t)h->H * h->W;
+  const size_t frame_bytes = frame_elems * elem_size(dev_dtype);
+  // the chunk is uploaded into a buffer of its own that stays with the handle until finish (float64 rescue of the final fit),
+  // as long as the retained chunks fit their budget; beyond it, into the shared workspace as before (float32 fits stay)
+  void* own = nullptr;
+  if (g_opt_rescue.load() && h->retain_complete && h->kept_bytes + (size_t)T * frame_bytes <= ensemble_retain_budget()) {
+    if (hipMalloc(&own, (size_t)T * frame_bytes) != hipSuccess) { (void)hipGetLastError(); own = nullptr; }
+  }
+  if (!own) {
+    if (h->retain_complete) ensemble_give_up_retention(h);
+    LSPIV_TRY(ensure(&c->d_frames, &c->frames_cap, (size_t)T * frame_bytes));
+  }
+  char* const d_chunk = own ? (char*)own : (char*)c->d_frames;
+  struct OwnGuard { void* p; ~OwnGuard() { if (p) (void)hipFree(p); } } own_guard{own};   // released on every error path below
+  LSPIV_TRY(stage_ring(c, frame_bytes));
+  const int64_t fpb = std::max<int64_t>(1, (int64_t)(c->pinned_cap / frame_bytes));
+  const int64_t align = std::max(1, chunk_alignment_for(h->wy, h->wx, (int64_t)n_win)), base_offset = h->pairs_done;
+  int64_t launched = 0;
+  {
+    int batch = 0;
+    for (int64_t f0 = 0; f0 < T; ++batch) {
+      const int64_t f1 = std::min<int64_t>(T, f0 + fpb);
+      LSPIV_TRY(stage_frames(c, batch, d_chunk, frames, dtype, false, frame_elems, f0, f1, signal_threshold));
+      HIP_TRY(hipStreamWaitEvent(c->stream, c->staged[batch & 1], 0));
+      // pairs [0, f1 - 1) are resident; accumulate up to the last segment anchor below that (everything at the end)
+      int64_t p1 = f1 - 1;
+      if (f1 < T) p1 = (g_opt_signal_mode.load() == 1 && signal_threshold >= 0.0f) ? 0 : ((base_offset + p1) / align) * align - base_offset;
+      const int64_t p0 = launched;
+      if (p1 > p0) {
+        LSPIV_TRY(ensemble_launch(h, c, d_chunk + (size_t)p0 * frame_bytes, dev_dtype, p1 - p0 + 1, corr_min, s2n_min,
+                                  signal_threshold, c->d_out + p0 * n_win, c->d_out + n_tiles + p0 * n_win, c->stream));
+        launched = p1;
+      }
+      f0 = f1;
+    }
+  }
+  if (own) {
+    own_guard.p = nullptr;          // the handle owns it from here
+    ensemble_keep(h, own, true, (size_t)T * frame_bytes, dev_dtype, T, c->d_out, c->stream);
+  }
+  HIP_TRY(hipMemcpyAsync(corr_max, c->d_out, n_tiles * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(hipMemcpyAsync(s2n, c->d_out + n_tiles, n_tiles * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  return LSPIV_OK;
+}
+
+// ---- float64 rescue of the final fit, in stages (piv_rescue.hip, ens_*) ---------------------------------------------------
+// mean planes (count filter) -> c->d_planes, their float32 fits -> c->d_out [u | v]
+static int ensemble_mean_fit(lspiv_ensemble* h, DeviceCtx* c, float min_count) {
+  const size_t n_win = (size_t)h->g.n_rows * h->g.n_cols;
+  ensemble_wait_accumulated(h, c->stream);   // accumulate_dev may have run on caller streams
+  LSPIV_TRY(ensure(&c->d_planes, &c->planes_cap, n_win * h->wy * h->wx * sizeof(float)));
+  LSPIV_TRY(ensure(&c->d_out, &c->out_cap, 2 * n_win * sizeof(float)));
+  LSPIV_TRY(launch_status(lspiv::launch_ensemble_mean(h->d_sum, h->d_count, min_count, (uint32_t)n_win, h->wy * h->wx, c->d_planes, c->stream)));
+  return launch_status(lspiv::launch_peaks_from_planes(c->d_planes, (uint32_t)n_win, h->wy, h->wx, g_opt_border.load(), c->d_out,
+                                                       c->d_out + n_win, c->stream));
+}
+static lspiv::EnsRescueRec* ensemble_recs(lspiv_ensemble* h) { return reinterpret_cast<lspiv::EnsRescueRec*>((char*)h->d_rescue + 256); }
+
+// flag the windows whose float32 fit (c->d_out, of the mean planes in c->d_planes) cannot be trusted to 1e-4; the records end
+// up sorted by window index -- the same list on every handle that holds the same state (multi-GPU: after the all-reduce)
+static int ensemble_flag(lspiv_ensemble* h, DeviceCtx* c) {
+  h->last_flagged = h->last_rescued = h->last_skipped = 0;
+  h->n_rec = 0;
+  const uint32_t n_win = (uint32_t)(h->g.n_rows * h->g.n_cols);
+  const size_t hdr_bytes = 256;
+  LSPIV_TRY(ensure(&h->d_rescue, &h->rescue_cap, hdr_bytes + (size_t)n_win * sizeof(lspiv::EnsRescueRec)));
+  lspiv::EnsRescueHdr* d_hdr = static_cast<lspiv::EnsRescueHdr*>(h->d_rescue);
+  HIP_TRY(hipMemsetAsync(d_hdr, 0, hdr_bytes, c->stream));
+  // flag model of the per-pair epilogues (fill_params); the block-per-window kernels (kinds 3 / 9 / 10) assume twice the plane noise
+  // of the fused FFT kernels there, and so does the mean of their planes here
+  const int kind = lspiv_kernel_kind(h->wy, h->wx);
+  const double noise_mult = (kind == 3 || kind == 9 || kind == 10) ? 2.0 : 1.0;
+  const float k = (float)(noise_mult * 2.0 * g_opt_rescue_kappa.load() * 1e-9 / (0.6931471805599453 * 1e-4));
+  LSPIV_TRY(launch_status(lspiv::launch_ens_flag(c->d_planes, n_win, h->wy, h->wx, c->d_out, c->d_out + n_win, k, (float)(g_opt_rescue_tau.load() * 1e-9),
+                                                d_hdr, ensemble_recs(h), n_win, c->stream)));
+  lspiv::EnsRescueHdr hdr;
+  HIP_TRY(hipMemcpyAsync(&hdr, d_hdr, sizeof(hdr), hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  h->last_flagged = hdr.n_rec;
+  h->last_skipped = hdr.n_skipped;
+  const uint32_t n_rec = std::min<uint32_t>(hdr.n_rec, n_win);
+  uint64_t digest = 0xcbf29ce484222325ull;   // FNV-1a
+  if (n_rec > 0) {   // the kernel appends in whatever order its waves finish: sort (a few records, once per video)
+    std::vector<lspiv::EnsRescueRec> recs(n_rec);
+    HIP_TRY(hipMemcpy(recs.data(), ensemble_recs(h), n_rec * sizeof(lspiv::EnsRescueRec), hipMemcpyDeviceToHost));
+    std::sort(recs.begin(), recs.end(), [](const lspiv::EnsRescueRec& a, const lspiv::EnsRescueRec& b) { return a.w < b.w; });
+    if (n_rec > 1) HIP_TRY(hipMemcpy(ensemble_recs(h), recs.data(), n_rec * sizeof(lspiv::EnsRescueRec), hipMemcpyHostToDevice));
+    auto mix = [&digest](uint32_t v) { for (int b = 0; b < 4; ++b) { digest ^= (v >> (8 * b)) & 0xffu; digest *= 0x100000001b3ull; } };
+    for (const auto& r : recs) {
+      mix(r.w); mix(r.ncand);
+      for (uint32_t k = 0; k < std::min<uint32_t>(r.ncand, lspiv::kEnsMaxCand); ++k) mix(r.pos[k]);
+    }
+  }
+  h->rec_digest = digest;
+  h->n_rec = n_rec;
+  return LSPIV_OK;
+}
+
+// this handle's share of the float64 sums: over the pairs of its retained chunks, merged in pair-block order -> h->d_totals
+// (n_rec, kEnsMaxCand * 5).  *complete = false (and zeros) when some chunk of this handle could not be kept.
+static int ensemble_partials(lspiv_ensemble* h, DeviceCtx* c, bool* complete) {
+  const size_t row = (size_t)lspiv::kEnsMaxCand * 5 * sizeof(double);
+  LSPIV_TRY(ensure(&h->d_totals, &h->totals_cap, std::max<size_t>(1, h->n_rec) * row));
+  ensemble_wait_accumulated(h, c->stream);   // the kept records and frame copies were written on the accumulating streams
+  HIP_TRY(hipMemsetAsync(h->d_totals, 0, std::max<size_t>(1, h->n_rec) * row, c->stream));
+  *complete = h->retain_complete;
+  if (h->n_rec == 0 || !h->retain_complete || h->kept.empty()) return LSPIV_OK;
+  uint32_t n_blk = 0;
+  for (const auto& kp : h->kept) n_blk += (uint32_t)((kp.T - 1 + lspiv::kEnsPairBlock - 1) / lspiv::kEnsPairBlock);
+  const size_t per_rec = (size_t)n_blk * row;
+  if ((size_t)h->n_rec * per_rec > ((size_t)4 << 30)) { *complete = false; return LSPIV_OK; }   // (thousands of flagged windows x thousands of pair-blocks)
+  LSPIV_TRY(ensure(&h->d_partial, &h->partial_cap, (size_t)h->n_rec * per_rec));
+  lspiv::EnsRescueArgs a;
+  memset(&a, 0, sizeof(a));
+  a.recs = ensemble_recs(h); a.n_rec = h->n_rec; a.n_blk = n_blk; a.partial = h->d_partial; a.count = h->d_count;
+  lspiv::PivParams p;
+  uint32_t blk0 = 0;
+  for (const auto& kp : h->kept) {
+    LSPIV_TRY(fill_params(&p, kp.d_frames, kp.dtype, kp.T, h->H, h->W, h->wy, h->wx, h->oy, h->ox, -1.0f, h->g));
+    a.cmax = kp.d_cmax; a.n_pairs = (uint32_t)(kp.T - 1); a.blk0 = blk0;
+    LSPIV_TRY(launch_status(lspiv::launch_ens_partial(p, kp.dtype, a, c->stream)));
+    blk0 += (a.n_pairs + lspiv::kEnsPairBlock - 1) / lspiv::kEnsPairBlock;
+  }
+  return launch_status(lspiv::launch_ens_merge(a, h->d_totals, c->stream));
+}
+
+// the fit of the flagged windows from the float64 totals (all pairs of the sum), overwriting c->d_out [u | v]
+static int ensemble_final(lspiv_ensemble* h, DeviceCtx* c, const double* d_totals) {
+  if (h->n_rec == 0) return LSPIV_OK;
+  const size_t n_win = (size_t)h->g.n_rows * h->g.n_cols;
+  lspiv::PivParams p;
+  memset(&p, 0, sizeof(p));
+  p.wy = h->wy; p.wx = h->wx; p.border_mode = g_opt_border.load();
+  lspiv::EnsRescueArgs a;
+  memset(&a, 0, sizeof(a));
+  a.recs = ensemble_recs(h); a.n_rec = h->n_rec; a.count = h->d_count;
+  LSPIV_TRY(launch_status(lspiv::launch_ens_final(p, a, d_totals, c->d_out, c->d_out + n_win, c->stream)));
+  h->last_rescued = (int64_t)h->n_rec - h->last_skipped;
+  return LSPIV_OK;
+}
+
+// results of c->d_out / c->d_planes / the count to the caller ("v_sign" applied first)
+static int ensemble_deliver(lspiv_ensemble* h, DeviceCtx* c, float* u, float* v, float* corr_count, float* corr_mean) {
+  const size_t n_win = (size_t)h->g.n_rows * h->g.n_cols;
+  LSPIV_TRY(apply_v_sign(c->d_out + n_win, (int64_t)n_win, c->stream));
+  HIP_TRY(hipMemcpyAsync(u, c->d_out, n_win * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(hipMemcpyAsync(v, c->d_out + n_win, n_win * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+  if (corr_count) HIP_TRY(hipMemcpyAsync(corr_count, h->d_count, n_win * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+  if (corr_mean) HIP_TRY(hipMemcpyAsync(corr_mean, c->d_planes, n_win * h->wy * h->wx * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  return LSPIV_OK;
+}
+
+int lspiv_ensemble_flag(lspiv_ensemble* h, float count_min, float n_frames, int64_t* n_records) {
+  std::lock_guard<std::mutex> host_lock(locks_here().host);
+  if (!h || !n_records) return fail(LSPIV_EINVAL, "NULL argument");
+  DeviceCtx* c;
+  LSPIV_TRY(get_ctx(&c));
+  h->flag_min_count = count_min * n_frames;
+  h->n_rec = 0;
+  *n_records = 0;
+  if (!g_opt_rescue.load()) return LSPIV_OK;
+  LSPIV_TRY(ensemble_mean_fit(h, c, h->flag_min_count));
+  LSPIV_TRY(ensemble_flag(h, c));
+  *n_records = h->n_rec;
+  return LSPIV_OK;
+}
+
+int lspiv_ensemble_flag_digest(lspiv_ensemble* h, uint64_t* digest) {
+  if (!h || !digest) return fail(LSPIV_EINVAL, "NULL argument");
+  *digest = h->n_rec ? h->rec_digest : 0;
+  return LSPIV_OK;
+}
+
+int lspiv_ensemble_partials(lspiv_ensemble* h, double* partials, int* complete) {
+  std::lock_guard<std::mutex> host_lock(locks_here().host);
+  if (!h || !complete || (h->n_rec && !partials)) return fail(LSPIV_EINVAL, "NULL argument");
+  DeviceCtx* c;
+  LSPIV_TRY(get_ctx(&c));
+  bool ok = false;
+  LSPIV_TRY(ensemble_partials(h, c, &ok));
+  *complete = ok ? 1 : 0;
+  if (h->n_rec)
+    HIP_TRY(hipMemcpyAsync(partials, h->d_totals, (size_t)h->n_rec * LSPIV_ENS_PARTIAL_DOUBLES * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  return LSPIV_OK;
+}
+
+int lspiv_ensemble_finish_partials(lspiv_ensemble* h, const double* partials, float* u, float* v, float* corr_count, float* corr_mean) {
+  std::lock_guard<std::mutex> host_lock(locks_here().host);
+  if (!h || !u || !v || (h->n_rec && !partials)) return fail(LSPIV_EINVAL, "NULL argument");
+  DeviceCtx* c;
+  LSPIV_TRY(get_ctx(&c));
+  LSPIV_TRY(ensemble_mean_fit(h, c, h->flag_min_count));   // the shared workspaces may have been used since lspiv_ensemble_flag
+  if (h->n_rec) {
+    const size_t bytes = (size_t)h->n_rec * LSPIV_ENS_PARTIAL_DOUBLES * sizeof(double);
+    LSPIV_TRY(ensure(&h->d_totals, &h->totals_cap, bytes));
+    HIP_TRY(hipMemcpyAsync(h->d_totals, partials, bytes, hipMemcpyHostToDevice, c->stream));
+    LSPIV_TRY(ensemble_final(h, c, h->d_totals));
+  }
+  return ensemble_deliver(h, c, u, v, corr_count, corr_mean);
+}
+
+int lspiv_ensemble_set_retain(lspiv_ensemble* h, int mode) {
+  if (!h) return fail(LSPIV_EINVAL, "NULL argument");
+  if (mode < LSPIV_RETAIN_NONE || mode > LSPIV_RETAIN_BORROW) return fail(LSPIV_EINVAL, "retain mode %d not in {0, 1, 2}", mode);
+  h->retain_mode = mode;
+  return LSPIV_OK;
+}
+
+int lspiv_ensemble_stats(lspiv_ensemble* h, int64_t* stats) {
+  if (!h || !stats) return fail(LSPIV_EINVAL, "NULL argument");
+  stats[0] = h->last_flagged; stats[1] = h->last_rescued; stats[2] = h->last_skipped;
+  stats[3] = (int64_t)h->kept.size(); stats[4] = (int64_t)h->kept_bytes; stats[5] = h->retain_complete ? 1 : 0;
+  return LSPIV_OK;
+}
+
+int lspiv_ensemble_finish(lspiv_ensemble* h, float count_min, float n_frames, float* u, float* v, float* corr_count,
+                          float* corr_mean) {
+  std::lock_guard<std::mutex> host_lock(locks_here().host);
+  if (!h || !u || !v) return fail(LSPIV_EINVAL, "NULL argument");
+  DeviceCtx* c;
+  LSPIV_TRY(get_ctx(&c));
+  h->flag_min_count = count_min * n_frames;
+  h->n_rec = 0;
+  LSPIV_TRY(ensemble_mean_fit(h, c, h->flag_min_count));
+  if (g_opt_rescue.load()) {
+    // float64 rescue of the ill-conditioned fits (include/lspiv.h): needs the frames of EVERY pair in the sum -- a state that
+    // was imported holds other handles' pairs (the multi-GPU path runs the three stages itself and all-reduces the partials)
+    LSPIV_TRY(ensemble_flag(h, c));
+    bool complete = false;
+    if (h->n_rec && !h->foreign) LSPIV_TRY(ensemble_partials(h, c, &complete));
+    if (h->n_rec && complete) LSPIV_TRY(ensemble_final(h, c, h->d_totals));
+    else h->last_skipped = h->last_flagged;
+  }
+  return ensemble_deliver(h, c, u, v, corr_count, corr_mean);
+}
+
+int lspiv_ensemble_export(lspiv_ensemble* h, float* corr_sum, float* corr_count) {
+  if (!h || !corr_sum || !corr_count) return fail(LSPIV_EINVAL, "NULL argument");
+  DeviceCtx* c;
+  LSPIV_TRY(get_ctx(&c));
+  const size_t n_win = (size_t)h->g.n_rows * h->g.n_cols;
+  ensemble_wait_accumulated(h, c->stream);
+  HIP_TRY(hipMemcpyAsync(corr_sum, h->d_sum, n_win * h->wy * h->wx * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(hipMemcpyAsync(corr_count, h->d_count, n_win * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  return LSPIV_OK;
+}
+
+int lspiv_ensemble_import(lspiv_ensemble* h, const float* corr_sum, const float* corr_count, int add) {
+  if (!h || !corr_sum || !corr_count) return fail(LSPIV_EINVAL, "NULL argument");
+  DeviceCtx* c;
+  LSPIV_TRY(get_ctx(&c));
+  const size_t n_win = (size_t)h->g.n_rows * h->g.n_cols, np = n_win * h->wy * h->wx;
+  // the sums now hold pairs whose frames this handle never saw.  Replaced by a total over several handles (multi-GPU: the
+  // all-reduced state): the staged finish (lspiv_ensemble_flag / _partials / _finish_partials) still reaches every pair, each handle
+  // through its own retained chunks.  Added to: this handle's chunks no longer tell which pairs are in the sum -- float32 fits.
+  if (add) ensemble_give_up_retention(h);
+  else h->foreign = true;
+  ensemble_wait_accumulated(h, c->stream);
+  if (!add) {
+    HIP_TRY(hipMemcpyAsync(h->d_sum, corr_sum, np * sizeof(float), hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipMemcpyAsync(h->d_count, corr_count, n_win * sizeof(float), hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    return LSPIV_OK;
+  }
+  // add on the host side of the boundary: export, sum, import (a few tens of MB, once per video)
+  std::vector<float> s(np), k(n_win);
+  LSPIV_TRY(lspiv_ensemble_export(h, s.data(), k.data()));
+  for (size_t i = 0; i < np; ++i) s[i] += corr_sum[i];
+  for (size_t i = 0; i < n_win; ++i) k[i] += corr_count[i];
+  return lspiv_ensemble_import(h, s.data(), k.data(), 0);
+}
+
+int lspiv_ensemble_destroy(lspiv_ensemble* h) {
+  if (!h) return LSPIV_OK;
+  ensemble_drop_kept(h);
+  for (auto& e : h->acc_events) (void)hipEventDestroy(e.ev);
+  for (void* p : {(void*)h->d_sum, (void*)h->d_count, (void*)h->d_part, h->d_rescue, (void*)h->d_partial, (void*)h->d_totals})
+    if (p) hipFree(p);
+  delete h;
+  return LSPIV_OK;
+}
+
+}  // extern "C"

@@ -1,0 +1,513 @@
+// C ABI of liblspiv_hip.so, PIV (api_core.hip has the overview): the window grid, the kernel of a window's family, the float64 rescue
+// pass after it, the chunk alignment, the device-pointer and host-pointer PIV entry points.
+#include "api_internal.h"
+
+#include <algorithm>
+#include <cmath>
+#include <cstdlib>
+#include <cstring>
+
+namespace lspiv_api __attribute__((visibility("hidden"))) {
+
+int check_window(int wy, int wx, int oy, int ox) {
+  if (wy < 2 || wx < 2 || wy > LSPIV_MAX_WINDOW || wx > LSPIV_MAX_WINDOW)
+    return fail(LSPIV_EUNSUPPORTED, "window %dx%d outside supported range 2..%d", wy, wx, LSPIV_MAX_WINDOW);
+  if (oy < 0 || ox < 0 || oy >= wy || ox >= wx)
+    return fail(LSPIV_EINVAL, "overlap (%d,%d) must satisfy 0 <= overlap < window (%d,%d)", oy, ox, wy, wx);
+  return LSPIV_OK;
+}
+
+// ffpiv.window.get_axis_shape restated: (dim - win)//(win - overlap) + 1
+int64_t axis_shape(int64_t dim, int win, int ov) { return dim < win ? 0 : (dim - win) / (win - ov) + 1; }
+
+int make_grid(int64_t H, int64_t W, int wy, int wx, int oy, int ox, Grid* g) {
+  LSPIV_TRY(check_window(wy, wx, oy, ox));
+  if (H <= 0 || W <= 0) return fail(LSPIV_ESHAPE, "frame shape (%lld,%lld) invalid", (long long)H, (long long)W);
+  g->n_rows = axis_shape(H, wy, oy);
+  g->n_cols = axis_shape(W, wx, ox);
+  if (g->n_rows <= 0 || g->n_cols <= 0)
+    return fail(LSPIV_ESHAPE, "frame (%lld,%lld) smaller than window (%d,%d)", (long long)H, (long long)W, wy, wx);
+  return LSPIV_OK;
+}
+
+// the rescue lists of stream `s`, large enough for a launch of n_tiles windows (a quarter of them "fit", a sixteenth "amb":
+// beyond that the excess keeps its float32 result -- imagery THAT sparse has no usable peaks)
+int rescue_ws(DeviceCtx* c, hipStream_t s, uint32_t n_tiles, lspiv::PivParams* p) {
+  std::lock_guard<std::mutex> lk(locks_here().lists);
+  DeviceCtx::RescueWs* ws = nullptr;
+  for (auto& w : c->rescue) if (w.stream == s) ws = &w;
+  if (!ws) { c->rescue.push_back({s, nullptr, 0, 0, 0}); ws = &c->rescue.back(); }
+  const uint32_t cap_fit = std::max<uint32_t>(4096u, n_tiles / 4u), cap_amb = std::max<uint32_t>(1024u, n_tiles / 16u);
+  const size_t hdr_bytes = 256;   // sizeof(RescueHdr) rounded up, keeps the lists 256-byte aligned
+  static_assert(sizeof(lspiv::RescueHdr) <= 256, "header slot too small");
+  if (cap_fit > ws->cap_fit || cap_amb > ws->cap_amb || !ws->base) {
+    const uint32_t nf = std::max(cap_fit, ws->cap_fit), na = std::max(cap_amb, ws->cap_amb);
+    const size_t bytes = hdr_bytes + (size_t)nf * sizeof(uint4) + (size_t)na * sizeof(uint32_t);
+    void* grown = nullptr;
+    HIP_TRY(hipMalloc(&grown, bytes));
+    if (ws->base) {
+      // the header moves along: its per-pass counters are zero between passes (the rescue kernel's last block resets them) and
+      // the totals of lspiv_rescue_stats ("summed over all launches") survive the regrow
+      hipError_t e = hipStreamSynchronize(s);
+      if (e == hipSuccess) e = hipMemcpy(grown, ws->base, hdr_bytes, hipMemcpyDeviceToDevice);
+      if (e != hipSuccess) { (void)hipFree(grown); return fail(LSPIV_EHIP, "rescue lists: %s", hipGetErrorString(e)); }
+      HIP_TRY(hipFree(ws->base));
+    } else {
+      HIP_TRY(hipMemsetAsync(grown, 0, hdr_bytes, s));   // ordered before the kernels of this stream
+    }
+    ws->base = grown;
+    ws->cap_bytes = bytes; ws->cap_fit = nf; ws->cap_amb = na;
+  }
+  p->rescue_hdr = static_cast<lspiv::RescueHdr*>(ws->base);
+  p->rescue_fit = reinterpret_cast<uint4*>((char*)ws->base + hdr_bytes);
+  p->rescue_amb = reinterpret_cast<uint32_t*>((char*)ws->base + hdr_bytes + (size_t)ws->cap_fit * sizeof(uint4));
+  p->rescue_cap_fit = ws->cap_fit;
+  p->rescue_cap_amb = ws->cap_amb;
+  return LSPIV_OK;
+}
+
+int fill_params(lspiv::PivParams* p, const void* d_frames, int dtype, int64_t T, int64_t H, int64_t W, int wy, int wx,
+                int oy, int ox, float signal_threshold, const Grid& g) {
+  if (dtype < 0 || dtype > 2) return fail(LSPIV_EINVAL, "dtype %d not in {0:u8, 1:f32, 2:f64}", dtype);
+  if (T < 2) return fail(LSPIV_ESHAPE, "need at least 2 frames, got %lld", (long long)T);
+  const int64_t n_win = g.n_rows * g.n_cols;
+  const int64_t n_tiles = (T - 1) * n_win;
+  if (n_tiles >= (int64_t)1 << 31 || H * W >= (int64_t)1 << 31)
+    return fail(LSPIV_EINVAL, "chunk too large for one launch: %lld windows (limit 2^31); use smaller chunks",
+                (long long)n_tiles);
+  memset(p, 0, sizeof(*p));
+  p->frames = d_frames;
+  p->frame_elems = H * W;
+  p->H = (int)H; p->W = (int)W;
+  p->wy = wy; p->wx = wx;
+  p->sy = wy - oy; p->sx = wx - ox;
+  p->n_rows = (int)g.n_rows; p->n_cols = (int)g.n_cols;
+  p->n_win = (uint32_t)n_win;
+  p->n_tiles = (uint32_t)n_tiles;
+  p->n_pairs = (uint32_t)(T - 1);
+  p->signal_threshold = signal_threshold;
+  p->border_mode = g_opt_border.load();
+  p->nz_positive = g_opt_signal_pos.load();
+  {
+    const double n = (double)wy * (double)wx;
+    const double g2 = g_opt_std_ddof.load() && n > 1.0 ? (n - 1.0) / n : 1.0;   // sample std: every normalised window shrinks by sqrt((n-1)/n)
+    p->std_gain2 = (float)g2;
+    p->std_gain = (float)std::sqrt(g2);
+    p->norm_clip = g_opt_norm_clip.load();
+  }
+  // flag model of the rescue pass (common.h, peak_cond): k = 2 kappa / (ln 2 * 1e-4)
+  p->rescue_k = (float)(2.0 * g_opt_rescue_kappa.load() * 1e-9 / (0.6931471805599453 * 1e-4));
+  p->rescue_tau = (float)(g_opt_rescue_tau.load() * 1e-9);
+  p->div_ncols = lspiv::FastDiv::make((uint32_t)g.n_cols);
+  p->div_jobs = lspiv::FastDiv::make((uint32_t)((n_win + 1) / 2));
+  p->div_nwin = lspiv::FastDiv::make((uint32_t)n_win);
+  return LSPIV_OK;
+}
+
+static int dispatch_kernels(const lspiv::PivParams& p, int dtype, bool ensemble, hipStream_t s);
+
+// PIV kernel of the window's family, then -- per-timestep mode, unless switched off -- the float64 rescue pass over the
+// windows that kernel flagged (piv_rescue.hip)
+// The PIV kernel and the two rescue kernels of ONE launch share the stream's lists and counters: they are issued under one
+// lock, so that two host threads launching on the same stream (NULL -> the library's stream) cannot interleave as PIV 1,
+// PIV 2, rescue 1 -- rescue 1 would then consume launch 2's records with launch 1's parameters.  Launches are asynchronous:
+// the lock is held for microseconds.  (The rescue kernels skip a record whose index is outside their launch all the same.)
+// "time_kernel" option (measurement only, off by default): HIP events on the launch's own stream right before and right after the
+// PIV kernel(s) of a launch -- NOT around the rescue kernels that follow --, i.e. the duration rocprofv3 --kernel-trace reports for
+// the dominant kernel, inside the launch exactly as a caller issues it (rescue pass on: the kernel appends its records).  A ring of
+// the last 16 launches per device; lspiv_kernel_times reads and empties it.  bench.py's roofline.achieved comes from here.
+constexpr int kTimerRing = 16;
+struct KernelTimer { hipEvent_t e0[kTimerRing] = {}, e1[kTimerRing] = {}; int n = 0; };
+KernelTimer g_timers[kMaxDevices];   // guarded by the device's dispatch lock
+static int timed_dispatch_kernels(const lspiv::PivParams& p, int dtype, bool ensemble, hipStream_t s) {
+  if (!g_opt_time_kernel.load()) return dispatch_kernels(p, dtype, ensemble, s);
+  KernelTimer& t = g_timers[current_device_slot()];
+  const int k = t.n % kTimerRing;
+  if (!t.e0[k]) { HIP_TRY(hipEventCreate(&t.e0[k])); HIP_TRY(hipEventCreate(&t.e1[k])); }
+  HIP_TRY(hipEventRecord(t.e0[k], s));
+  LSPIV_TRY(dispatch_kernels(p, dtype, ensemble, s));
+  HIP_TRY(hipEventRecord(t.e1[k], s));
+  ++t.n;
+  return LSPIV_OK;
+}
+int dispatch(const lspiv::PivParams& p0, int dtype, bool ensemble, hipStream_t s) {
+  if (ensemble || !g_opt_rescue.load()) {
+    if (!g_opt_time_kernel.load()) return dispatch_kernels(p0, dtype, ensemble, s);
+    std::lock_guard<std::mutex> launch_lock(locks_here().dispatch);
+    return timed_dispatch_kernels(p0, dtype, ensemble, s);
+  }
+  DeviceCtx* c;
+  LSPIV_TRY(get_ctx(&c));
+  lspiv::PivParams p = p0;
+  std::lock_guard<std::mutex> launch_lock(locks_here().dispatch);
+  LSPIV_TRY(rescue_ws(c, s, p.n_tiles, &p));
+  LSPIV_TRY(timed_dispatch_kernels(p, dtype, false, s));
+  return launch_status(lspiv::launch_piv_rescue(p, dtype, s), "rescue kernel launch failed");
+}
+
+// "v_sign" option: the engine's v negated (after the kernels and the rescue pass; the default costs nothing)
+int apply_v_sign(float* d_v, int64_t n, hipStream_t s) {
+  if (!g_opt_v_sign.load() || !d_v) return LSPIV_OK;
+  return launch_status(lspiv::launch_negate(d_v, n, s));
+}
+
+static int dispatch_kernels(const lspiv::PivParams& p, int dtype, bool ensemble, hipStream_t s) {
+  const int kind = lspiv_kernel_kind(p.wy, p.wx);
+  hipError_t e;
+  switch (kind) {
+    case 7: e = lspiv::launch_piv_embed16(p, dtype, ensemble, s); break;
+    case 4: e = lspiv::launch_piv_embed32(p, dtype, ensemble, s); break;
+    case 5: e = lspiv::launch_piv_embed64(p, dtype, ensemble, s); break;
+    case 6: e = p.wy == 8 ? lspiv::launch_piv_fft8(p, dtype, ensemble, s) : lspiv::launch_piv_fft16(p, dtype, ensemble, s); break;
+    case 8:
+      switch (p.wy) {
+#define LSPIV_PFA_CASE(n) case n: e = lspiv::launch_piv_fft##n(p, dtype, ensemble, s); break;
+        LSPIV_PFA_SIZES(LSPIV_PFA_CASE)
+#undef LSPIV_PFA_CASE
+        default: return fail(LSPIV_EUNSUPPORTED, "no prime-factor kernel for window %d", p.wy);
+      }
+      break;
+    case 1: e = lspiv::launch_piv_fft32(p, dtype, ensemble, s); break;
+    case 2: e = lspiv::launch_piv_fft64(p, dtype, ensemble, s); break;
+    case 3: e = lspiv::launch_piv_direct(p, dtype, ensemble, s); break;
+    case 9: e = lspiv::launch_piv_dft(p, dtype, ensemble, s); break;
+    case 10: {   // above 128 px: the same passes on slots of HBM scratch owned by the context (one stream at a time, like the
+                 // other context workspaces)
+      DeviceCtx* c;
+      LSPIV_TRY(get_ctx(&c));
+      const size_t slot = lspiv::piv_dft_global_slot_floats(p.wy, p.wx);
+      const int blocks = lspiv::piv_dft_global_blocks(ensemble ? p.n_win : p.n_tiles);
+      LSPIV_TRY(ensure(&c->d_dft, &c->dft_cap, slot * (size_t)blocks * sizeof(float)));
+      lspiv::PivParams q = p;
+      q.dft_scratch = (float*)c->d_dft;
+      q.dft_slot = slot;
+      e = lspiv::launch_piv_dft_global(q, dtype, ensemble, s);
+      break;
+    }
+    default: return fail(LSPIV_EUNSUPPORTED, "no kernel for window %dx%d", p.wy, p.wx);
+  }
+  return launch_status(e);
+}
+
+// "stack" signal mode: one pass over the chunk's frames leaves a keep flag per window position; the PIV kernels then run
+// their threshold path with a pair threshold that always passes and consult the flags instead
+int apply_signal_mode(DeviceCtx* c, lspiv::PivParams* p, int dtype, hipStream_t s) {
+  if (g_opt_signal_mode.load() != 1 || p->signal_threshold < 0.0f) return LSPIV_OK;
+  LSPIV_TRY(ensure(&c->d_keep, &c->keep_cap, (size_t)p->n_win));
+  LSPIV_TRY(launch_status(lspiv::launch_window_signal(p->frames, dtype, (int64_t)p->n_pairs + 1, *p, p->signal_threshold, c->d_keep, s)));
+  p->win_keep = c->d_keep;
+  p->signal_threshold = 0.0f;
+  return LSPIV_OK;
+}
+// run length of the window family on small grids (kWalkAnchor), 1 for per-pair kernels, a forced length as it is
+static int base_alignment(int wy, int wx) {
+  const int kind = lspiv_kernel_kind(wy, wx);
+  if (kind < 0) return kind;
+  const int walk = lspiv::walk_setting();
+  if (!kind_walks(kind) || walk == 0) return 1;
+  return walk > 1 ? walk : (int)lspiv::kWalkAnchor;
+}
+int chunk_alignment_for(int wy, int wx, int64_t n_win) {
+  const int base = base_alignment(wy, wx);
+  if (base <= 1 || lspiv::walk_setting() > 1) return base;     // per-pair kernels, or a forced anchor length
+  return (int)lspiv::walk_anchor(wy, (uint32_t)std::min<int64_t>(n_win, 0x7fffffff));
+}
+
+}  // namespace lspiv_api
+
+using namespace lspiv_api;
+
+uint32_t lspiv::job_slots(int waves_per_simd, int groups) {
+  static const int cus = [] {
+    int dev = 0;
+    hipDeviceProp_t prop;
+    if (hipGetDevice(&dev) != hipSuccess || hipGetDeviceProperties(&prop, dev) != hipSuccess || prop.multiProcessorCount < 1) return 256;
+    return prop.multiProcessorCount;
+  }();
+  return (uint32_t)(cus * 4 * waves_per_simd * groups);
+}
+
+extern "C" {
+
+int lspiv_kernel_times(float* ms, int cap, int* n) {
+  if (!ms || !n || cap < 0) return fail(LSPIV_EINVAL, "bad argument");
+  std::lock_guard<std::mutex> launch_lock(locks_here().dispatch);
+  KernelTimer& t = g_timers[current_device_slot()];
+  const int have = std::min(std::min(t.n, kTimerRing), cap);
+  for (int i = 0; i < have; ++i) {
+    const int k = (t.n - have + i) % kTimerRing;
+    HIP_TRY(hipEventSynchronize(t.e1[k]));
+    HIP_TRY(hipEventElapsedTime(&ms[i], t.e0[k], t.e1[k]));
+  }
+  *n = have;
+  t.n = 0;
+  return LSPIV_OK;
+}
+
+int lspiv_rescue_stats(void* stream, int64_t* stats) {
+  if (!stats) return fail(LSPIV_EINVAL, "stats is NULL");
+  DeviceCtx* c;
+  LSPIV_TRY(get_ctx(&c));
+  hipStream_t s = on_stream(c, stream);
+  void* base = nullptr;
+  {
+    std::lock_guard<std::mutex> lk(locks_here().lists);
+    for (auto& w : c->rescue) if (w.stream == s) base = w.base;
+  }
+  for (int k = 0; k < 5; ++k) stats[k] = 0;
+  if (!base) return LSPIV_OK;   // no pass has run on this stream
+  lspiv::RescueHdr h;
+  HIP_TRY(hipMemcpyAsync(&h, base, sizeof(h), hipMemcpyDeviceToHost, s));
+  HIP_TRY(hipStreamSynchronize(s));
+  stats[0] = h.last_fit; stats[1] = h.last_amb;
+  stats[2] = (int64_t)h.total_fit; stats[3] = (int64_t)h.total_amb; stats[4] = (int64_t)h.total_windows;
+  return LSPIV_OK;
+}
+
+int lspiv_kernel_kind(int wy, int wx) {
+  if (wy < 2 || wx < 2 || wy > LSPIV_MAX_WINDOW || wx > LSPIV_MAX_WINDOW) return LSPIV_EUNSUPPORTED;
+  if (wy > 64 || wx > 64) return lspiv::piv_dft_fits(wy, wx) ? 9 : 10;   // 2-D DFT of any shape: LDS-resident up to 128 x 128, HBM slots above
+  if (!g_opt_norm_clip.load()) {   // the un-clipped reading of A3 lives in the block-per-window kernels only (a switch, not a tuned path)
+    static const int min_area = getenv("LSPIV_DFT_MIN_AREA") ? atoi(getenv("LSPIV_DFT_MIN_AREA")) : 1500;
+    return wy * wx >= min_area && lspiv::piv_dft_fits(wy, wx) ? 9 : 3;
+  }
+  if (wy == 32 && wx == 32) return 1;
+  if (wy == 64 && wx == 64) return 2;
+  if (wy == 16 && wx == 16) return 6;
+  if (wy == 8 && wx == 8 && getenv("LSPIV_NO_PFA") == nullptr) return 6;
+  const bool no_pfa = getenv("LSPIV_NO_PFA") != nullptr;             // A/B switch: the P * 2^m sizes without their own FFT kernels
+  if (!no_pfa && wy == wx) {
+    switch (wy) {
+#define LSPIV_PFA_CASE(n) case n:
+      LSPIV_PFA_SIZES(LSPIV_PFA_CASE)
+#undef LSPIV_PFA_CASE
+        return 8;
+      default: break;
+    }
+  }
+  const bool no_embed = getenv("LSPIV_NO_EMBED") != nullptr;   // A/B switch: direct kernel for every other size
+  if (!no_embed && wy == wx && wy >= 4 && wy <= 8) return 7;
+  if (!no_embed && wy == wx && wy >= 9 && wy <= 15) return 4;
+  // 17..20: the direct kernel's N^4 multiply-adds are still cheaper than two 64-point transforms per window (measured
+  // crossover between 20 and 22, tools/direct_bench.py)
+  if (!no_embed && wy == wx && wy > 20 && wy < 32) return 5;
+  // what is left -- non-square windows, odd 17 / 19 / 33 .. 63: the direct spatial kernel costs wy wx multiply-adds per plane
+  // sample, the LDS-resident DFT passes (wy + wx) complex ones, a composite length in two shorter passes.  Measured on
+  // 785 x 875 frames (tools/gpu_ab_direct.sh; M window pairs/s, direct | DFT): 40 x 24 23.2 | 13.1, 35 x 35 14.0 | 12.2,
+  // 48 x 32 10.4 | 11.9, 41 x 41 8.1 | 9.2, 64 x 32 6.1 | 11.3, 49 x 49 3.6 | 10.7, 63 x 63 1.6 | 7.2 -- the DFT kernel takes over
+  // from 1500 samples per window (LSPIV_DFT_MIN_AREA)
+  static const int dft_min_area = getenv("LSPIV_DFT_MIN_AREA") ? atoi(getenv("LSPIV_DFT_MIN_AREA")) : 1500;
+  if (wy * wx >= dft_min_area && lspiv::piv_dft_fits(wy, wx)) return 9;
+  return 3;
+}
+
+int lspiv_grid_shape(int64_t H, int64_t W, int wy, int wx, int oy, int ox, int64_t* n_rows, int64_t* n_cols) {
+  if (!n_rows || !n_cols) return fail(LSPIV_EINVAL, "output pointer is NULL");
+  LSPIV_TRY(check_window(wy, wx, oy, ox));
+  *n_rows = axis_shape(H, wy, oy);
+  *n_cols = axis_shape(W, wx, ox);
+  return LSPIV_OK;
+}
+
+int lspiv_grid_coords(int64_t H, int64_t W, int wy, int wx, int oy, int ox, int64_t* rows, int64_t* cols) {
+  int64_t nr, nc;
+  LSPIV_TRY(lspiv_grid_shape(H, W, wy, wx, oy, ox, &nr, &nc));
+  if ((nr > 0 && !rows) || (nc > 0 && !cols)) return fail(LSPIV_EINVAL, "output pointer is NULL");
+  // ffpiv.window.get_axis_coords restated: int64(arange(n) * (win - overlap) + win / 2.0)
+  for (int64_t k = 0; k < nr; ++k) rows[k] = (int64_t)std::floor((double)k * (wy - oy) + wy / 2.0);
+  for (int64_t k = 0; k < nc; ++k) cols[k] = (int64_t)std::floor((double)k * (wx - ox) + wx / 2.0);
+  return LSPIV_OK;
+}
+
+int64_t lspiv_required_bytes(int64_t T, int64_t H, int64_t W, int dtype, int wy, int wx, int oy, int ox,
+                             int with_planes) {
+  Grid g;
+  LSPIV_TRY(make_grid(H, W, wy, wx, oy, ox, &g));
+  if (dtype < 0 || dtype > 2 || T < 2) return fail(LSPIV_EINVAL, "bad dtype/T");
+  const int64_t n_tiles = (T - 1) * g.n_rows * g.n_cols;
+  int64_t b = T * H * W * (int64_t)elem_size(dtype) + 4 * n_tiles * 4;
+  if (with_planes) b += n_tiles * wy * wx * 4;
+  if (g_opt_rescue.load())   // the rescue lists of the launch stream: n_tiles / 4 records of 16 bytes + n_tiles / 16 of 4 (rescue_ws)
+    b += 256 + (int64_t)std::max<int64_t>(4096, n_tiles / 4) * 16 + (int64_t)std::max<int64_t>(1024, n_tiles / 16) * 4;
+  return b;
+}
+
+int lspiv_available_bytes(int64_t* free_bytes, int64_t* total_bytes) {
+  DeviceCtx* c;
+  LSPIV_TRY(get_ctx(&c));
+  size_t f = 0, t = 0;
+  HIP_TRY(hipMemGetInfo(&f, &t));
+  // workspaces this library already holds are reusable, count them as free
+  f += c->frames_cap + c->out_cap + c->planes_cap;
+  if (free_bytes) *free_bytes = (int64_t)f;
+  if (total_bytes) *total_bytes = (int64_t)t;
+  return LSPIV_OK;
+}
+
+// Without a grid: the alignment that is right for EVERY frame shape -- the longest run length the family uses, a multiple of the
+// shorter one (ABI 5; it returned the short one before, which cut chunks off the anchors of large grids: ADVICE r05)
+int lspiv_chunk_alignment(int wy, int wx) {
+  const int base = base_alignment(wy, wx);
+  if (base <= 1 || lspiv::walk_setting() > 1) return base;
+  static_assert(lspiv::kWalkAnchorLong % lspiv::kWalkAnchor == 0, "the long anchor must be a multiple of the short one");
+  return (int)lspiv::kWalkAnchorLong;
+}
+int lspiv_chunk_alignment_grid(int64_t H, int64_t W, int wy, int wx, int oy, int ox) {
+  Grid g;
+  LSPIV_TRY(make_grid(H, W, wy, wx, oy, ox, &g));
+  return chunk_alignment_for(wy, wx, g.n_rows * g.n_cols);
+}
+
+int lspiv_piv_pairs_dev_at(const void* d_frames, int dtype, int64_t T, int64_t H, int64_t W, int wy, int wx, int oy,
+                           int ox, float signal_threshold, int64_t pair_offset, float* d_out, float* d_corr_planes,
+                           void* stream) {
+  if (!d_frames || !d_out) return fail(LSPIV_EINVAL, "d_frames / d_out is NULL");
+  if (pair_offset < 0) return fail(LSPIV_EINVAL, "pair_offset %lld is negative", (long long)pair_offset);
+  Grid g;
+  LSPIV_TRY(make_grid(H, W, wy, wx, oy, ox, &g));
+  DeviceCtx* c;
+  LSPIV_TRY(get_ctx(&c));
+  lspiv::PivParams p;
+  LSPIV_TRY(fill_params(&p, d_frames, dtype, T, H, W, wy, wx, oy, ox, signal_threshold, g));
+  p.pair_offset = pair_offset;
+  p.u = d_out;
+  p.v = d_out + (size_t)p.n_tiles;
+  p.cmax = d_out + 2 * (size_t)p.n_tiles;
+  p.s2n = d_out + 3 * (size_t)p.n_tiles;
+  p.planes = d_corr_planes;
+  hipStream_t s = on_stream(c, stream);
+  LSPIV_TRY(apply_signal_mode(c, &p, dtype, s));
+  LSPIV_TRY(dispatch(p, dtype, false, s));
+  return apply_v_sign(p.v, (int64_t)p.n_tiles, s);
+}
+
+int lspiv_piv_pairs_dev(const void* d_frames, int dtype, int64_t T, int64_t H, int64_t W, int wy, int wx, int oy,
+                        int ox, float signal_threshold, float* d_out, float* d_corr_planes, void* stream) {
+  return lspiv_piv_pairs_dev_at(d_frames, dtype, T, H, W, wy, wx, oy, ox, signal_threshold, 0, d_out, d_corr_planes, stream);
+}
+
+// the host entry point, optionally with the px -> m/s scaling of pyorc/velocimetry/ffpiv.py:418-419 applied on the device before the
+// results come back (dt != NULL: seconds per pair, T - 1 entries)
+static int piv_pairs_host(const void* frames, int dtype, int64_t T, int64_t H, int64_t W, int wy, int wx, int oy, int ox,
+                          float signal_threshold, int64_t pair_offset, float* u, float* v, float* corr_max, float* s2n,
+                          float* corr_planes, const double* dt, double res_x, double res_y) {
+  std::lock_guard<std::mutex> host_lock(locks_here().host);
+  if (!frames || !u || !v || !corr_max || !s2n) return fail(LSPIV_EINVAL, "NULL buffer");
+  if (pair_offset < 0) return fail(LSPIV_EINVAL, "pair_offset %lld is negative", (long long)pair_offset);
+  Grid g;
+  LSPIV_TRY(make_grid(H, W, wy, wx, oy, ox, &g));
+  if (dtype < 0 || dtype > 2) return fail(LSPIV_EINVAL, "dtype %d not in {0:u8, 1:f32, 2:f64}", dtype);
+  if (T < 2) return fail(LSPIV_ESHAPE, "need at least 2 frames, got %lld", (long long)T);
+  DeviceCtx* c;
+  LSPIV_TRY(get_ctx(&c));
+  const int dev_dtype = dtype == LSPIV_F64 ? LSPIV_F32 : dtype;   // float64 is narrowed while it is staged
+  const size_t fbytes = (size_t)T * H * W * elem_size(dev_dtype);
+  const size_t n_tiles = (size_t)(T - 1) * g.n_rows * g.n_cols;
+  LSPIV_TRY(ensure(&c->d_frames, &c->frames_cap, fbytes));
+  LSPIV_TRY(ensure(&c->d_out, &c->out_cap, 4 * n_tiles * sizeof(float)));
+  if (corr_planes) {
+    LSPIV_TRY(ensure(&c->d_planes, &c->planes_cap, n_tiles * wy * wx * sizeof(float)));
+  }
+  // Pipelined upload: the stack is copied through a two-slot pinned ring in sub-batches of whole frames; the kernel
+  // for the pairs that have become resident runs while the next sub-batch is staged and DMA'd.  Launches are cut at
+  // the anchors of the walking kernels' segments (multiples of lspiv_chunk_alignment of the absolute pair index), so
+  // the pipelined run issues exactly the jobs of one launch over the whole stack: same bits as lspiv_piv_pairs_dev_at.
+  lspiv::PivParams base;
+  LSPIV_TRY(fill_params(&base, c->d_frames, dev_dtype, T, H, W, wy, wx, oy, ox, signal_threshold, g));
+  const size_t n_win = (size_t)g.n_rows * g.n_cols;
+  const size_t frame_bytes = (size_t)H * W * elem_size(dev_dtype);
+  LSPIV_TRY(stage_ring(c, frame_bytes));
+  const int64_t fpb = std::max<int64_t>(1, (int64_t)(c->pinned_cap / frame_bytes));
+  const bool src_pinned = dtype != LSPIV_F64 && is_pinned(frames);
+  const int64_t align = std::max(1, chunk_alignment_for(wy, wx, (int64_t)n_win));
+  // "stack" signal mode scores a window position over ALL frames of the chunk: one launch once everything is resident
+  const bool whole_chunk_only = g_opt_signal_mode.load() == 1 && signal_threshold >= 0.0f;
+  int64_t launched = 0;   // pairs [0, launched) have been issued
+  int batch = 0;
+  TraceSpan span;
+  trace_begin(&span, LSPIV_TRACE_PIV_HOST, c->stream);
+  for (int64_t f0 = 0; f0 < T; ++batch) {
+    const int64_t f1 = std::min<int64_t>(T, f0 + fpb);
+    LSPIV_TRY(stage_frames(c, batch, c->d_frames, frames, dtype, src_pinned, (size_t)H * W, f0, f1, signal_threshold));
+    HIP_TRY(hipStreamWaitEvent(c->stream, c->staged[batch & 1], 0));
+    // pairs whose two frames are resident: [0, f1 - 1); issue up to the last anchor below that (everything at the end)
+    int64_t p1 = f1 - 1;
+    if (f1 < T) p1 = whole_chunk_only ? 0 : ((pair_offset + p1) / align) * align - pair_offset;
+    const int64_t p0 = launched;
+    if (p1 > p0) {
+      lspiv::PivParams p = base;
+      p.frames = (const char*)c->d_frames + (size_t)p0 * frame_bytes;
+      p.pair_offset = pair_offset + p0;
+      p.n_pairs = (uint32_t)(p1 - p0);
+      p.n_tiles = (uint32_t)((p1 - p0) * n_win);
+      p.u = c->d_out + p0 * n_win;
+      p.v = c->d_out + n_tiles + p0 * n_win;
+      p.cmax = c->d_out + 2 * n_tiles + p0 * n_win;
+      p.s2n = c->d_out + 3 * n_tiles + p0 * n_win;
+      p.planes = corr_planes ? c->d_planes + (size_t)p0 * n_win * wy * wx : nullptr;
+      LSPIV_TRY(apply_signal_mode(c, &p, dev_dtype, c->stream));
+      LSPIV_TRY(dispatch(p, dev_dtype, false, c->stream));
+      LSPIV_TRY(apply_v_sign(p.v, (int64_t)p.n_tiles, c->stream));
+      launched = p1;
+    }
+    f0 = f1;
+  }
+  if (dt) {
+    // u, v to metres per second where they are: (u * res / dt).astype(float32) -- float32 product, float64 division, one rounding
+    // (masks.hip, scale_velocity_kernel: bit for bit what numpy computes for a python-float resolution, tests/test_masks.py)
+    LSPIV_TRY(ensure(&c->d_scratch, &c->scratch_cap, (size_t)(T - 1) * sizeof(double)));
+    HIP_TRY(hipMemcpyAsync(c->d_scratch, dt, (size_t)(T - 1) * sizeof(double), hipMemcpyHostToDevice, c->stream));
+    LSPIV_TRY(launch_status(lspiv::launch_scale_velocity(c->d_out, T - 1, (int64_t)n_win, (float)res_x, (float)res_y, (const double*)c->d_scratch, c->stream)));
+  }
+  const size_t ob = n_tiles * sizeof(float);
+  HIP_TRY(hipMemcpyAsync(u, c->d_out, ob, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(hipMemcpyAsync(v, c->d_out + n_tiles, ob, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(hipMemcpyAsync(corr_max, c->d_out + 2 * n_tiles, ob, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(hipMemcpyAsync(s2n, c->d_out + 3 * n_tiles, ob, hipMemcpyDeviceToHost, c->stream));
+  if (corr_planes)
+    HIP_TRY(hipMemcpyAsync(corr_planes, c->d_planes, n_tiles * wy * wx * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+  trace_end(&span, c->stream);
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  return LSPIV_OK;
+}
+
+int lspiv_piv_pairs_at(const void* frames, int dtype, int64_t T, int64_t H, int64_t W, int wy, int wx, int oy, int ox,
+                       float signal_threshold, int64_t pair_offset, float* u, float* v, float* corr_max, float* s2n,
+                       float* corr_planes) {
+  return piv_pairs_host(frames, dtype, T, H, W, wy, wx, oy, ox, signal_threshold, pair_offset, u, v, corr_max, s2n, corr_planes, nullptr, 1.0, 1.0);
+}
+
+int lspiv_piv_velocity_at(const void* frames, int dtype, int64_t T, int64_t H, int64_t W, int wy, int wx, int oy, int ox,
+                          float signal_threshold, int64_t pair_offset, double res_x, double res_y, const double* dt, float* v_x, float* v_y,
+                          float* corr_max, float* s2n) {
+  if (!dt) return fail(LSPIV_EINVAL, "dt is NULL");
+  return piv_pairs_host(frames, dtype, T, H, W, wy, wx, oy, ox, signal_threshold, pair_offset, v_x, v_y, corr_max, s2n, nullptr, dt, res_x, res_y);
+}
+
+int lspiv_piv_pairs(const void* frames, int dtype, int64_t T, int64_t H, int64_t W, int wy, int wx, int oy, int ox,
+                    float signal_threshold, float* u, float* v, float* corr_max, float* s2n, float* corr_planes) {
+  return lspiv_piv_pairs_at(frames, dtype, T, H, W, wy, wx, oy, ox, signal_threshold, 0, u, v, corr_max, s2n, corr_planes);
+}
+
+int lspiv_u_v_displacement(const float* corr_planes, int64_t P, int64_t n_win, int wy, int wx, float* u, float* v) {
+  std::lock_guard<std::mutex> host_lock(locks_here().host);
+  if (!corr_planes || !u || !v) return fail(LSPIV_EINVAL, "NULL buffer");
+  if (P < 0 || n_win < 0 || wy < 1 || wx < 1 || wy > 4096 || wx > 4096) return fail(LSPIV_EINVAL, "bad shape");
+  const int64_t n = P * n_win;
+  if (n == 0) return LSPIV_OK;
+  if (n >= (int64_t)1 << 31) return fail(LSPIV_EINVAL, "too many planes for one launch");
+  DeviceCtx* c;
+  LSPIV_TRY(get_ctx(&c));
+  const size_t pb = (size_t)n * wy * wx * sizeof(float);
+  LSPIV_TRY(ensure(&c->d_planes, &c->planes_cap, pb));
+  LSPIV_TRY(ensure(&c->d_out, &c->out_cap, 2 * (size_t)n * sizeof(float)));
+  HIP_TRY(hipMemcpyAsync(c->d_planes, corr_planes, pb, hipMemcpyHostToDevice, c->stream));
+  LSPIV_TRY(launch_status(lspiv::launch_peaks_from_planes(c->d_planes, (uint32_t)n, wy, wx, g_opt_border.load(), c->d_out, c->d_out + n, c->stream)));
+  LSPIV_TRY(apply_v_sign(c->d_out + n, n, c->stream));
+  HIP_TRY(hipMemcpyAsync(u, c->d_out, n * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(hipMemcpyAsync(v, c->d_out + n, n * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  return LSPIV_OK;
+}
+
+}  // extern "C"

@@ -32,7 +32,7 @@
 
 namespace lspiv_comm_detail {
 
-int comm_fail(int code, const char* fmt, ...);   // sets the library's thread-local message (lspiv_api.hip)
+int comm_fail(int code, const char* fmt, ...);   // sets the library's thread-local message (api_core.hip)
 
 // ---- the few RCCL symbols this library uses, resolved at run time -----------------------------------------------
 typedef struct { char internal[128]; } NcclUniqueId;

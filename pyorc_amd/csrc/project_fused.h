@@ -1,4 +1,4 @@
-// project_cv with both remaps in one kernel (project.hip; plan: lspiv_api.hip build_remap_fused).  Declared here and not in common.h:
+// project_cv with both remaps in one kernel (project.hip; plan: api_project.hip build_remap_fused).  Declared here and not in common.h:
 // common.h is one of the four sources the PIV kernels' hash is taken over (Makefile KERNEL_SRC), and the committed PIV profiles are keyed to it.
 #pragma once
 #include <hip/hip_runtime.h>

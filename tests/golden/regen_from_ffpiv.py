@@ -143,7 +143,7 @@ def main(argv=None) -> int:
     best = ranked[0]
     print("best reading: " + ", ".join(f"{k}={v}" for k, v in zip(names, best))
           + ("  (= the defaults)" if best == default and score[best][0] == n_cases else
-             "  -> flip piv_oracle.SEMANTICS and the option defaults in pyorc_amd/csrc/lspiv_api.hip"))
+             "  -> flip piv_oracle.SEMANTICS and the option defaults in pyorc_amd/csrc/api_core.hip"))
     if score[best][0] < n_cases:
         print(f"NOTE: no combination matches all {n_cases} cases (best: {score[best][0]}); what is left unexplained is outside the switch set "
               "(eps of the peak fit, FFT normalisation, grid) -- the stage reports below place it.")

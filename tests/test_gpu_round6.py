@@ -234,3 +234,43 @@ def test_borrowed_chunks_stay_pinned_across_a_change_of_the_retention_mode(gpu):
         del junk
         e.close(); ref.close()
         assert e._held == []
+
+
+def test_host_calls_that_fail_after_their_upload_leave_the_library_usable(gpu):
+    """An argument error that only the "_dev" twin sees comes after the host entry point has queued its upload: the call waits for
+    its stream before it returns, a trace span begun for it is dropped, and the next calls on the same workspaces and projection
+    slots give the results they give in a fresh process."""
+    from oracle import filters_oracle as fo
+    from pyorc_amd import _lib, filters
+    from pyorc_amd.project import Projection
+
+    lib = gpu
+    fr = particle_stack(5, 64, 96, seed=3)
+    out = np.empty_like(fr)
+    assert lib.lspiv_normalize(_lib.ptr(fr), 5, 64, 96, 15, _lib.ptr(out)) == _lib.LSPIV_EINVAL
+    assert b"too small to provide 15 samples" in lib.lspiv_last_error()
+    assert lib.lspiv_reduce_rolling(_lib.ptr(fr), 5, 64, 96, 6, _lib.ptr(out)) == _lib.LSPIV_EINVAL
+    fields = np.zeros((4, 2, 8, 9), np.float32)
+    mask = np.empty((2, 8, 9), np.uint8)
+    params = np.zeros(6)
+    assert lib.lspiv_mask(_lib.ptr(fields), 2, 8, 9, 42, _lib.ptr(params), 2, _lib.ptr(mask)) == _lib.LSPIV_EINVAL
+    assert b"unknown mask kind 42" in lib.lspiv_last_error()
+    assert np.array_equal(filters.normalize(fr, 4), fo.normalize(fr, 4))
+    f = (np.random.default_rng(1).standard_normal((3, 40, 50)) * 6).astype(np.float32)
+    assert np.array_equal(filters.minmax(f, -2.0, 3.0), fo.minmax(f, -2.0, 3.0))
+
+    src, dst = (60, 80), (40, 48)
+    plan = Projection(src, dst, *projection_maps(src, dst, seed=2))
+    assert not plan.nearest_only                                         # group means: the uint8 entry point refuses the plan
+    cam = particle_stack(3, src[0], src[1], seed=4)
+    ref = plan.project_frames(cam)
+    u8 = np.empty((3,) + dst, np.uint8)
+    assert lib.lspiv_trace(1) == 0
+    for _ in range(3):                                                    # more calls than projection slots
+        assert lib.lspiv_project_frames_u8(plan._h, _lib.ptr(cam), 3, _lib.ptr(u8)) == _lib.LSPIV_EINVAL
+    assert _trace_read(lib) == []
+    assert np.array_equal(plan.project_frames(cam), ref)
+    spans = _trace_read(lib)
+    assert lib.lspiv_trace(0) == 0
+    assert len(spans) == 1 and spans[0][0] == 1
+    plan.close()

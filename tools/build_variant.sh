@@ -3,7 +3,7 @@
 # patch (-p file, relative to the repo root, `patch -p0` form with paths pyorc_amd/csrc/...) and extra -D flags, builds only the
 # translation units named by UNITS (default: piv_fft32 piv_fft64 -- the rest are taken from the tree's objects), links
 # build/ab/lib_<name>.so.  Load it with LSPIV_LIBRARY=build/ab/lib_<name>.so (exempt from the stale check).
-#   usage: tools/build_variant.sh <name> [-r git-rev] [-p patchfile] [-DFOO=1 ...]      env: UNITS="piv_fft64 lspiv_api"
+#   usage: tools/build_variant.sh <name> [-r git-rev] [-p patchfile] [-DFOO=1 ...]      env: UNITS="piv_fft64 api_piv"
 # -r: the kernel headers (common.h fft_regs.h piv_fft_impl.h) of that revision instead of the tree's.  Only the UNITS are recompiled
 # (the other objects are the tree's, touched so that make leaves them alone).
 set -e
