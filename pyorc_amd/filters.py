@@ -9,6 +9,9 @@ with a real cv2, not bit identity.
 
 from __future__ import annotations
 
+import ctypes as C
+import threading
+
 import numpy as np
 
 from . import _lib
@@ -130,3 +133,115 @@ def smooth(frames, wdw: int = 1) -> np.ndarray:
 def edge_detect(frames, wdw_1: int = 1, wdw_2: int = 2) -> np.ndarray:
     """``Frames.edge_detect``: blur(2 wdw_2 + 1) - blur(2 wdw_1 + 1), float32."""
     return _blur(frames, 2 * int(wdw_1) + 1, 2 * int(wdw_2) + 1)
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------
+# the recipe's frame filters as one chain on the device
+# ---------------------------------------------------------------------------------------------------------------------------------
+CHAIN_OPS = ("normalize", "edge_detect", "minmax", "smooth")
+_CHAIN_LOCK = threading.Lock()   # lspiv_normalize_apply_dev keeps its temporaries in the context's scratch: one caller's launches at a time
+
+
+class Chain:
+    """``Frames`` filter calls ``[(op, params), ...]`` (the reference's names and parameters: ``normalize(samples)``,
+    ``edge_detect(wdw_1, wdw_2)``, ``minmax(min, max)``, ``smooth(wdw)``) as the sequence of ``*_dev`` entry points that computes them
+    on a piece of a uint8 camera stack.  The one place that knows that sequence: ``pipeline.CameraToVelocity`` and the resident stack of
+    ``velocimetry.get_ffpiv`` (``pyorc_amd.resident``) both run it.
+
+    * ``normalize`` first, against a mean plane computed once for the whole stack (:meth:`mean_plane`): ``lspiv_normalize_apply_dev``;
+    * ``edge_detect`` and a ``minmax`` right after it: ONE ``lspiv_edge_detect_clip_dev`` call (the bits of the two);
+    * ``smooth``: ``lspiv_gaussian_blur_dev``;
+    * any other ``minmax`` (on float32 frames): ``lspiv_minmax_dev``, in place.
+
+    At most one Gaussian stage, so a piece needs one uint8 scratch stack (with ``normalize``) and one float32 one (with a Gaussian
+    stage): :attr:`scratch_bytes_per_pixel`."""
+
+    def __init__(self, ops):
+        self.ops = tuple((str(op), dict(p)) for op, p in ops)
+        self.steps = []
+        self.samples = None
+        floats = False
+        for i, (op, p) in enumerate(self.ops):
+            if op == "normalize":
+                if i != 0:
+                    raise ValueError("normalize works on the uint8 camera frames: first in the chain")
+                self.samples = int(p["samples"])
+                self.steps.append(["normalize"])
+            elif op in ("edge_detect", "smooth"):
+                if floats:
+                    raise ValueError("one Gaussian stage per chain")
+                floats = True
+                if op == "edge_detect":
+                    self.steps.append(["edge", 2 * int(p["wdw_1"]) + 1, 2 * int(p["wdw_2"]) + 1, -np.inf, np.inf, False])
+                else:
+                    self.steps.append(["smooth", 2 * int(p["wdw"]) + 1])
+            elif op == "minmax":
+                if not floats:
+                    raise ValueError("minmax in the chain works on float32 frames (after edge_detect or smooth)")
+                lo, hi = float(p["min"]), float(p["max"])
+                last = self.steps[-1]
+                if last[0] == "edge" and not last[5]:
+                    last[3:] = [lo, hi, True]       # rides in the filter's store
+                else:
+                    self.steps.append(["minmax", lo, hi])
+            else:
+                raise ValueError(f"no device chain for Frames.{op}")
+        self.float_out = floats
+
+    @property
+    def names(self):
+        return [op for op, _ in self.ops]
+
+    @property
+    def scratch_bytes_per_pixel(self) -> int:
+        """Bytes per camera pixel a piece occupies in HBM while it runs: the upload, plus the stages' outputs."""
+        return 1 + (1 if self.samples else 0) + (4 if self.float_out else 0)
+
+    def mean_plane(self, sampled) -> DeviceFrames:
+        """The float32 mean plane ``normalize`` removes, from the SAMPLED frames only (``frames[::round(T / samples)]`` of the whole
+        stack, uint8): ``lspiv_normalize_mean_dev`` over that compact stack with every frame sampled -- integer sums, so the bits of
+        the whole-stack mean.  A ``(1, H, W)`` ``DeviceFrames``."""
+        d = sampled if is_device(sampled) else DeviceFrames.from_host(np.ascontiguousarray(sampled, dtype=np.uint8))
+        n, H, W = d.shape
+        mean = DeviceFrames.empty((1, H, W), np.float32)
+        _lib.check(_lib.load().lspiv_normalize_mean_dev(d.c_ptr, n, H, W, n, mean.c_ptr, None))
+        return mean
+
+    def run_dev(self, d_src: int, T: int, H: int, W: int, d_mean=None, d_u8=None, d_f32=None, stream=None):
+        """Device pointers: ``T`` uint8 frames at ``d_src`` through the chain; ``d_u8`` / ``d_f32`` receive the uint8 / float32 stages'
+        outputs (``T * H * W`` samples each; needed with ``normalize`` / a Gaussian stage), ``d_mean`` is :meth:`mean_plane`'s.  Kernels
+        on ``stream`` (None: the library's).  Returns (pointer, dtype) of the chain's output."""
+        lib = _lib.load()
+        vp = lambda p: None if p is None else C.c_void_p(int(p))      # noqa: E731
+        src, dt = int(d_src), np.dtype(np.uint8)
+        s = vp(stream)
+        with _CHAIN_LOCK:
+            for step in self.steps:
+                kind = step[0]
+                if kind == "normalize":
+                    _lib.check(lib.lspiv_normalize_apply_dev(vp(src), T, H, W, vp(d_mean), vp(d_u8), s))
+                    src = int(d_u8)
+                elif kind == "edge":
+                    _lib.check(lib.lspiv_edge_detect_clip_dev(vp(src), _lib.DTYPE_CODES[dt], T, H, W, step[1], step[2], step[3], step[4],
+                                                              vp(d_f32), s))
+                    src, dt = int(d_f32), np.dtype(np.float32)
+                elif kind == "smooth":
+                    _lib.check(lib.lspiv_gaussian_blur_dev(vp(src), _lib.DTYPE_CODES[dt], T, H, W, step[1], vp(d_f32), s))
+                    src, dt = int(d_f32), np.dtype(np.float32)
+                else:
+                    _lib.check(lib.lspiv_minmax_dev(vp(src), T * H * W, step[1], step[2], vp(src), s))
+        return src, dt
+
+    def apply(self, frames: DeviceFrames, mean=None) -> DeviceFrames:
+        """A ``DeviceFrames`` piece of uint8 camera frames through the chain, on the library's stream; scratch from the pool, per call
+        (the resident stack's loader threads stage pieces side by side).  Returns the output stack."""
+        T, H, W = frames.shape
+        if frames.dtype != np.uint8:
+            raise ValueError(f"the chain starts on uint8 camera frames, got {frames.dtype}")
+        if self.samples and mean is None:
+            raise ValueError("normalize needs the stack's mean plane (Chain.mean_plane)")
+        u8 = DeviceFrames.empty(frames.shape, np.uint8) if self.samples else None
+        f32 = DeviceFrames.empty(frames.shape, np.float32) if self.float_out else None
+        self.run_dev(frames.ptr, T, H, W, None if mean is None else mean.ptr, None if u8 is None else u8.ptr,
+                     None if f32 is None else f32.ptr)
+        return f32 if f32 is not None else (u8 if u8 is not None else frames)

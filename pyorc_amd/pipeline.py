@@ -6,7 +6,8 @@ x4..x8 the bytes of the camera stack) -> ``get_piv()`` (window stack x3.9, corre
 ``to_netcdf`` (int16).  ``CameraToVelocity`` keeps everything between the raw uint8 camera frames and the result
 block in HBM and calls only ``*_dev`` entry points of the C ABI:
 
-    H2D uint8 frames -> lspiv_normalize_dev -> lspiv_edge_detect_clip_dev (edge_detect + minmax in one pass)   (each optional)
+    H2D uint8 frames -> lspiv_normalize_mean_dev + _apply_dev -> lspiv_edge_detect_clip_dev (edge_detect + minmax in one pass)
+                        (each optional; the sequence is ``filters.Chain``'s, shared with get_ffpiv's resident stack)
                      -> lspiv_project_frames_dev (lspiv_project_frames_u8_dev: nearest-neighbour-only plan, uint8 in) -> lspiv_piv_pairs_dev
                      -> lspiv_pack_int16_dev (optional) -> D2H (16 B or 8 B per vector)
 
@@ -31,6 +32,7 @@ from typing import Optional
 import numpy as np
 
 from . import _lib, window
+from .filters import Chain
 from .project import Projection
 
 
@@ -72,6 +74,12 @@ class CameraToVelocity:
                                                    float("inf") if minmax[1] is None else float(minmax[1]))
         if self.minmax and not self.edge_detect:   # checked before any buffer exists
             raise ValueError("minmax in the chain follows edge_detect (float32 frames); uint8 frames are not thresholded")
+        ops = [("normalize", {"samples": int(normalize_samples)})] if normalize_samples else []
+        if edge_detect is not None:
+            ops.append(("edge_detect", {"wdw_1": int(edge_detect[0]), "wdw_2": int(edge_detect[1])}))
+            if self.minmax:
+                ops.append(("minmax", {"min": self.minmax[0], "max": self.minmax[1]}))
+        self.chain = Chain(ops)     # the stages before the projection: normalize -> edge_detect + minmax in one pass
         self.n_rows, self.n_cols = window.get_array_shape(self.ortho_shape, self.window_size, self.overlap)
         if self.n_rows < 1 or self.n_cols < 1:
             raise ValueError("ortho frame smaller than the interrogation window")
@@ -111,21 +119,18 @@ class CameraToVelocity:
         n_vec = (T - 1) * self.n_rows * self.n_cols
         d_cam = self._cam.ensure(T * n_cam)
         _lib.check(lib.lspiv_memcpy_h2d(d_cam, _lib.ptr(a), a.nbytes))
-        src = d_cam
+        d_mean = None
         if self.normalize_samples:
-            src = self._norm.ensure(T * n_cam)
-            _lib.check(lib.lspiv_normalize_dev(d_cam, T, self.cam_shape[0], self.cam_shape[1], self.normalize_samples, src, None))
-        src_dtype = np.uint8
-        if self.edge_detect:
-            d_edge = self._edge.ensure(T * n_cam * 4)
-            # the recipe's minmax rides in the filter's store (lspiv_edge_detect_clip_dev: the bits of edge_detect + minmax, one pass)
-            lo, hi = self.minmax if self.minmax else (float("-inf"), float("inf"))
-            _lib.check(lib.lspiv_edge_detect_clip_dev(src, 0, T, self.cam_shape[0], self.cam_shape[1], self.edge_detect[0],
-                                                      self.edge_detect[1], lo, hi, d_edge, None))
-            src, src_dtype = d_edge, np.float32
+            # the mean plane, then the per-frame stretch in the chain: mean + apply is lspiv_normalize_dev bit for bit
+            d_mean = self._mean.ensure(n_cam * 4)
+            _lib.check(lib.lspiv_normalize_mean_dev(d_cam, T, self.cam_shape[0], self.cam_shape[1], self.normalize_samples, d_mean, None))
+        d_norm = self._norm.ensure(T * n_cam) if self.normalize_samples else None
+        d_edge = self._edge.ensure(T * n_cam * 4) if self.edge_detect else None
+        src, src_dtype = self.chain.run_dev(d_cam.value, T, self.cam_shape[0], self.cam_shape[1], d_mean and d_mean.value,
+                                            d_norm and d_norm.value, d_edge and d_edge.value)
         osz = 1 if self.ortho_uint8 else 4
         d_ortho = self._ortho.ensure(T * n_ortho * osz)
-        self.projection.project_frames_dev(src.value, src_dtype, T, d_ortho.value, keep_uint8=self.ortho_uint8)
+        self.projection.project_frames_dev(src, src_dtype, T, d_ortho.value, keep_uint8=self.ortho_uint8)
         d_out = self._out.ensure(4 * n_vec * 4)
         _lib.check(lib.lspiv_piv_pairs_dev(d_ortho, 0 if self.ortho_uint8 else 1, T, self.ortho_shape[0], self.ortho_shape[1], self.window_size[0],
                                            self.window_size[1], self.overlap[0], self.overlap[1], self.signal_threshold,
@@ -207,18 +212,10 @@ class CameraToVelocity:
             f0, f1 = (0 if k == 0 else p0 + 1), p1 + 1      # the frames this chunk brings in; frame p0 came with chunk k-1
             n_new = f1 - f0
             _lib.check(lib.lspiv_memcpy_h2d(at(d_cam, f0 * n_cam), _lib.ptr(a[f0:f1]), n_new * n_cam))   # blocking; chunk k-1 computes meanwhile
-            src, src_dtype, esz = at(d_cam, f0 * n_cam), np.uint8, 1
-            if self.normalize_samples:
-                dst = at(d_norm, f0 * n_cam)
-                _lib.check(lib.lspiv_normalize_apply_dev(src, n_new, Hc, Wc, d_mean, dst, comp))
-                src = dst
-            if self.edge_detect:
-                dst = at(d_edge, f0 * n_cam * 4)
-                lo, hi = self.minmax if self.minmax else (float("-inf"), float("inf"))
-                _lib.check(lib.lspiv_edge_detect_clip_dev(src, 0, n_new, Hc, Wc, self.edge_detect[0], self.edge_detect[1], lo, hi, dst, comp))
-                src, src_dtype, esz = dst, np.float32, 4
+            src, src_dtype = self.chain.run_dev(d_cam.value + f0 * n_cam, n_new, Hc, Wc, d_mean and d_mean.value,
+                                                d_norm and d_norm.value + f0 * n_cam, d_edge and d_edge.value + f0 * n_cam * 4, comp.value)
             osz = 1 if self.ortho_uint8 else 4
-            self.projection.project_frames_dev(src.value, src_dtype, n_new, d_ortho.value + f0 * n_ortho * osz, comp.value,
+            self.projection.project_frames_dev(src, src_dtype, n_new, d_ortho.value + f0 * n_ortho * osz, comp.value,
                                                keep_uint8=self.ortho_uint8)
             blk_out = at(d_out, 4 * p0 * n_win * 4)
             _lib.check(lib.lspiv_piv_pairs_dev_at(at(d_ortho, p0 * n_ortho * osz), 0 if self.ortho_uint8 else 1, p1 - p0 + 1, self.ortho_shape[0],

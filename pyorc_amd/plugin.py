@@ -33,6 +33,13 @@ how pyorc's own service strings the two together (pyorc/service/velocimetry.py:5
 CAMERA chunk is loaded and uploaded, the orthoprojection kernel writes into the HBM-resident stack the PIV kernels read
 (``pyorc_amd.resident``).  ``project_hip`` registers its graph node, :func:`hip_projection_source` recognises it; anything else between
 ``project`` and ``get_piv`` takes the generic path (the blocks run the kernel, the float32 frames come back and go up again).
+
+Fourth seam: the recipe's ``frames:`` section filters the camera frames before ``project`` (``normalize -> edge_detect -> minmax``,
+pyorc's float32 output of cv2 and numpy on the host).  ``install()`` wraps ``Frames.normalize`` / ``edge_detect`` / ``minmax`` /
+``smooth`` (those the installed pyorc has): each calls the original and returns its result unchanged, and records the result's dask
+name with the call's parameters and its source.  When the ``project_hip`` source is such a chain on a uint8 stack,
+:func:`hip_projection_source` says so (``root``, ``ops``), and ``get_ffpiv`` loads the uint8 camera blocks and runs the chain on the
+device (``pyorc_amd.filters.Chain``) before the projection.  Anything it does not recognise keeps the hand-off above.
 """
 
 from __future__ import annotations
@@ -195,6 +202,19 @@ _PASS_NOT = ("invert", "logical_not", "notnull")
 _PASS_NAN = ("isnan", "isnull")
 
 
+# ---- the Frames filters the recipe runs before project (normalize -> edge_detect -> minmax): recorded by result name, so that get_ffpiv
+# can run them on the device between the upload of the raw uint8 camera blocks and the projection -------------------------------------
+_FILTERS: "OrderedDict[str, tuple]" = OrderedDict()     # dask array name of a wrapped filter's result -> (op, params, source DataArray)
+_FILTERS_MAX = 32
+# the wrapped methods, their parameters under the reference's names, with the reference's defaults (pyorc/api/frames.py:279-467)
+FILTER_PARAMS = {
+    "normalize": (("samples", 15),),
+    "edge_detect": (("wdw_1", 1), ("wdw_2", 2)),
+    "minmax": (("min", float("-inf")), ("max", float("inf"))),
+    "smooth": (("wdw", 1),),
+}
+
+
 def _graph_name(obj):
     data = getattr(obj, "data", None)
     name = getattr(data, "name", None)
@@ -209,6 +229,67 @@ def _register_projection(da_proj, source, plan_args, dst_shape, device) -> None:
         _PROJECTIONS[name] = {"source": source, "plan_args": plan_args, "dst_shape": tuple(int(v) for v in dst_shape), "device": device}
         while len(_PROJECTIONS) > _PROJECTIONS_MAX:
             _PROJECTIONS.popitem(last=False)
+
+
+def _filter_params(op, values):
+    """The parameters of one recorded call as the device chain takes them, or None when they are not something it can run (a kernel
+    size outside 1..31, a NaN limit, a sample count below 1): such a result is not recorded and the host computes it."""
+    import math
+
+    try:
+        if op == "minmax":
+            lo, hi = (float(values[k]) for k in ("min", "max"))
+            return None if math.isnan(lo) or math.isnan(hi) else {"min": lo, "max": hi}
+        p = {k: int(values[k]) for k, _ in FILTER_PARAMS[op]}
+    except (TypeError, ValueError, OverflowError):
+        return None
+    if op == "normalize":
+        return p if p["samples"] >= 1 else None
+    sizes = [2 * w + 1 for w in p.values()]
+    if any(not 1 <= k <= 31 for k in sizes) or (op == "edge_detect" and sizes[1] < sizes[0]):
+        return None
+    return p
+
+
+def _register_filter(result, op, params, source) -> None:
+    name, _ = _graph_name(result)
+    if name is None:          # an eager result: nothing lazy to run elsewhere
+        return
+    with _PLANS_LOCK:
+        _FILTERS[name] = (op, params, source)
+        while len(_FILTERS) > _FILTERS_MAX:
+            _FILTERS.popitem(last=False)
+
+
+def _wrap_filter(op, orig):
+    """``Frames.<op>`` that calls the ORIGINAL method and hands its result back unchanged (the same object); a dask-backed result is also
+    recorded with the call's parameters and the accessor's DataArray (``self._obj``), for :func:`hip_projection_source`."""
+    import inspect
+
+    try:
+        sig = inspect.signature(orig)
+    except (TypeError, ValueError):
+        sig = None
+    names = [k for k, _ in FILTER_PARAMS[op]]
+    known = sig is not None and all(k in sig.parameters for k in names)
+
+    @functools.wraps(orig)
+    def method(self, *args, **kwargs):
+        result = orig(self, *args, **kwargs)
+        if known:
+            try:
+                bound = sig.bind(self, *args, **kwargs)
+                bound.apply_defaults()
+                params = _filter_params(op, bound.arguments)
+                source = getattr(self, "_obj", None)
+                if params is not None and source is not None:
+                    _register_filter(result, op, params, source)
+            except Exception:      # recording is an optimisation: whatever goes wrong here, the original's result stands
+                pass
+        return result
+
+    method.__lspiv_original__ = orig
+    return method
 
 
 def _prefix(name: str) -> str:
@@ -244,7 +325,12 @@ def _match_projection(name, graph):
 
 def hip_projection_source(frames) -> Optional[dict]:
     """``{"source", "plan_args", "dst_shape", "device"}`` when ``frames`` is the product of :func:`project_hip` (module docstring, third
-    seam) over a plain ``(time, y, x)`` camera stack of the same length, else None."""
+    seam) over a plain ``(time, y, x)`` camera stack of the same length, else None.
+
+    When that camera stack is itself a chain of recorded filter calls (:func:`install` wraps ``Frames.normalize`` / ``edge_detect`` /
+    ``minmax`` / ``smooth``) on a uint8 stack, the answer also carries ``"root"`` (that uint8 stack: the first one below the chain whose
+    name is not a recorded result) and ``"ops"`` (``[(op, params), ...]`` in the order they apply): ``get_ffpiv`` then loads the root and
+    runs the chain on the device (:func:`filter_chain`)."""
     import numpy as np
 
     name, data = _graph_name(frames)
@@ -257,7 +343,52 @@ def hip_projection_source(frames) -> Optional[dict]:
         src = hit["source"]
         ok = (len(src.shape) == 3 and len(frames.shape) == 3 and len(src) == len(frames) and tuple(frames.shape[1:]) == hit["dst_shape"]
               and np.dtype(frames.dtype) == np.float32)
-        return hit if ok else None
+        if not ok:
+            return None
+    except Exception:
+        return None
+    chain = filter_chain(src)
+    return hit if chain is None else dict(hit, **chain)
+
+
+def filter_chain(stack) -> Optional[dict]:
+    """``{"root", "ops"}`` when ``stack`` is the result of recorded filter calls down to a 3-D uint8 stack of the same shape, with
+    ``normalize`` (if any) first, ``minmax`` only on float32 frames (after ``edge_detect``, ``smooth`` or ``minmax``) and at most one
+    Gaussian stage (one float32 scratch stack per piece); else None.  Every link is an exact recorded name: a layer that was not
+    recorded ends the walk, and becomes the root."""
+    import numpy as np
+
+    ops = []
+    root = stack
+    try:
+        with _PLANS_LOCK:
+            known = dict(_FILTERS)
+        seen = set()
+        while True:
+            name, _ = _graph_name(root)
+            if name is None or name not in known or name in seen:
+                break
+            seen.add(name)
+            op, params, parent = known[name]
+            ops.append((op, dict(params)))
+            root = parent
+        if not ops:
+            return None
+        ops.reverse()
+        if (len(root.shape) != 3 or tuple(root.shape) != tuple(stack.shape) or np.dtype(root.dtype) != np.uint8
+                or tuple(getattr(root, "dims", ("time",)))[:1] != ("time",)):
+            return None
+        float_frames = False
+        for i, (op, _) in enumerate(ops):
+            if op == "normalize" and i != 0:
+                return None
+            if op == "minmax" and not float_frames:
+                return None
+            if op in ("edge_detect", "smooth"):
+                if float_frames:
+                    return None
+                float_frames = True
+        return {"root": root, "ops": ops}
     except Exception:
         return None
 
@@ -345,28 +476,42 @@ def install(pyorc_module=None) -> bool:
             project_mod = None   # somebody else's: leave it
     except ImportError:
         project_mod = None
+    orig_filters = {}
+    for op in FILTER_PARAMS:   # the recipe's frame filters, those this pyorc has: recorded, so that get_ffpiv can run them on the device
+        orig = getattr(frames_cls, op, None)
+        if callable(orig):
+            orig_filters[op] = (orig, op in frames_cls.__dict__)      # (the method, defined on Frames itself rather than inherited)
+            setattr(frames_cls, op, _wrap_filter(op, orig))
     _installed.update(project_mod=project_mod, ffpiv_mod=ffpiv_mod, frames_cls=frames_cls, velo_pkg=velo_pkg, orig_ffpiv=orig_ffpiv,
-                      orig_get_piv=orig_get_piv, reexported=reexported)
+                      orig_get_piv=orig_get_piv, reexported=reexported, orig_filters=orig_filters)
     return True
 
 
 def uninstall() -> None:
-    """Put pyorc's own ``get_ffpiv`` / ``Frames.get_piv`` back; drop the cached projection plans and the registered graph nodes."""
+    """Put pyorc's own ``get_ffpiv`` / ``Frames.get_piv`` / filter methods back; drop the cached projection plans and the registered graph
+    nodes."""
     if not _installed:
         with _PLANS_LOCK:
             _PLANS.clear()
             _PROJECTIONS.clear()
+            _FILTERS.clear()
         _remove_hook()
         return
     _installed["ffpiv_mod"].get_ffpiv = _installed["orig_ffpiv"]
     if _installed["reexported"]:
         _installed["velo_pkg"].get_ffpiv = _installed["orig_ffpiv"]
     _installed["frames_cls"].get_piv = _installed["orig_get_piv"]
+    for op, (orig, own) in _installed.get("orig_filters", {}).items():
+        if own:
+            setattr(_installed["frames_cls"], op, orig)
+        else:
+            delattr(_installed["frames_cls"], op)
     if _installed.get("project_mod") is not None and getattr(_installed["project_mod"], "project_hip", None) is project_hip:
         del _installed["project_mod"].project_hip
     with _PLANS_LOCK:
         _PLANS.clear()
         _PROJECTIONS.clear()
+        _FILTERS.clear()
     _installed.clear()
     _remove_hook()
 

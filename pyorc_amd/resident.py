@@ -16,7 +16,8 @@ different natural sizes:
 So a lazy run keeps the (narrowed) stack resident: :class:`ResidentStack` receives the loaded pieces in time order -- no halo frame is
 loaded, a piece starts where the previous one ended --, uploads each to its place (``lspiv_upload_frames``: exactly the staging of the
 PIV host entry points; or, for the direct product of ``project_hip``, the CAMERA frames, projected into place by the orthoprojection
-kernel: the ortho frames never exist on the host), and launches every pair up to the last anchor that has both its frames.  The bits
+kernel: the ortho frames never exist on the host -- when the recipe's frame filters come before ``project``, the raw uint8 camera frames
+are uploaded and filtered on the device first), and launches every pair up to the last anchor that has both its frames.  The bits
 are those of one launch over the whole stack, hence those of the chunked host path and of the reference's independent windows.
 
 Stacks beyond the HBM budget run as consecutive windows of this kind, cut on the anchors, each re-loading one halo frame.
@@ -92,16 +93,18 @@ class ResidentStack:
     pairs ``[p0, p1)`` have become computable: ``p0`` is where the previous launch ended (``first`` at the start, a multiple of
     ``align`` afterwards), ``p1`` the last multiple of ``align`` below the frames that have arrived -- everything at :meth:`finish`.
     ``projection``: a ``pyorc_amd.project.Projection``; pieces are then CAMERA frames, uploaded to a scratch stack and projected into
-    place (``Projection.project_into``), float32 out like ``project_hip``'s blocks."""
+    place (``Projection.project_into``), float32 out like ``project_hip``'s blocks.  ``chain``: a ``pyorc_amd.filters.Chain`` the
+    camera frames go through between their upload and the projection (the recipe's frame filters; ``mean``: its mean plane)."""
 
     def __init__(self, first: int, capacity: int, frame_shape, host_dtype, align: int, launch: Callable, signal_threshold=None,
-                 projection=None):
+                 projection=None, chain=None, mean=None):
         self.first, self.capacity = int(first), int(capacity)
         self.frame_shape = (int(frame_shape[0]), int(frame_shape[1]))
         self.align = max(1, int(align))
         self._launch = launch
         self.signal_threshold = signal_threshold
         self.projection = projection
+        self.chain, self.mean = chain, mean
         self.dtype = np.dtype(np.float32) if projection is not None else DeviceFrames.device_dtype(host_dtype)
         self.stack = DeviceFrames.empty((self.capacity,) + self.frame_shape, self.dtype)
         self.run_start = self.first     # first frame of the current gap-free run
@@ -128,6 +131,8 @@ class ResidentStack:
             self.stack.upload(f0 - self.first, frames, self.signal_threshold)
         else:
             cam = DeviceFrames.from_host(frames)
+            if self.chain is not None:   # the filters on the library's stream, ahead of the projection; scratch of this call's own
+                cam = self.chain.apply(cam, self.mean)
             self.projection.project_into(cam, self.stack, f0 - self.first)
             del cam      # stream-ordered: the block goes back to the pool, the next upload waits for the library's stream first
         with self._lock:

@@ -12,7 +12,9 @@ Differences, all deliberate and documented in DESIGN.md:
     memory_factor``, ffpiv.py:129; same warning text), divided by the number of loads the chunk executor keeps in flight, cut on dask's
     own block boundaries and WITHOUT the reference's halo frame (no block is decoded + projected twice); the kernels are launched on
     their anchors as the frames arrive.  When the stack is the direct product of ``project_hip`` (``pyorc_amd.plugin``), the CAMERA
-    frames are loaded and projected on the device: ortho frames never exist on the host;
+    frames are loaded and projected on the device: ortho frames never exist on the host -- and when those camera frames are the recipe's
+    filters (``normalize`` / ``edge_detect`` / ``minmax`` / ``smooth``) over a uint8 stack, the uint8 frames are loaded and filtered on
+    the device too;
   * for a materialised stack (numpy, ``DeviceFrames``) the chunk size is planned against free HBM, not host RAM, and rounded down to a multiple of
     ``window.chunk_alignment`` (>= one multiple): chunks then start on the anchors of the time-walking kernels'
     segments, so the result is the same, bit for bit, whatever chunk size the planner or the user picked -- as in the
@@ -394,7 +396,9 @@ def _stack_signal_mode(signal_threshold) -> bool:
 class LazyPlan(dict):
     """What :func:`plan_lazy` decided (a dict, for the tests and ``executor.LAST_STATS``): ``windows`` [(w0, w1)] frame ranges resident at
     a time, ``loads`` per window [(f0, f1)], ``load_frames``, ``host_budget`` / ``host_frame_bytes`` / ``peak_host_bytes``, ``depth`` (None =
-    adaptive) and ``max_depth``, ``align``, ``blocks`` (dask's), ``source`` ("frames" | "camera": the pre-projection stack of project_hip)."""
+    adaptive) and ``max_depth``, ``align``, ``blocks`` (dask's), ``source`` ("frames" | "camera": the pre-projection stack of project_hip),
+    ``chain`` (a ``filters.Chain`` when the camera frames are the recipe's filters over a uint8 stack: that stack is loaded, the filters run
+    on the device) and ``hbm_scratch`` (bytes of HBM next to the resident stack)."""
 
 
 def plan_lazy(frames, n_frames, dim_size, window_size, overlap, n_win, chunksize, memory_factor, engine, prefetch,
@@ -407,12 +411,18 @@ def plan_lazy(frames, n_frames, dim_size, window_size, overlap, n_win, chunksize
       raised and 5 it is (ffpiv.py:131-137); a user ``chunksize`` is honoured as the load size;
     * below that bound, loads are the overlap granule of ``pyorc_amd.resident.load_size`` -- at least ``MIN_LOADS`` of them when the
       stack has that many anchors -- in whole dask blocks;
-    * what is resident at a time is bounded by HBM (``lspiv_available_bytes / memory_factor``): normally everything."""
+    * what is resident at a time is bounded by HBM (``lspiv_available_bytes / memory_factor``): normally everything, less the scratch of
+      the pieces being staged (a filter chain's: ``max_depth + 1`` pieces of its uint8 upload and outputs, and its mean plane)."""
     from . import plugin
 
     align = window.chunk_alignment(window_size, dim_size, overlap)
     handoff = plugin.hip_projection_source(frames)
-    src = frames if handoff is None else handoff["source"]
+    chain = None
+    if handoff is not None and handoff.get("ops"):
+        from .filters import Chain
+
+        chain = Chain(handoff["ops"])
+    src = frames if handoff is None else handoff["root"] if chain is not None else handoff["source"]
     src_shape = tuple(int(v) for v in (src[0].shape if handoff is not None else dim_size))
     host_frame_bytes = int(np.prod(src_shape)) * np.dtype(src.dtype).itemsize
     blocks = resident.time_blocks(src)
@@ -438,6 +448,10 @@ def plan_lazy(frames, n_frames, dim_size, window_size, overlap, n_win, chunksize
     hbm_avail = (window.available_memory() if hbm_available is None else hbm_available) / memory_factor
     per_frame = int(np.prod(dim_size)) * dev_itemsize + 16 * n_win
     scratch = load_frames * host_frame_bytes if handoff is not None else 0
+    if chain is not None:
+        # every loader thread stages a piece at a time: its upload and the chain's outputs, + the mean plane
+        cam_pixels = int(np.prod(src_shape))
+        scratch = (deepest + 1) * load_frames * chain.scratch_bytes_per_pixel * cam_pixels + (4 * cam_pixels if chain.samples else 0)
     frames_per_window = max(align + 1, int((hbm_avail - scratch) // per_frame))
     frames_per_window = min(frames_per_window, max(2, MAX_WINDOWS_PER_LAUNCH // max(n_win, 1)))
     windows = resident.hbm_windows(n_frames, frames_per_window, align, blocks)
@@ -445,7 +459,7 @@ def plan_lazy(frames, n_frames, dim_size, window_size, overlap, n_win, chunksize
     biggest = max((b - a for ls in loads for a, b in ls), default=0)
     return LazyPlan(windows=windows, loads=loads, load_frames=load_frames, align=align, blocks=blocks, depth=depth, max_depth=deepest,
                     host_budget=host_budget, host_frame_bytes=host_frame_bytes, peak_host_bytes=(deepest + 1) * biggest * host_frame_bytes,
-                    source="frames" if handoff is None else "camera", handoff=handoff)
+                    source="frames" if handoff is None else "camera", handoff=handoff, chain=chain, hbm_scratch=scratch)
 
 
 def _get_ffpiv_lazy(frames, plan, y, x, dt, time, res_y, res_x, n_cols, n_rows, window_size, overlap, ensemble_corr,
@@ -457,9 +471,20 @@ def _get_ffpiv_lazy(frames, plan, y, x, dt, time, res_y, res_x, n_cols, n_rows, 
     n_total = len(frames) - 1
     n_win = n_rows * n_cols
     dim_size = tuple(int(v) for v in frames[0].shape)
-    handoff = plan["handoff"]
-    lazy = frames if handoff is None else handoff["source"]
+    handoff, chain, mean = plan["handoff"], plan.get("chain"), None
+    lazy = frames if handoff is None else handoff["root"] if chain is not None else handoff["source"]
     projection = None if handoff is None else plugin.projection_for(handoff)
+    mean_s = 0.0
+    if chain is not None and chain.samples:
+        # normalize's mean plane, from the sampled camera frames only (frames.py:296-299), loaded and uploaded once for the run
+        import time as _time
+
+        t0 = _time.perf_counter()
+        iv = round(len(lazy) / chain.samples)
+        if iv == 0:
+            raise AssertionError(f"Amount of frames is too small to provide {chain.samples} samples")
+        mean = chain.mean_plane(np.ascontiguousarray(_values(load_frame_chunk(lazy[::iv]))))
+        mean_s = _time.perf_counter() - t0
     names = ("s2n", "corr", "v_x", "v_y")
     done = []
     ens = None
@@ -492,9 +517,13 @@ def _get_ffpiv_lazy(frames, plan, y, x, dt, time, res_y, res_x, n_cols, n_rows, 
     stats = {"plan": {k: plan[k] for k in ("windows", "load_frames", "align", "depth", "max_depth", "source", "peak_host_bytes", "host_budget")},
              "load_s": 0.0, "waited_s": 0.0, "upload_s": 0.0, "launch_s": 0.0, "chunks": 0, "depth_per_chunk": [], "load_s_per_chunk": [],
              "waited_s_per_chunk": []}
+    if chain is not None:
+        stats["plan"]["chain"] = chain.names
+        stats["mean_s"] = mean_s       # sampled frames loaded, uploaded, mean plane computed
     try:
         for (w0, w1), loads in zip(plan["windows"], plan["loads"]):
-            stack = resident.ResidentStack(w0, w1 - w0, dim_size, frames.dtype, plan["align"], launch, signal_threshold, projection)
+            stack = resident.ResidentStack(w0, w1 - w0, dim_size, frames.dtype, plan["align"], launch, signal_threshold, projection,
+                                           chain, mean)
             pieces = [(f0, lazy[f0:f1]) for f0, f1 in loads]
 
             def load_and_stage(piece, stack=stack):
