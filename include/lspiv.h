@@ -279,6 +279,14 @@ int lspiv_ensemble_finish_partials(lspiv_ensemble* handle, const double* partial
                                    float* corr_mean);
 int lspiv_ensemble_export(lspiv_ensemble* handle, float* corr_sum, float* corr_count);
 int lspiv_ensemble_import(lspiv_ensemble* handle, const float* corr_sum, const float* corr_count, int add);
+/* corr_sum / corr_count of n handles (same geometry, any devices; n <= 64) summed in handle order, ((s0 + s1) + s2) + ..., and
+ * written back to EVERY handle as its replaced state -- what an all-reduce followed by lspiv_ensemble_import(add = 0) on each handle
+ * leaves, bit for bit (adds only, one float32 rounding each: a float32 sum in the same order matches).  The sum runs on handles[0]'s
+ * device; other devices' buffers are read over the fabric where peer access is possible, else copied there first; the total goes back
+ * with peer copies.  Every handle is marked as holding a foreign state, so the staged finish below (flag / partials / finish_partials)
+ * keeps the float64 rescue.  Waits for every handle's accumulations; takes the host locks of the devices involved in ascending order;
+ * the calling thread's device is unchanged afterwards. */
+int lspiv_ensemble_allreduce(lspiv_ensemble** handles, int n);
 int lspiv_ensemble_destroy(lspiv_ensemble* handle);
 
 /* ---------------------------------------------------------------- next rows */

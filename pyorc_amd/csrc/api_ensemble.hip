@@ -115,6 +115,94 @@ static void ensemble_wait_accumulated(lspiv_ensemble* h, hipStream_t reader) {
     if (e.stream != reader && hipStreamWaitEvent(reader, e.ev, 0) != hipSuccess) { (void)hipGetLastError(); (void)hipStreamSynchronize(e.stream); }
 }
 
+// ---- lspiv_ensemble_allreduce: corr_sum / corr_count of several handles summed on the first handle's device ----------------------
+constexpr int kAllreduceMax = 64;
+struct AllreduceSrc { const float* p[kAllreduceMax]; };
+// out[i] = ((src0[i] + src1[i]) + src2[i]) + ...: adds only, one rounding each, in handle order (numpy's float32 sum in that order)
+__global__ __launch_bounds__(256) void ensemble_allreduce_kernel(AllreduceSrc src, int n, int64_t count, float* out) {
+  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < count; i += (int64_t)gridDim.x * 256) {
+    float acc = src.p[0][i];
+    for (int k = 1; k < n; ++k) acc = __fadd_rn(acc, src.p[k][i]);
+    out[i] = acc;
+  }
+}
+static int launch_allreduce(const AllreduceSrc& src, int n, int64_t count, float* out, hipStream_t s) {
+  if (count <= 0) return LSPIV_OK;
+  const int64_t blocks = std::min<int64_t>((count + 255) / 256, 65536);
+  hipLaunchKernelGGL(ensemble_allreduce_kernel, dim3((unsigned)blocks), dim3(256), 0, s, src, n, count, out);
+  return launch_status(hipGetLastError(), "allreduce kernel launch failed");
+}
+// peer access from `dev` to `peer`, enabled once per ordered pair for the process (the caller has `dev` current)
+static bool peer_reachable(int dev, int peer) {
+  static std::mutex mu;
+  static signed char state[kMaxDevices][kMaxDevices];   // 0 unknown, 1 enabled, -1 not possible
+  if (dev == peer) return true;
+  if (dev < 0 || peer < 0 || dev >= kMaxDevices || peer >= kMaxDevices) return false;
+  std::lock_guard<std::mutex> lk(mu);
+  if (state[dev][peer] == 0) {
+    int can = 0;
+    if (hipDeviceCanAccessPeer(&can, dev, peer) != hipSuccess) { (void)hipGetLastError(); can = 0; }
+    if (can) {
+      const hipError_t e = hipDeviceEnablePeerAccess(peer, 0);
+      if (e != hipSuccess && e != hipErrorPeerAccessAlreadyEnabled) can = 0;
+      (void)hipGetLastError();
+    }
+    state[dev][peer] = can ? 1 : -1;
+  }
+  return state[dev][peer] == 1;
+}
+// the state sum itself, with the devices' host locks held and handles[0]'s device current
+static int ensemble_allreduce_locked(lspiv_ensemble** handles, int n) {
+  lspiv_ensemble* root = handles[0];
+  const int rd = root->device;
+  DeviceCtx* c;
+  LSPIV_TRY(get_ctx(&c));
+  const size_t n_win = (size_t)root->g.n_rows * root->g.n_cols, np = n_win * root->wy * root->wx;
+  // every handle's accumulations have been issued on its device's streams: the root's stream waits for the local ones, the host for
+  // the remote ones (an event of another device is not waited for by a stream)
+  for (int k = 0; k < n; ++k) {
+    if (handles[k]->device == rd) ensemble_wait_accumulated(handles[k], c->stream);
+    else for (auto& e : handles[k]->acc_events) HIP_TRY(hipEventSynchronize(e.ev));
+  }
+  AllreduceSrc ss{}, sc{};
+  std::vector<void*> staging;
+  int rc = LSPIV_OK;
+  for (int k = 0; k < n && rc == LSPIV_OK; ++k) {
+    lspiv_ensemble* h = handles[k];
+    if (h->device == rd || peer_reachable(rd, h->device)) { ss.p[k] = h->d_sum; sc.p[k] = h->d_count; continue; }
+    void* p = nullptr;
+    if (hipMalloc(&p, (np + n_win) * sizeof(float)) != hipSuccess) { (void)hipGetLastError(); rc = fail(LSPIV_ENOMEM, "hipMalloc allreduce staging"); break; }
+    staging.push_back(p);
+    float* f = (float*)p;
+    if (hipMemcpyPeerAsync(f, rd, h->d_sum, h->device, np * sizeof(float), c->stream) != hipSuccess ||
+        hipMemcpyPeerAsync(f + np, rd, h->d_count, h->device, n_win * sizeof(float), c->stream) != hipSuccess) {
+      rc = fail(LSPIV_EHIP, "hipMemcpyPeerAsync: %s", hipGetErrorString(hipGetLastError()));
+      break;
+    }
+    ss.p[k] = f; sc.p[k] = f + np;
+  }
+  // in place on the root handle: element i is read from every source before it is written, by the same thread
+  if (rc == LSPIV_OK) rc = launch_allreduce(ss, n, (int64_t)np, root->d_sum, c->stream);
+  if (rc == LSPIV_OK) rc = launch_allreduce(sc, n, (int64_t)n_win, root->d_count, c->stream);
+  for (int k = 1; k < n && rc == LSPIV_OK; ++k) {
+    lspiv_ensemble* h = handles[k];
+    if (h == root) continue;
+    hipError_t e1, e2;
+    if (h->device == rd) {
+      e1 = hipMemcpyAsync(h->d_sum, root->d_sum, np * sizeof(float), hipMemcpyDeviceToDevice, c->stream);
+      e2 = hipMemcpyAsync(h->d_count, root->d_count, n_win * sizeof(float), hipMemcpyDeviceToDevice, c->stream);
+    } else {
+      e1 = hipMemcpyPeerAsync(h->d_sum, h->device, root->d_sum, rd, np * sizeof(float), c->stream);
+      e2 = hipMemcpyPeerAsync(h->d_count, h->device, root->d_count, rd, n_win * sizeof(float), c->stream);
+    }
+    if (e1 != hipSuccess || e2 != hipSuccess) rc = fail(LSPIV_EHIP, "allreduce copy back: %s", hipGetErrorString(hipGetLastError()));
+  }
+  const hipError_t se = hipStreamSynchronize(c->stream);   // also before the staging buffers go
+  for (void* p : staging) (void)hipFree(p);
+  if (rc == LSPIV_OK && se != hipSuccess) rc = fail(LSPIV_EHIP, "allreduce: %s", hipGetErrorString(se));
+  return rc;
+}
+
 extern "C" {
 
 // ---- ensemble -------------------------------------------------------------------------------
@@ -492,6 +580,37 @@ int lspiv_ensemble_import(lspiv_ensemble* h, const float* corr_sum, const float*
   for (size_t i = 0; i < np; ++i) s[i] += corr_sum[i];
   for (size_t i = 0; i < n_win; ++i) k[i] += corr_count[i];
   return lspiv_ensemble_import(h, s.data(), k.data(), 0);
+}
+
+int lspiv_ensemble_allreduce(lspiv_ensemble** handles, int n) {
+  if (!handles || n < 1) return fail(LSPIV_EINVAL, "need at least one handle");
+  if (n > kAllreduceMax) return fail(LSPIV_EINVAL, "at most %d handles, got %d", kAllreduceMax, n);
+  std::vector<int> devs;
+  for (int k = 0; k < n; ++k) {
+    const lspiv_ensemble* h = handles[k];
+    if (!h) return fail(LSPIV_EINVAL, "handle %d is NULL", k);
+    const lspiv_ensemble* r = handles[0];
+    if (h->H != r->H || h->W != r->W || h->wy != r->wy || h->wx != r->wx || h->oy != r->oy || h->ox != r->ox)
+      return fail(LSPIV_ESHAPE, "handle %d has another geometry than handle 0", k);
+    if (h->device < 0 || h->device >= kMaxDevices) return fail(LSPIV_EINVAL, "handle %d: device %d out of range", k, h->device);
+    devs.push_back(h->device);
+  }
+  std::sort(devs.begin(), devs.end());
+  devs.erase(std::unique(devs.begin(), devs.end()), devs.end());
+  int prev = 0;
+  HIP_TRY(hipGetDevice(&prev));
+  int rc = LSPIV_OK;
+  {
+    // the host locks of every device involved, in ascending device order (two callers cannot hold one each and wait for the other)
+    std::vector<std::unique_lock<std::mutex>> held;
+    for (int d : devs) held.emplace_back(g_locks[d].host);
+    if (hipSetDevice(handles[0]->device) != hipSuccess) rc = fail(LSPIV_EHIP, "hipSetDevice(%d): %s", handles[0]->device, hipGetErrorString(hipGetLastError()));
+    if (rc == LSPIV_OK) rc = ensemble_allreduce_locked(handles, n);
+    // the sums now hold pairs whose frames each handle never saw: what lspiv_ensemble_import(add = 0) records (the staged finish)
+    if (rc == LSPIV_OK) for (int k = 0; k < n; ++k) handles[k]->foreign = true;
+  }
+  (void)hipSetDevice(prev);
+  return rc;
 }
 
 int lspiv_ensemble_destroy(lspiv_ensemble* h) {

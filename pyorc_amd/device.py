@@ -38,7 +38,7 @@ class _Pool:
         import threading
 
         self.limit = int(os.environ.get("LSPIV_POOL_BYTES", 16 << 30))
-        self.free = {}      # bucket size -> [raw pointer values]
+        self.free = {}      # (device, bucket size) -> [raw pointer values]: a block is handed out again on its own device only
         self.cached = 0
         self._lock = threading.RLock()   # stacks are made and dropped on several threads (the chunk executor's loaders stage their pieces)
 
@@ -48,25 +48,33 @@ class _Pool:
         step = 1 << max(n.bit_length() - 4, 8)      # 1/8 .. 1/16 of the size: <= 12.5 % of slack
         return (n + step - 1) // step * step
 
+    @staticmethod
+    def device() -> int:
+        d = C.c_int(0)
+        _lib.check(_lib.load().lspiv_get_device(C.byref(d)))
+        return int(d.value)
+
     def take(self, nbytes: int):
         b = self.bucket(nbytes)
+        dev = self.device()
         with self._lock:
-            lst = self.free.get(b)
+            lst = self.free.get((dev, b))
             if lst:
                 self.cached -= b
-                return C.c_void_p(lst.pop()), b
+                return C.c_void_p(lst.pop()), (dev, b)
         p = C.c_void_p()
         rc = _lib.load().lspiv_dev_malloc(C.byref(p), b)
         if rc == _lib.LSPIV_ENOMEM and self.cached:   # give the cache back and retry once
             self.release()
             rc = _lib.load().lspiv_dev_malloc(C.byref(p), b)
         _lib.check(rc)
-        return p, b
+        return p, (dev, b)
 
-    def give(self, ptr: C.c_void_p, b: int):
+    def give(self, ptr: C.c_void_p, key):
+        b = key[1]
         with self._lock:
             if self.cached + b <= self.limit:
-                self.free.setdefault(b, []).append(ptr.value)
+                self.free.setdefault(key, []).append(ptr.value)
                 self.cached += b
                 return
         _lib.load().lspiv_dev_free(ptr)
@@ -96,6 +104,7 @@ class _Allocation:
     def __init__(self, nbytes: int):
         _lib.require_device()
         self.ptr, self._bucket = _pool.take(nbytes)
+        self.device = self._bucket[0]
         self.nbytes = int(nbytes)
 
     def __del__(self):
@@ -156,6 +165,11 @@ class DeviceFrames:
         return n
 
     # ---- array-like surface ------------------------------------------------------------------
+    @property
+    def device(self) -> int:
+        """The HIP device this stack lives on."""
+        return self._alloc.device
+
     @property
     def ptr(self) -> int:
         return self._alloc.ptr.value + self._offset

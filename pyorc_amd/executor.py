@@ -34,6 +34,8 @@ import time as _time
 from concurrent.futures import Future, ThreadPoolExecutor
 from typing import Callable, Iterator, List, Optional, Sequence, Tuple
 
+import numpy as np
+
 DEFAULT_DEPTH = 1          # the depth an adaptive run starts from
 DEFAULT_WORKERS = 1
 DEFAULT_MAX_DEPTH = 4
@@ -99,6 +101,94 @@ def bind_device(device: Optional[int]) -> None:
     from . import _lib
 
     _lib.check(_lib.load().lspiv_set_device(int(device)))
+
+
+def resolve_devices(devices, count: int) -> Optional[List[int]]:
+    """The ``devices`` keyword of ``get_ffpiv``: None (the calling thread's device, as before) -> None; ``"all"`` -> ``[0, count)``; a
+    sequence of device indices -> that list (repeats allowed: ``[0, 0]`` is two workers on device 0).  ``count``: what
+    ``lspiv_device_count`` reports.  ValueError for an empty list, an index outside ``[0, count)`` or a non-integer."""
+    if devices is None:
+        return None
+    if isinstance(devices, str):
+        if devices != "all":
+            raise ValueError(f'devices must be None, "all" or a sequence of device indices, got {devices!r}')
+        if count < 1:
+            raise ValueError("devices='all': no device visible")
+        return list(range(count))
+    try:
+        seq = list(devices)
+    except TypeError:
+        raise ValueError(f'devices must be None, "all" or a sequence of device indices, got {devices!r}') from None
+    if not seq:
+        raise ValueError("devices: empty list")
+    out = []
+    for d in seq:
+        if isinstance(d, bool) or not isinstance(d, (int, np.integer)):
+            raise ValueError(f"devices: {d!r} is not a device index")
+        if not 0 <= int(d) < count:
+            raise ValueError(f"devices: index {int(d)} outside [0, {count})")
+        out.append(int(d))
+    return out
+
+
+class on_device:
+    """``with on_device(d):`` the calling thread works on device ``d`` and gets its own device back afterwards (None: no change)."""
+
+    def __init__(self, device: Optional[int]):
+        self.device, self._prev = device, None
+
+    def __enter__(self):
+        if self.device is not None:
+            self._prev = current_device()
+            bind_device(self.device)
+        return self
+
+    def __exit__(self, *exc):
+        if self.device is not None and self._prev is not None:
+            bind_device(self._prev)
+
+
+class Stopped(Exception):
+    """Raised inside a device worker whose group has already failed: it stops loading and launching."""
+
+
+def run_on_devices(devices: Optional[Sequence[int]], work: Callable) -> list:
+    """``[work(k, stop) for k, device in enumerate(devices)]``, each on its own thread bound to its device (``bind_device``).
+
+    ``devices`` None: ``work(0, stop)`` on the calling thread, on its device -- one device is the case D = 1 of the same code.
+    ``stop`` is a ``threading.Event`` the workers poll between loads and launches (``stop_point(stop)``): the first exception of any
+    worker sets it, every thread is joined, and that exception is raised to the caller -- no partial result, no thread left running."""
+    stop = threading.Event()
+    if devices is None:
+        return [work(0, stop)]
+    results: list = [None] * len(devices)
+    errors: list = []
+
+    def run(k: int, device: int) -> None:
+        try:
+            bind_device(device)
+            results[k] = work(k, stop)
+        except BaseException as e:      # noqa: BLE001 -- handed to the caller
+            if not isinstance(e, Stopped):
+                errors.append((_time.perf_counter(), k, e))
+            stop.set()
+
+    threads = [threading.Thread(target=run, args=(k, d), name=f"lspiv-dev{k}", daemon=True) for k, d in enumerate(devices)]
+    for t in threads:
+        t.start()
+    for t in threads:
+        t.join()
+    if errors:
+        raise min(errors, key=lambda e: e[0])[2]
+    if stop.is_set():
+        raise RuntimeError("a device worker stopped without an error")
+    return results
+
+
+def stop_point(stop: Optional[threading.Event]) -> None:
+    """Raise :class:`Stopped` when another device worker of the group has failed."""
+    if stop is not None and stop.is_set():
+        raise Stopped()
 
 
 class ChunkPrefetcher:

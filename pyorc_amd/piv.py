@@ -166,6 +166,9 @@ class Ensemble:
         self.n_rows, self.n_cols = window.get_array_shape(dim_size, window_size, overlap)
         _lib.check(lib.lspiv_ensemble_begin(dim_size[0], dim_size[1], window_size[0], window_size[1],
                                             overlap[0], overlap[1], C.byref(self._h)))
+        d = C.c_int(0)
+        _lib.check(lib.lspiv_get_device(C.byref(d)))
+        self.device = int(d.value)   # the handle's sums live here; every call on it is made with this device current
         self._held = []   # DeviceFrames chunks the handle borrows until finish (float64 rescue of the final fit)
         self._retain_mode = None   # set_retain not called yet: accumulate() of a DeviceFrames chunk picks RETAIN_BORROW
 
@@ -314,3 +317,14 @@ class Ensemble:
             self.close()
         except Exception:
             pass
+
+
+def ensemble_allreduce(ensembles) -> None:
+    """Sum the states of several :class:`Ensemble` handles (same geometry, any devices) in list order on the first one's device and
+    leave the total in every handle, marked as a foreign state (``lspiv_ensemble_allreduce``): bit for bit what ``export_state`` of
+    each, a float32 sum in list order and ``import_state`` of the total on each would leave, without the host round trip."""
+    hs = [e._h for e in ensembles]
+    if not hs or any(not h for h in hs):
+        raise ValueError("ensemble_allreduce needs open Ensemble handles")
+    arr = (C.c_void_p * len(hs))(*[h.value for h in hs])
+    _lib.check(_lib.load().lspiv_ensemble_allreduce(arr, len(hs)))

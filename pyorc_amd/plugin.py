@@ -393,10 +393,13 @@ def filter_chain(stack) -> Optional[dict]:
         return None
 
 
-def projection_for(handoff: dict):
-    """The device-resident :class:`pyorc_amd.project.Projection` of a recognised ``project_hip`` node (shared with its dask blocks)."""
+def projection_for(handoff: dict, device=-1):
+    """The device-resident :class:`pyorc_amd.project.Projection` of a recognised ``project_hip`` node (shared with its dask blocks).
+    ``device``: the device of the worker that projects (default: the one the graph was built for); the plan is made and kept per
+    device -- call this with that device current."""
     src = handoff["source"]
-    return _projection_plan(tuple(int(v) for v in src.shape[-2:]), handoff["dst_shape"], handoff["plan_args"], handoff["device"])
+    dev = handoff["device"] if device == -1 else device
+    return _projection_plan(tuple(int(v) for v in src.shape[-2:]), handoff["dst_shape"], handoff["plan_args"], dev)
 
 
 def project_hip(da, cc, x, y, z, reducer="mean"):

@@ -130,32 +130,63 @@ def sharded_ensemble(load_frames: Callable[[int, int], np.ndarray], n_pairs: int
     s = comm.allreduce(s, SUM)
     k = comm.allreduce(k, SUM)
     ens.import_state(s, k)
-    # every rank now holds the same sums.  The float64 rescue of the ill-conditioned fits needs the frames of every pair: each
-    # rank contributes the float64 sums over ITS retained block for the (identical, sorted) list of flagged windows -- one more
-    # float64 all-reduce of a few hundred bytes (include/lspiv.h, lspiv_ensemble_flag / _partials / _finish_partials)
-    if hasattr(ens, "flag"):
-        n_rec = ens.flag(count_min, n_chunks)
-        part, ok = ens.partials()
-        # one small MAX all-reduce settles both questions for everybody: did every rank keep its frames, and do all ranks hold the
-        # same list (they do -- identical sums after the all-reduce --; a rank that disagreed would make the next exchange hang)
-        # -- the same LIST, not only the same length: the partials are summed positionally, so the digest of the sorted records
-        # (window, candidates) rides along as two exact 32-bit halves, each with its negative (MAX of x and of -x agree <=> all equal)
-        dg = ens.flag_digest() if hasattr(ens, "flag_digest") else 0
-        hi, lo = float(dg >> 32), float(dg & 0xFFFFFFFF)
-        agreed = comm.allreduce(np.array([0.0 if ok else 1.0, float(n_rec), -float(n_rec), hi, -hi, lo, -lo], dtype=np.float64), MAX)
-        all_ok = agreed[0] == 0.0 and agreed[1] == -agreed[2] and agreed[3] == -agreed[4] and agreed[5] == -agreed[6]
-        if all_ok:
-            if n_rec:
-                part = comm.allreduce(part, SUM)
-            u, v, cnt = ens.finish_partials(part)
-        else:      # some rank could not keep its frames (or the lists differ): float32 fits everywhere (the ranks agree)
-            u, v, cnt = ens.finish(count_min, n_chunks)
-    else:
-        u, v, cnt = ens.finish(count_min, n_chunks)
+    u, v, cnt = staged_finish([ens], count_min, n_chunks, comm)
     n_win = k.size
     local = np.stack([cm, sn]).astype(np.float32)[:, :, None, :] if cm is not None else np.empty((2, 0, 1, n_win), np.float32)
     per_pair = gather_blocks(local, n_pairs, comm, align)  # (2, n_pairs, 1, n_win)
     return u, v, cnt, per_pair[0, :, 0], per_pair[1, :, 0]
+
+
+class _Alone:
+    """The communicator of a single process: every all-reduce returns its input."""
+    rank, world = 0, 1
+
+    @staticmethod
+    def allreduce(arr, op=SUM):
+        return arr
+
+
+def staged_finish(handles, count_min: float, n_chunks: float, comm=None):
+    """The finish of an ensemble whose sum is spread over several handles that all hold the same (all-reduced) state: the float64
+    rescue of the ill-conditioned fits reaches every pair, each handle contributing the float64 sums over ITS retained chunks
+    (include/lspiv.h, lspiv_ensemble_flag / _partials / _finish_partials).  ``handles``: this process's handles, in device order (one
+    per rank in ``sharded_ensemble``; one per device worker in ``velocimetry.get_ffpiv(devices=...)``), each called with its own device
+    current; ``comm``: the ranks' communicator (None: this process alone).  Returns (u, v, corr_count) of ``handles[0]``'s finish."""
+    from .executor import on_device
+
+    comm = _Alone() if comm is None else comm
+    ens = handles[0]
+    if not all(hasattr(h, "flag") for h in handles):
+        with on_device(getattr(ens, "device", None)):
+            return ens.finish(count_min, n_chunks)
+    flags, parts = [], []
+    for h in handles:
+        with on_device(getattr(h, "device", None)):
+            n_rec = h.flag(count_min, n_chunks)
+            part, ok = h.partials()
+            dg = h.flag_digest() if hasattr(h, "flag_digest") else 0
+        hi, lo = float(dg >> 32), float(dg & 0xFFFFFFFF)
+        # did every handle keep its frames, and do all hold the same LIST (the partials are summed positionally): the digest of the
+        # sorted records (window, candidates) as two exact 32-bit halves, each with its negative (MAX of x and of -x agree <=> all equal)
+        flags.append(np.array([0.0 if ok else 1.0, float(n_rec), -float(n_rec), hi, -hi, lo, -lo], dtype=np.float64))
+        parts.append(part)
+    agreed = flags[0]
+    for f in flags[1:]:
+        agreed = np.maximum(agreed, f)
+    # one small MAX all-reduce settles both questions for every rank (a rank that disagreed would make the next exchange hang)
+    agreed = comm.allreduce(agreed, MAX)
+    all_ok = agreed[0] == 0.0 and agreed[1] == -agreed[2] and agreed[3] == -agreed[4] and agreed[5] == -agreed[6]
+    with on_device(getattr(ens, "device", None)):
+        if all_ok:
+            n_rec = int(agreed[1])
+            part = parts[0]
+            for p in parts[1:]:     # in handle (= device) order
+                part = part + p
+            if n_rec:
+                part = comm.allreduce(part, SUM)
+            return ens.finish_partials(part)
+        # some handle could not keep its frames (or the lists differ): float32 fits everywhere (the handles agree)
+        return ens.finish(count_min, n_chunks)
 
 
 class ShardedPivDev:

@@ -30,6 +30,7 @@ on plain ``(T, H, W)`` numpy arrays (returns ``PivResult``, a dict with the same
 
 from __future__ import annotations
 
+import math
 import warnings
 from typing import Literal, Optional, Tuple
 
@@ -173,6 +174,7 @@ def get_ffpiv(
     signal_threshold: Optional[float] = None,
     time: Optional[np.ndarray] = None,
     prefetch: Optional[int] = None,
+    devices=None,
 ):
     """Compute time-resolved (or ensemble) PIV on the MI355X; signature of pyorc's ``get_ffpiv`` (ffpiv.py:24-42).
 
@@ -186,6 +188,12 @@ def get_ffpiv(
     AHEAD of the chunk being launched, on a worker thread (``pyorc_amd.executor``; default ``LSPIV_PREFETCH_DEPTH`` or 1; 0 = the
     reference's serial load-then-compute loop, ffpiv.py:399-408).  Same chunks, same order, same results; stacks that are already
     materialised (numpy, ``DeviceFrames``) have nothing to prefetch.
+
+    ``devices``: None (the calling thread's device: one worker, as always), ``"all"`` (every device ``lspiv_device_count`` reports) or
+    a sequence of device indices (repeats allowed: ``[0, 0]`` is two workers on device 0).  Each device works on one thread of its
+    own over a contiguous block of pairs cut on the kernels' anchors (:func:`device_work`), so per-timestep results are the bits of
+    one device; ensemble sums are reduced device to device (``piv.ensemble_allreduce``) and finished with the float64 rescue of
+    every device's pairs (``shard.staged_finish``).  A ``DeviceFrames`` stack runs on the device it lives on.
     """
     if engine != "hip":
         raise ValueError(f"Selected PIV engine {engine} does not exist.")
@@ -211,20 +219,149 @@ def get_ffpiv(
     dt_arr = np.asarray(_values(dt), dtype=np.float64)
     if dt_arr.shape != (n_frames - 1,):
         raise ValueError(f"dt must have one entry per frame pair ({n_frames - 1}), got shape {dt_arr.shape}")
+    devs = _resolve_frames_devices(frames, devices)
+    align = window.chunk_alignment(window_size, dim_size, overlap)
     if _is_lazy(frames) and n_frames >= 2 and not _stack_signal_mode(signal_threshold):
         # a lazy stack: resident in HBM, loads planned against HOST memory and cut where dask cuts, launches on the anchors
-        plan = plan_lazy(frames, n_frames, dim_size, window_size, overlap, n_rows * n_cols, user_chunksize, memory_factor, engine, prefetch)
-        return _get_ffpiv_lazy(frames, plan, y, x, dt_arr, time, res_y, res_x, n_cols, n_rows, window_size, overlap, ensemble_corr,
-                               corr_min, s2n_min, count_min, signal_threshold, ref_slices)
-    frames_chunks = [frames[a:b] for a, b in slices]
+        plans = plan_lazy_devices(frames, n_frames, dim_size, window_size, overlap, n_rows * n_cols, user_chunksize, memory_factor,
+                                  engine, prefetch, devs)
+        return _get_ffpiv_lazy(frames, plans, y, x, dt_arr, time, res_y, res_x, n_cols, n_rows, window_size, overlap, ensemble_corr,
+                               corr_min, s2n_min, count_min, signal_threshold, ref_slices, devs)
+
+    def device_budget(device, count):   # HBM budget of one worker on `device` (`count` workers share it)
+        with executor.on_device(device):
+            return window.available_memory() / memory_factor / count
+
+    work = device_work(n_frames, slices, devs, align, _stack_signal_mode(signal_threshold),
+                       lambda a, b, d, cnt: _device_slices(b - a + 1, dim_size, window_size, overlap, search_area_size, dtype, user_chunksize,
+                                                           device_budget(d, cnt), engine, n_rows * n_cols, align))
     depth = (executor.default_depth() if prefetch is None else int(prefetch)) if hasattr(frames, "load") else 0
-    args = (frames_chunks, slices, y, x, dt_arr, time, res_y, res_x, n_cols, n_rows, window_size, overlap)
+    args = (frames, work, y, x, dt_arr, time, res_y, res_x, n_cols, n_rows, window_size, overlap)
     if ensemble_corr:
         # quirk Q3 (ffpiv.py:373): the count filter is scaled with the number of CHUNKS -- of the reference's planner
         # (same formula, fed with HBM figures), not of the aligned chunks actually launched
         return _get_ffpiv_mean(*args, corr_min, s2n_min, count_min, signal_threshold, like=frames,
-                               ref_slices=ref_slices, prefetch=depth)
-    return _get_ffpiv_timestep(*args, signal_threshold, like=frames, prefetch=depth)
+                               ref_slices=ref_slices, prefetch=depth, devices=devs)
+    return _get_ffpiv_timestep(*args, signal_threshold, like=frames, prefetch=depth, devices=devs)
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------
+# several devices from one process: who computes which pairs
+# ---------------------------------------------------------------------------------------------------------------------------------
+def _resolve_frames_devices(frames, devices):
+    """``devices`` of :func:`get_ffpiv` -> None or a list of device indices, checked before any GPU work.  A ``DeviceFrames`` stack
+    lives on one device: ``"all"`` runs it there, a list may only name that device (its workers would share one HBM stack and gain
+    nothing: it runs as one worker)."""
+    if devices is None:
+        return None
+    from . import _lib
+
+    devs = executor.resolve_devices(devices, _lib.device_count())
+    if is_device(frames):
+        home = frames.device
+        if not isinstance(devices, str) and any(d != home for d in devs):
+            raise ValueError(f"devices={list(devs)}: the DeviceFrames stack lives on device {home}")
+        return [home]
+    return devs
+
+
+def device_work(n_frames: int, slices, devices, align: int, whole_chunks: bool, plan_block):
+    """Per device worker, the frame slices ``[(a, b), ...]`` it launches (pair ``p`` = frames ``p, p + 1``; consecutive slices share
+    one frame, as in :func:`aligned_slices`).
+
+    * ``devices`` None: one worker with ``slices`` (the single-device plan) -- what ``get_ffpiv`` has always run;
+    * ``whole_chunks`` (the "stack" reading of ``signal_threshold``, whose statistic depends on the chunk cut): the chunks of the
+      single-device plan, dealt out as contiguous runs balanced to within one chunk (``shard.pair_block`` over the chunk list) -- the
+      bits cannot move; workers beyond the number of chunks stay idle;
+    * otherwise D contiguous pair blocks on the anchors (``shard.pair_block`` with ``align``: balanced to within one anchor); the
+      block ``[a, b)`` of worker ``k`` is cut into chunks by ``plan_block(a, b, device, workers on that device)`` (frame slices
+      relative to ``a``, planned against that device's memory) -- every chunk still starts on an anchor.  Workers beyond the number
+      of anchors stay idle."""
+    from . import shard
+
+    if devices is None:
+        return [list(slices)]
+    D = len(devices)
+    if whole_chunks:
+        return [list(slices[i0:i1]) for i0, i1 in (shard.pair_block(len(slices), k, D) for k in range(D))]
+    n_pairs = n_frames - 1
+    out = []
+    for k, d in enumerate(devices):
+        a, b = shard.pair_block(n_pairs, k, D, align)
+        out.append([(a + s0, a + s1) for s0, s1 in plan_block(a, b, d, devices.count(d))] if b > a else [])
+    return out
+
+
+def _device_slices(n_block_frames, dim_size, window_size, overlap, search_area_size, dtype, chunksize, avail_mem, engine, n_win, align):
+    """The chunk plan of :func:`get_ffpiv` for one device's block of ``n_block_frames`` frames against that device's ``avail_mem``."""
+    req = window.required_memory(n_frames=n_block_frames, dim_size=dim_size, window_size=window_size, overlap=overlap,
+                                 search_area_size=search_area_size, dtype=dtype)
+    cs, _ = plan_chunks(n_block_frames, req, avail_mem, chunksize, engine, n_win=n_win)
+
+    def fits(n_chunk_frames: int) -> bool:
+        return window.required_memory(n_frames=n_chunk_frames, dim_size=dim_size, window_size=window_size, overlap=overlap,
+                                      search_area_size=search_area_size, dtype=dtype) <= avail_mem
+
+    return aligned_slices(n_block_frames, cs, align, n_win=n_win, fits=fits)
+
+
+def _merge_stats(per_device, devices) -> dict:
+    """``executor.LAST_STATS`` of a run: the keys of one worker's statistics (times and chunk counts summed, per-chunk lists in pair
+    order, depths maxed), plus ``devices`` and ``per_device`` (each worker's own statistics, in worker order)."""
+    active = [st for st in per_device if st]
+    if len(per_device) == 1:
+        out = dict(per_device[0] or {})
+    else:
+        out = {}
+        for st in active:
+            for key, v in st.items():
+                if key == "plan" or key == "ensemble":
+                    continue
+                if isinstance(v, bool):
+                    out[key] = out.get(key, False) or v
+                elif key in ("depth", "max_depth"):
+                    out[key] = max(out.get(key, 0), v)
+                elif isinstance(v, (int, float)):
+                    out[key] = out.get(key, 0) + v
+                elif isinstance(v, list):
+                    out[key] = out.get(key, []) + list(v)
+        plans = [st["plan"] for st in active if "plan" in st]
+        if plans:
+            plan = dict(plans[0])
+            plan["windows"] = [w for pl in plans for w in pl["windows"]]
+            for key in ("peak_host_bytes", "host_budget"):
+                plan[key] = sum(pl[key] for pl in plans)
+            plan["load_frames"] = max(pl["load_frames"] for pl in plans)
+            out["plan"] = plan
+            # the halo frame of every block after the first is loaded by both neighbours
+            out["boundary_frames"] = max(0, len(plans) - 1)
+    out["devices"] = None if devices is None else list(devices)
+    out["per_device"] = [dict(st) if st else {} for st in per_device]
+    out["idle_devices"] = sum(1 for st in per_device if not st)
+    return {k: (round(v, 6) if isinstance(v, float) else v) for k, v in out.items()}
+
+
+def _finish_ensembles(handles, count_min, n_chunks):
+    """u, v, corr_count of the ensemble summed over ``handles`` (one per device worker that had pairs, in pair order): one handle
+    finishes as it always has; several are reduced device to device and finished with every device's float64 rescue."""
+    from . import shard
+
+    if len(handles) == 1:
+        with executor.on_device(getattr(handles[0], "device", None)):
+            return handles[0].finish(count_min, n_chunks)
+    with executor.on_device(getattr(handles[0], "device", None)):
+        piv.ensemble_allreduce(handles)
+    return shard.staged_finish(handles, count_min, n_chunks)
+
+
+def _close_ensembles(handles, stats=None):
+    for k, h in enumerate(handles):
+        if h is None:
+            continue
+        with executor.on_device(getattr(h, "device", None)):
+            if stats is not None and stats[k] is not None:
+                stats[k]["ensemble"] = h.stats() if hasattr(h, "stats") else {}
+            h.close()
 
 
 def _to_velocity(disp: np.ndarray, res, dt_chunk: np.ndarray, out: Optional[np.ndarray] = None) -> np.ndarray:
@@ -238,59 +375,75 @@ def _to_velocity(disp: np.ndarray, res, dt_chunk: np.ndarray, out: Optional[np.n
     return out
 
 
-def _get_ffpiv_timestep(frames_chunks, slices, y, x, dt, time, res_y, res_x, n_cols, n_rows, window_size, overlap,
-                        signal_threshold, like=None, prefetch=0):
+def _get_ffpiv_timestep(frames, work, y, x, dt, time, res_y, res_x, n_cols, n_rows, window_size, overlap,
+                        signal_threshold, like=None, prefetch=0, devices=None):
     """Per-chunk loop of pyorc/velocimetry/ffpiv.py:379-443 (one fused GPU call per chunk); chunk n + 1 is loaded on a worker
-    thread while chunk n is launched (``pyorc_amd.executor.ChunkPrefetcher``; ``prefetch = 0``: the reference's serial order)."""
+    thread while chunk n is launched (``pyorc_amd.executor.ChunkPrefetcher``; ``prefetch = 0``: the reference's serial order).
+    ``work``: the chunk slices of every device worker (:func:`device_work`), each worker loops over its own on its own device."""
     # the four result variables of the WHOLE run are allocated once and every chunk's launch writes its time slice of them (corr, s2n
     # straight from the library, v_x / v_y through the px -> m/s scaling): no per-chunk arrays to concatenate at the end (the
     # reference's xr.concat, ffpiv.py:442 -- 125 KB per pair, i.e. as many bytes again as a uint8 chunk's upload at 32 x 32)
-    n_total = slices[-1][1] - 1 if slices else 0
+    n_total = max((sl[-1][1] - 1 for sl in work if sl), default=0)
     names = ("s2n", "corr", "v_x", "v_y")
-    full = None            # name -> (n_total, n_rows, n_cols) float32
-    px = None              # scratch for a chunk's u, v in pixels
-    done = []              # (first pair, one past the last pair) of every chunk that delivered
-    times = []
+    full = {k: np.empty((n_total, n_rows, n_cols), dtype=np.float32) for k in names}
     on_device = piv.device_scaling_is_numpys(res_x, res_y)
-    loader = executor.ChunkPrefetcher(frames_chunks, load_frame_chunk, depth=prefetch)
+    per_device = [None] * len(work)
+
+    def run(k, stop):
+        slices = work[k]
+        if not slices:
+            return [], []
+        frames_chunks = [frames[a:b] for a, b in slices]
+        px = None              # scratch for a chunk's u, v in pixels
+        done = []              # (first pair, one past the last pair) of every chunk that delivered
+        times = []
+        loader = executor.ChunkPrefetcher(frames_chunks, load_frame_chunk, depth=prefetch)
+        try:
+            for n, da in loader:
+                executor.stop_point(stop)
+                a, b = slices[n]
+                if len(da) >= 2:  # we need at least one image-pair to do PIV
+                    nb = a + len(da)  # load_frame_chunk may have dropped trailing frames
+                    p = nb - 1 - a
+                    vals = _values(da)
+                    grid = window.get_array_shape(tuple(vals.shape[1:]), window_size, overlap)
+                    if tuple(grid) != (n_rows, n_cols):
+                        raise ValueError(f"grid {tuple(grid)} does not match coordinates ({n_rows}, {n_cols})")
+                    dt_chunk = dt[a:nb - 1]  # dt.sel(time=da.time[1:]), ffpiv.py:403-404
+                    if on_device:
+                        # u and v to meter per second on the device, before they cross PCIe: the arithmetic of ffpiv.py:418-419 for
+                        # python-float resolutions (float32 product, float64 division, float32 storage)
+                        piv.piv_pairs(vals, window_size, overlap, signal_threshold, pair_offset=a, scale=(res_x, res_y, dt_chunk),
+                                      out=(full["v_x"][a:a + p], full["v_y"][a:a + p], full["corr"][a:a + p], full["s2n"][a:a + p]))
+                    else:
+                        if px is None or px[0].shape[0] < p:
+                            px = [np.empty((p, n_rows, n_cols), dtype=np.float32) for _ in range(2)]
+                        u, v = px[0][:p], px[1][:p]
+                        piv.piv_pairs(vals, window_size, overlap, signal_threshold, pair_offset=a,
+                                      out=(u, v, full["corr"][a:a + p], full["s2n"][a:a + p]))
+                        # ... on the host with numpy's own arithmetic for any other kind of resolution (a numpy float64 scalar makes the product float64)
+                        _to_velocity(u, res_x, dt_chunk[:, None, None], out=full["v_x"][a:a + p])
+                        _to_velocity(v, res_y, dt_chunk[:, None, None], out=full["v_y"][a:a + p])
+                    done.append((a, a + p))
+                    times.append(time[a + 1:nb])
+                # remove chunk safely from memory.  (The reference follows this with gc.collect() to get rid of its window stack and
+                # correlation volume, ffpiv.py:437-440; neither exists here, and a collection costs ~1 ms per chunk: dropped.)
+                frames_chunks[n] = None
+                del da
+        finally:
+            # also when a launch raises in the loop body: the worker threads stop loading the next chunks NOW, not when the traceback is
+            # collected (ADVICE r05), and the statistics of what ran are kept
+            loader.close()
+            per_device[k] = loader.stats
+        return done, times
+
     try:
-        for n, da in loader:
-            a, b = slices[n]
-            if len(da) >= 2:  # we need at least one image-pair to do PIV
-                nb = a + len(da)  # load_frame_chunk may have dropped trailing frames
-                p = nb - 1 - a
-                vals = _values(da)
-                grid = window.get_array_shape(tuple(vals.shape[1:]), window_size, overlap)
-                if tuple(grid) != (n_rows, n_cols):
-                    raise ValueError(f"grid {tuple(grid)} does not match coordinates ({n_rows}, {n_cols})")
-                if full is None:
-                    full = {k: np.empty((n_total, n_rows, n_cols), dtype=np.float32) for k in names}
-                dt_chunk = dt[a:nb - 1]  # dt.sel(time=da.time[1:]), ffpiv.py:403-404
-                if on_device:
-                    # u and v to meter per second on the device, before they cross PCIe: the arithmetic of ffpiv.py:418-419 for
-                    # python-float resolutions (float32 product, float64 division, float32 storage)
-                    piv.piv_pairs(vals, window_size, overlap, signal_threshold, pair_offset=a, scale=(res_x, res_y, dt_chunk),
-                                  out=(full["v_x"][a:a + p], full["v_y"][a:a + p], full["corr"][a:a + p], full["s2n"][a:a + p]))
-                else:
-                    if px is None or px[0].shape[0] < p:
-                        px = [np.empty((p, n_rows, n_cols), dtype=np.float32) for _ in range(2)]
-                    u, v = px[0][:p], px[1][:p]
-                    piv.piv_pairs(vals, window_size, overlap, signal_threshold, pair_offset=a,
-                                  out=(u, v, full["corr"][a:a + p], full["s2n"][a:a + p]))
-                    # ... on the host with numpy's own arithmetic for any other kind of resolution (a numpy float64 scalar makes the product float64)
-                    _to_velocity(u, res_x, dt_chunk[:, None, None], out=full["v_x"][a:a + p])
-                    _to_velocity(v, res_y, dt_chunk[:, None, None], out=full["v_y"][a:a + p])
-                done.append((a, a + p))
-                times.append(time[a + 1:nb])
-            # remove chunk safely from memory.  (The reference follows this with gc.collect() to get rid of its window stack and
-            # correlation volume, ffpiv.py:437-440; neither exists here, and a collection costs ~1 ms per chunk: dropped.)
-            frames_chunks[n] = None
-            del da
+        results = executor.run_on_devices(devices, run)
     finally:
-        # also when a launch raises in the loop body: the worker threads stop loading the next chunks NOW, not when the traceback is
-        # collected (ADVICE r05), and the statistics of what ran are kept
-        loader.close()
-        executor.LAST_STATS.clear(); executor.LAST_STATS.update(loader.stats)
+        # written once, by the calling thread (the device workers only fill their own entry)
+        executor.LAST_STATS.clear(); executor.LAST_STATS.update(_merge_stats(per_device, devices))
+    done = [d for r in results for d in r[0]]
+    times = [t for r in results for t in r[1]]
     if not done:
         raise ValueError("no chunk with at least one frame pair")
     if done[0][0] == 0 and done[-1][1] == n_total and all(x[1] == y[0] for x, y in zip(done, done[1:])):
@@ -304,50 +457,64 @@ def _get_ffpiv_timestep(frames_chunks, slices, y, x, dt, time, res_y, res_x, n_c
     return _dataset(data, t, y, x, like)
 
 
-def _get_ffpiv_mean(frames_chunks, slices, y, x, dt, time, res_y, res_x, n_cols, n_rows, window_size, overlap,
-                    corr_min, s2n_min, count_min, signal_threshold, like=None, ref_slices=None, prefetch=0):
+def _get_ffpiv_mean(frames, work, y, x, dt, time, res_y, res_x, n_cols, n_rows, window_size, overlap,
+                    corr_min, s2n_min, count_min, signal_threshold, like=None, ref_slices=None, prefetch=0, devices=None):
     """Ensemble correlation of pyorc/velocimetry/ffpiv.py:182-376; corr_sum / corr_count stay in HBM; chunks loaded ahead of
-    their launches like in ``_get_ffpiv_timestep`` (the reference's loop: ffpiv.py:348-370)."""
-    dim_size = None
-    ens = None
+    their launches like in ``_get_ffpiv_timestep`` (the reference's loop: ffpiv.py:348-370).  Every device worker accumulates its
+    chunks into a handle of its own; the handles are reduced and finished together (:func:`_finish_ensembles`)."""
     # the masked per-pair corr_max / s2n of the whole run: allocated once, every chunk writes its time slice (Ensemble.accumulate(out=))
-    n_total = slices[-1][1] - 1 if slices else 0
+    n_total = max((sl[-1][1] - 1 for sl in work if sl), default=0)
     n_win = n_rows * n_cols
-    full = None
-    done = []
-    t_first = None
-    loader = executor.ChunkPrefetcher(frames_chunks, load_frame_chunk, depth=prefetch)
+    full = (np.empty((n_total, n_win), dtype=np.float32), np.empty((n_total, n_win), dtype=np.float32))
+    handles = [None] * len(work)
+    per_device = [None] * len(work)
+
+    def run(k, stop):
+        slices = work[k]
+        if not slices:
+            return [], None
+        frames_chunks = [frames[a:b] for a, b in slices]
+        done = []
+        t_first = None
+        loader = executor.ChunkPrefetcher(frames_chunks, load_frame_chunk, depth=prefetch)
+        try:
+            for n, da in loader:
+                executor.stop_point(stop)
+                a, b = slices[n]
+                if len(da) < 2:
+                    continue
+                arr = _values(da)
+                p = len(da) - 1
+                if handles[k] is None:
+                    handles[k] = piv.Ensemble(tuple(arr.shape[1:]), window_size, overlap)
+                handles[k].accumulate(arr, corr_min, s2n_min, signal_threshold, out=(full[0][a:a + p], full[1][a:a + p]))
+                done.append((a, a + p))
+                t_first = time[a + 1:a + 2]
+                frames_chunks[n] = None
+                del da
+        finally:
+            loader.close()
+            per_device[k] = loader.stats
+        return done, t_first
+
     try:
-        for n, da in loader:
-            a, b = slices[n]
-            if len(da) < 2:
-                continue
-            arr = _values(da)
-            p = len(da) - 1
-            if ens is None:
-                dim_size = tuple(arr.shape[1:])
-                ens = piv.Ensemble(dim_size, window_size, overlap)
-                full = (np.empty((n_total, n_win), dtype=np.float32), np.empty((n_total, n_win), dtype=np.float32))
-            ens.accumulate(arr, corr_min, s2n_min, signal_threshold, out=(full[0][a:a + p], full[1][a:a + p]))
-            done.append((a, a + p))
-            t_first = time[a + 1:a + 2]
-            frames_chunks[n] = None
-            del da
-        if ens is None:
+        results = executor.run_on_devices(devices, run)
+        done = [d for r in results for d in r[0]]
+        live = [h for h in handles if h is not None]
+        if not live:
             raise ValueError("no chunk with at least one frame pair")
         # quirk Q3: `n_frames` is the number of CHUNKS, not pairs (ffpiv.py:373), and `time[0:1]` of the LAST chunk ends
         # up on the result (ffpiv.py:336) -- both taken from the reference's own chunk plan, not from the aligned
-        # chunks that were launched, so neither depends on the segment anchoring
+        # chunks that were launched, so neither depends on the segment anchoring or on the number of devices
         n_frames = len(done)
+        t_first = [r[1] for r in results if r[1] is not None][-1]
         if ref_slices:
             n_frames = len(ref_slices)
             t_first = time[ref_slices[-1][0] + 1:ref_slices[-1][0] + 2]
-        u, v, corr_count = ens.finish(count_min, n_frames)
+        u, v, corr_count = _finish_ensembles(live, count_min, n_frames)
     finally:
-        loader.close()
-        if ens is not None:
-            ens.close()
-    executor.LAST_STATS.clear(); executor.LAST_STATS.update(loader.stats)
+        _close_ensembles(handles, per_device)
+        executor.LAST_STATS.clear(); executor.LAST_STATS.update(_merge_stats(per_device, devices))
     if done[0][0] == 0 and done[-1][1] == n_total and all(x[1] == y[0] for x, y in zip(done, done[1:])):
         corr_max_concat, s2n_concat = full
     else:   # a chunk lost trailing frames (load_frame_chunk's TypeError retry) or was skipped
@@ -402,7 +569,7 @@ class LazyPlan(dict):
 
 
 def plan_lazy(frames, n_frames, dim_size, window_size, overlap, n_win, chunksize, memory_factor, engine, prefetch,
-              host_available=None, hbm_available=None) -> LazyPlan:
+              host_available=None, hbm_available=None, first=0, stop=None, host_share=1) -> LazyPlan:
     """How a lazy stack runs.  The reference's planner (ffpiv.py:119-139) with its own quantities where they still mean something:
 
     * what a load materialises is bounded by the HOST: ``available_memory() / memory_factor`` (ffpiv.py:129) divided by the loads the
@@ -412,7 +579,10 @@ def plan_lazy(frames, n_frames, dim_size, window_size, overlap, n_win, chunksize
     * below that bound, loads are the overlap granule of ``pyorc_amd.resident.load_size`` -- at least ``MIN_LOADS`` of them when the
       stack has that many anchors -- in whole dask blocks;
     * what is resident at a time is bounded by HBM (``lspiv_available_bytes / memory_factor``): normally everything, less the scratch of
-      the pieces being staged (a filter chain's: ``max_depth + 1`` pieces of its uint8 upload and outputs, and its mean plane)."""
+      the pieces being staged (a filter chain's: ``max_depth + 1`` pieces of its uint8 upload and outputs, and its mean plane).
+
+    ``first`` / ``stop``: the frame range of ONE device's block (:func:`plan_lazy_devices`; ``first`` on an anchor), ``host_share``: how
+    many devices' loaders share the host budget -- each gets that fraction of it and of ``max_depth`` (at least one load ahead)."""
     from . import plugin
 
     align = window.chunk_alignment(window_size, dim_size, overlap)
@@ -428,17 +598,23 @@ def plan_lazy(frames, n_frames, dim_size, window_size, overlap, n_win, chunksize
     blocks = resident.time_blocks(src)
     if prefetch is None and executor.adaptive_by_default():
         depth, deepest = None, executor.max_depth()
+        if host_share > 1:
+            deepest = max(1, deepest // host_share)
     else:
         depth = executor.default_depth() if prefetch is None else int(prefetch)
+        if host_share > 1 and depth > 0:
+            depth = max(1, depth // host_share)
         deepest = depth
+    stop = n_frames if stop is None else int(stop)
+    first = int(first)
     host_avail = window.available_host_memory() if host_available is None else host_available
-    host_budget = host_avail / memory_factor
+    host_budget = host_avail / memory_factor / max(1, host_share)
     if chunksize is None:
         host_frames = int(host_budget // ((deepest + 1) * host_frame_bytes))
         if host_frames <= 5:
             warnings.warn(CHUNK_SIZE_WARNING.format(avail_mem=host_budget / 1e9, chunksize=host_frames, engine=engine), stacklevel=4)
             host_frames = 5  # hard override, try to manage with 5
-        load_frames = resident.load_size(n_frames, align, host_frames, blocks)
+        load_frames = resident.load_size(stop - first, align, host_frames, blocks)
     else:
         load_frames = int(chunksize)
         if load_frames < 2:
@@ -454,7 +630,7 @@ def plan_lazy(frames, n_frames, dim_size, window_size, overlap, n_win, chunksize
         scratch = (deepest + 1) * load_frames * chain.scratch_bytes_per_pixel * cam_pixels + (4 * cam_pixels if chain.samples else 0)
     frames_per_window = max(align + 1, int((hbm_avail - scratch) // per_frame))
     frames_per_window = min(frames_per_window, max(2, MAX_WINDOWS_PER_LAUNCH // max(n_win, 1)))
-    windows = resident.hbm_windows(n_frames, frames_per_window, align, blocks)
+    windows = [(first + w0, first + w1) for w0, w1 in resident.hbm_windows(stop - first, frames_per_window, align, blocks)]
     loads = [resident.plan_loads(w1, load_frames, blocks, first=w0) for w0, w1 in windows]
     biggest = max((b - a for ls in loads for a, b in ls), default=0)
     return LazyPlan(windows=windows, loads=loads, load_frames=load_frames, align=align, blocks=blocks, depth=depth, max_depth=deepest,
@@ -462,77 +638,146 @@ def plan_lazy(frames, n_frames, dim_size, window_size, overlap, n_win, chunksize
                     source="frames" if handoff is None else "camera", handoff=handoff, chain=chain, hbm_scratch=scratch)
 
 
-def _get_ffpiv_lazy(frames, plan, y, x, dt, time, res_y, res_x, n_cols, n_rows, window_size, overlap, ensemble_corr,
-                    corr_min, s2n_min, count_min, signal_threshold, ref_slices):
+def lazy_unit(align: int, blocks, n_frames: int, n_devices: int) -> int:
+    """The unit the device blocks of a lazy stack are cut in: whole anchors, and whole dask blocks as well (their common multiple)
+    when the blocks are regular and the stack still has a unit for every device; else whole anchors."""
+    if not blocks or len(blocks) <= 2:
+        return align
+    lens = np.diff(blocks)[:-1]           # the last block may be short
+    typical = int(lens[0]) if len(lens) else 0
+    if typical <= 0 or any(int(v) != typical for v in lens):
+        return align
+    both = align * typical // math.gcd(align, typical)
+    return both if -(-(n_frames - 1) // both) >= n_devices else align
+
+
+def plan_lazy_devices(frames, n_frames, dim_size, window_size, overlap, n_win, chunksize, memory_factor, engine, prefetch, devices,
+                      host_available=None, hbm_available=None):
+    """One :func:`plan_lazy` per device worker (``[plan]`` for ``devices`` None: the single-device run).  Worker ``k`` gets the frames of
+    pair block ``shard.frame_block(n_pairs, k, D, unit)`` (:func:`lazy_unit`: anchors, and dask's blocks where possible; its halo frame
+    is the first frame of the next block: loaded by both), a 1/D share of the host budget and of the loads in flight, and a plan of
+    its own against the HBM of its device (shared by the workers on that device).  A worker without pairs gets None.
+    ``host_available`` / ``hbm_available``: figures for the tests (per device: a callable of the device index, or a number)."""
+    from . import plugin, shard
+
+    if devices is None:
+        return [plan_lazy(frames, n_frames, dim_size, window_size, overlap, n_win, chunksize, memory_factor, engine, prefetch,
+                          host_available=host_available, hbm_available=hbm_available)]
+    D = len(devices)
+    align = window.chunk_alignment(window_size, dim_size, overlap)
+    handoff = plugin.hip_projection_source(frames)
+    src = frames if handoff is None else handoff.get("root", handoff["source"]) if handoff.get("ops") else handoff["source"]
+    unit = lazy_unit(align, resident.time_blocks(src), n_frames, D)
+    host = window.available_host_memory() if host_available is None else host_available
+    plans = []
+    for k, d in enumerate(devices):
+        f0, f1 = shard.frame_block(n_frames - 1, k, D, unit)
+        if f1 - f0 < 2:
+            plans.append(None)
+            continue
+        if hbm_available is None:
+            with executor.on_device(d):
+                hbm = window.available_memory()
+        else:
+            hbm = hbm_available(d) if callable(hbm_available) else hbm_available
+        plans.append(plan_lazy(frames, n_frames, dim_size, window_size, overlap, n_win, chunksize, memory_factor, engine, prefetch,
+                               host_available=host, hbm_available=hbm / devices.count(d), first=f0, stop=f1, host_share=D))
+    return plans
+
+
+def _get_ffpiv_lazy(frames, plans, y, x, dt, time, res_y, res_x, n_cols, n_rows, window_size, overlap, ensemble_corr,
+                    corr_min, s2n_min, count_min, signal_threshold, ref_slices, devices=None):
     """The loops of pyorc/velocimetry/ffpiv.py:348-370 and :399-440 over a lazy stack: pieces are loaded ahead (``ChunkPrefetcher``),
-    pushed into an HBM-resident stack (``ResidentStack``) and launched on the anchors; results land in the run's arrays."""
+    pushed into an HBM-resident stack (``ResidentStack``) and launched on the anchors; results land in the run's arrays.  ``plans``:
+    one :class:`LazyPlan` per device worker (:func:`plan_lazy_devices`); every worker runs its own windows on its own device."""
     from . import plugin
 
     n_total = len(frames) - 1
     n_win = n_rows * n_cols
     dim_size = tuple(int(v) for v in frames[0].shape)
-    handoff, chain, mean = plan["handoff"], plan.get("chain"), None
+    first = next(pl for pl in plans if pl is not None)
+    handoff, chain = first["handoff"], first.get("chain")
     lazy = frames if handoff is None else handoff["root"] if chain is not None else handoff["source"]
-    projection = None if handoff is None else plugin.projection_for(handoff)
+    mean, mean_host = None, None
     mean_s = 0.0
     if chain is not None and chain.samples:
-        # normalize's mean plane, from the sampled camera frames only (frames.py:296-299), loaded and uploaded once for the run
+        # normalize's mean plane, from the sampled camera frames only (frames.py:296-299), loaded once for the run and computed on the
+        # first device; the other devices get a copy of the same plane (the same bits in every device's filters)
         import time as _time
 
         t0 = _time.perf_counter()
         iv = round(len(lazy) / chain.samples)
         if iv == 0:
             raise AssertionError(f"Amount of frames is too small to provide {chain.samples} samples")
-        mean = chain.mean_plane(np.ascontiguousarray(_values(load_frame_chunk(lazy[::iv]))))
+        with executor.on_device(None if devices is None else devices[0]):
+            mean = chain.mean_plane(np.ascontiguousarray(_values(load_frame_chunk(lazy[::iv]))))
+            if devices is not None and any(d != devices[0] for d in devices):
+                mean_host = mean.to_host()
         mean_s = _time.perf_counter() - t0
     names = ("s2n", "corr", "v_x", "v_y")
-    done = []
-    ens = None
     on_device = piv.device_scaling_is_numpys(res_x, res_y)
     if ensemble_corr:
-        ens = piv.Ensemble(dim_size, window_size, overlap)
         full = (np.empty((n_total, n_win), dtype=np.float32), np.empty((n_total, n_win), dtype=np.float32))
-
-        def launch(view, p0, p1):
-            ens.accumulate(view, corr_min, s2n_min, signal_threshold, out=(full[0][p0:p1], full[1][p0:p1]))
-            done.append((p0, p1))
     else:
         full = {k: np.empty((n_total, n_rows, n_cols), dtype=np.float32) for k in names}
-        px = []
+    handles = [None] * len(plans)
+    per_device = [None] * len(plans)
 
-        def launch(view, p0, p1):
-            p = p1 - p0
-            if on_device:
-                piv.piv_pairs(view, window_size, overlap, signal_threshold, pair_offset=p0, scale=(res_x, res_y, dt[p0:p1]),
-                              out=(full["v_x"][p0:p1], full["v_y"][p0:p1], full["corr"][p0:p1], full["s2n"][p0:p1]))
-            else:
-                if not px or px[0].shape[0] < p:
-                    px[:] = [np.empty((p, n_rows, n_cols), dtype=np.float32) for _ in range(2)]
-                u, v = px[0][:p], px[1][:p]
-                piv.piv_pairs(view, window_size, overlap, signal_threshold, pair_offset=p0, out=(u, v, full["corr"][p0:p1], full["s2n"][p0:p1]))
-                _to_velocity(u, res_x, dt[p0:p1, None, None], out=full["v_x"][p0:p1])
-                _to_velocity(v, res_y, dt[p0:p1, None, None], out=full["v_y"][p0:p1])
-            done.append((p0, p1))
+    def run(k, stop):
+        plan = plans[k]
+        if plan is None:
+            return []
+        done = []
+        device = None if devices is None else devices[k]
+        chain_k = plan.get("chain")
+        mean_k = mean if (mean_host is None or device == devices[0]) else resident.DeviceFrames.from_host(mean_host)
+        projection = None if handoff is None else plugin.projection_for(handoff) if devices is None else plugin.projection_for(handoff, device)
+        if ensemble_corr:
+            ens = handles[k] = piv.Ensemble(dim_size, window_size, overlap)
 
-    stats = {"plan": {k: plan[k] for k in ("windows", "load_frames", "align", "depth", "max_depth", "source", "peak_host_bytes", "host_budget")},
-             "load_s": 0.0, "waited_s": 0.0, "upload_s": 0.0, "launch_s": 0.0, "chunks": 0, "depth_per_chunk": [], "load_s_per_chunk": [],
-             "waited_s_per_chunk": []}
-    if chain is not None:
-        stats["plan"]["chain"] = chain.names
-        stats["mean_s"] = mean_s       # sampled frames loaded, uploaded, mean plane computed
-    try:
+            def launch(view, p0, p1):
+                executor.stop_point(stop)
+                ens.accumulate(view, corr_min, s2n_min, signal_threshold, out=(full[0][p0:p1], full[1][p0:p1]))
+                done.append((p0, p1))
+        else:
+            px = []
+
+            def launch(view, p0, p1):
+                executor.stop_point(stop)
+                p = p1 - p0
+                if on_device:
+                    piv.piv_pairs(view, window_size, overlap, signal_threshold, pair_offset=p0, scale=(res_x, res_y, dt[p0:p1]),
+                                  out=(full["v_x"][p0:p1], full["v_y"][p0:p1], full["corr"][p0:p1], full["s2n"][p0:p1]))
+                else:
+                    if not px or px[0].shape[0] < p:
+                        px[:] = [np.empty((p, n_rows, n_cols), dtype=np.float32) for _ in range(2)]
+                    u, v = px[0][:p], px[1][:p]
+                    piv.piv_pairs(view, window_size, overlap, signal_threshold, pair_offset=p0, out=(u, v, full["corr"][p0:p1], full["s2n"][p0:p1]))
+                    _to_velocity(u, res_x, dt[p0:p1, None, None], out=full["v_x"][p0:p1])
+                    _to_velocity(v, res_y, dt[p0:p1, None, None], out=full["v_y"][p0:p1])
+                done.append((p0, p1))
+
+        stats = per_device[k] = {
+            "plan": {key: plan[key] for key in ("windows", "load_frames", "align", "depth", "max_depth", "source", "peak_host_bytes", "host_budget")},
+            "load_s": 0.0, "waited_s": 0.0, "upload_s": 0.0, "launch_s": 0.0, "chunks": 0, "depth_per_chunk": [], "load_s_per_chunk": [],
+            "waited_s_per_chunk": []}
+        if chain_k is not None:
+            stats["plan"]["chain"] = chain_k.names
+            stats["mean_s"] = mean_s if k == 0 else 0.0      # sampled frames loaded, uploaded, mean plane computed (once)
         for (w0, w1), loads in zip(plan["windows"], plan["loads"]):
+            executor.stop_point(stop)
             stack = resident.ResidentStack(w0, w1 - w0, dim_size, frames.dtype, plan["align"], launch, signal_threshold, projection,
-                                           chain, mean)
+                                           chain_k, mean_k)
             pieces = [(f0, lazy[f0:f1]) for f0, f1 in loads]
 
             def load_and_stage(piece, stack=stack):
                 # on a loader thread: materialise the piece AND bring it to the device (upload -- or upload + projection -- into its place:
                 # PCIe and the host's page handling stay off the thread that launches; the loaded array is released here as well)
+                executor.stop_point(stop)
                 f0, da = piece
                 return stack.stage(f0, _values(load_frame_chunk(da)))
 
-            with executor.ChunkPrefetcher(pieces, load_and_stage, depth=plan["depth"]) as loader:
+            with executor.ChunkPrefetcher(pieces, load_and_stage, depth=plan["depth"], max_depth_=plan["max_depth"]) as loader:
                 try:
                     for n, n_staged in loader:
                         pieces[n] = None
@@ -547,19 +792,25 @@ def _get_ffpiv_lazy(frames, plan, y, x, dt, time, res_y, res_x, n_cols, n_rows, 
             stack.finish()
             stats["upload_s"] += stack.upload_s; stats["launch_s"] += stack.launch_s
             del stack
+        for key, v in list(stats.items()):
+            if isinstance(v, float):
+                stats[key] = round(v, 6)
+        return done
+
+    try:
+        results = executor.run_on_devices(devices, run)
+        done = sorted(d for r in results for d in r)
         if not done:
             raise ValueError("no chunk with at least one frame pair")
-        if ens is not None:
+        if ensemble_corr:
             # quirk Q3: `n_frames` is the number of CHUNKS of the reference's plan (ffpiv.py:373), `time[0:1]` that of its LAST chunk (:336)
-            n_chunks = len(ref_slices) if ref_slices else len(plan["loads"][0])
-            u, v, corr_count = ens.finish(count_min, n_chunks)
+            n_chunks = len(ref_slices) if ref_slices else len(first["loads"][0])
+            u, v, corr_count = _finish_ensembles([h for h in handles if h is not None], count_min, n_chunks)
     finally:
-        executor.LAST_STATS.clear(); executor.LAST_STATS.update({k: (round(v, 6) if isinstance(v, float) else v) for k, v in stats.items()})
-        if ens is not None:
-            ens.close()
-    done.sort()
+        _close_ensembles(handles, per_device)
+        executor.LAST_STATS.clear(); executor.LAST_STATS.update(_merge_stats(per_device, devices))
     whole = done[0][0] == 0 and done[-1][1] == n_total and all(a[1] == b[0] for a, b in zip(done, done[1:]))
-    if ens is not None:
+    if ensemble_corr:
         cm, sn = full if whole else tuple(np.concatenate([f[i:j] for i, j in done], axis=0) for f in full)
         t_first = time[ref_slices[-1][0] + 1:ref_slices[-1][0] + 2] if ref_slices else time[1:2]
         with warnings.catch_warnings():
