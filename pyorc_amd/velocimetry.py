@@ -101,8 +101,8 @@ def plan_chunks(n_frames: int, req_mem: float, avail_mem: float, chunksize: Opti
         chunks = int((req_mem // avail_mem) + 1)
         chunksize = int(np.ceil(n_frames / chunks))
         if chunksize <= 5:
-            warnings.warn(
-                CHUNK_SIZE_WARNING.format(avail_mem=avail_mem / 1e9, chunksize=chunksize, engine=engine), stacklevel=3
+            warnings.warn(   # at the caller of get_ffpiv (get_ffpiv -> _plan_slices -> here)
+                CHUNK_SIZE_WARNING.format(avail_mem=avail_mem / 1e9, chunksize=chunksize, engine=engine), stacklevel=4
             )
             chunksize = 5  # hard override, try to manage with 5
             chunks = int(np.ceil(n_frames / chunksize))
@@ -203,17 +203,8 @@ def get_ffpiv(
     dim_size = tuple(frames[0].shape)
     dtype = frames.dtype if np.dtype(frames.dtype) in (np.dtype(np.uint8), np.dtype(np.float32)) else np.float64
     n_rows, n_cols = len(y), len(x)
-    # compute memory availability and size of problem (HBM instead of host RAM)
-    user_chunksize = chunksize
-    req_mem = window.required_memory(n_frames=n_frames, dim_size=dim_size, window_size=window_size,
-                                     overlap=overlap, search_area_size=search_area_size, dtype=dtype)
-    avail_mem = window.available_memory() / memory_factor
-    chunksize, ref_slices = plan_chunks(n_frames, req_mem, avail_mem, chunksize, engine, n_win=n_rows * n_cols)
-    def fits(n_chunk_frames: int) -> bool:   # does a chunk of that many frames respect the planner's memory budget?
-        return window.required_memory(n_frames=n_chunk_frames, dim_size=dim_size, window_size=window_size, overlap=overlap,
-                                      search_area_size=search_area_size, dtype=dtype) <= avail_mem
-
-    slices = aligned_slices(n_frames, chunksize, window.chunk_alignment(window_size, dim_size, overlap), n_win=n_rows * n_cols, fits=fits)
+    n_win = n_rows * n_cols
+    _, ref_slices, slices = _plan_slices(n_frames, dim_size, window_size, overlap, dtype, chunksize, memory_factor, engine, n_win)
     if time is None:
         time = frames["time"] if _is_xr(frames) else np.arange(n_frames)
     dt_arr = np.asarray(_values(dt), dtype=np.float64)
@@ -221,28 +212,21 @@ def get_ffpiv(
         raise ValueError(f"dt must have one entry per frame pair ({n_frames - 1}), got shape {dt_arr.shape}")
     devs = _resolve_frames_devices(frames, devices)
     align = window.chunk_alignment(window_size, dim_size, overlap)
-    if _is_lazy(frames) and n_frames >= 2 and not _stack_signal_mode(signal_threshold):
+    stack_mode = _stack_signal_mode(signal_threshold)
+    resident_run = _is_lazy(frames) and n_frames >= 2 and not stack_mode
+    if resident_run:
         # a lazy stack: resident in HBM, loads planned against HOST memory and cut where dask cuts, launches on the anchors
-        plans = plan_lazy_devices(frames, n_frames, dim_size, window_size, overlap, n_rows * n_cols, user_chunksize, memory_factor,
-                                  engine, prefetch, devs)
-        return _get_ffpiv_lazy(frames, plans, y, x, dt_arr, time, res_y, res_x, n_cols, n_rows, window_size, overlap, ensemble_corr,
-                               corr_min, s2n_min, count_min, signal_threshold, ref_slices, devs)
-
-    def device_budget(device, count):   # HBM budget of one worker on `device` (`count` workers share it)
-        with executor.on_device(device):
-            return window.available_memory() / memory_factor / count
-
-    work = device_work(n_frames, slices, devs, align, _stack_signal_mode(signal_threshold),
-                       lambda a, b, d, cnt: _device_slices(b - a + 1, dim_size, window_size, overlap, search_area_size, dtype, user_chunksize,
-                                                           device_budget(d, cnt), engine, n_rows * n_cols, align))
+        work = plan_lazy_devices(frames, n_frames, dim_size, window_size, overlap, n_win, chunksize, memory_factor, engine, prefetch, devs)
+    else:
+        work = device_work(n_frames, slices, devs, align, stack_mode,
+                           lambda a, b, d, cnt: _plan_slices(b - a + 1, dim_size, window_size, overlap, dtype, chunksize, memory_factor,
+                                                             engine, n_win, d, cnt)[2])
+    args = (n_frames - 1, len(work), y, x, dt_arr, res_x, res_y, window_size, overlap, signal_threshold)
+    sink = _ensemble_sink(*args, corr_min, s2n_min, count_min, ref_slices) if ensemble_corr else _timestep_sink(*args)
+    if resident_run:
+        return _run_resident(frames, work, sink, devs, time, signal_threshold)
     depth = (executor.default_depth() if prefetch is None else int(prefetch)) if hasattr(frames, "load") else 0
-    args = (frames, work, y, x, dt_arr, time, res_y, res_x, n_cols, n_rows, window_size, overlap)
-    if ensemble_corr:
-        # quirk Q3 (ffpiv.py:373): the count filter is scaled with the number of CHUNKS -- of the reference's planner
-        # (same formula, fed with HBM figures), not of the aligned chunks actually launched
-        return _get_ffpiv_mean(*args, corr_min, s2n_min, count_min, signal_threshold, like=frames,
-                               ref_slices=ref_slices, prefetch=depth, devices=devs)
-    return _get_ffpiv_timestep(*args, signal_threshold, like=frames, prefetch=depth, devices=devs)
+    return _run_chunks(frames, work, sink, depth, devs, time, window_size, overlap, (n_rows, n_cols))
 
 
 # ---------------------------------------------------------------------------------------------------------------------------------
@@ -292,17 +276,19 @@ def device_work(n_frames: int, slices, devices, align: int, whole_chunks: bool, 
     return out
 
 
-def _device_slices(n_block_frames, dim_size, window_size, overlap, search_area_size, dtype, chunksize, avail_mem, engine, n_win, align):
-    """The chunk plan of :func:`get_ffpiv` for one device's block of ``n_block_frames`` frames against that device's ``avail_mem``."""
-    req = window.required_memory(n_frames=n_block_frames, dim_size=dim_size, window_size=window_size, overlap=overlap,
-                                 search_area_size=search_area_size, dtype=dtype)
-    cs, _ = plan_chunks(n_block_frames, req, avail_mem, chunksize, engine, n_win=n_win)
+def _plan_slices(n_frames, dim_size, window_size, overlap, dtype, chunksize, memory_factor, engine, n_win, device=None, share=1):
+    """The chunk plan of :func:`get_ffpiv` for ``n_frames`` frames against the HBM of ``device`` (None: the calling thread's) that
+    ``share`` workers divide -> (chunksize, the reference planner's slices -- quirk Q3 counts them --, the slices launched: on the
+    anchors, :func:`aligned_slices`)."""
+    def need(n):   # HBM bytes of one launch on n frames
+        return window.required_memory(n_frames=n, dim_size=dim_size, window_size=window_size, overlap=overlap, dtype=dtype)
 
-    def fits(n_chunk_frames: int) -> bool:
-        return window.required_memory(n_frames=n_chunk_frames, dim_size=dim_size, window_size=window_size, overlap=overlap,
-                                      search_area_size=search_area_size, dtype=dtype) <= avail_mem
-
-    return aligned_slices(n_block_frames, cs, align, n_win=n_win, fits=fits)
+    req = need(n_frames)
+    with executor.on_device(device):
+        avail = window.available_memory() / memory_factor / share
+    cs, ref_slices = plan_chunks(n_frames, req, avail, chunksize, engine, n_win=n_win)
+    align = window.chunk_alignment(window_size, dim_size, overlap)
+    return cs, ref_slices, aligned_slices(n_frames, cs, align, n_win=n_win, fits=lambda n: need(n) <= avail)
 
 
 def _merge_stats(per_device, devices) -> dict:
@@ -341,91 +327,167 @@ def _merge_stats(per_device, devices) -> dict:
     return {k: (round(v, 6) if isinstance(v, float) else v) for k, v in out.items()}
 
 
-def _finish_ensembles(handles, count_min, n_chunks):
-    """u, v, corr_count of the ensemble summed over ``handles`` (one per device worker that had pairs, in pair order): one handle
-    finishes as it always has; several are reduced device to device and finished with every device's float64 rescue."""
-    from . import shard
-
-    if len(handles) == 1:
-        with executor.on_device(getattr(handles[0], "device", None)):
-            return handles[0].finish(count_min, n_chunks)
-    with executor.on_device(getattr(handles[0], "device", None)):
-        piv.ensemble_allreduce(handles)
-    return shard.staged_finish(handles, count_min, n_chunks)
-
-
-def _close_ensembles(handles, stats=None):
-    for k, h in enumerate(handles):
-        if h is None:
-            continue
-        with executor.on_device(getattr(h, "device", None)):
-            if stats is not None and stats[k] is not None:
-                stats[k]["ensemble"] = h.stats() if hasattr(h, "stats") else {}
-            h.close()
-
-
-def _to_velocity(disp: np.ndarray, res, dt_chunk: np.ndarray, out: Optional[np.ndarray] = None) -> np.ndarray:
+def _to_velocity(disp: np.ndarray, res, dt_chunk: np.ndarray, out: np.ndarray) -> None:
     """``(disp * res / dt).astype(float32)`` of ffpiv.py:418-419 with the same arithmetic (the product in whatever type numpy
-    gives it, the division in float64, one rounding to float32) but without the two float64 temporaries of the one-liner;
-    ``out``: where the result goes (a time slice of the run's result array)."""
-    prod = disp * res
-    if out is None:
-        out = prod if prod.dtype == np.float32 else np.empty(prod.shape, dtype=np.float32)
-    np.divide(prod, dt_chunk, out=out, dtype=np.float64, casting="same_kind")
-    return out
+    gives it, the division in float64, one rounding to float32) but without the two float64 temporaries of the one-liner, into
+    ``out`` (a time slice of the run's result array)."""
+    np.divide(disp * res, dt_chunk, out=out, dtype=np.float64, casting="same_kind")
 
 
-def _get_ffpiv_timestep(frames, work, y, x, dt, time, res_y, res_x, n_cols, n_rows, window_size, overlap,
-                        signal_threshold, like=None, prefetch=0, devices=None):
-    """Per-chunk loop of pyorc/velocimetry/ffpiv.py:379-443 (one fused GPU call per chunk); chunk n + 1 is loaded on a worker
-    thread while chunk n is launched (``pyorc_amd.executor.ChunkPrefetcher``; ``prefetch = 0``: the reference's serial order).
-    ``work``: the chunk slices of every device worker (:func:`device_work`), each worker loops over its own on its own device."""
-    # the four result variables of the WHOLE run are allocated once and every chunk's launch writes its time slice of them (corr, s2n
-    # straight from the library, v_x / v_y through the px -> m/s scaling): no per-chunk arrays to concatenate at the end (the
-    # reference's xr.concat, ffpiv.py:442 -- 125 KB per pair, i.e. as many bytes again as a uint8 chunk's upload at 32 x 32)
-    n_total = max((sl[-1][1] - 1 for sl in work if sl), default=0)
-    names = ("s2n", "corr", "v_x", "v_y")
-    full = {k: np.empty((n_total, n_rows, n_cols), dtype=np.float32) for k in names}
+# ---------------------------------------------------------------------------------------------------------------------------------
+# where the launches write: one sink per mode, a tuple (launch, close, result) --
+#   launch(k, frames, p0, p1): pairs [p0, p1) (frames p0 .. p1) on device worker k, called on that worker's thread;
+#   close(per_device):         release what the workers hold (and note it in their statistics, per_device[k]);
+#   result(time, like):        the Dataset / PivResult of everything launched.
+# ---------------------------------------------------------------------------------------------------------------------------------
+def _delivered(full, done):
+    """``full`` (the run's result arrays, allocated once, every launch writing its time slice) when every pair was delivered, in order;
+    else the ``done`` ranges of it concatenated (a chunk lost trailing frames -- load_frame_chunk's TypeError retry -- or was
+    skipped).  ``done``: (first pair, one past the last pair) of every launch, sorted."""
+    if not done:
+        raise ValueError("no chunk with at least one frame pair")
+    n = len(next(iter(full.values())))
+    if done[0][0] == 0 and done[-1][1] == n and all(a[1] == b[0] for a, b in zip(done, done[1:])):
+        return full
+    return {k: np.concatenate([v[i:j] for i, j in done], axis=0) for k, v in full.items()}
+
+
+def _timestep_sink(n_pairs, n_workers, y, x, dt, res_x, res_y, window_size, overlap, signal_threshold):
+    """Per-timestep PIV (pyorc/velocimetry/ffpiv.py:379-443).  The four result variables of the WHOLE run are allocated once and every
+    launch writes its time slice of them (corr, s2n straight from the library, v_x / v_y through the px -> m/s scaling): no per-chunk
+    arrays to concatenate at the end (the reference's xr.concat, ffpiv.py:442 -- 125 KB per pair, i.e. as many bytes again as a uint8
+    chunk's upload at 32 x 32)."""
+    full = {k: np.empty((n_pairs, len(y), len(x)), dtype=np.float32) for k in ("s2n", "corr", "v_x", "v_y")}
+    done = []
+    px = [None] * n_workers            # per worker: scratch for a launch's u, v in pixels
     on_device = piv.device_scaling_is_numpys(res_x, res_y)
+
+    def launch(k, frames, p0, p1):
+        p = p1 - p0
+        dt_chunk = dt[p0:p1]  # dt.sel(time=da.time[1:]), ffpiv.py:403-404
+        if on_device:
+            # u and v to meter per second on the device, before they cross PCIe: the arithmetic of ffpiv.py:418-419 for python-float
+            # resolutions (float32 product, float64 division, float32 storage)
+            uv, scale = (full["v_x"][p0:p1], full["v_y"][p0:p1]), (res_x, res_y, dt_chunk)
+        else:
+            # ... in pixels, scaled on the host with numpy's own arithmetic for any other kind of resolution (a numpy float64 scalar
+            # makes the product float64)
+            if px[k] is None or px[k][0].shape[0] < p:
+                px[k] = [np.empty((p, len(y), len(x)), dtype=np.float32) for _ in range(2)]
+            uv, scale = (px[k][0][:p], px[k][1][:p]), None
+        piv.piv_pairs(frames, window_size, overlap, signal_threshold, pair_offset=p0, scale=scale,
+                      out=uv + (full["corr"][p0:p1], full["s2n"][p0:p1]))
+        if scale is None:
+            _to_velocity(uv[0], res_x, dt_chunk[:, None, None], out=full["v_x"][p0:p1])
+            _to_velocity(uv[1], res_y, dt_chunk[:, None, None], out=full["v_y"][p0:p1])
+        done.append((p0, p1))
+
+    def result(time, like):
+        done.sort()
+        data = _delivered(full, done)
+        times = [time[i + 1:j + 1] for i, j in done]
+        t = xr.concat(times, dim="time") if _is_xr(like) else np.concatenate([np.asarray(tt) for tt in times])
+        return _dataset(data, t, y, x, like)
+
+    return launch, lambda per_device: None, result
+
+
+def _ensemble_sink(n_pairs, n_workers, y, x, dt, res_x, res_y, window_size, overlap, signal_threshold, corr_min, s2n_min, count_min,
+                   ref_slices):
+    """Ensemble correlation (pyorc/velocimetry/ffpiv.py:182-376): every device worker accumulates its pairs into an ``Ensemble`` handle
+    of its own (corr_sum / corr_count stay in HBM); the masked per-pair corr_max / s2n of the whole run are allocated once and every
+    launch writes its time slice (the ``out`` of ``Ensemble.accumulate``).  One handle finishes as it always has; several are reduced
+    device to device (``piv.ensemble_allreduce``) and finished with every device's float64 rescue (``shard.staged_finish``)."""
+    full = {k: np.empty((n_pairs, len(y) * len(x)), dtype=np.float32) for k in ("corr", "s2n")}
+    done = []
+    handles = [None] * n_workers
+
+    def launch(k, frames, p0, p1):
+        if handles[k] is None:   # made on the worker's thread: on the worker's device
+            handles[k] = piv.Ensemble(tuple(frames.shape[1:]), window_size, overlap)
+        handles[k].accumulate(frames, corr_min, s2n_min, signal_threshold, out=(full["corr"][p0:p1], full["s2n"][p0:p1]))
+        done.append((p0, p1))
+
+    def close(per_device):
+        for k, h in enumerate(handles):
+            if h is None:
+                continue
+            with executor.on_device(getattr(h, "device", None)):
+                if per_device[k] is not None:
+                    per_device[k]["ensemble"] = h.stats() if hasattr(h, "stats") else {}
+                h.close()
+
+    def result(time, like):
+        from . import shard
+
+        done.sort()
+        data = _delivered(full, done)
+        # quirk Q3: `n_frames` is the number of CHUNKS, not pairs (ffpiv.py:373), and `time[0:1]` of the LAST chunk ends up on the
+        # result (ffpiv.py:336) -- both taken from the reference's own chunk plan (same formula, fed with HBM figures), not from the
+        # chunks that were launched, so neither depends on the segment anchoring, on the loads or on the number of devices
+        assert ref_slices   # plan_chunks' first slice is (0, min(chunksize, n_frames)) with chunksize >= 2; fewer frames raised above
+        n_chunks, last = len(ref_slices), ref_slices[-1][0]
+        live = [h for h in handles if h is not None]
+        if len(live) == 1:
+            with executor.on_device(getattr(live[0], "device", None)):
+                u, v, corr_count = live[0].finish(count_min, n_chunks)
+        else:
+            with executor.on_device(getattr(live[0], "device", None)):
+                piv.ensemble_allreduce(live)
+            u, v, corr_count = shard.staged_finish(live, count_min, n_chunks)
+        with warnings.catch_warnings():
+            warnings.simplefilter("ignore", category=RuntimeWarning)
+            # very low amounts of found valid correlations are entirely filtered out (ffpiv.py:280-286)
+            data["corr"][:, corr_count < count_min * n_chunks] = np.nan
+            corr_mean = np.nanmean(data["corr"], axis=0).reshape(-1, len(y), len(x))
+            s2n_mean = np.nanmean(data["s2n"], axis=0).reshape(-1, len(y), len(x))
+        dt_av = dt.mean()
+        data = {"s2n": s2n_mean, "corr": corr_mean, "v_x": (u * res_x / dt_av).astype(np.float32),
+                "v_y": (v * res_y / dt_av).astype(np.float32)}
+        return _dataset(data, time[last + 1:last + 2], y, x, like)
+
+    return launch, close, result
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------
+# the drivers: which frames reach the sink, on which device worker
+# ---------------------------------------------------------------------------------------------------------------------------------
+def _run_workers(sink, devices, run, per_device, time, like):
+    """``run(k, stop)`` on every device worker, each on a thread of its own, then the sink's result.  Whatever happens, the sink is
+    closed and ``executor.LAST_STATS`` written -- once, by the calling thread: the workers only fill their own ``per_device`` entry."""
+    _, close, result = sink
+    try:
+        executor.run_on_devices(devices, run)
+        return result(time, like)
+    finally:
+        close(per_device)
+        executor.LAST_STATS.clear(); executor.LAST_STATS.update(_merge_stats(per_device, devices))
+
+
+def _run_chunks(frames, work, sink, prefetch, devices, time, window_size, overlap, grid):
+    """The chunk loops of pyorc/velocimetry/ffpiv.py:348-370 and :399-440 (one fused GPU call per chunk); chunk n + 1 is loaded on a
+    worker thread while chunk n is launched (``pyorc_amd.executor.ChunkPrefetcher``; ``prefetch = 0``: the reference's serial order).
+    ``work``: the chunk slices of every device worker (:func:`device_work`), each worker loops over its own on its own device;
+    ``grid``: (rows, columns) of the coordinates."""
+    launch = sink[0]
     per_device = [None] * len(work)
 
     def run(k, stop):
         slices = work[k]
         if not slices:
-            return [], []
+            return
         frames_chunks = [frames[a:b] for a, b in slices]
-        px = None              # scratch for a chunk's u, v in pixels
-        done = []              # (first pair, one past the last pair) of every chunk that delivered
-        times = []
         loader = executor.ChunkPrefetcher(frames_chunks, load_frame_chunk, depth=prefetch)
         try:
             for n, da in loader:
                 executor.stop_point(stop)
-                a, b = slices[n]
                 if len(da) >= 2:  # we need at least one image-pair to do PIV
-                    nb = a + len(da)  # load_frame_chunk may have dropped trailing frames
-                    p = nb - 1 - a
                     vals = _values(da)
-                    grid = window.get_array_shape(tuple(vals.shape[1:]), window_size, overlap)
-                    if tuple(grid) != (n_rows, n_cols):
-                        raise ValueError(f"grid {tuple(grid)} does not match coordinates ({n_rows}, {n_cols})")
-                    dt_chunk = dt[a:nb - 1]  # dt.sel(time=da.time[1:]), ffpiv.py:403-404
-                    if on_device:
-                        # u and v to meter per second on the device, before they cross PCIe: the arithmetic of ffpiv.py:418-419 for
-                        # python-float resolutions (float32 product, float64 division, float32 storage)
-                        piv.piv_pairs(vals, window_size, overlap, signal_threshold, pair_offset=a, scale=(res_x, res_y, dt_chunk),
-                                      out=(full["v_x"][a:a + p], full["v_y"][a:a + p], full["corr"][a:a + p], full["s2n"][a:a + p]))
-                    else:
-                        if px is None or px[0].shape[0] < p:
-                            px = [np.empty((p, n_rows, n_cols), dtype=np.float32) for _ in range(2)]
-                        u, v = px[0][:p], px[1][:p]
-                        piv.piv_pairs(vals, window_size, overlap, signal_threshold, pair_offset=a,
-                                      out=(u, v, full["corr"][a:a + p], full["s2n"][a:a + p]))
-                        # ... on the host with numpy's own arithmetic for any other kind of resolution (a numpy float64 scalar makes the product float64)
-                        _to_velocity(u, res_x, dt_chunk[:, None, None], out=full["v_x"][a:a + p])
-                        _to_velocity(v, res_y, dt_chunk[:, None, None], out=full["v_y"][a:a + p])
-                    done.append((a, a + p))
-                    times.append(time[a + 1:nb])
+                    got = tuple(window.get_array_shape(tuple(vals.shape[1:]), window_size, overlap))
+                    if got != grid:
+                        raise ValueError(f"grid {got} does not match coordinates {grid}")
+                    a = slices[n][0]
+                    launch(k, vals, a, a + len(da) - 1)   # load_frame_chunk may have dropped trailing frames
                 # remove chunk safely from memory.  (The reference follows this with gc.collect() to get rid of its window stack and
                 # correlation volume, ffpiv.py:437-440; neither exists here, and a collection costs ~1 ms per chunk: dropped.)
                 frames_chunks[n] = None
@@ -435,105 +497,8 @@ def _get_ffpiv_timestep(frames, work, y, x, dt, time, res_y, res_x, n_cols, n_ro
             # collected, and the statistics of what ran are kept
             loader.close()
             per_device[k] = loader.stats
-        return done, times
 
-    try:
-        results = executor.run_on_devices(devices, run)
-    finally:
-        # written once, by the calling thread (the device workers only fill their own entry)
-        executor.LAST_STATS.clear(); executor.LAST_STATS.update(_merge_stats(per_device, devices))
-    done = [d for r in results for d in r[0]]
-    times = [t for r in results for t in r[1]]
-    if not done:
-        raise ValueError("no chunk with at least one frame pair")
-    if done[0][0] == 0 and done[-1][1] == n_total and all(x[1] == y[0] for x, y in zip(done, done[1:])):
-        data = full            # every pair delivered, in order: the arrays are the result
-    else:                      # a chunk lost trailing frames (load_frame_chunk's TypeError retry) or was skipped: close the gaps
-        data = {k: np.concatenate([full[k][i:j] for i, j in done], axis=0) for k in names}
-    if _is_xr(like):
-        t = xr.concat(times, dim="time")
-    else:
-        t = np.concatenate([np.asarray(tt) for tt in times])
-    return _dataset(data, t, y, x, like)
-
-
-def _get_ffpiv_mean(frames, work, y, x, dt, time, res_y, res_x, n_cols, n_rows, window_size, overlap,
-                    corr_min, s2n_min, count_min, signal_threshold, like=None, ref_slices=None, prefetch=0, devices=None):
-    """Ensemble correlation of pyorc/velocimetry/ffpiv.py:182-376; corr_sum / corr_count stay in HBM; chunks loaded ahead of
-    their launches like in ``_get_ffpiv_timestep`` (the reference's loop: ffpiv.py:348-370).  Every device worker accumulates its
-    chunks into a handle of its own; the handles are reduced and finished together (:func:`_finish_ensembles`)."""
-    # the masked per-pair corr_max / s2n of the whole run: allocated once, every chunk writes its time slice (Ensemble.accumulate(out=))
-    n_total = max((sl[-1][1] - 1 for sl in work if sl), default=0)
-    n_win = n_rows * n_cols
-    full = (np.empty((n_total, n_win), dtype=np.float32), np.empty((n_total, n_win), dtype=np.float32))
-    handles = [None] * len(work)
-    per_device = [None] * len(work)
-
-    def run(k, stop):
-        slices = work[k]
-        if not slices:
-            return [], None
-        frames_chunks = [frames[a:b] for a, b in slices]
-        done = []
-        t_first = None
-        loader = executor.ChunkPrefetcher(frames_chunks, load_frame_chunk, depth=prefetch)
-        try:
-            for n, da in loader:
-                executor.stop_point(stop)
-                a, b = slices[n]
-                if len(da) < 2:
-                    continue
-                arr = _values(da)
-                p = len(da) - 1
-                if handles[k] is None:
-                    handles[k] = piv.Ensemble(tuple(arr.shape[1:]), window_size, overlap)
-                handles[k].accumulate(arr, corr_min, s2n_min, signal_threshold, out=(full[0][a:a + p], full[1][a:a + p]))
-                done.append((a, a + p))
-                t_first = time[a + 1:a + 2]
-                frames_chunks[n] = None
-                del da
-        finally:
-            loader.close()
-            per_device[k] = loader.stats
-        return done, t_first
-
-    try:
-        results = executor.run_on_devices(devices, run)
-        done = [d for r in results for d in r[0]]
-        live = [h for h in handles if h is not None]
-        if not live:
-            raise ValueError("no chunk with at least one frame pair")
-        # quirk Q3: `n_frames` is the number of CHUNKS, not pairs (ffpiv.py:373), and `time[0:1]` of the LAST chunk ends
-        # up on the result (ffpiv.py:336) -- both taken from the reference's own chunk plan, not from the aligned
-        # chunks that were launched, so neither depends on the segment anchoring or on the number of devices
-        n_frames = len(done)
-        t_first = [r[1] for r in results if r[1] is not None][-1]
-        if ref_slices:
-            n_frames = len(ref_slices)
-            t_first = time[ref_slices[-1][0] + 1:ref_slices[-1][0] + 2]
-        u, v, corr_count = _finish_ensembles(live, count_min, n_frames)
-    finally:
-        _close_ensembles(handles, per_device)
-        executor.LAST_STATS.clear(); executor.LAST_STATS.update(_merge_stats(per_device, devices))
-    if done[0][0] == 0 and done[-1][1] == n_total and all(x[1] == y[0] for x, y in zip(done, done[1:])):
-        corr_max_concat, s2n_concat = full
-    else:   # a chunk lost trailing frames (load_frame_chunk's TypeError retry) or was skipped
-        corr_max_concat = np.concatenate([full[0][i:j] for i, j in done], axis=0)
-        s2n_concat = np.concatenate([full[1][i:j] for i, j in done], axis=0)
-    with warnings.catch_warnings():
-        warnings.simplefilter("ignore", category=RuntimeWarning)
-        # very low amounts of found valid correlations are entirely filtered out (ffpiv.py:280-286)
-        corr_max_concat[:, corr_count < count_min * n_frames] = np.nan
-        corr_max_mean = np.nanmean(corr_max_concat, axis=0).reshape(-1, n_rows, n_cols)
-        s2n_mean = np.nanmean(s2n_concat, axis=0).reshape(-1, n_rows, n_cols)
-    dt_av = dt.mean()
-    data = {
-        "s2n": s2n_mean,
-        "corr": corr_max_mean,
-        "v_x": (u * res_x / dt_av).astype(np.float32),
-        "v_y": (v * res_y / dt_av).astype(np.float32),
-    }
-    return _dataset(data, t_first, y, x, like)
+    return _run_workers(sink, devices, run, per_device, time, frames)
 
 
 # ---------------------------------------------------------------------------------------------------------------------------------
@@ -558,6 +523,14 @@ def _stack_signal_mode(signal_threshold) -> bool:
         return _lib.get_option("signal_mode") == 1
     except Exception:
         return False
+
+
+def _lazy_source(frames, handoff):
+    """The stack a lazy run loads: ``frames`` itself, or for a ``project_hip`` hand-off (``plugin.hip_projection_source``) its camera
+    frames -- or, when those are the recipe's filters over a uint8 stack (``ops``), that stack (``root``)."""
+    if handoff is None:
+        return frames
+    return handoff["root"] if handoff.get("ops") else handoff["source"]
 
 
 class LazyPlan(dict):
@@ -592,7 +565,7 @@ def plan_lazy(frames, n_frames, dim_size, window_size, overlap, n_win, chunksize
         from .filters import Chain
 
         chain = Chain(handoff["ops"])
-    src = frames if handoff is None else handoff["root"] if chain is not None else handoff["source"]
+    src = _lazy_source(frames, handoff)
     src_shape = tuple(int(v) for v in (src[0].shape if handoff is not None else dim_size))
     host_frame_bytes = int(np.prod(src_shape)) * np.dtype(src.dtype).itemsize
     blocks = resident.time_blocks(src)
@@ -665,9 +638,7 @@ def plan_lazy_devices(frames, n_frames, dim_size, window_size, overlap, n_win, c
                           host_available=host_available, hbm_available=hbm_available)]
     D = len(devices)
     align = window.chunk_alignment(window_size, dim_size, overlap)
-    handoff = plugin.hip_projection_source(frames)
-    src = frames if handoff is None else handoff.get("root", handoff["source"]) if handoff.get("ops") else handoff["source"]
-    unit = lazy_unit(align, resident.time_blocks(src), n_frames, D)
+    unit = lazy_unit(align, resident.time_blocks(_lazy_source(frames, plugin.hip_projection_source(frames))), n_frames, D)
     host = window.available_host_memory() if host_available is None else host_available
     plans = []
     for k, d in enumerate(devices):
@@ -685,19 +656,17 @@ def plan_lazy_devices(frames, n_frames, dim_size, window_size, overlap, n_win, c
     return plans
 
 
-def _get_ffpiv_lazy(frames, plans, y, x, dt, time, res_y, res_x, n_cols, n_rows, window_size, overlap, ensemble_corr,
-                    corr_min, s2n_min, count_min, signal_threshold, ref_slices, devices=None):
+def _run_resident(frames, plans, sink, devices, time, signal_threshold):
     """The loops of pyorc/velocimetry/ffpiv.py:348-370 and :399-440 over a lazy stack: pieces are loaded ahead (``ChunkPrefetcher``),
-    pushed into an HBM-resident stack (``ResidentStack``) and launched on the anchors; results land in the run's arrays.  ``plans``:
-    one :class:`LazyPlan` per device worker (:func:`plan_lazy_devices`); every worker runs its own windows on its own device."""
+    pushed into an HBM-resident stack (``ResidentStack``) and launched on the anchors.  ``plans``: one :class:`LazyPlan` per device
+    worker (:func:`plan_lazy_devices`); every worker runs its own windows on its own device."""
     from . import plugin
 
-    n_total = len(frames) - 1
-    n_win = n_rows * n_cols
+    launch = sink[0]
     dim_size = tuple(int(v) for v in frames[0].shape)
     first = next(pl for pl in plans if pl is not None)
-    handoff, chain = first["handoff"], first.get("chain")
-    lazy = frames if handoff is None else handoff["root"] if chain is not None else handoff["source"]
+    handoff, chain = first["handoff"], first["chain"]
+    lazy = _lazy_source(frames, handoff)
     mean, mean_host = None, None
     mean_s = 0.0
     if chain is not None and chain.samples:
@@ -714,60 +683,31 @@ def _get_ffpiv_lazy(frames, plans, y, x, dt, time, res_y, res_x, n_cols, n_rows,
             if devices is not None and any(d != devices[0] for d in devices):
                 mean_host = mean.to_host()
         mean_s = _time.perf_counter() - t0
-    names = ("s2n", "corr", "v_x", "v_y")
-    on_device = piv.device_scaling_is_numpys(res_x, res_y)
-    if ensemble_corr:
-        full = (np.empty((n_total, n_win), dtype=np.float32), np.empty((n_total, n_win), dtype=np.float32))
-    else:
-        full = {k: np.empty((n_total, n_rows, n_cols), dtype=np.float32) for k in names}
-    handles = [None] * len(plans)
     per_device = [None] * len(plans)
 
     def run(k, stop):
         plan = plans[k]
         if plan is None:
-            return []
-        done = []
+            return
         device = None if devices is None else devices[k]
-        chain_k = plan.get("chain")
         mean_k = mean if (mean_host is None or device == devices[0]) else resident.DeviceFrames.from_host(mean_host)
         projection = None if handoff is None else plugin.projection_for(handoff) if devices is None else plugin.projection_for(handoff, device)
-        if ensemble_corr:
-            ens = handles[k] = piv.Ensemble(dim_size, window_size, overlap)
 
-            def launch(view, p0, p1):
-                executor.stop_point(stop)
-                ens.accumulate(view, corr_min, s2n_min, signal_threshold, out=(full[0][p0:p1], full[1][p0:p1]))
-                done.append((p0, p1))
-        else:
-            px = []
-
-            def launch(view, p0, p1):
-                executor.stop_point(stop)
-                p = p1 - p0
-                if on_device:
-                    piv.piv_pairs(view, window_size, overlap, signal_threshold, pair_offset=p0, scale=(res_x, res_y, dt[p0:p1]),
-                                  out=(full["v_x"][p0:p1], full["v_y"][p0:p1], full["corr"][p0:p1], full["s2n"][p0:p1]))
-                else:
-                    if not px or px[0].shape[0] < p:
-                        px[:] = [np.empty((p, n_rows, n_cols), dtype=np.float32) for _ in range(2)]
-                    u, v = px[0][:p], px[1][:p]
-                    piv.piv_pairs(view, window_size, overlap, signal_threshold, pair_offset=p0, out=(u, v, full["corr"][p0:p1], full["s2n"][p0:p1]))
-                    _to_velocity(u, res_x, dt[p0:p1, None, None], out=full["v_x"][p0:p1])
-                    _to_velocity(v, res_y, dt[p0:p1, None, None], out=full["v_y"][p0:p1])
-                done.append((p0, p1))
+        def launch_k(view, p0, p1):
+            executor.stop_point(stop)
+            launch(k, view, p0, p1)
 
         stats = per_device[k] = {
             "plan": {key: plan[key] for key in ("windows", "load_frames", "align", "depth", "max_depth", "source", "peak_host_bytes", "host_budget")},
             "load_s": 0.0, "waited_s": 0.0, "upload_s": 0.0, "launch_s": 0.0, "chunks": 0, "depth_per_chunk": [], "load_s_per_chunk": [],
             "waited_s_per_chunk": []}
-        if chain_k is not None:
-            stats["plan"]["chain"] = chain_k.names
+        if plan["chain"] is not None:
+            stats["plan"]["chain"] = plan["chain"].names
             stats["mean_s"] = mean_s if k == 0 else 0.0      # sampled frames loaded, uploaded, mean plane computed (once)
         for (w0, w1), loads in zip(plan["windows"], plan["loads"]):
             executor.stop_point(stop)
-            stack = resident.ResidentStack(w0, w1 - w0, dim_size, frames.dtype, plan["align"], launch, signal_threshold, projection,
-                                           chain_k, mean_k)
+            stack = resident.ResidentStack(w0, w1 - w0, dim_size, frames.dtype, plan["align"], launch_k, signal_threshold, projection,
+                                           plan["chain"], mean_k)
             pieces = [(f0, lazy[f0:f1]) for f0, f1 in loads]
 
             def load_and_stage(piece, stack=stack):
@@ -784,49 +724,15 @@ def _get_ffpiv_lazy(frames, plans, y, x, dt, time, res_y, res_x, n_cols, n_rows,
                         stack.commit(loads[n][0], n_staged)
                 finally:
                     loader.close()
-                    st = loader.stats
-                    stats["load_s"] += st["load_s"]; stats["waited_s"] += st["waited_s"]; stats["chunks"] += st["chunks"]
-                    stats["depth_per_chunk"] += st["depth_per_chunk"]
-                    stats["load_s_per_chunk"] += st["load_s_per_chunk"]; stats["waited_s_per_chunk"] += st["waited_s_per_chunk"]
-                    stats["depth"], stats["workers"], stats["adaptive"] = st["depth"], st["workers"], st["adaptive"]
+                    st = loader.stats     # this window's loads: added up; depth / workers / adaptive: the last window's
+                    for key in ("load_s", "waited_s", "chunks", "depth_per_chunk", "load_s_per_chunk", "waited_s_per_chunk"):
+                        stats[key] += st[key]
+                    stats.update(depth=st["depth"], workers=st["workers"], adaptive=st["adaptive"])
             stack.finish()
             stats["upload_s"] += stack.upload_s; stats["launch_s"] += stack.launch_s
             del stack
         for key, v in list(stats.items()):
             if isinstance(v, float):
                 stats[key] = round(v, 6)
-        return done
 
-    try:
-        results = executor.run_on_devices(devices, run)
-        done = sorted(d for r in results for d in r)
-        if not done:
-            raise ValueError("no chunk with at least one frame pair")
-        if ensemble_corr:
-            # quirk Q3: `n_frames` is the number of CHUNKS of the reference's plan (ffpiv.py:373), `time[0:1]` that of its LAST chunk (:336)
-            n_chunks = len(ref_slices) if ref_slices else len(first["loads"][0])
-            u, v, corr_count = _finish_ensembles([h for h in handles if h is not None], count_min, n_chunks)
-    finally:
-        _close_ensembles(handles, per_device)
-        executor.LAST_STATS.clear(); executor.LAST_STATS.update(_merge_stats(per_device, devices))
-    whole = done[0][0] == 0 and done[-1][1] == n_total and all(a[1] == b[0] for a, b in zip(done, done[1:]))
-    if ensemble_corr:
-        cm, sn = full if whole else tuple(np.concatenate([f[i:j] for i, j in done], axis=0) for f in full)
-        t_first = time[ref_slices[-1][0] + 1:ref_slices[-1][0] + 2] if ref_slices else time[1:2]
-        with warnings.catch_warnings():
-            warnings.simplefilter("ignore", category=RuntimeWarning)
-            cm[:, corr_count < count_min * n_chunks] = np.nan
-            corr_max_mean = np.nanmean(cm, axis=0).reshape(-1, n_rows, n_cols)
-            s2n_mean = np.nanmean(sn, axis=0).reshape(-1, n_rows, n_cols)
-        dt_av = dt.mean()
-        data = {"s2n": s2n_mean, "corr": corr_max_mean, "v_x": (u * res_x / dt_av).astype(np.float32), "v_y": (v * res_y / dt_av).astype(np.float32)}
-        return _dataset(data, t_first, y, x, frames)
-    data = full if whole else {k: np.concatenate([full[k][i:j] for i, j in done], axis=0) for k in names}
-    times = [time[i + 1:j + 1] for i, j in done]
-    if len(times) == 1:
-        t = times[0]
-    elif _is_xr(frames):
-        t = xr.concat(times, dim="time")
-    else:
-        t = np.concatenate([np.asarray(tt) for tt in times])
-    return _dataset(data, t, y, x, frames)
+    return _run_workers(sink, devices, run, per_device, time, frames)

@@ -97,7 +97,7 @@ def test_no_devices_keeps_the_single_device_plan():
     assert V.device_work(201, slices, None, 25, False, None) == [slices]
 
 
-def test_the_per_device_plan_uses_that_devices_budget(monkeypatch):
+def test_each_device_block_is_planned_against_its_share_of_that_devices_budget(monkeypatch):
     """Two workers on one device share its HBM: each block is planned against half of it."""
     from pyorc_amd import executor, velocimetry as V
 
@@ -110,9 +110,10 @@ def test_the_per_device_plan_uses_that_devices_budget(monkeypatch):
     V.device_work(301, None, [0, 0, 1], 25, False, plan_block)
     assert seen == [(0, 2), (0, 2), (1, 1)]
     monkeypatch.setattr(executor, "bind_device", lambda d: None)
-    monkeypatch.setattr(V.window, "available_memory", lambda: 8e9)
-    one = V._device_slices(151, (1080, 1920), (32, 32), (16, 16), (32, 32), np.uint8, None, 8e9, "hip", 100, 25)
-    small = V._device_slices(151, (1080, 1920), (32, 32), (16, 16), (32, 32), np.uint8, 3, 8e9, "hip", 100, 25)
+    monkeypatch.setattr(V.window, "available_memory", lambda: 16e9)
+    monkeypatch.setattr(V.window, "chunk_alignment", lambda ws, dim=None, ov=None: 25)
+    one = V._plan_slices(151, (1080, 1920), (32, 32), (16, 16), np.uint8, None, 1, "hip", 100, device=0, share=2)[2]
+    small = V._plan_slices(151, (1080, 1920), (32, 32), (16, 16), np.uint8, 3, 1, "hip", 100, device=0, share=2)[2]
     assert one == [(0, 151)] and small[0] == (0, 26)
 
 
@@ -275,3 +276,87 @@ def test_the_allreduce_kernel_stays_out_of_the_kernel_hash_sources():
 
     for name in _lib.KERNEL_SOURCES:
         assert "allreduce" not in open(os.path.join(ROOT, "pyorc_amd", "csrc", name)).read()
+
+
+# ---- the multi-worker assembly, end to end on the CPU ------------------------------------------------------------------------------
+class _Lazy:
+    """The least a lazy stack offers: ``load()`` and time slicing."""
+
+    def __init__(self, data):
+        self._d, self.dtype, self.shape = data, data.dtype, data.shape
+
+    def __len__(self):
+        return len(self._d)
+
+    def __getitem__(self, key):
+        return _Lazy(self._d[key]) if isinstance(key, slice) else self._d[key]
+
+    def load(self):
+        return np.array(self._d)
+
+
+# LAST_STATS keys of today's runs: one worker keeps its own statistics (an ensemble's included), several are merged (no ``ensemble``;
+# a lazy stack adds ``boundary_frames``)
+_EAGER_KEYS = {"depth", "workers", "adaptive", "max_depth", "depth_per_chunk", "chunks", "load_s", "waited_s", "consumed_s",
+               "load_s_per_chunk", "waited_s_per_chunk", "devices", "per_device", "idle_devices"}
+_LAZY_KEYS = {"plan", "load_s", "waited_s", "upload_s", "launch_s", "chunks", "depth_per_chunk", "load_s_per_chunk", "waited_s_per_chunk",
+              "depth", "workers", "adaptive", "devices", "per_device", "idle_devices"}
+
+
+@pytest.mark.parametrize("ensemble", [False, True])
+@pytest.mark.parametrize("lazy", [False, True])
+def test_device_workers_assemble_the_single_worker_result(monkeypatch, lazy, ensemble):
+    """``devices=[0, 0]`` and ``[0, 0, 0]`` against ``devices=None`` through the whole of ``get_ffpiv`` (oracle doubles for the launches):
+    per-timestep results bit for bit, ensemble results to float32 rounding (the device-to-device sum is float32), and the statistics'
+    keys as they are."""
+    from pyorc_amd import _lib, executor, velocimetry as V
+    from pyorc_amd.synth import particle_stack
+    from tests import doubles
+    from tests.test_shard_gloo import OracleEnsemble
+
+    class Ens(OracleEnsemble):
+        def accumulate(self, frames, corr_min, s2n_min, thr=None, out=None):
+            return super().accumulate(np.asarray(frames), corr_min, s2n_min, thr, out)
+
+        def close(self):
+            pass
+
+    def allreduce(handles):
+        states = [h.export_state() for h in handles]
+        s, k = states[0]
+        for s1, k1 in states[1:]:
+            s, k = s + s1, k + k1
+        for h in handles:
+            h.import_state(s, k)
+
+    monkeypatch.setattr(executor, "bind_device", lambda d: None)
+    monkeypatch.setattr(_lib, "device_count", lambda: 4)
+    monkeypatch.setattr(V.piv, "piv_pairs", doubles.oracle_piv_pairs)
+    monkeypatch.setattr(V.piv, "Ensemble", Ens)
+    monkeypatch.setattr(V.piv, "ensemble_allreduce", allreduce)
+    monkeypatch.setattr(V.window, "chunk_alignment", lambda ws, dim=None, ov=None: 5)
+    monkeypatch.setattr(V.window, "available_memory", lambda: 1e12)
+    doubles.use_host_stacks(monkeypatch)
+    fr = particle_stack(33, 64, 96, seed=4).astype(np.float32)
+    y, x = np.arange(3) * 0.5, np.arange(5) * 0.5
+    dt = np.full(32, 0.04)
+
+    def run(devices):
+        ds = V.get_ffpiv(_Lazy(fr) if lazy else fr, y, x, dt, (32, 32), (16, 16), (32, 32), 0.02, 0.02, chunksize=11,
+                         ensemble_corr=ensemble, devices=devices)
+        return ds, dict(executor.LAST_STATS)
+
+    ref, st = run(None)
+    assert st["chunks"] >= 3                                   # several chunks (loads) per worker
+    keys = _LAZY_KEYS if lazy else _EAGER_KEYS
+    assert set(st) == keys | ({"ensemble"} if ensemble else set())
+    for devices in ([0, 0], [0, 0, 0]):
+        got, st = run(devices)
+        assert set(st) == keys | ({"boundary_frames"} if lazy else set()), devices
+        assert st["devices"] == devices and len(st["per_device"]) == len(devices) and st["idle_devices"] == 0
+        assert np.array_equal(got.coords["time"], ref.coords["time"])
+        for k in ("v_x", "v_y", "corr", "s2n"):
+            if ensemble and k in ("v_x", "v_y"):
+                np.testing.assert_allclose(got[k], ref[k], rtol=1e-5, atol=1e-6, err_msg=f"{k} {devices}")
+            else:
+                assert np.array_equal(got[k], ref[k], equal_nan=True), (k, devices)
