@@ -37,7 +37,9 @@
 extern "C" {
 #endif
 
-#define LSPIV_ABI_VERSION 5   /* 5 (round 6): lspiv_chunk_alignment(wy, wx) without a grid now returns the alignment that is right on EVERY grid (75
+#define LSPIV_ABI_VERSION 5   /* (additions since, nothing existing moved, no version change: the search-area entry points lspiv_piv_search_pairs_at /
+                               * lspiv_piv_search_pairs_dev_at and lspiv_search_supported)
+                               * 5 (round 6): lspiv_chunk_alignment(wy, wx) without a grid now returns the alignment that is right on EVERY grid (75
                                * where it returned 25: callers that cut chunks on it stay bit-reproducible on large grids); additions:
                                * lspiv_upload_frames, lspiv_trace / lspiv_trace_read; the host-pointer projection entry points no longer
                                * share the PIV host entry points' lock and workspaces.
@@ -201,6 +203,25 @@ int lspiv_piv_velocity_at(const void* frames, int dtype, int64_t T, int64_t H, i
                           int wy, int wx, int oy, int ox, float signal_threshold, int64_t pair_offset,
                           double res_x, double res_y, const double* dt,
                           float* v_x, float* v_y, float* corr_max, float* s2n);
+
+/* Extended search area: an interrogation window wy x wx of frame t searched inside a LARGER search area say x sax of frame t+1
+ * (ffpiv.cross_corr's search_area_size != window_size).  This project's reading (ffpiv's own is unknown: unpinned like the rest of
+ * the PIV path): the grid is that of the search area -- tiles of say x sax anchored top-left, step search area -
+ * overlap, so oy, ox are relative to the search area --; per tile and pair B = the tile of frame t+1 normalised over its say sax
+ * samples, a = the central wy x wx block of the tile of frame t (offset (say - wy) / 2) normalised over its own samples and placed
+ * at that offset in a tile of zeros; plane = clip(fftshift(irfft2(conj(rfft2 A) rfft2 B)) / (wy wx), 0, 1), say x sax samples, zero
+ * displacement at its centre; corr_max, s2n, u, v from that plane as in lspiv_piv_pairs.  corr_planes: (T-1) * n_win * say * sax.  The
+ * signal threshold scores a over wy wx samples and B over say sax.  Supported (lspiv_search_supported == 1, host-only): square search
+ * areas 16, 32, 64 with a square even window 4 .. search area - 2; anything else, and option "norm_clip" = 0, is LSPIV_EUNSUPPORTED.
+ * Per-pair kernels: results do not depend on the chunking (chunk alignment 1).  lspiv_required_bytes with the SEARCH AREA as its
+ * window is the memory these calls need.  A displacement up to (search area - window) / 2 is measured without aliasing. */
+int lspiv_search_supported(int say, int sax, int wy, int wx);
+int lspiv_piv_search_pairs_at(const void* frames, int dtype, int64_t T, int64_t H, int64_t W,
+                              int say, int sax, int wy, int wx, int oy, int ox, float signal_threshold, int64_t pair_offset,
+                              float* u, float* v, float* corr_max, float* s2n, float* corr_planes);
+int lspiv_piv_search_pairs_dev_at(const void* d_frames, int dtype, int64_t T, int64_t H, int64_t W,
+                                  int say, int sax, int wy, int wx, int oy, int ox, float signal_threshold, int64_t pair_offset,
+                                  float* d_out, float* d_corr_planes, void* stream);
 
 /* Host frames into a slice of an HBM-resident stack, the way lspiv_piv_pairs brings them in -- pinned ring, staging threads,
  * float64 narrowed to float32 with the "narrow_offset" guard (so d_dst receives n_frames * H * W samples of LSPIV_F32 for LSPIV_F64

@@ -104,6 +104,30 @@ int fill_params(lspiv::PivParams* p, const void* d_frames, int dtype, int64_t T,
   return LSPIV_OK;
 }
 
+// search-area mode: an even square window wy = wx = n, 4 <= n <= S - 2, of frame t inside a square search area S = say = sax of
+// frame t+1, S in {16, 32, 64}
+static bool search_shape_ok(int say, int sax, int wy, int wx) {
+  return say == sax && (say == 16 || say == 32 || say == 64) && wy == wx && wy >= 4 && wy <= say - 2 && (wy & 1) == 0;
+}
+static int check_search(int say, int sax, int wy, int wx) {
+  if (!search_shape_ok(say, sax, wy, wx))
+    return fail(LSPIV_EUNSUPPORTED, "search area %dx%d with window %dx%d is not supported: the search area must be square, 16, 32 or 64, "
+                "and the window square and even with 4 <= window <= search area - 2", say, sax, wy, wx);
+  if (!g_opt_norm_clip.load())
+    return fail(LSPIV_EUNSUPPORTED, "option norm_clip = 0 is served by the block-per-window kernels only, not with a search area");
+  return LSPIV_OK;
+}
+// p filled for the search area (fill_params with wy = wx = S) -> window n inside it
+static void set_search_window(lspiv::PivParams* p, int n) {
+  p->nw = n;
+  if (g_opt_std_ddof.load()) {   // sample std of BOTH windows: (n^2 - 1) / n^2 of the window times (S^2 - 1) / S^2 of the search area, under one root
+    const double na = (double)n * n, nb = (double)p->wy * p->wx;
+    const double g2 = std::sqrt((na - 1.0) / na * (nb - 1.0) / nb);
+    p->std_gain2 = (float)g2;
+    p->std_gain = (float)std::sqrt(g2);   // the rescue pass scales each window by it: only the product of the two matters
+  }
+}
+
 static int dispatch_kernels(const lspiv::PivParams& p, int dtype, bool ensemble, hipStream_t s);
 
 // PIV kernel of the window's family, then -- per-timestep mode, unless switched off -- the float64 rescue pass over the
@@ -152,6 +176,11 @@ int apply_v_sign(float* d_v, int64_t n, hipStream_t s) {
 }
 
 static int dispatch_kernels(const lspiv::PivParams& p, int dtype, bool ensemble, hipStream_t s) {
+  if (p.nw) {   // search-area mode: per-pair kernels of the search area's transform size
+    if (ensemble) return fail(LSPIV_EUNSUPPORTED, "ensemble mode has no search-area kernels");
+    return launch_status(p.wy == 16 ? lspiv::launch_piv_search16(p, dtype, s) : p.wy == 32 ? lspiv::launch_piv_search32(p, dtype, s)
+                                                                                            : lspiv::launch_piv_search64(p, dtype, s));
+  }
   const int kind = lspiv_kernel_kind(p.wy, p.wx);
   hipError_t e;
   switch (kind) {
@@ -358,9 +387,10 @@ int lspiv_chunk_alignment_grid(int64_t H, int64_t W, int wy, int wx, int oy, int
   return chunk_alignment_for(wy, wx, g.n_rows * g.n_cols);
 }
 
-int lspiv_piv_pairs_dev_at(const void* d_frames, int dtype, int64_t T, int64_t H, int64_t W, int wy, int wx, int oy,
-                           int ox, float signal_threshold, int64_t pair_offset, float* d_out, float* d_corr_planes,
-                           void* stream) {
+// nw: 0, or the window inside the search area wy x wx (search-area mode)
+static int piv_pairs_dev(const void* d_frames, int dtype, int64_t T, int64_t H, int64_t W, int wy, int wx, int nw, int oy,
+                         int ox, float signal_threshold, int64_t pair_offset, float* d_out, float* d_corr_planes,
+                         void* stream) {
   if (!d_frames || !d_out) return fail(LSPIV_EINVAL, "d_frames / d_out is NULL");
   if (pair_offset < 0) return fail(LSPIV_EINVAL, "pair_offset %lld is negative", (long long)pair_offset);
   Grid g;
@@ -369,6 +399,7 @@ int lspiv_piv_pairs_dev_at(const void* d_frames, int dtype, int64_t T, int64_t H
   LSPIV_TRY(get_ctx(&c));
   lspiv::PivParams p;
   LSPIV_TRY(fill_params(&p, d_frames, dtype, T, H, W, wy, wx, oy, ox, signal_threshold, g));
+  if (nw) set_search_window(&p, nw);
   p.pair_offset = pair_offset;
   p.u = d_out;
   p.v = d_out + (size_t)p.n_tiles;
@@ -381,6 +412,21 @@ int lspiv_piv_pairs_dev_at(const void* d_frames, int dtype, int64_t T, int64_t H
   return apply_v_sign(p.v, (int64_t)p.n_tiles, s);
 }
 
+int lspiv_piv_pairs_dev_at(const void* d_frames, int dtype, int64_t T, int64_t H, int64_t W, int wy, int wx, int oy,
+                           int ox, float signal_threshold, int64_t pair_offset, float* d_out, float* d_corr_planes,
+                           void* stream) {
+  return piv_pairs_dev(d_frames, dtype, T, H, W, wy, wx, 0, oy, ox, signal_threshold, pair_offset, d_out, d_corr_planes, stream);
+}
+
+int lspiv_search_supported(int say, int sax, int wy, int wx) { return search_shape_ok(say, sax, wy, wx) ? 1 : 0; }
+
+int lspiv_piv_search_pairs_dev_at(const void* d_frames, int dtype, int64_t T, int64_t H, int64_t W, int say, int sax, int wy, int wx,
+                                  int oy, int ox, float signal_threshold, int64_t pair_offset, float* d_out, float* d_corr_planes,
+                                  void* stream) {
+  LSPIV_TRY(check_search(say, sax, wy, wx));
+  return piv_pairs_dev(d_frames, dtype, T, H, W, say, sax, wy, oy, ox, signal_threshold, pair_offset, d_out, d_corr_planes, stream);
+}
+
 int lspiv_piv_pairs_dev(const void* d_frames, int dtype, int64_t T, int64_t H, int64_t W, int wy, int wx, int oy,
                         int ox, float signal_threshold, float* d_out, float* d_corr_planes, void* stream) {
   return lspiv_piv_pairs_dev_at(d_frames, dtype, T, H, W, wy, wx, oy, ox, signal_threshold, 0, d_out, d_corr_planes, stream);
@@ -388,7 +434,8 @@ int lspiv_piv_pairs_dev(const void* d_frames, int dtype, int64_t T, int64_t H, i
 
 // the host entry point, optionally with the px -> m/s scaling of pyorc/velocimetry/ffpiv.py:418-419 applied on the device before the
 // results come back (dt != NULL: seconds per pair, T - 1 entries)
-static int piv_pairs_host(const void* frames, int dtype, int64_t T, int64_t H, int64_t W, int wy, int wx, int oy, int ox,
+// nw: 0, or the window inside the search area wy x wx (search-area mode)
+static int piv_pairs_host(const void* frames, int dtype, int64_t T, int64_t H, int64_t W, int wy, int wx, int nw, int oy, int ox,
                           float signal_threshold, int64_t pair_offset, float* u, float* v, float* corr_max, float* s2n,
                           float* corr_planes, const double* dt, double res_x, double res_y) {
   std::lock_guard<std::mutex> host_lock(locks_here().host);
@@ -414,12 +461,13 @@ static int piv_pairs_host(const void* frames, int dtype, int64_t T, int64_t H, i
   // the pipelined run issues exactly the jobs of one launch over the whole stack: same bits as lspiv_piv_pairs_dev_at.
   lspiv::PivParams base;
   LSPIV_TRY(fill_params(&base, c->d_frames, dev_dtype, T, H, W, wy, wx, oy, ox, signal_threshold, g));
+  if (nw) set_search_window(&base, nw);
   const size_t n_win = (size_t)g.n_rows * g.n_cols;
   const size_t frame_bytes = (size_t)H * W * elem_size(dev_dtype);
   LSPIV_TRY(stage_ring(c, frame_bytes));
   const int64_t fpb = std::max<int64_t>(1, (int64_t)(c->pinned_cap / frame_bytes));
   const bool src_pinned = dtype != LSPIV_F64 && is_pinned(frames);
-  const int64_t align = std::max(1, chunk_alignment_for(wy, wx, (int64_t)n_win));
+  const int64_t align = nw ? 1 : std::max(1, chunk_alignment_for(wy, wx, (int64_t)n_win));   // (the search-area kernels are per-pair)
   // "stack" signal mode scores a window position over ALL frames of the chunk: one launch once everything is resident
   const bool whole_chunk_only = g_opt_signal_mode.load() == 1 && signal_threshold >= 0.0f;
   int64_t launched = 0;   // pairs [0, launched) have been issued
@@ -474,14 +522,21 @@ static int piv_pairs_host(const void* frames, int dtype, int64_t T, int64_t H, i
 int lspiv_piv_pairs_at(const void* frames, int dtype, int64_t T, int64_t H, int64_t W, int wy, int wx, int oy, int ox,
                        float signal_threshold, int64_t pair_offset, float* u, float* v, float* corr_max, float* s2n,
                        float* corr_planes) {
-  return piv_pairs_host(frames, dtype, T, H, W, wy, wx, oy, ox, signal_threshold, pair_offset, u, v, corr_max, s2n, corr_planes, nullptr, 1.0, 1.0);
+  return piv_pairs_host(frames, dtype, T, H, W, wy, wx, 0, oy, ox, signal_threshold, pair_offset, u, v, corr_max, s2n, corr_planes, nullptr, 1.0, 1.0);
+}
+
+int lspiv_piv_search_pairs_at(const void* frames, int dtype, int64_t T, int64_t H, int64_t W, int say, int sax, int wy, int wx, int oy,
+                              int ox, float signal_threshold, int64_t pair_offset, float* u, float* v, float* corr_max, float* s2n,
+                              float* corr_planes) {
+  LSPIV_TRY(check_search(say, sax, wy, wx));
+  return piv_pairs_host(frames, dtype, T, H, W, say, sax, wy, oy, ox, signal_threshold, pair_offset, u, v, corr_max, s2n, corr_planes, nullptr, 1.0, 1.0);
 }
 
 int lspiv_piv_velocity_at(const void* frames, int dtype, int64_t T, int64_t H, int64_t W, int wy, int wx, int oy, int ox,
                           float signal_threshold, int64_t pair_offset, double res_x, double res_y, const double* dt, float* v_x, float* v_y,
                           float* corr_max, float* s2n) {
   if (!dt) return fail(LSPIV_EINVAL, "dt is NULL");
-  return piv_pairs_host(frames, dtype, T, H, W, wy, wx, oy, ox, signal_threshold, pair_offset, v_x, v_y, corr_max, s2n, nullptr, dt, res_x, res_y);
+  return piv_pairs_host(frames, dtype, T, H, W, wy, wx, 0, oy, ox, signal_threshold, pair_offset, v_x, v_y, corr_max, s2n, nullptr, dt, res_x, res_y);
 }
 
 int lspiv_piv_pairs(const void* frames, int dtype, int64_t T, int64_t H, int64_t W, int wy, int wx, int oy, int ox,

@@ -58,7 +58,8 @@ struct PivParams {
   const void* frames;      // device (T, H, W), dtype by template
   int64_t frame_elems;     // H * W
   int H, W;
-  int wy, wx;              // window (== search area, pyorc/api/frames.py:168)
+  int wy, wx;              // the search area = the tile cut from frame t+1 and the size of the plane; also the window cut from frame t unless nw is set
+  int nw;                  // 0, or the side n of the square interrogation window of frame t, centred in the search area (search-area kernels, piv_fft_impl.h)
   int sy, sx;              // window stride = window - overlap
   int n_rows, n_cols;
   uint32_t n_win;          // n_rows * n_cols
@@ -395,6 +396,10 @@ hipError_t launch_piv_dft_global(const PivParams& p, int dtype, bool ensemble, h
 hipError_t launch_piv_embed16(const PivParams& p, int dtype, bool ensemble, hipStream_t s);
 hipError_t launch_piv_embed32(const PivParams& p, int dtype, bool ensemble, hipStream_t s);
 hipError_t launch_piv_embed64(const PivParams& p, int dtype, bool ensemble, hipStream_t s);
+// an even square window p.nw, 4 .. S - 2, searched inside a search area S = p.wy = p.wx = 16 / 32 / 64 (per-timestep mode only)
+hipError_t launch_piv_search16(const PivParams& p, int dtype, hipStream_t s);
+hipError_t launch_piv_search32(const PivParams& p, int dtype, hipStream_t s);
+hipError_t launch_piv_search64(const PivParams& p, int dtype, hipStream_t s);
 // float64 re-evaluation of the windows the PIV kernel of this pass appended to p.rescue_* (piv_rescue.hip)
 hipError_t launch_piv_rescue(const PivParams& p, int dtype, hipStream_t s);
 // ensemble mode: flag the windows of the float32 mean planes (u, v = their float32 fits) whose fit cannot be trusted; partial

@@ -525,6 +525,118 @@ __device__ __forceinline__ void prepare_pair_embed(const PivParams& p, const Til
   }
 }
 
+// ---- search-area mode: an n x n window of frame t searched inside the N x N area of frame t+1 (N = 16, 32, 64) -------------
+// The window of frame t+1 is the real N x N surrounding of the n x n window, not a periodic copy: B = the N x N tile of frame
+// t+1 normalised over its N^2 samples (the regular loader), A = the central n x n block of frame t's tile, offset o = (N - n) / 2
+// in both axes, normalised over its own n^2 samples and placed at offset o in an N x N array of zeros.  Both are N x N arrays,
+// so the packed transform, the Hermitian cross spectrum, the shared inverse and the full-plane epilogue of the N-point kernel
+// serve unchanged; lag k of the circular N-point correlation is sum_m a[m] B[m + o + k], i.e. zero displacement sits at lag 0
+// (the plane centre after the fftshift), and lags |k| <= o never wrap.  Scale: 1 / (std_a std_b n^2).
+// One row of any sample type as floats (the whole N x N tile is inside the frame: vector loads, no bounds)
+template <typename T, int N>
+__device__ __forceinline__ void load_row_any(const T* row, float (&x)[N]) {
+  if constexpr (sizeof(T) == 1) {
+    RowRaw<uint8_t, N> raw;
+    raw.fetch(reinterpret_cast<const uint8_t*>(row));
+#pragma unroll
+    for (int k = 0; k < N / 4; ++k) {
+      const uint32_t w = raw.w[k];
+      x[4 * k + 0] = (float)(w & 0xffu);
+      x[4 * k + 1] = (float)((w >> 8) & 0xffu);
+      x[4 * k + 2] = (float)((w >> 16) & 0xffu);
+      x[4 * k + 3] = (float)(w >> 24);
+    }
+  } else if constexpr (sizeof(T) == 4) {
+    load_row_f32<N>(reinterpret_cast<const float*>(row), x);
+  } else {
+#pragma unroll
+    for (int k = 0; k < N / 2; ++k) {
+      const f64x2 v = *reinterpret_cast<const f64x2_u*>(row + 2 * k);
+      x[2 * k + 0] = (float)v[0]; x[2 * k + 1] = (float)v[1];
+    }
+  }
+}
+// The masked window of frame t: derived from load_center_embed (non-periodic), the block at offset o instead of the corner.
+// "column j belongs to the block" is a uniform scalar test, "this lane's row belongs to it" one lane mask; samples outside the
+// block are dropped by selects, not products, so that a non-finite sample outside the block stays out of the statistics.
+// x0 = the block's first sample (shifted mean: a constant block has exactly zero variance).  Returns 1 / std (0: zero variance).
+template <typename T, int N, bool WANT_NZ>
+__device__ __forceinline__ float load_center_masked(const T* row, float x0, int o, int n, bool row_in, bool nz_pos,
+                                                    float (&x)[N], int& nonzero, bool& finite) {
+  const float inv_nn = 1.0f / (float)(n * n);
+  load_row_any<T, N>(row, x);
+  float s[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+  int nz = 0;
+#pragma unroll
+  for (int j = 0; j < N; ++j) {
+    const bool in = (unsigned)(j - o) < (unsigned)n;
+    s[j & 3] += in ? x[j] - x0 : 0.0f;
+    if (WANT_NZ) nz += (in && (nz_pos ? x[j] > 0.0f : x[j] != 0.0f)) ? 1 : 0;
+  }
+  if (WANT_NZ) nonzero = group_sum_i<N>(row_in ? nz : 0);
+  const float mean = x0 + group_sum<N>(row_in ? (s[0] + s[1]) + (s[2] + s[3]) : 0.0f) * inv_nn;
+  float q[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+#pragma unroll
+  for (int j = 0; j < N; ++j) {
+    const bool in = (unsigned)(j - o) < (unsigned)n;
+    const float d = x[j] - mean;
+    q[j & 3] += in ? d * d : 0.0f;
+    x[j] = (in && row_in) ? fmaxf(d, 0.0f) : 0.0f;
+  }
+  const float qq = group_sum<N>(row_in ? (q[0] + q[1]) + (q[2] + q[3]) : 0.0f);
+  finite = finite && (fabsf(mean) <= 3.0e38f) && (qq <= 3.0e38f);
+  const float var = qq * inv_nn;
+  return var > 0.0f ? __builtin_amdgcn_rsqf(var) : 0.0f;
+}
+// 64-point search: ONE window per job, as in the 64-point embedding (the half spectrum of window 0 does not survive window 1's
+// masked statistics inside 256 VGPRs)
+template <int N> constexpr bool kSearchSingle = N == 64;
+template <typename T, int N, bool WANT_NZ>
+__device__ __forceinline__ void prepare_pair_search(const PivParams& p, const TileRef& t, int lg, float (&xr)[N],
+                                                    float (&xi)[N], float& scale, float& hi, bool& skip) {
+  static_assert(Geo<N>::FULL && N % 16 == 0, "search areas are 16, 32 or 64 px");
+  const int n = p.nw, o = (N - n) >> 1;
+  const float inv_nn = 1.0f / (float)(n * n);
+  const T* frames = static_cast<const T*>(p.frames);
+  const uint32_t wrow = p.div_ncols.div(t.win);
+  const uint32_t wcol = t.win - wrow * (uint32_t)p.n_cols;
+  const int64_t base = ((int64_t)t.pair * p.H + (int64_t)wrow * p.sy) * p.W + (int64_t)wcol * p.sx;
+  const bool row_in = (unsigned)(lg - o) < (unsigned)n;
+  const bool nz_pos = p.nz_positive != 0;
+  bool finite = true;
+  int nza = 0, nzb = Geo<N>::NN;
+  const float x0 = to_f32(frames[base + (int64_t)o * p.W + o]);
+  const float inv_a = load_center_masked<T, N, WANT_NZ>(frames + base + (int64_t)lg * p.W, x0, o, n, row_in, nz_pos, xr, nza, finite);
+  __builtin_amdgcn_sched_barrier(0);   // one window after the other
+  const T* rowb = frames + base + p.frame_elems + (int64_t)lg * p.W;
+  float inv_b, rho;
+  if constexpr (sizeof(T) == 1) {
+    RowRaw<uint8_t, N> rb;
+    rb.fetch(reinterpret_cast<const uint8_t*>(rowb));
+    const RowStats sb = stats_u8<N>(rb, WANT_NZ, nzb);
+    inv_b = sb.inv_std;
+    rho = (inv_a == 0.0f || inv_b == 0.0f) ? 0.0f : inv_b * __builtin_amdgcn_rcpf(inv_a);
+    center_u8<N>(rb, sb.mean, rho, xi);   // the balance factor rides on the conversion (prepare_pair)
+  } else {
+    RowRaw<T, N> rb;
+    rb.fetch(rowb);
+    inv_b = load_center<N>(rb, xi, WANT_NZ, nz_pos, nzb, finite);
+    rho = (inv_a == 0.0f || inv_b == 0.0f) ? 0.0f : inv_b * __builtin_amdgcn_rcpf(inv_a);
+#pragma unroll
+    for (int j = 0; j < N; ++j) xi[j] *= rho;
+  }
+  const bool dead = (inv_a == 0.0f) || (inv_b == 0.0f);
+  // plane = (unnormalised inverse N x N transform) / N^2 / n^2, and the cross-spectrum formula carries a factor 4
+  scale = dead ? 0.0f : inv_a * inv_a * inv_nn * (1.0f / (4.0f * (float)Geo<N>::NN)) * p.std_gain2;
+  hi = dead ? 0.0f : 1.0f;
+  skip = !finite;
+  if (WANT_NZ) {
+    const float fa = (float)nza * inv_nn, fb = (float)nzb * (1.0f / Geo<N>::NN);   // the window over n^2, the search area over N^2
+    skip = skip || !(fa >= p.signal_threshold && fb >= p.signal_threshold);
+    if (p.win_keep) skip = skip || !p.win_keep[t.win];   // "stack" mode: one score per window position (A7)
+  }
+}
+
 // one row of a parked plane <-> registers: ds_read/write_b128, plus one b64 for the two last samples when N % 4 == 2
 typedef float f32x2 __attribute__((ext_vector_type(2)));
 template <int N>
@@ -671,7 +783,7 @@ __device__ __forceinline__ void cross_spectrum_half(int partner_byte, const floa
 // Everything between "two window pairs" and "two clipped correlation planes in registers".
 // On return xr = plane of tile 0, xi = plane of tile 1, natural (un-shifted) order: lane = row y,
 // register = column x;  skip[k] = plane k is NaN (signal pre-mask / non-finite input).
-template <typename T, int N, bool WANT_NZ, bool EMBED = false>
+template <typename T, int N, bool WANT_NZ, bool EMBED = false, bool SEARCH = false>
 __device__ __forceinline__ void correlate_job(const PivParams& p, const TileRef (&t)[2], float* buf, int lg,
                                               int partner_byte, float (&xr)[N], float (&xi)[N], bool (&skip)[2],
                                               float (&mean)[2]) {
@@ -691,12 +803,12 @@ __device__ __forceinline__ void correlate_job(const PivParams& p, const TileRef 
   };
   // uint8 rows (8 VGPRs each) are all fetched up front; wider samples are addressed only when their window's turn
   // comes -- four live 64-bit row pointers were exactly the 8 VGPRs that kept the float kernel above 128
-  if constexpr (sizeof(T) == 1 && !EMBED) { fetch_rows(0); fetch_rows(1); }
+  if constexpr (sizeof(T) == 1 && !EMBED && !SEARCH) { fetch_rows(0); fetch_rows(1); }
   // 64-point embedding: ONE window per job.  Holding window 0's half spectrum (66 VGPRs) through window 1's scalar
   // loads and masked statistics does not fit 256 VGPRs (200-900 B/lane of scratch, and slower than doing without the
   // shared inverse), so the second slot of the inverse transform stays empty there: 2 instead of 1.5 transforms per
   // window, no spills.
-  constexpr bool SINGLE = EMBED && N == 64;
+  constexpr bool SINGLE = (EMBED && N == 64) || (SEARCH && kSearchSingle<N>);
 #pragma unroll
   for (int k = 0; k < 2; ++k) {
     // keep the two windows' register-hungry phases apart: the scheduler otherwise interleaves window 1's
@@ -719,6 +831,8 @@ __device__ __forceinline__ void correlate_job(const PivParams& p, const TileRef 
     }
     if constexpr (EMBED) {
       prepare_pair_embed<T, N, WANT_NZ>(p, t[k], lg, xr, xi, scale, hi[k], skip[k]);
+    } else if constexpr (SEARCH) {
+      prepare_pair_search<T, N, WANT_NZ>(p, t[k], lg, xr, xi, scale, hi[k], skip[k]);
     } else {
       if constexpr (sizeof(T) != 1) fetch_rows(k);
       prepare_pair(raw[k][0], raw[k][1], xr, xi, want_nz, p.signal_threshold, p.nz_positive != 0, scale, hi[k], skip[k]);
@@ -1864,6 +1978,109 @@ static hipError_t launch_embed(const PivParams& p, int dtype, bool ensemble, hip
     case 0: return nz ? launch_embed_t<uint8_t, N, true>(p, ensemble, s) : launch_embed_t<uint8_t, N, false>(p, ensemble, s);
     case 1: return nz ? launch_embed_t<float, N, true>(p, ensemble, s) : launch_embed_t<float, N, false>(p, ensemble, s);
     case 2: return nz ? launch_embed_t<double, N, true>(p, ensemble, s) : launch_embed_t<double, N, false>(p, ensemble, s);
+    default: return hipErrorInvalidValue;
+  }
+}
+
+// ---- search-area kernel: per pair, no walking (the window of frame t differs from the previous pair's search area, so no
+// spectrum can be carried); piv_fft_kernel's job layout and full-plane epilogue over the N x N plane -------------------------
+// The plane can exceed 1 before the clip (Cauchy-Schwarz bounds it by N / n, not 1: the search area is normalised over N^2
+// samples, the sum runs over n^2 of them), so the upper clip binds for real; the plane mean is then no longer the DC bin and is
+// summed from the clipped plane (a cold, wave-uniform branch).
+// registers (no scratch at these bounds): 16-point 80 - 131 VGPRs, three waves per SIMD (float64 rows with the signal score spill 12 bytes
+// at four); 32-point 134 - 164 without the signal score (three waves), 186 - 245 with it (two: at three it spills 72 - 312 bytes per lane);
+// 64-point, one window per job, 186 - 241 (two waves)
+template <int N, bool WANT_NZ> constexpr int kSearchWaves = N <= 16 ? 3 : (N == 32 && !WANT_NZ) ? 3 : 2;
+template <int N>
+__device__ __forceinline__ float search_plane_mean(const float (&c)[N], float vmax, float dc) {
+  if (__builtin_amdgcn_ballot_w64(vmax >= 1.0f) == 0) return dc;
+  const float s = group_sum<N>(tree_sum<N>(c)) * (1.0f / Geo<N>::NN);
+  return vmax >= 1.0f ? s : dc;
+}
+template <typename T, int N, bool PLANES, bool WANT_NZ>
+__global__ __launch_bounds__(BLOCK, (kSearchWaves<N, WANT_NZ>)) void piv_fft_search_kernel(PivParams p) {
+  extern __shared__ __attribute__((aligned(16))) float smem[];
+  using G = Geo<N>;
+  const int lane = threadIdx.x & 63;
+  const int wave = threadIdx.x >> 6;
+  const int grp = lane / G::LG;
+  const int lg = lane & (G::LG - 1);
+  float* buf = smem + (wave * G::GROUPS + grp) * G::LDS_JOB;
+  const int partner_byte = partner_byte_of<N>(lane, lg);
+  const uint32_t nb = gridDim.x;                                   // XCD-aware block order, as piv_fft_kernel
+  const uint32_t q = nb >> 3, r = nb & 7u;
+  const uint32_t xcd = blockIdx.x & 7u, slot = blockIdx.x >> 3;
+  const uint32_t blk = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + slot;
+  constexpr bool SINGLE = kSearchSingle<N>;
+  // windows (2j, 2j+1) of ONE pair share an inverse transform: the partner is fixed by the grid, results do not depend on the chunking
+  const uint32_t jobs_per_pair = SINGLE ? p.n_win : (p.n_win + 1) >> 1;
+  uint32_t job = (blk * WAVES_PER_BLOCK + wave) * G::GROUPS + grp;
+  const bool job_valid = job < p.n_pairs * jobs_per_pair;
+  job = job_valid ? job : p.n_pairs * jobs_per_pair - 1;
+  const uint32_t pair = SINGLE ? p.div_nwin.div(job) : p.div_jobs.div(job);
+  const uint32_t w0 = (job - pair * jobs_per_pair) * (SINGLE ? 1 : 2);
+  TileRef t[2];
+  t[0].pair = t[1].pair = pair;
+  t[0].win = w0;
+  t[0].valid = job_valid;
+  t[1].valid = !SINGLE && job_valid && (w0 + 1 < p.n_win);
+  t[1].win = (!SINGLE && w0 + 1 < p.n_win) ? w0 + 1 : w0;
+
+  float xr[N], xi[N], mean[2];
+  bool skip[2];
+  correlate_job<T, N, WANT_NZ, false, true>(p, t, buf, lg, partner_byte, xr, xi, skip, mean);
+
+  const float nanv = __builtin_nanf("");
+  {
+    float row_max, u, v;
+    const uint32_t g = t[0].pair * p.n_win + t[0].win;
+    const float vmax = plane_max<N>(xr, row_max);
+    find_peak<N>(buf, lg, xr, vmax, row_max, p, u, v, p.rescue_hdr && t[0].valid && !skip[0], g);
+    float cm = vmax, sn = vmax * __builtin_amdgcn_rcpf(search_plane_mean<N>(xr, vmax, mean[0]));
+    if (skip[0]) u = v = cm = sn = nanv;
+    if (t[0].valid && lg == 0) {
+      p.u[g] = u; p.v[g] = v; p.cmax[g] = cm; p.s2n[g] = sn;
+    }
+  }
+  if constexpr (!SINGLE) {
+    float row_max, u, v;
+    const uint32_t g = t[1].pair * p.n_win + t[1].win;
+    const float vmax = plane_max<N>(xi, row_max);
+    find_peak<N>(buf, lg, xi, vmax, row_max, p, u, v, p.rescue_hdr && t[1].valid && !skip[1], g);
+    float cm = vmax, sn = vmax * __builtin_amdgcn_rcpf(search_plane_mean<N>(xi, vmax, mean[1]));
+    if (skip[1]) u = v = cm = sn = nanv;
+    if (t[1].valid && lg == 0) {
+      p.u[g] = u; p.v[g] = v; p.cmax[g] = cm; p.s2n[g] = sn;
+    }
+  }
+  if constexpr (PLANES) {
+    if (t[0].valid) store_plane_rows<N>(p.planes + ((size_t)t[0].pair * p.n_win + t[0].win) * G::NN, lg, xr, skip[0]);
+    if constexpr (!SINGLE) {
+      if (t[1].valid) store_plane_rows<N>(p.planes + ((size_t)t[1].pair * p.n_win + t[1].win) * G::NN, lg, xi, skip[1]);
+    }
+  }
+}
+
+template <typename T, int N, bool WANT_NZ>
+static hipError_t launch_search_t(const PivParams& p, hipStream_t s) {
+  using G = Geo<N>;
+  constexpr uint32_t jobs_per_block = WAVES_PER_BLOCK * G::GROUPS;
+  const uint32_t jobs = p.n_pairs * (kSearchSingle<N> ? p.n_win : (p.n_win + 1) / 2);
+  const uint32_t blocks = (jobs + jobs_per_block - 1) / jobs_per_block;
+  if (p.planes)
+    hipLaunchKernelGGL((piv_fft_search_kernel<T, N, true, WANT_NZ>), dim3(blocks), dim3(BLOCK), G::LDS_BYTES, s, p);
+  else
+    hipLaunchKernelGGL((piv_fft_search_kernel<T, N, false, WANT_NZ>), dim3(blocks), dim3(BLOCK), G::LDS_BYTES, s, p);
+  return hipGetLastError();
+}
+template <int N>
+static hipError_t launch_search(const PivParams& p, int dtype, hipStream_t s) {
+  if (p.wy != N || p.wx != N || p.nw < 4 || p.nw > N - 2 || (p.nw & 1)) return hipErrorInvalidValue;
+  const bool nz = p.signal_threshold >= 0.0f;
+  switch (dtype) {
+    case 0: return nz ? launch_search_t<uint8_t, N, true>(p, s) : launch_search_t<uint8_t, N, false>(p, s);
+    case 1: return nz ? launch_search_t<float, N, true>(p, s) : launch_search_t<float, N, false>(p, s);
+    case 2: return nz ? launch_search_t<double, N, true>(p, s) : launch_search_t<double, N, false>(p, s);
     default: return hipErrorInvalidValue;
   }
 }

@@ -100,6 +100,27 @@ __device__ __forceinline__ void window_stats_wave2(const T* A, const T* B, int W
   sd_b = vb > 0.0 ? sqrt(vb) : 0.0;
 }
 
+// search-area mode (p.nw != 0; piv_fft_impl.h): the window of frame t is the central nw x nw block of its wy x wx tile, normalised over
+// its own samples and zero elsewhere ("masked a"), the window of frame t+1 the whole tile; the sums are scaled by 1 / nw^2 and stay
+// circular at the tile size.  p.nw == 0: everything below is what it was.
+__device__ __forceinline__ bool a_inside(const PivParams& p, int y, int x) {
+  const int o = (p.wy - p.nw) >> 1;
+  return p.nw == 0 || ((unsigned)(y - o) < (unsigned)p.nw && (unsigned)(x - o) < (unsigned)p.nw);
+}
+__device__ __forceinline__ double corr_samples(const PivParams& p) { return p.nw ? (double)p.nw * (double)p.nw : (double)p.wy * (double)p.wx; }
+// statistics of both windows of a pair: over the tile, and -- search-area mode -- those of frame t again over its block
+template <typename T, bool STAGE = false>
+__device__ __forceinline__ void pair_stats_wave(const PivParams& p, const T* A, const T* B, int lane, double& mean_a, double& sd_a,
+                                                double& mean_b, double& sd_b, T* la = nullptr, T* lb = nullptr) {
+  window_stats_wave2<T, STAGE>(A, B, p.W, p.wy, p.wx, lane, mean_a, sd_a, mean_b, sd_b, la, lb);
+  if (p.nw) {
+    const int o = (p.wy - p.nw) >> 1;
+    const T* Ab = A + (int64_t)o * p.W + o;
+    double mb, sb;
+    window_stats_wave2<T, false>(Ab, Ab, p.W, p.nw, p.nw, lane, mean_a, sd_a, mb, sb);
+  }
+}
+
 // max((x - mean) / std, 0) with the reciprocal of std formed once per window (1 ulp of float64 from the division)
 // (inv_sd < 0 encodes the "norm_clip" = 0 option: |inv_sd| is the factor and the negative lobes stay)
 __device__ __forceinline__ double norm_clip(double x, double mean, double inv_sd) {
@@ -123,7 +144,7 @@ __device__ __forceinline__ uint32_t choose_wave(const PivParams& p, PA A, PA B, 
   lw.start(lane, y, x);
 #pragma unroll 4
   for (int e = lane; e < n; e += 64, lw.next(y, x)) {
-    const double av = norm_clip((double)A[y * pitch + x], mean_a, inv_a);
+    const double av = a_inside(p, y, x) ? norm_clip((double)A[y * pitch + x], mean_a, inv_a) : 0.0;
     int y1 = y + ky1; y1 = y1 >= wy ? y1 - wy : y1;
     int x1 = x + kx1; x1 = x1 >= wx ? x1 - wx : x1;
     int y2 = y + ky2; y2 = y2 >= wy ? y2 - wy : y2;
@@ -154,7 +175,7 @@ __device__ __forceinline__ Lag5 lag5_wave(const PivParams& p, PA A, PA B, int pi
   lw.start(lane, y, x);
 #pragma unroll 4
   for (int e = lane; e < n; e += 64, lw.next(y, x)) {
-    const double av = norm_clip((double)A[y * pitch + x], mean_a, inv_a);
+    const double av = a_inside(p, y, x) ? norm_clip((double)A[y * pitch + x], mean_a, inv_a) : 0.0;
     int y0 = y + ky0; y0 = y0 >= wy ? y0 - wy : y0;
     int ym = y + kym; ym = ym >= wy ? ym - wy : ym;
     int yp = y + kyp; yp = yp >= wy ? yp - wy : yp;
@@ -167,7 +188,7 @@ __device__ __forceinline__ Lag5 lag5_wave(const PivParams& p, PA A, PA B, int pi
     accl += av * norm_clip((double)B[y0 * pitch + xm], mean_b, inv_b);
     accr += av * norm_clip((double)B[y0 * pitch + xp], mean_b, inv_b);
   }
-  const double inv_n = 1.0 / (double)n;
+  const double inv_n = 1.0 / corr_samples(p);
   auto clip01 = [](double c) { return c < 0.0 ? 0.0 : (c > 1.0 ? 1.0 : c); };
   Lag5 o;
   o.c0 = clip01(wave_sum_d(acc0) * inv_n); o.cu = clip01(wave_sum_d(accu) * inv_n); o.cd = clip01(wave_sum_d(accd) * inv_n);
@@ -254,8 +275,8 @@ __global__ __launch_bounds__(RBLOCK) void piv_rescue_fit_kernel(PivParams p) {
     const T* A = window_base<T>(p, g);
     const T* B = A + p.frame_elems;
     double mean_a, sd_a, mean_b, sd_b;
-    if (staged) window_stats_wave2<T, true>(A, B, p.W, wy, wx, lane, mean_a, sd_a, mean_b, sd_b, la, lb);
-    else window_stats_wave2<T, false>(A, B, p.W, wy, wx, lane, mean_a, sd_a, mean_b, sd_b, nullptr, nullptr);
+    if (staged) pair_stats_wave<T, true>(p, A, B, lane, mean_a, sd_a, mean_b, sd_b, la, lb);
+    else pair_stats_wave<T, false>(p, A, B, lane, mean_a, sd_a, mean_b, sd_b);
     // (a zero-variance window is NaN already and is never listed)
     if (sd_a != 0.0 && sd_b != 0.0) {
       const double sg = p.norm_clip ? (double)p.std_gain : -(double)p.std_gain;   // options "std_ddof" / "norm_clip"
@@ -303,7 +324,7 @@ __global__ __launch_bounds__(RBLOCK) void piv_rescue_amb_kernel(PivParams p) {
     const T* A = window_base<T>(p, g);
     const T* B = A + p.frame_elems;
     double mean_a, sd_a, mean_b, sd_b;
-    window_stats_wave2<T>(A, B, p.W, wy, wx, lane, mean_a, sd_a, mean_b, sd_b);   // every wave computes the same totals
+    pair_stats_wave<T>(p, A, B, lane, mean_a, sd_a, mean_b, sd_b);   // every wave computes the same totals
     const bool dead = sd_a == 0.0 || sd_b == 0.0;   // never listed; kept out of the control flow around the barriers below
     const double sg = p.norm_clip ? (double)p.std_gain : -(double)p.std_gain;   // options "std_ddof" / "norm_clip"
     const double inv_a = dead ? 1.0 : sg / sd_a, inv_b = dead ? 1.0 : sg / sd_b;
@@ -312,7 +333,7 @@ __global__ __launch_bounds__(RBLOCK) void piv_rescue_amb_kernel(PivParams p) {
     if (fast) {
       for (int e = threadIdx.x; e < n; e += RBLOCK) {
         const int y = e / wx, x = e - y * wx;
-        la[e] = norm_clip((double)A[(int64_t)y * p.W + x], mean_a, inv_a);
+        la[e] = a_inside(p, y, x) ? norm_clip((double)A[(int64_t)y * p.W + x], mean_a, inv_a) : 0.0;
         const double bv = norm_clip((double)B[(int64_t)y * p.W + x], mean_b, inv_b);
         lb2[y * pitch + x] = bv;
         lb2[y * pitch + wx + x] = bv;
@@ -359,7 +380,7 @@ __global__ __launch_bounds__(RBLOCK) void piv_rescue_amb_kernel(PivParams p) {
         for (int r = 0; r < AMB_R; ++r) {
           const int kx = kx0 + r;
           const int jpo = kx + cx >= wx ? kx + cx - wx : kx + cx;
-          double c = acc[r] / (double)n;
+          double c = acc[r] / corr_samples(p);
           c = c < 0.0 ? 0.0 : (c > 1.0 ? 1.0 : c);
           amax_merge_d(best, bi, c, ipo * wx + jpo);
         }
@@ -376,13 +397,13 @@ __global__ __launch_bounds__(RBLOCK) void piv_rescue_amb_kernel(PivParams p) {
         for (int y = 0; y < wy; ++y) {
           int xb = kx;
           for (int x = 0; x < wx; ++x) {
-            const double av = norm_clip((double)A[(int64_t)y * p.W + x], mean_a, inv_a);
+            const double av = a_inside(p, y, x) ? norm_clip((double)A[(int64_t)y * p.W + x], mean_a, inv_a) : 0.0;
             if (av != 0.0) acc += av * norm_clip((double)B[(int64_t)yb * p.W + xb], mean_b, inv_b);
             xb = xb + 1 == wx ? 0 : xb + 1;
           }
           yb = yb + 1 == wy ? 0 : yb + 1;
         }
-        double c = acc / (double)n;
+        double c = acc / corr_samples(p);
         c = c < 0.0 ? 0.0 : (c > 1.0 ? 1.0 : c);
         amax_merge_d(best, bi, c, o);
       }

@@ -28,12 +28,20 @@ from . import velocimetry, window
 ENGINES = ["hip"]
 
 
-def resolve_window(window_size, overlap=None) -> Tuple[Tuple[int, int], Tuple[int, int], Tuple[int, int]]:
-    """(window_size, search_area_size, overlap) as pyorc/api/frames.py:159-171 derives them."""
+def resolve_window(window_size, overlap=None, search_area_size=None) -> Tuple[Tuple[int, int], Tuple[int, int], Tuple[int, int]]:
+    """(window_size, search_area_size, overlap) as pyorc/api/frames.py:159-171 derives them.  ``search_area_size``: None = the window
+    size (the reference's only choice), else an int or a pair, rounded to even like the window; a default ``overlap`` is then half the
+    SEARCH AREA, which is what the grid is laid out by."""
     if window_size is None:
         raise ValueError("window_size is required when frames carry no camera configuration")
     ws = 2 * (window_size,) if isinstance(window_size, (int, np.integer)) else tuple(window_size)
     ws_even = window.round_to_even(ws)
+    if search_area_size is not None:
+        sa = 2 * (search_area_size,) if isinstance(search_area_size, (int, np.integer)) else tuple(search_area_size)
+        sa_even = window.round_to_even(sa)
+        if overlap is None:
+            overlap = tuple(int(round(s) / 2) for s in sa_even)
+        return ws_even, sa_even, tuple(int(o) for o in overlap)
     if overlap is None:
         if isinstance(window_size, (int, np.integer)):
             overlap = 2 * (int(round(window_size) / 2),)
@@ -52,12 +60,13 @@ def get_piv_coords(dim_size, window_size, search_area_size, overlap, x=None, y=N
 
 
 def get_piv(frames, window_size=None, overlap=None, engine: str = "hip", ensemble_corr: bool = False,
-            time=None, resolution: Optional[float] = None, **kwargs):
+            time=None, resolution: Optional[float] = None, search_area_size=None, **kwargs):
     """PIV on projected frames with the MI355X engine; parameters of ``Frames.get_piv`` (frames.py:114-121).
 
     Extra keywords for plain arrays: ``time`` (T,) seconds (default ``arange(T)``), ``resolution`` metres per
     pixel (default 1.0 => velocities in px/s).  ``**kwargs`` are forwarded to ``get_ffpiv`` (``chunksize``,
-    ``memory_factor``, ``corr_min``, ``s2n_min``, ``count_min``, ``signal_threshold``).
+    ``memory_factor``, ``corr_min``, ``s2n_min``, ``count_min``, ``signal_threshold``).  ``search_area_size``: None (the window size,
+    as in the reference) or a larger square search area of 16, 32 or 64 px ("Extended search area").
     """
     if engine not in ENGINES:
         raise ValueError(f"Selected PIV engine {engine} does not exist.")
@@ -71,7 +80,7 @@ def get_piv(frames, window_size=None, overlap=None, engine: str = "hip", ensembl
             camera_config.window_size = window_size
         window_size = camera_config.window_size
         resolution = camera_config.resolution if resolution is None else resolution
-    ws, sa, ov = resolve_window(window_size, overlap)
+    ws, sa, ov = resolve_window(window_size, overlap, search_area_size)
     if is_xr:
         t = frames["time"]
         dt = t.diff(dim="time")

@@ -31,13 +31,11 @@ def _check_args(window_size, overlap, search_area_size, normalize, engine):
         raise ValueError(f"Selected PIV engine {engine} does not exist.")
     if normalize:
         raise NotImplementedError("stack-level `normalize` is never used by pyorc (ffpiv.py:227,455)")
-    sa = tuple(window_size) if search_area_size is None else tuple(search_area_size)
-    if sa != tuple(window_size):
-        raise NotImplementedError("search_area_size must equal window_size (pyorc/api/frames.py:168)")
+    return window.search_spec(window_size, search_area_size)   # ValueError for an unsupported combination
 
 
 def piv_pairs(imgs, window_size=(32, 32), overlap=(16, 16), signal_threshold: Optional[float] = None,
-              return_planes: bool = False, pair_offset: int = 0, out=None, scale=None):
+              return_planes: bool = False, pair_offset: int = 0, out=None, scale=None, search_area_size=None):
     """Fused PIV of every consecutive frame pair of ``imgs`` (T, H, W).
 
     Returns ``(u, v, corr_max, s2n[, planes])``: float32 arrays (T-1, n_rows, n_cols); u, v in
@@ -49,7 +47,12 @@ def piv_pairs(imgs, window_size=(32, 32), overlap=(16, 16), signal_threshold: Op
     ``scale = (res_x, res_y, dt)``: u, v come back in metres per second, ``(u * res_x / dt[:, None, None]).astype(float32)`` (ffpiv.py:
     418-419) computed on the device before the results cross PCIe -- float32 product, float64 division, one rounding: numpy's own
     arithmetic for PYTHON-FLOAT resolutions (the caller checks that, :func:`device_scaling_is_numpys`); ``dt``: (T-1,) float64 seconds.
+    ``search_area_size``: None / the window size (today's path), or a larger square search area of 16, 32 or 64 px in which the even
+    square window of frame t is searched in frame t+1 ("Extended search area"): the grid, ``overlap`` and the planes
+    (``say x sax`` each) are then those of the search area.  ``window_size`` may also be a ``window.SearchWindow``.
     """
+    window_size = window.search_spec(window_size, search_area_size)
+    search = isinstance(window_size, window.SearchWindow)
     lib = _lib.load()
     _lib.require_device()
     a = imgs if is_device(imgs) else _lib.as_frames(imgs)
@@ -78,6 +81,16 @@ def piv_pairs(imgs, window_size=(32, 32), overlap=(16, 16), signal_threshold: Op
     planes = None
     if return_planes:
         planes = np.empty((P, n_rows * n_cols, window_size[0], window_size[1]), dtype=np.float32)
+    if search:
+        n = window_size.window
+        _lib.check(lib.lspiv_piv_search_pairs_at(_lib.ptr(a), _lib.DTYPE_CODES[a.dtype], T, H, W, window_size[0], window_size[1], n[0], n[1],
+                                                 overlap[0], overlap[1], _sig(signal_threshold), int(pair_offset),
+                                                 _lib.ptr(out[0]), _lib.ptr(out[1]), _lib.ptr(out[2]), _lib.ptr(out[3]),
+                                                 _lib.ptr(planes) if planes is not None else None))
+        if scale is not None:   # no fused scaling entry point for this mode: numpy's own arithmetic (ffpiv.py:418-419)
+            for k in range(2):
+                np.divide(out[k] * scale[k], dt[:, None, None], out=out[k], dtype=np.float64, casting="same_kind")
+        return (*out, planes) if return_planes else tuple(out)
     if scale is not None:
         _lib.check(lib.lspiv_piv_velocity_at(_lib.ptr(a), _lib.DTYPE_CODES[a.dtype], T, H, W, window_size[0], window_size[1],
                                              overlap[0], overlap[1], _sig(signal_threshold), int(pair_offset), float(scale[0]), float(scale[1]),
@@ -105,9 +118,15 @@ def _piv_pairs_device(a, window_size, overlap, signal_threshold, return_planes, 
     P, n_win = T - 1, n_rows * n_cols
     d_out = DeviceFrames.empty((4, P, n_win), np.float32)
     d_planes = DeviceFrames.empty((P * n_win, window_size[0], window_size[1]), np.float32) if return_planes else None
-    _lib.check(lib.lspiv_piv_pairs_dev_at(a.c_ptr, a.dtype_code, T, H, W, window_size[0], window_size[1], overlap[0], overlap[1],
-                                          _sig(signal_threshold), int(pair_offset), d_out.c_ptr,
-                                          d_planes.c_ptr if d_planes is not None else None, None))
+    if isinstance(window_size, window.SearchWindow):
+        n = window_size.window
+        _lib.check(lib.lspiv_piv_search_pairs_dev_at(a.c_ptr, a.dtype_code, T, H, W, window_size[0], window_size[1], n[0], n[1],
+                                                     overlap[0], overlap[1], _sig(signal_threshold), int(pair_offset), d_out.c_ptr,
+                                                     d_planes.c_ptr if d_planes is not None else None, None))
+    else:
+        _lib.check(lib.lspiv_piv_pairs_dev_at(a.c_ptr, a.dtype_code, T, H, W, window_size[0], window_size[1], overlap[0], overlap[1],
+                                              _sig(signal_threshold), int(pair_offset), d_out.c_ptr,
+                                              d_planes.c_ptr if d_planes is not None else None, None))
     if scale is not None:  # px / frame -> m / s in place on the [u | v] blocks (lspiv_scale_velocity_dev: the same kernel as the host entry point's)
         _lib.check(lib.lspiv_scale_velocity_dev(d_out.c_ptr, P, n_win, scale[0], scale[1], _lib.ptr(scale[2]), None))
     if out is not None:    # straight into the caller's arrays: [u | v | corr | s2n] are four consecutive (P, n_win) blocks
@@ -124,14 +143,15 @@ def _piv_pairs_device(a, window_size, overlap, signal_threshold, return_planes, 
 
 def cross_corr(imgs, window_size=(64, 64), overlap=(32, 32), search_area_size=None, normalize=False,
                engine="hip", signal_threshold=None, verbose=False):
-    """``ffpiv.cross_corr`` drop-in: returns ``(x, y, corr)``, corr (T-1, n_win, wy, wx) float32.
+    """``ffpiv.cross_corr`` drop-in: returns ``(x, y, corr)``, corr (T-1, n_win, wy, wx) float32 -- with a ``search_area_size`` larger
+    than the window ("Extended search area") planes, grid and coordinates are those of the search area.
 
     Planes of window pairs below ``signal_threshold`` are NaN (pyorc/velocimetry/ffpiv.py:93-97).
     """
-    _check_args(window_size, overlap, search_area_size, normalize, engine)
+    spec = _check_args(window_size, overlap, search_area_size, normalize, engine)
     a = _lib.as_frames(imgs)
-    x, y = window.get_rect_coordinates(a.shape[-2:], window_size, overlap)
-    *_, planes = piv_pairs(a, window_size, overlap, signal_threshold, return_planes=True)
+    x, y = window.get_rect_coordinates(a.shape[-2:], tuple(spec), overlap)
+    *_, planes = piv_pairs(a, spec, overlap, signal_threshold, return_planes=True)
     return x, y, planes
 
 

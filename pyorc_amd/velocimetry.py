@@ -197,8 +197,11 @@ def get_ffpiv(
     """
     if engine != "hip":
         raise ValueError(f"Selected PIV engine {engine} does not exist.")
-    if tuple(search_area_size) != tuple(window_size):
-        raise NotImplementedError("search_area_size must equal window_size (pyorc/api/frames.py:168)")
+    # a search area of its own: one window argument that answers for the search area wherever a grid, a plan or an alignment is asked for
+    window_size = window.search_spec(window_size, search_area_size)
+    if ensemble_corr and isinstance(window_size, window.SearchWindow):
+        raise NotImplementedError("ensemble_corr=True with search_area_size != window_size is not implemented: the search-area kernels "
+                                  "serve per-timestep mode only")
     n_frames = len(frames)
     dim_size = tuple(frames[0].shape)
     dtype = frames.dtype if np.dtype(frames.dtype) in (np.dtype(np.uint8), np.dtype(np.float32)) else np.float64
@@ -360,7 +363,8 @@ def _timestep_sink(n_pairs, n_workers, y, x, dt, res_x, res_y, window_size, over
     full = {k: np.empty((n_pairs, len(y), len(x)), dtype=np.float32) for k in ("s2n", "corr", "v_x", "v_y")}
     done = []
     px = [None] * n_workers            # per worker: scratch for a launch's u, v in pixels
-    on_device = piv.device_scaling_is_numpys(res_x, res_y)
+    # (the search-area entry points have no fused scaling: numpy's arithmetic on the host, the same bits)
+    on_device = piv.device_scaling_is_numpys(res_x, res_y) and not isinstance(window_size, window.SearchWindow)
 
     def launch(k, frames, p0, p1):
         p = p1 - p0

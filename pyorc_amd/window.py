@@ -28,6 +28,40 @@ def round_to_even(input_tuple: Sequence[float]) -> Tuple[int, ...]:
     return tuple(int(np.round(float(x) / 2.0) * 2) for x in input_tuple)
 
 
+SEARCH_AREAS = (16, 32, 64)
+
+
+class SearchWindow(tuple):
+    """A window searched inside a larger search area, as ONE window argument of the layers below ``get_ffpiv`` / ``piv_pairs``: the tuple
+    itself is the SEARCH AREA ``(say, sax)`` -- which lays out the grid, the correlation planes and the memory plan, so every
+    function that takes a window size answers for the search area --, ``.window`` the ``(wy, wx)`` cut from frame t."""
+
+    def __new__(cls, search_area, window):
+        self = super().__new__(cls, (int(search_area[0]), int(search_area[1])))
+        self.window = (int(window[0]), int(window[1]))
+        return self
+
+
+def search_spec(window_size, search_area_size=None):
+    """``window_size`` as the layers below take it: the plain tuple when there is no search area of its own (None, or equal to the
+    window: today's path), else a validated :class:`SearchWindow`.  Host-only.  Supported: a square search area of 16, 32 or 64 px
+    with a square even window, 4 <= window <= search area - 2; not with the option ``norm_clip`` = 0."""
+    if isinstance(window_size, SearchWindow):
+        return window_size
+    ws = (int(window_size[0]), int(window_size[1]))
+    if search_area_size is None or (int(search_area_size[0]), int(search_area_size[1])) == ws:
+        return ws
+    sa = (int(search_area_size[0]), int(search_area_size[1]))
+    if not _lib.load().lspiv_search_supported(sa[0], sa[1], ws[0], ws[1]):
+        raise ValueError(f"search_area_size {sa} with window_size {ws} is not supported: the search area must be square and one of "
+                         f"{SEARCH_AREAS}, the window square and even with 4 <= window <= search area - 2 (or search_area_size == "
+                         "window_size)")
+    if _lib.get_option("norm_clip") == 0:
+        raise ValueError("option norm_clip = 0 is served by the block-per-window kernels only, not with a search_area_size "
+                         "larger than the window")
+    return SearchWindow(sa, ws)
+
+
 def get_axis_shape(dim_size: int, window_size: int, overlap: int) -> int:
     nr, nc = C.c_int64(), C.c_int64()
     _lib.check(_lib.load().lspiv_grid_shape(dim_size, dim_size, window_size, window_size, overlap, overlap,
@@ -105,6 +139,8 @@ def chunk_alignment(window_size, dim_size=None, overlap=None) -> int:
     that shape are cut.  Without them the alignment that is right on EVERY grid comes back (``lspiv_chunk_alignment``, ABI 5: the
     longest anchor length of the window family, a multiple of every grid's -- 75 where ABI 4 answered 25)."""
     lib = _lib.load()
+    if isinstance(window_size, SearchWindow):
+        return 1   # the search-area kernels are per-pair: any chunking gives the same bits
     if dim_size is None:
         return _lib.check(lib.lspiv_chunk_alignment(int(window_size[0]), int(window_size[1])))
     ov = (int(window_size[0]) // 2, int(window_size[1]) // 2) if overlap is None else overlap
