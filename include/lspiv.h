@@ -124,7 +124,8 @@ int         lspiv_synchronize(void);                    /* hipDeviceSynchronize 
  *                      function of the frame alone) that is subtracted while narrowing; default 1024 (never triggers on 8-bit-like
  *                      imagery, whose results stay bit-identical to a float32 copy of the stack), -1 never; environment
  *                      LSPIV_NARROW_OFFSET.  lspiv_piv_pairs / lspiv_ensemble_accumulate only, and only without a signal
- *                      threshold (which counts samples != 0).  float64 stacks already in HBM ("_dev") are converted as they are. */
+ *                      threshold (which counts samples != 0).  float64 stacks already in HBM ("_dev") are converted as they are, except by the
+ *                      search-area kernels, which take a float64 sample of the window off before they convert. */
 int         lspiv_set_option(const char* name, int value);
 int         lspiv_get_option(const char* name, int* value);
 /* counters of the rescue pass on `stream` (NULL: the library's own stream), after synchronising with it: stats[0..4] =

@@ -532,9 +532,10 @@ __device__ __forceinline__ void prepare_pair_embed(const PivParams& p, const Til
 // so the packed transform, the Hermitian cross spectrum, the shared inverse and the full-plane epilogue of the N-point kernel
 // serve unchanged; lag k of the circular N-point correlation is sum_m a[m] B[m + o + k], i.e. zero displacement sits at lag 0
 // (the plane centre after the fftshift), and lags |k| <= o never wrap.  Scale: 1 / (std_a std_b n^2).
-// One row of any sample type as floats (the whole N x N tile is inside the frame: vector loads, no bounds)
+// One row of uint8 or float32 samples as floats (the whole N x N tile is inside the frame: vector loads, no bounds)
 template <typename T, int N>
 __device__ __forceinline__ void load_row_any(const T* row, float (&x)[N]) {
+  static_assert(sizeof(T) <= 4, "float64 rows go through load_row_f64");
   if constexpr (sizeof(T) == 1) {
     RowRaw<uint8_t, N> raw;
     raw.fetch(reinterpret_cast<const uint8_t*>(row));
@@ -546,32 +547,51 @@ __device__ __forceinline__ void load_row_any(const T* row, float (&x)[N]) {
       x[4 * k + 2] = (float)((w >> 16) & 0xffu);
       x[4 * k + 3] = (float)(w >> 24);
     }
-  } else if constexpr (sizeof(T) == 4) {
-    load_row_f32<N>(reinterpret_cast<const float*>(row), x);
   } else {
+    load_row_f32<N>(reinterpret_cast<const float*>(row), x);
+  }
+}
+// One row of float64 samples: a pivot (a sample of the same window, float64) comes off BEFORE the conversion, so that texture
+// riding on a large offset keeps its digits (sigma 1 on 1e4 converted as it is keeps 1e-3 of the texture).  The statistics are
+// shift-invariant; the signal score is not, so it is decided here on the float64 sample: bit j of nzm = sample j counts.
+// A non-finite pivot makes the whole row non-finite: the pivot lies inside the window, which is skipped anyway.
+template <int N, bool WANT_NZ>
+__device__ __forceinline__ void load_row_f64(const double* row, double pivot, bool nz_pos, float (&x)[N], uint64_t& nzm) {
+  nzm = 0;
 #pragma unroll
-    for (int k = 0; k < N / 2; ++k) {
-      const f64x2 v = *reinterpret_cast<const f64x2_u*>(row + 2 * k);
-      x[2 * k + 0] = (float)v[0]; x[2 * k + 1] = (float)v[1];
+  for (int k = 0; k < N / 2; ++k) {
+    const f64x2 v = *reinterpret_cast<const f64x2_u*>(row + 2 * k);
+#pragma unroll
+    for (int e = 0; e < 2; ++e) {
+      x[2 * k + e] = (float)(v[e] - pivot);
+      if (WANT_NZ) nzm |= (uint64_t)((nz_pos ? v[e] > 0.0 : v[e] != 0.0) ? 1 : 0) << (2 * k + e);
     }
   }
 }
 // The masked window of frame t: derived from load_center_embed (non-periodic), the block at offset o instead of the corner.
 // "column j belongs to the block" is a uniform scalar test, "this lane's row belongs to it" one lane mask; samples outside the
 // block are dropped by selects, not products, so that a non-finite sample outside the block stays out of the statistics.
-// x0 = the block's first sample (shifted mean: a constant block has exactly zero variance).  Returns 1 / std (0: zero variance).
+// first = the block's first sample (shifted mean: a constant block has exactly zero variance); float64 rows take it off as their
+// pivot while they are loaded.  Returns 1 / std (0: zero variance).
 template <typename T, int N, bool WANT_NZ>
-__device__ __forceinline__ float load_center_masked(const T* row, float x0, int o, int n, bool row_in, bool nz_pos,
+__device__ __forceinline__ float load_center_masked(const T* row, T first, int o, int n, bool row_in, bool nz_pos,
                                                     float (&x)[N], int& nonzero, bool& finite) {
   const float inv_nn = 1.0f / (float)(n * n);
-  load_row_any<T, N>(row, x);
+  float x0 = 0.0f;
+  uint64_t nzm = 0;
+  if constexpr (sizeof(T) == 8) {
+    load_row_f64<N, WANT_NZ>(row, first, nz_pos, x, nzm);
+  } else {
+    load_row_any<T, N>(row, x);
+    x0 = to_f32(first);
+  }
   float s[4] = {0.0f, 0.0f, 0.0f, 0.0f};
   int nz = 0;
 #pragma unroll
   for (int j = 0; j < N; ++j) {
     const bool in = (unsigned)(j - o) < (unsigned)n;
     s[j & 3] += in ? x[j] - x0 : 0.0f;
-    if (WANT_NZ) nz += (in && (nz_pos ? x[j] > 0.0f : x[j] != 0.0f)) ? 1 : 0;
+    if (WANT_NZ) nz += (in && (sizeof(T) == 8 ? ((nzm >> j) & 1) != 0 : nz_pos ? x[j] > 0.0f : x[j] != 0.0f)) ? 1 : 0;
   }
   if (WANT_NZ) nonzero = group_sum_i<N>(row_in ? nz : 0);
   const float mean = x0 + group_sum<N>(row_in ? (s[0] + s[1]) + (s[2] + s[3]) : 0.0f) * inv_nn;
@@ -588,9 +608,11 @@ __device__ __forceinline__ float load_center_masked(const T* row, float x0, int 
   const float var = qq * inv_nn;
   return var > 0.0f ? __builtin_amdgcn_rsqf(var) : 0.0f;
 }
-// 64-point search: ONE window per job, as in the 64-point embedding (the half spectrum of window 0 does not survive window 1's
-// masked statistics inside 256 VGPRs)
-template <int N> constexpr bool kSearchSingle = N == 64;
+// ONE window per job at every size, the second slot of the inverse transform left empty as in the 64-point embedding: two windows
+// packed into one complex float32 inverse round each other's samples into their own (1e-7 of a plane, 2e-6 of a result), so a window's
+// result would move with what its neighbour holds -- a NaN there, or another chunking.  A window's result is a function of its own
+// samples alone.  (At 64 points the half spectrum of window 0 would not survive window 1's masked statistics inside 256 VGPRs either.)
+template <int N> constexpr bool kSearchSingle = true;
 template <typename T, int N, bool WANT_NZ>
 __device__ __forceinline__ void prepare_pair_search(const PivParams& p, const TileRef& t, int lg, float (&xr)[N],
                                                     float (&xi)[N], float& scale, float& hi, bool& skip) {
@@ -605,8 +627,8 @@ __device__ __forceinline__ void prepare_pair_search(const PivParams& p, const Ti
   const bool nz_pos = p.nz_positive != 0;
   bool finite = true;
   int nza = 0, nzb = Geo<N>::NN;
-  const float x0 = to_f32(frames[base + (int64_t)o * p.W + o]);
-  const float inv_a = load_center_masked<T, N, WANT_NZ>(frames + base + (int64_t)lg * p.W, x0, o, n, row_in, nz_pos, xr, nza, finite);
+  const T first = frames[base + (int64_t)o * p.W + o];
+  const float inv_a = load_center_masked<T, N, WANT_NZ>(frames + base + (int64_t)lg * p.W, first, o, n, row_in, nz_pos, xr, nza, finite);
   __builtin_amdgcn_sched_barrier(0);   // one window after the other
   const T* rowb = frames + base + p.frame_elems + (int64_t)lg * p.W;
   float inv_b, rho;
@@ -618,9 +640,17 @@ __device__ __forceinline__ void prepare_pair_search(const PivParams& p, const Ti
     rho = (inv_a == 0.0f || inv_b == 0.0f) ? 0.0f : inv_b * __builtin_amdgcn_rcpf(inv_a);
     center_u8<N>(rb, sb.mean, rho, xi);   // the balance factor rides on the conversion (prepare_pair)
   } else {
-    RowRaw<T, N> rb;
-    rb.fetch(rowb);
-    inv_b = load_center<N>(rb, xi, WANT_NZ, nz_pos, nzb, finite);
+    if constexpr (sizeof(T) == 8) {   // pivot: the area's sample under the block's first one
+      uint64_t nzm;
+      load_row_f64<N, WANT_NZ>(rowb, frames[base + p.frame_elems + (int64_t)o * p.W + o], nz_pos, xi, nzm);
+      if (WANT_NZ) nzb = group_sum_i<N>(__builtin_popcountll(nzm));
+      int none = 0;
+      inv_b = center_clip_f<N>(xi, false, nz_pos, none, finite);
+    } else {
+      RowRaw<T, N> rb;
+      rb.fetch(rowb);
+      inv_b = load_center<N>(rb, xi, WANT_NZ, nz_pos, nzb, finite);
+    }
     rho = (inv_a == 0.0f || inv_b == 0.0f) ? 0.0f : inv_b * __builtin_amdgcn_rcpf(inv_a);
 #pragma unroll
     for (int j = 0; j < N; ++j) xi[j] *= rho;
@@ -1987,9 +2017,8 @@ static hipError_t launch_embed(const PivParams& p, int dtype, bool ensemble, hip
 // The plane can exceed 1 before the clip (Cauchy-Schwarz bounds it by N / n, not 1: the search area is normalised over N^2
 // samples, the sum runs over n^2 of them), so the upper clip binds for real; the plane mean is then no longer the DC bin and is
 // summed from the clipped plane (a cold, wave-uniform branch).
-// registers (no scratch at these bounds): 16-point 80 - 131 VGPRs, three waves per SIMD (float64 rows with the signal score spill 12 bytes
-// at four); 32-point 134 - 164 without the signal score (three waves), 186 - 245 with it (two: at three it spills 72 - 312 bytes per lane);
-// 64-point, one window per job, 186 - 241 (two waves)
+// registers (ROCm 7.2, no scratch in any variant), one window per job: 16-point 48 - 74 VGPRs, 32-point 89 - 133, 64-point 186 - 218;
+// the bounds below are what the two-windows-per-job kernels needed and no longer bind at 16 and 32 points
 template <int N, bool WANT_NZ> constexpr int kSearchWaves = N <= 16 ? 3 : (N == 32 && !WANT_NZ) ? 3 : 2;
 template <int N>
 __device__ __forceinline__ float search_plane_mean(const float (&c)[N], float vmax, float dc) {
@@ -2012,7 +2041,7 @@ __global__ __launch_bounds__(BLOCK, (kSearchWaves<N, WANT_NZ>)) void piv_fft_sea
   const uint32_t xcd = blockIdx.x & 7u, slot = blockIdx.x >> 3;
   const uint32_t blk = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + slot;
   constexpr bool SINGLE = kSearchSingle<N>;
-  // windows (2j, 2j+1) of ONE pair share an inverse transform: the partner is fixed by the grid, results do not depend on the chunking
+  // one window per job (kSearchSingle): the !SINGLE branches are the packed layout of piv_fft_kernel, kept for an A/B build
   const uint32_t jobs_per_pair = SINGLE ? p.n_win : (p.n_win + 1) >> 1;
   uint32_t job = (blk * WAVES_PER_BLOCK + wave) * G::GROUPS + grp;
   const bool job_valid = job < p.n_pairs * jobs_per_pair;

@@ -1,5 +1,9 @@
 """Extended search area, host side: the reference against the oracle at S == n, argument validation, the grid and the planner follow
-the search area, and the CPU check of the inputs the GPU tests rely on (tie shares, the fast-flow case)."""
+the search area, and the CPU check of the inputs the GPU tests rely on (tie shares, the fast-flow case, and for each input of
+tests/test_gpu_search_area_paths.py the property it provokes: the clip at 1, every window size, the signal score's instances,
+non-finite samples, the rescue pass, window counts, a large float64 offset)."""
+import functools
+
 import numpy as np
 import pytest
 
@@ -120,3 +124,266 @@ def test_fast_flow_input_meets_its_conditions_in_the_reference():
     plain = fast_flow_shares(u12, v12)[2]
     print("plain 12 x 12:", plain)
     assert plain < 0.2
+
+
+# ---- inputs of tests/test_gpu_search_area_paths.py, each with the CPU check of what its GPU test relies on ----------------------
+def as_samples(a, dtype):
+    """The sample types of case_stack: uint8 as drawn, float32 / float64 through the affine map x * 0.37 - 11."""
+    return a if dtype == np.uint8 else a.astype(dtype) * dtype(0.37) - dtype(11.0)
+
+
+# A. the clip at 1 binds: (n, S, density) of fine_particles(3, 3 S, 3 S + 5, seed 1, sigma 0.6), overlap S / 2: 50 windows over the two
+# pairs, of which the reference clips 8, 14 and 10 (each on exactly one sample: no tie)
+CLIP_CASES = [(6, 16, 0.08), (12, 32, 0.02), (20, 64, 0.02)]
+
+
+@functools.lru_cache(maxsize=None)
+def clip_stack(S, density):
+    return fine_particles(3, 3 * S, 3 * S + 5, 1, density, sigma=0.6)
+
+
+@functools.lru_cache(maxsize=None)
+def clip_ref(i, dtype):   # the reference of the samples as the kernel receives them
+    n, S, density = CLIP_CASES[i]
+    return ref.search_piv(as_samples(clip_stack(S, density), dtype).astype(np.float64), (n, n), (S, S), (S // 2, S // 2))
+
+
+@pytest.mark.parametrize("dtype", [np.uint8, np.float32, np.float64])
+@pytest.mark.parametrize("i", range(3), ids=[f"{c[0]}in{c[1]}" for c in CLIP_CASES])
+def test_clip_inputs_bind_the_clip_on_one_sample(i, dtype):
+    n, S, density = CLIP_CASES[i]
+    r = clip_ref(i, dtype)
+    assert (r["corr"] == 1.0).sum() == (8, 14, 10)[i]
+    bound, free = int((r["corr"] == 1.0).sum()), int((r["corr"] < 1.0).sum())
+    print(f"{n} in {S}: clipped {bound}, unclipped {free}, ties {int(r['tie'].sum())} of {r['tie'].size}")
+    assert r["tie"].size == 50 and r["tie"].sum() == 0 and bound >= 5 and free >= 5
+    assert ((r["planes"] == 1.0).sum(axis=(-2, -1)).reshape(r["corr"].shape) == (r["corr"] == 1.0)).all()   # one clipped sample each
+    for t in range(2):
+        flat = (r["corr"][t] == 1.0).ravel()
+        assert flat.any() and not flat.all()
+    # bound and unbound windows meet inside one wave: a wave holds 4 / 2 / 1 consecutive jobs of one window each, jobs in the order
+    # (pair, window)
+    per_wave = {16: 4, 32: 2, 64: 1}[S]
+    flat = (r["corr"] == 1.0).ravel()
+    assert S == 64 or any(0 < flat[k:k + per_wave].sum() < flat[k:k + per_wave].size for k in range(0, flat.size, per_wave))
+
+
+# B. every window size: fine_particles(3, 2 S, 2 S + 5, seed, 0.3), overlap S / 2, 18 windows; seed 0 but for 4 in 32 (seed 3) and
+# 4 in 64 (seed 10: seeds 0 - 3 have 2 ties, 4 - 9 at least 1; scanned over seeds 0 ... 40) -- no size has a tie in the reference
+SIZES = [(n, S) for S in (16, 32, 64) for n in range(4, S - 1, 2)]
+SIZE_IDS = [f"{n}in{S}" for n, S in SIZES]
+SIZE_DTYPES = (np.uint8, np.float32, np.float64)
+
+
+def size_seed(n, S):
+    return {(4, 32): 3, (4, 64): 10}.get((n, S), 0)
+
+
+@functools.lru_cache(maxsize=None)
+def size_stack(S, seed):
+    return fine_particles(3, 2 * S, 2 * S + 5, seed, 0.3)
+
+
+def size_samples(n, S):
+    return as_samples(size_stack(S, size_seed(n, S)), SIZE_DTYPES[(n // 2) % 3])   # the sample type rotates with n
+
+
+@functools.lru_cache(maxsize=None)
+def size_ref(n, S, ddof=0):
+    with po.semantics(std_ddof=ddof):
+        return ref.search_piv(size_samples(n, S).astype(np.float64), (n, n), (S, S), (S // 2, S // 2))
+
+
+def test_all_fifty_window_sizes_are_listed():
+    assert len(SIZES) == 50 and all(window.search_spec((n, n), (S, S)).window == (n, n) for n, S in SIZES)
+    for S in (16, 32, 64):   # the sample type rotates with n: each type meets a third of every area's sizes
+        kinds = [(n // 2) % 3 for n, s in SIZES if s == S]
+        assert all(kinds.count(k) >= len(kinds) // 3 for k in range(3)), (S, kinds)
+
+
+@pytest.mark.parametrize("n,S", SIZES, ids=SIZE_IDS)
+def test_every_window_size_has_no_tie_in_the_reference(n, S):
+    for ddof in (0, 1) if n in (4, S // 2, S - 2) else (0,):
+        r = size_ref(n, S, ddof)
+        assert r["tie"].size == 18 and r["tie"].sum() == 0 and np.isfinite(r["corr"]).all(), (n, S, ddof, int(r["tie"].sum()))
+
+
+# C. the signal score: particle_stack with regions zeroed, threshold 0.05, n = 6 / 12 / 24 in S = 16 / 32 / 64
+SIGNAL_CASES = {16: (6, 22, 0.08), 32: (12, 9, 0.04), 64: (24, 0, 0.04)}   # S: (n, seed and density of particle_stack)
+SIGNAL_THR = 0.05
+
+
+@functools.lru_cache(maxsize=None)
+def signal_stack(S):
+    """3 frames of 3 S x (3 S + 5), overlap S / 2 (a 5 x 5 grid).  Zeroed: the block of tile (1, 1) in frame 0 (its block fails, the
+    area of frame 1 passes), the tile (3, 3) of frame 1 but for its centre column pair (pair 0: the area fails, the block of frame 0
+    passes), and the top right corner in every frame (positions that fail in signal_mode 1)."""
+    n, seed, density = SIGNAL_CASES[S]
+    a = particle_stack(3, 3 * S, 3 * S + 5, seed=seed, density=density)
+    o, h = (S - n) // 2, S // 2
+    a[0, h + o:h + o + n, h + o:h + o + n] = 0
+    a[1, 3 * h:3 * h + S, 3 * h:3 * h + S] = 0
+    a[:, :S, 2 * S:] = 0
+    return a
+
+
+def signal_instances(a, n, S, thr=SIGNAL_THR):
+    """Per window pair of the reference: (the n x n block of frame t passes, the S x S area of frame t + 1 passes), under the
+    current semantics' notion of a signal sample."""
+    tiles = po.sliding_window_stack(a, (S, S), (S // 2, S // 2))
+    o = (S - n) // 2
+    blocks = tiles[..., o:o + n, o:o + n]
+    return (po.signal_mask(blocks[:-1], blocks[:-1], thr), po.signal_mask(tiles[1:], tiles[1:], thr))
+
+
+@pytest.mark.parametrize("S", [16, 32, 64])
+def test_signal_inputs_hold_the_three_instances_and_differing_masks(S):
+    n = SIGNAL_CASES[S][0]
+    a = signal_stack(S)
+    masks = {}
+    for dtype, positive in ((np.uint8, 0), (np.uint8, 1), (np.float32, 1), (np.float64, 1), (np.float32, 0), (np.float64, 0)):
+        x = as_samples(a, dtype)
+        with po.semantics(signal_positive=positive):
+            block_ok, area_ok = signal_instances(x, n, S)
+            r = ref.search_piv(x, (n, n), (S, S), (S // 2, S // 2), SIGNAL_THR)
+            with po.semantics(signal_mode=1):
+                r1 = ref.search_piv(x, (n, n), (S, S), (S // 2, S // 2), SIGNAL_THR)
+        counts = (int((~block_ok & area_ok).sum()), int((block_ok & ~area_ok).sum()), int((block_ok & area_ok).sum()))
+        print(S, np.dtype(dtype).name, "positive", positive, "block fails / area fails / both pass:", counts,
+              "ties", int(r["tie"].sum()), int(r1["tie"].sum()), "mode 1 dropped", int(np.isnan(r1["corr"]).sum()))
+        assert np.array_equal(np.isfinite(r["corr"]).reshape(block_ok.shape), block_ok & area_ok)
+        assert r["tie"].sum() == 0 and r1["tie"].sum() == 0
+        if dtype == np.uint8 or positive:      # (float samples are all non-zero after the map: every window passes x != 0)
+            assert min(counts) >= 1, counts
+            assert 0 < np.isnan(r1["corr"]).sum() < r1["corr"].size
+        else:
+            assert counts[2] == block_ok.size
+        masks[np.dtype(dtype).name, positive] = np.isnan(r["corr"])
+    for name in ("float32", "float64"):        # background samples are negative: x > 0 and x != 0 part ways
+        assert not np.array_equal(masks[name, 0], masks[name, 1])
+        assert (as_samples(a, np.dtype(name).type) < 0).any()
+
+
+# D. non-finite samples: clean stacks of A's recipe, (n, S, density); samples placed in frame 1 at (y, x) scaled with S
+NONFINITE_CASES = [(16, 32, 0.02), (24, 64, 0.02)]
+
+
+def nonfinite_points(S):
+    """((y, x), value, lies in a block): a NaN and a +Inf in the frame's border, inside tiles but outside every central block, and a
+    NaN inside a block."""
+    return (((3, S + S // 4), np.nan, False), ((S + S // 2 + 2, 2), np.inf, False), ((S + 2 * S // 5, 2 * S - S // 8), np.nan, True))
+
+
+def nonfinite_stack(n, S, density, dtype):
+    clean = as_samples(clip_stack(S, density), dtype)
+    dirty = clean.copy()
+    for (y, x), val, _ in nonfinite_points(S):
+        dirty[1, y, x] = val
+    return clean, dirty
+
+
+def nonfinite_mask(n, S, shape):
+    """(2, rows, cols) expected NaN mask, from the geometry alone: pair 0 wherever the area of frame 1 holds a sample, pair 1 wherever
+    the block of frame 1 does."""
+    x, y = po.get_rect_coordinates(shape, (n, n), (S // 2, S // 2), search_area_size=(S, S))
+    y0, x0 = (np.asarray(y) - S // 2)[:, None], (np.asarray(x) - S // 2)[None, :]     # tile origins
+    o = (S - n) // 2
+    mask = np.zeros((2, len(y), len(x)), bool)
+    for (py, px), _, _ in nonfinite_points(S):
+        mask[0] |= (py >= y0) & (py < y0 + S) & (px >= x0) & (px < x0 + S)
+        mask[1] |= (py >= y0 + o) & (py < y0 + o + n) & (px >= x0 + o) & (px < x0 + o + n)
+    return mask
+
+
+@pytest.mark.parametrize("n,S,density", NONFINITE_CASES, ids=[f"{c[0]}in{c[1]}" for c in NONFINITE_CASES])
+def test_nonfinite_inputs_sit_where_the_gpu_test_says(n, S, density):
+    clean, dirty = nonfinite_stack(n, S, density, np.float64)
+    r = ref.search_piv(clean, (n, n), (S, S), (S // 2, S // 2))
+    assert r["tie"].sum() == 0 and np.isfinite(r["corr"]).all()
+    mask = nonfinite_mask(n, S, clean.shape[1:])
+    x, y = po.get_rect_coordinates(clean.shape[1:], (n, n), (S // 2, S // 2), search_area_size=(S, S))
+    o = (S - n) // 2
+    for (py, px), val, in_block in nonfinite_points(S):
+        tiles = [(i, j) for i, cy in enumerate(y) for j, cx in enumerate(x) if 0 <= py - (cy - S // 2) < S and 0 <= px - (cx - S // 2) < S]
+        blocks = [(i, j) for i, j in tiles if 0 <= py - (y[i] - S // 2 + o) < n and 0 <= px - (x[j] - S // 2 + o) < n]
+        assert len(tiles) >= 2 and len(blocks) == (1 if in_block else 0), ((py, px), tiles, blocks)
+        assert all(mask[0, i, j] for i, j in tiles) and all(mask[1, i, j] for i, j in blocks)
+    assert mask[1].sum() == 1 and mask[0].sum() >= 6 and not mask.all(axis=0).all()
+    # the reference itself, on the dirty stack, is NaN exactly there (numpy propagates a NaN through a tile's statistics, and only there)
+    rd = ref.search_piv(np.where(np.isfinite(dirty), dirty, np.nan), (n, n), (S, S), (S // 2, S // 2))
+    assert np.array_equal(np.isnan(rd["corr"]), mask)
+    flat = mask.reshape(2, -1)   # a skipped window next to a live partner (2j, 2j + 1) of the same pair
+    assert any(flat[t, w] != flat[t, w ^ 1] for t in range(2) for w in range(flat.shape[1] - 1))
+
+
+# E. the rescue pass with a masked window, window counts, float64 on a large offset
+def sparse_integer_particles(H, W, seed, count, dtype=np.uint8):
+    """The input of test_rescue_covers_sparse_integer_particles: single bright pixels with one dim neighbour, moving by (1, 2) px."""
+    rng = np.random.default_rng(seed)
+    a = np.zeros((3, H, W), np.uint8)
+    yy, xx = rng.integers(2, H - 4, count), rng.integers(2, W - 7, count)
+    for t in range(3):
+        a[t, yy + t, xx + 2 * t] = rng.integers(100, 255, count)
+        a[t, yy + t, xx + 2 * t + 1] = 60
+    return a.astype(dtype)
+
+
+# (n, S, H, W, seed, count, sample type): 16 in 32 is the 70 x 101 original (500 particles), 6 in 16 has its density; 24 in 64 is sparser
+# (at that density no peak of a 24 x 24 window keeps an exactly zero neighbour, at 300 particles 20 of 30 do).  Seeds with no tie in the
+# reference
+RESCUE_CASES = [(6, 16, 36, 53, 3, 135, np.uint8), (24, 64, 130, 200, 0, 300, np.uint8), (16, 32, 70, 101, 5, 500, np.float32),
+                (16, 32, 70, 101, 5, 500, np.float64)]
+
+
+@functools.lru_cache(maxsize=None)
+def rescue_ref(i):
+    n, S, H, W, seed, count, _ = RESCUE_CASES[i]
+    return ref.search_piv(sparse_integer_particles(H, W, seed, count), (n, n), (S, S), (S // 2, S // 2))
+
+
+@pytest.mark.parametrize("i", range(len(RESCUE_CASES)))
+def test_rescue_inputs_have_rare_ties_and_exact_zero_neighbours(i):
+    n, S, H, W, seed, count, dtype = RESCUE_CASES[i]
+    r = rescue_ref(i)
+    assert r["tie"].mean() <= 0.01, (n, S, int(r["tie"].sum()))
+    assert np.array_equal(sparse_integer_particles(H, W, seed, count, dtype), sparse_integer_particles(H, W, seed, count))   # exact in floats
+    # what makes the float32 log fit ill-conditioned: a peak of the plane with an exactly zero neighbour
+    P = np.nan_to_num(r["planes"])
+    iy, ix = np.unravel_index(P.reshape(P.shape[:2] + (-1,)).argmax(-1), (S, S))
+    inner = (iy > 0) & (iy < S - 1) & (ix > 0) & (ix < S - 1)
+    t, w = np.nonzero(inner)
+    nb = np.stack([P[t, w, iy[t, w] + dy, ix[t, w] + dx] for dy, dx in ((-1, 0), (1, 0), (0, -1), (0, 1))])
+    print(f"{n} in {S}: ties {int(r['tie'].sum())} of {r['tie'].size}, peaks with a zero neighbour {int((nb == 0).any(0).sum())}")
+    assert (nb == 0).any(0).sum() >= 1
+
+
+# window counts: one window (a frame of exactly S x S: the second slot of the only job is never valid) and an even count (2 x 3)
+COUNT_CASES = [(S, H, W) for S in (16, 32, 64) for H, W in ((S, S), (3 * S // 2, 2 * S + 3))]
+
+
+@functools.lru_cache(maxsize=None)
+def count_stack(H, W):
+    return fine_particles(3, H, W, 0, 0.3)
+
+
+@pytest.mark.parametrize("S,H,W", COUNT_CASES, ids=[f"{c[0]}-{c[1]}x{c[2]}" for c in COUNT_CASES])
+def test_window_count_inputs_have_no_tie(S, H, W):
+    x, y = po.get_rect_coordinates((H, W), (S // 2, S // 2), (S // 2, S // 2), search_area_size=(S, S))
+    assert (len(y), len(x)) == ((1, 1) if H == S else (2, 3))
+    r = ref.search_piv(count_stack(H, W), (S // 2, S // 2), (S, S), (S // 2, S // 2))
+    assert r["tie"].sum() == 0 and np.isfinite(r["corr"]).all(), (S, H, W, int(r["tie"].sum()))
+
+
+def offset_stack():
+    """The recipe of test_float64_stack_on_a_large_dc_offset (tests/test_gpu_parity.py): texture of sigma ~ 1 on an offset of 1e4.  Its
+    seed 9 leaves 4 ties in the 252 planes of 16 in 32 (over the cap of 1 %; seeds 10 - 12 leave 2 - 4), seed 13 none."""
+    return particle_stack(5, 128, 160, seed=13, density=0.03).astype(np.float64) / 60.0 + 1.0e4
+
+
+def test_large_offset_input_has_no_tie_and_float32_would_lose_it():
+    a = offset_stack()
+    r = ref.search_piv(a, (16, 16), (32, 32), (16, 16))
+    assert r["tie"].mean() <= 0.01 and np.isfinite(r["corr"]).all()
+    lost = ref.search_piv(a.astype(np.float32), (16, 16), (32, 32), (16, 16))   # narrowed as it is: the texture keeps 1e-3 only
+    with np.errstate(invalid="ignore"):
+        assert max(np.nanmax(np.abs(lost[k] - r[k]) / np.maximum(np.abs(r[k]), 0.05)) for k in ("u", "v", "corr")) > 1e-4
