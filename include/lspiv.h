@@ -38,7 +38,8 @@ extern "C" {
 #endif
 
 #define LSPIV_ABI_VERSION 5   /* (additions since, nothing existing moved, no version change: the search-area entry points lspiv_piv_search_pairs_at /
-                               * lspiv_piv_search_pairs_dev_at and lspiv_search_supported)
+                               * lspiv_piv_search_pairs_dev_at and lspiv_search_supported; the sliding ensemble, lspiv_ensemble_set_sliding /
+                               * lspiv_ensemble_sliding_reserve / lspiv_ensemble_sliding_finish)
                                * 5 (round 6): lspiv_chunk_alignment(wy, wx) without a grid now returns the alignment that is right on EVERY grid (75
                                * where it returned 25: callers that cut chunks on it stay bit-reproducible on large grids); additions:
                                * lspiv_upload_frames, lspiv_trace / lspiv_trace_read; the host-pointer projection entry points no longer
@@ -309,6 +310,33 @@ int lspiv_ensemble_import(lspiv_ensemble* handle, const float* corr_sum, const f
  * keeps the float64 rescue.  Waits for every handle's accumulations; takes the host locks of the devices involved in ascending order;
  * the calling thread's device is unchanged afterwards. */
 int lspiv_ensemble_allreduce(lspiv_ensemble** handles, int n);
+/* Sliding ensemble: time-resolved fields from a moving window of pairs (the project's own mode).  The
+ * pairs of the run, by absolute index, form blocks of `stride_pairs` = s; output j is fitted on the mean plane of the
+ * `window_pairs` = M pairs of blocks j .. j + M / s - 1 (1 <= s <= M, M % s == 0, else LSPIV_EINVAL).  Call before the first
+ * accumulate only.  The handle then keeps a BLOCK STORE in HBM -- one plane sum and one count per (block, window) for the whole run,
+ * n_win * (wy * wx + 1) * 4 bytes per block, grown geometrically, LSPIV_ENOMEM with the bytes it needed when that fails -- and leaves
+ * corr_sum / corr_count untouched.  Every pair is correlated once.  A block sum is a fixed sequence of float32 additions in pair
+ * order and an output a fixed sequence of block sums: the results are bit-identical for every chunking whose boundaries are
+ * multiples of s.  Every accumulate call must hold a multiple of s pairs unless it is the last one (LSPIV_EINVAL otherwise); the
+ * pairs after the last whole block are correlated -- their corr_max / s2n are returned -- and enter no output.  The even square
+ * windows 6 .. 64 run the time-walking ensemble kernel once per call with one segment per block; every other window size, and
+ * LSPIV_WALK=0, take one launch of the one-owner ensemble kernel per block: correct for every size the ensemble mode supports, and
+ * slower.  The first accumulate records the slot layout of the store; a later call that would write another one (LSPIV_WALK changed
+ * in between, 64 x 64 windows) returns LSPIV_EINVAL, and lspiv_ensemble_sliding_finish decodes the recorded layout.  On such a handle lspiv_ensemble_finish, _flag, _partials, _finish_partials, _export, _import and _allreduce return
+ * LSPIV_EINVAL. */
+int lspiv_ensemble_set_sliding(lspiv_ensemble* handle, int64_t window_pairs, int64_t stride_pairs);
+/* Room in the block store of a sliding handle for a run of `n_pairs` pairs in all, allocated once: a caller that knows the length of
+ * its run calls this before the first accumulate, and the store is then neither grown nor moved (growing doubles the store and copies
+ * the blocks written so far, with the old and the new store alive together).  LSPIV_ENOMEM with the bytes it needed; never shrinks. */
+int lspiv_ensemble_sliding_reserve(lspiv_ensemble* handle, int64_t n_pairs);
+/* Outputs [first_out, first_out + n_out) of a sliding handle, of the (pairs accumulated / s) - M / s + 1 there are (LSPIV_EINVAL
+ * outside that range; may be called more than once): per output and window the block sums and counts added in block order, NaN plane
+ * and NaN u, v where the count is < count_min * M, else the mean plane and its sub-pixel peak as in lspiv_ensemble_finish.
+ * u, v, corr_count: (n_out, n_win) float32; corr_mean NULL or (n_out, n_win, wy, wx).  Works through the outputs in tiles sized to
+ * the plane workspace.  The float64 rescue re-evaluates an output's ill-conditioned fits over ITS pairs from the retained frames,
+ * under the retention rules of lspiv_ensemble_finish; lspiv_ensemble_stats then reports the totals over the outputs of this call. */
+int lspiv_ensemble_sliding_finish(lspiv_ensemble* handle, float count_min, int64_t first_out, int64_t n_out,
+                                  float* u, float* v, float* corr_count, float* corr_mean);
 int lspiv_ensemble_destroy(lspiv_ensemble* handle);
 
 /* ---------------------------------------------------------------- next rows */

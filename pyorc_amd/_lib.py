@@ -91,6 +91,9 @@ SIGNATURES = {
     "lspiv_ensemble_export": (_i32, [_vp, _vp, _vp]),
     "lspiv_ensemble_import": (_i32, [_vp, _vp, _vp, _i32]),
     "lspiv_ensemble_allreduce": (_i32, [C.POINTER(_vp), _i32]),
+    "lspiv_ensemble_set_sliding": (_i32, [_vp, _i64, _i64]),
+    "lspiv_ensemble_sliding_reserve": (_i32, [_vp, _i64]),
+    "lspiv_ensemble_sliding_finish": (_i32, [_vp, _f32, _i64, _i64, _vp, _vp, _vp, _vp]),
     "lspiv_ensemble_destroy": (_i32, [_vp]),
     "lspiv_projection_create": (_i32, [_i64, _i64, _i64, _i64, _vp, _vp, _i64, _vp, _vp, _i64, _vp, _i64, C.POINTER(_vp)]),
     "lspiv_project_frames": (_i32, [_vp, _vp, _i32, _i64, _vp]),

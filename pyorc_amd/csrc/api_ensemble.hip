@@ -42,6 +42,14 @@ struct lspiv_ensemble {
   uint32_t n_rec;           // records of the last lspiv_ensemble_flag (sorted by window), 0 if none
   uint64_t rec_digest;      // FNV-1a over (w, ncand, pos[0 .. ncand-1]) of those records: what ranks compare before they sum partials
   float flag_min_count;     // count_min * n_frames of that call
+  // sliding ensemble (lspiv_ensemble_set_sliding): outputs over windows of sl_window pairs advancing by sl_stride pairs.  The block
+  // store keeps one slot per (block of sl_stride pairs, window) for the whole run, in the layout the accumulating kernel writes:
+  // block b's plane sums at d_store + b * n_win * wy * wx, its counts at d_store_cnt + b * n_win; d_sum / d_count stay untouched
+  int64_t sl_window, sl_stride;   // 0: not a sliding handle
+  float* d_store; float* d_store_cnt;
+  size_t store_blocks;      // capacity, in blocks
+  bool tail_open;           // the last accumulate ended inside a block: it was the last one
+  int sl_layout;            // slot layout of the store, recorded by the first accumulate: 0 nothing written yet, 1 fft-shifted row-major, 2 lane-major (64 x 64 walking kernel)
 };
 
 // HBM the retained chunks of one ensemble may occupy: LSPIV_ENSEMBLE_RETAIN_BYTES, default a quarter of the device
@@ -203,6 +211,43 @@ static int ensemble_allreduce_locked(lspiv_ensemble** handles, int n) {
   return rc;
 }
 
+// ---- sliding ensemble: the block store --------------------------------------------------------------------------------------
+// room for `blocks` blocks (geometric growth; the blocks written so far move along).  `s`: the stream the caller launches on next.
+static int sliding_reserve(lspiv_ensemble* h, size_t blocks, hipStream_t s) {
+  if (blocks <= h->store_blocks) return LSPIV_OK;
+  const size_t n_win = (size_t)h->g.n_rows * h->g.n_cols, plane = (size_t)h->wy * h->wx;
+  const size_t used = (size_t)(h->pairs_done / h->sl_stride);
+  void *ps = nullptr, *pc = nullptr;
+  size_t cap = std::max(blocks, 2 * h->store_blocks);
+  for (;;) {
+    if (hipMalloc(&ps, cap * n_win * plane * sizeof(float)) == hipSuccess) {
+      if (hipMalloc(&pc, cap * n_win * sizeof(float)) == hipSuccess) break;
+      (void)hipFree(ps);
+    }
+    (void)hipGetLastError();
+    ps = pc = nullptr;
+    if (cap == blocks)
+      return fail(LSPIV_ENOMEM, "sliding ensemble: the block store needs %zu bytes for %zu blocks of %lld pairs", blocks * n_win * (plane + 1) * sizeof(float),
+                  blocks, (long long)h->sl_stride);
+    cap = blocks;   // the doubled store did not fit: what this call needs
+  }
+  if (used) {
+    ensemble_wait_accumulated(h, s);   // earlier accumulate_dev calls may have written the store on other streams
+    hipError_t e = hipMemcpyAsync(ps, h->d_store, used * n_win * plane * sizeof(float), hipMemcpyDeviceToDevice, s);
+    if (e == hipSuccess) e = hipMemcpyAsync(pc, h->d_store_cnt, used * n_win * sizeof(float), hipMemcpyDeviceToDevice, s);
+    if (e == hipSuccess) e = hipStreamSynchronize(s);
+    if (e != hipSuccess) { (void)hipFree(ps); (void)hipFree(pc); return fail(LSPIV_EHIP, "sliding ensemble: moving the block store: %s", hipGetErrorString(e)); }
+  }
+  if (h->d_store) (void)hipFree(h->d_store);
+  if (h->d_store_cnt) (void)hipFree(h->d_store_cnt);
+  h->d_store = (float*)ps; h->d_store_cnt = (float*)pc; h->store_blocks = cap;
+  return LSPIV_OK;
+}
+static int not_on_sliding(const lspiv_ensemble* h, const char* call) {
+  if (h && h->sl_stride) return fail(LSPIV_EINVAL, "%s: this is a sliding ensemble handle (lspiv_ensemble_set_sliding); its results come from lspiv_ensemble_sliding_finish", call);
+  return LSPIV_OK;
+}
+
 extern "C" {
 
 // ---- ensemble -------------------------------------------------------------------------------
@@ -244,6 +289,57 @@ static int ensemble_launch(lspiv_ensemble* h, DeviceCtx* c, const void* d_frames
   const int kind = lspiv_kernel_kind(h->wy, h->wx);
   const int walk = lspiv::walk_setting();
   p.pair_offset = h->pairs_done;   // advanced only once the launch has been issued (a failed accumulate changes nothing)
+  if (h->sl_stride) {
+    // sliding ensemble: the sums of this call's blocks go into the block store, nothing into d_sum / d_count
+    if (h->tail_open)
+      return fail(LSPIV_EINVAL, "sliding ensemble: the previous accumulate call did not end on a multiple of %lld pairs, so it was the last one", (long long)h->sl_stride);
+    const int64_t sp = h->sl_stride, blk0 = h->pairs_done / sp, nb = ((int64_t)p.n_pairs + sp - 1) / sp;   // (a trailing partial block gets a slot too; no output reads it)
+    LSPIV_TRY(sliding_reserve(h, (size_t)(blk0 + nb), s));
+    // the slot layout is the store's for the whole run: what the first call wrote is what lspiv_ensemble_sliding_finish decodes
+    const bool walking = kind_walks(kind) && walk != 0;
+    int lane_major = 0; bool split = false;
+    if (walking) lspiv::walk_ensemble_slot_layout(h->wy, &lane_major, &split);
+    if (split) return fail(LSPIV_EUNSUPPORTED, "sliding ensemble: not available in a build with LSPIV_ENS_SPLIT_HALVES (the split slot layout depends on the call)");
+    const int layout = lane_major ? 2 : 1;
+    if (h->sl_layout && h->sl_layout != layout)
+      return fail(LSPIV_EINVAL, "sliding ensemble: the 'walk' setting (LSPIV_WALK) changed between accumulate calls; the block store of a %d x %d window holds %s slots and this call would write %s ones",
+                  h->wy, h->wx, h->sl_layout == 2 ? "lane-major" : "row-major", layout == 2 ? "lane-major" : "row-major");
+    const size_t plane = (size_t)h->wy * h->wx;
+    float* const slots = h->d_store + (size_t)blk0 * p.n_win * plane;
+    float* const counts = h->d_store_cnt + (size_t)blk0 * p.n_win;
+    LSPIV_TRY(apply_signal_mode(c, &p, dtype, s));   // "stack" mode: one set of keep flags per call, as in the plain ensemble
+    if (walking) {
+      // the walking kernel with segment = block and WITHOUT its merge (corr_sum = nullptr): every (block, window) job writes its
+      // whole slot and its count, in the kernel's own slot layout (ensemble_sliding_mean_kernel decodes it)
+      const lspiv::WalkSegments w = lspiv::walk_segments(p.n_pairs, p.pair_offset, (uint32_t)sp);
+      p.seg_len = w.seg_len; p.seg_first = w.seg_first; p.n_seg = w.n_seg;
+      p.part_sum = slots; p.part_cnt = counts;
+      p.corr_sum = nullptr; p.corr_count = nullptr;
+      LSPIV_TRY(dispatch(p, dtype, true, s));
+    } else {
+      // every other window family: the one-owner ensemble kernel once per block, adding into that block's zeroed row-major slot
+      HIP_TRY(hipMemsetAsync(slots, 0, (size_t)nb * p.n_win * plane * sizeof(float), s));
+      HIP_TRY(hipMemsetAsync(counts, 0, (size_t)nb * p.n_win * sizeof(float), s));
+      const size_t frame_bytes = (size_t)h->H * h->W * elem_size(dtype);
+      for (int64_t b = 0; b < nb; ++b) {
+        lspiv::PivParams q = p;
+        const int64_t first = b * sp;
+        q.n_pairs = (uint32_t)std::min<int64_t>(sp, (int64_t)p.n_pairs - first);
+        q.n_tiles = q.n_pairs * p.n_win;
+        q.frames = (const char*)d_frames + (size_t)first * frame_bytes;
+        q.cmax = d_cmax + (size_t)first * p.n_win;
+        q.s2n = d_s2n + (size_t)first * p.n_win;
+        q.pair_offset = p.pair_offset + first;
+        q.corr_sum = slots + (size_t)b * p.n_win * plane;
+        q.corr_count = counts + (size_t)b * p.n_win;
+        LSPIV_TRY(dispatch(q, dtype, true, s));
+      }
+    }
+    h->pairs_done += p.n_pairs;
+    h->tail_open = (p.n_pairs % sp) != 0;
+    h->sl_layout = layout;
+    return LSPIV_OK;
+  }
   if (kind_walks(kind) && walk != 0) {
     // segments anchored at multiples of the anchor length of the absolute pair index (common.h): the partial sums, and
     // the order they are merged in, are the same for every chunking whose boundaries are multiples of that length
@@ -322,7 +418,10 @@ int lspiv_ensemble_accumulate(lspiv_ensemble* h, const void* frames, int dtype, 
   struct OwnGuard { void* p; ~OwnGuard() { if (p) (void)hipFree(p); } } own_guard{own};   // released on every error path below
   LSPIV_TRY(stage_ring(c, frame_bytes));
   const int64_t fpb = std::max<int64_t>(1, (int64_t)(c->pinned_cap / frame_bytes));
-  const int64_t align = std::max(1, chunk_alignment_for(h->wy, h->wx, (int64_t)n_win)), base_offset = h->pairs_done;
+  // sub-batches are cut on the segment anchors -- on the blocks of a sliding handle
+  const int64_t align = h->sl_stride ? h->sl_stride : std::max(1, chunk_alignment_for(h->wy, h->wx, (int64_t)n_win)), base_offset = h->pairs_done;
+  if (h->sl_stride)   // the block store grows once per call, not once per sub-batch
+    LSPIV_TRY(sliding_reserve(h, (size_t)((base_offset + T - 1 + h->sl_stride - 1) / h->sl_stride), c->stream));
   int64_t launched = 0;
   {
     int batch = 0;
@@ -367,10 +466,11 @@ static lspiv::EnsRescueRec* ensemble_recs(lspiv_ensemble* h) { return reinterpre
 
 // flag the windows whose float32 fit (c->d_out, of the mean planes in c->d_planes) cannot be trusted to 1e-4; the records end
 // up sorted by window index -- the same list on every handle that holds the same state (multi-GPU: after the all-reduce)
-static int ensemble_flag(lspiv_ensemble* h, DeviceCtx* c) {
+// (n_planes: the planes in c->d_planes and results in c->d_out [u | v] -- the handle's windows, or a tile of a sliding handle's outputs)
+static int ensemble_flag(lspiv_ensemble* h, DeviceCtx* c, uint32_t n_planes = 0) {
   h->last_flagged = h->last_rescued = h->last_skipped = 0;
   h->n_rec = 0;
-  const uint32_t n_win = (uint32_t)(h->g.n_rows * h->g.n_cols);
+  const uint32_t n_win = n_planes ? n_planes : (uint32_t)(h->g.n_rows * h->g.n_cols);
   const size_t hdr_bytes = 256;
   LSPIV_TRY(ensure(&h->d_rescue, &h->rescue_cap, hdr_bytes + (size_t)n_win * sizeof(lspiv::EnsRescueRec)));
   lspiv::EnsRescueHdr* d_hdr = static_cast<lspiv::EnsRescueHdr*>(h->d_rescue);
@@ -407,7 +507,9 @@ static int ensemble_flag(lspiv_ensemble* h, DeviceCtx* c) {
 
 // this handle's share of the float64 sums: over the pairs of its retained chunks, merged in pair-block order -> h->d_totals
 // (n_rec, kEnsMaxCand * 5).  *complete = false (and zeros) when some chunk of this handle could not be kept.
-static int ensemble_partials(lspiv_ensemble* h, DeviceCtx* c, bool* complete) {
+// Sliding handle (count != nullptr): the records index the tile of outputs that starts at output `out0`, `count` is that tile's
+// (output, window) count array, and a record sums the pairs of its own output only.
+static int ensemble_partials(lspiv_ensemble* h, DeviceCtx* c, bool* complete, const float* count = nullptr, int64_t out0 = 0) {
   const size_t row = (size_t)lspiv::kEnsMaxCand * 5 * sizeof(double);
   LSPIV_TRY(ensure(&h->d_totals, &h->totals_cap, std::max<size_t>(1, h->n_rec) * row));
   ensemble_wait_accumulated(h, c->stream);   // the kept records and frame copies were written on the accumulating streams
@@ -421,28 +523,34 @@ static int ensemble_partials(lspiv_ensemble* h, DeviceCtx* c, bool* complete) {
   LSPIV_TRY(ensure(&h->d_partial, &h->partial_cap, (size_t)h->n_rec * per_rec));
   lspiv::EnsRescueArgs a;
   memset(&a, 0, sizeof(a));
-  a.recs = ensemble_recs(h); a.n_rec = h->n_rec; a.n_blk = n_blk; a.partial = h->d_partial; a.count = h->d_count;
+  a.recs = ensemble_recs(h); a.n_rec = h->n_rec; a.n_blk = n_blk; a.partial = h->d_partial; a.count = count ? count : h->d_count;
+  if (count) {
+    a.virt_nwin = (uint32_t)(h->g.n_rows * h->g.n_cols); a.out0 = (uint32_t)out0;
+    a.stride = (uint32_t)h->sl_stride; a.window = (uint32_t)h->sl_window;
+  }
   lspiv::PivParams p;
   uint32_t blk0 = 0;
+  int64_t pair0 = 0;   // (every chunk of the run is kept, in order: retain_complete)
   for (const auto& kp : h->kept) {
     LSPIV_TRY(fill_params(&p, kp.d_frames, kp.dtype, kp.T, h->H, h->W, h->wy, h->wx, h->oy, h->ox, -1.0f, h->g));
-    a.cmax = kp.d_cmax; a.n_pairs = (uint32_t)(kp.T - 1); a.blk0 = blk0;
+    a.cmax = kp.d_cmax; a.n_pairs = (uint32_t)(kp.T - 1); a.blk0 = blk0; a.pair0 = (uint32_t)pair0;
     LSPIV_TRY(launch_status(lspiv::launch_ens_partial(p, kp.dtype, a, c->stream)));
     blk0 += (a.n_pairs + lspiv::kEnsPairBlock - 1) / lspiv::kEnsPairBlock;
+    pair0 += kp.T - 1;
   }
   return launch_status(lspiv::launch_ens_merge(a, h->d_totals, c->stream));
 }
 
 // the fit of the flagged windows from the float64 totals (all pairs of the sum), overwriting c->d_out [u | v]
-static int ensemble_final(lspiv_ensemble* h, DeviceCtx* c, const double* d_totals) {
+static int ensemble_final(lspiv_ensemble* h, DeviceCtx* c, const double* d_totals, const float* count = nullptr, size_t n_planes = 0) {
   if (h->n_rec == 0) return LSPIV_OK;
-  const size_t n_win = (size_t)h->g.n_rows * h->g.n_cols;
+  const size_t n_win = n_planes ? n_planes : (size_t)h->g.n_rows * h->g.n_cols;
   lspiv::PivParams p;
   memset(&p, 0, sizeof(p));
   p.wy = h->wy; p.wx = h->wx; p.border_mode = g_opt_border.load();
   lspiv::EnsRescueArgs a;
   memset(&a, 0, sizeof(a));
-  a.recs = ensemble_recs(h); a.n_rec = h->n_rec; a.count = h->d_count;
+  a.recs = ensemble_recs(h); a.n_rec = h->n_rec; a.count = count ? count : h->d_count;
   LSPIV_TRY(launch_status(lspiv::launch_ens_final(p, a, d_totals, c->d_out, c->d_out + n_win, c->stream)));
   h->last_rescued = (int64_t)h->n_rec - h->last_skipped;
   return LSPIV_OK;
@@ -463,6 +571,7 @@ static int ensemble_deliver(lspiv_ensemble* h, DeviceCtx* c, float* u, float* v,
 int lspiv_ensemble_flag(lspiv_ensemble* h, float count_min, float n_frames, int64_t* n_records) {
   std::lock_guard<std::mutex> host_lock(locks_here().host);
   if (!h || !n_records) return fail(LSPIV_EINVAL, "NULL argument");
+  LSPIV_TRY(not_on_sliding(h, "lspiv_ensemble_flag"));
   DeviceCtx* c;
   LSPIV_TRY(get_ctx(&c));
   h->flag_min_count = count_min * n_frames;
@@ -484,6 +593,7 @@ int lspiv_ensemble_flag_digest(lspiv_ensemble* h, uint64_t* digest) {
 int lspiv_ensemble_partials(lspiv_ensemble* h, double* partials, int* complete) {
   std::lock_guard<std::mutex> host_lock(locks_here().host);
   if (!h || !complete || (h->n_rec && !partials)) return fail(LSPIV_EINVAL, "NULL argument");
+  LSPIV_TRY(not_on_sliding(h, "lspiv_ensemble_partials"));
   DeviceCtx* c;
   LSPIV_TRY(get_ctx(&c));
   bool ok = false;
@@ -498,6 +608,7 @@ int lspiv_ensemble_partials(lspiv_ensemble* h, double* partials, int* complete) 
 int lspiv_ensemble_finish_partials(lspiv_ensemble* h, const double* partials, float* u, float* v, float* corr_count, float* corr_mean) {
   std::lock_guard<std::mutex> host_lock(locks_here().host);
   if (!h || !u || !v || (h->n_rec && !partials)) return fail(LSPIV_EINVAL, "NULL argument");
+  LSPIV_TRY(not_on_sliding(h, "lspiv_ensemble_finish_partials"));
   DeviceCtx* c;
   LSPIV_TRY(get_ctx(&c));
   LSPIV_TRY(ensemble_mean_fit(h, c, h->flag_min_count));   // the shared workspaces may have been used since lspiv_ensemble_flag
@@ -528,6 +639,7 @@ int lspiv_ensemble_finish(lspiv_ensemble* h, float count_min, float n_frames, fl
                           float* corr_mean) {
   std::lock_guard<std::mutex> host_lock(locks_here().host);
   if (!h || !u || !v) return fail(LSPIV_EINVAL, "NULL argument");
+  LSPIV_TRY(not_on_sliding(h, "lspiv_ensemble_finish"));
   DeviceCtx* c;
   LSPIV_TRY(get_ctx(&c));
   h->flag_min_count = count_min * n_frames;
@@ -545,8 +657,84 @@ int lspiv_ensemble_finish(lspiv_ensemble* h, float count_min, float n_frames, fl
   return ensemble_deliver(h, c, u, v, corr_count, corr_mean);
 }
 
+// ---- sliding ensemble ---------------------------------------------------------------------------------------------------
+int lspiv_ensemble_set_sliding(lspiv_ensemble* h, int64_t window_pairs, int64_t stride_pairs) {
+  if (!h) return fail(LSPIV_EINVAL, "NULL argument");
+  if (h->pairs_done || h->foreign) return fail(LSPIV_EINVAL, "lspiv_ensemble_set_sliding must be called before the first accumulate");
+  if (stride_pairs < 1 || stride_pairs > window_pairs || window_pairs % stride_pairs != 0 || window_pairs >= (int64_t)1 << 24)
+    return fail(LSPIV_EINVAL, "sliding ensemble: need 1 <= stride <= window and window %% stride == 0, got window %lld, stride %lld",
+                (long long)window_pairs, (long long)stride_pairs);
+  h->sl_window = window_pairs; h->sl_stride = stride_pairs;
+  return LSPIV_OK;
+}
+
+int lspiv_ensemble_sliding_reserve(lspiv_ensemble* h, int64_t n_pairs) {
+  std::lock_guard<std::mutex> host_lock(locks_here().host);
+  if (!h) return fail(LSPIV_EINVAL, "NULL argument");
+  if (!h->sl_stride) return fail(LSPIV_EINVAL, "lspiv_ensemble_sliding_reserve: not a sliding handle (lspiv_ensemble_set_sliding)");
+  if (n_pairs < 0) return fail(LSPIV_EINVAL, "lspiv_ensemble_sliding_reserve: n_pairs %lld", (long long)n_pairs);
+  DeviceCtx* c;
+  LSPIV_TRY(get_ctx(&c));
+  return sliding_reserve(h, (size_t)((n_pairs + h->sl_stride - 1) / h->sl_stride), c->stream);
+}
+
+int lspiv_ensemble_sliding_finish(lspiv_ensemble* h, float count_min, int64_t first_out, int64_t n_out, float* u, float* v,
+                                  float* corr_count, float* corr_mean) {
+  std::lock_guard<std::mutex> host_lock(locks_here().host);
+  if (!h || !u || !v || !corr_count) return fail(LSPIV_EINVAL, "NULL argument");
+  if (!h->sl_stride) return fail(LSPIV_EINVAL, "lspiv_ensemble_sliding_finish: not a sliding handle (lspiv_ensemble_set_sliding)");
+  DeviceCtx* c;
+  LSPIV_TRY(get_ctx(&c));
+  const int64_t q = h->sl_window / h->sl_stride, n_blk = h->pairs_done / h->sl_stride, total = n_blk - q + 1;
+  if (first_out < 0 || n_out < 0 || first_out + n_out > std::max<int64_t>(total, 0))
+    return fail(LSPIV_EINVAL, "sliding ensemble: outputs [%lld, %lld) asked for, %lld pairs in blocks of %lld with windows of %lld pairs give %lld",
+                (long long)first_out, (long long)(first_out + n_out), (long long)h->pairs_done, (long long)h->sl_stride, (long long)h->sl_window,
+                (long long)std::max<int64_t>(total, 0));
+  const size_t n_win = (size_t)h->g.n_rows * h->g.n_cols, plane = (size_t)h->wy * h->wx;
+  const float min_count = count_min * (float)h->sl_window;
+  const int lane_major = h->sl_layout == 2 ? h->wy : 0;   // as the accumulate calls wrote the store, whatever 'walk' says now
+  // tiles of outputs sized to the plane workspace: what it already holds, at least 256 MiB worth, at least one output
+  const size_t out_bytes = n_win * plane * sizeof(float);
+  int64_t tile = (int64_t)(std::max<size_t>(c->planes_cap, (size_t)256 << 20) / out_bytes);
+  tile = std::max<int64_t>(1, std::min<int64_t>(tile, std::min<int64_t>(n_out, 65535)));
+  tile = std::max<int64_t>(1, std::min<int64_t>(tile, (int64_t)(0x7fffffff / n_win)));   // (records carry the tile's plane index in 32 bits)
+  int64_t flagged = 0, rescued = 0, skipped = 0;
+  ensemble_wait_accumulated(h, c->stream);   // accumulate_dev may have run on caller streams
+  for (int64_t j0 = first_out; j0 < first_out + n_out; j0 += tile) {
+    const int64_t nt = std::min<int64_t>(tile, first_out + n_out - j0);
+    const size_t n_planes = (size_t)nt * n_win;
+    LSPIV_TRY(ensure(&c->d_planes, &c->planes_cap, n_planes * plane * sizeof(float)));
+    LSPIV_TRY(ensure(&c->d_out, &c->out_cap, 3 * n_planes * sizeof(float)));   // [u | v | count]
+    float* const d_cnt = c->d_out + 2 * n_planes;
+    LSPIV_TRY(launch_status(lspiv::launch_ensemble_sliding_mean(h->d_store, h->d_store_cnt, (uint32_t)q, j0, (uint32_t)nt, (uint32_t)n_win, (int)plane,
+                                                                min_count, c->d_planes, d_cnt, c->stream, lane_major)));
+    LSPIV_TRY(launch_status(lspiv::launch_peaks_from_planes(c->d_planes, (uint32_t)n_planes, h->wy, h->wx, g_opt_border.load(), c->d_out,
+                                                             c->d_out + n_planes, c->stream)));
+    if (g_opt_rescue.load()) {
+      // the float64 rescue of lspiv_ensemble_finish per output: a flagged (output, window) is re-evaluated over that output's pairs
+      LSPIV_TRY(ensemble_flag(h, c, (uint32_t)n_planes));
+      bool complete = false;
+      if (h->n_rec) LSPIV_TRY(ensemble_partials(h, c, &complete, d_cnt, j0));
+      if (h->n_rec && complete) LSPIV_TRY(ensemble_final(h, c, h->d_totals, d_cnt, n_planes));
+      else h->last_skipped = h->last_flagged;
+      flagged += h->last_flagged; rescued += h->last_rescued; skipped += h->last_skipped;
+    }
+    LSPIV_TRY(apply_v_sign(c->d_out + n_planes, (int64_t)n_planes, c->stream));
+    const size_t o = (size_t)(j0 - first_out) * n_win;
+    HIP_TRY(hipMemcpyAsync(u + o, c->d_out, n_planes * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipMemcpyAsync(v + o, c->d_out + n_planes, n_planes * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipMemcpyAsync(corr_count + o, d_cnt, n_planes * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+    if (corr_mean) HIP_TRY(hipMemcpyAsync(corr_mean + o * plane, c->d_planes, n_planes * plane * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));   // the workspaces are reused by the next tile
+  }
+  h->last_flagged = flagged; h->last_rescued = rescued; h->last_skipped = skipped;
+  h->n_rec = 0;
+  return LSPIV_OK;
+}
+
 int lspiv_ensemble_export(lspiv_ensemble* h, float* corr_sum, float* corr_count) {
   if (!h || !corr_sum || !corr_count) return fail(LSPIV_EINVAL, "NULL argument");
+  LSPIV_TRY(not_on_sliding(h, "lspiv_ensemble_export"));
   DeviceCtx* c;
   LSPIV_TRY(get_ctx(&c));
   const size_t n_win = (size_t)h->g.n_rows * h->g.n_cols;
@@ -559,6 +747,7 @@ int lspiv_ensemble_export(lspiv_ensemble* h, float* corr_sum, float* corr_count)
 
 int lspiv_ensemble_import(lspiv_ensemble* h, const float* corr_sum, const float* corr_count, int add) {
   if (!h || !corr_sum || !corr_count) return fail(LSPIV_EINVAL, "NULL argument");
+  LSPIV_TRY(not_on_sliding(h, "lspiv_ensemble_import"));
   DeviceCtx* c;
   LSPIV_TRY(get_ctx(&c));
   const size_t n_win = (size_t)h->g.n_rows * h->g.n_cols, np = n_win * h->wy * h->wx;
@@ -589,6 +778,7 @@ int lspiv_ensemble_allreduce(lspiv_ensemble** handles, int n) {
   for (int k = 0; k < n; ++k) {
     const lspiv_ensemble* h = handles[k];
     if (!h) return fail(LSPIV_EINVAL, "handle %d is NULL", k);
+    LSPIV_TRY(not_on_sliding(h, "lspiv_ensemble_allreduce"));
     const lspiv_ensemble* r = handles[0];
     if (h->H != r->H || h->W != r->W || h->wy != r->wy || h->wx != r->wx || h->oy != r->oy || h->ox != r->ox)
       return fail(LSPIV_ESHAPE, "handle %d has another geometry than handle 0", k);
@@ -617,7 +807,8 @@ int lspiv_ensemble_destroy(lspiv_ensemble* h) {
   if (!h) return LSPIV_OK;
   ensemble_drop_kept(h);
   for (auto& e : h->acc_events) (void)hipEventDestroy(e.ev);
-  for (void* p : {(void*)h->d_sum, (void*)h->d_count, (void*)h->d_part, h->d_rescue, (void*)h->d_partial, (void*)h->d_totals})
+  for (void* p : {(void*)h->d_sum, (void*)h->d_count, (void*)h->d_part, h->d_rescue, (void*)h->d_partial, (void*)h->d_totals,
+                  (void*)h->d_store, (void*)h->d_store_cnt})
     if (p) hipFree(p);
   delete h;
   return LSPIV_OK;

@@ -86,7 +86,8 @@ struct PivParams {
   float* corr_sum;         // n_win * wy * wx
   float* corr_count;       // n_win
   // walking ensemble kernels: per-segment partial sums / counts (zeroed by the caller), merged in segment order
-  float* part_sum;         // n_seg * n_win * wy * wx, or nullptr: the single-owner kernels
+  float* part_sum;         // n_seg * n_win * wy * wx, or nullptr: the single-owner kernels.  With corr_sum == nullptr the slots are the
+                           // result: no merge follows the walking kernel (sliding ensemble: the slots are the handle's block store)
   float* part_cnt;         // n_seg * n_win
   float* dft_scratch;      // windows above 128 px: per-block slots of HBM for the two planes (piv_dft_global_kernel), else nullptr
   size_t dft_slot;         // floats per slot
@@ -135,6 +136,12 @@ struct EnsRescueArgs {
   uint32_t blk0, n_blk;       // this chunk's first pair-block in `partial`, pair-blocks over all retained chunks
   double* partial;            // (n_rec, n_blk, kEnsMaxCand, 5)
   const float* count;         // (n_win) pairs in the sum
+  // sliding ensemble (lspiv_ensemble_sliding_finish): the records were flagged on a tile of per-output mean planes, record.w =
+  // (output - out0) * virt_nwin + window, `count` is indexed the same way, and output j sums the pairs [j * stride, j * stride + window)
+  // of the absolute pair index only.  virt_nwin = 0: one sum over all pairs, record.w is the window
+  uint32_t virt_nwin;
+  uint32_t out0, stride, window;
+  uint32_t pair0;             // absolute index of this chunk's first pair
 };
 
 // ---- wave64 cross-lane helpers -----------------------------------------------------------------
@@ -468,6 +475,12 @@ hipError_t launch_ensemble_merge(const float* part_sum, const float* part_cnt, u
                                  float* corr_sum, float* corr_count, hipStream_t s, int lane_major_n = 0, bool split_halves = false);
 hipError_t launch_ensemble_mean(const float* sum, const float* count, float min_count, uint32_t n_win,
                                 int plane_elems, float* mean, hipStream_t s);
+// the slot layout the walking ensemble kernel of an n x n window writes (the lane_major_n / split_halves of launch_ensemble_merge)
+void walk_ensemble_slot_layout(int n, int* lane_major_n, bool* split_halves);
+// sliding ensemble: for the outputs j0 .. j0 + n_out - 1, mean[(j - j0) * n_win + w] = the fft-shifted row-major mean plane of the q
+// block slots (j .. j + q - 1, w) of `store` added in block order, NaN where the added counts are < min_count; count_out likewise
+hipError_t launch_ensemble_sliding_mean(const float* store, const float* store_cnt, uint32_t q, int64_t j0, uint32_t n_out, uint32_t n_win,
+                                        int plane_elems, float min_count, float* mean, float* count_out, hipStream_t s, int lane_major_n = 0);
 // orthoprojection gather (project.hip) and int16 result packing
 hipError_t launch_project(const void* frames, int dtype, int64_t src_elems, int n_frames, const int* nn_src,
                           const int* grp_of, const int* grp_off, const int* grp_src, float* out, int n_out,

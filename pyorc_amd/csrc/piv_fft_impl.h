@@ -2355,7 +2355,7 @@ static hipError_t launch_t(const PivParams& p, bool ensemble, hipStream_t s) {
     hipLaunchKernelGGL((piv_fft_walk_ensemble_kernel<T, N, WANT_NZ>), dim3(walk_blocks(p.n_seg, p.n_win, jobs_per_block, q.xcd_by_windows)),
                        dim3(BLOCK), ens_lds, s, q);
     hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return e;
+    if (e != hipSuccess || !p.corr_sum) return e;   // no corr_sum: the per-segment slots are what the caller wants (sliding ensemble)
     return launch_ensemble_merge(p.part_sum, p.part_cnt, p.n_seg, p.n_win, G::NN, p.corr_sum, p.corr_count, s, kEnsLdsRmw<N> ? N : 0, kEnsSplitHalves<N>);
   }
   if (ensemble) {

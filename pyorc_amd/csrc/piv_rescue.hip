@@ -543,10 +543,18 @@ __global__ __launch_bounds__(RBLOCK) void ens_partial_kernel(PivParams p, EnsRes
     for (int c = 0; c < kEnsMaxCand; ++c)
 #pragma unroll
       for (int q = 0; q < 5; ++q) acc[c][q] = 0.0;
-    const uint32_t pa = blk * kEnsPairBlock, pb = min(pa + (uint32_t)kEnsPairBlock, a.n_pairs);
+    uint32_t pa = blk * kEnsPairBlock, pb = min(pa + (uint32_t)kEnsPairBlock, a.n_pairs);
+    uint32_t rw = rec.w;
+    if (a.virt_nwin) {   // sliding ensemble: the record's window of the grid, and its output's pairs inside this chunk
+      const uint32_t jl = rec.w / a.virt_nwin;
+      rw = rec.w - jl * a.virt_nwin;
+      const int64_t first = (int64_t)(a.out0 + jl) * a.stride - (int64_t)a.pair0;   // relative to the chunk, may be negative
+      pa = (uint32_t)max((int64_t)pa, min(first, (int64_t)a.n_pairs));
+      pb = (uint32_t)max((int64_t)0, min((int64_t)pb, first + (int64_t)a.window));
+    }
     for (uint32_t pair = pa; pair < pb && rec.ncand != 0; ++pair) {
-      if (!(a.cmax[(size_t)pair * p.n_win + rec.w] > 0.0f)) continue;   // not in the sum (uniform over the wave)
-      const T* A = window_base<T>(p, pair * p.n_win + rec.w);
+      if (!(a.cmax[(size_t)pair * p.n_win + rw] > 0.0f)) continue;   // not in the sum (uniform over the wave)
+      const T* A = window_base<T>(p, pair * p.n_win + rw);
       const T* B = A + p.frame_elems;
       double mean_a, sd_a, mean_b, sd_b;
       if (staged) window_stats_wave2<T, true>(A, B, p.W, wy, wx, lane, mean_a, sd_a, mean_b, sd_b, la, lb);

@@ -74,6 +74,68 @@ hipError_t launch_ensemble_merge(const float* part_sum, const float* part_cnt, u
   return hipGetLastError();
 }
 
+// sliding ensemble: merge over WINDOWS OF BLOCKS + count filter + mean plane, one pass.  The block store holds one slot per (block,
+// window) in the layout the accumulating kernel left it in (fft-shifted row-major, or LANE_MAJOR as above); output j of the tile
+// (blockIdx.y) is the sum of the slots of blocks j .. j + q - 1 in block order -- a fixed sequence of float32 additions, so an output
+// does not depend on how the run was cut into accumulate calls -- divided by the summed count, NaN below min_count.
+// Streaming, no LDS: V elements per thread (V = 4: 16-byte loads, planes of a multiple of four samples; V = 1: the odd-sized planes of
+// the per-block path), the loads of up to four blocks are issued before their adds (independent addresses, one block stride apart).
+template <bool LANE_MAJOR, int V>
+__global__ __launch_bounds__(256) void ensemble_sliding_mean_kernel(const float* __restrict__ store, const float* __restrict__ store_cnt,
+                                                                    uint32_t q, int64_t j0, int64_t n_elems, uint32_t n_win, int plane,
+                                                                    int n, float min_count, float* __restrict__ mean,
+                                                                    float* __restrict__ count_out) {
+  typedef float fv __attribute__((ext_vector_type(V)));
+  const int64_t i = ((int64_t)blockIdx.x * 256 + threadIdx.x) * V;
+  if (i >= n_elems) return;
+  const uint32_t jl = blockIdx.y;
+  const int64_t win = i / plane;
+  const int e = (int)(i - win * plane);
+  const float* src = store + (j0 + jl) * n_elems + i;
+  const float* csrc = store_cnt + (j0 + jl) * (int64_t)n_win + win;
+  fv acc = *reinterpret_cast<const fv*>(src);
+  float c = csrc[0];
+  uint32_t b = 1;
+  for (; b + 4 <= q; b += 4) {
+    const fv x0 = *reinterpret_cast<const fv*>(src + (int64_t)b * n_elems), x1 = *reinterpret_cast<const fv*>(src + (int64_t)(b + 1) * n_elems);
+    const fv x2 = *reinterpret_cast<const fv*>(src + (int64_t)(b + 2) * n_elems), x3 = *reinterpret_cast<const fv*>(src + (int64_t)(b + 3) * n_elems);
+    const float c0 = csrc[(int64_t)b * n_win], c1 = csrc[(int64_t)(b + 1) * n_win], c2 = csrc[(int64_t)(b + 2) * n_win], c3 = csrc[(int64_t)(b + 3) * n_win];
+    acc += x0; acc += x1; acc += x2; acc += x3;
+    c += c0; c += c1; c += c2; c += c3;
+  }
+  for (; b < q; ++b) {
+    acc += *reinterpret_cast<const fv*>(src + (int64_t)b * n_elems);
+    c += csrc[(int64_t)b * n_win];
+  }
+  const fv out = c < min_count ? (fv)__builtin_nanf("") : acc / c;
+  const int64_t ow = (int64_t)jl * n_win + win;
+  int o = e;
+  if (LANE_MAJOR) {   // the decode of ensemble_merge_kernel: the thread's four elements are columns x .. x + 3 of row y
+    const int h = n / 2, qc = e / (4 * n), y = (e - qc * 4 * n) >> 2, x = 4 * qc;
+    const int ip = y + h >= n ? y + h - n : y + h, jp = x + h >= n ? x + h - n : x + h;
+    o = ip * n + jp;
+  }
+  *reinterpret_cast<fv*>(mean + ow * plane + o) = out;
+  if (e == 0) count_out[ow] = c;
+}
+
+hipError_t launch_ensemble_sliding_mean(const float* store, const float* store_cnt, uint32_t q, int64_t j0, uint32_t n_out, uint32_t n_win,
+                                        int plane_elems, float min_count, float* mean, float* count_out, hipStream_t s, int lane_major_n) {
+  const int64_t n_elems = (int64_t)n_win * plane_elems;
+  if (n_elems == 0 || n_out == 0) return hipSuccess;
+  if (q < 1 || n_out > 65535u) return hipErrorInvalidValue;
+  if (lane_major_n && (lane_major_n * lane_major_n != plane_elems || lane_major_n % 8 != 0)) return hipErrorInvalidValue;
+  const int v = plane_elems % 4 == 0 ? 4 : 1;
+  const dim3 grid((unsigned)((n_elems / v + 255) / 256), n_out);
+  if (lane_major_n)
+    hipLaunchKernelGGL((ensemble_sliding_mean_kernel<true, 4>), grid, dim3(256), 0, s, store, store_cnt, q, j0, n_elems, n_win, plane_elems, lane_major_n, min_count, mean, count_out);
+  else if (v == 4)
+    hipLaunchKernelGGL((ensemble_sliding_mean_kernel<false, 4>), grid, dim3(256), 0, s, store, store_cnt, q, j0, n_elems, n_win, plane_elems, 0, min_count, mean, count_out);
+  else
+    hipLaunchKernelGGL((ensemble_sliding_mean_kernel<false, 1>), grid, dim3(256), 0, s, store, store_cnt, q, j0, n_elems, n_win, plane_elems, 0, min_count, mean, count_out);
+  return hipGetLastError();
+}
+
 hipError_t launch_ensemble_mean(const float* sum, const float* count, float min_count, uint32_t n_win,
                                 int plane_elems, float* mean, hipStream_t s) {
   if (n_win == 0) return hipSuccess;

@@ -67,6 +67,7 @@ def get_piv(frames, window_size=None, overlap=None, engine: str = "hip", ensembl
     pixel (default 1.0 => velocities in px/s).  ``**kwargs`` are forwarded to ``get_ffpiv`` (``chunksize``,
     ``memory_factor``, ``corr_min``, ``s2n_min``, ``count_min``, ``signal_threshold``).  ``search_area_size``: None (the window size,
     as in the reference) or a larger square search area of 16, 32 or 64 px ("Extended search area").
+    ``ensemble_window`` / ``ensemble_stride`` (in ``**kwargs``, with ``ensemble_corr=True``): a sliding ensemble, INTEGRATION.md 2c.
     """
     if engine not in ENGINES:
         raise ValueError(f"Selected PIV engine {engine} does not exist.")

@@ -176,7 +176,11 @@ def u_v_displacement(corr, n_rows: int, n_cols: int, engine: str = "hip") -> Tup
 class Ensemble:
     """Device-resident ensemble-correlation accumulator (pyorc/velocimetry/ffpiv.py:182-376)."""
 
-    def __init__(self, dim_size, window_size, overlap):
+    def __init__(self, dim_size, window_size, overlap, sliding=None):
+        """``sliding=(M, s)``: a sliding ensemble -- outputs over windows of M pairs that advance by s
+        pairs, read with :meth:`finish_sliding`; every ``accumulate`` but the last must then hold a multiple of s pairs."""
+        if sliding is not None:
+            sliding = window.sliding_spec(True, *sliding)
         lib = _lib.load()
         _lib.require_device()
         self._h = C.c_void_p()
@@ -191,6 +195,10 @@ class Ensemble:
         self.device = int(d.value)   # the handle's sums live here; every call on it is made with this device current
         self._held = []   # DeviceFrames chunks the handle borrows until finish (float64 rescue of the final fit)
         self._retain_mode = None   # set_retain not called yet: accumulate() of a DeviceFrames chunk picks RETAIN_BORROW
+        self.sliding = sliding
+        self.pairs_done = 0        # pairs accumulated so far (a sliding handle's outputs are counted from it)
+        if sliding is not None:
+            _lib.check(lib.lspiv_ensemble_set_sliding(self._h, sliding[0], sliding[1]))
 
     RETAIN_NONE, RETAIN_COPY, RETAIN_BORROW = 0, 1, 2
 
@@ -251,6 +259,7 @@ class Ensemble:
         _lib.check(_lib.load().lspiv_ensemble_accumulate(self._h, _lib.ptr(a), _lib.DTYPE_CODES[a.dtype], a.shape[0],
                                                          float(corr_min), float(s2n_min), _sig(signal_threshold),
                                                          _lib.ptr(cm), _lib.ptr(sn)))
+        self.pairs_done += P
         return cm, sn
 
     def accumulate_dev(self, d_frames: int, dtype, n_frames: int, corr_min: float, s2n_min: float,
@@ -259,6 +268,7 @@ class Ensemble:
         _lib.check(_lib.load().lspiv_ensemble_accumulate_dev(
             self._h, C.c_void_p(d_frames), _lib.DTYPE_CODES[np.dtype(dtype)], n_frames, float(corr_min), float(s2n_min),
             _sig(signal_threshold), C.c_void_p(d_corr_s2n), C.c_void_p(stream) if stream else None))
+        self.pairs_done += int(n_frames) - 1
 
     def finish(self, count_min: float, n_frames: float, return_mean: bool = False):
         """Count filter + mean plane + sub-pixel peak: u, v (1, n_rows, n_cols) px, corr_count (n_win,)."""
@@ -271,6 +281,32 @@ class Ensemble:
                                                      _lib.ptr(v), _lib.ptr(cnt),
                                                      _lib.ptr(mean) if mean is not None else None))
         return (u, v, cnt, mean) if return_mean else (u, v, cnt)
+
+    def reserve_sliding(self, n_pairs: int):
+        """Room in the block store for a run of ``n_pairs`` pairs in all, allocated once (before the first ``accumulate``): the store
+        then never grows, which would double it and copy the blocks written so far."""
+        if self.sliding is None:
+            raise ValueError("reserve_sliding needs an Ensemble made with sliding=(M, s)")
+        _lib.check(_lib.load().lspiv_ensemble_sliding_reserve(self._h, int(n_pairs)))
+
+    def finish_sliding(self, count_min: float, first: int = 0, n: Optional[int] = None, return_planes: bool = False):
+        """Outputs ``first .. first + n - 1`` of a sliding ensemble (``n`` None: all from ``first``): u, v (n, n_rows, n_cols) px and
+        count (n, n_rows, n_cols) -- NaN where fewer than ``count_min * M`` pairs of the window were kept --, and with
+        ``return_planes`` the mean planes (n, n_win, wy, wx)."""
+        if self.sliding is None:
+            raise ValueError("finish_sliding needs an Ensemble made with sliding=(M, s)")
+        M, s = self.sliding
+        total = max(0, self.pairs_done // s - M // s + 1)
+        first = int(first)
+        n = total - first if n is None else int(n)
+        if first < 0 or n < 1 or first + n > total:
+            raise ValueError(f"outputs [{first}, {first + n}) asked for, the {self.pairs_done} pairs accumulated give {total}")
+        n_win = self.n_rows * self.n_cols
+        u, v, cnt = (np.empty((n, self.n_rows, self.n_cols), dtype=np.float32) for _ in range(3))
+        mean = np.empty((n, n_win) + self.window_size, dtype=np.float32) if return_planes else None
+        _lib.check(_lib.load().lspiv_ensemble_sliding_finish(self._h, float(count_min), first, n, _lib.ptr(u), _lib.ptr(v), _lib.ptr(cnt),
+                                                             _lib.ptr(mean) if mean is not None else None))
+        return (u, v, cnt, mean) if return_planes else (u, v, cnt)
 
     # ---- the finish in three stages, for a sum spread over several handles (include/lspiv.h; pyorc_amd.shard.sharded_ensemble) ----
     PARTIAL_DOUBLES = 20

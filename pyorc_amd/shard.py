@@ -121,6 +121,8 @@ def sharded_ensemble(load_frames: Callable[[int, int], np.ndarray], n_pairs: int
     re-evaluated in float64 from the frames on every rank's block (round 4), like on one GPU.
     """
     ens = make_ensemble()
+    if getattr(ens, "sliding", None) is not None:
+        raise NotImplementedError("a sliding ensemble (sliding=(M, s)) is not implemented for pyorc_amd.shard: its outputs span the ranks' pair blocks")
     f0, f1 = frame_block(n_pairs, comm.rank, comm.world, align)
     if f1 - f0 >= 2:
         cm, sn = ens.accumulate(load_frames(f0, f1), corr_min, s2n_min, signal_threshold)

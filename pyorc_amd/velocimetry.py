@@ -175,6 +175,8 @@ def get_ffpiv(
     time: Optional[np.ndarray] = None,
     prefetch: Optional[int] = None,
     devices=None,
+    ensemble_window: Optional[int] = None,
+    ensemble_stride: Optional[int] = None,
 ):
     """Compute time-resolved (or ensemble) PIV on the MI355X; signature of pyorc's ``get_ffpiv`` (ffpiv.py:24-42).
 
@@ -194,6 +196,11 @@ def get_ffpiv(
     own over a contiguous block of pairs cut on the kernels' anchors (:func:`device_work`), so per-timestep results are the bits of
     one device; ensemble sums are reduced device to device (``piv.ensemble_allreduce``) and finished with the float64 rescue of
     every device's pairs (``shard.staged_finish``).  A ``DeviceFrames`` stack runs on the device it lives on.
+
+    ``ensemble_window`` = M, ``ensemble_stride`` = s (with ``ensemble_corr=True`` only; the project's own mode, INTEGRATION.md section
+    2c): a SLIDING ensemble -- output j is fitted on the mean correlation plane of the M pairs [j s, j s + M), so the result keeps a time
+    axis of ``(P // s) - M // s + 1`` steps.  1 <= s <= M, M % s == 0; s None = M (block ensembles).  Chunks are cut on multiples of s
+    and every chunking gives the same bits.  One device, materialised stacks (numpy, ``DeviceFrames``).
     """
     if engine != "hip":
         raise ValueError(f"Selected PIV engine {engine} does not exist.")
@@ -202,11 +209,15 @@ def get_ffpiv(
     if ensemble_corr and isinstance(window_size, window.SearchWindow):
         raise NotImplementedError("ensemble_corr=True with search_area_size != window_size is not implemented: the search-area kernels "
                                   "serve per-timestep mode only")
+    sliding = window.sliding_spec(ensemble_corr, ensemble_window, ensemble_stride)
     n_frames = len(frames)
     dim_size = tuple(frames[0].shape)
     dtype = frames.dtype if np.dtype(frames.dtype) in (np.dtype(np.uint8), np.dtype(np.float32)) else np.float64
     n_rows, n_cols = len(y), len(x)
     n_win = n_rows * n_cols
+    if sliding is not None:
+        return _get_ffpiv_sliding(frames, y, x, dt, window_size, overlap, res_y, res_x, chunksize, memory_factor, engine, corr_min, s2n_min,
+                                  count_min, signal_threshold, time, prefetch, devices, sliding, n_frames, dim_size, dtype)
     _, ref_slices, slices = _plan_slices(n_frames, dim_size, window_size, overlap, dtype, chunksize, memory_factor, engine, n_win)
     if time is None:
         time = frames["time"] if _is_xr(frames) else np.arange(n_frames)
@@ -230,6 +241,64 @@ def get_ffpiv(
         return _run_resident(frames, work, sink, devs, time, signal_threshold)
     depth = (executor.default_depth() if prefetch is None else int(prefetch)) if hasattr(frames, "load") else 0
     return _run_chunks(frames, work, sink, depth, devs, time, window_size, overlap, (n_rows, n_cols))
+
+
+def sliding_labels(time, dt, M: int, s: int, n_out: int):
+    """(time label, dt_j) of every output of a sliding ensemble: the mean second-frame time and the mean ``dt`` of its M pairs."""
+    t2 = np.asarray(time, dtype=np.float64)[1:]
+    dt = np.asarray(dt, dtype=np.float64)
+    return (np.array([t2[j * s:j * s + M].mean() for j in range(n_out)]), np.array([dt[j * s:j * s + M].mean() for j in range(n_out)]))
+
+
+def _get_ffpiv_sliding(frames, y, x, dt, window_size, overlap, res_y, res_x, chunksize, memory_factor, engine, corr_min, s2n_min, count_min,
+                       signal_threshold, time, prefetch, devices, sliding, n_frames, dim_size, dtype):
+    """``get_ffpiv`` with ``ensemble_window``: the chunk loop of the ensemble mode on chunks cut on multiples of s pairs, one sliding
+    ``Ensemble`` handle, a result with one time step per output (:func:`_sliding_sink`)."""
+    M, s = sliding
+    n_win = len(y) * len(x)
+    if _is_lazy(frames):
+        raise NotImplementedError("ensemble_window with a lazy stack is not implemented: load the stack (numpy or DeviceFrames) first")
+    n_blk, n_out = window.sliding_outputs(n_frames - 1, M, s)
+    many = "ensemble_window with devices={} is not implemented: a sliding ensemble runs on one device"
+    if devices is not None and not isinstance(devices, str) and len(list(devices)) > 1:
+        raise NotImplementedError(many.format(list(devices)))
+    devs = _resolve_frames_devices(frames, devices)
+    if devs is not None and len(devs) > 1:
+        raise NotImplementedError(many.format(list(devs)))
+    slices = plan_sliding_slices(n_frames, dim_size, window_size, overlap, dtype, chunksize, memory_factor, engine, n_win, s,
+                                 None if devs is None else devs[0])
+    if time is None:
+        time = frames["time"] if _is_xr(frames) else np.arange(n_frames)
+    dt_arr = np.asarray(_values(dt), dtype=np.float64)
+    if dt_arr.shape != (n_frames - 1,):
+        raise ValueError(f"dt must have one entry per frame pair ({n_frames - 1}), got shape {dt_arr.shape}")
+    sink = _sliding_sink(n_frames - 1, y, x, dt_arr, res_x, res_y, window_size, overlap, signal_threshold, corr_min, s2n_min, count_min, M, s,
+                         n_out)
+    depth = (executor.default_depth() if prefetch is None else int(prefetch)) if hasattr(frames, "load") else 0
+    return _run_chunks(frames, [slices], sink, depth, devs, time, window_size, overlap, (len(y), len(x)))
+
+
+def plan_sliding_slices(n_frames, dim_size, window_size, overlap, dtype, chunksize, memory_factor, engine, n_win, s, device=None):
+    """The chunk plan of a sliding ensemble: the planner of :func:`_plan_slices` with the run's block store counted next to every
+    chunk, and chunks of a multiple of s pairs (>= one block) -- ``window.chunk_alignment`` keeps its meaning for the other modes."""
+    blocks = -(-(n_frames - 1) // s)     # (a trailing partial block has a slot too)
+
+    def need(n):
+        return window.required_memory(n_frames=n, dim_size=dim_size, window_size=window_size, overlap=overlap, dtype=dtype,
+                                      sliding_blocks=blocks)
+
+    with executor.on_device(device):
+        avail = window.available_memory() / memory_factor
+    cs, _ = plan_chunks(n_frames, need(n_frames), avail, chunksize, engine, n_win=n_win)
+    if cs >= n_frames and (n_frames - 1) * max(n_win, 1) <= MAX_WINDOWS_PER_LAUNCH:
+        return [(0, n_frames)]     # the whole stack in one call: the trailing pairs ride along (the last call may end inside a block)
+    slices = aligned_slices(n_frames, cs, s, n_win=n_win, fits=lambda n: need(n) <= avail)
+    if len(slices) > 1 and (slices[0][1] - 1) % s != 0:
+        # aligned_slices fell back to chunks off the blocks: a sliding handle takes whole blocks only (all calls but the last)
+        raise ValueError(f"ensemble_stride {s}: a block of {s} pairs ({s + 1} frames, {need(s + 1)} bytes with the block store of {blocks} blocks) does "
+                         f"not fit one call -- {int(avail)} bytes are available (memory_factor, chunksize {chunksize}) and one launch takes "
+                         f"{MAX_WINDOWS_PER_LAUNCH} windows, this grid has {n_win} per pair; use a smaller ensemble_stride")
+    return slices
 
 
 # ---------------------------------------------------------------------------------------------------------------------------------
@@ -449,6 +518,55 @@ def _ensemble_sink(n_pairs, n_workers, y, x, dt, res_x, res_y, window_size, over
         data = {"s2n": s2n_mean, "corr": corr_mean, "v_x": (u * res_x / dt_av).astype(np.float32),
                 "v_y": (v * res_y / dt_av).astype(np.float32)}
         return _dataset(data, time[last + 1:last + 2], y, x, like)
+
+    return launch, close, result
+
+
+def _sliding_sink(n_pairs, y, x, dt, res_x, res_y, window_size, overlap, signal_threshold, corr_min, s2n_min, count_min, M, s, n_out):
+    """The ensemble sink for a sliding ensemble: one handle with a block store, ``n_out`` time steps.
+    ``corr`` / ``s2n`` of output j: nanmean over its M pairs of the masked per-pair values, the windows below ``count_min * M`` set to
+    NaN first (as ffpiv.py:284-286 does for the one ensemble); velocities with the mean ``dt`` of those pairs."""
+    full = {k: np.empty((n_pairs, len(y) * len(x)), dtype=np.float32) for k in ("corr", "s2n")}
+    done = []
+    handle = [None]
+
+    def launch(k, frames, p0, p1):
+        if handle[0] is None:
+            handle[0] = piv.Ensemble(tuple(frames.shape[1:]), window_size, overlap, sliding=(M, s))
+            handle[0].reserve_sliding(n_pairs)     # the whole run's block store at once: what plan_sliding_slices counted
+        handle[0].accumulate(frames, corr_min, s2n_min, signal_threshold, out=(full["corr"][p0:p1], full["s2n"][p0:p1]))
+        done.append((p0, p1))
+
+    def close(per_device):
+        h = handle[0]
+        if h is not None:
+            with executor.on_device(getattr(h, "device", None)):
+                if per_device[0] is not None:
+                    per_device[0]["ensemble"] = h.stats() if hasattr(h, "stats") else {}
+                h.close()
+
+    def result(time, like):
+        done.sort()
+        if not done or done[0][0] != 0 or done[-1][1] != n_pairs or any(a[1] != b[0] for a, b in zip(done, done[1:])):
+            raise ValueError("ensemble_window: a chunk lost frames while it was loaded; the outputs of a sliding ensemble need every pair")
+        h = handle[0]
+        with executor.on_device(getattr(h, "device", None)):
+            u, v, cnt = h.finish_sliding(count_min)
+        low = cnt.reshape(n_out, -1) < np.float32(count_min) * np.float32(M)     # the device's threshold, in its arithmetic
+        corr = np.empty((n_out, len(y) * len(x)), dtype=np.float32)
+        s2n = np.empty_like(corr)
+        with warnings.catch_warnings():
+            warnings.simplefilter("ignore", category=RuntimeWarning)
+            for j in range(n_out):
+                c = full["corr"][j * s:j * s + M].copy()
+                c[:, low[j]] = np.nan
+                corr[j] = np.nanmean(c, axis=0)
+                s2n[j] = np.nanmean(full["s2n"][j * s:j * s + M], axis=0)
+        t_out, dt_out = sliding_labels(np.asarray(time), dt, M, s, n_out)
+        shape = (n_out, len(y), len(x))
+        data = {"s2n": s2n.reshape(shape), "corr": corr.reshape(shape),
+                "v_x": (u * res_x / dt_out[:, None, None]).astype(np.float32), "v_y": (v * res_y / dt_out[:, None, None]).astype(np.float32)}
+        return _dataset(data, t_out, y, x, like)
 
     return launch, close, result
 

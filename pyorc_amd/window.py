@@ -91,17 +91,59 @@ def get_rect_coordinates(dim_size, window_size, overlap, search_area_size=None, 
 
 
 def required_memory(n_frames: int, dim_size, window_size, overlap, search_area_size=None,
-                    dtype=np.uint8, with_planes: bool = False) -> int:
+                    dtype=np.uint8, with_planes: bool = False, sliding_blocks: int = 0) -> int:
     """HBM bytes one fused call on ``n_frames`` frames needs (frames + four result planes).
 
     The reference's figure is the host RAM of the materialised window stack + correlation volume
     (x3.9 .. x14.8 of the frames); the fused kernel materialises neither.
+
+    ``sliding_blocks``: the blocks of a sliding ensemble's WHOLE run (:func:`sliding_outputs`); its block store stays in HBM next
+    to every chunk (:func:`sliding_store_bytes`).
     """
     sa = window_size if search_area_size is None else search_area_size
     code = _lib.DTYPE_CODES[np.dtype(dtype)]
     r = _lib.load().lspiv_required_bytes(n_frames, dim_size[0], dim_size[1], code, sa[0], sa[1],
                                          overlap[0], overlap[1], int(with_planes))
-    return _lib.check(r)
+    need = _lib.check(r)
+    if sliding_blocks:
+        need += sliding_store_bytes(sliding_blocks, dim_size, sa, overlap)
+    return need
+
+
+def sliding_spec(ensemble_corr: bool, ensemble_window, ensemble_stride):
+    """The sliding-ensemble keywords of ``get_ffpiv`` checked -> None (no ``ensemble_window``) or ``(M, s)`` pairs: 1 <= s <= M and
+    M % s == 0; ``ensemble_stride`` None means s = M (block ensembles).  Both keywords need ``ensemble_corr=True``.  Host-only."""
+    if ensemble_window is None:
+        if ensemble_stride is not None:
+            raise ValueError("ensemble_stride needs ensemble_window")
+        return None
+    if not ensemble_corr:
+        raise ValueError("ensemble_window / ensemble_stride need ensemble_corr=True")
+    for name, val in (("ensemble_window", ensemble_window), ("ensemble_stride", ensemble_stride)):
+        if val is not None and (isinstance(val, bool) or not isinstance(val, (int, np.integer))):
+            raise ValueError(f"{name} must be a whole number of frame pairs, got {val!r}")
+    M = int(ensemble_window)
+    s = M if ensemble_stride is None else int(ensemble_stride)
+    if not (1 <= s <= M) or M % s != 0:
+        raise ValueError(f"need 1 <= ensemble_stride <= ensemble_window and ensemble_window % ensemble_stride == 0, got "
+                         f"ensemble_window {M}, ensemble_stride {s}")
+    return M, s
+
+
+def sliding_outputs(n_pairs: int, M: int, s: int) -> Tuple[int, int]:
+    """(n_blk, n_out) of a sliding ensemble over ``n_pairs`` pairs: block b = pairs [b s, (b + 1) s), output j = blocks j .. j + M / s - 1.
+    Trailing pairs that fill no block enter no output."""
+    n_blk = n_pairs // s
+    n_out = n_blk - M // s + 1
+    if n_out < 1:
+        raise ValueError(f"ensemble_window {M} needs at least {M} pairs, got {n_pairs}")
+    return n_blk, n_out
+
+
+def sliding_store_bytes(n_blocks: int, dim_size, window_size, overlap) -> int:
+    """HBM bytes of a sliding ensemble's block store: one float32 plane sum and one count per (block, window).  Host-only."""
+    n_rows, n_cols = get_array_shape(dim_size, window_size, overlap)
+    return int(n_blocks) * n_rows * n_cols * (int(window_size[0]) * int(window_size[1]) + 1) * 4
 
 
 def available_memory() -> int:
