@@ -39,7 +39,8 @@ extern "C" {
 
 #define LSPIV_ABI_VERSION 5   /* (additions since, nothing existing moved, no version change: the search-area entry points lspiv_piv_search_pairs_at /
                                * lspiv_piv_search_pairs_dev_at and lspiv_search_supported; the sliding ensemble, lspiv_ensemble_set_sliding /
-                               * lspiv_ensemble_sliding_reserve / lspiv_ensemble_sliding_finish)
+                               * lspiv_ensemble_sliding_reserve / lspiv_ensemble_sliding_finish; multi-pass PIV, lspiv_shift_supported /
+                               * lspiv_piv_shift_pairs_dev_at / lspiv_piv_predict_shift_dev / lspiv_piv_multipass_dev_at / lspiv_piv_multipass_at)
                                * 5 (round 6): lspiv_chunk_alignment(wy, wx) without a grid now returns the alignment that is right on EVERY grid (75
                                * where it returned 25: callers that cut chunks on it stay bit-reproducible on large grids); additions:
                                * lspiv_upload_frames, lspiv_trace / lspiv_trace_read; the host-pointer projection entry points no longer
@@ -224,6 +225,52 @@ int lspiv_piv_search_pairs_at(const void* frames, int dtype, int64_t T, int64_t 
 int lspiv_piv_search_pairs_dev_at(const void* d_frames, int dtype, int64_t T, int64_t H, int64_t W,
                                   int say, int sax, int wy, int wx, int oy, int ox, float signal_threshold, int64_t pair_offset,
                                   float* d_out, float* d_corr_planes, void* stream);
+
+/* Multi-pass PIV: a chain of passes (wy_k, wx_k, oy_k, ox_k), k = 0 .. K, square even windows, non-increasing; a coarse pass predicts the
+ * displacement, each finer pass cuts its window of frame t+1 at an INTEGER offset from that prediction and measures the residual, the
+ * full window against a full window (the project's own semantics, unpinned like the search area).  All
+ * pass-to-pass arithmetic is in the kernels' orientation (u column shift, v row shift, rows downward); option "v_sign" is applied once,
+ * to the final result.  Option "norm_clip" = 0 and "signal_mode" = 1 are LSPIV_EUNSUPPORTED in every entry point below.
+ *
+ * lspiv_shift_supported: 1 for wy = wx in {16, 32, 64} (the windows of passes k >= 1), else 0.  Host-only.
+ *
+ * lspiv_piv_shift_pairs_dev_at: ONE shifted pass.  d_shift: (T-1) * n_win * 2 int16 {dy, dx} per (pair, window) on the device, or NULL
+ * (all zero).  Per window and pair: A = the window of frame t at its grid origin (y0, x0), B = the window of frame t+1 at (y0 + dy,
+ * x0 + dx), the offset CLAMPED by the kernel to dy in [-y0, H - wy - y0], dx in [-x0, W - wx - x0] (no offset array reads outside the
+ * stack); plane, corr_max, s2n as lspiv_piv_pairs computes them for the pair (A, B), the signal threshold scoring A and the shifted B;
+ * u = clamped dx + residual u, v = clamped dy + residual v (float32 sums, a NaN residual stays NaN).  d_out, d_corr_planes as
+ * lspiv_piv_pairs_dev_at.  Per-pair kernels, one window per job: a window's result depends on its own samples and offset alone, so
+ * results do not depend on the chunking (pair_offset is accepted for symmetry).  Unsupported windows: LSPIV_EUNSUPPORTED.
+ *
+ * lspiv_piv_predict_shift_dev: the predictor between two passes.  d_u, d_v: n_pairs * coarse windows float32 (kernel orientation);
+ * d_shift: n_pairs * fine windows * 2 int16 {dy, dx}.  Per pair: q = rint (half to even, float32) of every vector, clamped to the int16
+ * range [-32768, 32767] (no displacement a frame can hold is touched), valid when u and v are finite (any finite float32); M2 = twice the median of q over the valid vectors of the 3 x 3 neighbourhood clipped at the grid's edges (even count: the
+ * sum of the two middle values; none: 0), u and v separately; bilinear interpolation between the coarse window centres origin + w / 2 at
+ * the fine centres, integer weights w1 = clamp(cf - cc[i0], 0, s), w0 = s - w1, i0 = clamp(floor((cf - cc[0]) / s), 0, count - 2)
+ * (constant outside the outermost centres; a one-entry axis has w1 = 0); d = floor((2 num + den) / (2 den)), den = 2 s_y s_x; then the
+ * frame clamp above.  Exact integer arithmetic after the rint.  Windows must be even; a frame side above 32767 is LSPIV_EINVAL.
+ *
+ * lspiv_piv_multipass_dev_at: the chain.  passes: n_passes * 4 ints {wy, wx, oy, ox} on the HOST, coarsest first; the last one is the
+ * grid of the result.  Pass 0 is lspiv_piv_pairs_dev_at of its window (any window that serves; bit for bit, at the same pair_offset);
+ * passes k >= 1 need lspiv_shift_supported.  d_out: 4 * (T-1) * n_win floats of the LAST pass's grid, [u | v | corr_max | s2n];
+ * d_corr_planes: NULL or the last pass's planes; d_shift_out: NULL or the last pass's CLAMPED offsets, (T-1) * n_win * 2 int16.
+ * n_passes = 1 is lspiv_piv_pairs_dev_at (d_shift_out: zeros).  Chunks cut on lspiv_chunk_alignment_grid of PASS 0 reproduce one
+ * call bit for bit: every later pass is pair-local.  Intermediates live in a per-device workspace: one stream at a time.
+ * lspiv_piv_multipass_at: the host-fed twin -- the chunk is staged like lspiv_piv_pairs_at stages it (float64 narrowed to float32),
+ * the chain runs on it, results come back; shift_out: NULL or host int16. */
+int lspiv_shift_supported(int wy, int wx);
+int lspiv_piv_shift_pairs_dev_at(const void* d_frames, int dtype, int64_t T, int64_t H, int64_t W,
+                                 int wy, int wx, int oy, int ox, float signal_threshold, int64_t pair_offset,
+                                 const int16_t* d_shift, float* d_out, float* d_corr_planes, void* stream);
+int lspiv_piv_predict_shift_dev(const float* d_u, const float* d_v, int64_t n_pairs, int64_t H, int64_t W,
+                                int cwy, int cwx, int coy, int cox, int fwy, int fwx, int foy, int fox,
+                                int16_t* d_shift, void* stream);
+int lspiv_piv_multipass_dev_at(const void* d_frames, int dtype, int64_t T, int64_t H, int64_t W,
+                               int n_passes, const int* passes, float signal_threshold, int64_t pair_offset,
+                               float* d_out, float* d_corr_planes, int16_t* d_shift_out, void* stream);
+int lspiv_piv_multipass_at(const void* frames, int dtype, int64_t T, int64_t H, int64_t W,
+                           int n_passes, const int* passes, float signal_threshold, int64_t pair_offset,
+                           float* u, float* v, float* corr_max, float* s2n, float* corr_planes, int16_t* shift_out);
 
 /* Host frames into a slice of an HBM-resident stack, the way lspiv_piv_pairs brings them in -- pinned ring, staging threads,
  * float64 narrowed to float32 with the "narrow_offset" guard (so d_dst receives n_frames * H * W samples of LSPIV_F32 for LSPIV_F64

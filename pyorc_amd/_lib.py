@@ -77,6 +77,11 @@ SIGNATURES = {
     "lspiv_search_supported": (_i32, [_i32, _i32, _i32, _i32]),
     "lspiv_piv_search_pairs_at": (_i32, [_vp, _i32, _i64, _i64, _i64, _i32, _i32, _i32, _i32, _i32, _i32, _f32, _i64, _vp, _vp, _vp, _vp, _vp]),
     "lspiv_piv_search_pairs_dev_at": (_i32, [_vp, _i32, _i64, _i64, _i64, _i32, _i32, _i32, _i32, _i32, _i32, _f32, _i64, _vp, _vp, _vp]),
+    "lspiv_shift_supported": (_i32, [_i32, _i32]),
+    "lspiv_piv_shift_pairs_dev_at": (_i32, [_vp, _i32, _i64, _i64, _i64, _i32, _i32, _i32, _i32, _f32, _i64, _vp, _vp, _vp, _vp]),
+    "lspiv_piv_predict_shift_dev": (_i32, [_vp, _vp, _i64, _i64, _i64, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _vp, _vp]),
+    "lspiv_piv_multipass_dev_at": (_i32, [_vp, _i32, _i64, _i64, _i64, _i32, _vp, _f32, _i64, _vp, _vp, _vp, _vp]),
+    "lspiv_piv_multipass_at": (_i32, [_vp, _i32, _i64, _i64, _i64, _i32, _vp, _f32, _i64, _vp, _vp, _vp, _vp, _vp, _vp]),
     "lspiv_u_v_displacement": (_i32, [_vp, _i64, _i64, _i32, _i32, _vp, _vp]),
     "lspiv_ensemble_begin": (_i32, [_i64, _i64, _i32, _i32, _i32, _i32, C.POINTER(_vp)]),
     "lspiv_ensemble_accumulate": (_i32, [_vp, _vp, _i32, _i64, _f32, _f32, _f32, _vp, _vp]),
@@ -210,7 +215,7 @@ def load() -> C.CDLL:
     return lib
 
 
-KERNEL_SOURCES = ("piv_fft_impl.h", "fft_regs.h", "common.h", "piv_rescue.hip")
+KERNEL_SOURCES = ("piv_fft_impl.h", "fft_regs.h", "common.h", "piv_rescue.hip", "piv_multipass.hip")
 
 
 def _hash_files(paths) -> str:
@@ -331,7 +336,7 @@ def as_frames(imgs) -> np.ndarray:
 
 
 def kernel_code_hash(csrc_dir: Optional[str] = None) -> str:
-    """sha256 over the sources of the fused PIV kernels (csrc/piv_fft_impl.h, fft_regs.h, common.h, piv_rescue.hip): what a
+    """sha256 over the sources of the fused PIV kernels (csrc/piv_fft_impl.h, fft_regs.h, common.h, piv_rescue.hip, piv_multipass.hip): what a
     committed profile summary is keyed to (tools/summarize_profile.py writes it, bench.py compares it) and what the binary
     carries as LSPIV_BUILD_KERNEL_HASH."""
     d = csrc_dir or os.path.join(_HERE, "csrc")

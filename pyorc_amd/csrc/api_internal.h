@@ -63,6 +63,7 @@ struct DeviceCtx {
   void* d_scratch = nullptr; size_t scratch_cap = 0;   // temporaries of *_dev entry points (normalize)
   void* d_dft = nullptr; size_t dft_cap = 0;           // plane slots of the windows above 128 px (grow-only)
   uint8_t* d_keep = nullptr; size_t keep_cap = 0;      // per-window flags of the "stack" signal mode
+  void* d_mp = nullptr; size_t mp_cap = 0;             // multi-pass chains: the intermediate passes' results and offsets (grow-only)
   // float64 rescue pass: one set of lists per launch stream (a stream orders its own PIV kernel -> rescue kernel pairs;
   // two streams must not share counters), grow-only
   struct RescueWs { hipStream_t stream; void* base; size_t cap_bytes; uint32_t cap_fit, cap_amb; };
@@ -90,10 +91,12 @@ struct DeviceCtx {
 //   host:     host-pointer entry points share one set of workspaces (upload buffer, result buffer, pinned ring) per device
 //   dispatch: the PIV kernel and the rescue kernels of ONE launch share their stream's lists and counters (see dispatch())
 //   lists:    the per-stream rescue lists of a context (DeviceCtx::rescue)
+//   multipass: the passes of ONE chain share the device's multi-pass workspace (DeviceCtx::d_mp): a chain is issued under it, so that
+//             two host threads launching chains on the same stream cannot interleave their passes
 //   project:  one per projection slot (DeviceCtx::proj): the host-pointer projection entry points; never nested with the others
-// Order when nested: host -> dispatch -> lists.
+// Order when nested: host -> multipass -> dispatch -> lists.
 constexpr int kMaxDevices = 64;
-struct DeviceLocks { std::mutex host, dispatch, lists, project[DeviceCtx::kProjSlots]; std::atomic<unsigned> next_project{0}; };
+struct DeviceLocks { std::mutex host, multipass, dispatch, lists, project[DeviceCtx::kProjSlots]; std::atomic<unsigned> next_project{0}; };
 extern DeviceLocks g_locks[kMaxDevices];
 int current_device_slot();
 inline DeviceLocks& locks_here() { return g_locks[current_device_slot()]; }

@@ -176,6 +176,11 @@ int apply_v_sign(float* d_v, int64_t n, hipStream_t s) {
 }
 
 static int dispatch_kernels(const lspiv::PivParams& p, int dtype, bool ensemble, hipStream_t s) {
+  if (p.shifted) {   // multi-pass mode: the shifted per-pair kernels
+    if (ensemble) return fail(LSPIV_EUNSUPPORTED, "ensemble mode has no shifted kernels");
+    return launch_status(p.wy == 16 ? lspiv::launch_piv_shift16(p, dtype, s) : p.wy == 32 ? lspiv::launch_piv_shift32(p, dtype, s)
+                                                                                           : lspiv::launch_piv_shift64(p, dtype, s));
+  }
   if (p.nw) {   // search-area mode: per-pair kernels of the search area's transform size
     if (ensemble) return fail(LSPIV_EUNSUPPORTED, "ensemble mode has no search-area kernels");
     return launch_status(p.wy == 16 ? lspiv::launch_piv_search16(p, dtype, s) : p.wy == 32 ? lspiv::launch_piv_search32(p, dtype, s)
@@ -425,6 +430,196 @@ int lspiv_piv_search_pairs_dev_at(const void* d_frames, int dtype, int64_t T, in
                                   void* stream) {
   LSPIV_TRY(check_search(say, sax, wy, wx));
   return piv_pairs_dev(d_frames, dtype, T, H, W, say, sax, wy, oy, ox, signal_threshold, pair_offset, d_out, d_corr_planes, stream);
+}
+
+// ---- multi-pass PIV (include/lspiv.h) ---------------------------------------------------------------
+static bool shift_shape_ok(int wy, int wx) { return wy == wx && (wy == 16 || wy == 32 || wy == 64); }
+static int check_multipass_options() {
+  if (!g_opt_norm_clip.load())
+    return fail(LSPIV_EUNSUPPORTED, "option norm_clip = 0 is served by the block-per-window kernels only, not by multi-pass PIV");
+  if (g_opt_signal_mode.load() == 1)
+    return fail(LSPIV_EUNSUPPORTED, "option signal_mode = 1 scores a window position over a chunk; a shifted window has no position of its own: "
+                "not supported by multi-pass PIV");
+  return LSPIV_OK;
+}
+static int check_shift(int wy, int wx, int64_t H, int64_t W) {
+  if (!shift_shape_ok(wy, wx))
+    return fail(LSPIV_EUNSUPPORTED, "shifted pass with window %dx%d is not supported: the window must be square and one of {16, 32, 64}", wy, wx);
+  if (H > 32767 || W > 32767) return fail(LSPIV_EINVAL, "frame (%lld,%lld): a side above 32767 does not fit the int16 offsets", (long long)H, (long long)W);
+  return check_multipass_options();
+}
+
+// one shifted pass on stream s: kernel + rescue pass (both write the residual), then the clamped offset is added; v_sign is the caller's
+static int shift_pass(const void* d_frames, int dtype, int64_t T, int64_t H, int64_t W, int wy, int wx, int oy, int ox, float signal_threshold,
+                      int64_t pair_offset, const int16_t* d_shift, float* d_out, float* d_planes, hipStream_t s, lspiv::PivParams* out_p) {
+  Grid g;
+  LSPIV_TRY(make_grid(H, W, wy, wx, oy, ox, &g));
+  lspiv::PivParams p;
+  LSPIV_TRY(fill_params(&p, d_frames, dtype, T, H, W, wy, wx, oy, ox, signal_threshold, g));
+  p.pair_offset = pair_offset;
+  p.shifted = 1;
+  p.shift = d_shift;
+  p.u = d_out;
+  p.v = d_out + (size_t)p.n_tiles;
+  p.cmax = d_out + 2 * (size_t)p.n_tiles;
+  p.s2n = d_out + 3 * (size_t)p.n_tiles;
+  p.planes = d_planes;
+  LSPIV_TRY(dispatch(p, dtype, false, s));
+  LSPIV_TRY(launch_status(lspiv::launch_add_shift(p, s)));
+  if (out_p) *out_p = p;
+  return LSPIV_OK;
+}
+
+static int pass_grid(int64_t H, int64_t W, int wy, int wx, int oy, int ox, lspiv::PassGrid* pg) {
+  Grid g;
+  LSPIV_TRY(make_grid(H, W, wy, wx, oy, ox, &g));
+  if ((wy & 1) || (wx & 1)) return fail(LSPIV_EINVAL, "window %dx%d: the passes of a chain are even", wy, wx);
+  *pg = {wy, wx, wy - oy, wx - ox, (int)g.n_rows, (int)g.n_cols};
+  return LSPIV_OK;
+}
+
+// the clamped offsets of a pass, as the kernels used them: the predictor clamps what it stores, so its output IS the clamped array
+static int multipass_dev(DeviceCtx* c, const void* d_frames, int dtype, int64_t T, int64_t H, int64_t W, int n_passes, const int* passes,
+                         float signal_threshold, int64_t pair_offset, float* d_out, float* d_planes, int16_t* d_shift_out, hipStream_t s) {
+  if (!d_frames || !d_out || !passes) return fail(LSPIV_EINVAL, "d_frames / d_out / passes is NULL");
+  if (n_passes < 1 || n_passes > 8) return fail(LSPIV_EINVAL, "n_passes %d not in 1..8", n_passes);
+  if (pair_offset < 0) return fail(LSPIV_EINVAL, "pair_offset %lld is negative", (long long)pair_offset);
+  if (T < 2) return fail(LSPIV_ESHAPE, "need at least 2 frames, got %lld", (long long)T);
+  LSPIV_TRY(check_multipass_options());
+  if (H > 32767 || W > 32767) return fail(LSPIV_EINVAL, "frame (%lld,%lld): a side above 32767 does not fit the int16 offsets", (long long)H, (long long)W);
+  lspiv::PassGrid pg[8];
+  size_t max_tiles = 0;
+  for (int k = 0; k < n_passes; ++k) {
+    const int* q = passes + 4 * k;
+    if (q[0] != q[1]) return fail(LSPIV_EINVAL, "pass %d: window %dx%d is not square", k, q[0], q[1]);
+    if (k > 0 && !shift_shape_ok(q[0], q[1]))
+      return fail(LSPIV_EUNSUPPORTED, "pass %d: window %dx%d is not supported: the windows of passes after the first must be one of {16, 32, 64}", k, q[0], q[1]);
+    if (k > 0 && q[0] > passes[4 * (k - 1)]) return fail(LSPIV_EINVAL, "pass %d: window %d is larger than pass %d's %d", k, q[0], k - 1, passes[4 * (k - 1)]);
+    LSPIV_TRY(pass_grid(H, W, q[0], q[1], q[2], q[3], &pg[k]));
+    if (k + 1 < n_passes) max_tiles = std::max(max_tiles, (size_t)(T - 1) * pg[k].n_rows * pg[k].n_cols);
+  }
+  const int* last = passes + 4 * (n_passes - 1);
+  const size_t last_tiles = (size_t)(T - 1) * pg[n_passes - 1].n_rows * pg[n_passes - 1].n_cols;
+  if (n_passes == 1) {
+    if (d_shift_out) HIP_TRY(hipMemsetAsync(d_shift_out, 0, last_tiles * 2 * sizeof(int16_t), s));
+    return lspiv_piv_pairs_dev_at(d_frames, dtype, T, H, W, last[0], last[1], last[2], last[3], signal_threshold, pair_offset, d_out, d_planes, s);
+  }
+  // the passes of one chain are issued under one lock: they share the workspace below, and a second chain on the same stream must come
+  // after this one's last pass, not between two of them (chains on DIFFERENT streams of one device still share it: one stream at a time)
+  std::lock_guard<std::mutex> chain_lock(locks_here().multipass);
+  // workspace: two result blocks of the largest intermediate pass (ping-pong) and one offset array of the largest pass that takes one
+  size_t max_shift = 0;
+  for (int k = 1; k < n_passes; ++k) max_shift = std::max(max_shift, (size_t)(T - 1) * pg[k].n_rows * pg[k].n_cols);
+  const size_t blk = (4 * max_tiles * sizeof(float) + 255) & ~(size_t)255;
+  LSPIV_TRY(ensure(&c->d_mp, &c->mp_cap, 2 * blk + max_shift * 2 * sizeof(int16_t)));
+  float* res[2] = {reinterpret_cast<float*>(c->d_mp), reinterpret_cast<float*>((char*)c->d_mp + blk)};
+  int16_t* ws_shift = reinterpret_cast<int16_t*>((char*)c->d_mp + 2 * blk);
+  // pass 0: today's per-timestep path on its own grid, in the kernels' orientation (no v_sign before the end)
+  {
+    const int* q = passes;
+    Grid g;
+    LSPIV_TRY(make_grid(H, W, q[0], q[1], q[2], q[3], &g));
+    lspiv::PivParams p;
+    LSPIV_TRY(fill_params(&p, d_frames, dtype, T, H, W, q[0], q[1], q[2], q[3], signal_threshold, g));
+    p.pair_offset = pair_offset;
+    p.u = res[0]; p.v = res[0] + (size_t)p.n_tiles; p.cmax = res[0] + 2 * (size_t)p.n_tiles; p.s2n = res[0] + 3 * (size_t)p.n_tiles;
+    LSPIV_TRY(dispatch(p, dtype, false, s));
+  }
+  for (int k = 1; k < n_passes; ++k) {
+    const int* q = passes + 4 * k;
+    const bool final_pass = k == n_passes - 1;
+    const float* prev = res[(k - 1) & 1];
+    const size_t prev_tiles = (size_t)(T - 1) * pg[k - 1].n_rows * pg[k - 1].n_cols;
+    int16_t* shift = final_pass && d_shift_out ? d_shift_out : ws_shift;
+    LSPIV_TRY(launch_status(lspiv::launch_predict_shift(prev, prev + prev_tiles, (uint32_t)(T - 1), (int)H, (int)W, pg[k - 1], pg[k], shift, s)));
+    LSPIV_TRY(shift_pass(d_frames, dtype, T, H, W, q[0], q[1], q[2], q[3], signal_threshold, pair_offset, shift, final_pass ? d_out : res[k & 1],
+                         final_pass ? d_planes : nullptr, s, nullptr));
+  }
+  return apply_v_sign(d_out + last_tiles, (int64_t)last_tiles, s);
+}
+
+int lspiv_shift_supported(int wy, int wx) { return shift_shape_ok(wy, wx) ? 1 : 0; }
+
+int lspiv_piv_shift_pairs_dev_at(const void* d_frames, int dtype, int64_t T, int64_t H, int64_t W, int wy, int wx, int oy, int ox,
+                                 float signal_threshold, int64_t pair_offset, const int16_t* d_shift, float* d_out, float* d_corr_planes,
+                                 void* stream) {
+  if (!d_frames || !d_out) return fail(LSPIV_EINVAL, "d_frames / d_out is NULL");
+  if (pair_offset < 0) return fail(LSPIV_EINVAL, "pair_offset %lld is negative", (long long)pair_offset);
+  LSPIV_TRY(check_shift(wy, wx, H, W));
+  DeviceCtx* c;
+  LSPIV_TRY(get_ctx(&c));
+  hipStream_t s = on_stream(c, stream);
+  lspiv::PivParams p;
+  LSPIV_TRY(shift_pass(d_frames, dtype, T, H, W, wy, wx, oy, ox, signal_threshold, pair_offset, d_shift, d_out, d_corr_planes, s, &p));
+  return apply_v_sign(p.v, (int64_t)p.n_tiles, s);
+}
+
+int lspiv_piv_predict_shift_dev(const float* d_u, const float* d_v, int64_t n_pairs, int64_t H, int64_t W, int cwy, int cwx, int coy, int cox,
+                                int fwy, int fwx, int foy, int fox, int16_t* d_shift, void* stream) {
+  if (!d_u || !d_v || !d_shift) return fail(LSPIV_EINVAL, "NULL argument");
+  if (n_pairs < 0) return fail(LSPIV_EINVAL, "n_pairs %lld is negative", (long long)n_pairs);
+  if (H > 32767 || W > 32767) return fail(LSPIV_EINVAL, "frame (%lld,%lld): a side above 32767 does not fit the int16 offsets", (long long)H, (long long)W);
+  lspiv::PassGrid cg, fg;
+  LSPIV_TRY(pass_grid(H, W, cwy, cwx, coy, cox, &cg));
+  LSPIV_TRY(pass_grid(H, W, fwy, fwx, foy, fox, &fg));
+  if (n_pairs * (int64_t)fg.n_rows * fg.n_cols >= (int64_t)1 << 31 || n_pairs * (int64_t)cg.n_rows * cg.n_cols >= (int64_t)1 << 31)
+    return fail(LSPIV_EINVAL, "too many windows for one launch (limit 2^31)");
+  return launch_on(stream, [&](hipStream_t s) { return lspiv::launch_predict_shift(d_u, d_v, (uint32_t)n_pairs, (int)H, (int)W, cg, fg, d_shift, s); });
+}
+
+int lspiv_piv_multipass_dev_at(const void* d_frames, int dtype, int64_t T, int64_t H, int64_t W, int n_passes, const int* passes,
+                               float signal_threshold, int64_t pair_offset, float* d_out, float* d_corr_planes, int16_t* d_shift_out, void* stream) {
+  DeviceCtx* c;
+  LSPIV_TRY(get_ctx(&c));
+  return multipass_dev(c, d_frames, dtype, T, H, W, n_passes, passes, signal_threshold, pair_offset, d_out, d_corr_planes, d_shift_out,
+                       on_stream(c, stream));
+}
+
+int lspiv_piv_multipass_at(const void* frames, int dtype, int64_t T, int64_t H, int64_t W, int n_passes, const int* passes, float signal_threshold,
+                           int64_t pair_offset, float* u, float* v, float* corr_max, float* s2n, float* corr_planes, int16_t* shift_out) {
+  std::lock_guard<std::mutex> host_lock(locks_here().host);
+  if (!frames || !u || !v || !corr_max || !s2n || !passes) return fail(LSPIV_EINVAL, "NULL buffer");
+  if (n_passes < 1 || n_passes > 8) return fail(LSPIV_EINVAL, "n_passes %d not in 1..8", n_passes);
+  if (dtype < 0 || dtype > 2) return fail(LSPIV_EINVAL, "dtype %d not in {0:u8, 1:f32, 2:f64}", dtype);
+  if (T < 2) return fail(LSPIV_ESHAPE, "need at least 2 frames, got %lld", (long long)T);
+  const int* last = passes + 4 * (n_passes - 1);
+  Grid g;
+  LSPIV_TRY(make_grid(H, W, last[0], last[1], last[2], last[3], &g));
+  DeviceCtx* c;
+  LSPIV_TRY(get_ctx(&c));
+  const int dev_dtype = dtype == LSPIV_F64 ? LSPIV_F32 : dtype;   // float64 is narrowed while it is staged
+  const size_t frame_elems = (size_t)H * W, frame_bytes = frame_elems * elem_size(dev_dtype);
+  const size_t n_tiles = (size_t)(T - 1) * g.n_rows * g.n_cols;
+  const size_t out_bytes = 4 * n_tiles * sizeof(float), shift_bytes = shift_out ? n_tiles * 2 * sizeof(int16_t) : 0;
+  LSPIV_TRY(ensure(&c->d_frames, &c->frames_cap, (size_t)T * frame_bytes));
+  LSPIV_TRY(ensure(&c->d_out, &c->out_cap, ((out_bytes + 255) & ~(size_t)255) + shift_bytes));
+  int16_t* d_shift = shift_out ? reinterpret_cast<int16_t*>((char*)c->d_out + ((out_bytes + 255) & ~(size_t)255)) : nullptr;
+  if (corr_planes) LSPIV_TRY(ensure(&c->d_planes, &c->planes_cap, n_tiles * last[0] * last[1] * sizeof(float)));
+  // the whole chunk is staged first (the chain's later passes need every frame of a pair anyway), then the chain runs on it
+  LSPIV_TRY(stage_ring(c, frame_bytes));
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  const bool src_pinned = dtype != LSPIV_F64 && is_pinned(frames);
+  const int64_t fpb = std::max<int64_t>(1, (int64_t)(c->pinned_cap / frame_bytes));
+  int batch = 0;
+  for (int64_t f0 = 0; f0 < T; ++batch) {
+    const int64_t f1 = std::min<int64_t>(T, f0 + fpb);
+    LSPIV_TRY(stage_frames(c, batch, c->d_frames, frames, dtype, src_pinned, frame_elems, f0, f1, signal_threshold));
+    f0 = f1;
+  }
+  HIP_TRY(hipStreamSynchronize(c->copy_stream));
+  const int rc = multipass_dev(c, c->d_frames, dev_dtype, T, H, W, n_passes, passes, signal_threshold, pair_offset, c->d_out,
+                               corr_planes ? c->d_planes : nullptr, d_shift, c->stream);
+  if (rc != LSPIV_OK) { (void)hipStreamSynchronize(c->stream); return rc; }
+  const size_t ob = n_tiles * sizeof(float);
+  HIP_TRY(hipMemcpyAsync(u, c->d_out, ob, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(hipMemcpyAsync(v, c->d_out + n_tiles, ob, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(hipMemcpyAsync(corr_max, c->d_out + 2 * n_tiles, ob, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(hipMemcpyAsync(s2n, c->d_out + 3 * n_tiles, ob, hipMemcpyDeviceToHost, c->stream));
+  if (shift_out) HIP_TRY(hipMemcpyAsync(shift_out, d_shift, shift_bytes, hipMemcpyDeviceToHost, c->stream));
+  if (corr_planes)
+    HIP_TRY(hipMemcpyAsync(corr_planes, c->d_planes, n_tiles * last[0] * last[1] * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  return LSPIV_OK;
 }
 
 int lspiv_piv_pairs_dev(const void* d_frames, int dtype, int64_t T, int64_t H, int64_t W, int wy, int wx, int oy,

@@ -111,7 +111,28 @@ struct PivParams {
   FastDiv div_ncols;       // window index -> (row, col)
   FastDiv div_jobs;        // fft kernels: job index -> (pair, job in pair), divisor (n_win + 1) / 2
   FastDiv div_nwin;        // one-window-per-job kernels: job index -> (pair, window), divisor n_win
+  // multi-pass mode (piv_fft_impl.h, "shifted kernel"): shifted != 0 selects the shifted per-pair kernels; shift = nullptr (all
+  // zero) or n_tiles x {dy, dx}, the integer offset of result g's window of frame t+1 from its window of frame t.  The kernels
+  // and the rescue pass clamp it to the frame (window_shift) and write the RESIDUAL displacement; launch_add_shift adds the
+  // clamped offset afterwards
+  int shifted;
+  const int16_t* shift;
 };
+
+// The offset of result g = pair * n_win + window (grid row wrow, column wcol), clamped so that the shifted window stays inside
+// the frame: dy in [-y0, H - wy - y0], dx in [-x0, W - wx - x0].  The ONE place the clamp lives: the shifted kernels, the rescue
+// kernels and the add step all call it, so what is read, what is re-evaluated and what is added cannot differ -- and no offset
+// array can make a kernel read outside the stack.
+struct WinShift { int dy, dx; };
+__device__ __forceinline__ WinShift window_shift(const PivParams& p, uint32_t g, uint32_t wrow, uint32_t wcol) {
+  WinShift s = {0, 0};
+  if (p.shift) {
+    const int y0 = (int)wrow * p.sy, x0 = (int)wcol * p.sx;
+    s.dy = min(max((int)p.shift[2 * (size_t)g], -y0), p.H - p.wy - y0);
+    s.dx = min(max((int)p.shift[2 * (size_t)g + 1], -x0), p.W - p.wx - x0);
+  }
+  return s;
+}
 
 // ---- float64 rescue of the ENSEMBLE's final fit (piv_rescue.hip) ---------------------------------
 // lspiv_ensemble_finish fits the MEAN plane; where that float32 fit is ill-conditioned (same flag model as above) the five
@@ -407,6 +428,17 @@ hipError_t launch_piv_embed64(const PivParams& p, int dtype, bool ensemble, hipS
 hipError_t launch_piv_search16(const PivParams& p, int dtype, hipStream_t s);
 hipError_t launch_piv_search32(const PivParams& p, int dtype, hipStream_t s);
 hipError_t launch_piv_search64(const PivParams& p, int dtype, hipStream_t s);
+// multi-pass mode: an n x n window of frame t against the n x n window of frame t+1 at a per-window integer offset (p.shift), n = p.wy
+// = p.wx = 16 / 32 / 64 (per-timestep mode only); u, v are the residual
+hipError_t launch_piv_shift16(const PivParams& p, int dtype, hipStream_t s);
+hipError_t launch_piv_shift32(const PivParams& p, int dtype, hipStream_t s);
+hipError_t launch_piv_shift64(const PivParams& p, int dtype, hipStream_t s);
+// u[g] += clamped dx, v[g] += clamped dy of p.shift (float32 sums; a NaN residual stays NaN): after the rescue pass (piv_multipass.hip)
+hipError_t launch_add_shift(const PivParams& p, hipStream_t s);
+// window grid of one pass of a chain, and the predictor between two passes (piv_multipass.hip)
+struct PassGrid { int wy, wx, sy, sx, n_rows, n_cols; };   // window, strides, grid
+hipError_t launch_predict_shift(const float* u, const float* v, uint32_t n_pairs, int H, int W, const PassGrid& coarse, const PassGrid& fine,
+                                int16_t* shift, hipStream_t s);
 // float64 re-evaluation of the windows the PIV kernel of this pass appended to p.rescue_* (piv_rescue.hip)
 hipError_t launch_piv_rescue(const PivParams& p, int dtype, hipStream_t s);
 // ensemble mode: flag the windows of the float32 mean planes (u, v = their float32 fits) whose fit cannot be trusted; partial

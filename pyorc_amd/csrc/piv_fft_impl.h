@@ -358,13 +358,16 @@ __device__ __forceinline__ void prepare_pair(const RowRaw<uint8_t, N>& ra, const
   center_u8<N>(rb, sb.mean, rho, xi);  // the balance factor rides on the conversion
   skip = want_nz && below_threshold<N>(nza, nzb, thr);
 }
-template <typename T, int N>
+// SEQ: one window after the other (the shifted kernel: the two rows of 64 float64 samples in flight together do not fit 256 VGPRs
+// next to the signal score)
+template <typename T, int N, bool SEQ = false>
 __device__ __forceinline__ void prepare_pair(const RowRaw<T, N>& ra, const RowRaw<T, N>& rb, float (&xr)[N],
                                              float (&xi)[N], bool want_nz, float thr, bool nz_pos, float& scale,
                                              float& hi, bool& skip) {
   bool finite = true;
   int nza = Geo<N>::NN, nzb = Geo<N>::NN;
   const float inv_a = load_center<N>(ra, xr, want_nz, nz_pos, nza, finite);
+  if constexpr (SEQ) __builtin_amdgcn_sched_barrier(0);
   const float inv_b = load_center<N>(rb, xi, want_nz, nz_pos, nzb, finite);
   float rho;
   finish_pair<N>(inv_a, inv_b, rho, scale, hi);
@@ -813,7 +816,8 @@ __device__ __forceinline__ void cross_spectrum_half(int partner_byte, const floa
 // Everything between "two window pairs" and "two clipped correlation planes in registers".
 // On return xr = plane of tile 0, xi = plane of tile 1, natural (un-shifted) order: lane = row y,
 // register = column x;  skip[k] = plane k is NaN (signal pre-mask / non-finite input).
-template <typename T, int N, bool WANT_NZ, bool EMBED = false, bool SEARCH = false>
+// SHIFT (multi-pass mode): the plain pair, but frame t+1's window sits at the window's own clamped offset (window_shift), ONE window per job
+template <typename T, int N, bool WANT_NZ, bool EMBED = false, bool SEARCH = false, bool SHIFT = false>
 __device__ __forceinline__ void correlate_job(const PivParams& p, const TileRef (&t)[2], float* buf, int lg,
                                               int partner_byte, float (&xr)[N], float (&xi)[N], bool (&skip)[2],
                                               float (&mean)[2]) {
@@ -828,17 +832,22 @@ __device__ __forceinline__ void correlate_job(const PivParams& p, const TileRef 
     const uint32_t wrow = p.div_ncols.div(t[k].win);
     const uint32_t wcol = t[k].win - wrow * (uint32_t)p.n_cols;
     const int64_t off = ((int64_t)t[k].pair * p.H + (int64_t)(wrow * p.sy + row_of<N>(lg))) * p.W + (int64_t)wcol * p.sx;
+    int64_t offb = off + p.frame_elems;
+    if constexpr (SHIFT) {   // the only new work of the shifted kernel: the address of frame t+1's rows
+      const WinShift ws = window_shift(p, t[k].pair * p.n_win + t[k].win, wrow, wcol);
+      offb += (int64_t)ws.dy * p.W + ws.dx;
+    }
     raw[k][0].fetch(frames + off);
-    raw[k][1].fetch(frames + off + p.frame_elems);
+    raw[k][1].fetch(frames + offb);
   };
   // uint8 rows (8 VGPRs each) are all fetched up front; wider samples are addressed only when their window's turn
   // comes -- four live 64-bit row pointers were exactly the 8 VGPRs that kept the float kernel above 128
-  if constexpr (sizeof(T) == 1 && !EMBED && !SEARCH) { fetch_rows(0); fetch_rows(1); }
+  if constexpr (sizeof(T) == 1 && !EMBED && !SEARCH) { fetch_rows(0); if constexpr (!SHIFT) fetch_rows(1); }
   // 64-point embedding: ONE window per job.  Holding window 0's half spectrum (66 VGPRs) through window 1's scalar
   // loads and masked statistics does not fit 256 VGPRs (200-900 B/lane of scratch, and slower than doing without the
   // shared inverse), so the second slot of the inverse transform stays empty there: 2 instead of 1.5 transforms per
   // window, no spills.
-  constexpr bool SINGLE = (EMBED && N == 64) || (SEARCH && kSearchSingle<N>);
+  constexpr bool SINGLE = (EMBED && N == 64) || (SEARCH && kSearchSingle<N>) || SHIFT;
 #pragma unroll
   for (int k = 0; k < 2; ++k) {
     // keep the two windows' register-hungry phases apart: the scheduler otherwise interleaves window 1's
@@ -865,7 +874,10 @@ __device__ __forceinline__ void correlate_job(const PivParams& p, const TileRef 
       prepare_pair_search<T, N, WANT_NZ>(p, t[k], lg, xr, xi, scale, hi[k], skip[k]);
     } else {
       if constexpr (sizeof(T) != 1) fetch_rows(k);
-      prepare_pair(raw[k][0], raw[k][1], xr, xi, want_nz, p.signal_threshold, p.nz_positive != 0, scale, hi[k], skip[k]);
+      if constexpr (SHIFT && sizeof(T) != 1)
+        prepare_pair<T, N, true>(raw[k][0], raw[k][1], xr, xi, want_nz, p.signal_threshold, p.nz_positive != 0, scale, hi[k], skip[k]);
+      else
+        prepare_pair(raw[k][0], raw[k][1], xr, xi, want_nz, p.signal_threshold, p.nz_positive != 0, scale, hi[k], skip[k]);
       scale *= p.std_gain2;   // 1, or (n - 1) / n under the "std_ddof" option
       if (WANT_NZ && p.win_keep) skip[k] = skip[k] || !p.win_keep[t[k].win];   // "stack" mode (A7)
     }
@@ -2110,6 +2122,85 @@ static hipError_t launch_search(const PivParams& p, int dtype, hipStream_t s) {
     case 0: return nz ? launch_search_t<uint8_t, N, true>(p, s) : launch_search_t<uint8_t, N, false>(p, s);
     case 1: return nz ? launch_search_t<float, N, true>(p, s) : launch_search_t<float, N, false>(p, s);
     case 2: return nz ? launch_search_t<double, N, true>(p, s) : launch_search_t<double, N, false>(p, s);
+    default: return hipErrorInvalidValue;
+  }
+}
+
+// ---- shifted kernel (multi-pass mode): per pair, no walking -- every window of frame t+1 sits at an offset of
+// its own, so no spectrum can be carried from pair to pair; piv_fft_kernel's job layout and full-plane epilogue ---------------------
+// The full N x N window of frame t against the full N x N window of frame t+1 at (y0 + dy, x0 + dx): against piv_fft_kernel the only new
+// work is that address (correlate_job, SHIFT).  u, v are the RESIDUAL; launch_add_shift adds the clamped offset after the rescue pass.
+// ONE window per job, for the reason given at kSearchSingle: a window's result has to be a function of its own samples and its own
+// offset alone (the chain's predictor reads rint(u), and a test moves one window's offset and compares every other window's bits), and
+// two windows in one complex float32 inverse round each other's samples into their own.  The uint8 row prefetch stays (both rows of the
+// one window, 2 N / 4 VGPRs, before any arithmetic).
+// registers (ROCm 7.2, no scratch in any variant; uint8 | float32 | float64, over the four variants with / without signal score and planes):
+// 16-point 52 - 55 | 57 - 69 | 61 - 74 VGPRs, 32-point 92 - 93 | 96 - 100 | 110 - 112, 64-point 184 - 186 | 184 - 206 | 201 - 208: inside the
+// bounds of piv_fft_kernel (kWavesPerSimd) at every size.  Float rows are loaded one window after the other (prepare_pair, SEQ): both rows
+// of 64 float64 samples in flight next to the signal score took 256 VGPRs and 32 - 40 bytes of scratch
+template <typename T, int N, bool PLANES, bool WANT_NZ>
+__global__ __launch_bounds__(BLOCK, (kWavesPerSimd<T, N>)) void piv_fft_shift_kernel(PivParams p) {
+  extern __shared__ __attribute__((aligned(16))) float smem[];
+  using G = Geo<N>;
+  const int lane = threadIdx.x & 63;
+  const int wave = threadIdx.x >> 6;
+  const int grp = lane / G::LG;
+  const int lg = lane & (G::LG - 1);
+  float* buf = smem + (wave * G::GROUPS + grp) * G::LDS_JOB;
+  const int partner_byte = partner_byte_of<N>(lane, lg);
+  const uint32_t nb = gridDim.x;                                   // XCD-aware block order, as piv_fft_kernel
+  const uint32_t q = nb >> 3, r = nb & 7u;
+  const uint32_t xcd = blockIdx.x & 7u, slot = blockIdx.x >> 3;
+  const uint32_t blk = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + slot;
+  // a job is ONE window of one pair; jobs past the end recompute the last job and store nothing
+  uint32_t job = (blk * WAVES_PER_BLOCK + wave) * G::GROUPS + grp;
+  const bool job_valid = job < p.n_tiles;
+  job = job_valid ? job : p.n_tiles - 1;
+  const uint32_t pair = p.div_nwin.div(job);
+  TileRef t[2];
+  t[0].pair = t[1].pair = pair;
+  t[0].win = t[1].win = job - pair * p.n_win;
+  t[0].valid = job_valid;
+  t[1].valid = false;
+
+  float xr[N], xi[N], mean[2];
+  bool skip[2];
+  correlate_job<T, N, WANT_NZ, false, false, true>(p, t, buf, lg, partner_byte, xr, xi, skip, mean);
+
+  float row_max, u, v;
+  const uint32_t g = job;
+  const float vmax = plane_max<N>(xr, row_max);
+  find_peak<N>(buf, lg, xr, vmax, row_max, p, u, v, p.rescue_hdr && job_valid && !skip[0], g);
+  float cm = vmax, sn = vmax * __builtin_amdgcn_rcpf(mean[0]);
+  if (skip[0]) u = v = cm = sn = __builtin_nanf("");
+  if (job_valid && lg == 0) {
+    p.u[g] = u; p.v[g] = v; p.cmax[g] = cm; p.s2n[g] = sn;
+  }
+  if constexpr (PLANES) {
+    if (job_valid) store_plane_rows<N>(p.planes + (size_t)g * G::NN, lg, xr, skip[0]);
+  }
+}
+
+template <typename T, int N, bool WANT_NZ>
+static hipError_t launch_shift_t(const PivParams& p, hipStream_t s) {
+  using G = Geo<N>;
+  constexpr uint32_t jobs_per_block = WAVES_PER_BLOCK * G::GROUPS;
+  const uint32_t blocks = (p.n_tiles + jobs_per_block - 1) / jobs_per_block;
+  if (p.planes)
+    hipLaunchKernelGGL((piv_fft_shift_kernel<T, N, true, WANT_NZ>), dim3(blocks), dim3(BLOCK), G::LDS_BYTES, s, p);
+  else
+    hipLaunchKernelGGL((piv_fft_shift_kernel<T, N, false, WANT_NZ>), dim3(blocks), dim3(BLOCK), G::LDS_BYTES, s, p);
+  return hipGetLastError();
+}
+template <int N>
+static hipError_t launch_shift(const PivParams& p, int dtype, hipStream_t s) {
+  static_assert(Geo<N>::FULL && N % 16 == 0, "shifted passes are 16, 32 or 64 px");
+  if (p.wy != N || p.wx != N || p.nw != 0 || p.n_tiles == 0 || p.H < N || p.W < N) return hipErrorInvalidValue;
+  const bool nz = p.signal_threshold >= 0.0f;
+  switch (dtype) {
+    case 0: return nz ? launch_shift_t<uint8_t, N, true>(p, s) : launch_shift_t<uint8_t, N, false>(p, s);
+    case 1: return nz ? launch_shift_t<float, N, true>(p, s) : launch_shift_t<float, N, false>(p, s);
+    case 2: return nz ? launch_shift_t<double, N, true>(p, s) : launch_shift_t<double, N, false>(p, s);
     default: return hipErrorInvalidValue;
   }
 }

@@ -1,0 +1,145 @@
+// Multi-pass PIV (gfx950): what runs BETWEEN the passes of a chain.
+//
+// A coarse pass predicts the displacement; the next, finer pass cuts its window of frame t+1 at an integer offset from that
+// prediction (the shifted kernels, piv_fft_impl.h) and measures the residual.  Two small kernels, both one thread per (pair, window):
+//   predict_shift_kernel   (u, v) of pass k on its grid -> int16 offsets (dy, dx) on the grid of pass k + 1.  After the first step
+//                          (rint of every vector) it is exact integer arithmetic, so that a float64 reference on the host gives the
+//                          very same integers: median of the rounded vectors over the 3 x 3 neighbourhood, bilinear interpolation
+//                          between the coarse window centres with integer weights, one rounding division, the frame clamp.
+//   add_shift_kernel       u += clamped dx, v += clamped dy after the rescue pass: the kernels and the rescue pass write the residual.
+// All of it in the kernels' native orientation (u = column shift, v = row shift, rows downward); the "v_sign" option is applied to
+// the final result only.
+#include <climits>
+
+#include "common.h"
+
+namespace lspiv {
+
+namespace {
+
+constexpr int MBLOCK = 256;
+
+__device__ __forceinline__ int64_t floor_div(int64_t a, int64_t b) {   // b > 0
+  const int64_t q = a / b;
+  return (a % b != 0 && a < 0) ? q - 1 : q;
+}
+
+// per axis: the coarse interval [i0, i0 + 1] a fine centre falls into and its integer weights (w0, w1), w0 + w1 = s; constant
+// extrapolation outside the outermost coarse centres; a one-entry axis has i0 = 0, w1 = 0
+struct AxisW { int i0, i1, w0, w1; };
+__device__ __forceinline__ AxisW axis_weights(int cf, int half_c, int s, int count) {
+  AxisW a;
+  const int d = cf - half_c;                                   // cf - cc[0]
+  int i0 = d >= 0 ? d / s : -((-d + s - 1) / s);               // floor
+  i0 = min(max(i0, 0), max(count - 2, 0));
+  a.i0 = i0;
+  a.i1 = min(i0 + 1, count - 1);
+  a.w1 = count > 1 ? min(max(cf - (i0 * s + half_c), 0), s) : 0;
+  a.w0 = s - a.w1;
+  return a;
+}
+
+// finite: the exponent field is not all ones (on the bits: no floating-point compare a fast-math flag could fold)
+__device__ __forceinline__ bool is_finite(float x) { return (__builtin_bit_cast(uint32_t, x) & 0x7f800000u) != 0x7f800000u; }
+// q = rint (half to even, in float32) clamped to the range of the int16 offsets, [-32768, 32767]: a frame side is at most 32767, so no
+// displacement a frame can hold is touched, the conversion to int is defined for every finite input, and sums of two q cannot overflow
+__device__ __forceinline__ int round_q(float x) { return (int)fminf(fmaxf(rintf(x), -32768.0f), 32767.0f); }
+
+// twice the median of the rounded vectors over the valid ones of the 3 x 3 neighbourhood of coarse window (r, c), clipped at the
+// grid's edges, centre included: odd count 2 * middle, even count the sum of the two middle values, none 0.  The nine values of a
+// component live in registers: an odd-even transposition sort with constant indices, invalid entries sorted to the end.
+__device__ __forceinline__ void median2(const float* u, const float* v, int n_rows, int n_cols, int r, int c, int& mu, int& mv) {
+  int qu[9], qv[9];
+  int k = 0;
+#pragma unroll
+  for (int e = 0; e < 9; ++e) {
+    const int rr = r + e / 3 - 1, cc = c + e % 3 - 1;
+    const bool in = (unsigned)rr < (unsigned)n_rows && (unsigned)cc < (unsigned)n_cols;
+    const size_t i = (size_t)(in ? rr : r) * n_cols + (in ? cc : c);
+    const float fu = u[i], fv = v[i];
+    const bool ok = in && is_finite(fu) && is_finite(fv);
+    qu[e] = ok ? round_q(fu) : INT_MAX;       // (INT_MAX, the invalid entries' sort key, is outside the range of q)
+    qv[e] = ok ? round_q(fv) : INT_MAX;
+    k += ok ? 1 : 0;
+  }
+#pragma unroll
+  for (int round = 0; round < 9; ++round) {
+#pragma unroll
+    for (int i = round & 1; i + 1 < 9; i += 2) {
+      const int a = qu[i], b = qu[i + 1];
+      qu[i] = min(a, b); qu[i + 1] = max(a, b);
+      const int a2 = qv[i], b2 = qv[i + 1];
+      qv[i] = min(a2, b2); qv[i + 1] = max(a2, b2);
+    }
+  }
+  const int lo = (k - 1) >> 1, hi = k >> 1;   // the same entry for an odd count
+  int ul = 0, uh = 0, vl = 0, vh = 0;
+#pragma unroll
+  for (int i = 0; i < 9; ++i) {
+    ul = i == lo ? qu[i] : ul; uh = i == hi ? qu[i] : uh;
+    vl = i == lo ? qv[i] : vl; vh = i == hi ? qv[i] : vh;
+  }
+  mu = k > 0 ? ul + uh : 0;
+  mv = k > 0 ? vl + vh : 0;
+}
+
+__global__ __launch_bounds__(MBLOCK) void predict_shift_kernel(const float* u, const float* v, uint32_t n_pairs, int H, int W, PassGrid cg,
+                                                               PassGrid fg, int16_t* shift) {
+  const uint32_t n_fine = (uint32_t)fg.n_rows * (uint32_t)fg.n_cols;
+  const uint64_t g = (uint64_t)blockIdx.x * MBLOCK + threadIdx.x;
+  if (g >= (uint64_t)n_pairs * n_fine) return;
+  const uint32_t pair = (uint32_t)(g / n_fine), win = (uint32_t)(g - (uint64_t)pair * n_fine);
+  const int r = (int)(win / (uint32_t)fg.n_cols), c = (int)(win - (uint32_t)r * (uint32_t)fg.n_cols);
+  const int y0 = r * fg.sy, x0 = c * fg.sx;
+  const AxisW ay = axis_weights(y0 + fg.wy / 2, cg.wy / 2, cg.sy, cg.n_rows);
+  const AxisW ax = axis_weights(x0 + fg.wx / 2, cg.wx / 2, cg.sx, cg.n_cols);
+  const size_t base = (size_t)pair * cg.n_rows * cg.n_cols;
+  const float* pu = u + base;
+  const float* pv = v + base;
+  int64_t num_u = 0, num_v = 0;
+#pragma unroll
+  for (int e = 0; e < 4; ++e) {
+    const int iy = e & 2 ? ay.i1 : ay.i0, ix = e & 1 ? ax.i1 : ax.i0;
+    const int64_t w = (int64_t)(e & 2 ? ay.w1 : ay.w0) * (int64_t)(e & 1 ? ax.w1 : ax.w0);
+    int mu = 0, mv = 0;
+    if (w != 0) median2(pu, pv, cg.n_rows, cg.n_cols, iy, ix, mu, mv);
+    num_u += w * mu;
+    num_v += w * mv;
+  }
+  const int64_t den = 2 * (int64_t)cg.sy * (int64_t)cg.sx;           // the medians carry a factor 2
+  const int64_t dx = floor_div(2 * num_u + den, 2 * den);           // round half up
+  const int64_t dy = floor_div(2 * num_v + den, 2 * den);
+  const int64_t cy = min(max(dy, (int64_t)-y0), (int64_t)(H - fg.wy - y0));   // the frame clamp of window_shift
+  const int64_t cx = min(max(dx, (int64_t)-x0), (int64_t)(W - fg.wx - x0));
+  shift[2 * g] = (int16_t)cy;
+  shift[2 * g + 1] = (int16_t)cx;
+}
+
+__global__ __launch_bounds__(MBLOCK) void add_shift_kernel(PivParams p) {
+  const uint32_t g = blockIdx.x * MBLOCK + threadIdx.x;
+  if (g >= p.n_tiles) return;
+  const uint32_t pair = p.div_nwin.div(g), win = g - pair * p.n_win;
+  const uint32_t wrow = p.div_ncols.div(win), wcol = win - wrow * (uint32_t)p.n_cols;
+  const WinShift ws = window_shift(p, g, wrow, wcol);
+  if (ws.dx != 0) p.u[g] = p.u[g] + (float)ws.dx;   // (a zero offset leaves the residual's bits, the sign of a zero included)
+  if (ws.dy != 0) p.v[g] = p.v[g] + (float)ws.dy;
+}
+
+}  // namespace
+
+hipError_t launch_predict_shift(const float* u, const float* v, uint32_t n_pairs, int H, int W, const PassGrid& coarse, const PassGrid& fine,
+                                int16_t* shift, hipStream_t s) {
+  const uint64_t n = (uint64_t)n_pairs * (uint64_t)fine.n_rows * (uint64_t)fine.n_cols;
+  if (n == 0) return hipSuccess;
+  if (n >= (uint64_t)1 << 31) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(predict_shift_kernel, dim3((uint32_t)((n + MBLOCK - 1) / MBLOCK)), dim3(MBLOCK), 0, s, u, v, n_pairs, H, W, coarse, fine, shift);
+  return hipGetLastError();
+}
+
+hipError_t launch_add_shift(const PivParams& p, hipStream_t s) {
+  if (!p.shift || p.n_tiles == 0) return hipSuccess;   // all-zero offsets: nothing to add
+  hipLaunchKernelGGL(add_shift_kernel, dim3((p.n_tiles + MBLOCK - 1) / MBLOCK), dim3(MBLOCK), 0, s, p);
+  return hipGetLastError();
+}
+
+}  // namespace lspiv

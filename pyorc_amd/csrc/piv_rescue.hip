@@ -240,6 +240,20 @@ __device__ __forceinline__ const T* window_base(const PivParams& p, uint32_t g) 
   return static_cast<const T*>(p.frames) + ((int64_t)pair * p.H + (int64_t)wrow * p.sy) * p.W + (int64_t)wcol * p.sx;
 }
 
+// the window of frame t+1 of result g: one frame on, and -- multi-pass mode -- at the window's clamped offset (common.h, window_shift).
+// (The ensemble's partial sums below keep A + frame_elems: ensemble mode has no shifted pass.)
+template <typename T>
+__device__ __forceinline__ const T* window_base_b(const PivParams& p, uint32_t g, const T* A) {
+  const T* B = A + p.frame_elems;
+  if (p.shift) {
+    const uint32_t pair = g / p.n_win, win = g - pair * p.n_win;
+    const uint32_t wrow = win / (uint32_t)p.n_cols, wcol = win - wrow * (uint32_t)p.n_cols;
+    const WinShift ws = window_shift(p, g, wrow, wcol);
+    B += (int64_t)ws.dy * p.W + ws.dx;
+  }
+  return B;
+}
+
 // first arg-max merge in shifted row-major order: larger value wins, equal values -> smaller index
 __device__ __forceinline__ void amax_merge_d(double& v, int& idx, double pv, int pidx) {
   const bool take = (pv > v) || (pv == v && pidx < idx);
@@ -273,7 +287,7 @@ __global__ __launch_bounds__(RBLOCK) void piv_rescue_fit_kernel(PivParams p) {
     const uint32_t g = rec.x;
     if (g >= p.n_tiles) continue;   // a record of another launch (two host threads interleaving on one stream): never write out of bounds
     const T* A = window_base<T>(p, g);
-    const T* B = A + p.frame_elems;
+    const T* B = window_base_b<T>(p, g, A);
     double mean_a, sd_a, mean_b, sd_b;
     if (staged) pair_stats_wave<T, true>(p, A, B, lane, mean_a, sd_a, mean_b, sd_b, la, lb);
     else pair_stats_wave<T, false>(p, A, B, lane, mean_a, sd_a, mean_b, sd_b);
@@ -322,7 +336,7 @@ __global__ __launch_bounds__(RBLOCK) void piv_rescue_amb_kernel(PivParams p) {
     const uint32_t g = min(p.rescue_amb[i], p.n_tiles - 1);   // (clamped, not skipped: the barriers below stay uniform)
     const bool g_ok = p.rescue_amb[i] < p.n_tiles;
     const T* A = window_base<T>(p, g);
-    const T* B = A + p.frame_elems;
+    const T* B = window_base_b<T>(p, g, A);
     double mean_a, sd_a, mean_b, sd_b;
     pair_stats_wave<T>(p, A, B, lane, mean_a, sd_a, mean_b, sd_b);   // every wave computes the same totals
     const bool dead = sd_a == 0.0 || sd_b == 0.0;   // never listed; kept out of the control flow around the barriers below

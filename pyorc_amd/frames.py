@@ -60,7 +60,7 @@ def get_piv_coords(dim_size, window_size, search_area_size, overlap, x=None, y=N
 
 
 def get_piv(frames, window_size=None, overlap=None, engine: str = "hip", ensemble_corr: bool = False,
-            time=None, resolution: Optional[float] = None, search_area_size=None, **kwargs):
+            time=None, resolution: Optional[float] = None, search_area_size=None, coarse_passes=None, **kwargs):
     """PIV on projected frames with the MI355X engine; parameters of ``Frames.get_piv`` (frames.py:114-121).
 
     Extra keywords for plain arrays: ``time`` (T,) seconds (default ``arange(T)``), ``resolution`` metres per
@@ -68,6 +68,8 @@ def get_piv(frames, window_size=None, overlap=None, engine: str = "hip", ensembl
     ``memory_factor``, ``corr_min``, ``s2n_min``, ``count_min``, ``signal_threshold``).  ``search_area_size``: None (the window size,
     as in the reference) or a larger square search area of 16, 32 or 64 px ("Extended search area").
     ``ensemble_window`` / ``ensemble_stride`` (in ``**kwargs``, with ``ensemble_corr=True``): a sliding ensemble, INTEGRATION.md 2c.
+    ``coarse_passes``: multi-pass PIV -- coarse passes run before ``window_size``, coarsest first, each an int n
+    (n x n at overlap n / 2) or a pair ``(n, overlap)``; the result stays on the grid of ``window_size`` / ``overlap``.
     """
     if engine not in ENGINES:
         raise ValueError(f"Selected PIV engine {engine} does not exist.")
@@ -98,6 +100,7 @@ def get_piv(frames, window_size=None, overlap=None, engine: str = "hip", ensembl
     coords, _ = get_piv_coords(tuple(frames[0].shape), ws, sa, ov, xs, ys)
     ds = velocimetry.get_ffpiv(frames, coords["y"], coords["x"], dt, engine=engine, ensemble_corr=ensemble_corr,
                                search_area_size=sa, window_size=ws, overlap=ov, res_x=res, res_y=res,
+                               **({"coarse_passes": coarse_passes} if coarse_passes is not None and len(coarse_passes) else {}),
                                **({} if is_xr else {"time": t}), **kwargs)
     if is_xr and camera_config is not None:
         # the tail of the reference accessor (frames.py:190-196): 2-D coordinates, attributes, encoding

@@ -51,6 +51,10 @@ def piv_pairs(imgs, window_size=(32, 32), overlap=(16, 16), signal_threshold: Op
     square window of frame t is searched in frame t+1 ("Extended search area"): the grid, ``overlap`` and the planes
     (``say x sax`` each) are then those of the search area.  ``window_size`` may also be a ``window.SearchWindow``.
     """
+    if isinstance(window_size, window.MultiPassWindow):   # a chain of passes (INTEGRATION.md section 2d): the final grid is this call's
+        if search_area_size is not None and tuple(int(q) for q in search_area_size) != tuple(window_size):
+            raise NotImplementedError("coarse_passes together with a search_area_size larger than the window is not implemented")
+        return piv_multipass(imgs, window_size, signal_threshold, return_planes, pair_offset, out=out, scale=scale)
     window_size = window.search_spec(window_size, search_area_size)
     search = isinstance(window_size, window.SearchWindow)
     lib = _lib.load()
@@ -62,10 +66,7 @@ def piv_pairs(imgs, window_size=(32, 32), overlap=(16, 16), signal_threshold: Op
         raise ValueError(f"need >= 2 frames at least one window large, got {a.shape} for window {window_size}")
     P = T - 1
     if out is not None:
-        out = list(out)
-        if len(out) != 4 or any(not isinstance(o, np.ndarray) or o.dtype != np.float32 or o.shape != (P, n_rows, n_cols) or
-                                not o.flags.c_contiguous or not o.flags.writeable for o in out):
-            raise ValueError(f"out must be four writable C-contiguous float32 arrays of shape {(P, n_rows, n_cols)}")
+        out = _check_out(out, (P, n_rows, n_cols))
     dt = None
     if scale is not None:
         if return_planes:
@@ -129,16 +130,202 @@ def _piv_pairs_device(a, window_size, overlap, signal_threshold, return_planes, 
                                               d_planes.c_ptr if d_planes is not None else None, None))
     if scale is not None:  # px / frame -> m / s in place on the [u | v] blocks (lspiv_scale_velocity_dev: the same kernel as the host entry point's)
         _lib.check(lib.lspiv_scale_velocity_dev(d_out.c_ptr, P, n_win, scale[0], scale[1], _lib.ptr(scale[2]), None))
-    if out is not None:    # straight into the caller's arrays: [u | v | corr | s2n] are four consecutive (P, n_win) blocks
-        for k in range(4):
-            _lib.check(lib.lspiv_memcpy_d2h(_lib.ptr(out[k]), C.c_void_p(d_out.ptr + k * P * n_win * 4), out[k].nbytes))
-        out = tuple(out)
-    else:
-        res = d_out.to_host().reshape(4, P, n_rows, n_cols)     # lspiv_memcpy_d2h runs on, and waits for, the library's stream
-        out = tuple(np.ascontiguousarray(res[k]) for k in range(4))
+    out = _results_to_host(d_out, P, n_rows, n_cols, out)
     if return_planes:
         return (*out, d_planes.to_host().reshape(P, n_win, window_size[0], window_size[1]))
     return out
+
+
+# ---- multi-pass PIV ---------------------------------------------------------------------------------------
+def _device_stack(imgs, signal_threshold):
+    """``imgs`` as a stack in HBM: a ``DeviceFrames`` as it is, a host stack the way the PIV host entry points bring it in (float64
+    narrowed to float32 while it is staged)."""
+    from .device import DeviceFrames
+
+    if is_device(imgs):
+        return imgs
+    a = _lib.as_frames(imgs)
+    d = DeviceFrames.empty(a.shape, DeviceFrames.device_dtype(a.dtype))
+    d.upload(0, a, signal_threshold)
+    return d
+
+
+def _check_out(out, shape):
+    out = list(out)
+    if len(out) != 4 or any(not isinstance(o, np.ndarray) or o.dtype != np.float32 or o.shape != shape or
+                            not o.flags.c_contiguous or not o.flags.writeable for o in out):
+        raise ValueError(f"out must be four writable C-contiguous float32 arrays of shape {shape}")
+    return out
+
+
+def _results_to_host(d_out, P, n_rows, n_cols, out=None):
+    """The [u | v | corr | s2n] block of a launch, four consecutive (P, n_win) blocks in HBM, as four host arrays: straight into the
+    caller's ``out`` arrays, or new ones."""
+    lib = _lib.load()
+    n_win = n_rows * n_cols
+    if out is not None:
+        for k in range(4):
+            _lib.check(lib.lspiv_memcpy_d2h(_lib.ptr(out[k]), C.c_void_p(d_out.ptr + k * P * n_win * 4), out[k].nbytes))
+        return tuple(out)
+    res = d_out.to_host().reshape(4, P, n_rows, n_cols)     # lspiv_memcpy_d2h runs on, and waits for, the library's stream
+    return tuple(np.ascontiguousarray(res[k]) for k in range(4))
+
+
+def piv_pairs_shifted(imgs, window_size=(32, 32), overlap=(16, 16), shift=None, signal_threshold: Optional[float] = None,
+                      return_planes: bool = False, pair_offset: int = 0):
+    """One SHIFTED pass: per window and pair the ``n x n`` window of frame t against the ``n x n`` window of frame t+1 at the integer
+    offset ``shift[pair, row, col] = (dy, dx)`` (int16, ``(T-1, n_rows, n_cols, 2)``; None: zeros), clamped by the kernel so that the
+    window stays inside the frame.  Returns ``(u, v, corr_max, s2n[, planes])`` like :func:`piv_pairs`; u, v include the clamped offset.
+    ``n`` in 16, 32, 64.  Host stacks and ``DeviceFrames``."""
+    from .device import DeviceFrames
+
+    lib = _lib.load()
+    _lib.require_device()
+    ws, ov = (int(window_size[0]), int(window_size[1])), (int(overlap[0]), int(overlap[1]))
+    if not lib.lspiv_shift_supported(ws[0], ws[1]):
+        raise ValueError(f"window_size {ws} is not supported by the shifted pass: the window must be square and one of {window.SHIFT_WINDOWS}")
+    a = _device_stack(imgs, signal_threshold)
+    T, H, W = a.shape
+    n_rows, n_cols = window.get_array_shape((H, W), ws, ov)
+    if T < 2 or n_rows < 1 or n_cols < 1:
+        raise ValueError(f"need >= 2 frames at least one window large, got {a.shape} for window {ws}")
+    P, n_win = T - 1, n_rows * n_cols
+    d_shift = None
+    if shift is not None:
+        sh = np.ascontiguousarray(shift, dtype=np.int16)
+        if sh.shape != (P, n_rows, n_cols, 2):
+            raise ValueError(f"shift must have shape {(P, n_rows, n_cols, 2)}, got {sh.shape}")
+        d_shift = DeviceFrames.empty((1, 1, sh.size * 2), np.uint8)
+        _lib.check(lib.lspiv_memcpy_h2d(d_shift.c_ptr, _lib.ptr(sh), sh.nbytes))
+    d_out = DeviceFrames.empty((4, P, n_win), np.float32)
+    d_planes = DeviceFrames.empty((P * n_win, ws[0], ws[1]), np.float32) if return_planes else None
+    _lib.check(lib.lspiv_piv_shift_pairs_dev_at(a.c_ptr, a.dtype_code, T, H, W, ws[0], ws[1], ov[0], ov[1], _sig(signal_threshold),
+                                                int(pair_offset), d_shift.c_ptr if d_shift is not None else None, d_out.c_ptr,
+                                                d_planes.c_ptr if d_planes is not None else None, None))
+    res = _results_to_host(d_out, P, n_rows, n_cols)
+    if return_planes:
+        return (*res, d_planes.to_host().reshape(P, n_win, ws[0], ws[1]))
+    return res
+
+
+def predict_shift(u, v, dim_size, coarse, fine):
+    """The predictor between two passes on the device: ``(u, v)`` ``(P, rows_c, cols_c)`` of a pass on its grid ``coarse = (n, overlap)``
+    (kernel orientation: before any ``v_sign``) -> int16 offsets ``(P, rows_f, cols_f, 2)`` = (dy, dx) on the grid ``fine``, clamped to
+    the frame: rint, 3 x 3 median, bilinear interpolation between the window centres, all in exact integer arithmetic."""
+    from .device import DeviceFrames
+
+    lib = _lib.load()
+    _lib.require_device()
+    (nc, oc), (nf, of) = (int(coarse[0]), int(coarse[1])), (int(fine[0]), int(fine[1]))
+    H, W = int(dim_size[0]), int(dim_size[1])
+    rc, cc = window.get_array_shape((H, W), (nc, nc), (oc, oc))
+    rf, cf = window.get_array_shape((H, W), (nf, nf), (of, of))
+    uu = np.ascontiguousarray(u, dtype=np.float32).reshape(-1, rc, cc)
+    vv = np.ascontiguousarray(v, dtype=np.float32).reshape(-1, rc, cc)
+    if uu.shape != vv.shape:
+        raise ValueError(f"u {uu.shape} and v {vv.shape} differ")
+    P = uu.shape[0]
+    d_uv = DeviceFrames.empty((2, P, rc * cc), np.float32)
+    _lib.check(lib.lspiv_memcpy_h2d(d_uv.c_ptr, _lib.ptr(uu), uu.nbytes))
+    _lib.check(lib.lspiv_memcpy_h2d(C.c_void_p(d_uv.ptr + uu.nbytes), _lib.ptr(vv), vv.nbytes))
+    out = np.empty((P, rf, cf, 2), dtype=np.int16)
+    d_shift = DeviceFrames.empty((1, 1, max(out.nbytes, 1)), np.uint8)
+    _lib.check(lib.lspiv_piv_predict_shift_dev(d_uv.c_ptr, C.c_void_p(d_uv.ptr + uu.nbytes), P, H, W, nc, nc, oc, oc, nf, nf, of, of,
+                                               d_shift.c_ptr, None))
+    if out.size:
+        _lib.check(lib.lspiv_memcpy_d2h(_lib.ptr(out), d_shift.c_ptr, out.nbytes))
+    return out
+
+
+def piv_multipass(imgs, passes, signal_threshold: Optional[float] = None, return_planes: bool = False, pair_offset: int = 0,
+                  return_shift: bool = False, return_passes: bool = False, out=None, scale=None):
+    """Multi-pass PIV: ``passes`` = ``[(n_0, overlap_0), ..., (n_K, overlap_K)]`` coarsest first (or a ``window.MultiPassWindow``); pass
+    0 is :func:`piv_pairs` of its window, each later pass (16, 32 or 64 px) cuts its window of frame t+1 at the integer offset the
+    previous pass predicts and measures the residual.  Returns ``(u, v, corr_max, s2n[, planes][, shift][, per_pass])`` on the LAST
+    pass's grid; ``shift`` int16 ``(T-1, n_rows, n_cols, 2)`` = the last pass's clamped offsets (dy, dx); ``per_pass`` a list with every
+    pass's ``(u, v, corr_max, s2n, shift)`` in the kernels' orientation (shift None for pass 0) -- the chain is then composed call by
+    call from :func:`piv_pairs`, :func:`predict_shift` and :func:`piv_pairs_shifted` IN ADDITION to the one call (a diagnostic: the work
+    is done twice; the C ABI hands out no intermediates), which gives the bits of the one call.
+    ``out`` / ``scale`` as in :func:`piv_pairs` (the scaling is numpy's own arithmetic on the host)."""
+    from .device import DeviceFrames
+
+    spec = passes if isinstance(passes, window.MultiPassWindow) else None
+    if spec is None:
+        passes = [(int(n), int(o)) for n, o in passes]
+        if not passes:
+            raise ValueError("passes is empty")
+        spec = window.multipass_spec((passes[-1][0],) * 2, (passes[-1][1],) * 2, passes[:-1])
+        if not isinstance(spec, window.MultiPassWindow):
+            spec = window.MultiPassWindow(passes)          # one pass: today's path through the chain's entry point
+    passes = list(spec.passes)
+    lib = _lib.load()
+    _lib.require_device()
+    host = not is_device(imgs)
+    a = imgs if not host else _lib.as_frames(imgs)
+    T, H, W = a.shape
+    n, ov = passes[-1]
+    n_rows, n_cols = window.get_array_shape((H, W), (n, n), (ov, ov))
+    if T < 2 or n_rows < 1 or n_cols < 1:
+        raise ValueError(f"need >= 2 frames at least one window large, got {a.shape} for window {(n, n)}")
+    P, n_win = T - 1, n_rows * n_cols
+    if out is not None:
+        out = _check_out(out, (P, n_rows, n_cols))
+    dt = None
+    if scale is not None:
+        if return_planes:
+            raise ValueError("scale and return_planes exclude each other")
+        dt = np.ascontiguousarray(scale[2], dtype=np.float64).reshape(-1)
+        if dt.shape != (P,):
+            raise ValueError(f"scale: dt must have one entry per frame pair ({P}), got shape {dt.shape}")
+    arr = (C.c_int * (4 * len(passes)))(*[q for m, o in passes for q in (m, m, o, o)])
+    shift = np.empty((P, n_rows, n_cols, 2), dtype=np.int16) if (return_shift or return_passes) else None
+    planes = None
+    if host and not return_passes:
+        res = out if out is not None else [np.empty((P, n_rows, n_cols), dtype=np.float32) for _ in range(4)]
+        planes = np.empty((P, n_win, n, n), dtype=np.float32) if return_planes else None
+        _lib.check(lib.lspiv_piv_multipass_at(_lib.ptr(a), _lib.DTYPE_CODES[a.dtype], T, H, W, len(passes), arr, _sig(signal_threshold),
+                                              int(pair_offset), _lib.ptr(res[0]), _lib.ptr(res[1]), _lib.ptr(res[2]), _lib.ptr(res[3]),
+                                              _lib.ptr(planes) if planes is not None else None, _lib.ptr(shift) if shift is not None else None))
+        res = tuple(res)
+    else:
+        d = _device_stack(a, signal_threshold)
+        d_out = DeviceFrames.empty((4, P, n_win), np.float32)
+        d_planes = DeviceFrames.empty((P * n_win, n, n), np.float32) if return_planes else None
+        d_shift = DeviceFrames.empty((1, 1, shift.nbytes), np.uint8) if shift is not None else None
+        _lib.check(lib.lspiv_piv_multipass_dev_at(d.c_ptr, d.dtype_code, T, H, W, len(passes), arr, _sig(signal_threshold), int(pair_offset),
+                                                  d_out.c_ptr, d_planes.c_ptr if d_planes is not None else None,
+                                                  d_shift.c_ptr if d_shift is not None else None, None))
+        res = _results_to_host(d_out, P, n_rows, n_cols, out)
+        if return_planes:
+            planes = d_planes.to_host().reshape(P, n_win, n, n)
+        if shift is not None:
+            _lib.check(lib.lspiv_memcpy_d2h(_lib.ptr(shift), d_shift.c_ptr, shift.nbytes))
+    if scale is not None:   # no fused scaling entry point for this mode: numpy's own arithmetic (ffpiv.py:418-419)
+        for k in range(2):
+            np.divide(res[k] * scale[k], dt[:, None, None], out=res[k], dtype=np.float64, casting="same_kind")
+    ret = list(res)
+    if return_planes:
+        ret.append(planes)
+    if return_shift:
+        ret.append(shift)
+    if return_passes:
+        # the chain again, call by call on the stack in HBM, in the kernels' orientation (a v_sign of the per-call entry points is undone:
+        # a negation is exact)
+        flip = _lib.get_option("v_sign") == 1
+        per, prev = [], None
+        for k, (m, o) in enumerate(passes):
+            if k == 0:
+                u, v, cm, sn = piv_pairs(d, (m, m), (o, o), signal_threshold, pair_offset=pair_offset)
+                sh = None
+            else:
+                sh = predict_shift(prev[0], prev[1], (H, W), passes[k - 1], (m, o))
+                u, v, cm, sn = piv_pairs_shifted(d, (m, m), (o, o), sh, signal_threshold, pair_offset=pair_offset)
+            if flip:
+                v = -v
+            prev = (u, v)
+            per.append((u, v, cm, sn, sh))
+        ret.append(per)
+    return tuple(ret)
 
 
 def cross_corr(imgs, window_size=(64, 64), overlap=(32, 32), search_area_size=None, normalize=False,

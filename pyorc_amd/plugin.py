@@ -122,6 +122,8 @@ def _wrap_get_piv(orig):
         search_area = kwargs.pop("search_area_size", None)
         # ... and so are the sliding ensemble's `ensemble_window=` / `ensemble_stride=`
         sliding = {k: kwargs.pop(k) for k in ("ensemble_window", "ensemble_stride") if k in kwargs}
+        # ... and the multi-pass chain's `coarse_passes=`
+        coarse = kwargs.pop("coarse_passes", None)
         engine, bound = kwargs.get("engine"), None
         if sig is not None and "engine" in sig.parameters:
             try:
@@ -134,19 +136,22 @@ def _wrap_get_piv(orig):
                 raise TypeError("search_area_size is a keyword of engine='hip' only")
             if sliding:
                 raise TypeError(f"{' / '.join(sliding)} is a keyword of engine='hip' only")
+            if coarse is not None:
+                raise TypeError("coarse_passes is a keyword of engine='hip' only")
             return orig(self, *args, **kwargs)
         # fail before any work if there is no MI355X / no library: the reference raises ValueError for an engine it cannot run
         from . import _lib
 
         _lib.load()
         _lib.require_device()
-        if search_area is not None or sliding:
+        extra = {"coarse_passes": coarse} if coarse is not None and len(coarse) else {}
+        if search_area is not None or sliding or extra:
             # the reference's method body lays the grid out by the window; with a search area of its own the engine's mirror of that
             # body (pyorc_amd.frames.get_piv: same configuration copy, coordinates, attributes and encoding) runs instead -- and with the
-            # sliding ensemble's keywords, which the reference's body would not pass on
+            # sliding ensemble's keywords and the multi-pass chain's, which the reference's body would not pass on
             from . import frames as frames_mod
 
-            return frames_mod.get_piv(self._obj, *args, **{**kwargs, **sliding, "engine": ENGINE, "search_area_size": search_area})
+            return frames_mod.get_piv(self._obj, *args, **{**kwargs, **sliding, **extra, "engine": ENGINE, "search_area_size": search_area})
         if bound is not None:
             bound.arguments["engine"] = "numba"
             call_args, call_kwargs = bound.args, bound.kwargs

@@ -66,6 +66,14 @@ def gather_blocks(local: np.ndarray, n_pairs: int, comm, align: int = 1) -> np.n
     return np.concatenate([recv[r][:, :sizes[r]] for r in range(comm.world)], axis=1)
 
 
+def _no_multipass(window_size) -> None:
+    """A multi-pass chain (``window.MultiPassWindow``) is not sharded over ranks."""
+    from . import window
+
+    if isinstance(window_size, window.MultiPassWindow):
+        raise NotImplementedError("coarse_passes with pyorc_amd.shard is not implemented: run the chain through get_ffpiv (devices=)")
+
+
 def sharded_piv(load_frames: Callable[[int, int], np.ndarray], n_pairs: int, window_size, overlap, comm,
                 compute: Optional[Callable] = None, signal_threshold=None, align: Optional[int] = None,
                 frame_shape=None) -> np.ndarray:
@@ -77,6 +85,7 @@ def sharded_piv(load_frames: Callable[[int, int], np.ndarray], n_pairs: int, win
     ``frame_shape`` (H, W): the rank blocks are cut on the anchor length of THAT window grid (``window.chunk_alignment``: 25 pairs, 75 on
     large grids); without it on the longest anchor of the window family, which is right for every grid.
     """
+    _no_multipass(window_size)
     if compute is None:
         from . import piv
 
@@ -330,6 +339,7 @@ def sharded_piv_dev(block, n_pairs: int, window_size, overlap, comm, signal_thre
     pairs + the halo frame; a rank without pairs passes an empty ``(0, H, W)`` stack -- the frame shape is still needed for the
     exchange --, ``None`` raises ValueError).  Returns (4, n_pairs, n_rows, n_cols) on every rank --
     bit-identical to ``piv.piv_pairs`` over the whole stack on one GPU."""
+    _no_multipass(window_size)
     if block is None:
         raise ValueError("sharded_piv_dev needs this rank's DeviceFrames block (ranks without pairs pass an empty (0, H, W) stack)")
     plan = ShardedPivDev(comm, n_pairs, block.shape[1:], window_size, overlap, signal_threshold, align)

@@ -177,6 +177,7 @@ def get_ffpiv(
     devices=None,
     ensemble_window: Optional[int] = None,
     ensemble_stride: Optional[int] = None,
+    coarse_passes=None,
 ):
     """Compute time-resolved (or ensemble) PIV on the MI355X; signature of pyorc's ``get_ffpiv`` (ffpiv.py:24-42).
 
@@ -201,11 +202,23 @@ def get_ffpiv(
     2c): a SLIDING ensemble -- output j is fitted on the mean correlation plane of the M pairs [j s, j s + M), so the result keeps a time
     axis of ``(P // s) - M // s + 1`` steps.  1 <= s <= M, M % s == 0; s None = M (block ensembles).  Chunks are cut on multiples of s
     and every chunking gives the same bits.  One device, materialised stacks (numpy, ``DeviceFrames``).
+
+    ``coarse_passes`` (the project's own mode): multi-pass PIV -- a list of coarse passes, coarsest first, each
+    an int n (window n x n at overlap n / 2) or a pair ``(n, overlap)``, run before the final pass ``window_size`` / ``overlap`` (16, 32 or
+    64 px), whose grid is the result's.  Every pass after the first cuts its window of frame t+1 at the integer offset the previous pass
+    predicts.  None or empty: today's path.  Chunks are cut on the anchors of pass 0; ``devices=`` and ``chunksize=`` give the same bits.
+    Per-timestep mode without a search area of its own.
     """
     if engine != "hip":
         raise ValueError(f"Selected PIV engine {engine} does not exist.")
     # a search area of its own: one window argument that answers for the search area wherever a grid, a plan or an alignment is asked for
     window_size = window.search_spec(window_size, search_area_size)
+    if coarse_passes is not None and len(coarse_passes):
+        if ensemble_corr:
+            raise NotImplementedError("coarse_passes with ensemble_corr=True is not implemented: the shifted kernels serve per-timestep mode only")
+        if isinstance(window_size, window.SearchWindow):
+            raise NotImplementedError("coarse_passes together with a search_area_size larger than the window is not implemented")
+        window_size = window.multipass_spec(window_size, overlap, coarse_passes)   # ValueError for an unsupported chain
     if ensemble_corr and isinstance(window_size, window.SearchWindow):
         raise NotImplementedError("ensemble_corr=True with search_area_size != window_size is not implemented: the search-area kernels "
                                   "serve per-timestep mode only")
@@ -227,7 +240,8 @@ def get_ffpiv(
     devs = _resolve_frames_devices(frames, devices)
     align = window.chunk_alignment(window_size, dim_size, overlap)
     stack_mode = _stack_signal_mode(signal_threshold)
-    resident_run = _is_lazy(frames) and n_frames >= 2 and not stack_mode
+    # (a chain's later passes read every frame of a chunk at offsets of their own: a lazy stack takes the chunk-loading path)
+    resident_run = _is_lazy(frames) and n_frames >= 2 and not stack_mode and not isinstance(window_size, window.MultiPassWindow)
     if resident_run:
         # a lazy stack: resident in HBM, loads planned against HOST memory and cut where dask cuts, launches on the anchors
         work = plan_lazy_devices(frames, n_frames, dim_size, window_size, overlap, n_win, chunksize, memory_factor, engine, prefetch, devs)
@@ -432,8 +446,8 @@ def _timestep_sink(n_pairs, n_workers, y, x, dt, res_x, res_y, window_size, over
     full = {k: np.empty((n_pairs, len(y), len(x)), dtype=np.float32) for k in ("s2n", "corr", "v_x", "v_y")}
     done = []
     px = [None] * n_workers            # per worker: scratch for a launch's u, v in pixels
-    # (the search-area entry points have no fused scaling: numpy's arithmetic on the host, the same bits)
-    on_device = piv.device_scaling_is_numpys(res_x, res_y) and not isinstance(window_size, window.SearchWindow)
+    # (the search-area and multi-pass entry points have no fused scaling: numpy's arithmetic on the host, the same bits)
+    on_device = piv.device_scaling_is_numpys(res_x, res_y) and not isinstance(window_size, (window.SearchWindow, window.MultiPassWindow))
 
     def launch(k, frames, p0, p1):
         p = p1 - p0

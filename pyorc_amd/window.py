@@ -62,6 +62,74 @@ def search_spec(window_size, search_area_size=None):
     return SearchWindow(sa, ws)
 
 
+SHIFT_WINDOWS = (16, 32, 64)
+MAX_PASSES = 8
+
+
+class MultiPassWindow(tuple):
+    """A chain of passes as ONE window argument of the layers below ``get_ffpiv`` / ``piv_pairs``: the tuple
+    itself is the FINAL pass's window ``(n, n)`` -- which lays out the grid and the result --, ``.passes`` every pass ``(n_k, overlap_k)``,
+    coarsest first, the final one last.  The chunk alignment is pass 0's, the memory plan answers for the whole chain."""
+
+    def __new__(cls, passes):
+        passes = tuple((int(n), int(o)) for n, o in passes)
+        self = super().__new__(cls, (passes[-1][0], passes[-1][0]))
+        self.passes = passes
+        return self
+
+    @property
+    def overlap(self):
+        return (self.passes[-1][1], self.passes[-1][1])
+
+
+def multipass_spec(window_size, overlap, coarse_passes=None):
+    """``window_size`` as the layers below take it: the plain tuple without coarse passes (None or empty: today's path), else a
+    validated :class:`MultiPassWindow`.  ``coarse_passes``: coarsest first, each an int n (window n x n at overlap n / 2) or a pair
+    ``(n, overlap)``; the final pass is ``window_size`` / ``overlap``.  Every pass is square and even, the list is non-increasing in n,
+    pass 0 takes any even square window the per-timestep path serves, every later pass one of 16, 32, 64.  Host-only."""
+    if isinstance(window_size, MultiPassWindow):
+        if coarse_passes:
+            raise ValueError("coarse_passes given twice: window_size is a MultiPassWindow already")
+        return window_size
+    ws = (int(window_size[0]), int(window_size[1]))
+    if coarse_passes is None or len(coarse_passes) == 0:
+        return ws
+    if isinstance(window_size, SearchWindow):
+        raise NotImplementedError("coarse_passes together with a search_area_size larger than the window is not implemented")
+    ov = (int(overlap[0]), int(overlap[1]))
+    if ws[0] != ws[1] or ov[0] != ov[1]:
+        raise ValueError(f"coarse_passes need a square window and overlap, got window_size {ws}, overlap {ov}")
+    passes = []
+    for e in coarse_passes:
+        if isinstance(e, (int, np.integer)) and not isinstance(e, bool):
+            n, o = int(e), int(e) // 2
+        else:
+            try:
+                n, o = e
+            except (TypeError, ValueError):
+                raise ValueError(f"coarse_passes: an entry is a window size n or a pair (n, overlap), got {e!r}") from None
+            if any(isinstance(q, bool) or not isinstance(q, (int, np.integer)) for q in (n, o)):
+                raise ValueError(f"coarse_passes: an entry is a window size n or a pair (n, overlap) of whole numbers, got {e!r}")
+            n, o = int(n), int(o)
+        passes.append((n, o))
+    passes.append((ws[0], ov[0]))
+    if len(passes) > MAX_PASSES:
+        raise ValueError(f"coarse_passes: at most {MAX_PASSES} passes in a chain, got {len(passes)}")
+    for k, (n, o) in enumerate(passes):
+        if n < 2 or n % 2:
+            raise ValueError(f"pass {k}: window {n} must be even and >= 2")
+        if not 0 <= o < n:
+            raise ValueError(f"pass {k}: overlap {o} must satisfy 0 <= overlap < window {n}")
+        if k and n not in SHIFT_WINDOWS:
+            raise ValueError(f"pass {k}: window {n} is not supported: every pass after the first (the final window_size included) must be "
+                             f"one of {SHIFT_WINDOWS}")
+        if k and n > passes[k - 1][0]:
+            raise ValueError(f"pass {k}: window {n} is larger than pass {k - 1}'s {passes[k - 1][0]}: list the passes coarsest first")
+    if _lib.load().lspiv_kernel_kind(passes[0][0], passes[0][0]) < 0:
+        raise ValueError(f"pass 0: no kernel for window {passes[0][0]}")
+    return MultiPassWindow(passes)
+
+
 def get_axis_shape(dim_size: int, window_size: int, overlap: int) -> int:
     nr, nc = C.c_int64(), C.c_int64()
     _lib.check(_lib.load().lspiv_grid_shape(dim_size, dim_size, window_size, window_size, overlap, overlap,
@@ -91,15 +159,25 @@ def get_rect_coordinates(dim_size, window_size, overlap, search_area_size=None, 
 
 
 def required_memory(n_frames: int, dim_size, window_size, overlap, search_area_size=None,
-                    dtype=np.uint8, with_planes: bool = False, sliding_blocks: int = 0) -> int:
+                    dtype=np.uint8, with_planes: bool = False, sliding_blocks: int = 0, coarse_passes=None) -> int:
     """HBM bytes one fused call on ``n_frames`` frames needs (frames + four result planes).
 
     The reference's figure is the host RAM of the materialised window stack + correlation volume
     (x3.9 .. x14.8 of the frames); the fused kernel materialises neither.
 
     ``sliding_blocks``: the blocks of a sliding ensemble's WHOLE run (:func:`sliding_outputs`); its block store stays in HBM next
-    to every chunk (:func:`sliding_store_bytes`).
+    to every chunk (:func:`sliding_store_bytes`).  ``coarse_passes`` (or a :class:`MultiPassWindow`): a multi-pass chain.
     """
+    if coarse_passes or isinstance(window_size, MultiPassWindow):
+        # a chain: the frames once, the largest pass's launch (results, rescue lists, the planes of the final pass), and the
+        # intermediates of two grids -- two result blocks and an offset array of the largest grid (lspiv_piv_multipass_dev_at)
+        spec = multipass_spec(window_size, overlap, coarse_passes)
+        frames_bytes = int(n_frames) * int(dim_size[0]) * int(dim_size[1]) * np.dtype(dtype).itemsize
+        last = len(spec.passes) - 1
+        per_pass = [required_memory(n_frames, dim_size, (n, n), (o, o), dtype=dtype, with_planes=with_planes and k == last) - frames_bytes
+                    for k, (n, o) in enumerate(spec.passes)]
+        tiles = [(int(n_frames) - 1) * int(np.prod(get_array_shape(dim_size, (n, n), (o, o)))) for n, o in spec.passes]
+        return frames_bytes + max(per_pass) + 2 * 16 * max(tiles[:-1]) + 4 * max(tiles[1:])
     sa = window_size if search_area_size is None else search_area_size
     code = _lib.DTYPE_CODES[np.dtype(dtype)]
     r = _lib.load().lspiv_required_bytes(n_frames, dim_size[0], dim_size[1], code, sa[0], sa[1],
@@ -183,6 +261,10 @@ def chunk_alignment(window_size, dim_size=None, overlap=None) -> int:
     lib = _lib.load()
     if isinstance(window_size, SearchWindow):
         return 1   # the search-area kernels are per-pair: any chunking gives the same bits
+    if isinstance(window_size, MultiPassWindow):
+        # pass 0 is the per-timestep path on ITS window and grid; every later pass is pair-local
+        n0, o0 = window_size.passes[0]
+        return chunk_alignment((n0, n0), dim_size, None if dim_size is None else (o0, o0))
     if dim_size is None:
         return _lib.check(lib.lspiv_chunk_alignment(int(window_size[0]), int(window_size[1])))
     ov = (int(window_size[0]) // 2, int(window_size[1]) // 2) if overlap is None else overlap
