@@ -39,7 +39,8 @@ extern "C" {
 
 #define LSPIV_ABI_VERSION 5   /* (additions since, nothing existing moved, no version change: the search-area entry points lspiv_piv_search_pairs_at /
                                * lspiv_piv_search_pairs_dev_at and lspiv_search_supported; the sliding ensemble, lspiv_ensemble_set_sliding /
-                               * lspiv_ensemble_sliding_reserve / lspiv_ensemble_sliding_finish; multi-pass PIV, lspiv_shift_supported /
+                               * lspiv_ensemble_sliding_reserve / lspiv_ensemble_sliding_finish; the multi-pass ensemble, lspiv_ensemble_set_shift /
+                               * _set_shift_dev / _get_shift; multi-pass PIV, lspiv_shift_supported /
                                * lspiv_piv_shift_pairs_dev_at / lspiv_piv_predict_shift_dev / lspiv_piv_multipass_dev_at / lspiv_piv_multipass_at)
                                * 5 (round 6): lspiv_chunk_alignment(wy, wx) without a grid now returns the alignment that is right on EVERY grid (75
                                * where it returned 25: callers that cut chunks on it stay bit-reproducible on large grids); additions:
@@ -384,6 +385,21 @@ int lspiv_ensemble_sliding_reserve(lspiv_ensemble* handle, int64_t n_pairs);
  * under the retention rules of lspiv_ensemble_finish; lspiv_ensemble_stats then reports the totals over the outputs of this call. */
 int lspiv_ensemble_sliding_finish(lspiv_ensemble* handle, float count_min, int64_t first_out, int64_t n_out,
                                   float* u, float* v, float* corr_count, float* corr_mean);
+/* Multi-pass ensemble: a SHIFTED handle (the project's own mode).  `shift`: n_win x {dy, dx} int16, the
+ * integer offset of every window's cut of frame t+1 from its cut of frame t, the SAME for every pair of the run; it is copied into the
+ * handle and clamped there so that the shifted window stays inside the frame (lspiv_ensemble_get_shift returns the clamped values, n_win
+ * x {dy, dx}; LSPIV_EINVAL on a handle without offsets).  NULL clears the offsets: the plain ensemble again.  Before the first
+ * accumulate only, and not on a sliding handle (LSPIV_EINVAL); the window must satisfy lspiv_shift_supported and the option norm_clip
+ * be 1 (LSPIV_EUNSUPPORTED).  "_dev": the same from a device array; the copy runs on `stream` (NULL: the library's) and has completed
+ * on return.  On a shifted handle lspiv_ensemble_accumulate / _accumulate_dev run the shifted ensemble kernel -- one owner per window,
+ * one plane per inverse transform, float32 additions in pair order: the same bits for every chunking -- and return LSPIV_EUNSUPPORTED
+ * under the option signal_mode = 1, as multi-pass PIV does; lspiv_ensemble_finish / _finish_partials fit the mean plane, rescue that
+ * fit in float64 at the clamped offsets, and return the TOTAL displacement u = dx + residual, v = dy + residual (float32 sums; a NaN
+ * residual stays NaN, a zero offset leaves the residual's bits; "v_sign" applied last).  lspiv_ensemble_export / _import carry the
+ * sums as before; lspiv_ensemble_allreduce returns LSPIV_EINVAL unless every handle holds the same clamped offsets (or none). */
+int lspiv_ensemble_set_shift(lspiv_ensemble* handle, const int16_t* shift);
+int lspiv_ensemble_set_shift_dev(lspiv_ensemble* handle, const int16_t* d_shift, void* stream);
+int lspiv_ensemble_get_shift(lspiv_ensemble* handle, int16_t* shift);
 int lspiv_ensemble_destroy(lspiv_ensemble* handle);
 
 /* ---------------------------------------------------------------- next rows */

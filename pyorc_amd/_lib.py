@@ -99,6 +99,9 @@ SIGNATURES = {
     "lspiv_ensemble_set_sliding": (_i32, [_vp, _i64, _i64]),
     "lspiv_ensemble_sliding_reserve": (_i32, [_vp, _i64]),
     "lspiv_ensemble_sliding_finish": (_i32, [_vp, _f32, _i64, _i64, _vp, _vp, _vp, _vp]),
+    "lspiv_ensemble_set_shift": (_i32, [_vp, _vp]),
+    "lspiv_ensemble_set_shift_dev": (_i32, [_vp, _vp, _vp]),
+    "lspiv_ensemble_get_shift": (_i32, [_vp, _vp]),
     "lspiv_ensemble_destroy": (_i32, [_vp]),
     "lspiv_projection_create": (_i32, [_i64, _i64, _i64, _i64, _vp, _vp, _i64, _vp, _vp, _i64, _vp, _i64, C.POINTER(_vp)]),
     "lspiv_project_frames": (_i32, [_vp, _vp, _i32, _i64, _vp]),

@@ -49,6 +49,11 @@ struct lspiv_ensemble {
   float* d_store; float* d_store_cnt;
   size_t store_blocks;      // capacity, in blocks
   bool tail_open;           // the last accumulate ended inside a block: it was the last one
+  // multi-pass ensemble (lspiv_ensemble_set_shift): a SHIFTED handle -- frame t+1's window of every pair sits at
+  // the window's own offset.  d_shift: n_win x {dy, dx}, already clamped (launch_clamp_shift: window_shift's clamp is idempotent);
+  // shift_host: the same values, for lspiv_ensemble_get_shift and the comparison in lspiv_ensemble_allreduce.  nullptr: the plain ensemble
+  int16_t* d_shift;
+  std::vector<int16_t> shift_host;
   int sl_layout;            // slot layout of the store, recorded by the first accumulate: 0 nothing written yet, 1 fft-shifted row-major, 2 lane-major (64 x 64 walking kernel)
 };
 
@@ -289,6 +294,16 @@ static int ensemble_launch(lspiv_ensemble* h, DeviceCtx* c, const void* d_frames
   const int kind = lspiv_kernel_kind(h->wy, h->wx);
   const int walk = lspiv::walk_setting();
   p.pair_offset = h->pairs_done;   // advanced only once the launch has been issued (a failed accumulate changes nothing)
+  if (h->d_shift) {
+    // shifted handle: the one-owner kernel on shifted windows (piv_fft_impl.h, "shifted ensemble kernel"); no walking, no segments --
+    // its sums are the same bits for every chunking
+    LSPIV_TRY(check_multipass_options());   // (signal_mode = 1, norm_clip = 0: refused here, where multi-pass PIV refuses them)
+    p.shifted = 1;
+    p.shift = h->d_shift;
+    LSPIV_TRY(dispatch(p, dtype, true, s));
+    h->pairs_done += p.n_pairs;
+    return LSPIV_OK;
+  }
   if (h->sl_stride) {
     // sliding ensemble: the sums of this call's blocks go into the block store, nothing into d_sum / d_count
     if (h->tail_open)
@@ -419,7 +434,7 @@ int lspiv_ensemble_accumulate(lspiv_ensemble* h, const void* frames, int dtype, 
   LSPIV_TRY(stage_ring(c, frame_bytes));
   const int64_t fpb = std::max<int64_t>(1, (int64_t)(c->pinned_cap / frame_bytes));
   // sub-batches are cut on the segment anchors -- on the blocks of a sliding handle
-  const int64_t align = h->sl_stride ? h->sl_stride : std::max(1, chunk_alignment_for(h->wy, h->wx, (int64_t)n_win)), base_offset = h->pairs_done;
+  const int64_t align = h->sl_stride ? h->sl_stride : h->d_shift ? 1 : std::max(1, chunk_alignment_for(h->wy, h->wx, (int64_t)n_win)), base_offset = h->pairs_done;
   if (h->sl_stride)   // the block store grows once per call, not once per sub-batch
     LSPIV_TRY(sliding_reserve(h, (size_t)((base_offset + T - 1 + h->sl_stride - 1) / h->sl_stride), c->stream));
   int64_t launched = 0;
@@ -533,6 +548,7 @@ static int ensemble_partials(lspiv_ensemble* h, DeviceCtx* c, bool* complete, co
   int64_t pair0 = 0;   // (every chunk of the run is kept, in order: retain_complete)
   for (const auto& kp : h->kept) {
     LSPIV_TRY(fill_params(&p, kp.d_frames, kp.dtype, kp.T, h->H, h->W, h->wy, h->wx, h->oy, h->ox, -1.0f, h->g));
+    p.shift = h->d_shift;   // shifted handle: frame t+1's window at the window's clamped offset (ens_partial_kernel, window_shift)
     a.cmax = kp.d_cmax; a.n_pairs = (uint32_t)(kp.T - 1); a.blk0 = blk0; a.pair0 = (uint32_t)pair0;
     LSPIV_TRY(launch_status(lspiv::launch_ens_partial(p, kp.dtype, a, c->stream)));
     blk0 += (a.n_pairs + lspiv::kEnsPairBlock - 1) / lspiv::kEnsPairBlock;
@@ -559,6 +575,16 @@ static int ensemble_final(lspiv_ensemble* h, DeviceCtx* c, const double* d_total
 // results of c->d_out / c->d_planes / the count to the caller ("v_sign" applied first)
 static int ensemble_deliver(lspiv_ensemble* h, DeviceCtx* c, float* u, float* v, float* corr_count, float* corr_mean) {
   const size_t n_win = (size_t)h->g.n_rows * h->g.n_cols;
+  if (h->d_shift) {
+    // shifted handle: the fit and its float64 rescue gave the RESIDUAL; the total displacement adds the clamped offset (one "pair" of
+    // n_win results: add_shift_kernel's index is the window then)
+    lspiv::PivParams p;
+    LSPIV_TRY(fill_params(&p, nullptr, 0, 2, h->H, h->W, h->wy, h->wx, h->oy, h->ox, -1.0f, h->g));
+    p.shift = h->d_shift;
+    p.u = c->d_out;
+    p.v = c->d_out + n_win;
+    LSPIV_TRY(launch_status(lspiv::launch_add_shift(p, c->stream)));
+  }
   LSPIV_TRY(apply_v_sign(c->d_out + n_win, (int64_t)n_win, c->stream));
   HIP_TRY(hipMemcpyAsync(u, c->d_out, n_win * sizeof(float), hipMemcpyDeviceToHost, c->stream));
   HIP_TRY(hipMemcpyAsync(v, c->d_out + n_win, n_win * sizeof(float), hipMemcpyDeviceToHost, c->stream));
@@ -657,10 +683,66 @@ int lspiv_ensemble_finish(lspiv_ensemble* h, float count_min, float n_frames, fl
   return ensemble_deliver(h, c, u, v, corr_count, corr_mean);
 }
 
+// ---- multi-pass ensemble: shifted handles -------------------------------------------------------------
+// `src` (host, or device when on_device) -> the handle's own field, clamped by window_shift on the device; nullptr clears it
+static int ensemble_set_shift(lspiv_ensemble* h, const int16_t* src, bool on_device, void* stream, const char* call) {
+  if (!h) return fail(LSPIV_EINVAL, "NULL argument");
+  if (h->sl_stride) return fail(LSPIV_EINVAL, "%s: this is a sliding ensemble handle (lspiv_ensemble_set_sliding); a sliding ensemble has no shifted pass", call);
+  if (h->pairs_done || h->foreign) return fail(LSPIV_EINVAL, "%s must be called before the first accumulate", call);
+  if (!src) {
+    if (h->d_shift) (void)hipFree(h->d_shift);
+    h->d_shift = nullptr;
+    h->shift_host.clear();
+    return LSPIV_OK;
+  }
+  if (!lspiv_shift_supported(h->wy, h->wx))
+    return fail(LSPIV_EUNSUPPORTED, "shifted ensemble pass with window %dx%d is not supported: the window must be square and one of {16, 32, 64}", h->wy, h->wx);
+  if (!g_opt_norm_clip.load())
+    return fail(LSPIV_EUNSUPPORTED, "option norm_clip = 0 is served by the block-per-window kernels only, not by a shifted ensemble pass");
+  if (h->H > 32767 || h->W > 32767)
+    return fail(LSPIV_EINVAL, "frame (%lld,%lld): a side above 32767 does not fit the int16 offsets", (long long)h->H, (long long)h->W);
+  DeviceCtx* c;
+  LSPIV_TRY(get_ctx(&c));
+  hipStream_t s = on_stream(c, stream);
+  const size_t n_win = (size_t)h->g.n_rows * h->g.n_cols, bytes = n_win * 2 * sizeof(int16_t);
+  void* d = nullptr;
+  if (hipMalloc(&d, bytes) != hipSuccess) { (void)hipGetLastError(); return fail(LSPIV_ENOMEM, "hipMalloc window offsets"); }
+  std::vector<int16_t> host(n_win * 2);
+  lspiv::PivParams p;
+  int rc = fill_params(&p, nullptr, 0, 2, h->H, h->W, h->wy, h->wx, h->oy, h->ox, -1.0f, h->g);
+  if (rc == LSPIV_OK) {
+    p.shift = (const int16_t*)d;
+    hipError_t e = hipMemcpyAsync(d, src, bytes, on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, s);
+    if (e == hipSuccess) e = lspiv::launch_clamp_shift(p, (int16_t*)d, s);
+    if (e == hipSuccess) e = hipMemcpyAsync(host.data(), d, bytes, hipMemcpyDeviceToHost, s);
+    if (e == hipSuccess) e = hipStreamSynchronize(s);   // the field is complete before any accumulate, on whatever stream
+    if (e != hipSuccess) { (void)hipGetLastError(); rc = fail(LSPIV_EHIP, "%s: %s", call, hipGetErrorString(e)); }
+  }
+  if (rc != LSPIV_OK) { (void)hipFree(d); return rc; }
+  if (h->d_shift) (void)hipFree(h->d_shift);
+  h->d_shift = (int16_t*)d;
+  h->shift_host.swap(host);
+  return LSPIV_OK;
+}
+int lspiv_ensemble_set_shift(lspiv_ensemble* h, const int16_t* shift) {
+  std::lock_guard<std::mutex> host_lock(locks_here().host);
+  return ensemble_set_shift(h, shift, false, nullptr, "lspiv_ensemble_set_shift");
+}
+int lspiv_ensemble_set_shift_dev(lspiv_ensemble* h, const int16_t* d_shift, void* stream) {
+  return ensemble_set_shift(h, d_shift, true, stream, "lspiv_ensemble_set_shift_dev");
+}
+int lspiv_ensemble_get_shift(lspiv_ensemble* h, int16_t* shift) {
+  if (!h || !shift) return fail(LSPIV_EINVAL, "NULL argument");
+  if (!h->d_shift) return fail(LSPIV_EINVAL, "lspiv_ensemble_get_shift: not a shifted handle (lspiv_ensemble_set_shift)");
+  memcpy(shift, h->shift_host.data(), h->shift_host.size() * sizeof(int16_t));
+  return LSPIV_OK;
+}
+
 // ---- sliding ensemble ---------------------------------------------------------------------------------------------------
 int lspiv_ensemble_set_sliding(lspiv_ensemble* h, int64_t window_pairs, int64_t stride_pairs) {
   if (!h) return fail(LSPIV_EINVAL, "NULL argument");
   if (h->pairs_done || h->foreign) return fail(LSPIV_EINVAL, "lspiv_ensemble_set_sliding must be called before the first accumulate");
+  if (h->d_shift) return fail(LSPIV_EINVAL, "lspiv_ensemble_set_sliding: this is a shifted handle (lspiv_ensemble_set_shift); a sliding ensemble has no shifted pass");
   if (stride_pairs < 1 || stride_pairs > window_pairs || window_pairs % stride_pairs != 0 || window_pairs >= (int64_t)1 << 24)
     return fail(LSPIV_EINVAL, "sliding ensemble: need 1 <= stride <= window and window %% stride == 0, got window %lld, stride %lld",
                 (long long)window_pairs, (long long)stride_pairs);
@@ -782,6 +864,8 @@ int lspiv_ensemble_allreduce(lspiv_ensemble** handles, int n) {
     const lspiv_ensemble* r = handles[0];
     if (h->H != r->H || h->W != r->W || h->wy != r->wy || h->wx != r->wx || h->oy != r->oy || h->ox != r->ox)
       return fail(LSPIV_ESHAPE, "handle %d has another geometry than handle 0", k);
+    if (h->shift_host != r->shift_host)   // (both empty: two plain handles)
+      return fail(LSPIV_EINVAL, "handle %d has other window offsets (lspiv_ensemble_set_shift) than handle 0: their sums are not sums of the same planes", k);
     if (h->device < 0 || h->device >= kMaxDevices) return fail(LSPIV_EINVAL, "handle %d: device %d out of range", k, h->device);
     devs.push_back(h->device);
   }
@@ -808,7 +892,7 @@ int lspiv_ensemble_destroy(lspiv_ensemble* h) {
   ensemble_drop_kept(h);
   for (auto& e : h->acc_events) (void)hipEventDestroy(e.ev);
   for (void* p : {(void*)h->d_sum, (void*)h->d_count, (void*)h->d_part, h->d_rescue, (void*)h->d_partial, (void*)h->d_totals,
-                  (void*)h->d_store, (void*)h->d_store_cnt})
+                  (void*)h->d_store, (void*)h->d_store_cnt, (void*)h->d_shift})
     if (p) hipFree(p);
   delete h;
   return LSPIV_OK;

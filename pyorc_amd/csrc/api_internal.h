@@ -221,6 +221,10 @@ int fill_params(lspiv::PivParams* p, const void* d_frames, int dtype, int64_t T,
 int dispatch(const lspiv::PivParams& p0, int dtype, bool ensemble, hipStream_t s);
 int apply_v_sign(float* d_v, int64_t n, hipStream_t s);
 int apply_signal_mode(DeviceCtx* c, lspiv::PivParams* p, int dtype, hipStream_t s);
+// shifted passes (multi-pass PIV, multi-pass ensemble): the window is 16, 32 or 64 px square, the frame fits the int16 offsets, and the
+// options norm_clip = 0 / signal_mode = 1 are refused (LSPIV_EUNSUPPORTED)
+int check_shift(int wy, int wx, int64_t H, int64_t W);
+int check_multipass_options();
 // window kinds served by the time-walking kernels (every even square window 6 .. 64)
 inline bool kind_walks(int kind) { return kind == 1 || kind == 2 || kind == 6 || kind == 8; }
 // the anchor length the walking kernels use on a grid of n_win windows (common.h, walk_anchor)

@@ -177,7 +177,9 @@ int apply_v_sign(float* d_v, int64_t n, hipStream_t s) {
 
 static int dispatch_kernels(const lspiv::PivParams& p, int dtype, bool ensemble, hipStream_t s) {
   if (p.shifted) {   // multi-pass mode: the shifted per-pair kernels
-    if (ensemble) return fail(LSPIV_EUNSUPPORTED, "ensemble mode has no shifted kernels");
+    if (ensemble)   // multi-pass ensemble: one owner per window sums the shifted planes over the chunk's pairs
+      return launch_status(p.wy == 16 ? lspiv::launch_piv_shift_ensemble16(p, dtype, s) : p.wy == 32 ? lspiv::launch_piv_shift_ensemble32(p, dtype, s)
+                                                                                                      : lspiv::launch_piv_shift_ensemble64(p, dtype, s));
     return launch_status(p.wy == 16 ? lspiv::launch_piv_shift16(p, dtype, s) : p.wy == 32 ? lspiv::launch_piv_shift32(p, dtype, s)
                                                                                            : lspiv::launch_piv_shift64(p, dtype, s));
   }
@@ -245,6 +247,23 @@ int chunk_alignment_for(int wy, int wx, int64_t n_win) {
   const int base = base_alignment(wy, wx);
   if (base <= 1 || lspiv::walk_setting() > 1) return base;     // per-pair kernels, or a forced anchor length
   return (int)lspiv::walk_anchor(wy, (uint32_t)std::min<int64_t>(n_win, 0x7fffffff));
+}
+
+// ---- shifted passes: what a window, a frame and the options must satisfy (multi-pass PIV and the multi-pass ensemble) ----
+static bool shift_shape_ok(int wy, int wx) { return wy == wx && (wy == 16 || wy == 32 || wy == 64); }
+int check_multipass_options() {
+  if (!g_opt_norm_clip.load())
+    return fail(LSPIV_EUNSUPPORTED, "option norm_clip = 0 is served by the block-per-window kernels only, not by multi-pass PIV");
+  if (g_opt_signal_mode.load() == 1)
+    return fail(LSPIV_EUNSUPPORTED, "option signal_mode = 1 scores a window position over a chunk; a shifted window has no position of its own: "
+                "not supported by multi-pass PIV");
+  return LSPIV_OK;
+}
+int check_shift(int wy, int wx, int64_t H, int64_t W) {
+  if (!shift_shape_ok(wy, wx))
+    return fail(LSPIV_EUNSUPPORTED, "shifted pass with window %dx%d is not supported: the window must be square and one of {16, 32, 64}", wy, wx);
+  if (H > 32767 || W > 32767) return fail(LSPIV_EINVAL, "frame (%lld,%lld): a side above 32767 does not fit the int16 offsets", (long long)H, (long long)W);
+  return check_multipass_options();
 }
 
 }  // namespace lspiv_api
@@ -433,22 +452,6 @@ int lspiv_piv_search_pairs_dev_at(const void* d_frames, int dtype, int64_t T, in
 }
 
 // ---- multi-pass PIV (include/lspiv.h) ---------------------------------------------------------------
-static bool shift_shape_ok(int wy, int wx) { return wy == wx && (wy == 16 || wy == 32 || wy == 64); }
-static int check_multipass_options() {
-  if (!g_opt_norm_clip.load())
-    return fail(LSPIV_EUNSUPPORTED, "option norm_clip = 0 is served by the block-per-window kernels only, not by multi-pass PIV");
-  if (g_opt_signal_mode.load() == 1)
-    return fail(LSPIV_EUNSUPPORTED, "option signal_mode = 1 scores a window position over a chunk; a shifted window has no position of its own: "
-                "not supported by multi-pass PIV");
-  return LSPIV_OK;
-}
-static int check_shift(int wy, int wx, int64_t H, int64_t W) {
-  if (!shift_shape_ok(wy, wx))
-    return fail(LSPIV_EUNSUPPORTED, "shifted pass with window %dx%d is not supported: the window must be square and one of {16, 32, 64}", wy, wx);
-  if (H > 32767 || W > 32767) return fail(LSPIV_EINVAL, "frame (%lld,%lld): a side above 32767 does not fit the int16 offsets", (long long)H, (long long)W);
-  return check_multipass_options();
-}
-
 // one shifted pass on stream s: kernel + rescue pass (both write the residual), then the clamped offset is added; v_sign is the caller's
 static int shift_pass(const void* d_frames, int dtype, int64_t T, int64_t H, int64_t W, int wy, int wx, int oy, int ox, float signal_threshold,
                       int64_t pair_offset, const int16_t* d_shift, float* d_out, float* d_planes, hipStream_t s, lspiv::PivParams* out_p) {

@@ -114,12 +114,12 @@ struct PivParams {
   // multi-pass mode (piv_fft_impl.h, "shifted kernel"): shifted != 0 selects the shifted per-pair kernels; shift = nullptr (all
   // zero) or n_tiles x {dy, dx}, the integer offset of result g's window of frame t+1 from its window of frame t.  The kernels
   // and the rescue pass clamp it to the frame (window_shift) and write the RESIDUAL displacement; launch_add_shift adds the
-  // clamped offset afterwards
+  // clamped offset afterwards.  Shifted ensemble pass: shift holds n_win x {dy, dx}, one field for every pair (the index is the window)
   int shifted;
   const int16_t* shift;
 };
 
-// The offset of result g = pair * n_win + window (grid row wrow, column wcol), clamped so that the shifted window stays inside
+// The offset of result g = pair * n_win + window (shifted ensemble pass: g = window; grid row wrow, column wcol), clamped so that the shifted window stays inside
 // the frame: dy in [-y0, H - wy - y0], dx in [-x0, W - wx - x0].  The ONE place the clamp lives: the shifted kernels, the rescue
 // kernels and the add step all call it, so what is read, what is re-evaluated and what is added cannot differ -- and no offset
 // array can make a kernel read outside the stack.
@@ -433,8 +433,15 @@ hipError_t launch_piv_search64(const PivParams& p, int dtype, hipStream_t s);
 hipError_t launch_piv_shift16(const PivParams& p, int dtype, hipStream_t s);
 hipError_t launch_piv_shift32(const PivParams& p, int dtype, hipStream_t s);
 hipError_t launch_piv_shift64(const PivParams& p, int dtype, hipStream_t s);
+// multi-pass ensemble: the same windows summed over the pairs of a chunk by one owner per window (corr_sum / corr_count, per-pair cmax / s2n);
+// p.shift = nullptr or n_win x {dy, dx}: ONE offset field for every pair, indexed by the window
+hipError_t launch_piv_shift_ensemble16(const PivParams& p, int dtype, hipStream_t s);
+hipError_t launch_piv_shift_ensemble32(const PivParams& p, int dtype, hipStream_t s);
+hipError_t launch_piv_shift_ensemble64(const PivParams& p, int dtype, hipStream_t s);
 // u[g] += clamped dx, v[g] += clamped dy of p.shift (float32 sums; a NaN residual stays NaN): after the rescue pass (piv_multipass.hip)
 hipError_t launch_add_shift(const PivParams& p, hipStream_t s);
+// out[w] = the clamped offset of window w of p.shift (n_win x {dy, dx}; out may be p.shift itself): a shifted ensemble handle's field
+hipError_t launch_clamp_shift(const PivParams& p, int16_t* out, hipStream_t s);
 // window grid of one pass of a chain, and the predictor between two passes (piv_multipass.hip)
 struct PassGrid { int wy, wx, sy, sx, n_rows, n_cols; };   // window, strides, grid
 hipError_t launch_predict_shift(const float* u, const float* v, uint32_t n_pairs, int H, int W, const PassGrid& coarse, const PassGrid& fine,

@@ -817,7 +817,8 @@ __device__ __forceinline__ void cross_spectrum_half(int partner_byte, const floa
 // On return xr = plane of tile 0, xi = plane of tile 1, natural (un-shifted) order: lane = row y,
 // register = column x;  skip[k] = plane k is NaN (signal pre-mask / non-finite input).
 // SHIFT (multi-pass mode): the plain pair, but frame t+1's window sits at the window's own clamped offset (window_shift), ONE window per job
-template <typename T, int N, bool WANT_NZ, bool EMBED = false, bool SEARCH = false, bool SHIFT = false>
+// SHIFT_WIN (shifted ensemble pass): the offsets are one field for every pair of the run, indexed by the window alone
+template <typename T, int N, bool WANT_NZ, bool EMBED = false, bool SEARCH = false, bool SHIFT = false, bool SHIFT_WIN = false>
 __device__ __forceinline__ void correlate_job(const PivParams& p, const TileRef (&t)[2], float* buf, int lg,
                                               int partner_byte, float (&xr)[N], float (&xi)[N], bool (&skip)[2],
                                               float (&mean)[2]) {
@@ -834,7 +835,7 @@ __device__ __forceinline__ void correlate_job(const PivParams& p, const TileRef 
     const int64_t off = ((int64_t)t[k].pair * p.H + (int64_t)(wrow * p.sy + row_of<N>(lg))) * p.W + (int64_t)wcol * p.sx;
     int64_t offb = off + p.frame_elems;
     if constexpr (SHIFT) {   // the only new work of the shifted kernel: the address of frame t+1's rows
-      const WinShift ws = window_shift(p, t[k].pair * p.n_win + t[k].win, wrow, wcol);
+      const WinShift ws = window_shift(p, SHIFT_WIN ? t[k].win : t[k].pair * p.n_win + t[k].win, wrow, wcol);
       offb += (int64_t)ws.dy * p.W + ws.dx;
     }
     raw[k][0].fetch(frames + off);
@@ -2285,6 +2286,79 @@ __global__ __launch_bounds__(BLOCK, (kWavesPerSimd<T, N>)) void piv_fft_ensemble
     if (keep[0] || keep[1]) accumulate_planes<N>(p.corr_sum + (size_t)w * G::NN, lg, xr, keep[0], xi, keep[1]);
   }
   if (valid && lg == 0) p.corr_count[w] += cnt;
+}
+
+// ---- shifted ensemble kernel (multi-pass ensemble): the one-owner ensemble kernel above on shifted windows ----
+// A job owns ONE window and walks the pairs of the chunk in order; frame t+1's window of EVERY pair sits at the window's own clamped
+// offset (correlate_job, SHIFT with SHIFT_WIN: p.shift holds n_win x {dy, dx}, one field for the whole run).  The walking kernels'
+// carried spectrum cannot be used: they keep the forward transform of frame t+1's window to serve as frame t's window of the next pair,
+// and here frame t+1's window (at y0 + dy) is NOT the window of the next pair's frame t (at y0) -- two forward conversions per pair.
+// ONE plane per inverse transform (correlate_job's SINGLE, as in piv_fft_shift_kernel): two planes in one complex float32 inverse round
+// each other's samples into their own, so a shared inverse would tie a pair's bits to which pair it is coupled with -- and that depends
+// on where a chunk starts and ends.  With one plane per inverse a window's sum is a function of its own samples and its own offset alone,
+// added up in absolute pair order by its single owner (no atomics): the same bits for EVERY chunking, odd chunk starts included.  The
+// price against the plain one-owner kernel: 2 instead of 1.5 transforms per pair and a read-modify-write of the sum (MALL-resident, by
+// its owner) per pair instead of per two pairs.  corr_sum / corr_count / the per-pair cmax and s2n are written as piv_fft_ensemble_kernel
+// writes them.
+// registers (ROCm 7.2, no scratch in any variant; uint8 | float32 | float64, without - with the signal score): 16-point 66 - 69 | 63 - 83 |
+// 72 - 89 VGPRs, 32-point 106 - 108 | 106 - 114 | 120 - 126, 64-point 214 - 216 | 206 - 212 | 216 - 217: inside the bounds of piv_fft_kernel
+// (kWavesPerSimd: 4 / 4 / 2 waves per SIMD) at every size.  The sum stays in HBM (no kEnsRegAcc variant): 32 more VGPRs at 32 points
+// would leave the 128 of four waves.
+template <typename T, int N, bool WANT_NZ>
+__global__ __launch_bounds__(BLOCK, (kWavesPerSimd<T, N>)) void piv_fft_shift_ensemble_kernel(PivParams p) {
+  extern __shared__ __attribute__((aligned(16))) float smem[];
+  using G = Geo<N>;
+  const int lane = threadIdx.x & 63;
+  const int wave = threadIdx.x >> 6;
+  const int grp = lane / G::LG;
+  const int lg = lane & (G::LG - 1);
+  float* buf = smem + (wave * G::GROUPS + grp) * G::LDS_JOB;
+  const int partner_byte = partner_byte_of<N>(lane, lg);
+  const uint32_t job = (blockIdx.x * WAVES_PER_BLOCK + wave) * G::GROUPS + grp;
+  const bool valid = job < p.n_win;
+  const uint32_t w = valid ? job : p.n_win - 1;   // jobs past the end recompute the last window and store nothing
+  float cnt = 0.0f;
+  for (uint32_t pair = 0; pair < p.n_pairs; ++pair) {
+    TileRef t[2] = {{pair, w, valid}, {pair, w, false}};
+    float xr[N], xi[N], mean[2];
+    bool skip[2];
+    correlate_job<T, N, WANT_NZ, false, false, true, true>(p, t, buf, lg, partner_byte, xr, xi, skip, mean);
+    float row_max;
+    const float vmax = plane_max<N>(xr, row_max);
+    float cm = vmax, sn = vmax * __builtin_amdgcn_rcpf(mean[0]);
+    const bool keep = valid && !skip[0] && (cm >= p.corr_min) && (sn >= p.s2n_min);  // NaN s2n compares false
+    cm = keep ? cm : 0.0f;
+    sn = keep ? sn : 0.0f;
+    cnt += (cm > 1e-6f) ? 1.0f : 0.0f;
+    if (valid && lg == 0) {
+      p.cmax[(size_t)pair * p.n_win + w] = cm;
+      p.s2n[(size_t)pair * p.n_win + w] = sn;
+    }
+    if (keep) accumulate_planes<N>(p.corr_sum + (size_t)w * G::NN, lg, xr, true, xi, false);   // (the empty second slot adds +0)
+  }
+  if (valid && lg == 0) p.corr_count[w] += cnt;
+}
+
+template <typename T, int N, bool WANT_NZ>
+static hipError_t launch_shift_ensemble_t(const PivParams& p, hipStream_t s) {
+  using G = Geo<N>;
+  constexpr uint32_t jobs_per_block = WAVES_PER_BLOCK * G::GROUPS;
+  const uint32_t blocks = (p.n_win + jobs_per_block - 1) / jobs_per_block;
+  hipLaunchKernelGGL((piv_fft_shift_ensemble_kernel<T, N, WANT_NZ>), dim3(blocks), dim3(BLOCK), G::LDS_BYTES, s, p);
+  return hipGetLastError();
+}
+template <int N>
+static hipError_t launch_shift_ensemble(const PivParams& p, int dtype, hipStream_t s) {
+  static_assert(Geo<N>::FULL && N % 16 == 0, "shifted passes are 16, 32 or 64 px");
+  if (p.wy != N || p.wx != N || p.nw != 0 || p.n_win == 0 || p.n_pairs == 0 || p.H < N || p.W < N || !p.corr_sum || !p.corr_count || !p.cmax || !p.s2n)
+    return hipErrorInvalidValue;
+  const bool nz = p.signal_threshold >= 0.0f;
+  switch (dtype) {
+    case 0: return nz ? launch_shift_ensemble_t<uint8_t, N, true>(p, s) : launch_shift_ensemble_t<uint8_t, N, false>(p, s);
+    case 1: return nz ? launch_shift_ensemble_t<float, N, true>(p, s) : launch_shift_ensemble_t<float, N, false>(p, s);
+    case 2: return nz ? launch_shift_ensemble_t<double, N, true>(p, s) : launch_shift_ensemble_t<double, N, false>(p, s);
+    default: return hipErrorInvalidValue;
+  }
 }
 
 // Walking ENSEMBLE kernel: the same iteration, but the planes are masked (corr_min, s2n_min, finite) and added to the

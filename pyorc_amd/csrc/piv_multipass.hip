@@ -1,11 +1,12 @@
 // Multi-pass PIV (gfx950): what runs BETWEEN the passes of a chain.
 //
 // A coarse pass predicts the displacement; the next, finer pass cuts its window of frame t+1 at an integer offset from that
-// prediction (the shifted kernels, piv_fft_impl.h) and measures the residual.  Two small kernels, both one thread per (pair, window):
+// prediction (the shifted kernels, piv_fft_impl.h) and measures the residual.  Small kernels, one thread per (pair, window):
 //   predict_shift_kernel   (u, v) of pass k on its grid -> int16 offsets (dy, dx) on the grid of pass k + 1.  After the first step
 //                          (rint of every vector) it is exact integer arithmetic, so that a float64 reference on the host gives the
 //                          very same integers: median of the rounded vectors over the 3 x 3 neighbourhood, bilinear interpolation
 //                          between the coarse window centres with integer weights, one rounding division, the frame clamp.
+//   clamp_shift_kernel     the offset field of a shifted ensemble handle -> its clamped values (window_shift), in place.
 //   add_shift_kernel       u += clamped dx, v += clamped dy after the rescue pass: the kernels and the rescue pass write the residual.
 // All of it in the kernels' native orientation (u = column shift, v = row shift, rows downward); the "v_sign" option is applied to
 // the final result only.
@@ -125,7 +126,24 @@ __global__ __launch_bounds__(MBLOCK) void add_shift_kernel(PivParams p) {
   if (ws.dy != 0) p.v[g] = p.v[g] + (float)ws.dy;
 }
 
+// shifted ensemble pass: the offset field of a handle (n_win x {dy, dx}, p.n_tiles = p.n_win) replaced by its clamped values -- through
+// window_shift, so that what lspiv_ensemble_get_shift hands out is what the kernels use.  In place: a thread reads and writes its own entry.
+__global__ __launch_bounds__(MBLOCK) void clamp_shift_kernel(PivParams p, int16_t* out) {
+  const uint32_t g = blockIdx.x * MBLOCK + threadIdx.x;
+  if (g >= p.n_win) return;
+  const uint32_t wrow = p.div_ncols.div(g), wcol = g - wrow * (uint32_t)p.n_cols;
+  const WinShift ws = window_shift(p, g, wrow, wcol);
+  out[2 * (size_t)g] = (int16_t)ws.dy;
+  out[2 * (size_t)g + 1] = (int16_t)ws.dx;
+}
+
 }  // namespace
+
+hipError_t launch_clamp_shift(const PivParams& p, int16_t* out, hipStream_t s) {
+  if (!p.shift || !out || p.n_win == 0) return hipSuccess;
+  hipLaunchKernelGGL(clamp_shift_kernel, dim3((p.n_win + MBLOCK - 1) / MBLOCK), dim3(MBLOCK), 0, s, p, out);
+  return hipGetLastError();
+}
 
 hipError_t launch_predict_shift(const float* u, const float* v, uint32_t n_pairs, int H, int W, const PassGrid& coarse, const PassGrid& fine,
                                 int16_t* shift, hipStream_t s) {

@@ -241,7 +241,7 @@ __device__ __forceinline__ const T* window_base(const PivParams& p, uint32_t g) 
 }
 
 // the window of frame t+1 of result g: one frame on, and -- multi-pass mode -- at the window's clamped offset (common.h, window_shift).
-// (The ensemble's partial sums below keep A + frame_elems: ensemble mode has no shifted pass.)
+// (The ensemble's partial sums below index the offsets by the window alone: a shifted ensemble pass has one field for every pair.)
 template <typename T>
 __device__ __forceinline__ const T* window_base_b(const PivParams& p, uint32_t g, const T* A) {
   const T* B = A + p.frame_elems;
@@ -570,6 +570,11 @@ __global__ __launch_bounds__(RBLOCK) void ens_partial_kernel(PivParams p, EnsRes
       if (!(a.cmax[(size_t)pair * p.n_win + rw] > 0.0f)) continue;   // not in the sum (uniform over the wave)
       const T* A = window_base<T>(p, pair * p.n_win + rw);
       const T* B = A + p.frame_elems;
+      if (p.shift) {   // shifted ensemble pass: frame t+1's window at the window's clamped offset, the same for every pair
+        const uint32_t wrow = rw / (uint32_t)p.n_cols, wcol = rw - wrow * (uint32_t)p.n_cols;
+        const WinShift ws = window_shift(p, rw, wrow, wcol);
+        B += (int64_t)ws.dy * p.W + ws.dx;
+      }
       double mean_a, sd_a, mean_b, sd_b;
       if (staged) window_stats_wave2<T, true>(A, B, p.W, wy, wx, lane, mean_a, sd_a, mean_b, sd_b, la, lb);
       else window_stats_wave2<T, false>(A, B, p.W, wy, wx, lane, mean_a, sd_a, mean_b, sd_b, nullptr, nullptr);

@@ -1,8 +1,12 @@
-// The 32 x 32 window of frame t against the 32 x 32 window of frame t+1 at a per-window integer offset (piv_fft_impl.h, "shifted kernel").
+// The 32 x 32 window of frame t against the 32 x 32 window of frame t+1 at a per-window integer offset (piv_fft_impl.h, "shifted kernel"),
+// per pair (multi-pass PIV) and summed over the pairs of a run (multi-pass ensemble, "shifted ensemble kernel").
 #include "piv_fft_impl.h"
 
 namespace lspiv {
 hipError_t launch_piv_shift32(const PivParams& p, int dtype, hipStream_t s) {
   return launch_shift<32>(p, dtype, s);
+}
+hipError_t launch_piv_shift_ensemble32(const PivParams& p, int dtype, hipStream_t s) {
+  return launch_shift_ensemble<32>(p, dtype, s);
 }
 }  // namespace lspiv

@@ -363,11 +363,16 @@ def u_v_displacement(corr, n_rows: int, n_cols: int, engine: str = "hip") -> Tup
 class Ensemble:
     """Device-resident ensemble-correlation accumulator (pyorc/velocimetry/ffpiv.py:182-376)."""
 
-    def __init__(self, dim_size, window_size, overlap, sliding=None):
+    def __init__(self, dim_size, window_size, overlap, sliding=None, shift=None):
         """``sliding=(M, s)``: a sliding ensemble -- outputs over windows of M pairs that advance by s
-        pairs, read with :meth:`finish_sliding`; every ``accumulate`` but the last must then hold a multiple of s pairs."""
+        pairs, read with :meth:`finish_sliding`; every ``accumulate`` but the last must then hold a multiple of s pairs.
+        ``shift``: int16 ``(n_rows, n_cols, 2)`` = (dy, dx) per window, or a ``DeviceFrames`` holding those bytes -- a SHIFTED ensemble pass
+        (INTEGRATION.md section 2e): frame t+1's window of every pair is cut at that offset (clamped to the frame: :attr:`shift`), and
+        ``finish`` returns the total displacement.  Windows of 16, 32 or 64 px; not together with ``sliding``."""
         if sliding is not None:
             sliding = window.sliding_spec(True, *sliding)
+            if shift is not None:
+                raise NotImplementedError("a sliding ensemble has no shifted pass: sliding= and shift= exclude each other")
         lib = _lib.load()
         _lib.require_device()
         self._h = C.c_void_p()
@@ -386,6 +391,35 @@ class Ensemble:
         self.pairs_done = 0        # pairs accumulated so far (a sliding handle's outputs are counted from it)
         if sliding is not None:
             _lib.check(lib.lspiv_ensemble_set_sliding(self._h, sliding[0], sliding[1]))
+        self.shifted = shift is not None
+        if shift is not None:
+            try:
+                self._set_shift(shift)
+            except Exception:
+                self.close()
+                raise
+
+    def _set_shift(self, shift):
+        lib = _lib.load()
+        n_bytes = self.n_rows * self.n_cols * 4
+        if is_device(shift):
+            if shift.nbytes != n_bytes:
+                raise ValueError(f"shift on the device must hold {(self.n_rows, self.n_cols, 2)} int16 ({n_bytes} bytes), got {shift.nbytes}")
+            _lib.check(lib.lspiv_ensemble_set_shift_dev(self._h, shift.c_ptr, None))
+            return
+        sh = np.ascontiguousarray(shift, dtype=np.int16)
+        if sh.shape != (self.n_rows, self.n_cols, 2):
+            raise ValueError(f"shift must have shape {(self.n_rows, self.n_cols, 2)}, got {sh.shape}")
+        _lib.check(lib.lspiv_ensemble_set_shift(self._h, _lib.ptr(sh)))
+
+    @property
+    def shift(self):
+        """The clamped offsets the handle uses, int16 ``(n_rows, n_cols, 2)`` = (dy, dx); None on a handle without offsets."""
+        if not self.shifted:
+            return None
+        out = np.empty((self.n_rows, self.n_cols, 2), dtype=np.int16)
+        _lib.check(_lib.load().lspiv_ensemble_get_shift(self._h, _lib.ptr(out)))
+        return out
 
     RETAIN_NONE, RETAIN_COPY, RETAIN_BORROW = 0, 1, 2
 
@@ -560,6 +594,71 @@ class Ensemble:
             self.close()
         except Exception:
             pass
+
+
+def ensemble_means(corr_max, s2n, corr_count, count_min: float, n_frames: float):
+    """``corr`` / ``s2n`` of an ensemble as the reference forms them (ffpiv.py:280-286): the nanmean over the pairs of the masked per-pair
+    values ``(P, n_win)``, the windows below the count filter set to NaN in ``corr_max`` first (in place).  Returns two ``(n_win,)`` arrays."""
+    import warnings
+
+    with warnings.catch_warnings():
+        warnings.simplefilter("ignore", category=RuntimeWarning)
+        corr_max[:, np.asarray(corr_count).reshape(-1) < count_min * n_frames] = np.nan
+        return np.nanmean(corr_max, axis=0), np.nanmean(s2n, axis=0)
+
+
+def ensemble_multipass(imgs, passes, corr_min: float, s2n_min: float, count_min: float, signal_threshold: Optional[float] = None,
+                       chunks=None, return_passes: bool = False):
+    """Multi-pass ensemble correlation on one device: ``passes`` = ``[(n_0, overlap_0), ..., (n_K, overlap_K)]``
+    coarsest first (or a ``window.MultiPassWindow``).  Every pass is a full ensemble over all pairs of ``imgs`` (a host stack or a
+    ``DeviceFrames``); pass 0 is today's ensemble of its window, each later pass (16, 32 or 64 px) cuts frame t+1's windows at the integer
+    offsets the previous pass's field predicts (:func:`predict_shift`, one field for every pair) and adds them to the residual it fits.
+    ``chunks``: the frame slices ``[(f0, f1), ...]`` every pass is accumulated in (consecutive ones share a frame; None: one call); their
+    number is the ``n_frames`` of the count filter, as in the reference's chunk loop (quirk Q3).
+    Every pass but the last needs a grid of at least 3 x 3 windows (``window.ensemble_chain_spec``: NotImplementedError).
+    Returns ``(u, v, corr_count, corr, s2n)`` of the LAST pass -- ``(1, n_rows, n_cols)``, count ``(n_win,)``; "v_sign" applied to v --
+    and with ``return_passes`` a list with every pass's ``(u, v, corr_count, shift, mean planes)`` in the kernels' orientation (shift None
+    for pass 0)."""
+    spec = passes if isinstance(passes, window.MultiPassWindow) else None
+    if spec is None:
+        passes = [(int(n), int(o)) for n, o in passes]
+        if not passes:
+            raise ValueError("passes is empty")
+        spec = window.multipass_spec((passes[-1][0],) * 2, (passes[-1][1],) * 2, passes[:-1])
+        if not isinstance(spec, window.MultiPassWindow):
+            spec = window.MultiPassWindow(passes)
+    passes = list(spec.passes)
+    a = imgs if is_device(imgs) else _lib.as_frames(imgs)
+    T, H, W = a.shape
+    if T < 2:
+        raise ValueError(f"need >= 2 frames, got {a.shape}")
+    window.ensemble_chain_spec(spec, (H, W))     # NotImplementedError for a steering pass of fewer than 3 x 3 windows
+    _lib.load()
+    _lib.require_device()
+    chunks = [(0, T)] if chunks is None else [(int(f0), int(f1)) for f0, f1 in chunks]
+    if chunks[0][0] != 0 or chunks[-1][1] != T or any(f1 - f0 < 2 for f0, f1 in chunks) or any(x[1] - 1 != y[0] for x, y in zip(chunks, chunks[1:])):
+        raise ValueError(f"chunks must cover the frames 0 .. {T} in order, each at least two frames, consecutive ones sharing a frame; got {chunks}")
+    flip = _lib.get_option("v_sign") == 1
+    per, prev = [], None
+    for k, (n, ov) in enumerate(passes):
+        shift = None if k == 0 else predict_shift(prev[0], prev[1], (H, W), passes[k - 1], (n, ov))[0]
+        e = Ensemble((H, W), (n, n), (ov, ov), shift=shift)
+        try:
+            cm, sn = (np.empty((T - 1, e.n_rows * e.n_cols), dtype=np.float32) for _ in range(2))
+            for f0, f1 in chunks:
+                e.accumulate(a[f0:f1], corr_min, s2n_min, signal_threshold, out=(cm[f0:f1 - 1], sn[f0:f1 - 1]))
+            u, v, cnt, mean = e.finish(count_min, len(chunks), return_mean=True)
+            used = e.shift
+        finally:
+            e.close()
+        if flip:           # the kernels' orientation between the passes (a negation is exact)
+            v = -v
+        prev = (u, v)
+        per.append((u, v, cnt, used, mean))
+    corr, s2n = ensemble_means(cm, sn, cnt, count_min, len(chunks))
+    shape = (1, e.n_rows, e.n_cols)
+    ret = (u, -v if flip else v, cnt, corr.reshape(shape), s2n.reshape(shape))
+    return ret + (per,) if return_passes else ret
 
 
 def ensemble_allreduce(ensembles) -> None:

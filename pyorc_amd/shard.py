@@ -132,6 +132,9 @@ def sharded_ensemble(load_frames: Callable[[int, int], np.ndarray], n_pairs: int
     ens = make_ensemble()
     if getattr(ens, "sliding", None) is not None:
         raise NotImplementedError("a sliding ensemble (sliding=(M, s)) is not implemented for pyorc_amd.shard: its outputs span the ranks' pair blocks")
+    if getattr(ens, "shifted", False):
+        raise NotImplementedError("a shifted ensemble pass (coarse_passes with ensemble_corr=True) is not implemented for pyorc_amd.shard: run the "
+                                  "chain through get_ffpiv (devices=)")
     f0, f1 = frame_block(n_pairs, comm.rank, comm.world, align)
     if f1 - f0 >= 2:
         cm, sn = ens.accumulate(load_frames(f0, f1), corr_min, s2n_min, signal_threshold)

@@ -207,15 +207,18 @@ def get_ffpiv(
     an int n (window n x n at overlap n / 2) or a pair ``(n, overlap)``, run before the final pass ``window_size`` / ``overlap`` (16, 32 or
     64 px), whose grid is the result's.  Every pass after the first cuts its window of frame t+1 at the integer offset the previous pass
     predicts.  None or empty: today's path.  Chunks are cut on the anchors of pass 0; ``devices=`` and ``chunksize=`` give the same bits.
-    Per-timestep mode without a search area of its own.
+    Without a search area of its own.  With ``ensemble_corr=True`` every pass is a full ensemble over all
+    pairs and ONE field steers the next pass's windows: the passes are the outer loop, the chunk loop the inner one; materialised
+    stacks (numpy, ``DeviceFrames``), not together with ``ensemble_window``, and every pass that steers another one needs a grid of at
+    least 3 x 3 windows (``window.ensemble_chain_spec``).
     """
     if engine != "hip":
         raise ValueError(f"Selected PIV engine {engine} does not exist.")
     # a search area of its own: one window argument that answers for the search area wherever a grid, a plan or an alignment is asked for
     window_size = window.search_spec(window_size, search_area_size)
     if coarse_passes is not None and len(coarse_passes):
-        if ensemble_corr:
-            raise NotImplementedError("coarse_passes with ensemble_corr=True is not implemented: the shifted kernels serve per-timestep mode only")
+        if ensemble_corr and ensemble_window is not None:
+            raise NotImplementedError("coarse_passes together with ensemble_window is not implemented: a sliding ensemble has no shifted pass")
         if isinstance(window_size, window.SearchWindow):
             raise NotImplementedError("coarse_passes together with a search_area_size larger than the window is not implemented")
         window_size = window.multipass_spec(window_size, overlap, coarse_passes)   # ValueError for an unsupported chain
@@ -231,7 +234,14 @@ def get_ffpiv(
     if sliding is not None:
         return _get_ffpiv_sliding(frames, y, x, dt, window_size, overlap, res_y, res_x, chunksize, memory_factor, engine, corr_min, s2n_min,
                                   count_min, signal_threshold, time, prefetch, devices, sliding, n_frames, dim_size, dtype)
-    _, ref_slices, slices = _plan_slices(n_frames, dim_size, window_size, overlap, dtype, chunksize, memory_factor, engine, n_win)
+    chain = ensemble_corr and isinstance(window_size, window.MultiPassWindow)     # multi-pass ensemble
+    if chain and _is_lazy(frames):
+        raise NotImplementedError("coarse_passes with ensemble_corr=True and a lazy stack is not implemented: load the stack (numpy or "
+                                  "DeviceFrames) first -- every pass reads the whole video, a lazy one would be computed once per pass")
+    if chain:
+        window.ensemble_chain_spec(window_size, dim_size)     # NotImplementedError for a steering pass of fewer than 3 x 3 windows
+    _, ref_slices, slices = _plan_slices(n_frames, dim_size, window_size, overlap, dtype, chunksize, memory_factor, engine, n_win,
+                                         ensemble_sums=chain)
     if time is None:
         time = frames["time"] if _is_xr(frames) else np.arange(n_frames)
     dt_arr = np.asarray(_values(dt), dtype=np.float64)
@@ -248,13 +258,38 @@ def get_ffpiv(
     else:
         work = device_work(n_frames, slices, devs, align, stack_mode,
                            lambda a, b, d, cnt: _plan_slices(b - a + 1, dim_size, window_size, overlap, dtype, chunksize, memory_factor,
-                                                             engine, n_win, d, cnt)[2])
+                                                             engine, n_win, d, cnt, ensemble_sums=chain)[2])
+    if chain:
+        return _run_ensemble_chain(frames, work, devs, time, window_size, dim_size, y, x, dt_arr, res_x, res_y, signal_threshold, corr_min,
+                                   s2n_min, count_min, ref_slices)
     args = (n_frames - 1, len(work), y, x, dt_arr, res_x, res_y, window_size, overlap, signal_threshold)
     sink = _ensemble_sink(*args, corr_min, s2n_min, count_min, ref_slices) if ensemble_corr else _timestep_sink(*args)
     if resident_run:
         return _run_resident(frames, work, sink, devs, time, signal_threshold)
     depth = (executor.default_depth() if prefetch is None else int(prefetch)) if hasattr(frames, "load") else 0
     return _run_chunks(frames, work, sink, depth, devs, time, window_size, overlap, (n_rows, n_cols))
+
+
+def _run_ensemble_chain(frames, work, devices, time, spec, dim_size, y, x, dt, res_x, res_y, signal_threshold, corr_min, s2n_min, count_min,
+                        ref_slices):
+    """The multi-pass ensemble: the passes of ``spec`` are the outer loop, the chunk loop of the ensemble sink
+    over ``work`` -- ONE chunk plan for the whole chain, cut on pass 0's anchors -- the inner one.  Every pass is accumulated per device
+    worker, all-reduced and finished as the plain ensemble is; its field, in the kernels' orientation, goes through the predictor and the
+    resulting offsets (a few KB, through the host) are set on every worker's handle of the next pass.  The last pass's sink builds the
+    result on the coordinates ``y``, ``x``."""
+    n_pairs = len(dt)
+    prev = out = None
+    for k, (n, ov) in enumerate(spec.passes):
+        ws, ovk = (n, n), (ov, ov)
+        last = k == len(spec.passes) - 1
+        grid = (len(y), len(x)) if last else tuple(window.get_array_shape(dim_size, ws, ovk))
+        shift = None if k == 0 else piv.predict_shift(prev[0], prev[1], dim_size, spec.passes[k - 1], (n, ov))[0]
+        yk, xk = (y, x) if last else (np.arange(grid[0]), np.arange(grid[1]))
+        sink = _ensemble_sink(n_pairs, len(work), yk, xk, dt, res_x, res_y, ws, ovk, signal_threshold, corr_min, s2n_min, count_min, ref_slices,
+                              shift=shift, field_only=not last)
+        out = _run_chunks(frames, work, sink, 0, devices, time, ws, ovk, grid)
+        prev = out
+    return out
 
 
 def sliding_labels(time, dt, M: int, s: int, n_out: int):
@@ -362,12 +397,15 @@ def device_work(n_frames: int, slices, devices, align: int, whole_chunks: bool, 
     return out
 
 
-def _plan_slices(n_frames, dim_size, window_size, overlap, dtype, chunksize, memory_factor, engine, n_win, device=None, share=1):
+def _plan_slices(n_frames, dim_size, window_size, overlap, dtype, chunksize, memory_factor, engine, n_win, device=None, share=1,
+                 ensemble_sums=False):
     """The chunk plan of :func:`get_ffpiv` for ``n_frames`` frames against the HBM of ``device`` (None: the calling thread's) that
     ``share`` workers divide -> (chunksize, the reference planner's slices -- quirk Q3 counts them --, the slices launched: on the
-    anchors, :func:`aligned_slices`)."""
+    anchors, :func:`aligned_slices`).  ``ensemble_sums``: the plane sums of an ensemble stay in HBM next to every chunk (the multi-pass
+    ensemble counts them, for its largest pass)."""
     def need(n):   # HBM bytes of one launch on n frames
-        return window.required_memory(n_frames=n, dim_size=dim_size, window_size=window_size, overlap=overlap, dtype=dtype)
+        return window.required_memory(n_frames=n, dim_size=dim_size, window_size=window_size, overlap=overlap, dtype=dtype,
+                                      ensemble_sums=ensemble_sums)
 
     req = need(n_frames)
     with executor.on_device(device):
@@ -480,18 +518,20 @@ def _timestep_sink(n_pairs, n_workers, y, x, dt, res_x, res_y, window_size, over
 
 
 def _ensemble_sink(n_pairs, n_workers, y, x, dt, res_x, res_y, window_size, overlap, signal_threshold, corr_min, s2n_min, count_min,
-                   ref_slices):
+                   ref_slices, shift=None, field_only=False):
     """Ensemble correlation (pyorc/velocimetry/ffpiv.py:182-376): every device worker accumulates its pairs into an ``Ensemble`` handle
     of its own (corr_sum / corr_count stay in HBM); the masked per-pair corr_max / s2n of the whole run are allocated once and every
     launch writes its time slice (the ``out`` of ``Ensemble.accumulate``).  One handle finishes as it always has; several are reduced
-    device to device (``piv.ensemble_allreduce``) and finished with every device's float64 rescue (``shard.staged_finish``)."""
+    device to device (``piv.ensemble_allreduce``) and finished with every device's float64 rescue (``shard.staged_finish``).
+    A pass of a multi-pass ensemble (:func:`_run_ensemble_chain`): ``shift`` (n_rows, n_cols, 2) makes the handles shifted ones
+    with these offsets; ``field_only``: the result is the pass's ``(u, v)`` in pixels and in the kernels' orientation, for the predictor."""
     full = {k: np.empty((n_pairs, len(y) * len(x)), dtype=np.float32) for k in ("corr", "s2n")}
     done = []
     handles = [None] * n_workers
 
     def launch(k, frames, p0, p1):
         if handles[k] is None:   # made on the worker's thread: on the worker's device
-            handles[k] = piv.Ensemble(tuple(frames.shape[1:]), window_size, overlap)
+            handles[k] = piv.Ensemble(tuple(frames.shape[1:]), window_size, overlap, **({} if shift is None else {"shift": shift}))
         handles[k].accumulate(frames, corr_min, s2n_min, signal_threshold, out=(full["corr"][p0:p1], full["s2n"][p0:p1]))
         done.append((p0, p1))
 
@@ -522,6 +562,10 @@ def _ensemble_sink(n_pairs, n_workers, y, x, dt, res_x, res_y, window_size, over
             with executor.on_device(getattr(live[0], "device", None)):
                 piv.ensemble_allreduce(live)
             u, v, corr_count = shard.staged_finish(live, count_min, n_chunks)
+        if field_only:
+            from . import _lib
+
+            return u, (-v if _lib.get_option("v_sign") == 1 else v)      # (a negation is exact)
         with warnings.catch_warnings():
             warnings.simplefilter("ignore", category=RuntimeWarning)
             # very low amounts of found valid correlations are entirely filtered out (ffpiv.py:280-286)

@@ -130,6 +130,25 @@ def multipass_spec(window_size, overlap, coarse_passes=None):
     return MultiPassWindow(passes)
 
 
+MIN_STEERING_GRID = 3
+
+
+def ensemble_chain_spec(spec: MultiPassWindow, dim_size) -> MultiPassWindow:
+    """``spec`` as a chain of ENSEMBLES on frames of ``dim_size``, or NotImplementedError: every pass that
+    steers another one needs a grid of at least 3 x 3 windows.  One field of such a pass moves a window of the next pass for EVERY
+    pair of the run, and the predictor's 3 x 3 median is all that keeps a stray ensemble vector out of it: on one or two windows per
+    side that median is the vector itself, or the mean of two.  (The per-timestep chain, section 2d, predicts per pair and takes any
+    grid.)  Host-only."""
+    for k, (n, o) in enumerate(spec.passes[:-1]):
+        rows, cols = get_array_shape(dim_size, (n, n), (o, o))
+        if min(rows, cols) < MIN_STEERING_GRID:
+            raise NotImplementedError(f"coarse_passes with ensemble_corr=True is not implemented for a steering pass of fewer than "
+                                      f"{MIN_STEERING_GRID} x {MIN_STEERING_GRID} windows (pass {k}: {n} px at overlap {o} gives {rows} x {cols} "
+                                      f"on a {dim_size[0]} x {dim_size[1]} frame): its one field steers every pair of the run, and the "
+                                      "predictor's 3 x 3 median has no neighbourhood there to reject a stray vector with")
+    return spec
+
+
 def get_axis_shape(dim_size: int, window_size: int, overlap: int) -> int:
     nr, nc = C.c_int64(), C.c_int64()
     _lib.check(_lib.load().lspiv_grid_shape(dim_size, dim_size, window_size, window_size, overlap, overlap,
@@ -159,7 +178,8 @@ def get_rect_coordinates(dim_size, window_size, overlap, search_area_size=None, 
 
 
 def required_memory(n_frames: int, dim_size, window_size, overlap, search_area_size=None,
-                    dtype=np.uint8, with_planes: bool = False, sliding_blocks: int = 0, coarse_passes=None) -> int:
+                    dtype=np.uint8, with_planes: bool = False, sliding_blocks: int = 0, coarse_passes=None,
+                    ensemble_sums: bool = False) -> int:
     """HBM bytes one fused call on ``n_frames`` frames needs (frames + four result planes).
 
     The reference's figure is the host RAM of the materialised window stack + correlation volume
@@ -167,6 +187,8 @@ def required_memory(n_frames: int, dim_size, window_size, overlap, search_area_s
 
     ``sliding_blocks``: the blocks of a sliding ensemble's WHOLE run (:func:`sliding_outputs`); its block store stays in HBM next
     to every chunk (:func:`sliding_store_bytes`).  ``coarse_passes`` (or a :class:`MultiPassWindow`): a multi-pass chain.
+    ``ensemble_sums``: an ensemble's plane sums and counts (:func:`ensemble_sums_bytes`) stay in HBM next to every chunk -- of the pass
+    that needs most, in a chain (the multi-pass ensemble, INTEGRATION.md section 2e, runs one pass at a time).
     """
     if coarse_passes or isinstance(window_size, MultiPassWindow):
         # a chain: the frames once, the largest pass's launch (results, rescue lists, the planes of the final pass), and the
@@ -177,7 +199,8 @@ def required_memory(n_frames: int, dim_size, window_size, overlap, search_area_s
         per_pass = [required_memory(n_frames, dim_size, (n, n), (o, o), dtype=dtype, with_planes=with_planes and k == last) - frames_bytes
                     for k, (n, o) in enumerate(spec.passes)]
         tiles = [(int(n_frames) - 1) * int(np.prod(get_array_shape(dim_size, (n, n), (o, o)))) for n, o in spec.passes]
-        return frames_bytes + max(per_pass) + 2 * 16 * max(tiles[:-1]) + 4 * max(tiles[1:])
+        sums = max(ensemble_sums_bytes(dim_size, (n, n), (o, o)) for n, o in spec.passes) if ensemble_sums else 0
+        return frames_bytes + max(per_pass) + 2 * 16 * max(tiles[:-1]) + 4 * max(tiles[1:]) + sums
     sa = window_size if search_area_size is None else search_area_size
     code = _lib.DTYPE_CODES[np.dtype(dtype)]
     r = _lib.load().lspiv_required_bytes(n_frames, dim_size[0], dim_size[1], code, sa[0], sa[1],
@@ -185,7 +208,16 @@ def required_memory(n_frames: int, dim_size, window_size, overlap, search_area_s
     need = _lib.check(r)
     if sliding_blocks:
         need += sliding_store_bytes(sliding_blocks, dim_size, sa, overlap)
+    if ensemble_sums:
+        need += ensemble_sums_bytes(dim_size, sa, overlap)
     return need
+
+
+def ensemble_sums_bytes(dim_size, window_size, overlap) -> int:
+    """HBM bytes of an ensemble handle's running state: one float32 plane sum and one count per window, and the window offsets of a
+    shifted handle (2 x int16)."""
+    n_win = int(np.prod(get_array_shape(dim_size, window_size, overlap)))
+    return n_win * (int(window_size[0]) * int(window_size[1]) + 2) * 4
 
 
 def sliding_spec(ensemble_corr: bool, ensemble_window, ensemble_stride):

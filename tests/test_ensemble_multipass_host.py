@@ -1,0 +1,165 @@
+"""Multi-pass ensemble, host side (CPU): the reference (tests/ensemble_multipass_ref.py) against the oracle's
+own ensemble at zero offsets, the value of the feature on the reference alone, the CPU checks of every input
+tests/test_gpu_ensemble_multipass.py relies on (tie shares, per-pair values next to a mask threshold, counts on the count threshold,
+coarse vectors next to a half-integer), the argument errors, and the planner."""
+import numpy as np
+import pytest
+
+from oracle import piv_oracle as po
+from pyorc_amd import frames, piv, shard, velocimetry, window
+from tests import ensemble_multipass_ref as ref
+from tests import lazy_doubles
+from tests import multipass_ref as mp
+from tests.test_multipass_host import near_half_dependents
+
+
+# ---- the reference ------------------------------------------------------------------------------------------------------------------------
+def test_reference_with_zero_offsets_is_the_oracles_ensemble():
+    a = ref.pass_stack(32)
+    n, ov, (H, W) = ref.PASS_CASES[32]
+    want = po.get_ffpiv(a, np.ones(len(a) - 1), (n, n), (ov, ov), 1.0, 1.0, ensemble_corr=True, signal_threshold=0.05, **ref.KW)
+    rows, cols = ref.grid_shape(32)
+    for shift in (None, np.zeros((rows, cols, 2), np.int16)):
+        with po.semantics(v_sign=0):
+            r = ref.ensemble_pass(a, n, ov, shift, signal_threshold=0.05, **ref.KW)
+        assert np.array_equal(r["planes"], want["corr_mean"], equal_nan=True)
+        assert np.array_equal(r["u"].astype(np.float32), want["v_x"], equal_nan=True)
+        assert np.array_equal(r["v"].astype(np.float32), want["v_y"], equal_nan=True)
+        assert np.array_equal(r["corr"], want["corr"], equal_nan=True) and np.array_equal(r["s2n"], want["s2n"], equal_nan=True)
+        assert not r["shift"].any()
+
+
+def test_reference_adds_the_clamped_offset_to_the_residual():
+    n, ov, dim = ref.PASS_CASES[16]
+    r = ref.pass_ref(16, shift="far", kw="OPEN")
+    assert np.array_equal(r["shift"], mp.clamp_shift(ref.far_shift(16), dim, n, ov))
+    again = ref.ensemble_pass(ref.pass_stack(16), n, ov, r["shift"], **ref.OPEN_KW)
+    for k in ("u", "v", "planes", "count"):
+        assert np.array_equal(again[k], r[k], equal_nan=True), k
+
+
+# ---- the value of the feature, on the reference alone -------------------------------------------------------------------------------------
+def test_the_ensemble_chain_recovers_what_the_plain_16_px_ensemble_loses():
+    """particle_stack(7, 160, 200, seed=5, density=0.012, uniform_shift=(9.3, -6.4)), six pairs, the ensemble's default masks, final window
+    16 @ 8.  Measured on the reference: plain 16 x 16 ensemble 0 % of the windows within 0.5 px of the truth; ensemble chain 64 @ 32 ->
+    16 @ 8 95.2 % (0.9 % NaN, median error 0.15 px); 64 @ 32 -> 32 @ 16 -> 16 @ 8 the same 95.2 %."""
+    assert ref.within_half_px(ref.river_plain()) == 0.0
+    for name in ref.CHAINS:
+        last = ref.river_chain(name)[-1]
+        share = ref.within_half_px(last)
+        print(name, share, float(np.isnan(last["u"]).mean()), float(np.nanmedian(np.hypot(last["u"] - ref.TRUTH[0], last["v"] - ref.TRUTH[1]))))
+        assert share >= 0.90
+
+
+# ---- the inputs the GPU tests rely on -----------------------------------------------------------------------------------------------------
+def input_is_clear_of_the_caps(r, corr_min, s2n_min, count_min, n_frames=1, name=""):
+    """What lets the reference alone stay inside the caps: ties on at most 1 % of the windows, no per-pair corr_max / s2n within 1e-3
+    (relative) of its threshold, no window's count on the count threshold."""
+    assert r["tie"].mean() <= 0.01, (name, float(r["tie"].mean()))
+    cm, sn = r["pair_corr"], r["pair_s2n"]
+    with np.errstate(invalid="ignore"):
+        assert not (np.abs(cm - corr_min) <= 1e-3 * corr_min).any(), name
+        assert not (np.abs(sn - s2n_min) <= 1e-3 * s2n_min).any(), name
+    assert not (np.abs(r["count"] - count_min * n_frames) < 1e-6).any(), name
+
+
+def test_pass_inputs_are_clear_of_the_caps():
+    for n in ref.PASS_CASES:
+        for T in ref.PASS_FRAMES:
+            for dtype in ref.PASS_DTYPES:
+                r = ref.pass_ref(n, T, dtype)
+                input_is_clear_of_the_caps(r, **ref.KW, name=(n, T, dtype))
+                assert np.isfinite(r["u"]).mean() > 0.9                       # most planes are kept under the lowered masks
+                assert (r["count"] >= T - 2).mean() > 0.9
+        sh = ref.hand_shift(n)
+        assert np.array_equal(ref.pass_ref(n)["shift"], sh)                   # inside the frame already
+        assert len({tuple(q) for q in sh.reshape(-1, 2)}) >= 4                # different offsets per window
+        input_is_clear_of_the_caps(ref.pass_ref(n, shift="far", kw="OPEN"), **ref.OPEN_KW, name=(n, "far"))
+        input_is_clear_of_the_caps(ref.pass_ref(n, shift=None), **ref.KW, name=(n, "zero"))
+        far = ref.pass_ref(n, shift="far", kw="OPEN")["shift"]
+        assert np.abs(far).max() <= max(ref.PASS_CASES[n][2]) and (far != ref.far_shift(n)).all()
+
+
+def test_mask_and_rescue_inputs_are_clear_of_the_caps():
+    r = ref.signal_ref()
+    input_is_clear_of_the_caps(r, **ref.KW, name="signal")
+    below = np.isnan(r["pair_corr"])
+    plain = np.isnan(ref.ensemble_pass(ref.signal_stack(), 32, 16, None, signal_threshold=ref.SIGNAL_THR, **ref.KW)["pair_corr"])
+    print("pairs below the threshold:", float(below.mean()), "differently with zero offsets:", int((below != plain).sum()))
+    assert 0.02 < below.mean() < 0.9 and (below != plain).any()              # the score is the SHIFTED window's
+    assert np.isnan(r["u"]).any() and np.isfinite(r["u"]).any()
+    r = ref.speckle_ref()
+    input_is_clear_of_the_caps(r, **ref.KW, name="speckle")
+    assert np.array_equal(r["shift"], ref.speckle_shift())
+
+
+def test_chain_inputs_are_clear_of_the_caps_and_of_half_integers():
+    for name, chain, passes, kw, a in [(k, ref.CHAINS[k], ref.river_chain(k), ref.DEFAULT_KW, ref.river_stack()) for k in ref.CHAINS] + \
+                                     [("blanked", ref.CHAINS["64"], ref.blanked_chain(), ref.COUNT_KW, ref.blanked_stack())]:
+        for k, r in enumerate(passes):
+            input_is_clear_of_the_caps(r, **kw, name=(name, k))
+            if k + 1 < len(passes):
+                dep = near_half_dependents(r["u"], r["v"], a.shape[1:], chain[k], chain[k + 1])
+                assert not dep.any(), (name, k, float(dep.mean()))
+    coarse, fine = ref.blanked_chain()
+    assert np.isnan(coarse["u"]).any() and np.isfinite(coarse["u"]).any()    # the predictor has to skip vectors
+    assert np.isnan(fine["u"]).mean() > 0.1 and (fine["count"] == 0).any()
+
+
+# ---- validation ---------------------------------------------------------------------------------------------------------------------------
+def test_what_the_ensemble_chain_still_refuses(lib):
+    a = np.zeros((3, 96, 96), np.uint8)
+    run = lambda f=a, **kw: velocimetry.get_ffpiv(f, np.arange(11), np.arange(11), np.ones(2), (16, 16), (8, 8), kw.pop("sa", (16, 16)), 1.0, 1.0,
+                                                  ensemble_corr=True, **kw)
+    with pytest.raises(NotImplementedError, match="coarse_passes together with ensemble_window is not implemented"):
+        run(coarse_passes=[64], ensemble_window=2)
+    with pytest.raises(NotImplementedError, match="coarse_passes together with a search_area_size"):
+        velocimetry.get_ffpiv(a, np.arange(3), np.arange(3), np.ones(2), (12, 12), (16, 16), (32, 32), 1.0, 1.0, coarse_passes=[64],
+                              ensemble_corr=True)
+    with pytest.raises(NotImplementedError, match="lazy stack is not implemented: load the stack"):
+        run(lazy_doubles.from_frames(a, block=2), coarse_passes=[64])
+    # a steering pass of fewer than 3 x 3 windows (64 @ 32 on 96 x 96: 2 x 2; 32 @ 16 on 160 x 60: 9 x 2): refused before any GPU work
+    with pytest.raises(NotImplementedError, match=r"not implemented for a steering pass of fewer than 3 x 3 windows \(pass 0: 64 px .* 2 x 2"):
+        run(coarse_passes=[64])
+    with pytest.raises(NotImplementedError, match=r"pass 1: 32 px at overlap 16 gives 9 x 2"):
+        piv.ensemble_multipass(np.zeros((3, 160, 60), np.uint8), [(40, 30), (32, 16), (16, 8)], 0.2, 3.0, 0.2)
+    spec3 = window.multipass_spec((16, 16), (8, 8), [64])
+    assert window.ensemble_chain_spec(spec3, (128, 128)) is spec3          # 3 x 3: the smallest grid that steers
+    with pytest.raises(ValueError, match=r"\(16, 32, 64\)"):
+        run(coarse_passes=[64, 48])
+    with pytest.raises(ValueError, match=r"\(16, 32, 64\)"):
+        frames.get_piv(a, 24, coarse_passes=[64], ensemble_corr=True)
+
+    class Shifted:
+        sliding, shifted = None, True
+
+    class Comm:
+        rank, world = 0, 1
+
+    with pytest.raises(NotImplementedError, match="shifted ensemble pass .* is not implemented for pyorc_amd.shard"):
+        shard.sharded_ensemble(lambda f0, f1: a[f0:f1], 2, Shifted, 0.2, 3.0, 0.2, Comm())
+    with pytest.raises(ValueError, match="passes is empty"):
+        piv.ensemble_multipass(a, [], 0.2, 3.0, 0.2)
+    with pytest.raises(ValueError, match=r"pass 1: window 24 is not supported.*\(16, 32, 64\)"):
+        piv.ensemble_multipass(a, [(64, 32), (24, 12)], 0.2, 3.0, 0.2)
+
+
+def test_new_symbols_are_in_the_library(lib):
+    for name in ("lspiv_ensemble_set_shift", "lspiv_ensemble_set_shift_dev", "lspiv_ensemble_get_shift"):
+        assert hasattr(lib, name), name
+    assert lib.lspiv_abi_version() == 5
+
+
+def test_planner_counts_the_ensemble_sums_of_the_largest_pass(lib):
+    dim, T = (160, 200), 10
+    spec = window.multipass_spec((16, 16), (8, 8), [64, 32])
+    chain = window.required_memory(T, dim, spec, (8, 8))
+    with_sums = window.required_memory(T, dim, spec, (8, 8), ensemble_sums=True)
+    sums = [window.ensemble_sums_bytes(dim, (n, n), (o, o)) for n, o in spec.passes]
+    n_win = [int(np.prod(window.get_array_shape(dim, (n, n), (o, o)))) for n, o in spec.passes]
+    assert sums == [w * (n * n + 2) * 4 for w, (n, _) in zip(n_win, spec.passes)]
+    assert with_sums - chain == max(sums) > 0
+    assert with_sums == window.required_memory(T, dim, (16, 16), (8, 8), coarse_passes=[64, 32], ensemble_sums=True)
+    plain = window.required_memory(T, dim, (32, 32), (16, 16))
+    assert window.required_memory(T, dim, (32, 32), (16, 16), ensemble_sums=True) - plain == sums[1]
+    assert window.required_memory(T, dim, (32, 32), (16, 16), ensemble_sums=False) == plain
