@@ -41,7 +41,9 @@ extern "C" {
                                * lspiv_piv_search_pairs_dev_at and lspiv_search_supported; the sliding ensemble, lspiv_ensemble_set_sliding /
                                * lspiv_ensemble_sliding_reserve / lspiv_ensemble_sliding_finish; the multi-pass ensemble, lspiv_ensemble_set_shift /
                                * _set_shift_dev / _get_shift; multi-pass PIV, lspiv_shift_supported /
-                               * lspiv_piv_shift_pairs_dev_at / lspiv_piv_predict_shift_dev / lspiv_piv_multipass_dev_at / lspiv_piv_multipass_at)
+                               * lspiv_piv_shift_pairs_dev_at / lspiv_piv_predict_shift_dev / lspiv_piv_multipass_dev_at / lspiv_piv_multipass_at; window deformation passes,
+                               * lspiv_deform_supported / lspiv_deform_required_bytes / lspiv_piv_predict_deform_dev /
+                               * lspiv_piv_deform_pairs_dev_at / lspiv_piv_multipass_deform_dev_at / lspiv_piv_multipass_deform_at)
                                * 5 (round 6): lspiv_chunk_alignment(wy, wx) without a grid now returns the alignment that is right on EVERY grid (75
                                * where it returned 25: callers that cut chunks on it stay bit-reproducible on large grids); additions:
                                * lspiv_upload_frames, lspiv_trace / lspiv_trace_read; the host-pointer projection entry points no longer
@@ -272,6 +274,46 @@ int lspiv_piv_multipass_dev_at(const void* d_frames, int dtype, int64_t T, int64
 int lspiv_piv_multipass_at(const void* frames, int dtype, int64_t T, int64_t H, int64_t W,
                            int n_passes, const int* passes, float signal_threshold, int64_t pair_offset,
                            float* u, float* v, float* corr_max, float* s2n, float* corr_planes, int16_t* shift_out);
+
+/* Window deformation passes (the project's own semantics, unpinned): after a chain, D passes on the FINAL grid,
+ * each between frame t and frame t+1 WARPED by the field of the pass before it at 1 / 64 px, so that the pass measures a residual of
+ * sub-pixel size on windows whose inner velocity gradient is taken out.  Kernel orientation throughout; "v_sign" once, at the end.
+ * Option "norm_clip" = 0 and "signal_mode" = 1 are LSPIV_EUNSUPPORTED.  Window: square, 16 / 32 / 64, the same overlap on both axes.
+ *
+ * lspiv_deform_supported: 1 for wy = wx in {16, 32, 64}, else 0.  Host-only.
+ * lspiv_deform_required_bytes: the HBM a pass takes next to the frames and results: the warped frames of one batch of pairs + the nodes.
+ *
+ * lspiv_piv_predict_deform_dev: d_u, d_v n_pairs * n_rows * n_cols float32 -> d_nodes n_pairs * n_rows * n_cols * 2 int32 {v, u} in
+ * 1 / 128 px on the same grid: q = rint(64 x) (float32, half to even) clamped to +-32767 * 64, valid when u and v are finite; node =
+ * twice the median of q over the valid vectors of the 3 x 3 neighbourhood (the median of lspiv_piv_predict_shift_dev; none valid: 0).
+ *
+ * lspiv_piv_deform_pairs_dev_at: ONE pass.  Dense field at pixel (y, x), per component, exact integers on doubled coordinates: per axis
+ * node i at c2[i] = 2 i s + n - 1, p2 = 2 y, S2 = 2 s, i0 = clamp(floor((p2 - c2[0]) / S2), 0, count - 2), w1 = clamp(p2 - c2[i0], 0, S2),
+ * w0 = S2 - w1 (constant outside the outermost nodes; one node: w1 = 0); d64 = floor((num + den) / (2 den)), num = the four corners'
+ * wy wx node, den = S2y S2x.  Warp: Y64 = clamp(64 y + dv64, 0, 64 (H - 1)), iy = Y64 >> 6, fy = Y64 & 63 (iy = H - 1: iy = H - 2, fy = 64),
+ * x likewise; B'(y, x) = the four neighbours of frame t+1 weighted (64 - fy | fy) (64 - fx | fx) / 4096 -- exact in float32 for uint8
+ * frames, a fixed order of unfused float32 products and sums otherwise (float64 samples narrowed first).  No field makes a read leave
+ * the frame.  Then the plain per-pair result of (window of frame t, the same window of B'): plane, corr_max, s2n, the signal threshold
+ * scoring both; u = float32(node.u) / 128 + residual u, v likewise (a NaN residual stays NaN).  d_nodes: (T-1) * n_win * 2 int32; d_out,
+ * d_corr_planes as lspiv_piv_pairs_dev_at.  Pair-local: pair_offset is accepted for symmetry.  The pairs run in batches through a
+ * per-device workspace: one stream at a time.
+ *
+ * lspiv_piv_multipass_deform_dev_at / _at: lspiv_piv_multipass_dev_at / _at followed by n_deform (0 .. 4) deformation passes on the last
+ * pass's grid, each fed with the (u, v) of the pass before it through lspiv_piv_predict_deform_dev.  n_deform = 0 is the plain chain, bit
+ * for bit; n_passes = 1 is allowed.  corr_max, s2n and planes are those of the last deformation pass; shift: the last CHAIN pass's. */
+int lspiv_deform_supported(int wy, int wx);
+int64_t lspiv_deform_required_bytes(int64_t T, int64_t H, int64_t W, int wy, int wx, int oy, int ox);
+int lspiv_piv_predict_deform_dev(const float* d_u, const float* d_v, int64_t n_pairs, int64_t n_rows, int64_t n_cols,
+                                 int32_t* d_nodes, void* stream);
+int lspiv_piv_deform_pairs_dev_at(const void* d_frames, int dtype, int64_t T, int64_t H, int64_t W,
+                                  int wy, int wx, int oy, int ox, float signal_threshold, int64_t pair_offset,
+                                  const int32_t* d_nodes, float* d_out, float* d_corr_planes, void* stream);
+int lspiv_piv_multipass_deform_dev_at(const void* d_frames, int dtype, int64_t T, int64_t H, int64_t W,
+                                      int n_passes, const int* passes, int n_deform, float signal_threshold, int64_t pair_offset,
+                                      float* d_out, float* d_corr_planes, int16_t* d_shift_out, void* stream);
+int lspiv_piv_multipass_deform_at(const void* frames, int dtype, int64_t T, int64_t H, int64_t W,
+                                  int n_passes, const int* passes, int n_deform, float signal_threshold, int64_t pair_offset,
+                                  float* u, float* v, float* corr_max, float* s2n, float* corr_planes, int16_t* shift_out);
 
 /* Host frames into a slice of an HBM-resident stack, the way lspiv_piv_pairs brings them in -- pinned ring, staging threads,
  * float64 narrowed to float32 with the "narrow_offset" guard (so d_dst receives n_frames * H * W samples of LSPIV_F32 for LSPIV_F64

@@ -82,6 +82,12 @@ SIGNATURES = {
     "lspiv_piv_predict_shift_dev": (_i32, [_vp, _vp, _i64, _i64, _i64, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _vp, _vp]),
     "lspiv_piv_multipass_dev_at": (_i32, [_vp, _i32, _i64, _i64, _i64, _i32, _vp, _f32, _i64, _vp, _vp, _vp, _vp]),
     "lspiv_piv_multipass_at": (_i32, [_vp, _i32, _i64, _i64, _i64, _i32, _vp, _f32, _i64, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "lspiv_deform_supported": (_i32, [_i32, _i32]),
+    "lspiv_deform_required_bytes": (_i64, [_i64, _i64, _i64, _i32, _i32, _i32, _i32]),
+    "lspiv_piv_predict_deform_dev": (_i32, [_vp, _vp, _i64, _i64, _i64, _vp, _vp]),
+    "lspiv_piv_deform_pairs_dev_at": (_i32, [_vp, _i32, _i64, _i64, _i64, _i32, _i32, _i32, _i32, _f32, _i64, _vp, _vp, _vp, _vp]),
+    "lspiv_piv_multipass_deform_dev_at": (_i32, [_vp, _i32, _i64, _i64, _i64, _i32, _vp, _i32, _f32, _i64, _vp, _vp, _vp, _vp]),
+    "lspiv_piv_multipass_deform_at": (_i32, [_vp, _i32, _i64, _i64, _i64, _i32, _vp, _i32, _f32, _i64, _vp, _vp, _vp, _vp, _vp, _vp]),
     "lspiv_u_v_displacement": (_i32, [_vp, _i64, _i64, _i32, _i32, _vp, _vp]),
     "lspiv_ensemble_begin": (_i32, [_i64, _i64, _i32, _i32, _i32, _i32, C.POINTER(_vp)]),
     "lspiv_ensemble_accumulate": (_i32, [_vp, _vp, _i32, _i64, _f32, _f32, _f32, _vp, _vp]),

@@ -176,6 +176,11 @@ int apply_v_sign(float* d_v, int64_t n, hipStream_t s) {
 }
 
 static int dispatch_kernels(const lspiv::PivParams& p, int dtype, bool ensemble, hipStream_t s) {
+  if (p.warped) {   // window deformation pass: the mixed-type per-pair kernels
+    if (ensemble) return fail(LSPIV_EUNSUPPORTED, "ensemble mode has no deformation kernels");
+    return launch_status(p.wy == 16 ? lspiv::launch_piv_deform16(p, dtype, s) : p.wy == 32 ? lspiv::launch_piv_deform32(p, dtype, s)
+                                                                                            : lspiv::launch_piv_deform64(p, dtype, s));
+  }
   if (p.shifted) {   // multi-pass mode: the shifted per-pair kernels
     if (ensemble)   // multi-pass ensemble: one owner per window sums the shifted planes over the chunk's pairs
       return launch_status(p.wy == 16 ? lspiv::launch_piv_shift_ensemble16(p, dtype, s) : p.wy == 32 ? lspiv::launch_piv_shift_ensemble32(p, dtype, s)
@@ -482,8 +487,55 @@ static int pass_grid(int64_t H, int64_t W, int wy, int wx, int oy, int ox, lspiv
 }
 
 // the clamped offsets of a pass, as the kernels used them: the predictor clamps what it stores, so its output IS the clamped array
+// ---- window deformation passes (include/lspiv.h) ------------------------------------------------------
+// The warped frames of one BATCH of pairs live in a per-device workspace of at most kDeformWsBytes (one frame at least): a pass runs
+// batch by batch -- warp, mixed-type kernel, rescue pass, nodes added -- before the workspace is reused.  Results are per pair, so the
+// batching cannot change a bit.
+constexpr size_t kDeformWsBytes = (size_t)256 << 20;
+static int64_t deform_batch_pairs(int64_t n_pairs, int64_t H, int64_t W) {
+  const int64_t fit = std::max<int64_t>(1, (int64_t)(kDeformWsBytes / ((size_t)H * (size_t)W * sizeof(float))));
+  return std::max<int64_t>(1, std::min<int64_t>(std::min<int64_t>(n_pairs, fit), 65535));   // (65535: the warp's grid runs the pairs along z)
+}
+static int check_deform(int wy, int wx, int oy, int ox, int64_t H, int64_t W) {
+  if (!shift_shape_ok(wy, wx) || oy != ox)
+    return fail(LSPIV_EUNSUPPORTED, "deformation pass with window %dx%d, overlap (%d,%d) is not supported: the window must be square and one of "
+                "{16, 32, 64}, the overlap the same on both axes", wy, wx, oy, ox);
+  if (H > 32767 || W > 32767) return fail(LSPIV_EINVAL, "frame (%lld,%lld): a side above 32767 does not fit the nodes' range", (long long)H, (long long)W);
+  return check_multipass_options();
+}
+// one deformation pass on stream s: d_nodes (T-1) * n_win * {v, u} -> d_out [u | v | corr_max | s2n] of all pairs (kernel orientation;
+// v_sign is the caller's).  The caller holds the device's multipass lock: the workspace is shared
+static int deform_pass(DeviceCtx* c, const void* d_frames, int dtype, int64_t T, int64_t H, int64_t W, int n, int ov, float signal_threshold,
+                       const int32_t* d_nodes, float* d_out, float* d_planes, hipStream_t s) {
+  Grid g;
+  LSPIV_TRY(make_grid(H, W, n, n, ov, ov, &g));
+  if (dtype < 0 || dtype > 2) return fail(LSPIV_EINVAL, "dtype %d not in {0:u8, 1:f32, 2:f64}", dtype);
+  const int64_t P = T - 1, n_win = g.n_rows * g.n_cols, batch = deform_batch_pairs(P, H, W);
+  const size_t frame_elems = (size_t)H * W, n_tiles = (size_t)P * n_win;
+  LSPIV_TRY(ensure(&c->d_deform, &c->deform_cap, (size_t)batch * frame_elems * sizeof(float)));
+  for (int64_t b0 = 0; b0 < P; b0 += batch) {
+    const int64_t nb = std::min<int64_t>(batch, P - b0);
+    lspiv::PivParams p;
+    LSPIV_TRY(fill_params(&p, (const char*)d_frames + (size_t)b0 * frame_elems * elem_size(dtype), dtype, nb + 1, H, W, n, n, ov, ov,
+                          signal_threshold, g));
+    const size_t t0 = (size_t)b0 * n_win;
+    p.nodes = d_nodes + 2 * t0;
+    p.warped = c->d_deform;
+    p.u = d_out + t0;
+    p.v = d_out + n_tiles + t0;
+    p.cmax = d_out + 2 * n_tiles + t0;
+    p.s2n = d_out + 3 * n_tiles + t0;
+    p.planes = d_planes ? d_planes + t0 * (size_t)n * n : nullptr;
+    LSPIV_TRY(launch_status(lspiv::launch_deform_warp(p, dtype, c->d_deform, s)));
+    LSPIV_TRY(dispatch(p, dtype, false, s));
+    LSPIV_TRY(launch_status(lspiv::launch_add_nodes(p, s)));
+  }
+  return LSPIV_OK;
+}
+
 static int multipass_dev(DeviceCtx* c, const void* d_frames, int dtype, int64_t T, int64_t H, int64_t W, int n_passes, const int* passes,
-                         float signal_threshold, int64_t pair_offset, float* d_out, float* d_planes, int16_t* d_shift_out, hipStream_t s) {
+                         float signal_threshold, int64_t pair_offset, float* d_out, float* d_planes, int16_t* d_shift_out, hipStream_t s,
+                         int n_deform = 0) {
   if (!d_frames || !d_out || !passes) return fail(LSPIV_EINVAL, "d_frames / d_out / passes is NULL");
   if (n_passes < 1 || n_passes > 8) return fail(LSPIV_EINVAL, "n_passes %d not in 1..8", n_passes);
   if (pair_offset < 0) return fail(LSPIV_EINVAL, "pair_offset %lld is negative", (long long)pair_offset);
@@ -503,7 +555,9 @@ static int multipass_dev(DeviceCtx* c, const void* d_frames, int dtype, int64_t 
   }
   const int* last = passes + 4 * (n_passes - 1);
   const size_t last_tiles = (size_t)(T - 1) * pg[n_passes - 1].n_rows * pg[n_passes - 1].n_cols;
-  if (n_passes == 1) {
+  if (n_deform < 0 || n_deform > 4) return fail(LSPIV_EINVAL, "n_deform %d not in 0..4", n_deform);
+  if (n_deform) LSPIV_TRY(check_deform(last[0], last[1], last[2], last[3], H, W));
+  if (n_passes == 1 && !n_deform) {
     if (d_shift_out) HIP_TRY(hipMemsetAsync(d_shift_out, 0, last_tiles * 2 * sizeof(int16_t), s));
     return lspiv_piv_pairs_dev_at(d_frames, dtype, T, H, W, last[0], last[1], last[2], last[3], signal_threshold, pair_offset, d_out, d_planes, s);
   }
@@ -514,19 +568,23 @@ static int multipass_dev(DeviceCtx* c, const void* d_frames, int dtype, int64_t 
   size_t max_shift = 0;
   for (int k = 1; k < n_passes; ++k) max_shift = std::max(max_shift, (size_t)(T - 1) * pg[k].n_rows * pg[k].n_cols);
   const size_t blk = (4 * max_tiles * sizeof(float) + 255) & ~(size_t)255;
-  LSPIV_TRY(ensure(&c->d_mp, &c->mp_cap, 2 * blk + max_shift * 2 * sizeof(int16_t)));
+  const size_t shift_bytes = (max_shift * 2 * sizeof(int16_t) + 255) & ~(size_t)255;
+  LSPIV_TRY(ensure(&c->d_mp, &c->mp_cap, 2 * blk + shift_bytes + (n_deform ? last_tiles * 2 * sizeof(int32_t) : 0)));
   float* res[2] = {reinterpret_cast<float*>(c->d_mp), reinterpret_cast<float*>((char*)c->d_mp + blk)};
   int16_t* ws_shift = reinterpret_cast<int16_t*>((char*)c->d_mp + 2 * blk);
+  int32_t* ws_nodes = reinterpret_cast<int32_t*>((char*)c->d_mp + 2 * blk + shift_bytes);
   // pass 0: today's per-timestep path on its own grid, in the kernels' orientation (no v_sign before the end)
   {
     const int* q = passes;
+    float* r0 = n_passes == 1 ? d_out : res[0];   // (a chain of one pass that deformation passes follow)
     Grid g;
     LSPIV_TRY(make_grid(H, W, q[0], q[1], q[2], q[3], &g));
     lspiv::PivParams p;
     LSPIV_TRY(fill_params(&p, d_frames, dtype, T, H, W, q[0], q[1], q[2], q[3], signal_threshold, g));
     p.pair_offset = pair_offset;
-    p.u = res[0]; p.v = res[0] + (size_t)p.n_tiles; p.cmax = res[0] + 2 * (size_t)p.n_tiles; p.s2n = res[0] + 3 * (size_t)p.n_tiles;
+    p.u = r0; p.v = r0 + (size_t)p.n_tiles; p.cmax = r0 + 2 * (size_t)p.n_tiles; p.s2n = r0 + 3 * (size_t)p.n_tiles;
     LSPIV_TRY(dispatch(p, dtype, false, s));
+    if (n_passes == 1 && d_shift_out) HIP_TRY(hipMemsetAsync(d_shift_out, 0, last_tiles * 2 * sizeof(int16_t), s));
   }
   for (int k = 1; k < n_passes; ++k) {
     const int* q = passes + 4 * k;
@@ -536,7 +594,14 @@ static int multipass_dev(DeviceCtx* c, const void* d_frames, int dtype, int64_t 
     int16_t* shift = final_pass && d_shift_out ? d_shift_out : ws_shift;
     LSPIV_TRY(launch_status(lspiv::launch_predict_shift(prev, prev + prev_tiles, (uint32_t)(T - 1), (int)H, (int)W, pg[k - 1], pg[k], shift, s)));
     LSPIV_TRY(shift_pass(d_frames, dtype, T, H, W, q[0], q[1], q[2], q[3], signal_threshold, pair_offset, shift, final_pass ? d_out : res[k & 1],
-                         final_pass ? d_planes : nullptr, s, nullptr));
+                         final_pass && !n_deform ? d_planes : nullptr, s, nullptr));
+  }
+  // the deformation passes on the final grid, each fed with the (u, v) of the pass before it: the nodes are read off d_out, then the
+  // pass overwrites it (stream order); the planes are those of the last one
+  for (int d = 0; d < n_deform; ++d) {
+    const lspiv::PassGrid& fg = pg[n_passes - 1];
+    LSPIV_TRY(launch_status(lspiv::launch_predict_deform(d_out, d_out + last_tiles, (uint32_t)(T - 1), fg.n_rows, fg.n_cols, ws_nodes, s)));
+    LSPIV_TRY(deform_pass(c, d_frames, dtype, T, H, W, last[0], last[2], signal_threshold, ws_nodes, d_out, d == n_deform - 1 ? d_planes : nullptr, s));
   }
   return apply_v_sign(d_out + last_tiles, (int64_t)last_tiles, s);
 }
@@ -578,8 +643,68 @@ int lspiv_piv_multipass_dev_at(const void* d_frames, int dtype, int64_t T, int64
                        on_stream(c, stream));
 }
 
+int lspiv_deform_supported(int wy, int wx) { return shift_shape_ok(wy, wx) ? 1 : 0; }
+
+int64_t lspiv_deform_required_bytes(int64_t T, int64_t H, int64_t W, int wy, int wx, int oy, int ox) {
+  Grid g;
+  LSPIV_TRY(make_grid(H, W, wy, wx, oy, ox, &g));
+  if (T < 2) return fail(LSPIV_ESHAPE, "need at least 2 frames, got %lld", (long long)T);
+  return deform_batch_pairs(T - 1, H, W) * H * W * (int64_t)sizeof(float) + (T - 1) * g.n_rows * g.n_cols * 2 * (int64_t)sizeof(int32_t);
+}
+
+int lspiv_piv_predict_deform_dev(const float* d_u, const float* d_v, int64_t n_pairs, int64_t n_rows, int64_t n_cols, int32_t* d_nodes, void* stream) {
+  if (!d_u || !d_v || !d_nodes) return fail(LSPIV_EINVAL, "NULL argument");
+  if (n_pairs < 0 || n_rows < 1 || n_cols < 1) return fail(LSPIV_ESHAPE, "grid (%lld, %lld, %lld) invalid", (long long)n_pairs, (long long)n_rows, (long long)n_cols);
+  if (n_rows > 32767 || n_cols > 32767 || n_pairs * n_rows * n_cols >= (int64_t)1 << 31)
+    return fail(LSPIV_EINVAL, "too many windows for one launch (limit 2^31)");
+  return launch_on(stream, [&](hipStream_t s) { return lspiv::launch_predict_deform(d_u, d_v, (uint32_t)n_pairs, (int)n_rows, (int)n_cols, d_nodes, s); });
+}
+
+int lspiv_piv_deform_pairs_dev_at(const void* d_frames, int dtype, int64_t T, int64_t H, int64_t W, int wy, int wx, int oy, int ox,
+                                  float signal_threshold, int64_t pair_offset, const int32_t* d_nodes, float* d_out, float* d_corr_planes,
+                                  void* stream) {
+  if (!d_frames || !d_out || !d_nodes) return fail(LSPIV_EINVAL, "d_frames / d_nodes / d_out is NULL");
+  if (pair_offset < 0) return fail(LSPIV_EINVAL, "pair_offset %lld is negative", (long long)pair_offset);
+  if (T < 2) return fail(LSPIV_ESHAPE, "need at least 2 frames, got %lld", (long long)T);
+  LSPIV_TRY(check_deform(wy, wx, oy, ox, H, W));
+  Grid g;
+  LSPIV_TRY(make_grid(H, W, wy, wx, oy, ox, &g));
+  DeviceCtx* c;
+  LSPIV_TRY(get_ctx(&c));
+  hipStream_t s = on_stream(c, stream);
+  std::lock_guard<std::mutex> chain_lock(locks_here().multipass);
+  LSPIV_TRY(deform_pass(c, d_frames, dtype, T, H, W, wy, oy, signal_threshold, d_nodes, d_out, d_corr_planes, s));
+  const int64_t n_tiles = (T - 1) * g.n_rows * g.n_cols;
+  return apply_v_sign(d_out + n_tiles, n_tiles, s);
+}
+
+int lspiv_piv_multipass_deform_dev_at(const void* d_frames, int dtype, int64_t T, int64_t H, int64_t W, int n_passes, const int* passes,
+                                      int n_deform, float signal_threshold, int64_t pair_offset, float* d_out, float* d_corr_planes,
+                                      int16_t* d_shift_out, void* stream) {
+  DeviceCtx* c;
+  LSPIV_TRY(get_ctx(&c));
+  return multipass_dev(c, d_frames, dtype, T, H, W, n_passes, passes, signal_threshold, pair_offset, d_out, d_corr_planes, d_shift_out,
+                       on_stream(c, stream), n_deform);
+}
+
+static int multipass_host(const void* frames, int dtype, int64_t T, int64_t H, int64_t W, int n_passes, const int* passes, int n_deform,
+                          float signal_threshold, int64_t pair_offset, float* u, float* v, float* corr_max, float* s2n, float* corr_planes,
+                          int16_t* shift_out);
+
+int lspiv_piv_multipass_deform_at(const void* frames, int dtype, int64_t T, int64_t H, int64_t W, int n_passes, const int* passes, int n_deform,
+                                  float signal_threshold, int64_t pair_offset, float* u, float* v, float* corr_max, float* s2n,
+                                  float* corr_planes, int16_t* shift_out) {
+  return multipass_host(frames, dtype, T, H, W, n_passes, passes, n_deform, signal_threshold, pair_offset, u, v, corr_max, s2n, corr_planes, shift_out);
+}
+
 int lspiv_piv_multipass_at(const void* frames, int dtype, int64_t T, int64_t H, int64_t W, int n_passes, const int* passes, float signal_threshold,
                            int64_t pair_offset, float* u, float* v, float* corr_max, float* s2n, float* corr_planes, int16_t* shift_out) {
+  return multipass_host(frames, dtype, T, H, W, n_passes, passes, 0, signal_threshold, pair_offset, u, v, corr_max, s2n, corr_planes, shift_out);
+}
+
+static int multipass_host(const void* frames, int dtype, int64_t T, int64_t H, int64_t W, int n_passes, const int* passes, int n_deform,
+                          float signal_threshold, int64_t pair_offset, float* u, float* v, float* corr_max, float* s2n, float* corr_planes,
+                          int16_t* shift_out) {
   std::lock_guard<std::mutex> host_lock(locks_here().host);
   if (!frames || !u || !v || !corr_max || !s2n || !passes) return fail(LSPIV_EINVAL, "NULL buffer");
   if (n_passes < 1 || n_passes > 8) return fail(LSPIV_EINVAL, "n_passes %d not in 1..8", n_passes);
@@ -611,7 +736,7 @@ int lspiv_piv_multipass_at(const void* frames, int dtype, int64_t T, int64_t H, 
   }
   HIP_TRY(hipStreamSynchronize(c->copy_stream));
   const int rc = multipass_dev(c, c->d_frames, dev_dtype, T, H, W, n_passes, passes, signal_threshold, pair_offset, c->d_out,
-                               corr_planes ? c->d_planes : nullptr, d_shift, c->stream);
+                               corr_planes ? c->d_planes : nullptr, d_shift, c->stream, n_deform);
   if (rc != LSPIV_OK) { (void)hipStreamSynchronize(c->stream); return rc; }
   const size_t ob = n_tiles * sizeof(float);
   HIP_TRY(hipMemcpyAsync(u, c->d_out, ob, hipMemcpyDeviceToHost, c->stream));

@@ -117,6 +117,12 @@ struct PivParams {
   // clamped offset afterwards.  Shifted ensemble pass: shift holds n_win x {dy, dx}, one field for every pair (the index is the window)
   int shifted;
   const int16_t* shift;
+  // window deformation pass (piv_deform_impl.h): warped != nullptr selects the mixed-type kernels -- window A
+  // from `frames` in its sample type, window B at the SAME position from `warped`, n_pairs float32 frames of H x W (pair k's frame
+  // k + 1 sampled at the dense field of its nodes, deform_warp_kernel).  nodes: n_tiles x {v, u} int32 in 1 / 128 px, result g's
+  // predicted displacement at its own centre; the kernels and the rescue pass write the RESIDUAL, launch_add_nodes adds nodes / 128
+  const float* warped;
+  const int32_t* nodes;
 };
 
 // The offset of result g = pair * n_win + window (shifted ensemble pass: g = window; grid row wrow, column wcol), clamped so that the shifted window stays inside
@@ -132,6 +138,68 @@ __device__ __forceinline__ WinShift window_shift(const PivParams& p, uint32_t g,
     s.dx = min(max((int)p.shift[2 * (size_t)g + 1], -x0), p.W - p.wx - x0);
   }
   return s;
+}
+
+// ---- window deformation: the dense displacement field of a pair's nodes and the sample of frame t+1 it
+// points at.  The ONE place this arithmetic lives.  Exact integers on doubled coordinates (the half-pixel window centres are nodes)
+// up to the blend, so that a float64 reference on the host lands on the same 1 / 64 px positions and -- for uint8 frames -- on the
+// same float32 sample: the blend's numerator is an integer below 2^20 and the division is by 4096.
+constexpr int kDeformQ = 64;   // sub-pixel positions per pixel
+// per axis: the node interval [i0, i1] pixel px falls into and its integer weights, w0 + w1 = 2 s; node i sits at the doubled
+// coordinate 2 i s + n - 1; constant outside the outermost nodes; a one-node axis has i0 = i1 = 0, w1 = 0
+struct DeformAxis { int i0, i1, w0, w1; };
+__device__ __forceinline__ DeformAxis deform_axis(int px, int n, int s, int count) {
+  DeformAxis a;
+  const int S2 = 2 * s, d = 2 * px - (n - 1);
+  int i0 = d >= 0 ? d / S2 : -((-d + S2 - 1) / S2);   // floor
+  i0 = min(max(i0, 0), max(count - 2, 0));
+  a.i0 = i0;
+  a.i1 = min(i0 + 1, count - 1);
+  a.w1 = count > 1 ? min(max(d - i0 * S2, 0), S2) : 0;
+  a.w0 = S2 - a.w1;
+  return a;
+}
+// the sample of frame I (H x W, the pair's frame t+1) that pixel (y, x) of the warped frame takes: the pair's nodes (n_win x {v, u},
+// 1 / 128 px) interpolated bilinearly to the pixel, rounded half up to 1 / 64 px, the position clamped to the frame (the edge is
+// replicated: no field can make a read leave the frame), four neighbours blended.  uint8: exact; float32 / float64 (narrowed first,
+// as the kernels' loaders do): a fixed order of float32 products and sums, none of them fused
+template <typename T>
+__device__ __forceinline__ float deform_sample(const PivParams& p, const int32_t* nodes, const T* I, int y, int x) {
+  const DeformAxis ay = deform_axis(y, p.wy, p.sy, p.n_rows), ax = deform_axis(x, p.wx, p.sx, p.n_cols);
+  int64_t num_v = 0, num_u = 0;
+#pragma unroll
+  for (int e = 0; e < 4; ++e) {
+    const int iy = e & 2 ? ay.i1 : ay.i0, ix = e & 1 ? ax.i1 : ax.i0;
+    const int64_t w = (int64_t)(e & 2 ? ay.w1 : ay.w0) * (int64_t)(e & 1 ? ax.w1 : ax.w0);
+    const int32_t* nd = nodes + 2 * ((size_t)iy * p.n_cols + ix);
+    num_v += w * nd[0];
+    num_u += w * nd[1];
+  }
+  const int64_t den = 4 * (int64_t)p.sy * (int64_t)p.sx;
+  // floor((num + den) / (2 den)) through one float64 division each: |num + den| < 2^38 and 2 den <= 2^15 are exact doubles, the quotient
+  // is below 2^23, so its rounding error (< 2^-29) cannot carry it across an integer it is at least 1 / (2 den) away from -- the exact
+  // integer result at a tenth of the instructions of a 64-bit integer division, which bounded the warp
+  const double two_den = (double)(2 * den);
+  const int64_t dv = (int64_t)floor((double)(num_v + den) / two_den), du = (int64_t)floor((double)(num_u + den) / two_den);
+  const int Y = (int)min(max((int64_t)kDeformQ * y + dv, (int64_t)0), (int64_t)kDeformQ * (p.H - 1));
+  const int X = (int)min(max((int64_t)kDeformQ * x + du, (int64_t)0), (int64_t)kDeformQ * (p.W - 1));
+  int iy = Y >> 6, fy = Y & 63, ix = X >> 6, fx = X & 63;
+  if (iy == p.H - 1) { iy = p.H - 2; fy = kDeformQ; }
+  if (ix == p.W - 1) { ix = p.W - 2; fx = kDeformQ; }
+  const T* r0 = I + (int64_t)iy * p.W + ix;
+  const T* r1 = r0 + p.W;
+  const int w00 = (kDeformQ - fy) * (kDeformQ - fx), w01 = (kDeformQ - fy) * fx, w10 = fy * (kDeformQ - fx), w11 = fy * fx;
+  if constexpr (sizeof(T) == 1) {
+    const int num = w00 * (int)r0[0] + w01 * (int)r0[1] + w10 * (int)r1[0] + w11 * (int)r1[1];
+    return (float)num * (1.0f / 4096.0f);
+  } else {
+#pragma clang fp contract(off)
+    float t = (float)w00 * (float)r0[0];
+    t = t + (float)w01 * (float)r0[1];
+    t = t + (float)w10 * (float)r1[0];
+    t = t + (float)w11 * (float)r1[1];
+    return t * (1.0f / 4096.0f);
+  }
 }
 
 // ---- float64 rescue of the ENSEMBLE's final fit (piv_rescue.hip) ---------------------------------
@@ -446,6 +514,15 @@ hipError_t launch_clamp_shift(const PivParams& p, int16_t* out, hipStream_t s);
 struct PassGrid { int wy, wx, sy, sx, n_rows, n_cols; };   // window, strides, grid
 hipError_t launch_predict_shift(const float* u, const float* v, uint32_t n_pairs, int H, int W, const PassGrid& coarse, const PassGrid& fine,
                                 int16_t* shift, hipStream_t s);
+// window deformation pass: the mixed-type kernels (p.warped, p.nodes; n = p.wy = p.wx = 16 / 32 / 64; u, v are
+// the residual), the node predictor (u, v of a pass -> int32 nodes {v, u} in 1 / 128 px on the same grid), the warp of every pair's
+// frame t+1 into p.warped, and u += nodes.u / 128, v += nodes.v / 128 after the rescue pass (piv_multipass.hip)
+hipError_t launch_piv_deform16(const PivParams& p, int dtype, hipStream_t s);
+hipError_t launch_piv_deform32(const PivParams& p, int dtype, hipStream_t s);
+hipError_t launch_piv_deform64(const PivParams& p, int dtype, hipStream_t s);
+hipError_t launch_predict_deform(const float* u, const float* v, uint32_t n_pairs, int n_rows, int n_cols, int32_t* nodes, hipStream_t s);
+hipError_t launch_deform_warp(const PivParams& p, int dtype, float* warped, hipStream_t s);
+hipError_t launch_add_nodes(const PivParams& p, hipStream_t s);
 // float64 re-evaluation of the windows the PIV kernel of this pass appended to p.rescue_* (piv_rescue.hip)
 hipError_t launch_piv_rescue(const PivParams& p, int dtype, hipStream_t s);
 // ensemble mode: flag the windows of the float32 mean planes (u, v = their float32 fits) whose fit cannot be trusted; partial

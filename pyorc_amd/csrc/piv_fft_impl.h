@@ -951,13 +951,16 @@ __device__ __forceinline__ float plane_max(const float (&c)[N], float& row_max) 
 // (common.h, peak_cond); decided and written here, so that nothing of it stays live in the callers.
 // first shifted row holding the plane maximum (register-only: DPP reductions, no LDS), so that a caller with two planes can
 // start the second plane's search while the first plane's LDS round trips are in flight
+// NODES (deformation pass): u, v are a residual against the window's node p.nodes[g]; the flag's tolerance is relative to the FULL
+// displacement node / 128 + residual, the value the pass hands out (a residual of a few hundredths of a pixel would otherwise flag
+// most windows for an accuracy nobody asks of the sum)
 template <int N>
 __device__ __forceinline__ int peak_row(int lg, float vmax, float row_max) {
   constexpr int C = N / 2, NONE = 1 << 12;
   const int sh = wrap_n<N>(row_of<N>(lg) + C);
   return group_min_i<N>((lane_active<N>(lg) && row_max == vmax) ? sh : NONE);
 }
-template <int N>
+template <int N, bool NODES = false>
 __device__ __forceinline__ void find_peak(float* buf, int lg, const float (&c)[N], float vmax, float row_max, const PivParams& p,
                                           float& u, float& v, bool note, uint32_t g, int ip_known = -1) {
   const int border_mode = p.border_mode;
@@ -992,7 +995,12 @@ __device__ __forceinline__ void find_peak(float* buf, int lg, const float (&c)[N
   float den_v, den_u;
   v = (float)ip + gauss_offset_fast(__builtin_amdgcn_logf(cl), l0, __builtin_amdgcn_logf(cr), den_v) - (float)C;
   u = (float)jp + gauss_offset_fast(__builtin_amdgcn_logf(cd), l0, __builtin_amdgcn_logf(cu), den_u) - (float)C;
-  const PeakCond pc = peak_cond(vmax, near_tie, border, cl, cr, den_v, v, cd, cu, den_u, u, p.rescue_k);
+  float full_v = v, full_u = u;
+  if constexpr (NODES) {
+    full_v += (float)p.nodes[2 * (size_t)g] * (1.0f / 128.0f);
+    full_u += (float)p.nodes[2 * (size_t)g + 1] * (1.0f / 128.0f);
+  }
+  const PeakCond pc = peak_cond(vmax, near_tie, border, cl, cr, den_v, full_v, cd, cu, den_u, full_u, p.rescue_k);
   if (note) {
     uint32_t pos2 = 0xffffffffu;
     if (__builtin_amdgcn_ballot_w64(pc.amb) != 0) {

@@ -8,6 +8,12 @@
 //                          between the coarse window centres with integer weights, one rounding division, the frame clamp.
 //   clamp_shift_kernel     the offset field of a shifted ensemble handle -> its clamped values (window_shift), in place.
 //   add_shift_kernel       u += clamped dx, v += clamped dy after the rescue pass: the kernels and the rescue pass write the residual.
+// Window deformation passes (section 2f) run on the final grid after the chain:
+//   predict_deform_kernel  (u, v) of a pass -> int32 nodes {v, u} in 1 / 128 px on the SAME grid: rint(64 x), then twice the 3 x 3 median
+//                          (the code of predict_shift_kernel's median on the finer units).
+//   deform_warp_kernel     frame t+1 of every pair of a batch sampled at the dense field of the pair's nodes (common.h, deform_sample)
+//                          -> a float32 workspace the mixed-type kernels (piv_deform_impl.h) and the rescue pass cut window B from.
+//   add_nodes_kernel       u += nodes.u / 128, v += nodes.v / 128 after the rescue pass.
 // All of it in the kernels' native orientation (u = column shift, v = row shift, rows downward); the "v_sign" option is applied to
 // the final result only.
 #include <climits>
@@ -45,10 +51,17 @@ __device__ __forceinline__ bool is_finite(float x) { return (__builtin_bit_cast(
 // q = rint (half to even, in float32) clamped to the range of the int16 offsets, [-32768, 32767]: a frame side is at most 32767, so no
 // displacement a frame can hold is touched, the conversion to int is defined for every finite input, and sums of two q cannot overflow
 __device__ __forceinline__ int round_q(float x) { return (int)fminf(fmaxf(rintf(x), -32768.0f), 32767.0f); }
+// deformation nodes: q = rint(64 x) (the product is exact in float32, or infinite), clamped to +-32767 * 64
+__device__ __forceinline__ int round_q64(float x) {
+  constexpr float lim = 32767.0f * (float)kDeformQ;
+  return (int)fminf(fmaxf(rintf((float)kDeformQ * x), -lim), lim);
+}
 
 // twice the median of the rounded vectors over the valid ones of the 3 x 3 neighbourhood of coarse window (r, c), clipped at the
 // grid's edges, centre included: odd count 2 * middle, even count the sum of the two middle values, none 0.  The nine values of a
 // component live in registers: an odd-even transposition sort with constant indices, invalid entries sorted to the end.
+// Q64: the vectors are rounded to 1 / 64 px (round_q64) instead of whole pixels.
+template <bool Q64 = false>
 __device__ __forceinline__ void median2(const float* u, const float* v, int n_rows, int n_cols, int r, int c, int& mu, int& mv) {
   int qu[9], qv[9];
   int k = 0;
@@ -59,8 +72,8 @@ __device__ __forceinline__ void median2(const float* u, const float* v, int n_ro
     const size_t i = (size_t)(in ? rr : r) * n_cols + (in ? cc : c);
     const float fu = u[i], fv = v[i];
     const bool ok = in && is_finite(fu) && is_finite(fv);
-    qu[e] = ok ? round_q(fu) : INT_MAX;       // (INT_MAX, the invalid entries' sort key, is outside the range of q)
-    qv[e] = ok ? round_q(fv) : INT_MAX;
+    qu[e] = ok ? (Q64 ? round_q64(fu) : round_q(fu)) : INT_MAX;       // (INT_MAX, the invalid entries' sort key, is outside the range of q)
+    qv[e] = ok ? (Q64 ? round_q64(fv) : round_q(fv)) : INT_MAX;
     k += ok ? 1 : 0;
   }
 #pragma unroll
@@ -126,6 +139,41 @@ __global__ __launch_bounds__(MBLOCK) void add_shift_kernel(PivParams p) {
   if (ws.dy != 0) p.v[g] = p.v[g] + (float)ws.dy;
 }
 
+// one thread per (pair, window): nodes[g] = {twice the median of rint(64 v), of rint(64 u)} over the valid 3 x 3 neighbours, 1 / 128 px
+__global__ __launch_bounds__(MBLOCK) void predict_deform_kernel(const float* u, const float* v, uint32_t n_pairs, int n_rows, int n_cols,
+                                                                int32_t* nodes) {
+  const uint32_t n_win = (uint32_t)n_rows * (uint32_t)n_cols;
+  const uint64_t g = (uint64_t)blockIdx.x * MBLOCK + threadIdx.x;
+  if (g >= (uint64_t)n_pairs * n_win) return;
+  const uint32_t pair = (uint32_t)(g / n_win), win = (uint32_t)(g - (uint64_t)pair * n_win);
+  const int r = (int)(win / (uint32_t)n_cols), c = (int)(win - (uint32_t)r * (uint32_t)n_cols);
+  const size_t base = (size_t)pair * n_win;
+  int mu = 0, mv = 0;
+  median2<true>(u + base, v + base, n_rows, n_cols, r, c, mu, mv);
+  nodes[2 * g] = mv;
+  nodes[2 * g + 1] = mu;
+}
+
+// one thread per pixel of the warped frames: block = 64 pixels of 4 rows (the lanes of a wave run along x: the field is smooth, so
+// they read near-contiguous addresses, and the two node columns of an interval are the same words for most lanes -- L1 / L2 hits on a
+// pair's few KB of nodes), blockIdx.z = the pair.  p.frames = frame 0 of the batch; pair k reads frame k + 1
+constexpr int WARP_BX = 64, WARP_BY = 4;
+template <typename T>
+__global__ __launch_bounds__(WARP_BX * WARP_BY) void deform_warp_kernel(PivParams p, float* warped) {
+  const int x = (int)(blockIdx.x * WARP_BX + threadIdx.x), y = (int)(blockIdx.y * WARP_BY + threadIdx.y);
+  if (x >= p.W || y >= p.H) return;
+  const uint32_t pair = blockIdx.z;
+  const T* I = static_cast<const T*>(p.frames) + ((int64_t)pair + 1) * p.frame_elems;
+  warped[(int64_t)pair * p.frame_elems + (int64_t)y * p.W + x] = deform_sample<T>(p, p.nodes + 2 * (size_t)pair * p.n_win, I, y, x);
+}
+
+__global__ __launch_bounds__(MBLOCK) void add_nodes_kernel(PivParams p) {
+  const uint32_t g = blockIdx.x * MBLOCK + threadIdx.x;
+  if (g >= p.n_tiles) return;
+  p.v[g] = (float)p.nodes[2 * (size_t)g] * (1.0f / 128.0f) + p.v[g];       // (|node| < 2^23: the conversion and the scaling are exact)
+  p.u[g] = (float)p.nodes[2 * (size_t)g + 1] * (1.0f / 128.0f) + p.u[g];
+}
+
 // shifted ensemble pass: the offset field of a handle (n_win x {dy, dx}, p.n_tiles = p.n_win) replaced by its clamped values -- through
 // window_shift, so that what lspiv_ensemble_get_shift hands out is what the kernels use.  In place: a thread reads and writes its own entry.
 __global__ __launch_bounds__(MBLOCK) void clamp_shift_kernel(PivParams p, int16_t* out) {
@@ -151,6 +199,33 @@ hipError_t launch_predict_shift(const float* u, const float* v, uint32_t n_pairs
   if (n == 0) return hipSuccess;
   if (n >= (uint64_t)1 << 31) return hipErrorInvalidValue;
   hipLaunchKernelGGL(predict_shift_kernel, dim3((uint32_t)((n + MBLOCK - 1) / MBLOCK)), dim3(MBLOCK), 0, s, u, v, n_pairs, H, W, coarse, fine, shift);
+  return hipGetLastError();
+}
+
+hipError_t launch_predict_deform(const float* u, const float* v, uint32_t n_pairs, int n_rows, int n_cols, int32_t* nodes, hipStream_t s) {
+  const uint64_t n = (uint64_t)n_pairs * (uint64_t)n_rows * (uint64_t)n_cols;
+  if (n == 0) return hipSuccess;
+  if (n >= (uint64_t)1 << 31) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(predict_deform_kernel, dim3((uint32_t)((n + MBLOCK - 1) / MBLOCK)), dim3(MBLOCK), 0, s, u, v, n_pairs, n_rows, n_cols, nodes);
+  return hipGetLastError();
+}
+
+hipError_t launch_deform_warp(const PivParams& p, int dtype, float* warped, hipStream_t s) {
+  if (!p.nodes || !warped || p.H < 2 || p.W < 2 || p.n_pairs == 0 || p.n_pairs > 65535) return hipErrorInvalidValue;
+  const dim3 grid((p.W + WARP_BX - 1) / WARP_BX, (p.H + WARP_BY - 1) / WARP_BY, p.n_pairs), block(WARP_BX, WARP_BY);
+  if (grid.y > 65535) return hipErrorInvalidValue;
+  switch (dtype) {
+    case 0: hipLaunchKernelGGL(deform_warp_kernel<uint8_t>, grid, block, 0, s, p, warped); break;
+    case 1: hipLaunchKernelGGL(deform_warp_kernel<float>, grid, block, 0, s, p, warped); break;
+    case 2: hipLaunchKernelGGL(deform_warp_kernel<double>, grid, block, 0, s, p, warped); break;
+    default: return hipErrorInvalidValue;
+  }
+  return hipGetLastError();
+}
+
+hipError_t launch_add_nodes(const PivParams& p, hipStream_t s) {
+  if (!p.nodes || p.n_tiles == 0) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(add_nodes_kernel, dim3((p.n_tiles + MBLOCK - 1) / MBLOCK), dim3(MBLOCK), 0, s, p);
   return hipGetLastError();
 }
 

@@ -19,6 +19,8 @@
 //
 // A fixed grid strides over both lists; its last block moves the counts to the statistics fields and zeroes the counters, so
 // a pass costs one extra launch and no memset.
+#include <type_traits>
+
 #include "common.h"
 
 namespace lspiv {
@@ -70,9 +72,11 @@ struct LaneWalk {
   }
 };
 
-template <typename T, bool STAGE = false>
-__device__ __forceinline__ void window_stats_wave2(const T* A, const T* B, int W, int wy, int wx, int lane, double& mean_a,
-                                                   double& sd_a, double& mean_b, double& sd_b, T* la = nullptr, T* lb = nullptr) {
+// TB: the sample type of window B (the float32 workspace of a deformation pass under a uint8 / float64 stack; else T)
+template <typename T, bool STAGE = false, typename TB = T>
+__device__ __forceinline__ void window_stats_wave2(const T* A, const TB* B, int W, int wy, int wx, int lane, double& mean_a,
+                                                   double& sd_a, double& mean_b, double& sd_b, T* la = nullptr,
+                                                   typename std::common_type<TB>::type* lb = nullptr) {   // (lb: TB is deduced from B alone)
   const int n = wy * wx;
   const LaneWalk lw(wx);
   // one pass over shifted samples d = x - x[0]: mean = x0 + S1 / n, variance = (S2 - S1^2 / n) / n.  With the shift the
@@ -85,7 +89,8 @@ __device__ __forceinline__ void window_stats_wave2(const T* A, const T* B, int W
 #pragma unroll 8
   for (int e = lane; e < n; e += 64, lw.next(y, x)) {
     const int64_t off = (int64_t)y * W + x;
-    const T ra = A[off], rb = B[off];
+    const T ra = A[off];
+    const TB rb = B[off];
     if constexpr (STAGE) { la[e] = ra; lb[e] = rb; }   // dense copy of the window (pitch wx) in the wave's LDS slice
     const double da = (double)ra - x0a, db = (double)rb - x0b;
     sa += da; qa = fma(da, da, qa);
@@ -109,10 +114,10 @@ __device__ __forceinline__ bool a_inside(const PivParams& p, int y, int x) {
 }
 __device__ __forceinline__ double corr_samples(const PivParams& p) { return p.nw ? (double)p.nw * (double)p.nw : (double)p.wy * (double)p.wx; }
 // statistics of both windows of a pair: over the tile, and -- search-area mode -- those of frame t again over its block
-template <typename T, bool STAGE = false>
-__device__ __forceinline__ void pair_stats_wave(const PivParams& p, const T* A, const T* B, int lane, double& mean_a, double& sd_a,
-                                                double& mean_b, double& sd_b, T* la = nullptr, T* lb = nullptr) {
-  window_stats_wave2<T, STAGE>(A, B, p.W, p.wy, p.wx, lane, mean_a, sd_a, mean_b, sd_b, la, lb);
+template <typename T, bool STAGE = false, typename TB = T>
+__device__ __forceinline__ void pair_stats_wave(const PivParams& p, const T* A, const TB* B, int lane, double& mean_a, double& sd_a,
+                                                double& mean_b, double& sd_b, T* la = nullptr, TB* lb = nullptr) {
+  window_stats_wave2<T, STAGE, TB>(A, B, p.W, p.wy, p.wx, lane, mean_a, sd_a, mean_b, sd_b, la, lb);
   if (p.nw) {
     const int o = (p.wy - p.nw) >> 1;
     const T* Ab = A + (int64_t)o * p.W + o;
@@ -132,8 +137,8 @@ __device__ __forceinline__ double norm_clip(double x, double mean, double inv_sd
 __device__ __forceinline__ int unshift(int ip, int c, int w) { return ip - c < 0 ? ip - c + w : ip - c; }
 
 // which of two shifted plane positions holds the larger float64 correlation (ties: the smaller row-major index, np.argmax)
-template <typename PA>
-__device__ __forceinline__ uint32_t choose_wave(const PivParams& p, PA A, PA B, int pitch, double mean_a, double inv_a, double mean_b,
+template <typename PA, typename PB>
+__device__ __forceinline__ uint32_t choose_wave(const PivParams& p, PA A, PB B, int pitch, double mean_a, double inv_a, double mean_b,
                                                 double inv_b, uint32_t pos1, uint32_t pos2, int lane) {
   const int wy = p.wy, wx = p.wx, n = wy * wx, cy = wy / 2, cx = wx / 2;
   const int ky1 = unshift((int)(pos1 >> 16), cy, wy), kx1 = unshift((int)(pos1 & 0xffffu), cx, wx);
@@ -161,8 +166,8 @@ __device__ __forceinline__ uint32_t choose_wave(const PivParams& p, PA A, PA B, 
 // k = the peak and its four neighbours, all in float64; every lane gets the five values
 // (A, B: the two windows, in global memory (pitch = frame width) or staged in LDS (pitch = window width))
 struct Lag5 { double c0, cu, cd, cl, cr; };   // centre, row above, row below, column left, column right
-template <typename PA>
-__device__ __forceinline__ Lag5 lag5_wave(const PivParams& p, PA A, PA B, int pitch, double mean_a, double inv_a, double mean_b,
+template <typename PA, typename PB>
+__device__ __forceinline__ Lag5 lag5_wave(const PivParams& p, PA A, PB B, int pitch, double mean_a, double inv_a, double mean_b,
                                           double inv_b, int ip, int jp, int lane) {
   const int wy = p.wy, wx = p.wx, n = wy * wx, cy = wy / 2, cx = wx / 2;
   // un-shifted lags of the peak and its four neighbours
@@ -207,8 +212,8 @@ __device__ __forceinline__ void fit5_d(const Lag5& c, int ip, int jp, int cy, in
 }
 
 // the five-sample fit at shifted position (ip, jp), all in float64; one wave, lane 0 stores
-template <typename PA>
-__device__ __forceinline__ void fit_wave(const PivParams& p, PA A, PA B, int pitch, double mean_a, double inv_a, double mean_b,
+template <typename PA, typename PB>
+__device__ __forceinline__ void fit_wave(const PivParams& p, PA A, PB B, int pitch, double mean_a, double inv_a, double mean_b,
                                          double inv_b, uint32_t g, int ip, int jp, int lane) {
   const int wy = p.wy, wx = p.wx, cy = wy / 2, cx = wx / 2;
   if (ip <= 0 || ip >= wy - 1 || jp <= 0 || jp >= wx - 1) {   // border peak: no fit (A5)
@@ -243,7 +248,21 @@ __device__ __forceinline__ const T* window_base(const PivParams& p, uint32_t g) 
 // the window of frame t+1 of result g: one frame on, and -- multi-pass mode -- at the window's clamped offset (common.h, window_shift).
 // (The ensemble's partial sums below index the offsets by the window alone: a shifted ensemble pass has one field for every pair.)
 template <typename T>
-__device__ __forceinline__ const T* window_base_b(const PivParams& p, uint32_t g, const T* A) {
+__device__ __forceinline__ const T* window_base_b_frames(const PivParams& p, uint32_t g, const T* A);
+// deformation pass (TB = float, p.warped): the window at A's own position in the pair's warped frame
+template <typename T, typename TB = T>
+__device__ __forceinline__ const TB* window_base_b(const PivParams& p, uint32_t g, const T* A) {
+  if constexpr (!std::is_same<T, TB>::value) {
+    return p.warped + (A - static_cast<const T*>(p.frames));
+  } else {
+    if constexpr (std::is_same<T, float>::value) {
+      if (p.warped) return p.warped + (A - static_cast<const T*>(p.frames));
+    }
+    return window_base_b_frames<T>(p, g, A);
+  }
+}
+template <typename T>
+__device__ __forceinline__ const T* window_base_b_frames(const PivParams& p, uint32_t g, const T* A) {
   const T* B = A + p.frame_elems;
   if (p.shift) {
     const uint32_t pair = g / p.n_win, win = g - pair * p.n_win;
@@ -270,16 +289,18 @@ __device__ __forceinline__ void amax_merge_d(double& v, int& idx, double pv, int
 // Windows whose two copies exceed the slice (float32 64 x 64 and up) take the direct path.
 constexpr int FIT_LDS_PER_WAVE = 8192;
 
-template <typename T>
+template <typename T, typename TB = T>
 __global__ __launch_bounds__(RBLOCK) void piv_rescue_fit_kernel(PivParams p) {
   extern __shared__ __attribute__((aligned(16))) unsigned char fsm[];
   typedef const T __attribute__((address_space(3))) * LdsPtr;
+  typedef const TB __attribute__((address_space(3))) * LdsPtrB;
   const RescueHdr* hdr = p.rescue_hdr;
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int wy = p.wy, wx = p.wx, n = wy * wx;
-  const bool staged = (size_t)2 * n * sizeof(T) <= (size_t)FIT_LDS_PER_WAVE;
-  T* la = reinterpret_cast<T*>(fsm + (size_t)wave * FIT_LDS_PER_WAVE);
-  T* lb = la + n;
+  const bool staged = (size_t)n * (sizeof(T) + sizeof(TB)) <= (size_t)FIT_LDS_PER_WAVE;
+  // (window B first: with a wider TB the narrower window A behind it stays aligned)
+  TB* lb = reinterpret_cast<TB*>(fsm + (size_t)wave * FIT_LDS_PER_WAVE);
+  T* la = reinterpret_cast<T*>(lb + n);
   const uint32_t n_fit = min(hdr->n_fit, p.rescue_cap_fit);
   const uint32_t n_waves = gridDim.x * (RBLOCK / 64);
   for (uint32_t i = blockIdx.x * (RBLOCK / 64) + (uint32_t)wave; i < n_fit; i += n_waves) {
@@ -287,10 +308,10 @@ __global__ __launch_bounds__(RBLOCK) void piv_rescue_fit_kernel(PivParams p) {
     const uint32_t g = rec.x;
     if (g >= p.n_tiles) continue;   // a record of another launch (two host threads interleaving on one stream): never write out of bounds
     const T* A = window_base<T>(p, g);
-    const T* B = window_base_b<T>(p, g, A);
+    const TB* B = window_base_b<T, TB>(p, g, A);
     double mean_a, sd_a, mean_b, sd_b;
-    if (staged) pair_stats_wave<T, true>(p, A, B, lane, mean_a, sd_a, mean_b, sd_b, la, lb);
-    else pair_stats_wave<T, false>(p, A, B, lane, mean_a, sd_a, mean_b, sd_b);
+    if (staged) pair_stats_wave<T, true, TB>(p, A, B, lane, mean_a, sd_a, mean_b, sd_b, la, lb);
+    else pair_stats_wave<T, false, TB>(p, A, B, lane, mean_a, sd_a, mean_b, sd_b);
     // (a zero-variance window is NaN already and is never listed)
     if (sd_a != 0.0 && sd_b != 0.0) {
       const double sg = p.norm_clip ? (double)p.std_gain : -(double)p.std_gain;   // options "std_ddof" / "norm_clip"
@@ -298,7 +319,8 @@ __global__ __launch_bounds__(RBLOCK) void piv_rescue_fit_kernel(PivParams p) {
       uint32_t pos = rec.y;
       if (staged) {
         __builtin_amdgcn_wave_barrier();   // the wave's own LDS writes above are in order with the reads below; this pins the compiler
-        const LdsPtr SA = (LdsPtr)la, SB = (LdsPtr)lb;
+        const LdsPtr SA = (LdsPtr)la;
+        const LdsPtrB SB = (LdsPtrB)lb;
         if (rec.z != 0xffffffffu) pos = choose_wave(p, SA, SB, wx, mean_a, inv_a, mean_b, inv_b, rec.y, rec.z, lane);   // two candidates
         fit_wave(p, SA, SB, wx, mean_a, inv_a, mean_b, inv_b, g, (int)(pos >> 16), (int)(pos & 0xffffu), lane);
         __builtin_amdgcn_wave_barrier();
@@ -316,7 +338,7 @@ __global__ __launch_bounds__(RBLOCK) void piv_rescue_fit_kernel(PivParams p) {
 // their non-zero samples, so a step is two broadcast reads (sample, its x) and four reads of b2 for four float64 FMAs. ------
 constexpr int AMB_R = 4;
 
-template <typename T>
+template <typename T, typename TB = T>
 __global__ __launch_bounds__(RBLOCK) void piv_rescue_amb_kernel(PivParams p) {
   extern __shared__ __attribute__((aligned(16))) double dsm[];
   __shared__ double red_v[RBLOCK / 64];
@@ -336,9 +358,9 @@ __global__ __launch_bounds__(RBLOCK) void piv_rescue_amb_kernel(PivParams p) {
     const uint32_t g = min(p.rescue_amb[i], p.n_tiles - 1);   // (clamped, not skipped: the barriers below stay uniform)
     const bool g_ok = p.rescue_amb[i] < p.n_tiles;
     const T* A = window_base<T>(p, g);
-    const T* B = window_base_b<T>(p, g, A);
+    const TB* B = window_base_b<T, TB>(p, g, A);
     double mean_a, sd_a, mean_b, sd_b;
-    pair_stats_wave<T>(p, A, B, lane, mean_a, sd_a, mean_b, sd_b);   // every wave computes the same totals
+    pair_stats_wave<T, false, TB>(p, A, B, lane, mean_a, sd_a, mean_b, sd_b);   // every wave computes the same totals
     const bool dead = sd_a == 0.0 || sd_b == 0.0;   // never listed; kept out of the control flow around the barriers below
     const double sg = p.norm_clip ? (double)p.std_gain : -(double)p.std_gain;   // options "std_ddof" / "norm_clip"
     const double inv_a = dead ? 1.0 : sg / sd_a, inv_b = dead ? 1.0 : sg / sd_b;
@@ -645,7 +667,7 @@ __global__ __launch_bounds__(RBLOCK) void ens_final_kernel(PivParams p, EnsRescu
   u[rec.w] = uu; v[rec.w] = vv;
 }
 
-template <typename T>
+template <typename T, typename TB = T>
 hipError_t launch_rescue_t(const PivParams& p, hipStream_t s) {
   const int n = p.wy * p.wx;
   const bool fast = n <= RESCUE_LDS_SAMPLES && (p.wx % AMB_R) == 0;
@@ -653,15 +675,15 @@ hipError_t launch_rescue_t(const PivParams& p, hipStream_t s) {
   // fixed grids (the record counts live on the device): empty blocks leave within microseconds
   const uint32_t fit_blocks = std::min<uint32_t>(4096u, std::max<uint32_t>(64u, p.n_tiles / 512u + 1u));
   const uint32_t amb_blocks = std::min<uint32_t>(1024u, std::max<uint32_t>(64u, p.n_tiles / 2048u + 1u));
-  const size_t fit_lds = (size_t)2 * n * sizeof(T) <= (size_t)FIT_LDS_PER_WAVE ? (size_t)(RBLOCK / 64) * FIT_LDS_PER_WAVE : 0;
-  hipLaunchKernelGGL(piv_rescue_fit_kernel<T>, dim3(fit_blocks), dim3(RBLOCK), fit_lds, s, p);
+  const size_t fit_lds = (size_t)n * (sizeof(T) + sizeof(TB)) <= (size_t)FIT_LDS_PER_WAVE ? (size_t)(RBLOCK / 64) * FIT_LDS_PER_WAVE : 0;
+  hipLaunchKernelGGL((piv_rescue_fit_kernel<T, TB>), dim3(fit_blocks), dim3(RBLOCK), fit_lds, s, p);
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) return e;
   // (per launch: the attribute belongs to the current device, and a process may drive several)
-  e = hipFuncSetAttribute(reinterpret_cast<const void*>(&piv_rescue_amb_kernel<T>), hipFuncAttributeMaxDynamicSharedMemorySize,
+  e = hipFuncSetAttribute(reinterpret_cast<const void*>(&piv_rescue_amb_kernel<T, TB>), hipFuncAttributeMaxDynamicSharedMemorySize,
                           (int)(3 * RESCUE_LDS_SAMPLES * sizeof(double) + (RESCUE_LDS_SAMPLES + 512) * sizeof(int)));
   if (e != hipSuccess) return e;
-  hipLaunchKernelGGL(piv_rescue_amb_kernel<T>, dim3(amb_blocks), dim3(RBLOCK), lds, s, p);
+  hipLaunchKernelGGL((piv_rescue_amb_kernel<T, TB>), dim3(amb_blocks), dim3(RBLOCK), lds, s, p);
   return hipGetLastError();
 }
 
@@ -712,9 +734,10 @@ hipError_t launch_ens_final(const PivParams& p, const EnsRescueArgs& a, const do
 hipError_t launch_piv_rescue(const PivParams& p, int dtype, hipStream_t s) {
   if (!p.rescue_hdr) return hipSuccess;
   switch (dtype) {
-    case 0: return launch_rescue_t<uint8_t>(p, s);
+    // (a deformation pass cuts window B from the float32 workspace; on a float32 stack that is the same-type kernels' p.warped branch)
+    case 0: return p.warped ? launch_rescue_t<uint8_t, float>(p, s) : launch_rescue_t<uint8_t>(p, s);
     case 1: return launch_rescue_t<float>(p, s);
-    case 2: return launch_rescue_t<double>(p, s);
+    case 2: return p.warped ? launch_rescue_t<double, float>(p, s) : launch_rescue_t<double>(p, s);
     default: return hipErrorInvalidValue;
   }
 }

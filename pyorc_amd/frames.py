@@ -70,6 +70,7 @@ def get_piv(frames, window_size=None, overlap=None, engine: str = "hip", ensembl
     ``ensemble_window`` / ``ensemble_stride`` (in ``**kwargs``, with ``ensemble_corr=True``): a sliding ensemble, INTEGRATION.md 2c.
     ``coarse_passes``: multi-pass PIV -- coarse passes run before ``window_size``, coarsest first, each an int n
     (n x n at overlap n / 2) or a pair ``(n, overlap)``; the result stays on the grid of ``window_size`` / ``overlap``.
+    ``deform_passes`` (in ``**kwargs``): 0 .. 4 window deformation passes after the chain, per-timestep mode only.
     """
     if engine not in ENGINES:
         raise ValueError(f"Selected PIV engine {engine} does not exist.")

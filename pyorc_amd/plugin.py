@@ -124,6 +124,8 @@ def _wrap_get_piv(orig):
         sliding = {k: kwargs.pop(k) for k in ("ensemble_window", "ensemble_stride") if k in kwargs}
         # ... and the multi-pass chain's `coarse_passes=`
         coarse = kwargs.pop("coarse_passes", None)
+        # ... and the window deformation passes' `deform_passes=`
+        deform = kwargs.pop("deform_passes", None)
         engine, bound = kwargs.get("engine"), None
         if sig is not None and "engine" in sig.parameters:
             try:
@@ -138,6 +140,8 @@ def _wrap_get_piv(orig):
                 raise TypeError(f"{' / '.join(sliding)} is a keyword of engine='hip' only")
             if coarse is not None:
                 raise TypeError("coarse_passes is a keyword of engine='hip' only")
+            if deform is not None:
+                raise TypeError("deform_passes is a keyword of engine='hip' only")
             return orig(self, *args, **kwargs)
         # fail before any work if there is no MI355X / no library: the reference raises ValueError for an engine it cannot run
         from . import _lib
@@ -145,6 +149,11 @@ def _wrap_get_piv(orig):
         _lib.load()
         _lib.require_device()
         extra = {"coarse_passes": coarse} if coarse is not None and len(coarse) else {}
+        if deform is not None:
+            from . import window as window_mod
+
+            if window_mod.deform_count(deform):     # ValueError outside 0 .. 4; 0 is today's path
+                extra["deform_passes"] = deform
         if search_area is not None or sliding or extra:
             # the reference's method body lays the grid out by the window; with a search area of its own the engine's mirror of that
             # body (pyorc_amd.frames.get_piv: same configuration copy, coordinates, attributes and encoding) runs instead -- and with the

@@ -71,7 +71,8 @@ def _no_multipass(window_size) -> None:
     from . import window
 
     if isinstance(window_size, window.MultiPassWindow):
-        raise NotImplementedError("coarse_passes with pyorc_amd.shard is not implemented: run the chain through get_ffpiv (devices=)")
+        raise NotImplementedError(("deform_passes" if getattr(window_size, "deform", 0) and len(window_size.passes) == 1 else "coarse_passes") +
+                                  " with pyorc_amd.shard is not implemented: run the chain through get_ffpiv (devices=)")
 
 
 def sharded_piv(load_frames: Callable[[int, int], np.ndarray], n_pairs: int, window_size, overlap, comm,

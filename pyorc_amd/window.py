@@ -64,17 +64,21 @@ def search_spec(window_size, search_area_size=None):
 
 SHIFT_WINDOWS = (16, 32, 64)
 MAX_PASSES = 8
+DEFORM_WINDOWS = (16, 32, 64)
+MAX_DEFORM_PASSES = 4
 
 
 class MultiPassWindow(tuple):
     """A chain of passes as ONE window argument of the layers below ``get_ffpiv`` / ``piv_pairs``: the tuple
     itself is the FINAL pass's window ``(n, n)`` -- which lays out the grid and the result --, ``.passes`` every pass ``(n_k, overlap_k)``,
-    coarsest first, the final one last.  The chunk alignment is pass 0's, the memory plan answers for the whole chain."""
+    coarsest first, the final one last.  The chunk alignment is pass 0's, the memory plan answers for the whole chain.  ``.deform``:
+    the window deformation passes that follow the chain on the final grid (0: none)."""
 
-    def __new__(cls, passes):
+    def __new__(cls, passes, deform: int = 0):
         passes = tuple((int(n), int(o)) for n, o in passes)
         self = super().__new__(cls, (passes[-1][0], passes[-1][0]))
         self.passes = passes
+        self.deform = int(deform)
         return self
 
     @property
@@ -82,25 +86,49 @@ class MultiPassWindow(tuple):
         return (self.passes[-1][1], self.passes[-1][1])
 
 
-def multipass_spec(window_size, overlap, coarse_passes=None):
+def deform_count(deform_passes) -> int:
+    """The ``deform_passes`` keyword checked: None or a whole number 0 .. 4 -> the count.  Host-only."""
+    if deform_passes is None:
+        return 0
+    if isinstance(deform_passes, bool) or not isinstance(deform_passes, (int, np.integer)) or not 0 <= int(deform_passes) <= MAX_DEFORM_PASSES:
+        raise ValueError(f"deform_passes must be a whole number 0 .. {MAX_DEFORM_PASSES}, got {deform_passes!r}")
+    return int(deform_passes)
+
+
+def deform_supported(window_size) -> bool:
+    """Can a window deformation pass run on this final window (``lspiv_deform_supported``: square, 16, 32 or 64)?  Host-only."""
+    return bool(_lib.load().lspiv_deform_supported(int(window_size[0]), int(window_size[1])))
+
+
+def multipass_spec(window_size, overlap, coarse_passes=None, deform_passes=None):
     """``window_size`` as the layers below take it: the plain tuple without coarse passes (None or empty: today's path), else a
-    validated :class:`MultiPassWindow`.  ``coarse_passes``: coarsest first, each an int n (window n x n at overlap n / 2) or a pair
+    validated :class:`MultiPassWindow`.  ``deform_passes`` = D (0 .. 4; None or 0: none): D window deformation passes follow the chain on
+    the final grid -- then a :class:`MultiPassWindow` comes back also without coarse passes (a chain of one
+    pass), and the final window must be one of 16, 32, 64 at one overlap for both axes.  ``coarse_passes``: coarsest first, each an int n (window n x n at overlap n / 2) or a pair
     ``(n, overlap)``; the final pass is ``window_size`` / ``overlap``.  Every pass is square and even, the list is non-increasing in n,
     pass 0 takes any even square window the per-timestep path serves, every later pass one of 16, 32, 64.  Host-only."""
+    deform = deform_count(deform_passes)
     if isinstance(window_size, MultiPassWindow):
         if coarse_passes:
             raise ValueError("coarse_passes given twice: window_size is a MultiPassWindow already")
+        if deform and deform != window_size.deform:
+            raise ValueError("deform_passes given twice: window_size is a MultiPassWindow already")
         return window_size
     ws = (int(window_size[0]), int(window_size[1]))
-    if coarse_passes is None or len(coarse_passes) == 0:
+    no_coarse = coarse_passes is None or len(coarse_passes) == 0
+    if no_coarse and not deform:
         return ws
     if isinstance(window_size, SearchWindow):
-        raise NotImplementedError("coarse_passes together with a search_area_size larger than the window is not implemented")
+        raise NotImplementedError(("coarse_passes" if not no_coarse else "deform_passes") +
+                                  " together with a search_area_size larger than the window is not implemented")
     ov = (int(overlap[0]), int(overlap[1]))
+    if deform and (ws[0] != ws[1] or ws[0] not in DEFORM_WINDOWS or ov[0] != ov[1]):
+        raise ValueError(f"deform_passes need a square final window, one of {DEFORM_WINDOWS}, at one overlap for both axes, got window_size {ws}, "
+                         f"overlap {ov}")
     if ws[0] != ws[1] or ov[0] != ov[1]:
         raise ValueError(f"coarse_passes need a square window and overlap, got window_size {ws}, overlap {ov}")
     passes = []
-    for e in coarse_passes:
+    for e in ([] if no_coarse else coarse_passes):
         if isinstance(e, (int, np.integer)) and not isinstance(e, bool):
             n, o = int(e), int(e) // 2
         else:
@@ -127,7 +155,7 @@ def multipass_spec(window_size, overlap, coarse_passes=None):
             raise ValueError(f"pass {k}: window {n} is larger than pass {k - 1}'s {passes[k - 1][0]}: list the passes coarsest first")
     if _lib.load().lspiv_kernel_kind(passes[0][0], passes[0][0]) < 0:
         raise ValueError(f"pass 0: no kernel for window {passes[0][0]}")
-    return MultiPassWindow(passes)
+    return MultiPassWindow(passes, deform)
 
 
 MIN_STEERING_GRID = 3
@@ -179,7 +207,7 @@ def get_rect_coordinates(dim_size, window_size, overlap, search_area_size=None, 
 
 def required_memory(n_frames: int, dim_size, window_size, overlap, search_area_size=None,
                     dtype=np.uint8, with_planes: bool = False, sliding_blocks: int = 0, coarse_passes=None,
-                    ensemble_sums: bool = False) -> int:
+                    ensemble_sums: bool = False, deform_passes=None) -> int:
     """HBM bytes one fused call on ``n_frames`` frames needs (frames + four result planes).
 
     The reference's figure is the host RAM of the materialised window stack + correlation volume
@@ -189,18 +217,22 @@ def required_memory(n_frames: int, dim_size, window_size, overlap, search_area_s
     to every chunk (:func:`sliding_store_bytes`).  ``coarse_passes`` (or a :class:`MultiPassWindow`): a multi-pass chain.
     ``ensemble_sums``: an ensemble's plane sums and counts (:func:`ensemble_sums_bytes`) stay in HBM next to every chunk -- of the pass
     that needs most, in a chain (the multi-pass ensemble, INTEGRATION.md section 2e, runs one pass at a time).
+    ``deform_passes`` (or a :class:`MultiPassWindow` that carries them): the warped frames of one batch of pairs and the nodes
+    (:func:`deform_bytes`) come on top.
     """
-    if coarse_passes or isinstance(window_size, MultiPassWindow):
+    if coarse_passes or deform_count(deform_passes) or isinstance(window_size, MultiPassWindow):
         # a chain: the frames once, the largest pass's launch (results, rescue lists, the planes of the final pass), and the
         # intermediates of two grids -- two result blocks and an offset array of the largest grid (lspiv_piv_multipass_dev_at)
-        spec = multipass_spec(window_size, overlap, coarse_passes)
+        spec = multipass_spec(window_size, overlap, coarse_passes, deform_passes)
         frames_bytes = int(n_frames) * int(dim_size[0]) * int(dim_size[1]) * np.dtype(dtype).itemsize
         last = len(spec.passes) - 1
         per_pass = [required_memory(n_frames, dim_size, (n, n), (o, o), dtype=dtype, with_planes=with_planes and k == last) - frames_bytes
                     for k, (n, o) in enumerate(spec.passes)]
         tiles = [(int(n_frames) - 1) * int(np.prod(get_array_shape(dim_size, (n, n), (o, o)))) for n, o in spec.passes]
         sums = max(ensemble_sums_bytes(dim_size, (n, n), (o, o)) for n, o in spec.passes) if ensemble_sums else 0
-        return frames_bytes + max(per_pass) + 2 * 16 * max(tiles[:-1]) + 4 * max(tiles[1:]) + sums
+        n, o = spec.passes[-1]
+        deform = deform_bytes(n_frames, dim_size, (n, n), (o, o)) if spec.deform else 0
+        return frames_bytes + max(per_pass) + 2 * 16 * max(tiles[:-1], default=0) + 4 * max(tiles[1:], default=0) + sums + deform
     sa = window_size if search_area_size is None else search_area_size
     code = _lib.DTYPE_CODES[np.dtype(dtype)]
     r = _lib.load().lspiv_required_bytes(n_frames, dim_size[0], dim_size[1], code, sa[0], sa[1],
@@ -211,6 +243,13 @@ def required_memory(n_frames: int, dim_size, window_size, overlap, search_area_s
     if ensemble_sums:
         need += ensemble_sums_bytes(dim_size, sa, overlap)
     return need
+
+
+def deform_bytes(n_frames: int, dim_size, window_size, overlap) -> int:
+    """HBM bytes the deformation passes of a call on ``n_frames`` frames take next to the chain: the float32 warped frames of ONE batch
+    of pairs (at most 256 MiB, one frame at least) and the int32 nodes of every pair (``lspiv_deform_required_bytes``)."""
+    return _lib.check(_lib.load().lspiv_deform_required_bytes(int(n_frames), int(dim_size[0]), int(dim_size[1]), int(window_size[0]),
+                                                              int(window_size[1]), int(overlap[0]), int(overlap[1])))
 
 
 def ensemble_sums_bytes(dim_size, window_size, overlap) -> int:
