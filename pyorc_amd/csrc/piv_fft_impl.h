@@ -1310,6 +1310,46 @@ template <typename T, int N> constexpr bool kWalkRelax = ((LSPIV_WALK_RELAX & 1)
 #endif
 template <int N> constexpr bool kF32Early = LSPIV_F32_EARLY && Geo<N>::FULL;
 
+// Un-pack phase of a walking iteration in batches of B ky steps (walk_iteration, UB): the two incoming exchanges (ds_bpermute) of all
+// B steps are issued first, then the steps run in ascending ky.  Written one ky at a time, the compiler waits for each step's
+// exchanges before it issues the next step's: N / 2 + 1 dependent crossbar round trips in a row, each queued behind the other
+// waves' transposes; a batch waits once for its first pair with the other B - 1 pairs in flight behind it.  Same expressions in the
+// same order per ky, so the bits stay; a batch holds 2 B transient registers.  B <= 1: one ky at a time, the former loop.
+// The value is chosen PER KERNEL from the compiler's resource report (tools/kres.py): a batch must cost
+// no VGPR, no scratch and no wave against B = 1, otherwise the kernel keeps 1 -- as do all sizes that were not looked at.
+// -DLSPIV_UNPACK_BATCH=b forces b for every walking kernel (A/B builds; 1 = the former order everywhere).
+#ifndef LSPIV_UNPACK_BATCH
+#define LSPIV_UNPACK_BATCH -1
+#endif
+// [sample type: uint8, float32, float64][PLANES][WANT_NZ] resp. [sample type][WANT_NZ]; of the admissible candidates (6, 9, 17 at
+// 32 x 32; 4, 8 at 64 x 64) the one with the least scratch, then the largest
+constexpr int kWalkBatch32[3][2][2] = {{{9, 1}, {17, 17}}, {{1, 1}, {17, 17}}, {{17, 17}, {17, 17}}};
+constexpr int kWalkBatch64[3][2][2] = {{{1, 4}, {4, 4}}, {{1, 1}, {4, 1}}, {{1, 8}, {4, 8}}};
+constexpr int kEnsBatch32[3][2] = {{1, 17}, {6, 6}, {17, 17}};
+constexpr int kEnsBatch64[3][2] = {{1, 1}, {1, 1}, {1, 1}};   // 8 is admissible everywhere and measured no gain (uint8: 30.39 -> 30.81 ms per 1000 pairs)
+template <typename T> constexpr int kSampleKind = sizeof(T) == 1 ? 0 : sizeof(T) == 4 ? 1 : 2;
+template <typename T, int N, bool PLANES, bool WANT_NZ>
+constexpr int kWalkUnpackBatchTuned = N == 32 ? kWalkBatch32[kSampleKind<T>][PLANES][WANT_NZ] : N == 64 ? kWalkBatch64[kSampleKind<T>][PLANES][WANT_NZ] : 1;
+template <typename T, int N, bool WANT_NZ>
+constexpr int kEnsUnpackBatchTuned = N == 32 ? kEnsBatch32[kSampleKind<T>][WANT_NZ] : N == 64 ? kEnsBatch64[kSampleKind<T>][WANT_NZ] : 1;
+template <typename T, int N, bool PLANES, bool WANT_NZ>
+constexpr int kWalkUnpackBatch = LSPIV_UNPACK_BATCH >= 0 ? LSPIV_UNPACK_BATCH : kWalkUnpackBatchTuned<T, N, PLANES, WANT_NZ>;
+template <typename T, int N, bool WANT_NZ>
+constexpr int kEnsUnpackBatch = LSPIV_UNPACK_BATCH >= 0 ? LSPIV_UNPACK_BATCH : kEnsUnpackBatchTuned<T, N, WANT_NZ>;
+
+// uint8 rows (walk_iteration, U8_EARLY): the rows of BOTH frames are requested before the first is consumed -- a scheduling barrier
+// behind the two fetches; left alone, the compiler sinks the second frame's address arithmetic and loads below the wait for the
+// first frame's row -- so an iteration waits for memory once instead of twice, as the float32 path does (kF32Early).  Per kernel
+// by the same rule as the batch.  -DLSPIV_U8_EARLY=0 / 1 forces it off / on for every uint8 walking kernel.
+#ifndef LSPIV_U8_EARLY
+#define LSPIV_U8_EARLY -1
+#endif
+template <int N, bool PLANES, bool WANT_NZ> constexpr bool kWalkU8EarlyTuned = N == 32 || N == 64;
+// 32 x 32 without the score: 168 -> 171 VGPRs, a wave lost; 64 x 64: measured together with batch 8, no gain
+template <int N, bool WANT_NZ> constexpr bool kEnsU8EarlyTuned = N == 32 && WANT_NZ;
+template <int N, bool PLANES, bool WANT_NZ> constexpr bool kWalkU8Early = LSPIV_U8_EARLY >= 0 ? LSPIV_U8_EARLY != 0 : kWalkU8EarlyTuned<N, PLANES, WANT_NZ>;
+template <int N, bool WANT_NZ> constexpr bool kEnsU8Early = LSPIV_U8_EARLY >= 0 ? LSPIV_U8_EARLY != 0 : kEnsU8EarlyTuned<N, WANT_NZ>;
+
 // ---- 64 x 64 walking ENSEMBLE kernel: the job's partial sum through the idle transpose tile ----------------------------------
 // One job per wave, 256 VGPRs (no room for an accumulator), no LDS to spare next to the tile: the partial sum lives in the job's
 // 16 KB HBM slot.  Round 3 read-modified-wrote it in the plane's row-major layout -- every lane its own 256-byte row, 16 bytes at a
@@ -1574,11 +1614,32 @@ struct WalkCarry {
   }
 };
 
+// One ky of the un-packing: mr / mi = registers N - ky of the mirrored lane's xr / xi.  Both cross spectra of the step, packed for
+// the shared inverse; the carry moves on.
+template <int N>
+__device__ __forceinline__ void unpack_step(int ky, float mr, float mi, int partner_byte, WalkCarry<N>& c, float (&xr)[N], float (&xi)[N]) {
+  constexpr int H = N / 2;
+  const int kn = (N - ky) % N;
+  const float pr = xr[ky] + mr, pi = xi[ky] - mi;     // 2 F_f      (each with its frame's 1 / (2 N^2))
+  const float ar = c.fpr[ky] * pr + c.fpi[ky] * pi, ai = c.fpr[ky] * pi - c.fpi[ky] * pr;   // conj(F_prev) P
+  // the new carry is formed AFTER the last use of the old one, straight into its place: no copies on the loop back-edge
+  c.fpr[ky] = xi[ky] + mi;                            // 2 F_{f+1}
+  c.fpi[ky] = mr - xr[ky];
+  const float qr = c.fpr[ky], qi = c.fpi[ky];
+  const float br = pr * qr + pi * qi, bi = pr * qi - pi * qr;                               // conj(P) Q
+  xr[ky] = ar - bi;                // (R_a + i R_b)[ky][kx]
+  xi[ky] = ai + br;
+  if (ky >= 1 && ky < H) {         // rows above N/2: conj of (R_a - i R_b) at the mirrored lane
+    xr[kn] = bperm_f(partner_byte, ar + bi);
+    xi[kn] = -bperm_f(partner_byte, ai - br);
+  }
+}
+
 // One iteration: rows of frames f (and f + 1 when `has2`) of the job's window -> clipped planes xr (pair f-1) and xi
 // (pair f), their means (DC bins) and NaN flags; the carry moves on to frame f + 1.
 // RELAX: without the scheduling barriers between the phases (a caller with registers to spare: the 32 x 32 ensemble kernel runs two
 // waves per SIMD for its register accumulator and may use 256 VGPRs)
-template <typename T, int N, bool WANT_NZ, bool RELAX = false, bool HALF_TILE = false>
+template <typename T, int N, bool WANT_NZ, bool RELAX = false, bool HALF_TILE = false, int UB = 1, bool U8_EARLY = false>
 __device__ __forceinline__ void walk_iteration(const PivParams& p, const T* row, bool has2, float* buf, int lg,
                                                int partner_byte, int lane0_byte, WalkCarry<N>& c, float (&xr)[N],
                                                float (&xi)[N], float& mean_a, float& mean_b, bool& skip_a, bool& skip_b,
@@ -1612,6 +1673,12 @@ __device__ __forceinline__ void walk_iteration(const PivParams& p, const T* row,
     if constexpr (sizeof(T) == 1 && HALF_TILE && LSPIV_ENS64_NT) {   // the 64 x 64 ensemble kernel: frames past the L2-resident slots
       raw0.template fetch<true>(row);
       raw1.template fetch<true>(has2 ? row + p.frame_elems : row);
+    } else if constexpr (U8_EARLY && sizeof(T) == 1) {
+      const T* row1 = has2 ? row + p.frame_elems : row;
+      __builtin_amdgcn_sched_barrier(0);   // the second address is formed before the first load ...
+      raw0.fetch(row);
+      raw1.fetch(row1);
+      __builtin_amdgcn_sched_barrier(0);   // ... and the loads of both rows are out before anything waits
     } else {
       raw0.fetch(row);
       raw1.fetch(has2 ? row + p.frame_elems : row);
@@ -1641,23 +1708,29 @@ __device__ __forceinline__ void walk_iteration(const PivParams& p, const T* row,
   LSPIV_SETPRIO(LSPIV_PRIO_U);
   // un-pack the two spectra, form both cross spectra and pack them for the shared inverse, one ky at a time (a
   // step only touches registers ky and N - ky of this lane and of the mirrored lane, so it can run in place)
+  if constexpr (UB <= 1) {
 #pragma unroll
-  for (int ky = 0; ky <= H; ++ky) {
-    const int kn = (N - ky) % N;
-    const float mr = bperm_f(partner_byte, xr[kn]);
-    const float mi = bperm_f(partner_byte, xi[kn]);
-    const float pr = xr[ky] + mr, pi = xi[ky] - mi;     // 2 F_f      (each with its frame's 1 / (2 N^2))
-    const float ar = c.fpr[ky] * pr + c.fpi[ky] * pi, ai = c.fpr[ky] * pi - c.fpi[ky] * pr;   // conj(F_prev) P
-    // the new carry is formed AFTER the last use of the old one, straight into its place: no copies on the loop back-edge
-    c.fpr[ky] = xi[ky] + mi;                            // 2 F_{f+1}
-    c.fpi[ky] = mr - xr[ky];
-    const float qr = c.fpr[ky], qi = c.fpi[ky];
-    const float br = pr * qr + pi * qi, bi = pr * qi - pi * qr;                               // conj(P) Q
-    xr[ky] = ar - bi;                // (R_a + i R_b)[ky][kx]
-    xi[ky] = ai + br;
-    if (ky >= 1 && ky < H) {         // rows above N/2: conj of (R_a - i R_b) at the mirrored lane
-      xr[kn] = bperm_f(partner_byte, ar + bi);
-      xi[kn] = -bperm_f(partner_byte, ai - br);
+    for (int ky = 0; ky <= H; ++ky) {
+      const int kn = (N - ky) % N;
+      const float mr = bperm_f(partner_byte, xr[kn]);
+      const float mi = bperm_f(partner_byte, xi[kn]);
+      unpack_step<N>(ky, mr, mi, partner_byte, c, xr, xi);
+    }
+  } else {
+    // in batches of UB steps (kWalkUnpackBatch): the mirrored lane's values of the whole batch are requested before its first step
+    // runs -- they are registers that no step of the batch writes, for the same reason
+#pragma unroll
+    for (int k0 = 0; k0 <= H; k0 += UB) {
+      float mr[UB], mi[UB];
+#pragma unroll
+      for (int b = 0; b < UB && k0 + b <= H; ++b) {
+        mr[b] = bperm_f(partner_byte, xr[(N - k0 - b) % N]);
+        mi[b] = bperm_f(partner_byte, xi[(N - k0 - b) % N]);
+      }
+      __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+      for (int b = 0; b < UB && k0 + b <= H; ++b) unpack_step<N>(k0 + b, mr[b], mi[b], partner_byte, c, xr, xi);
+      __builtin_amdgcn_sched_barrier(0);
     }
   }
   mean_a = bperm_f(lane0_byte, xr[0]);   // plane means = DC bins
@@ -1738,8 +1811,8 @@ __global__ __launch_bounds__(BLOCK, (kWalkWaves<T, N>)) void piv_fft_walk_kernel
     const bool has2 = f + 1 <= p1;
     float xr[N], xi[N], mean_a, mean_b;
     bool skip_a, skip_b, dead_a, dead_b;
-    walk_iteration<T, N, WANT_NZ, kWalkRelax<T, N>>(p, row, has2, buf, lg, partner_byte, lane0_byte, carry, xr, xi, mean_a, mean_b, skip_a, skip_b,
-                                                    dead_a, dead_b);
+    walk_iteration<T, N, WANT_NZ, kWalkRelax<T, N>, false, kWalkUnpackBatch<T, N, PLANES, WANT_NZ>, kWalkU8Early<N, PLANES, WANT_NZ>>(
+        p, row, has2, buf, lg, partner_byte, lane0_byte, carry, xr, xi, mean_a, mean_b, skip_a, skip_b, dead_a, dead_b);
     if (WANT_NZ && win_dropped) skip_a = skip_b = true;
     const bool valid_a = job_valid && f > p0, valid_b = job_valid && has2;
     if constexpr (kTwoPlaneEpilogue<N>) {
@@ -2445,8 +2518,9 @@ __global__ __launch_bounds__(BLOCK, (kWalkEnsBound<T, N, WANT_NZ>)) void piv_fft
     const bool has2 = f + 1 <= p1;
     float xr[N], xi[N], mean[2];
     bool skip[2], keep[2], dead[2];
-    walk_iteration<T, N, WANT_NZ, kEnsRelax<T, N>, kEnsHalfAcc<N>>(p, row, has2, buf, lg, partner_byte, lane0_byte, carry, xr, xi, mean[0], mean[1], skip[0], skip[1],
-                                                   dead[0], dead[1], (kEnsLdsRmw<N> && !first) ? part_hi : nullptr, kEnsLdsRmw<N>);
+    walk_iteration<T, N, WANT_NZ, kEnsRelax<T, N>, kEnsHalfAcc<N>, kEnsUnpackBatch<T, N, WANT_NZ>, kEnsU8Early<N, WANT_NZ>>(
+        p, row, has2, buf, lg, partner_byte, lane0_byte, carry, xr, xi, mean[0], mean[1], skip[0], skip[1], dead[0], dead[1],
+        (kEnsLdsRmw<N> && !first) ? part_hi : nullptr, kEnsLdsRmw<N>);
     if (WANT_NZ && win_dropped) skip[0] = skip[1] = true;
     const bool valid[2] = {job_valid && f > p0, job_valid && has2};
     float vmaxs[2];

@@ -7,17 +7,30 @@ output says where each instruction belongs.  Compile-only.
 
 Prints, for the loop body (from the loop header label to the backward branch), one row per segment between two s_setprio: VALU (and how
 many of them are v_fma / v_mul / v_add / v_sub = arithmetic of the transforms, v_cvt, v_mov / v_accvgpr, DPP, v_cndmask, v_perm*,
-transcendental), LDS, VMEM, scratch, SALU, waitcnt."""
+transcendental), LDS, VMEM, scratch, SALU, waitcnt, and the LDS ROUND TRIPS the segment waits for: an `s_waitcnt lgkmcnt(n)` counts as one
+when the newest operation it needs was issued after the previous such wait -- the wave then sits out a whole LDS / crossbar latency,
+while a wait for an operation that was already in flight behind the one the previous wait needed only trails it (rt = all of them,
+rt_perm = those whose awaited operation is a ds_bpermute).  A last line gives the position of the loop's VMEM loads relative to the first
+`s_waitcnt vmcnt` behind the first of them.
+
+    --asm FILE   read the assembly from FILE (an `hipcc -S --cuda-device-only` output) instead of compiling"""
 import collections
 import re
 import subprocess
 import sys
 
-src, key = sys.argv[1], sys.argv[2]
-extra = sys.argv[3:]
-asm = "/tmp/isa_phases.s"
-subprocess.run(["/opt/rocm/bin/hipcc", "-O3", "-std=c++17", "-fPIC", "--offload-arch=gfx950", "-fno-slp-vectorize", "-S", "--cuda-device-only",
-                src, "-o", asm] + extra, check=True, capture_output=True)
+args = sys.argv[1:]
+asm = None
+if "--asm" in args:
+    k = args.index("--asm")
+    asm = args[k + 1]
+    del args[k:k + 2]
+src, key = args[0], args[1]
+extra = args[2:]
+if asm is None:
+    asm = "/tmp/isa_phases.s"
+    subprocess.run(["/opt/rocm/bin/hipcc", "-O3", "-std=c++17", "-fPIC", "--offload-arch=gfx950", "-fno-slp-vectorize", "-S", "--cuda-device-only",
+                    src, "-o", asm] + extra, check=True, capture_output=True)
 txt = open(asm).read()
 m = re.search(r"\n(_Z\w*" + re.escape(key) + r"\w*):[^\n]*\n(.*?)s_endpgm", txt, re.S)
 if not m:
@@ -77,15 +90,34 @@ def classify(l):
     return c
 
 
+def lgkm_wait(l):
+    """n of an s_waitcnt that names lgkmcnt(n), else None"""
+    mm = re.search(r"lgkmcnt\((\d+)\)", l) if l.startswith("s_waitcnt") else None
+    return int(mm.group(1)) if mm else None
+
+
 segs, cur, prio = [], collections.Counter(), "?"
+issued = []      # the LGKM operations in issue order (LDS returns in order): True = ds_bpermute
+needed = 0       # operations [0, needed) are known complete
+mark = 0         # len(issued) at the last wait that needed something new
 for l in body:
     if l.startswith("s_setprio"):
         segs.append((prio, cur))
         cur, prio = collections.Counter(), l.split()[1]
         continue
     cur += classify(l)
+    op = l.split()[0]
+    if op.startswith("ds_") or op.startswith(("s_load", "s_buffer_load")):
+        issued.append("bpermute" in op)
+    n = lgkm_wait(l)
+    if n is not None and len(issued) - n > needed:
+        newest = len(issued) - n - 1           # the newest operation this wait needs
+        if newest >= mark:                     # issued after the previous wait: a whole round trip
+            cur["rt"] += 1
+            cur["rt_perm"] += 1 if issued[newest] else 0
+        needed, mark = newest + 1, len(issued)
 segs.append((prio, cur))
-cols = ["valu", "arith_f32", "cvt", "mov", "cndmask", "int/bit", "minmax/cmp", "trans", "dpp", "other_valu", "lds", "lds_perm", "vmem", "scratch", "salu", "waitcnt"]
+cols = ["valu", "arith_f32", "cvt", "mov", "cndmask", "int/bit", "minmax/cmp", "trans", "dpp", "other_valu", "lds", "lds_perm", "vmem", "scratch", "salu", "waitcnt", "rt", "rt_perm"]
 print(f"loop body: {len(body)} instructions, {len(segs)} segments (priority after the s_setprio that opens the segment)")
 print("seg prio " + " ".join(f"{c:>10s}" for c in cols))
 tot = collections.Counter()
@@ -93,3 +125,9 @@ for k, (p, c) in enumerate(segs):
     tot += c
     print(f"{k:3d} {p:>4s} " + " ".join(f"{c[x]:10d}" for x in cols))
 print("    all " + " ".join(f"{tot[x]:10d}" for x in cols))
+# VMEM loads of the loop against the first wait for one of them
+loads = [i for i, l in enumerate(body) if l.startswith(("global_load", "buffer_load", "flat_load")) and "_lds_" not in l]
+if loads:
+    first_wait = next((i for i in range(loads[0], len(body)) if body[i].startswith("s_waitcnt") and "vmcnt" in body[i]), len(body))
+    ahead = sum(1 for i in loads if i < first_wait)
+    print(f"vmem loads: {len(loads)} in the loop, {ahead} issued before the first vmcnt wait behind them ({body[first_wait] if first_wait < len(body) else 'none in the loop'})")
