@@ -777,7 +777,10 @@ int lspiv_ensemble_sliding_finish(lspiv_ensemble* h, float count_min, int64_t fi
   const int lane_major = h->sl_layout == 2 ? h->wy : 0;   // as the accumulate calls wrote the store, whatever 'walk' says now
   // tiles of outputs sized to the plane workspace: what it already holds, at least 256 MiB worth, at least one output
   const size_t out_bytes = n_win * plane * sizeof(float);
-  int64_t tile = (int64_t)(std::max<size_t>(c->planes_cap, (size_t)256 << 20) / out_bytes);
+  // (test hook: LSPIV_SLIDING_TILE_BYTES, read on every call, stands in for that size, so that a few outputs make several tiles)
+  const char* tile_env = getenv("LSPIV_SLIDING_TILE_BYTES");
+  const size_t tile_bytes = tile_env ? (size_t)std::max<long long>(0, atoll(tile_env)) : std::max<size_t>(c->planes_cap, (size_t)256 << 20);
+  int64_t tile = (int64_t)(tile_bytes / out_bytes);
   tile = std::max<int64_t>(1, std::min<int64_t>(tile, std::min<int64_t>(n_out, 65535)));
   tile = std::max<int64_t>(1, std::min<int64_t>(tile, (int64_t)(0x7fffffff / n_win)));   // (records carry the tile's plane index in 32 bits)
   int64_t flagged = 0, rescued = 0, skipped = 0;

@@ -492,8 +492,13 @@ static int pass_grid(int64_t H, int64_t W, int wy, int wx, int oy, int ox, lspiv
 // batch by batch -- warp, mixed-type kernel, rescue pass, nodes added -- before the workspace is reused.  Results are per pair, so the
 // batching cannot change a bit.
 constexpr size_t kDeformWsBytes = (size_t)256 << 20;
+// test hook: LSPIV_DEFORM_WS_BYTES stands in for kDeformWsBytes (read on every call), so that a small stack runs in several batches
+static size_t deform_ws_bytes() {
+  if (const char* e = getenv("LSPIV_DEFORM_WS_BYTES")) return (size_t)std::max<long long>(0, atoll(e));
+  return kDeformWsBytes;
+}
 static int64_t deform_batch_pairs(int64_t n_pairs, int64_t H, int64_t W) {
-  const int64_t fit = std::max<int64_t>(1, (int64_t)(kDeformWsBytes / ((size_t)H * (size_t)W * sizeof(float))));
+  const int64_t fit = std::max<int64_t>(1, (int64_t)(deform_ws_bytes() / ((size_t)H * (size_t)W * sizeof(float))));
   return std::max<int64_t>(1, std::min<int64_t>(std::min<int64_t>(n_pairs, fit), 65535));   // (65535: the warp's grid runs the pairs along z)
 }
 static int check_deform(int wy, int wx, int oy, int ox, int64_t H, int64_t W) {

@@ -250,3 +250,26 @@ def accuracy_figures(u, v):
     e = flow_error(u, v, (160, 200), n, ov)
     e = e[np.isfinite(e)]
     return float(np.median(e)), float((e <= 0.1).mean())
+
+
+# ---- the float64 rescue pass on warped windows: the inputs of tests/test_gpu_rescue_modes.py (stack and geometries: tests/multipass_ref.py) ----
+RESCUE_FIELDS = ("uniform", "mixed")
+
+
+@functools.lru_cache(maxsize=None)
+def rescue_nodes(n, overlap, field):
+    """int32 nodes (P, rows, cols, 2) {v, u} in 1 / 128 px.  "uniform": u = 1 px everywhere, the speckles' drift (the warp is a whole-pixel
+    move, the residual exactly 0); "mixed": every other column of nodes at u = 0.5 px, every other row at v = -37 / 128 px (the warp
+    interpolates: the speckles spread over two to four samples)."""
+    rows, cols = (len(q) for q in mp.grid_origins(mp.RESCUE_DIM, n, overlap))
+    nodes = np.zeros((mp.RESCUE_T - 1, rows, cols, 2), dtype=np.int32)
+    nodes[..., 1] = 128
+    if field == "mixed":
+        nodes[:, :, 1::2, 1] = 64
+        nodes[:, 1::2, :, 0] = -37
+    return nodes
+
+
+@functools.lru_cache(maxsize=None)
+def rescue_ref(n, overlap, field, dtype=np.uint8):
+    return deformed_piv(mp.rescue_stack(dtype), n, overlap, rescue_nodes(n, overlap, field))

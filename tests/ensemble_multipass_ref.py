@@ -221,3 +221,23 @@ def speckle_shift():
 @functools.lru_cache(maxsize=None)
 def speckle_ref():
     return ensemble_pass(speckle_stack(), *RESCUE, speckle_shift(), n_frames=1, **KW)
+
+
+# ---- the shifted ensemble over more than one pair-block (16 pairs): the inputs of tests/test_gpu_batch_loops.py -----------------------------
+LONG_T = 36                               # 35 pairs: pair-blocks 16 + 16 + 3 in one accumulate call
+LONG_CHUNKS = [(0, 18), (17, 36)]         # 17 + 18 pairs: two kept chunks of two pair-blocks each (16 + 1, 16 + 2)
+LONG_DTYPES = (np.float32, np.float64)
+
+
+@functools.lru_cache(maxsize=None)
+def long_speckle_stack(dtype=np.uint8, stepped=False):
+    """``stepped`` (tests/sliding_ref.py ``speckle_stack``): some pairs move 2 px, more of them after frame 20 -- the fit of a flagged
+    window then depends on which pairs the float64 sums hold; on the steady stack it does not."""
+    from tests import sliding_ref
+
+    return as_samples(sliding_ref.speckle_stack(T=LONG_T, stepped=stepped), dtype)
+
+
+@functools.lru_cache(maxsize=None)
+def long_speckle_ref(dtype=np.uint8, stepped=False):
+    return ensemble_pass(long_speckle_stack(dtype, stepped).astype(np.float64), *RESCUE, speckle_shift(), n_frames=1, **KW)

@@ -4,6 +4,7 @@ Like the rest of the PIV path it is this project's reading: unpinned against a r
 
 All pass-to-pass arithmetic is in the kernels' orientation (u column shift, v row shift, rows downward); SEMANTICS["v_sign"] is applied
 once, to the result of a shifted pass or of a chain."""
+import functools
 import warnings
 
 import numpy as np
@@ -141,3 +142,37 @@ def multipass(imgs, passes, signal_threshold=None):
     if po.SEMANTICS["v_sign"]:
         out[-1] = dict(out[-1], v=-out[-1]["v"])
     return out
+
+
+# ---- the float64 rescue pass on shifted windows: the inputs of tests/test_gpu_rescue_modes.py ------------------------------------------------
+# single-pixel speckles on a 16 px lattice drifting 1 px per frame (tests/sliding_ref.py ``speckle_stack``): every correlation peak sits on
+# exactly-zero neighbours, the worst case of the float32 fit, so windows are flagged
+RESCUE_GEOMETRIES = [(16, 8), (32, 16), (64, 32), (64, 48)]
+RESCUE_DIM = (136, 200)
+RESCUE_T = 5
+
+
+@functools.lru_cache(maxsize=None)
+def rescue_stack(dtype=np.uint8):
+    from tests import sliding_ref
+
+    return sliding_ref.as_samples(sliding_ref.speckle_stack(T=RESCUE_T, H=RESCUE_DIM[0], W=RESCUE_DIM[1], seed=11), dtype)
+
+
+@functools.lru_cache(maxsize=None)
+def rescue_offsets(n, overlap):
+    """Raw int16 offsets (P, rows, cols, 2) {dy, dx}: every other column of windows follows the drift (residual 0, the others keep 1 px),
+    every other pair sits 2 px lower -- and, in the speckle part, offsets that point out of the frame: pair 0's top row up, pair 2's left
+    column to the left (``clamp_shift`` brings both back to 0)."""
+    rows, cols = (len(q) for q in grid_origins(RESCUE_DIM, n, overlap))
+    sh = np.zeros((RESCUE_T - 1, rows, cols, 2), dtype=np.int16)
+    sh[:, :, 1::2, 1] = 1
+    sh[1::2, :, :, 0] = 2
+    sh[0, 0, :, 0] = -3
+    sh[2, :, 0, 1] = -2
+    return sh
+
+
+@functools.lru_cache(maxsize=None)
+def rescue_ref(n, overlap, dtype=np.uint8):
+    return shifted_piv(rescue_stack(dtype).astype(np.float64), n, overlap, rescue_offsets(n, overlap))

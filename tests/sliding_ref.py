@@ -101,10 +101,13 @@ RESCUE_CHUNKS = [(0, 5), (4, 9)]         # two accumulate calls of 4 pairs: outp
 
 
 @functools.lru_cache(maxsize=None)
-def speckle_stack(T=9, H=200, W=264, seed=11):
+def speckle_stack(T=9, H=200, W=264, seed=11, stepped=False):
     """The recipe of tests/test_gpu_parity.py (``_speckle_and_particles``).  Left part: one single-pixel speckle per 16 x 16 cell
     drifting one pixel per frame -- every correlation peak sits on exactly-zero neighbours, the worst case of the float32 fit, so
-    windows are flagged; right part: an ordinary sparse particle image."""
+    windows are flagged; right part: an ordinary sparse particle image.
+    ``stepped``: the speckles jump one pixel further at every 8th frame and, after frame 20, at every 3rd: a pair across a jump moves
+    2 px (3 px at frame 32), so a mean plane has its peak at 1 px, a smaller one at 2 px and exactly zero on the other side -- still the
+    worst case of the float32 fit, but the fit now depends on WHICH pairs are in the sum."""
     rng = np.random.default_rng(seed)
     fr = particle_stack(T, H, W, seed=seed, density=0.012)
     half = (W // 32) * 16
@@ -112,7 +115,7 @@ def speckle_stack(T=9, H=200, W=264, seed=11):
     ys, xs = np.meshgrid(np.arange(8, H, 16), np.arange(8, half - 8, 16), indexing="ij")
     amp = rng.integers(100, 255, ys.shape)
     for t in range(T):
-        fr[t, ys, xs + t] = amp
+        fr[t, ys, xs + t + (t // 8 + max(0, t - 20) // 3 if stepped else 0)] = amp
     return fr
 
 
@@ -143,3 +146,20 @@ def signal_ref(mode):
     output's frames, the device's the whole stack -- tests/test_sliding_host.py checks that both keep the same positions here."""
     with po.semantics(signal_mode=mode):
         return sliding_piv(signal_stack(), np.ones(12), (32, 32), (16, 16), 4, 2, signal_threshold=SIGNAL_THR, **KW)
+
+
+# ---- more than one tile of outputs, pair-block and kept chunk: the inputs of tests/test_gpu_batch_loops.py ----------------------------------
+# (case: frames, M, s, the two accumulate calls).  "long": 40 pairs, 10 blocks, 6 outputs; the rescue sums in blocks of 16 pairs per kept
+# chunk: outputs 0 .. 3 straddle pair 16, output 4 = pairs [16, 36) straddles pair 32; in two calls of 20 pairs each chunk holds the
+# ragged blocks 16 + 4.  "many": 35 pairs, 17 blocks, 16 outputs
+# "stepped": "long" on the stepped stack -- the flagged windows of "long" and "many" have the same fit whichever pairs are summed (every
+# pair moves 1 px), those of "stepped" do not: an output that sums another output's pairs, or drops a pair-block, moves
+LOOP_CASES = {"long": (41, 20, 4, [(0, 21), (20, 41)], False), "many": (36, 4, 2, [(0, 17), (16, 36)], False),
+              "stepped": (41, 20, 4, [(0, 21), (20, 41)], True)}
+LOOP_WINDOW = ((32, 32), (16, 16))
+
+
+@functools.lru_cache(maxsize=None)
+def loop_ref(case):
+    T, M, s, _, stepped = LOOP_CASES[case]
+    return sliding_piv(speckle_stack(T=T, stepped=stepped), np.ones(T - 1), *LOOP_WINDOW, M, s, **KW)

@@ -183,3 +183,37 @@ def test_planner_adds_one_batch_of_warped_frames_and_the_nodes(lib):
     assert window.deform_bytes(3, (20000, 20000), (64, 64), (32, 32)) - 2 * int(np.prod(window.get_array_shape((20000, 20000), (64, 64), (32, 32)))) * 8 \
         == 20000 * 20000 * 4
     assert window.chunk_alignment(window.multipass_spec((32, 32), (16, 16), None, 1), dim, (16, 16)) == window.chunk_alignment((32, 32), dim, (16, 16))
+
+
+# ---- the inputs of tests/test_gpu_rescue_modes.py and tests/test_gpu_batch_loops.py ---------------------------------------------------------
+@pytest.mark.parametrize("n,ov", ref.mp.RESCUE_GEOMETRIES, ids=[f"{n}@{ov}" for n, ov in ref.mp.RESCUE_GEOMETRIES])
+def test_rescue_inputs_have_no_ties(n, ov):
+    """Measured: tie share 0.0 for both node fields at every geometry and sample type; finite windows 94.5 % / 94.3 % (uniform / mixed) at
+    16 @ 8, 100 % / 93.5 % at 32 @ 16, all of them at 64 @ 32 and 64 @ 48."""
+    for field in ref.RESCUE_FIELDS:
+        for dtype in ref.PASS_DTYPES:
+            r = ref.rescue_ref(n, ov, field, dtype)
+            print(n, ov, field, dtype.__name__, "ties:", float(r["tie"].mean()), "finite:", float(np.isfinite(r["u"]).mean()))
+            assert r["tie"].mean() <= 0.01 and np.isfinite(r["u"]).mean() >= 0.93
+    uniform, mixed = (ref.rescue_nodes(n, ov, f) for f in ref.RESCUE_FIELDS)
+    assert (uniform[..., 1] == 128).all() and not uniform[..., 0].any()
+    assert {tuple(q) for q in mixed.reshape(-1, 2)} == {(0, 128), (0, 64), (-37, 128), (-37, 64)}
+    # the uniform field is a whole-pixel move of frame t+1: the warp interpolates nothing
+    a = ref.mp.rescue_stack()
+    assert np.array_equal(ref.rescue_ref(n, ov, "uniform")["warped"][:, :, :-1], a[1:, :, 1:].astype(np.float64))
+
+
+def test_batch_workspaces_of_one_and_two_frames_cut_the_pass_cases_into_batches(lib):
+    """LSPIV_DEFORM_WS_BYTES, as tests/test_gpu_batch_loops.py sets it: lspiv_deform_required_bytes reports the batch it gives."""
+    import os
+    from unittest import mock
+
+    for case, (n, ov, (H, W)) in ref.PASS_CASES.items():
+        n_win = int(np.prod(window.get_array_shape((H, W), (n, n), (ov, ov))))
+        nodes = (ref.PASS_T - 1) * n_win * 8
+        frame = H * W * 4
+        assert lib.lspiv_deform_required_bytes(ref.PASS_T, H, W, n, n, ov, ov) == 3 * frame + nodes          # unset: one batch
+        for env, batch in ((frame, 1), (2 * frame, 2), (2 * frame - 1, 1), (1, 1), (0, 1), (3 * frame, 3), (1 << 40, 3)):
+            with mock.patch.dict(os.environ, {"LSPIV_DEFORM_WS_BYTES": str(env)}):
+                assert lib.lspiv_deform_required_bytes(ref.PASS_T, H, W, n, n, ov, ov) == batch * frame + nodes, (case, env)
+        assert lib.lspiv_deform_required_bytes(ref.PASS_T, H, W, n, n, ov, ov) == 3 * frame + nodes

@@ -163,3 +163,24 @@ def test_planner_counts_the_ensemble_sums_of_the_largest_pass(lib):
     plain = window.required_memory(T, dim, (32, 32), (16, 16))
     assert window.required_memory(T, dim, (32, 32), (16, 16), ensemble_sums=True) - plain == sums[1]
     assert window.required_memory(T, dim, (32, 32), (16, 16), ensemble_sums=False) == plain
+
+
+def test_long_rescue_input_is_clear_of_the_caps_and_spans_three_pair_blocks():
+    """The input of tests/test_gpu_batch_loops.py's shifted ensemble: 35 pairs (pair-blocks 16 + 16 + 3; in two calls 16 + 1 and 16 + 2).
+    Measured: tie share 0.0, no NaN, on both sample types and both stacks."""
+    P = ref.LONG_T - 1
+    (f0, f1), (g0, g1) = ref.LONG_CHUNKS
+    assert P > 32 and P % 16 and f0 == 0 and f1 - 1 == g0 and g1 == ref.LONG_T and f1 - 1 > 16 and g1 - 1 - g0 > 16
+    for dtype in ref.LONG_DTYPES:
+        for stepped in (False, True):
+            r = ref.long_speckle_ref(dtype, stepped)
+            input_is_clear_of_the_caps(r, **ref.KW, name=("long speckle", dtype, stepped))
+            assert np.array_equal(r["shift"], ref.speckle_shift()) and np.isfinite(r["u"]).all()
+            # the sum over one call's pairs alone: on the stepped stack every window of the speckle part (columns 0 .. 6) moves, by at
+            # least 8e-3 px (measured); on the steady stack none of them moves at all -- only the stepped stack can tell which pairs were summed
+            a = ref.long_speckle_stack(dtype, stepped).astype(np.float64)
+            for f0, f1 in ref.LONG_CHUNKS:
+                part = ref.ensemble_pass(a[f0:f1], *ref.RESCUE, ref.speckle_shift(), n_frames=1, **ref.KW)
+                move = np.abs(part["u"] - r["u"])[0, :, :7]
+                print(dtype.__name__, stepped, (f0, f1), "speckle windows: smallest move", float(move.min()), "largest", float(move.max()))
+                assert (move > 1e-3).all() if stepped else (move < 1e-9).all()
