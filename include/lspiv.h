@@ -121,7 +121,13 @@ int         lspiv_synchronize(void);                    /* hipDeviceSynchronize 
  *   "rescue"           1 (default; environment LSPIV_RESCUE) | 0 float32 results as they are;
  *   "rescue_kappa"     plane noise the flag model assumes, in 1e-9 of the plane maximum (default 500);
  *   "rescue_tau"       relative gap between the two largest samples below which the arg-max counts as ambiguous and the whole
- *                      plane is re-evaluated, in 1e-9 (default 4000).
+ *                      plane is re-evaluated, in 1e-9 (default 4000);
+ *   "rescue_generic"   0 (default; environment LSPIV_RESCUE_GENERIC) square 16 / 32 / 64 px windows without a search area take fit
+ *                      kernels with the window size known at compile time | 1 every launch takes the run-time-geometry
+ *                      kernel.  The results are the same bit for bit; 1 is the reference of that claim
+ *                      (tests/test_gpu_rescue_fixed_size.py);
+ *   "rescue_fit_size"  read-only (lspiv_get_option): the compile-time window size of the fit kernel the last rescue pass of the
+ *                      process launched, 0 the run-time-geometry kernel, -1 no pass yet.  For tests of the dispatch.
  * float64 HOST stacks are narrowed to float32 while they are staged (the kernels compute in float32).  A frame that rides on a
  * DC offset far above its contrast would lose the low bits of its texture in that conversion, where the reference normalises
  * every window in float64; the per-window normalisation does not see a constant added to a frame, so:

@@ -157,6 +157,8 @@ std::atomic<int> g_opt_norm_clip{getenv("LSPIV_NORM_CLIP") && atoi(getenv("LSPIV
 std::atomic<int> g_opt_std_ddof{env_opt("LSPIV_STD_DDOF", 0, 1)};
 std::atomic<int> g_opt_round_odd{env_opt("LSPIV_ROUND_ODD", 0, 2)};
 std::atomic<int> g_opt_rescue{env_opt_def("LSPIV_RESCUE", 0, 1, 1)};
+std::atomic<int> g_opt_rescue_generic{env_opt("LSPIV_RESCUE_GENERIC", 0, 1)};
+std::atomic<int> g_rescue_fit_size{-1};
 std::atomic<int> g_opt_narrow_offset{env_opt_def("LSPIV_NARROW_OFFSET", -1, 1 << 30, 1024)};
 std::atomic<int> g_opt_rescue_kappa{env_opt_def("LSPIV_RESCUE_KAPPA", 0, 1000000, 500)};
 std::atomic<int> g_opt_rescue_tau{env_opt_def("LSPIV_RESCUE_TAU", 0, 1000000, 4000)};
@@ -182,6 +184,8 @@ static const Option kOptions[] = {
     {"std_ddof", &g_opt_std_ddof, 0, 1, "std_ddof must be 0 (population standard deviation) or 1 (sample)"},
     {"round_odd", &g_opt_round_odd, 0, 2, "round_odd must be 0 (half-even of x / 2), 1 (up) or 2 (down)"},
     {"rescue", &g_opt_rescue, 0, 1, "rescue must be 0 (float32 results as they are) or 1 (float64 rescue pass)"},
+    {"rescue_generic", &g_opt_rescue_generic, 0, 1,
+     "rescue_generic must be 0 (fixed-size fit kernels for square 16 / 32 / 64 px windows) or 1 (run-time geometry for every launch)"},
     {"narrow_offset", &g_opt_narrow_offset, -1, INT_MAX,
      "narrow_offset must be -1 (never) or the smallest |DC offset| of a float64 frame that is removed while narrowing"},
     {"rescue_kappa", &g_opt_rescue_kappa, 0, 1000000, "rescue_kappa must be 0 .. 1000000 (units of 1e-9)"},
@@ -270,6 +274,7 @@ int lspiv_set_option(const char* name, int value) {
     g_opt_walk.store(value);
     return LSPIV_OK;
   }
+  if (strcmp(name, "rescue_fit_size") == 0) return fail(LSPIV_EINVAL, "rescue_fit_size is read-only");
   const Option* o = find_option(name);
   if (!o) return fail(LSPIV_EINVAL, "unknown option '%s'", name);
   if (value < o->lo || value > o->hi) return fail(LSPIV_EINVAL, "%s", o->range);
@@ -279,6 +284,7 @@ int lspiv_set_option(const char* name, int value) {
 int lspiv_get_option(const char* name, int* value) {
   if (!name || !value) return fail(LSPIV_EINVAL, "NULL argument");
   if (strcmp(name, "walk") == 0) { *value = lspiv::walk_setting(); return LSPIV_OK; }
+  if (strcmp(name, "rescue_fit_size") == 0) { *value = g_rescue_fit_size.load(); return LSPIV_OK; }
   const Option* o = find_option(name);
   if (!o) return fail(LSPIV_EINVAL, "unknown option '%s'", name);
   *value = o->value->load();

@@ -14,6 +14,7 @@
 
 #include "common.h"
 #include "host_stage.h"
+#include "rescue_options.h"
 
 namespace lspiv_api __attribute__((visibility("hidden"))) {
 
@@ -207,6 +208,7 @@ extern std::atomic<int> g_opt_round_odd;     // round_to_even of odd sizes: 0 ha
 extern std::atomic<int> g_opt_rescue;
 extern std::atomic<int> g_opt_rescue_kappa;
 extern std::atomic<int> g_opt_rescue_tau;
+// ("rescue_generic" and the read-only "rescue_fit_size": rescue_options.h, shared with piv_rescue.hip)
 // float64 host stacks: a frame whose DC offset (host_stage.h, frame_offset) reaches this magnitude has it taken off while it is
 // narrowed to float32 -- PIV entry points only (the per-window normalisation does not see it), and only without a signal threshold
 // (which counts samples != 0).  -1: never.

@@ -19,9 +19,11 @@
 //
 // A fixed grid strides over both lists; its last block moves the counts to the statistics fields and zeroes the counters, so
 // a pass costs one extra launch and no memset.
+#include <atomic>
 #include <type_traits>
 
 #include "common.h"
+#include "rescue_options.h"
 
 namespace lspiv {
 
@@ -62,23 +64,40 @@ __device__ __forceinline__ double wave_sum_d(double x) {
 // mean / population std of both windows of a pair in float64, by one wave (every lane gets the totals); the two windows go
 // through the same loops and the loops are unrolled so that a batch of independent loads is in flight per wait
 // lane -> its samples e = lane, lane + 64, ...: (y, x) advanced without a division per sample
+// (WX: the width at compile time, 0 = run time.  A width that divides 64 leaves qx = 0: a lane keeps its column and its rows step by
+// 64 / WX -- 4, 2, 1 at 16, 32, 64 --, so everything that depends on x alone is a lane constant the compiler moves out of the loops)
+template <int WX = 0>
 struct LaneWalk {
+  static constexpr bool kColumn = WX != 0 && 64 % (WX ? WX : 1) == 0;
   int qy, qx, wx;   // 64 = qy * wx + qx
   __device__ LaneWalk(int wx_) : qy(64 / wx_), qx(64 - (64 / wx_) * wx_), wx(wx_) {}
   __device__ __forceinline__ void start(int lane, int& y, int& x) const { y = lane / wx; x = lane - y * wx; }
   __device__ __forceinline__ void next(int& y, int& x) const {
-    y += qy; x += qx;
-    if (x >= wx) { x -= wx; ++y; }
+    if constexpr (kColumn) {
+      y += 64 / (WX ? WX : 1);
+    } else {
+      y += qy; x += qx;
+      if (x >= wx) { x -= wx; ++y; }
+    }
   }
 };
+// v in [0, 2 w) folded back into [0, w): a mask when w is a power of two known at compile time (WN; 0 = run time)
+template <int WN>
+__device__ __forceinline__ int wrap_once(int v, int w) {
+  if constexpr (WN != 0 && (WN & (WN - 1)) == 0) return v & (WN - 1);
+  else return v >= w ? v - w : v;
+}
 
 // TB: the sample type of window B (the float32 workspace of a deformation pass under a uint8 / float64 stack; else T)
-template <typename T, bool STAGE = false, typename TB = T>
-__device__ __forceinline__ void window_stats_wave2(const T* A, const TB* B, int W, int wy, int wx, int lane, double& mean_a,
+// WY, WX: the window size at compile time (the fixed-size instantiations of the fit kernel), 0 = the arguments.  ONE body: the
+// expressions and their order are the same, so every float64 result has the same bits either way.
+template <typename T, bool STAGE = false, typename TB = T, int WY = 0, int WX = 0>
+__device__ __forceinline__ void window_stats_wave2(const T* A, const TB* B, int W, int wy_, int wx_, int lane, double& mean_a,
                                                    double& sd_a, double& mean_b, double& sd_b, T* la = nullptr,
                                                    typename std::common_type<TB>::type* lb = nullptr) {   // (lb: TB is deduced from B alone)
+  const int wy = WY ? WY : wy_, wx = WX ? WX : wx_;
   const int n = wy * wx;
-  const LaneWalk lw(wx);
+  const LaneWalk<WX> lw(wx);
   // one pass over shifted samples d = x - x[0]: mean = x0 + S1 / n, variance = (S2 - S1^2 / n) / n.  With the shift the
   // cancellation costs ~1e-16 (mean - x0)^2 / variance relative -- 1e-13 at worst for 8-bit imagery -- and a constant window
   // still has exactly zero variance (all d are 0).
@@ -108,17 +127,24 @@ __device__ __forceinline__ void window_stats_wave2(const T* A, const TB* B, int 
 // search-area mode (p.nw != 0; piv_fft_impl.h): the window of frame t is the central nw x nw block of its wy x wx tile, normalised over
 // its own samples and zero elsewhere ("masked a"), the window of frame t+1 the whole tile; the sums are scaled by 1 / nw^2 and stay
 // circular at the tile size.  p.nw == 0: everything below is what it was.
+// (FIXED: a fixed-size instantiation, which only launches with p.nw == 0 take)
+template <bool FIXED = false>
 __device__ __forceinline__ bool a_inside(const PivParams& p, int y, int x) {
+  if constexpr (FIXED) return true;
   const int o = (p.wy - p.nw) >> 1;
   return p.nw == 0 || ((unsigned)(y - o) < (unsigned)p.nw && (unsigned)(x - o) < (unsigned)p.nw);
 }
-__device__ __forceinline__ double corr_samples(const PivParams& p) { return p.nw ? (double)p.nw * (double)p.nw : (double)p.wy * (double)p.wx; }
+template <int WY = 0, int WX = 0>
+__device__ __forceinline__ double corr_samples(const PivParams& p) {
+  if constexpr (WY != 0) return (double)WY * (double)WX;
+  return p.nw ? (double)p.nw * (double)p.nw : (double)p.wy * (double)p.wx;
+}
 // statistics of both windows of a pair: over the tile, and -- search-area mode -- those of frame t again over its block
-template <typename T, bool STAGE = false, typename TB = T>
+template <typename T, bool STAGE = false, typename TB = T, int WY = 0, int WX = 0>
 __device__ __forceinline__ void pair_stats_wave(const PivParams& p, const T* A, const TB* B, int lane, double& mean_a, double& sd_a,
                                                 double& mean_b, double& sd_b, T* la = nullptr, TB* lb = nullptr) {
-  window_stats_wave2<T, STAGE, TB>(A, B, p.W, p.wy, p.wx, lane, mean_a, sd_a, mean_b, sd_b, la, lb);
-  if (p.nw) {
+  window_stats_wave2<T, STAGE, TB, WY, WX>(A, B, p.W, p.wy, p.wx, lane, mean_a, sd_a, mean_b, sd_b, la, lb);
+  if (WY == 0 && p.nw) {
     const int o = (p.wy - p.nw) >> 1;
     const T* Ab = A + (int64_t)o * p.W + o;
     double mb, sb;
@@ -134,26 +160,28 @@ __device__ __forceinline__ double norm_clip(double x, double mean, double inv_sd
 }
 
 // un-shifted lag of a shifted plane coordinate
-__device__ __forceinline__ int unshift(int ip, int c, int w) { return ip - c < 0 ? ip - c + w : ip - c; }
+template <int WN = 0>
+__device__ __forceinline__ int unshift(int ip, int c, int w) {
+  if constexpr (WN != 0 && (WN & (WN - 1)) == 0) return (ip - c) & (WN - 1);
+  else return ip - c < 0 ? ip - c + w : ip - c;
+}
 
 // which of two shifted plane positions holds the larger float64 correlation (ties: the smaller row-major index, np.argmax)
-template <typename PA, typename PB>
+template <int WY = 0, int WX = 0, typename PA, typename PB>
 __device__ __forceinline__ uint32_t choose_wave(const PivParams& p, PA A, PB B, int pitch, double mean_a, double inv_a, double mean_b,
                                                 double inv_b, uint32_t pos1, uint32_t pos2, int lane) {
-  const int wy = p.wy, wx = p.wx, n = wy * wx, cy = wy / 2, cx = wx / 2;
-  const int ky1 = unshift((int)(pos1 >> 16), cy, wy), kx1 = unshift((int)(pos1 & 0xffffu), cx, wx);
-  const int ky2 = unshift((int)(pos2 >> 16), cy, wy), kx2 = unshift((int)(pos2 & 0xffffu), cx, wx);
-  const LaneWalk lw(wx);
+  const int wy = WY ? WY : p.wy, wx = WX ? WX : p.wx, n = wy * wx, cy = wy / 2, cx = wx / 2;
+  const int ky1 = unshift<WY>((int)(pos1 >> 16), cy, wy), kx1 = unshift<WX>((int)(pos1 & 0xffffu), cx, wx);
+  const int ky2 = unshift<WY>((int)(pos2 >> 16), cy, wy), kx2 = unshift<WX>((int)(pos2 & 0xffffu), cx, wx);
+  const LaneWalk<WX> lw(wx);
   double acc1 = 0.0, acc2 = 0.0;
   int y, x;
   lw.start(lane, y, x);
 #pragma unroll 4
   for (int e = lane; e < n; e += 64, lw.next(y, x)) {
-    const double av = a_inside(p, y, x) ? norm_clip((double)A[y * pitch + x], mean_a, inv_a) : 0.0;
-    int y1 = y + ky1; y1 = y1 >= wy ? y1 - wy : y1;
-    int x1 = x + kx1; x1 = x1 >= wx ? x1 - wx : x1;
-    int y2 = y + ky2; y2 = y2 >= wy ? y2 - wy : y2;
-    int x2 = x + kx2; x2 = x2 >= wx ? x2 - wx : x2;
+    const double av = a_inside<WY != 0>(p, y, x) ? norm_clip((double)A[y * pitch + x], mean_a, inv_a) : 0.0;
+    const int y1 = wrap_once<WY>(y + ky1, wy), x1 = wrap_once<WX>(x + kx1, wx);
+    const int y2 = wrap_once<WY>(y + ky2, wy), x2 = wrap_once<WX>(x + kx2, wx);
     acc1 += av * norm_clip((double)B[y1 * pitch + x1], mean_b, inv_b);
     acc2 += av * norm_clip((double)B[y2 * pitch + x2], mean_b, inv_b);
   }
@@ -166,34 +194,30 @@ __device__ __forceinline__ uint32_t choose_wave(const PivParams& p, PA A, PB B, 
 // k = the peak and its four neighbours, all in float64; every lane gets the five values
 // (A, B: the two windows, in global memory (pitch = frame width) or staged in LDS (pitch = window width))
 struct Lag5 { double c0, cu, cd, cl, cr; };   // centre, row above, row below, column left, column right
-template <typename PA, typename PB>
+template <int WY = 0, int WX = 0, typename PA, typename PB>
 __device__ __forceinline__ Lag5 lag5_wave(const PivParams& p, PA A, PB B, int pitch, double mean_a, double inv_a, double mean_b,
                                           double inv_b, int ip, int jp, int lane) {
-  const int wy = p.wy, wx = p.wx, n = wy * wx, cy = wy / 2, cx = wx / 2;
+  const int wy = WY ? WY : p.wy, wx = WX ? WX : p.wx, n = wy * wx, cy = wy / 2, cx = wx / 2;
   // un-shifted lags of the peak and its four neighbours
-  const int ky0 = unshift(ip, cy, wy), kx0 = unshift(jp, cx, wx);
+  const int ky0 = unshift<WY>(ip, cy, wy), kx0 = unshift<WX>(jp, cx, wx);
   const int kym = ky0 == 0 ? wy - 1 : ky0 - 1, kyp = ky0 == wy - 1 ? 0 : ky0 + 1;
   const int kxm = kx0 == 0 ? wx - 1 : kx0 - 1, kxp = kx0 == wx - 1 ? 0 : kx0 + 1;
-  const LaneWalk lw(wx);
+  const LaneWalk<WX> lw(wx);
   double acc0 = 0.0, accu = 0.0, accd = 0.0, accl = 0.0, accr = 0.0;
   int y, x;
   lw.start(lane, y, x);
 #pragma unroll 4
   for (int e = lane; e < n; e += 64, lw.next(y, x)) {
-    const double av = a_inside(p, y, x) ? norm_clip((double)A[y * pitch + x], mean_a, inv_a) : 0.0;
-    int y0 = y + ky0; y0 = y0 >= wy ? y0 - wy : y0;
-    int ym = y + kym; ym = ym >= wy ? ym - wy : ym;
-    int yp = y + kyp; yp = yp >= wy ? yp - wy : yp;
-    int x0 = x + kx0; x0 = x0 >= wx ? x0 - wx : x0;
-    int xm = x + kxm; xm = xm >= wx ? xm - wx : xm;
-    int xp = x + kxp; xp = xp >= wx ? xp - wx : xp;
+    const double av = a_inside<WY != 0>(p, y, x) ? norm_clip((double)A[y * pitch + x], mean_a, inv_a) : 0.0;
+    const int y0 = wrap_once<WY>(y + ky0, wy), ym = wrap_once<WY>(y + kym, wy), yp = wrap_once<WY>(y + kyp, wy);
+    const int x0 = wrap_once<WX>(x + kx0, wx), xm = wrap_once<WX>(x + kxm, wx), xp = wrap_once<WX>(x + kxp, wx);
     acc0 += av * norm_clip((double)B[y0 * pitch + x0], mean_b, inv_b);
     accu += av * norm_clip((double)B[ym * pitch + x0], mean_b, inv_b);
     accd += av * norm_clip((double)B[yp * pitch + x0], mean_b, inv_b);
     accl += av * norm_clip((double)B[y0 * pitch + xm], mean_b, inv_b);
     accr += av * norm_clip((double)B[y0 * pitch + xp], mean_b, inv_b);
   }
-  const double inv_n = 1.0 / corr_samples(p);
+  const double inv_n = 1.0 / corr_samples<WY, WX>(p);
   auto clip01 = [](double c) { return c < 0.0 ? 0.0 : (c > 1.0 ? 1.0 : c); };
   Lag5 o;
   o.c0 = clip01(wave_sum_d(acc0) * inv_n); o.cu = clip01(wave_sum_d(accu) * inv_n); o.cd = clip01(wave_sum_d(accd) * inv_n);
@@ -212,10 +236,10 @@ __device__ __forceinline__ void fit5_d(const Lag5& c, int ip, int jp, int cy, in
 }
 
 // the five-sample fit at shifted position (ip, jp), all in float64; one wave, lane 0 stores
-template <typename PA, typename PB>
+template <int WY = 0, int WX = 0, typename PA, typename PB>
 __device__ __forceinline__ void fit_wave(const PivParams& p, PA A, PB B, int pitch, double mean_a, double inv_a, double mean_b,
                                          double inv_b, uint32_t g, int ip, int jp, int lane) {
-  const int wy = p.wy, wx = p.wx, cy = wy / 2, cx = wx / 2;
+  const int wy = WY ? WY : p.wy, wx = WX ? WX : p.wx, cy = wy / 2, cx = wx / 2;
   if (ip <= 0 || ip >= wy - 1 || jp <= 0 || jp >= wx - 1) {   // border peak: no fit (A5)
     if (lane == 0) {
       float u, v;
@@ -224,7 +248,7 @@ __device__ __forceinline__ void fit_wave(const PivParams& p, PA A, PB B, int pit
     }
     return;
   }
-  const Lag5 c = lag5_wave(p, A, B, pitch, mean_a, inv_a, mean_b, inv_b, ip, jp, lane);
+  const Lag5 c = lag5_wave<WY, WX>(p, A, B, pitch, mean_a, inv_a, mean_b, inv_b, ip, jp, lane);
   // the five logarithms side by side on five lanes instead of one after the other on lane 0
   const double eps = 1e-7;
   const double mine = log((lane == 0 ? c.c0 : lane == 1 ? c.cu : lane == 2 ? c.cd : lane == 3 ? c.cl : c.cr) + eps);
@@ -287,19 +311,28 @@ __device__ __forceinline__ void amax_merge_d(double& v, int& idx, double pv, int
 // statistics ride on that pass, and the six samples per element of the fit come out of LDS -- read straight from the frames the
 // fit issues 6 n single-sample loads through the texture path, which is what bounded this kernel (140 -> ~50 us per 32 k records).
 // Windows whose two copies exceed the slice (float32 64 x 64 and up) take the direct path.
+//
+// Fixed-size instantiations (WY, WX != 0; launch_rescue_t picks them for the square 16, 32 and 64 px windows of launches without a
+// search area, option "rescue_generic" = 0): the kernel is bound by instruction issue, and at run-time geometry two thirds of its
+// instructions (5 124 -> 1 501 at <u8, 32>) and a third of what it issues per record (3 185 -> 2 110) are index work -- the lane walk, a
+// compare-and-select wrap for each of the six shifted indices of a sample, the search-area test.  With the size known a lane keeps its column, the wraps are masks, and the wave's slice is as large as its two windows.
 constexpr int FIT_LDS_PER_WAVE = 8192;
+template <typename T, typename TB, int WY, int WX>
+constexpr size_t fit_slice_bytes() {
+  return WY ? (((size_t)WY * WX * (sizeof(T) + sizeof(TB)) + 15) & ~(size_t)15) : (size_t)FIT_LDS_PER_WAVE;
+}
 
-template <typename T, typename TB = T>
+template <typename T, typename TB = T, int WY = 0, int WX = 0>
 __global__ __launch_bounds__(RBLOCK) void piv_rescue_fit_kernel(PivParams p) {
   extern __shared__ __attribute__((aligned(16))) unsigned char fsm[];
   typedef const T __attribute__((address_space(3))) * LdsPtr;
   typedef const TB __attribute__((address_space(3))) * LdsPtrB;
   const RescueHdr* hdr = p.rescue_hdr;
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const int wy = p.wy, wx = p.wx, n = wy * wx;
+  const int wy = WY ? WY : p.wy, wx = WX ? WX : p.wx, n = wy * wx;
   const bool staged = (size_t)n * (sizeof(T) + sizeof(TB)) <= (size_t)FIT_LDS_PER_WAVE;
   // (window B first: with a wider TB the narrower window A behind it stays aligned)
-  TB* lb = reinterpret_cast<TB*>(fsm + (size_t)wave * FIT_LDS_PER_WAVE);
+  TB* lb = reinterpret_cast<TB*>(fsm + (size_t)wave * fit_slice_bytes<T, TB, WY, WX>());
   T* la = reinterpret_cast<T*>(lb + n);
   const uint32_t n_fit = min(hdr->n_fit, p.rescue_cap_fit);
   const uint32_t n_waves = gridDim.x * (RBLOCK / 64);
@@ -310,8 +343,8 @@ __global__ __launch_bounds__(RBLOCK) void piv_rescue_fit_kernel(PivParams p) {
     const T* A = window_base<T>(p, g);
     const TB* B = window_base_b<T, TB>(p, g, A);
     double mean_a, sd_a, mean_b, sd_b;
-    if (staged) pair_stats_wave<T, true, TB>(p, A, B, lane, mean_a, sd_a, mean_b, sd_b, la, lb);
-    else pair_stats_wave<T, false, TB>(p, A, B, lane, mean_a, sd_a, mean_b, sd_b);
+    if (staged) pair_stats_wave<T, true, TB, WY, WX>(p, A, B, lane, mean_a, sd_a, mean_b, sd_b, la, lb);
+    else pair_stats_wave<T, false, TB, WY, WX>(p, A, B, lane, mean_a, sd_a, mean_b, sd_b);
     // (a zero-variance window is NaN already and is never listed)
     if (sd_a != 0.0 && sd_b != 0.0) {
       const double sg = p.norm_clip ? (double)p.std_gain : -(double)p.std_gain;   // options "std_ddof" / "norm_clip"
@@ -321,12 +354,12 @@ __global__ __launch_bounds__(RBLOCK) void piv_rescue_fit_kernel(PivParams p) {
         __builtin_amdgcn_wave_barrier();   // the wave's own LDS writes above are in order with the reads below; this pins the compiler
         const LdsPtr SA = (LdsPtr)la;
         const LdsPtrB SB = (LdsPtrB)lb;
-        if (rec.z != 0xffffffffu) pos = choose_wave(p, SA, SB, wx, mean_a, inv_a, mean_b, inv_b, rec.y, rec.z, lane);   // two candidates
-        fit_wave(p, SA, SB, wx, mean_a, inv_a, mean_b, inv_b, g, (int)(pos >> 16), (int)(pos & 0xffffu), lane);
+        if (rec.z != 0xffffffffu) pos = choose_wave<WY, WX>(p, SA, SB, wx, mean_a, inv_a, mean_b, inv_b, rec.y, rec.z, lane);   // two candidates
+        fit_wave<WY, WX>(p, SA, SB, wx, mean_a, inv_a, mean_b, inv_b, g, (int)(pos >> 16), (int)(pos & 0xffffu), lane);
         __builtin_amdgcn_wave_barrier();
       } else {
-        if (rec.z != 0xffffffffu) pos = choose_wave(p, A, B, p.W, mean_a, inv_a, mean_b, inv_b, rec.y, rec.z, lane);
-        fit_wave(p, A, B, p.W, mean_a, inv_a, mean_b, inv_b, g, (int)(pos >> 16), (int)(pos & 0xffffu), lane);
+        if (rec.z != 0xffffffffu) pos = choose_wave<WY, WX>(p, A, B, p.W, mean_a, inv_a, mean_b, inv_b, rec.y, rec.z, lane);
+        fit_wave<WY, WX>(p, A, B, p.W, mean_a, inv_a, mean_b, inv_b, g, (int)(pos >> 16), (int)(pos & 0xffffu), lane);
       }
     }
   }
@@ -667,17 +700,37 @@ __global__ __launch_bounds__(RBLOCK) void ens_final_kernel(PivParams p, EnsRescu
   u[rec.w] = uu; v[rec.w] = vv;
 }
 
+// the fit kernel of one instantiation; the dynamic LDS is the staged windows' slices, none on the direct path
+template <typename T, typename TB, int WY, int WX>
+hipError_t launch_fit_t(const PivParams& p, uint32_t blocks, hipStream_t s) {
+  const size_t n = (size_t)p.wy * p.wx;
+  const size_t fit_lds = n * (sizeof(T) + sizeof(TB)) <= (size_t)FIT_LDS_PER_WAVE ? (size_t)(RBLOCK / 64) * fit_slice_bytes<T, TB, WY, WX>() : 0;
+  hipLaunchKernelGGL((piv_rescue_fit_kernel<T, TB, WY, WX>), dim3(blocks), dim3(RBLOCK), fit_lds, s, p);
+  lspiv_api::g_rescue_fit_size.store(WX);   // option "rescue_fit_size": which instantiation this pass took
+  return hipGetLastError();
+}
+
+// Which fixed sizes are instantiated per <T, TB>.  The build rule: an instantiation stays only if the compiler's
+// resource report (tools/kres.py piv_rescue.hip fit_kernel) shows no scratch and no more VGPRs than the generic sibling of its types.
+template <typename T, typename TB, int W> struct FitFixed { static constexpr bool ok = true; };
+template <> struct FitFixed<double, float, 32> { static constexpr bool ok = false; };   // 133 VGPRs against the generic kernel's 124
+
 template <typename T, typename TB = T>
-hipError_t launch_rescue_t(const PivParams& p, hipStream_t s) {
+hipError_t launch_rescue_t(const PivParams& p, bool generic, hipStream_t s) {
   const int n = p.wy * p.wx;
   const bool fast = n <= RESCUE_LDS_SAMPLES && (p.wx % AMB_R) == 0;
   const size_t lds = fast ? (size_t)3 * n * sizeof(double) + (size_t)(n + p.wy) * sizeof(int) : 0;
   // fixed grids (the record counts live on the device): empty blocks leave within microseconds
   const uint32_t fit_blocks = std::min<uint32_t>(4096u, std::max<uint32_t>(64u, p.n_tiles / 512u + 1u));
   const uint32_t amb_blocks = std::min<uint32_t>(1024u, std::max<uint32_t>(64u, p.n_tiles / 2048u + 1u));
-  const size_t fit_lds = (size_t)n * (sizeof(T) + sizeof(TB)) <= (size_t)FIT_LDS_PER_WAVE ? (size_t)(RBLOCK / 64) * FIT_LDS_PER_WAVE : 0;
-  hipLaunchKernelGGL((piv_rescue_fit_kernel<T, TB>), dim3(fit_blocks), dim3(RBLOCK), fit_lds, s, p);
-  hipError_t e = hipGetLastError();
+  // the square windows of the walking / shifted / deformed families at compile-time size; a search area and every other size: run time
+  const int fixed = (!generic && p.nw == 0 && p.wy == p.wx) ? p.wx : 0;
+  constexpr int W16 = FitFixed<T, TB, 16>::ok ? 16 : 0, W32 = FitFixed<T, TB, 32>::ok ? 32 : 0, W64 = FitFixed<T, TB, 64>::ok ? 64 : 0;   // (0: the generic kernel)
+  hipError_t e;
+  if (fixed == 16) e = launch_fit_t<T, TB, W16, W16>(p, fit_blocks, s);
+  else if (fixed == 32) e = launch_fit_t<T, TB, W32, W32>(p, fit_blocks, s);
+  else if (fixed == 64) e = launch_fit_t<T, TB, W64, W64>(p, fit_blocks, s);
+  else e = launch_fit_t<T, TB, 0, 0>(p, fit_blocks, s);
   if (e != hipSuccess) return e;
   // (per launch: the attribute belongs to the current device, and a process may drive several)
   e = hipFuncSetAttribute(reinterpret_cast<const void*>(&piv_rescue_amb_kernel<T, TB>), hipFuncAttributeMaxDynamicSharedMemorySize,
@@ -733,11 +786,12 @@ hipError_t launch_ens_final(const PivParams& p, const EnsRescueArgs& a, const do
 
 hipError_t launch_piv_rescue(const PivParams& p, int dtype, hipStream_t s) {
   if (!p.rescue_hdr) return hipSuccess;
+  const bool generic = lspiv_api::g_opt_rescue_generic.load() != 0;   // option "rescue_generic": run-time geometry for every launch
   switch (dtype) {
     // (a deformation pass cuts window B from the float32 workspace; on a float32 stack that is the same-type kernels' p.warped branch)
-    case 0: return p.warped ? launch_rescue_t<uint8_t, float>(p, s) : launch_rescue_t<uint8_t>(p, s);
-    case 1: return launch_rescue_t<float>(p, s);
-    case 2: return p.warped ? launch_rescue_t<double, float>(p, s) : launch_rescue_t<double>(p, s);
+    case 0: return p.warped ? launch_rescue_t<uint8_t, float>(p, generic, s) : launch_rescue_t<uint8_t>(p, generic, s);
+    case 1: return launch_rescue_t<float>(p, generic, s);
+    case 2: return p.warped ? launch_rescue_t<double, float>(p, generic, s) : launch_rescue_t<double>(p, generic, s);
     default: return hipErrorInvalidValue;
   }
 }
