@@ -43,7 +43,9 @@ extern "C" {
                                * _set_shift_dev / _get_shift; multi-pass PIV, lspiv_shift_supported /
                                * lspiv_piv_shift_pairs_dev_at / lspiv_piv_predict_shift_dev / lspiv_piv_multipass_dev_at / lspiv_piv_multipass_at; window deformation passes,
                                * lspiv_deform_supported / lspiv_deform_required_bytes / lspiv_piv_predict_deform_dev /
-                               * lspiv_piv_deform_pairs_dev_at / lspiv_piv_multipass_deform_dev_at / lspiv_piv_multipass_deform_at)
+                               * lspiv_piv_deform_pairs_dev_at / lspiv_piv_multipass_deform_dev_at / lspiv_piv_multipass_deform_at; SPOF phase-filtered
+                               * correlation, lspiv_spof_supported / lspiv_piv_spof_pairs_dev_at / lspiv_piv_spof_pairs_at /
+                               * lspiv_ensemble_set_spectral_filter / _get_spectral_filter)
                                * 5 (round 6): lspiv_chunk_alignment(wy, wx) without a grid now returns the alignment that is right on EVERY grid (75
                                * where it returned 25: callers that cut chunks on it stay bit-reproducible on large grids); additions:
                                * lspiv_upload_frames, lspiv_trace / lspiv_trace_read; the host-pointer projection entry points no longer
@@ -321,6 +323,34 @@ int lspiv_piv_multipass_deform_at(const void* frames, int dtype, int64_t T, int6
                                   int n_passes, const int* passes, int n_deform, float signal_threshold, int64_t pair_offset,
                                   float* u, float* v, float* corr_max, float* s2n, float* corr_planes, int16_t* shift_out);
 
+/* SPOF phase-filtered correlation (the project's own semantics, unpinned): the per-pair result with the
+ * symmetric phase-only filter ("robust phase correlation") as the weighting of the cross spectrum, for imagery whose static or slow
+ * background -- bed texture, standing ripples, glare -- carries more spectral energy than the tracers.  Replaces ffpiv.cross_corr +
+ * the corr_max / s2n reductions + ffpiv.u_v_displacement (pyorc/velocimetry/ffpiv.py:446-474) with, per pair of N x N windows A, B
+ * (N = wy = wx in {16, 32, 64}): a^ = normalize_intensity(A), b^ likewise ("std_ddof" and the zero clip as everywhere);
+ * Rn = conj(fft2 a^) fft2 b^ / N^2; R' = Rn / sqrt(|Rn|), 0 where Rn = 0; plane = clip(fftshift(ifft2(R').real), 0, 1), where the lower
+ * bound removes true negative lobes; corr_max = max of the plane; s2n = max / mean of the CLIPPED plane; u, v = the first maximum in
+ * row-major order and the three-point log-Gaussian fit on plane + 1e-7 ("border_peak", "v_sign" as everywhere).  signal_threshold
+ * scores A and B as lspiv_piv_pairs_dev_at does: a failing pair, or one with a non-finite sample, gives NaN u, v, corr_max, s2n and a
+ * NaN plane; a zero-variance window an exactly zero plane.  float32 arithmetic WITHOUT a float64 rescue pass (a filtered plane is no
+ * sum of lag products the rescue kernels could re-evaluate): the "rescue" option has no effect here.  Options "norm_clip" = 0 and
+ * "signal_mode" = 1 and every other window are LSPIV_EUNSUPPORTED.
+ *
+ * lspiv_spof_supported: 1 for wy = wx in {16, 32, 64}, else 0.  Host-only.
+ * lspiv_piv_spof_pairs_dev_at: d_out, d_corr_planes as lspiv_piv_pairs_dev_at lays them out.  One window per job, one plane per inverse
+ * transform: a window's result depends on its own samples alone, so every chunking gives the same bits; pair_offset is accepted for
+ * symmetry.  No workspace next to the frames and results.
+ * lspiv_piv_spof_pairs_at: the host-fed twin -- the chunk is staged like lspiv_piv_pairs_at stages it (float64 narrowed to float32). */
+#define LSPIV_FILTER_NONE 0
+#define LSPIV_FILTER_SPOF 1
+int lspiv_spof_supported(int wy, int wx);
+int lspiv_piv_spof_pairs_dev_at(const void* d_frames, int dtype, int64_t T, int64_t H, int64_t W,
+                                int wy, int wx, int oy, int ox, float signal_threshold, int64_t pair_offset,
+                                float* d_out, float* d_corr_planes, void* stream);
+int lspiv_piv_spof_pairs_at(const void* frames, int dtype, int64_t T, int64_t H, int64_t W,
+                            int wy, int wx, int oy, int ox, float signal_threshold, int64_t pair_offset,
+                            float* u, float* v, float* corr_max, float* s2n, float* corr_planes);
+
 /* Host frames into a slice of an HBM-resident stack, the way lspiv_piv_pairs brings them in -- pinned ring, staging threads,
  * float64 narrowed to float32 with the "narrow_offset" guard (so d_dst receives n_frames * H * W samples of LSPIV_F32 for LSPIV_F64
  * input, of `dtype` otherwise) -- without launching anything: what lets the chunk loop of pyorc/velocimetry/ffpiv.py:399-440 keep a
@@ -448,6 +478,19 @@ int lspiv_ensemble_sliding_finish(lspiv_ensemble* handle, float count_min, int64
 int lspiv_ensemble_set_shift(lspiv_ensemble* handle, const int16_t* shift);
 int lspiv_ensemble_set_shift_dev(lspiv_ensemble* handle, const int16_t* d_shift, void* stream);
 int lspiv_ensemble_get_shift(lspiv_ensemble* handle, int16_t* shift);
+/* SPOF phase-filtered ensemble: filter = LSPIV_FILTER_SPOF makes the handle sum the planes of
+ * lspiv_piv_spof_pairs_dev_at in place of ffpiv.cross_corr's (pyorc/velocimetry/ffpiv.py:222-241): a plane failing corr_min / s2n_min
+ * / finite counts as zero, corr_sum += plane, corr_count += (corr_max > 1e-6), the returned per-pair corr_max / s2n are the masked values
+ * of the FILTERED planes -- corr_min / s2n_min keep their meaning, their useful values are lower (filtered peaks are lower).
+ * LSPIV_FILTER_NONE: the plain ensemble again.  Before the first accumulate only (LSPIV_EINVAL); not on a sliding or a shifted handle,
+ * and a filtered handle refuses lspiv_ensemble_set_sliding / _set_shift (LSPIV_EINVAL); the window must satisfy lspiv_spof_supported
+ * and the options be as for the per-pair entry point (LSPIV_EUNSUPPORTED).  lspiv_ensemble_accumulate / _accumulate_dev then run the
+ * filtered ensemble kernel -- one owner per window, one plane per inverse transform, float32 additions in pair order: the same bits for
+ * every chunking.  lspiv_ensemble_finish / _finish_partials form the mean plane, the count filter and the fit as before, WITHOUT the
+ * float64 rescue (lspiv_ensemble_flag reports no records, nothing is retained for it).  lspiv_ensemble_export / _import carry the
+ * sums and leave the handle's filter as it is; lspiv_ensemble_allreduce returns LSPIV_EINVAL unless every handle has the same filter. */
+int lspiv_ensemble_set_spectral_filter(lspiv_ensemble* handle, int filter);
+int lspiv_ensemble_get_spectral_filter(lspiv_ensemble* handle, int* filter);
 int lspiv_ensemble_destroy(lspiv_ensemble* handle);
 
 /* ---------------------------------------------------------------- next rows */

@@ -88,6 +88,9 @@ SIGNATURES = {
     "lspiv_piv_deform_pairs_dev_at": (_i32, [_vp, _i32, _i64, _i64, _i64, _i32, _i32, _i32, _i32, _f32, _i64, _vp, _vp, _vp, _vp]),
     "lspiv_piv_multipass_deform_dev_at": (_i32, [_vp, _i32, _i64, _i64, _i64, _i32, _vp, _i32, _f32, _i64, _vp, _vp, _vp, _vp]),
     "lspiv_piv_multipass_deform_at": (_i32, [_vp, _i32, _i64, _i64, _i64, _i32, _vp, _i32, _f32, _i64, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "lspiv_spof_supported": (_i32, [_i32, _i32]),
+    "lspiv_piv_spof_pairs_dev_at": (_i32, [_vp, _i32, _i64, _i64, _i64, _i32, _i32, _i32, _i32, _f32, _i64, _vp, _vp, _vp]),
+    "lspiv_piv_spof_pairs_at": (_i32, [_vp, _i32, _i64, _i64, _i64, _i32, _i32, _i32, _i32, _f32, _i64, _vp, _vp, _vp, _vp, _vp]),
     "lspiv_u_v_displacement": (_i32, [_vp, _i64, _i64, _i32, _i32, _vp, _vp]),
     "lspiv_ensemble_begin": (_i32, [_i64, _i64, _i32, _i32, _i32, _i32, C.POINTER(_vp)]),
     "lspiv_ensemble_accumulate": (_i32, [_vp, _vp, _i32, _i64, _f32, _f32, _f32, _vp, _vp]),
@@ -108,6 +111,8 @@ SIGNATURES = {
     "lspiv_ensemble_set_shift": (_i32, [_vp, _vp]),
     "lspiv_ensemble_set_shift_dev": (_i32, [_vp, _vp, _vp]),
     "lspiv_ensemble_get_shift": (_i32, [_vp, _vp]),
+    "lspiv_ensemble_set_spectral_filter": (_i32, [_vp, _i32]),
+    "lspiv_ensemble_get_spectral_filter": (_i32, [_vp, C.POINTER(_i32)]),
     "lspiv_ensemble_destroy": (_i32, [_vp]),
     "lspiv_projection_create": (_i32, [_i64, _i64, _i64, _i64, _vp, _vp, _i64, _vp, _vp, _i64, _vp, _i64, C.POINTER(_vp)]),
     "lspiv_project_frames": (_i32, [_vp, _vp, _i32, _i64, _vp]),

@@ -54,6 +54,9 @@ struct lspiv_ensemble {
   // shift_host: the same values, for lspiv_ensemble_get_shift and the comparison in lspiv_ensemble_allreduce.  nullptr: the plain ensemble
   int16_t* d_shift;
   std::vector<int16_t> shift_host;
+  // SPOF phase-filtered ensemble (lspiv_ensemble_set_spectral_filter): LSPIV_FILTER_SPOF -- every pair's plane
+  // comes from the filtered one-owner kernel (piv_spof_impl.h); no float64 rescue of the final fit, nothing retained for it.  0: none
+  int filter;
   int sl_layout;            // slot layout of the store, recorded by the first accumulate: 0 nothing written yet, 1 fft-shifted row-major, 2 lane-major (64 x 64 walking kernel)
 };
 
@@ -294,6 +297,14 @@ static int ensemble_launch(lspiv_ensemble* h, DeviceCtx* c, const void* d_frames
   const int kind = lspiv_kernel_kind(h->wy, h->wx);
   const int walk = lspiv::walk_setting();
   p.pair_offset = h->pairs_done;   // advanced only once the launch has been issued (a failed accumulate changes nothing)
+  if (h->filter) {
+    // filtered handle: the one-owner kernel on the filtered planes (piv_spof_impl.h, "filtered ensemble kernel"); no walking, no segments --
+    // its sums are the same bits for every chunking
+    LSPIV_TRY(check_spof(h->wy, h->wx));   // (signal_mode = 1, norm_clip = 0: refused here, where the per-pair entry points refuse them)
+    LSPIV_TRY(dispatch(p, dtype, true, s, h->filter));
+    h->pairs_done += p.n_pairs;
+    return LSPIV_OK;
+  }
   if (h->d_shift) {
     // shifted handle: the one-owner kernel on shifted windows (piv_fft_impl.h, "shifted ensemble kernel"); no walking, no segments --
     // its sums are the same bits for every chunking
@@ -384,7 +395,7 @@ int lspiv_ensemble_accumulate_dev(lspiv_ensemble* h, const void* d_frames, int d
   LSPIV_TRY(ensemble_launch(h, c, d_frames, dtype, T, corr_min, s2n_min, signal_threshold, d_corr_s2n, d_corr_s2n + n_tiles, s));
   // retention for the float64 rescue of the final fit (lspiv_ensemble_set_retain)
   const size_t fbytes = (size_t)T * h->H * h->W * elem_size(dtype);
-  if (h->retain_mode == LSPIV_RETAIN_NONE || !h->retain_complete || !g_opt_rescue.load()) {
+  if (h->retain_mode == LSPIV_RETAIN_NONE || !h->retain_complete || !g_opt_rescue.load() || h->filter) {   // (a filtered handle has no rescue)
     if (h->retain_complete) ensemble_give_up_retention(h);
   } else if (h->retain_mode == LSPIV_RETAIN_BORROW) {
     ensemble_keep(h, const_cast<void*>(d_frames), false, fbytes, dtype, T, d_corr_s2n, s);
@@ -422,7 +433,7 @@ int lspiv_ensemble_accumulate(lspiv_ensemble* h, const void* frames, int dtype, 
   // the chunk is uploaded into a buffer of its own that stays with the handle until finish (float64 rescue of the final fit),
   // as long as the retained chunks fit their budget; beyond it, into the shared workspace as before (float32 fits stay)
   void* own = nullptr;
-  if (g_opt_rescue.load() && h->retain_complete && h->kept_bytes + (size_t)T * frame_bytes <= ensemble_retain_budget()) {
+  if (g_opt_rescue.load() && !h->filter && h->retain_complete && h->kept_bytes + (size_t)T * frame_bytes <= ensemble_retain_budget()) {
     if (hipMalloc(&own, (size_t)T * frame_bytes) != hipSuccess) { (void)hipGetLastError(); own = nullptr; }
   }
   if (!own) {
@@ -434,7 +445,7 @@ int lspiv_ensemble_accumulate(lspiv_ensemble* h, const void* frames, int dtype, 
   LSPIV_TRY(stage_ring(c, frame_bytes));
   const int64_t fpb = std::max<int64_t>(1, (int64_t)(c->pinned_cap / frame_bytes));
   // sub-batches are cut on the segment anchors -- on the blocks of a sliding handle
-  const int64_t align = h->sl_stride ? h->sl_stride : h->d_shift ? 1 : std::max(1, chunk_alignment_for(h->wy, h->wx, (int64_t)n_win)), base_offset = h->pairs_done;
+  const int64_t align = h->sl_stride ? h->sl_stride : (h->d_shift || h->filter) ? 1 : std::max(1, chunk_alignment_for(h->wy, h->wx, (int64_t)n_win)), base_offset = h->pairs_done;
   if (h->sl_stride)   // the block store grows once per call, not once per sub-batch
     LSPIV_TRY(sliding_reserve(h, (size_t)((base_offset + T - 1 + h->sl_stride - 1) / h->sl_stride), c->stream));
   int64_t launched = 0;
@@ -603,7 +614,7 @@ int lspiv_ensemble_flag(lspiv_ensemble* h, float count_min, float n_frames, int6
   h->flag_min_count = count_min * n_frames;
   h->n_rec = 0;
   *n_records = 0;
-  if (!g_opt_rescue.load()) return LSPIV_OK;
+  if (!g_opt_rescue.load() || h->filter) return LSPIV_OK;   // (a filtered handle has no rescue: no records, the float32 fits stay)
   LSPIV_TRY(ensemble_mean_fit(h, c, h->flag_min_count));
   LSPIV_TRY(ensemble_flag(h, c));
   *n_records = h->n_rec;
@@ -671,7 +682,8 @@ int lspiv_ensemble_finish(lspiv_ensemble* h, float count_min, float n_frames, fl
   h->flag_min_count = count_min * n_frames;
   h->n_rec = 0;
   LSPIV_TRY(ensemble_mean_fit(h, c, h->flag_min_count));
-  if (g_opt_rescue.load()) {
+  if (h->filter) h->last_flagged = h->last_rescued = h->last_skipped = 0;
+  if (g_opt_rescue.load() && !h->filter) {   // (a filtered plane is no sum of lag products: nothing to re-evaluate it from)
     // float64 rescue of the ill-conditioned fits (include/lspiv.h): needs the frames of EVERY pair in the sum -- a state that
     // was imported holds other handles' pairs (the multi-GPU path runs the three stages itself and all-reduces the partials)
     LSPIV_TRY(ensemble_flag(h, c));
@@ -689,6 +701,7 @@ static int ensemble_set_shift(lspiv_ensemble* h, const int16_t* src, bool on_dev
   if (!h) return fail(LSPIV_EINVAL, "NULL argument");
   if (h->sl_stride) return fail(LSPIV_EINVAL, "%s: this is a sliding ensemble handle (lspiv_ensemble_set_sliding); a sliding ensemble has no shifted pass", call);
   if (h->pairs_done || h->foreign) return fail(LSPIV_EINVAL, "%s must be called before the first accumulate", call);
+  if (h->filter && src) return fail(LSPIV_EINVAL, "%s: this is a filtered handle (lspiv_ensemble_set_spectral_filter); a filtered ensemble has no shifted pass", call);
   if (!src) {
     if (h->d_shift) (void)hipFree(h->d_shift);
     h->d_shift = nullptr;
@@ -738,11 +751,31 @@ int lspiv_ensemble_get_shift(lspiv_ensemble* h, int16_t* shift) {
   return LSPIV_OK;
 }
 
+// ---- SPOF phase-filtered ensemble ---------------------------------------------------------------------
+int lspiv_ensemble_set_spectral_filter(lspiv_ensemble* h, int filter) {
+  if (!h) return fail(LSPIV_EINVAL, "NULL argument");
+  if (filter != LSPIV_FILTER_NONE && filter != LSPIV_FILTER_SPOF) return fail(LSPIV_EINVAL, "spectral filter %d not in {0: none, 1: SPOF}", filter);
+  if (h->pairs_done || h->foreign) return fail(LSPIV_EINVAL, "lspiv_ensemble_set_spectral_filter must be called before the first accumulate");
+  if (filter && h->sl_stride)
+    return fail(LSPIV_EINVAL, "lspiv_ensemble_set_spectral_filter: this is a sliding ensemble handle (lspiv_ensemble_set_sliding); a sliding ensemble has no spectral filter");
+  if (filter && h->d_shift)
+    return fail(LSPIV_EINVAL, "lspiv_ensemble_set_spectral_filter: this is a shifted handle (lspiv_ensemble_set_shift); a shifted ensemble pass has no spectral filter");
+  if (filter) LSPIV_TRY(check_spof(h->wy, h->wx));
+  h->filter = filter;
+  return LSPIV_OK;
+}
+int lspiv_ensemble_get_spectral_filter(lspiv_ensemble* h, int* filter) {
+  if (!h || !filter) return fail(LSPIV_EINVAL, "NULL argument");
+  *filter = h->filter;
+  return LSPIV_OK;
+}
+
 // ---- sliding ensemble ---------------------------------------------------------------------------------------------------
 int lspiv_ensemble_set_sliding(lspiv_ensemble* h, int64_t window_pairs, int64_t stride_pairs) {
   if (!h) return fail(LSPIV_EINVAL, "NULL argument");
   if (h->pairs_done || h->foreign) return fail(LSPIV_EINVAL, "lspiv_ensemble_set_sliding must be called before the first accumulate");
   if (h->d_shift) return fail(LSPIV_EINVAL, "lspiv_ensemble_set_sliding: this is a shifted handle (lspiv_ensemble_set_shift); a sliding ensemble has no shifted pass");
+  if (h->filter) return fail(LSPIV_EINVAL, "lspiv_ensemble_set_sliding: this is a filtered handle (lspiv_ensemble_set_spectral_filter); a sliding ensemble has no spectral filter");
   if (stride_pairs < 1 || stride_pairs > window_pairs || window_pairs % stride_pairs != 0 || window_pairs >= (int64_t)1 << 24)
     return fail(LSPIV_EINVAL, "sliding ensemble: need 1 <= stride <= window and window %% stride == 0, got window %lld, stride %lld",
                 (long long)window_pairs, (long long)stride_pairs);
@@ -869,6 +902,8 @@ int lspiv_ensemble_allreduce(lspiv_ensemble** handles, int n) {
       return fail(LSPIV_ESHAPE, "handle %d has another geometry than handle 0", k);
     if (h->shift_host != r->shift_host)   // (both empty: two plain handles)
       return fail(LSPIV_EINVAL, "handle %d has other window offsets (lspiv_ensemble_set_shift) than handle 0: their sums are not sums of the same planes", k);
+    if (h->filter != r->filter)
+      return fail(LSPIV_EINVAL, "handle %d has another spectral filter (lspiv_ensemble_set_spectral_filter) than handle 0: their sums are not sums of the same planes", k);
     if (h->device < 0 || h->device >= kMaxDevices) return fail(LSPIV_EINVAL, "handle %d: device %d out of range", k, h->device);
     devs.push_back(h->device);
   }

@@ -221,13 +221,16 @@ std::vector<double> narrow_offsets(const double* frames, size_t frame_elems, int
 // ---- PIV launches, shared with the ensemble (api_piv.hip) ------------------------------------------------------------------
 int fill_params(lspiv::PivParams* p, const void* d_frames, int dtype, int64_t T, int64_t H, int64_t W, int wy, int wx,
                 int oy, int ox, float signal_threshold, const Grid& g);
-int dispatch(const lspiv::PivParams& p0, int dtype, bool ensemble, hipStream_t s);
+// filter: 0, or LSPIV_FILTER_SPOF -- the phase-filtered kernels (piv_spof_impl.h), never followed by a rescue pass
+int dispatch(const lspiv::PivParams& p0, int dtype, bool ensemble, hipStream_t s, int filter = 0);
 int apply_v_sign(float* d_v, int64_t n, hipStream_t s);
 int apply_signal_mode(DeviceCtx* c, lspiv::PivParams* p, int dtype, hipStream_t s);
 // shifted passes (multi-pass PIV, multi-pass ensemble): the window is 16, 32 or 64 px square, the frame fits the int16 offsets, and the
 // options norm_clip = 0 / signal_mode = 1 are refused (LSPIV_EUNSUPPORTED)
 int check_shift(int wy, int wx, int64_t H, int64_t W);
 int check_multipass_options();
+// SPOF-filtered correlation: the same windows, the same two options refused (LSPIV_EUNSUPPORTED)
+int check_spof(int wy, int wx);
 // window kinds served by the time-walking kernels (every even square window 6 .. 64)
 inline bool kind_walks(int kind) { return kind == 1 || kind == 2 || kind == 6 || kind == 8; }
 // the anchor length the walking kernels use on a grid of n_win windows (common.h, walk_anchor)

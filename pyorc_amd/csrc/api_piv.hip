@@ -1,6 +1,7 @@
 // C ABI of liblspiv_hip.so, PIV (api_core.hip has the overview): the window grid, the kernel of a window's family, the float64 rescue
 // pass after it, the chunk alignment, the device-pointer and host-pointer PIV entry points.
 #include "api_internal.h"
+#include "piv_spof.h"
 
 #include <algorithm>
 #include <cmath>
@@ -128,7 +129,7 @@ static void set_search_window(lspiv::PivParams* p, int n) {
   }
 }
 
-static int dispatch_kernels(const lspiv::PivParams& p, int dtype, bool ensemble, hipStream_t s);
+static int dispatch_kernels(const lspiv::PivParams& p, int dtype, bool ensemble, hipStream_t s, int filter);
 
 // PIV kernel of the window's family, then -- per-timestep mode, unless switched off -- the float64 rescue pass over the
 // windows that kernel flagged (piv_rescue.hip)
@@ -143,29 +144,31 @@ static int dispatch_kernels(const lspiv::PivParams& p, int dtype, bool ensemble,
 constexpr int kTimerRing = 16;
 struct KernelTimer { hipEvent_t e0[kTimerRing] = {}, e1[kTimerRing] = {}; int n = 0; };
 KernelTimer g_timers[kMaxDevices];   // guarded by the device's dispatch lock
-static int timed_dispatch_kernels(const lspiv::PivParams& p, int dtype, bool ensemble, hipStream_t s) {
-  if (!g_opt_time_kernel.load()) return dispatch_kernels(p, dtype, ensemble, s);
+static int timed_dispatch_kernels(const lspiv::PivParams& p, int dtype, bool ensemble, hipStream_t s, int filter) {
+  if (!g_opt_time_kernel.load()) return dispatch_kernels(p, dtype, ensemble, s, filter);
   KernelTimer& t = g_timers[current_device_slot()];
   const int k = t.n % kTimerRing;
   if (!t.e0[k]) { HIP_TRY(hipEventCreate(&t.e0[k])); HIP_TRY(hipEventCreate(&t.e1[k])); }
   HIP_TRY(hipEventRecord(t.e0[k], s));
-  LSPIV_TRY(dispatch_kernels(p, dtype, ensemble, s));
+  LSPIV_TRY(dispatch_kernels(p, dtype, ensemble, s, filter));
   HIP_TRY(hipEventRecord(t.e1[k], s));
   ++t.n;
   return LSPIV_OK;
 }
-int dispatch(const lspiv::PivParams& p0, int dtype, bool ensemble, hipStream_t s) {
-  if (ensemble || !g_opt_rescue.load()) {
-    if (!g_opt_time_kernel.load()) return dispatch_kernels(p0, dtype, ensemble, s);
+// filter != 0 (LSPIV_FILTER_SPOF): the phase-filtered kernels, which have no rescue pass -- a filtered plane is no sum of lag products of
+// the samples, so the rescue kernels could not re-evaluate it; the "rescue" option has no effect on them
+int dispatch(const lspiv::PivParams& p0, int dtype, bool ensemble, hipStream_t s, int filter) {
+  if (ensemble || filter || !g_opt_rescue.load()) {
+    if (!g_opt_time_kernel.load()) return dispatch_kernels(p0, dtype, ensemble, s, filter);
     std::lock_guard<std::mutex> launch_lock(locks_here().dispatch);
-    return timed_dispatch_kernels(p0, dtype, ensemble, s);
+    return timed_dispatch_kernels(p0, dtype, ensemble, s, filter);
   }
   DeviceCtx* c;
   LSPIV_TRY(get_ctx(&c));
   lspiv::PivParams p = p0;
   std::lock_guard<std::mutex> launch_lock(locks_here().dispatch);
   LSPIV_TRY(rescue_ws(c, s, p.n_tiles, &p));
-  LSPIV_TRY(timed_dispatch_kernels(p, dtype, false, s));
+  LSPIV_TRY(timed_dispatch_kernels(p, dtype, false, s, 0));
   return launch_status(lspiv::launch_piv_rescue(p, dtype, s), "rescue kernel launch failed");
 }
 
@@ -175,7 +178,15 @@ int apply_v_sign(float* d_v, int64_t n, hipStream_t s) {
   return launch_status(lspiv::launch_negate(d_v, n, s));
 }
 
-static int dispatch_kernels(const lspiv::PivParams& p, int dtype, bool ensemble, hipStream_t s) {
+static int dispatch_kernels(const lspiv::PivParams& p, int dtype, bool ensemble, hipStream_t s, int filter) {
+  if (filter) {   // SPOF phase-filtered correlation: the one-window-per-job kernels of piv_spof_impl.h, per pair or summed by one owner per window
+    if (filter != LSPIV_FILTER_SPOF) return fail(LSPIV_EINVAL, "spectral filter %d not in {0: none, 1: SPOF}", filter);
+    if (ensemble)
+      return launch_status(p.wy == 16 ? lspiv::launch_piv_spof_ensemble16(p, dtype, s) : p.wy == 32 ? lspiv::launch_piv_spof_ensemble32(p, dtype, s)
+                                                                                                     : lspiv::launch_piv_spof_ensemble64(p, dtype, s));
+    return launch_status(p.wy == 16 ? lspiv::launch_piv_spof16(p, dtype, s) : p.wy == 32 ? lspiv::launch_piv_spof32(p, dtype, s)
+                                                                                          : lspiv::launch_piv_spof64(p, dtype, s));
+  }
   if (p.warped) {   // window deformation pass: the mixed-type per-pair kernels
     if (ensemble) return fail(LSPIV_EUNSUPPORTED, "ensemble mode has no deformation kernels");
     return launch_status(p.wy == 16 ? lspiv::launch_piv_deform16(p, dtype, s) : p.wy == 32 ? lspiv::launch_piv_deform32(p, dtype, s)
@@ -269,6 +280,16 @@ int check_shift(int wy, int wx, int64_t H, int64_t W) {
     return fail(LSPIV_EUNSUPPORTED, "shifted pass with window %dx%d is not supported: the window must be square and one of {16, 32, 64}", wy, wx);
   if (H > 32767 || W > 32767) return fail(LSPIV_EINVAL, "frame (%lld,%lld): a side above 32767 does not fit the int16 offsets", (long long)H, (long long)W);
   return check_multipass_options();
+}
+// ---- SPOF phase-filtered correlation: the window is 16, 32 or 64 px square; norm_clip = 0 / signal_mode = 1 are refused like above ----
+int check_spof(int wy, int wx) {
+  if (!shift_shape_ok(wy, wx))
+    return fail(LSPIV_EUNSUPPORTED, "SPOF-filtered correlation with window %dx%d is not supported: the window must be square and one of {16, 32, 64}", wy, wx);
+  if (!g_opt_norm_clip.load())
+    return fail(LSPIV_EUNSUPPORTED, "option norm_clip = 0 is served by the block-per-window kernels only, not by SPOF-filtered correlation");
+  if (g_opt_signal_mode.load() == 1)
+    return fail(LSPIV_EUNSUPPORTED, "option signal_mode = 1 is not supported by SPOF-filtered correlation: its kernels score the two windows of a pair");
+  return LSPIV_OK;
 }
 
 }  // namespace lspiv_api
@@ -417,9 +438,10 @@ int lspiv_chunk_alignment_grid(int64_t H, int64_t W, int wy, int wx, int oy, int
 }
 
 // nw: 0, or the window inside the search area wy x wx (search-area mode)
+// filter: 0, or LSPIV_FILTER_SPOF (the caller has run check_spof)
 static int piv_pairs_dev(const void* d_frames, int dtype, int64_t T, int64_t H, int64_t W, int wy, int wx, int nw, int oy,
                          int ox, float signal_threshold, int64_t pair_offset, float* d_out, float* d_corr_planes,
-                         void* stream) {
+                         void* stream, int filter = 0) {
   if (!d_frames || !d_out) return fail(LSPIV_EINVAL, "d_frames / d_out is NULL");
   if (pair_offset < 0) return fail(LSPIV_EINVAL, "pair_offset %lld is negative", (long long)pair_offset);
   Grid g;
@@ -437,7 +459,7 @@ static int piv_pairs_dev(const void* d_frames, int dtype, int64_t T, int64_t H, 
   p.planes = d_corr_planes;
   hipStream_t s = on_stream(c, stream);
   LSPIV_TRY(apply_signal_mode(c, &p, dtype, s));
-  LSPIV_TRY(dispatch(p, dtype, false, s));
+  LSPIV_TRY(dispatch(p, dtype, false, s, filter));
   return apply_v_sign(p.v, (int64_t)p.n_tiles, s);
 }
 
@@ -445,6 +467,14 @@ int lspiv_piv_pairs_dev_at(const void* d_frames, int dtype, int64_t T, int64_t H
                            int ox, float signal_threshold, int64_t pair_offset, float* d_out, float* d_corr_planes,
                            void* stream) {
   return piv_pairs_dev(d_frames, dtype, T, H, W, wy, wx, 0, oy, ox, signal_threshold, pair_offset, d_out, d_corr_planes, stream);
+}
+
+int lspiv_spof_supported(int wy, int wx) { return shift_shape_ok(wy, wx) ? 1 : 0; }
+
+int lspiv_piv_spof_pairs_dev_at(const void* d_frames, int dtype, int64_t T, int64_t H, int64_t W, int wy, int wx, int oy, int ox,
+                                float signal_threshold, int64_t pair_offset, float* d_out, float* d_corr_planes, void* stream) {
+  LSPIV_TRY(check_spof(wy, wx));
+  return piv_pairs_dev(d_frames, dtype, T, H, W, wy, wx, 0, oy, ox, signal_threshold, pair_offset, d_out, d_corr_planes, stream, LSPIV_FILTER_SPOF);
 }
 
 int lspiv_search_supported(int say, int sax, int wy, int wx) { return search_shape_ok(say, sax, wy, wx) ? 1 : 0; }
@@ -765,7 +795,7 @@ int lspiv_piv_pairs_dev(const void* d_frames, int dtype, int64_t T, int64_t H, i
 // nw: 0, or the window inside the search area wy x wx (search-area mode)
 static int piv_pairs_host(const void* frames, int dtype, int64_t T, int64_t H, int64_t W, int wy, int wx, int nw, int oy, int ox,
                           float signal_threshold, int64_t pair_offset, float* u, float* v, float* corr_max, float* s2n,
-                          float* corr_planes, const double* dt, double res_x, double res_y) {
+                          float* corr_planes, const double* dt, double res_x, double res_y, int filter = 0) {
   std::lock_guard<std::mutex> host_lock(locks_here().host);
   if (!frames || !u || !v || !corr_max || !s2n) return fail(LSPIV_EINVAL, "NULL buffer");
   if (pair_offset < 0) return fail(LSPIV_EINVAL, "pair_offset %lld is negative", (long long)pair_offset);
@@ -795,7 +825,7 @@ static int piv_pairs_host(const void* frames, int dtype, int64_t T, int64_t H, i
   LSPIV_TRY(stage_ring(c, frame_bytes));
   const int64_t fpb = std::max<int64_t>(1, (int64_t)(c->pinned_cap / frame_bytes));
   const bool src_pinned = dtype != LSPIV_F64 && is_pinned(frames);
-  const int64_t align = nw ? 1 : std::max(1, chunk_alignment_for(wy, wx, (int64_t)n_win));   // (the search-area kernels are per-pair)
+  const int64_t align = (nw || filter) ? 1 : std::max(1, chunk_alignment_for(wy, wx, (int64_t)n_win));   // (the search-area and the filtered kernels are per-pair)
   // "stack" signal mode scores a window position over ALL frames of the chunk: one launch once everything is resident
   const bool whole_chunk_only = g_opt_signal_mode.load() == 1 && signal_threshold >= 0.0f;
   int64_t launched = 0;   // pairs [0, launched) have been issued
@@ -822,7 +852,7 @@ static int piv_pairs_host(const void* frames, int dtype, int64_t T, int64_t H, i
       p.s2n = c->d_out + 3 * n_tiles + p0 * n_win;
       p.planes = corr_planes ? c->d_planes + (size_t)p0 * n_win * wy * wx : nullptr;
       LSPIV_TRY(apply_signal_mode(c, &p, dev_dtype, c->stream));
-      LSPIV_TRY(dispatch(p, dev_dtype, false, c->stream));
+      LSPIV_TRY(dispatch(p, dev_dtype, false, c->stream, filter));
       LSPIV_TRY(apply_v_sign(p.v, (int64_t)p.n_tiles, c->stream));
       launched = p1;
     }
@@ -851,6 +881,14 @@ int lspiv_piv_pairs_at(const void* frames, int dtype, int64_t T, int64_t H, int6
                        float signal_threshold, int64_t pair_offset, float* u, float* v, float* corr_max, float* s2n,
                        float* corr_planes) {
   return piv_pairs_host(frames, dtype, T, H, W, wy, wx, 0, oy, ox, signal_threshold, pair_offset, u, v, corr_max, s2n, corr_planes, nullptr, 1.0, 1.0);
+}
+
+int lspiv_piv_spof_pairs_at(const void* frames, int dtype, int64_t T, int64_t H, int64_t W, int wy, int wx, int oy, int ox,
+                            float signal_threshold, int64_t pair_offset, float* u, float* v, float* corr_max, float* s2n,
+                            float* corr_planes) {
+  LSPIV_TRY(check_spof(wy, wx));
+  return piv_pairs_host(frames, dtype, T, H, W, wy, wx, 0, oy, ox, signal_threshold, pair_offset, u, v, corr_max, s2n, corr_planes, nullptr, 1.0, 1.0,
+                        LSPIV_FILTER_SPOF);
 }
 
 int lspiv_piv_search_pairs_at(const void* frames, int dtype, int64_t T, int64_t H, int64_t W, int say, int sax, int wy, int wx, int oy,

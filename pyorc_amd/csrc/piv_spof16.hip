@@ -1,0 +1,13 @@
+// The 16 x 16 window of frame t against the 16 x 16 window of frame t+1 through the symmetric phase-only filter (piv_spof_impl.h), per pair
+// and summed over the pairs of a run ("filtered ensemble kernel").
+#include "piv_spof_impl.h"
+#include "piv_spof.h"
+
+namespace lspiv {
+hipError_t launch_piv_spof16(const PivParams& p, int dtype, hipStream_t s) {
+  return launch_spof<16>(p, dtype, s);
+}
+hipError_t launch_piv_spof_ensemble16(const PivParams& p, int dtype, hipStream_t s) {
+  return launch_spof_ensemble<16>(p, dtype, s);
+}
+}  // namespace lspiv

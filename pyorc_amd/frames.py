@@ -71,6 +71,7 @@ def get_piv(frames, window_size=None, overlap=None, engine: str = "hip", ensembl
     ``coarse_passes``: multi-pass PIV -- coarse passes run before ``window_size``, coarsest first, each an int n
     (n x n at overlap n / 2) or a pair ``(n, overlap)``; the result stays on the grid of ``window_size`` / ``overlap``.
     ``deform_passes`` (in ``**kwargs``): 0 .. 4 window deformation passes after the chain, per-timestep mode only.
+    ``spectral_filter`` (in ``**kwargs``): ``"spof"`` -- SPOF phase-filtered correlation, windows of 16, 32 or 64 px.
     """
     if engine not in ENGINES:
         raise ValueError(f"Selected PIV engine {engine} does not exist.")

@@ -55,6 +55,11 @@ def piv_pairs(imgs, window_size=(32, 32), overlap=(16, 16), signal_threshold: Op
         if search_area_size is not None and tuple(int(q) for q in search_area_size) != tuple(window_size):
             raise NotImplementedError("coarse_passes together with a search_area_size larger than the window is not implemented")
         return piv_multipass(imgs, window_size, signal_threshold, return_planes, pair_offset, out=out, scale=scale)
+    if isinstance(window_size, window.FilteredWindow):   # a spectral filter: the filtered per-pair entry points
+        if search_area_size is not None and tuple(int(q) for q in search_area_size) != tuple(window_size):
+            raise NotImplementedError("spectral_filter together with a search_area_size larger than the window is not implemented")
+        return piv_pairs_filtered(imgs, window_size, overlap, window_size.spectral_filter, signal_threshold, return_planes, pair_offset, out=out,
+                                  scale=scale)
     window_size = window.search_spec(window_size, search_area_size)
     search = isinstance(window_size, window.SearchWindow)
     lib = _lib.load()
@@ -169,6 +174,64 @@ def _results_to_host(d_out, P, n_rows, n_cols, out=None):
         return tuple(out)
     res = d_out.to_host().reshape(4, P, n_rows, n_cols)     # lspiv_memcpy_d2h runs on, and waits for, the library's stream
     return tuple(np.ascontiguousarray(res[k]) for k in range(4))
+
+
+def piv_pairs_filtered(imgs, window_size=(32, 32), overlap=(16, 16), spectral_filter="spof", signal_threshold: Optional[float] = None,
+                       return_planes: bool = False, pair_offset: int = 0, out=None, scale=None):
+    """SPOF phase-filtered PIV of every consecutive frame pair of ``imgs``: :func:`piv_pairs` with every bin R
+    of the cross spectrum replaced by R / sqrt(|R|) before the inverse transform ("robust phase correlation"), for imagery whose static
+    or slow background outweighs the tracers.  Returns ``(u, v, corr_max, s2n[, planes])`` like :func:`piv_pairs`; ``corr_max`` is the
+    maximum of the filtered plane (lower than an NCC peak), ``s2n`` its ratio to the mean of the clipped plane.  ``window_size``: square,
+    16, 32 or 64 px.  ``spectral_filter``: ``"spof"``; None / ``"none"`` is :func:`piv_pairs`.  Pair-local, one window per job: every
+    chunking gives the same bits (``pair_offset`` is accepted for symmetry); no float64 rescue pass.  ``out`` / ``scale`` as in
+    :func:`piv_pairs` (the scaling is numpy's own arithmetic on the host).  Host stacks and ``DeviceFrames``."""
+    from .device import DeviceFrames
+
+    flt = window.spectral_filter_spec(spectral_filter)
+    if isinstance(window_size, window.FilteredWindow):
+        flt = flt or window_size.spectral_filter
+    if flt is None:
+        return piv_pairs(imgs, tuple(window_size), overlap, signal_threshold, return_planes, pair_offset, out=out, scale=scale)
+    ws = window.spectral_filter_supported(window_size)          # ValueError naming the sizes
+    ov = (int(overlap[0]), int(overlap[1]))
+    lib = _lib.load()
+    _lib.require_device()
+    a = imgs if is_device(imgs) else _lib.as_frames(imgs)
+    T, H, W = a.shape
+    n_rows, n_cols = window.get_array_shape((H, W), ws, ov)
+    if T < 2 or n_rows < 1 or n_cols < 1:
+        raise ValueError(f"need >= 2 frames at least one window large, got {a.shape} for window {ws}")
+    P, n_win = T - 1, n_rows * n_cols
+    if out is not None:
+        out = _check_out(out, (P, n_rows, n_cols))
+    dt = None
+    if scale is not None:
+        if return_planes:
+            raise ValueError("scale and return_planes exclude each other")
+        dt = np.ascontiguousarray(scale[2], dtype=np.float64).reshape(-1)
+        if dt.shape != (P,):
+            raise ValueError(f"scale: dt must have one entry per frame pair ({P}), got shape {dt.shape}")
+    planes = None
+    if is_device(a):
+        d_out = DeviceFrames.empty((4, P, n_win), np.float32)
+        d_planes = DeviceFrames.empty((P * n_win, ws[0], ws[1]), np.float32) if return_planes else None
+        _lib.check(lib.lspiv_piv_spof_pairs_dev_at(a.c_ptr, a.dtype_code, T, H, W, ws[0], ws[1], ov[0], ov[1], _sig(signal_threshold),
+                                                   int(pair_offset), d_out.c_ptr, d_planes.c_ptr if d_planes is not None else None, None))
+        res = _results_to_host(d_out, P, n_rows, n_cols, out)
+        if return_planes:
+            planes = d_planes.to_host().reshape(P, n_win, ws[0], ws[1])
+    else:
+        res = out if out is not None else [np.empty((P, n_rows, n_cols), dtype=np.float32) for _ in range(4)]
+        if return_planes:
+            planes = np.empty((P, n_win, ws[0], ws[1]), dtype=np.float32)
+        _lib.check(lib.lspiv_piv_spof_pairs_at(_lib.ptr(a), _lib.DTYPE_CODES[a.dtype], T, H, W, ws[0], ws[1], ov[0], ov[1],
+                                               _sig(signal_threshold), int(pair_offset), _lib.ptr(res[0]), _lib.ptr(res[1]), _lib.ptr(res[2]),
+                                               _lib.ptr(res[3]), _lib.ptr(planes) if planes is not None else None))
+        res = tuple(res)
+    if scale is not None:   # no fused scaling entry point for this mode: numpy's own arithmetic (ffpiv.py:418-419)
+        for k in range(2):
+            np.divide(res[k] * scale[k], dt[:, None, None], out=res[k], dtype=np.float64, casting="same_kind")
+    return (*res, planes) if return_planes else tuple(res)
 
 
 def piv_pairs_shifted(imgs, window_size=(32, 32), overlap=(16, 16), shift=None, signal_threshold: Optional[float] = None,
@@ -443,12 +506,25 @@ def u_v_displacement(corr, n_rows: int, n_cols: int, engine: str = "hip") -> Tup
 class Ensemble:
     """Device-resident ensemble-correlation accumulator (pyorc/velocimetry/ffpiv.py:182-376)."""
 
-    def __init__(self, dim_size, window_size, overlap, sliding=None, shift=None):
+    def __init__(self, dim_size, window_size, overlap, sliding=None, shift=None, spectral_filter=None):
         """``sliding=(M, s)``: a sliding ensemble -- outputs over windows of M pairs that advance by s
         pairs, read with :meth:`finish_sliding`; every ``accumulate`` but the last must then hold a multiple of s pairs.
         ``shift``: int16 ``(n_rows, n_cols, 2)`` = (dy, dx) per window, or a ``DeviceFrames`` holding those bytes -- a SHIFTED ensemble pass
         (INTEGRATION.md section 2e): frame t+1's window of every pair is cut at that offset (clamped to the frame: :attr:`shift`), and
-        ``finish`` returns the total displacement.  Windows of 16, 32 or 64 px; not together with ``sliding``."""
+        ``finish`` returns the total displacement.  Windows of 16, 32 or 64 px; not together with ``sliding``.
+        ``spectral_filter``: None / ``"none"`` (today's path) or ``"spof"`` (a ``window.FilteredWindow`` as
+        ``window_size`` carries its own) -- the planes summed are the SPOF phase-filtered ones of :func:`piv_pairs_filtered`; ``corr_min`` /
+        ``s2n_min`` keep their meaning, their useful values are lower.  Windows of 16, 32 or 64 px; every chunking gives the same bits;
+        no float64 rescue of the final fit.  Not together with ``sliding`` or ``shift``."""
+        flt = window.spectral_filter_spec(spectral_filter)
+        if isinstance(window_size, window.FilteredWindow):
+            flt = flt or window_size.spectral_filter
+        if flt is not None:
+            if sliding is not None:
+                raise NotImplementedError("spectral_filter together with ensemble_window is not implemented: a sliding ensemble has no spectral filter")
+            if shift is not None:
+                raise NotImplementedError("spectral_filter together with coarse_passes is not implemented: a shifted ensemble pass has no spectral filter")
+            window.spectral_filter_supported(window_size)      # ValueError naming the sizes
         if sliding is not None:
             sliding = window.sliding_spec(True, *sliding)
             if shift is not None:
@@ -472,12 +548,15 @@ class Ensemble:
         if sliding is not None:
             _lib.check(lib.lspiv_ensemble_set_sliding(self._h, sliding[0], sliding[1]))
         self.shifted = shift is not None
-        if shift is not None:
-            try:
+        self.spectral_filter = flt
+        try:
+            if shift is not None:
                 self._set_shift(shift)
-            except Exception:
-                self.close()
-                raise
+            if flt is not None:
+                _lib.check(lib.lspiv_ensemble_set_spectral_filter(self._h, window.SPECTRAL_FILTERS.index(flt)))
+        except Exception:
+            self.close()
+            raise
 
     def _set_shift(self, shift):
         lib = _lib.load()
@@ -647,7 +726,9 @@ class Ensemble:
         return (u, v, cnt, mean) if return_mean else (u, v, cnt)
 
     def export_state(self):
-        """(corr_sum (n_win, wy, wx) float32 in fft-shifted layout, corr_count (n_win,) float32) from HBM."""
+        """(corr_sum (n_win, wy, wx) float32 in fft-shifted layout, corr_count (n_win,) float32) from HBM.  The handle's
+        ``spectral_filter`` is not part of the state: a state goes back into a handle made with the same filter (``import_state``
+        leaves the handle's own as it is)."""
         n_win = self.n_rows * self.n_cols
         s = np.empty((n_win,) + self.window_size, dtype=np.float32)
         k = np.empty(n_win, dtype=np.float32)

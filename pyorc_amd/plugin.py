@@ -126,6 +126,8 @@ def _wrap_get_piv(orig):
         coarse = kwargs.pop("coarse_passes", None)
         # ... and the window deformation passes' `deform_passes=`
         deform = kwargs.pop("deform_passes", None)
+        # ... and the phase-filtered correlation's `spectral_filter=`
+        spectral = kwargs.pop("spectral_filter", None)
         engine, bound = kwargs.get("engine"), None
         if sig is not None and "engine" in sig.parameters:
             try:
@@ -142,6 +144,8 @@ def _wrap_get_piv(orig):
                 raise TypeError("coarse_passes is a keyword of engine='hip' only")
             if deform is not None:
                 raise TypeError("deform_passes is a keyword of engine='hip' only")
+            if spectral is not None:
+                raise TypeError("spectral_filter is a keyword of engine='hip' only")
             return orig(self, *args, **kwargs)
         # fail before any work if there is no MI355X / no library: the reference raises ValueError for an engine it cannot run
         from . import _lib
@@ -154,6 +158,11 @@ def _wrap_get_piv(orig):
 
             if window_mod.deform_count(deform):     # ValueError outside 0 .. 4; 0 is today's path
                 extra["deform_passes"] = deform
+        if spectral is not None:
+            from . import window as window_mod
+
+            if window_mod.spectral_filter_spec(spectral) is not None:     # ValueError for an unknown name; "none" is today's path
+                extra["spectral_filter"] = spectral
         if search_area is not None or sliding or extra:
             # the reference's method body lays the grid out by the window; with a search area of its own the engine's mirror of that
             # body (pyorc_amd.frames.get_piv: same configuration copy, coordinates, attributes and encoding) runs instead -- and with the

@@ -179,6 +179,7 @@ def get_ffpiv(
     ensemble_stride: Optional[int] = None,
     coarse_passes=None,
     deform_passes=None,
+    spectral_filter=None,
 ):
     """Compute time-resolved (or ensemble) PIV on the MI355X; signature of pyorc's ``get_ffpiv`` (ffpiv.py:24-42).
 
@@ -218,11 +219,28 @@ def get_ffpiv(
     t+1 warped at sub-pixel resolution by the field of the pass before it; the final window must be 16, 32 or 64 px.  One pass roughly
     halves the median error on sheared flows, a second one neither helps nor hurts.  Pair-local: ``chunksize=``, ``devices=``, host
     stacks, ``DeviceFrames`` and lazy stacks give the same bits.  Not with ``ensemble_corr=True`` and not with a search area.
+
+    ``spectral_filter`` (the project's own mode; None or ``"none"``: today's path bit for bit): ``"spof"`` runs
+    the correlation through the symmetric phase-only filter -- every bin R of the cross spectrum becomes R / sqrt(|R|) --, which keeps
+    the tracers' peak where a static or slow background (bed texture, ripples, glare) outweighs them.  Windows of 16, 32 or 64 px,
+    per-timestep and ensemble mode; ``corr`` / ``s2n`` are those of the filtered planes, so useful values of ``corr_min`` / ``s2n_min``
+    are lower than for the plain ensemble.  Pair-local: ``chunksize=``, ``devices=``, host stacks, ``DeviceFrames`` and lazy stacks give
+    the same bits.  No float64 rescue.  Not with ``coarse_passes``, ``deform_passes``, a search area or ``ensemble_window``.
     """
     if engine != "hip":
         raise ValueError(f"Selected PIV engine {engine} does not exist.")
     # a search area of its own: one window argument that answers for the search area wherever a grid, a plan or an alignment is asked for
     window_size = window.search_spec(window_size, search_area_size)
+    flt = window.spectral_filter_spec(spectral_filter)     # ValueError for an unknown name
+    if flt is not None:
+        if coarse_passes is not None and len(coarse_passes):
+            raise NotImplementedError("spectral_filter together with coarse_passes is not implemented: the shifted kernels have no filtered form")
+        if window.deform_count(deform_passes):
+            raise NotImplementedError("spectral_filter together with deform_passes is not implemented: the deformation kernels have no filtered form")
+        if isinstance(window_size, window.SearchWindow):
+            window.filtered_spec(window_size, flt)     # NotImplementedError naming the two keywords
+        if ensemble_window is not None:
+            raise NotImplementedError("spectral_filter together with ensemble_window is not implemented: a sliding ensemble has no spectral filter")
     n_deform = window.deform_count(deform_passes)     # ValueError outside 0 .. 4
     if n_deform:
         if ensemble_corr:
@@ -240,6 +258,8 @@ def get_ffpiv(
     if ensemble_corr and isinstance(window_size, window.SearchWindow):
         raise NotImplementedError("ensemble_corr=True with search_area_size != window_size is not implemented: the search-area kernels "
                                   "serve per-timestep mode only")
+    if flt is not None:
+        window_size = window.filtered_spec(window_size, flt)     # NotImplementedError with a search area, ValueError for another window
     sliding = window.sliding_spec(ensemble_corr, ensemble_window, ensemble_stride)
     n_frames = len(frames)
     dim_size = tuple(frames[0].shape)
@@ -265,8 +285,10 @@ def get_ffpiv(
     devs = _resolve_frames_devices(frames, devices)
     align = window.chunk_alignment(window_size, dim_size, overlap)
     stack_mode = _stack_signal_mode(signal_threshold)
-    # (a chain's later passes read every frame of a chunk at offsets of their own: a lazy stack takes the chunk-loading path)
-    resident_run = _is_lazy(frames) and n_frames >= 2 and not stack_mode and not isinstance(window_size, window.MultiPassWindow)
+    # (a chain's later passes read every frame of a chunk at offsets of their own: a lazy stack takes the chunk-loading path; so does a
+    # filtered run, whose per-pair entry points take chunks)
+    resident_run = (_is_lazy(frames) and n_frames >= 2 and not stack_mode and
+                    not isinstance(window_size, (window.MultiPassWindow, window.FilteredWindow)))
     if resident_run:
         # a lazy stack: resident in HBM, loads planned against HOST memory and cut where dask cuts, launches on the anchors
         work = plan_lazy_devices(frames, n_frames, dim_size, window_size, overlap, n_win, chunksize, memory_factor, engine, prefetch, devs)
@@ -499,8 +521,9 @@ def _timestep_sink(n_pairs, n_workers, y, x, dt, res_x, res_y, window_size, over
     full = {k: np.empty((n_pairs, len(y), len(x)), dtype=np.float32) for k in ("s2n", "corr", "v_x", "v_y")}
     done = []
     px = [None] * n_workers            # per worker: scratch for a launch's u, v in pixels
-    # (the search-area and multi-pass entry points have no fused scaling: numpy's arithmetic on the host, the same bits)
-    on_device = piv.device_scaling_is_numpys(res_x, res_y) and not isinstance(window_size, (window.SearchWindow, window.MultiPassWindow))
+    # (the search-area, multi-pass and filtered entry points have no fused scaling: numpy's arithmetic on the host, the same bits)
+    on_device = piv.device_scaling_is_numpys(res_x, res_y) and not isinstance(window_size, (window.SearchWindow, window.MultiPassWindow,
+                                                                                              window.FilteredWindow))
 
     def launch(k, frames, p0, p1):
         p = p1 - p0

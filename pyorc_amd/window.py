@@ -158,6 +158,60 @@ def multipass_spec(window_size, overlap, coarse_passes=None, deform_passes=None)
     return MultiPassWindow(passes, deform)
 
 
+SPECTRAL_FILTERS = ("none", "spof")
+SPOF_WINDOWS = (16, 32, 64)
+
+
+class FilteredWindow(tuple):
+    """A window whose correlation goes through a spectral filter, as ONE window argument of the layers below
+    ``get_ffpiv`` / ``piv_pairs``: the tuple itself is the window ``(wy, wx)`` -- grid, planes and memory plan are the plain per-pair
+    launch's --, ``.spectral_filter`` the filter's name.  The filtered kernels are per-pair: the chunk alignment is 1."""
+
+    def __new__(cls, window_size, spectral_filter: str):
+        self = super().__new__(cls, (int(window_size[0]), int(window_size[1])))
+        self.spectral_filter = str(spectral_filter)
+        return self
+
+
+def spectral_filter_spec(value) -> Optional[str]:
+    """The ``spectral_filter`` keyword checked: None and ``"none"`` -> None (today's path), ``"spof"`` -> ``"spof"`` (the symmetric
+    phase-only filter R / sqrt(|R|) on the cross spectrum); anything else is a ValueError listing the names.  Host-only."""
+    if value is None:
+        return None
+    if isinstance(value, str) and value in SPECTRAL_FILTERS:
+        return None if value == "none" else value
+    raise ValueError(f"spectral_filter must be None or one of {SPECTRAL_FILTERS}, got {value!r}")
+
+
+def spectral_filter_supported(window_size) -> Tuple[int, int]:
+    """``window_size`` as a pair of ints when the filtered kernels serve it (``lspiv_spof_supported``: square, 16, 32 or 64), else a
+    ValueError naming the sizes.  Host-only."""
+    ws = 2 * (window_size,) if isinstance(window_size, (int, np.integer)) else tuple(window_size)
+    if len(ws) != 2 or not _lib.load().lspiv_spof_supported(int(ws[0]), int(ws[1])):
+        raise ValueError(f"window_size {window_size!r} is not supported with spectral_filter: the window must be square and one of {SPOF_WINDOWS}")
+    return int(ws[0]), int(ws[1])
+
+
+def filtered_spec(window_size, spectral_filter=None):
+    """``window_size`` as the layers below take it: unchanged without a filter (None / "none": today's path), else a validated
+    :class:`FilteredWindow`.  Not together with a search area, a multi-pass chain or deformation passes (NotImplementedError)."""
+    if isinstance(window_size, FilteredWindow):
+        if spectral_filter_spec(spectral_filter) not in (None, window_size.spectral_filter):
+            raise ValueError("spectral_filter given twice: window_size is a FilteredWindow already")
+        return window_size
+    flt = spectral_filter_spec(spectral_filter)
+    if flt is None:
+        return window_size
+    if isinstance(window_size, SearchWindow):
+        raise NotImplementedError("spectral_filter together with a search_area_size larger than the window is not implemented: the "
+                                  "filtered kernels correlate two windows of one size")
+    if isinstance(window_size, MultiPassWindow):
+        raise NotImplementedError(("spectral_filter together with deform_passes" if window_size.deform and len(window_size.passes) == 1
+                                   else "spectral_filter together with coarse_passes") + " is not implemented: the shifted and the "
+                                  "deformation kernels have no filtered form")
+    return FilteredWindow(spectral_filter_supported(window_size), flt)
+
+
 MIN_STEERING_GRID = 3
 
 
@@ -218,7 +272,8 @@ def required_memory(n_frames: int, dim_size, window_size, overlap, search_area_s
     ``ensemble_sums``: an ensemble's plane sums and counts (:func:`ensemble_sums_bytes`) stay in HBM next to every chunk -- of the pass
     that needs most, in a chain (the multi-pass ensemble, INTEGRATION.md section 2e, runs one pass at a time).
     ``deform_passes`` (or a :class:`MultiPassWindow` that carries them): the warped frames of one batch of pairs and the nodes
-    (:func:`deform_bytes`) come on top.
+    (:func:`deform_bytes`) come on top.  A :class:`FilteredWindow` answers as the plain per-pair launch of its window: the filtered
+    kernels have no workspace.
     """
     if coarse_passes or deform_count(deform_passes) or isinstance(window_size, MultiPassWindow):
         # a chain: the frames once, the largest pass's launch (results, rescue lists, the planes of the final pass), and the
@@ -330,8 +385,8 @@ def chunk_alignment(window_size, dim_size=None, overlap=None) -> int:
     that shape are cut.  Without them the alignment that is right on EVERY grid comes back (``lspiv_chunk_alignment``, ABI 5: the
     longest anchor length of the window family, a multiple of every grid's -- 75 where ABI 4 answered 25)."""
     lib = _lib.load()
-    if isinstance(window_size, SearchWindow):
-        return 1   # the search-area kernels are per-pair: any chunking gives the same bits
+    if isinstance(window_size, (SearchWindow, FilteredWindow)):
+        return 1   # the search-area and the filtered kernels are per-pair: any chunking gives the same bits
     if isinstance(window_size, MultiPassWindow):
         # pass 0 is the per-timestep path on ITS window and grid; every later pass is pair-local
         n0, o0 = window_size.passes[0]
