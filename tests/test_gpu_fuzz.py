@@ -63,6 +63,17 @@ def test_fuzz_rows(gpu):
     assert "150 cases, 0 failures" in out.stdout
 
 
+@pytest.mark.gpu
+@pytest.mark.parametrize("switch,seed", [("FUZZ_BIGWDW", 51), ("FUZZ_W4", 52)])
+def test_fuzz_rows_blur_with_the_tools_own_switches(gpu, switch, seed):
+    """The blur kind alone under the two switches of tools/fuzz_rows.py that no other test sets: FUZZ_BIGWDW=1 draws windows up to 15 (the
+    LDS-ring kernel on float frames, with the planted NaN kept), FUZZ_W4=1 widths that are multiples of four, uint8 more often (the
+    four-column integer kernel)."""
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "tools", "fuzz_rows.py"), str(seed), "60"], capture_output=True, text=True, cwd=ROOT,
+                         env=dict(os.environ, FUZZ_KINDS="blur", **{switch: "1"}))
+    assert out.returncode == 0, out.stdout[-3000:] + out.stderr[-2000:]
+    assert "60 cases, 0 failures" in out.stdout
+
 
 @pytest.mark.gpu
 @pytest.mark.parametrize("switch", ["LSPIV_NORM_FRAME_MAJOR=1", "LSPIV_BLUR_BLOCK=1", "LSPIV_PROJECT_ONE_CELL=1", "LSPIV_PROJECT_FPT=4", "LSPIV_PROJECT_GX=0"])
