@@ -45,7 +45,8 @@ extern "C" {
                                * lspiv_deform_supported / lspiv_deform_required_bytes / lspiv_piv_predict_deform_dev /
                                * lspiv_piv_deform_pairs_dev_at / lspiv_piv_multipass_deform_dev_at / lspiv_piv_multipass_deform_at; SPOF phase-filtered
                                * correlation, lspiv_spof_supported / lspiv_piv_spof_pairs_dev_at / lspiv_piv_spof_pairs_at /
-                               * lspiv_ensemble_set_spectral_filter / _get_spectral_filter)
+                               * lspiv_ensemble_set_spectral_filter / _get_spectral_filter; the image mask, lspiv_mask_supported /
+                               * lspiv_piv_masked_pairs_dev_at / lspiv_piv_masked_pairs_at)
                                * 5 (round 6): lspiv_chunk_alignment(wy, wx) without a grid now returns the alignment that is right on EVERY grid (75
                                * where it returned 25: callers that cut chunks on it stay bit-reproducible on large grids); additions:
                                * lspiv_upload_frames, lspiv_trace / lspiv_trace_read; the host-pointer projection entry points no longer
@@ -350,6 +351,36 @@ int lspiv_piv_spof_pairs_dev_at(const void* d_frames, int dtype, int64_t T, int6
 int lspiv_piv_spof_pairs_at(const void* frames, int dtype, int64_t T, int64_t H, int64_t W,
                             int wy, int wx, int oy, int ox, float signal_threshold, int64_t pair_offset,
                             float* u, float* v, float* corr_max, float* s2n, float* corr_planes);
+
+/* Image mask (the project's own semantics, unpinned): the per-pair result over the VALID samples of each
+ * window, for windows that straddle banks, piers, vegetation or the edge of the orthoprojected area.  Replaces ffpiv.cross_corr + the
+ * corr_max / s2n reductions + ffpiv.u_v_displacement (pyorc/velocimetry/ffpiv.py:446-474) with, per pair of N x N windows A, B
+ * (N = wy = wx in {16, 32, 64}) under the window M of the mask (H x W bytes, non-zero = valid, one mask for every frame), k = sum M:
+ * mean = sum M A / k, std = sqrt(sum M (A - mean)^2 / k) ("std_ddof": k - 1), a^ = max((A - mean) / std, 0) on valid samples, 0 where
+ * std = 0 and EXACTLY 0 on excluded samples, b^ likewise under the same M; plane = clip(fftshift(irfft2(conj(rfft2 a^) rfft2 b^)) / k,
+ * 0, 1); corr_max = max of the plane; s2n = max / mean of the plane over all N^2 samples; u, v = the first maximum in row-major order
+ * and the three-point log-Gaussian fit on plane + 1e-7 ("border_peak", "v_sign" as everywhere).  An excluded sample never enters the
+ * arithmetic: a NaN, Inf or any value there changes no bit of any result.  k < k_min (the caller's max(2, ceil(coverage * N^2)), formed
+ * in float64 on the host), a valid non-finite sample, or a pair failing signal_threshold -- the share of signal samples AMONG THE VALID
+ * ones, count / k, of A and of B -- gives NaN u, v, corr_max, s2n and a NaN plane.  A window with k = N^2 gives the plane of
+ * lspiv_piv_pairs_dev_at.  The float64 rescue pass follows as on the other per-pair paths ("rescue"), with the mask.  Options
+ * "norm_clip" = 0 and "signal_mode" = 1 and every other window are LSPIV_EUNSUPPORTED; k_min outside 2 .. N^2 is LSPIV_EINVAL.
+ *
+ * lspiv_mask_supported: 1 for wy = wx in {16, 32, 64}, else 0.  Host-only.
+ * lspiv_piv_masked_pairs_dev_at: d_mask is H x W bytes on the device; the kernels read the caller's bytes as they are (a lane folds its
+ * row of them into one bit per sample), no copy is made.  d_out, d_corr_planes as lspiv_piv_pairs_dev_at lays them out.  One window per
+ * job, one plane per inverse transform: a window's result depends on its own samples and its own mask alone, so every chunking gives
+ * the same bits; pair_offset is accepted for symmetry.
+ * lspiv_piv_masked_pairs_at: the host-fed twin -- the chunk is staged like lspiv_piv_pairs_at stages it (float64 narrowed to float32),
+ * `mask` (H x W bytes of host memory) goes up once per call into memory the library owns. */
+int lspiv_mask_supported(int wy, int wx);
+int lspiv_piv_masked_pairs_dev_at(const void* d_frames, int dtype, int64_t T, int64_t H, int64_t W,
+                                  int wy, int wx, int oy, int ox, const uint8_t* d_mask, int64_t k_min,
+                                  float signal_threshold, int64_t pair_offset, float* d_out, float* d_corr_planes, void* stream);
+int lspiv_piv_masked_pairs_at(const void* frames, int dtype, int64_t T, int64_t H, int64_t W,
+                              int wy, int wx, int oy, int ox, const uint8_t* mask, int64_t k_min,
+                              float signal_threshold, int64_t pair_offset,
+                              float* u, float* v, float* corr_max, float* s2n, float* corr_planes);
 
 /* Host frames into a slice of an HBM-resident stack, the way lspiv_piv_pairs brings them in -- pinned ring, staging threads,
  * float64 narrowed to float32 with the "narrow_offset" guard (so d_dst receives n_frames * H * W samples of LSPIV_F32 for LSPIV_F64

@@ -1,6 +1,7 @@
 // C ABI of liblspiv_hip.so, PIV (api_core.hip has the overview): the window grid, the kernel of a window's family, the float64 rescue
 // pass after it, the chunk alignment, the device-pointer and host-pointer PIV entry points.
 #include "api_internal.h"
+#include "piv_masked.h"
 #include "piv_spof.h"
 
 #include <algorithm>
@@ -179,6 +180,11 @@ int apply_v_sign(float* d_v, int64_t n, hipStream_t s) {
 }
 
 static int dispatch_kernels(const lspiv::PivParams& p, int dtype, bool ensemble, hipStream_t s, int filter) {
+  if (p.mask) {   // image mask: the one-window-per-job kernels of piv_masked_impl.h, per pair (the rescue pass after them reads p.mask too)
+    if (ensemble || filter) return fail(LSPIV_EUNSUPPORTED, "an image mask has per-pair NCC kernels only");
+    return launch_status(p.wy == 16 ? lspiv::launch_piv_masked16(p, dtype, s) : p.wy == 32 ? lspiv::launch_piv_masked32(p, dtype, s)
+                                                                                            : lspiv::launch_piv_masked64(p, dtype, s));
+  }
   if (filter) {   // SPOF phase-filtered correlation: the one-window-per-job kernels of piv_spof_impl.h, per pair or summed by one owner per window
     if (filter != LSPIV_FILTER_SPOF) return fail(LSPIV_EINVAL, "spectral filter %d not in {0: none, 1: SPOF}", filter);
     if (ensemble)
@@ -289,6 +295,19 @@ int check_spof(int wy, int wx) {
     return fail(LSPIV_EUNSUPPORTED, "option norm_clip = 0 is served by the block-per-window kernels only, not by SPOF-filtered correlation");
   if (g_opt_signal_mode.load() == 1)
     return fail(LSPIV_EUNSUPPORTED, "option signal_mode = 1 is not supported by SPOF-filtered correlation: its kernels score the two windows of a pair");
+  return LSPIV_OK;
+}
+// ---- image mask: the window is 16, 32 or 64 px square, k_min lies in 2 .. N^2; norm_clip = 0 / signal_mode = 1 are refused like above ----
+static int check_masked(int wy, int wx, const void* mask, int64_t k_min) {
+  if (!shift_shape_ok(wy, wx))
+    return fail(LSPIV_EUNSUPPORTED, "masked correlation with window %dx%d is not supported: the window must be square and one of {16, 32, 64}", wy, wx);
+  if (!g_opt_norm_clip.load())
+    return fail(LSPIV_EUNSUPPORTED, "option norm_clip = 0 is served by the block-per-window kernels only, not by masked correlation");
+  if (g_opt_signal_mode.load() == 1)
+    return fail(LSPIV_EUNSUPPORTED, "option signal_mode = 1 is not supported by masked correlation: its kernels score the valid samples of the two windows of a pair");
+  if (!mask) return fail(LSPIV_EINVAL, "mask is NULL");
+  if (k_min < 2 || k_min > (int64_t)wy * wx)
+    return fail(LSPIV_EINVAL, "k_min %lld not in 2 .. %d (max(2, ceil(mask_coverage_min * window area)))", (long long)k_min, wy * wx);
   return LSPIV_OK;
 }
 
@@ -439,9 +458,11 @@ int lspiv_chunk_alignment_grid(int64_t H, int64_t W, int wy, int wx, int oy, int
 
 // nw: 0, or the window inside the search area wy x wx (search-area mode)
 // filter: 0, or LSPIV_FILTER_SPOF (the caller has run check_spof)
+// d_mask, k_min: nullptr, or the image mask of the frames' shape on the device and the smallest count of valid samples (the caller has
+// run check_masked)
 static int piv_pairs_dev(const void* d_frames, int dtype, int64_t T, int64_t H, int64_t W, int wy, int wx, int nw, int oy,
                          int ox, float signal_threshold, int64_t pair_offset, float* d_out, float* d_corr_planes,
-                         void* stream, int filter = 0) {
+                         void* stream, int filter = 0, const uint8_t* d_mask = nullptr, int64_t k_min = 0) {
   if (!d_frames || !d_out) return fail(LSPIV_EINVAL, "d_frames / d_out is NULL");
   if (pair_offset < 0) return fail(LSPIV_EINVAL, "pair_offset %lld is negative", (long long)pair_offset);
   Grid g;
@@ -457,6 +478,8 @@ static int piv_pairs_dev(const void* d_frames, int dtype, int64_t T, int64_t H, 
   p.cmax = d_out + 2 * (size_t)p.n_tiles;
   p.s2n = d_out + 3 * (size_t)p.n_tiles;
   p.planes = d_corr_planes;
+  p.mask = d_mask;
+  p.k_min = (uint32_t)k_min;
   hipStream_t s = on_stream(c, stream);
   LSPIV_TRY(apply_signal_mode(c, &p, dtype, s));
   LSPIV_TRY(dispatch(p, dtype, false, s, filter));
@@ -475,6 +498,15 @@ int lspiv_piv_spof_pairs_dev_at(const void* d_frames, int dtype, int64_t T, int6
                                 float signal_threshold, int64_t pair_offset, float* d_out, float* d_corr_planes, void* stream) {
   LSPIV_TRY(check_spof(wy, wx));
   return piv_pairs_dev(d_frames, dtype, T, H, W, wy, wx, 0, oy, ox, signal_threshold, pair_offset, d_out, d_corr_planes, stream, LSPIV_FILTER_SPOF);
+}
+
+int lspiv_mask_supported(int wy, int wx) { return shift_shape_ok(wy, wx) ? 1 : 0; }
+
+int lspiv_piv_masked_pairs_dev_at(const void* d_frames, int dtype, int64_t T, int64_t H, int64_t W, int wy, int wx, int oy, int ox,
+                                  const uint8_t* d_mask, int64_t k_min, float signal_threshold, int64_t pair_offset, float* d_out,
+                                  float* d_corr_planes, void* stream) {
+  LSPIV_TRY(check_masked(wy, wx, d_mask, k_min));
+  return piv_pairs_dev(d_frames, dtype, T, H, W, wy, wx, 0, oy, ox, signal_threshold, pair_offset, d_out, d_corr_planes, stream, 0, d_mask, k_min);
 }
 
 int lspiv_search_supported(int say, int sax, int wy, int wx) { return search_shape_ok(say, sax, wy, wx) ? 1 : 0; }
@@ -795,7 +827,8 @@ int lspiv_piv_pairs_dev(const void* d_frames, int dtype, int64_t T, int64_t H, i
 // nw: 0, or the window inside the search area wy x wx (search-area mode)
 static int piv_pairs_host(const void* frames, int dtype, int64_t T, int64_t H, int64_t W, int wy, int wx, int nw, int oy, int ox,
                           float signal_threshold, int64_t pair_offset, float* u, float* v, float* corr_max, float* s2n,
-                          float* corr_planes, const double* dt, double res_x, double res_y, int filter = 0) {
+                          float* corr_planes, const double* dt, double res_x, double res_y, int filter = 0, const uint8_t* mask = nullptr,
+                          int64_t k_min = 0) {
   std::lock_guard<std::mutex> host_lock(locks_here().host);
   if (!frames || !u || !v || !corr_max || !s2n) return fail(LSPIV_EINVAL, "NULL buffer");
   if (pair_offset < 0) return fail(LSPIV_EINVAL, "pair_offset %lld is negative", (long long)pair_offset);
@@ -820,12 +853,18 @@ static int piv_pairs_host(const void* frames, int dtype, int64_t T, int64_t H, i
   lspiv::PivParams base;
   LSPIV_TRY(fill_params(&base, c->d_frames, dev_dtype, T, H, W, wy, wx, oy, ox, signal_threshold, g));
   if (nw) set_search_window(&base, nw);
+  if (mask) {   // the image mask goes up once, into the context's own buffer (under the host lock, like the frames' workspace), ahead of the kernels
+    LSPIV_TRY(ensure(&c->d_mask, &c->mask_cap, (size_t)H * W));
+    HIP_TRY(hipMemcpyAsync(c->d_mask, mask, (size_t)H * W, hipMemcpyHostToDevice, c->stream));
+    base.mask = c->d_mask;
+    base.k_min = (uint32_t)k_min;
+  }
   const size_t n_win = (size_t)g.n_rows * g.n_cols;
   const size_t frame_bytes = (size_t)H * W * elem_size(dev_dtype);
   LSPIV_TRY(stage_ring(c, frame_bytes));
   const int64_t fpb = std::max<int64_t>(1, (int64_t)(c->pinned_cap / frame_bytes));
   const bool src_pinned = dtype != LSPIV_F64 && is_pinned(frames);
-  const int64_t align = (nw || filter) ? 1 : std::max(1, chunk_alignment_for(wy, wx, (int64_t)n_win));   // (the search-area and the filtered kernels are per-pair)
+  const int64_t align = (nw || filter || mask) ? 1 : std::max(1, chunk_alignment_for(wy, wx, (int64_t)n_win));   // (the search-area and the filtered kernels are per-pair)
   // "stack" signal mode scores a window position over ALL frames of the chunk: one launch once everything is resident
   const bool whole_chunk_only = g_opt_signal_mode.load() == 1 && signal_threshold >= 0.0f;
   int64_t launched = 0;   // pairs [0, launched) have been issued
@@ -889,6 +928,14 @@ int lspiv_piv_spof_pairs_at(const void* frames, int dtype, int64_t T, int64_t H,
   LSPIV_TRY(check_spof(wy, wx));
   return piv_pairs_host(frames, dtype, T, H, W, wy, wx, 0, oy, ox, signal_threshold, pair_offset, u, v, corr_max, s2n, corr_planes, nullptr, 1.0, 1.0,
                         LSPIV_FILTER_SPOF);
+}
+
+int lspiv_piv_masked_pairs_at(const void* frames, int dtype, int64_t T, int64_t H, int64_t W, int wy, int wx, int oy, int ox,
+                              const uint8_t* mask, int64_t k_min, float signal_threshold, int64_t pair_offset, float* u, float* v,
+                              float* corr_max, float* s2n, float* corr_planes) {
+  LSPIV_TRY(check_masked(wy, wx, mask, k_min));
+  return piv_pairs_host(frames, dtype, T, H, W, wy, wx, 0, oy, ox, signal_threshold, pair_offset, u, v, corr_max, s2n, corr_planes, nullptr, 1.0, 1.0,
+                        0, mask, k_min);
 }
 
 int lspiv_piv_search_pairs_at(const void* frames, int dtype, int64_t T, int64_t H, int64_t W, int say, int sax, int wy, int wx, int oy,

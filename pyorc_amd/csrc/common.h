@@ -123,6 +123,11 @@ struct PivParams {
   // predicted displacement at its own centre; the kernels and the rescue pass write the RESIDUAL, launch_add_nodes adds nodes / 128
   const float* warped;
   const int32_t* nodes;
+  // image mask (piv_masked_impl.h): mask != nullptr selects the masked per-pair kernels and the masked branch of
+  // the rescue pass -- H x W bytes, non-zero = valid, one mask for every frame; a window correlates its valid samples only and is NaN
+  // below k_min of them (k_min >= 2, formed on the host)
+  const uint8_t* mask;
+  uint32_t k_min;
 };
 
 // The offset of result g = pair * n_win + window (shifted ensemble pass: g = window; grid row wrow, column wcol), clamped so that the shifted window stays inside

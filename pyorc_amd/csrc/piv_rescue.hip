@@ -159,6 +159,20 @@ __device__ __forceinline__ double norm_clip(double x, double mean, double inv_sd
   return (d > 0.0 || inv_sd < 0.0) ? d : 0.0;
 }
 
+// image mask (p.mask): is the sample at offset `off` of the window valid?  Without a mask: yes, at no cost
+template <bool MASKED>
+__device__ __forceinline__ bool mask_on(const uint8_t* M, int off) {
+  if constexpr (MASKED) return M[off] != 0;
+  else return true;
+}
+// normalised sample of window B at offset `off`, zero where the mask excludes it
+template <bool MASKED, typename PB>
+__device__ __forceinline__ double norm_clip_b(PB B, const uint8_t* M, int off, double mean_b, double inv_b) {
+  const double v = norm_clip((double)B[off], mean_b, inv_b);
+  if constexpr (MASKED) return M[off] != 0 ? v : 0.0;
+  else return v;
+}
+
 // un-shifted lag of a shifted plane coordinate
 template <int WN = 0>
 __device__ __forceinline__ int unshift(int ip, int c, int w) {
@@ -167,9 +181,11 @@ __device__ __forceinline__ int unshift(int ip, int c, int w) {
 }
 
 // which of two shifted plane positions holds the larger float64 correlation (ties: the smaller row-major index, np.argmax)
-template <int WY = 0, int WX = 0, typename PA, typename PB>
+// (MASKED: M is the window of the image mask at A's pitch; an excluded sample of either window is selected to zero -- its value is
+// loaded and dropped, never multiplied)
+template <int WY = 0, int WX = 0, bool MASKED = false, typename PA, typename PB>
 __device__ __forceinline__ uint32_t choose_wave(const PivParams& p, PA A, PB B, int pitch, double mean_a, double inv_a, double mean_b,
-                                                double inv_b, uint32_t pos1, uint32_t pos2, int lane) {
+                                                double inv_b, uint32_t pos1, uint32_t pos2, int lane, const uint8_t* M = nullptr) {
   const int wy = WY ? WY : p.wy, wx = WX ? WX : p.wx, n = wy * wx, cy = wy / 2, cx = wx / 2;
   const int ky1 = unshift<WY>((int)(pos1 >> 16), cy, wy), kx1 = unshift<WX>((int)(pos1 & 0xffffu), cx, wx);
   const int ky2 = unshift<WY>((int)(pos2 >> 16), cy, wy), kx2 = unshift<WX>((int)(pos2 & 0xffffu), cx, wx);
@@ -179,11 +195,11 @@ __device__ __forceinline__ uint32_t choose_wave(const PivParams& p, PA A, PB B, 
   lw.start(lane, y, x);
 #pragma unroll 4
   for (int e = lane; e < n; e += 64, lw.next(y, x)) {
-    const double av = a_inside<WY != 0>(p, y, x) ? norm_clip((double)A[y * pitch + x], mean_a, inv_a) : 0.0;
+    const double av = (a_inside<WY != 0>(p, y, x) && mask_on<MASKED>(M, y * pitch + x)) ? norm_clip((double)A[y * pitch + x], mean_a, inv_a) : 0.0;
     const int y1 = wrap_once<WY>(y + ky1, wy), x1 = wrap_once<WX>(x + kx1, wx);
     const int y2 = wrap_once<WY>(y + ky2, wy), x2 = wrap_once<WX>(x + kx2, wx);
-    acc1 += av * norm_clip((double)B[y1 * pitch + x1], mean_b, inv_b);
-    acc2 += av * norm_clip((double)B[y2 * pitch + x2], mean_b, inv_b);
+    acc1 += av * norm_clip_b<MASKED>(B, M, y1 * pitch + x1, mean_b, inv_b);
+    acc2 += av * norm_clip_b<MASKED>(B, M, y2 * pitch + x2, mean_b, inv_b);
   }
   const double c1 = wave_sum_d(acc1), c2 = wave_sum_d(acc2);   // same scale and clip for both: compare the sums
   const uint32_t o1 = (pos1 >> 16) * (uint32_t)wx + (pos1 & 0xffffu), o2 = (pos2 >> 16) * (uint32_t)wx + (pos2 & 0xffffu);
@@ -194,9 +210,9 @@ __device__ __forceinline__ uint32_t choose_wave(const PivParams& p, PA A, PB B, 
 // k = the peak and its four neighbours, all in float64; every lane gets the five values
 // (A, B: the two windows, in global memory (pitch = frame width) or staged in LDS (pitch = window width))
 struct Lag5 { double c0, cu, cd, cl, cr; };   // centre, row above, row below, column left, column right
-template <int WY = 0, int WX = 0, typename PA, typename PB>
+template <int WY = 0, int WX = 0, bool MASKED = false, typename PA, typename PB>
 __device__ __forceinline__ Lag5 lag5_wave(const PivParams& p, PA A, PB B, int pitch, double mean_a, double inv_a, double mean_b,
-                                          double inv_b, int ip, int jp, int lane) {
+                                          double inv_b, int ip, int jp, int lane, const uint8_t* M = nullptr) {
   const int wy = WY ? WY : p.wy, wx = WX ? WX : p.wx, n = wy * wx, cy = wy / 2, cx = wx / 2;
   // un-shifted lags of the peak and its four neighbours
   const int ky0 = unshift<WY>(ip, cy, wy), kx0 = unshift<WX>(jp, cx, wx);
@@ -208,14 +224,14 @@ __device__ __forceinline__ Lag5 lag5_wave(const PivParams& p, PA A, PB B, int pi
   lw.start(lane, y, x);
 #pragma unroll 4
   for (int e = lane; e < n; e += 64, lw.next(y, x)) {
-    const double av = a_inside<WY != 0>(p, y, x) ? norm_clip((double)A[y * pitch + x], mean_a, inv_a) : 0.0;
+    const double av = (a_inside<WY != 0>(p, y, x) && mask_on<MASKED>(M, y * pitch + x)) ? norm_clip((double)A[y * pitch + x], mean_a, inv_a) : 0.0;
     const int y0 = wrap_once<WY>(y + ky0, wy), ym = wrap_once<WY>(y + kym, wy), yp = wrap_once<WY>(y + kyp, wy);
     const int x0 = wrap_once<WX>(x + kx0, wx), xm = wrap_once<WX>(x + kxm, wx), xp = wrap_once<WX>(x + kxp, wx);
-    acc0 += av * norm_clip((double)B[y0 * pitch + x0], mean_b, inv_b);
-    accu += av * norm_clip((double)B[ym * pitch + x0], mean_b, inv_b);
-    accd += av * norm_clip((double)B[yp * pitch + x0], mean_b, inv_b);
-    accl += av * norm_clip((double)B[y0 * pitch + xm], mean_b, inv_b);
-    accr += av * norm_clip((double)B[y0 * pitch + xp], mean_b, inv_b);
+    acc0 += av * norm_clip_b<MASKED>(B, M, y0 * pitch + x0, mean_b, inv_b);
+    accu += av * norm_clip_b<MASKED>(B, M, ym * pitch + x0, mean_b, inv_b);
+    accd += av * norm_clip_b<MASKED>(B, M, yp * pitch + x0, mean_b, inv_b);
+    accl += av * norm_clip_b<MASKED>(B, M, y0 * pitch + xm, mean_b, inv_b);
+    accr += av * norm_clip_b<MASKED>(B, M, y0 * pitch + xp, mean_b, inv_b);
   }
   const double inv_n = 1.0 / corr_samples<WY, WX>(p);
   auto clip01 = [](double c) { return c < 0.0 ? 0.0 : (c > 1.0 ? 1.0 : c); };
@@ -236,9 +252,9 @@ __device__ __forceinline__ void fit5_d(const Lag5& c, int ip, int jp, int cy, in
 }
 
 // the five-sample fit at shifted position (ip, jp), all in float64; one wave, lane 0 stores
-template <int WY = 0, int WX = 0, typename PA, typename PB>
+template <int WY = 0, int WX = 0, bool MASKED = false, typename PA, typename PB>
 __device__ __forceinline__ void fit_wave(const PivParams& p, PA A, PB B, int pitch, double mean_a, double inv_a, double mean_b,
-                                         double inv_b, uint32_t g, int ip, int jp, int lane) {
+                                         double inv_b, uint32_t g, int ip, int jp, int lane, const uint8_t* M = nullptr) {
   const int wy = WY ? WY : p.wy, wx = WX ? WX : p.wx, cy = wy / 2, cx = wx / 2;
   if (ip <= 0 || ip >= wy - 1 || jp <= 0 || jp >= wx - 1) {   // border peak: no fit (A5)
     if (lane == 0) {
@@ -248,7 +264,7 @@ __device__ __forceinline__ void fit_wave(const PivParams& p, PA A, PB B, int pit
     }
     return;
   }
-  const Lag5 c = lag5_wave<WY, WX>(p, A, B, pitch, mean_a, inv_a, mean_b, inv_b, ip, jp, lane);
+  const Lag5 c = lag5_wave<WY, WX, MASKED>(p, A, B, pitch, mean_a, inv_a, mean_b, inv_b, ip, jp, lane, M);
   // the five logarithms side by side on five lanes instead of one after the other on lane 0
   const double eps = 1e-7;
   const double mine = log((lane == 0 ? c.c0 : lane == 1 ? c.cu : lane == 2 ? c.cd : lane == 3 ? c.cl : c.cr) + eps);
@@ -297,6 +313,50 @@ __device__ __forceinline__ const T* window_base_b_frames(const PivParams& p, uin
   return B;
 }
 
+// ---- image mask (p.mask; piv_masked_impl.h) ------------------------------------------------------------------
+// the window of the mask under result g's two windows (one mask for every frame; masked launches have no offsets)
+__device__ __forceinline__ const uint8_t* window_mask_base(const PivParams& p, uint32_t g) {
+  const uint32_t pair = g / p.n_win, win = g - pair * p.n_win;
+  const uint32_t wrow = win / (uint32_t)p.n_cols, wcol = win - wrow * (uint32_t)p.n_cols;
+  return p.mask + (int64_t)wrow * p.sy * p.W + (int64_t)wcol * p.sx;
+}
+// The factors of both windows over their k valid samples, by one wave: mean = sum M x / k, variance = sum M (x - mean)^2 / k in two
+// passes (a valid sample to shift by is not at a fixed place, and the windows that come here are few); excluded samples are loaded and
+// selected away.  inv_a carries n / k next to the "std_ddof" gain sqrt((k - 1) / k) of THIS window: the lag sums divide by n, the
+// plane by k.  false: a zero-variance window (never listed)
+template <typename T>
+__device__ __forceinline__ bool masked_factors_wave(const PivParams& p, const T* A, const T* B, const uint8_t* M, int lane, double& mean_a,
+                                                    double& inv_a, double& mean_b, double& inv_b) {
+  const int wy = p.wy, wx = p.wx, n = wy * wx;
+  const LaneWalk<0> lw(wx);
+  double sa = 0.0, sb = 0.0, cnt = 0.0;
+  int y, x;
+  lw.start(lane, y, x);
+  for (int e = lane; e < n; e += 64, lw.next(y, x)) {
+    const int64_t off = (int64_t)y * p.W + x;
+    const bool on = M[off] != 0;
+    const double va = (double)A[off], vb = (double)B[off];
+    sa += on ? va : 0.0; sb += on ? vb : 0.0; cnt += on ? 1.0 : 0.0;
+  }
+  sa = wave_sum_d(sa); sb = wave_sum_d(sb);
+  const double k = wave_sum_d(cnt);
+  mean_a = sa / k; mean_b = sb / k;
+  double qa = 0.0, qb = 0.0;
+  lw.start(lane, y, x);
+  for (int e = lane; e < n; e += 64, lw.next(y, x)) {
+    const int64_t off = (int64_t)y * p.W + x;
+    const bool on = M[off] != 0;
+    const double da = (double)A[off] - mean_a, db = (double)B[off] - mean_b;
+    qa += on ? da * da : 0.0; qb += on ? db * db : 0.0;
+  }
+  const double va = wave_sum_d(qa) / k, vb = wave_sum_d(qb) / k;
+  if (!(va > 0.0) || !(vb > 0.0)) return false;
+  const double sg = p.std_gain != 1.0f ? sqrt((k - 1.0) / k) : 1.0;   // (norm_clip = 0 is refused with a mask)
+  inv_a = sg / sqrt(va) * ((double)n / k);
+  inv_b = sg / sqrt(vb);
+  return true;
+}
+
 // first arg-max merge in shifted row-major order: larger value wins, equal values -> smaller index
 __device__ __forceinline__ void amax_merge_d(double& v, int& idx, double pv, int pidx) {
   const bool take = (pv > v) || (pv == v && pidx < idx);
@@ -322,7 +382,8 @@ constexpr size_t fit_slice_bytes() {
   return WY ? (((size_t)WY * WX * (sizeof(T) + sizeof(TB)) + 15) & ~(size_t)15) : (size_t)FIT_LDS_PER_WAVE;
 }
 
-template <typename T, typename TB = T, int WY = 0, int WX = 0>
+// MASKED (p.mask): run-time geometry, the samples straight from the frames with the mask's window next to them
+template <typename T, typename TB = T, int WY = 0, int WX = 0, bool MASKED = false>
 __global__ __launch_bounds__(RBLOCK) void piv_rescue_fit_kernel(PivParams p) {
   extern __shared__ __attribute__((aligned(16))) unsigned char fsm[];
   typedef const T __attribute__((address_space(3))) * LdsPtr;
@@ -342,6 +403,17 @@ __global__ __launch_bounds__(RBLOCK) void piv_rescue_fit_kernel(PivParams p) {
     if (g >= p.n_tiles) continue;   // a record of another launch (two host threads interleaving on one stream): never write out of bounds
     const T* A = window_base<T>(p, g);
     const TB* B = window_base_b<T, TB>(p, g, A);
+    if constexpr (MASKED) {
+      static_assert(std::is_same<T, TB>::value && WY == 0 && WX == 0, "masked launches: both windows from the frames, generic kernel");
+      const uint8_t* M = window_mask_base(p, g);
+      double mean_a, inv_a, mean_b, inv_b;
+      if (masked_factors_wave<T>(p, A, B, M, lane, mean_a, inv_a, mean_b, inv_b)) {
+        uint32_t pos = rec.y;
+        if (rec.z != 0xffffffffu) pos = choose_wave<0, 0, true>(p, A, B, p.W, mean_a, inv_a, mean_b, inv_b, rec.y, rec.z, lane, M);
+        fit_wave<0, 0, true>(p, A, B, p.W, mean_a, inv_a, mean_b, inv_b, g, (int)(pos >> 16), (int)(pos & 0xffffu), lane, M);
+      }
+      continue;
+    }
     double mean_a, sd_a, mean_b, sd_b;
     if (staged) pair_stats_wave<T, true, TB, WY, WX>(p, A, B, lane, mean_a, sd_a, mean_b, sd_b, la, lb);
     else pair_stats_wave<T, false, TB, WY, WX>(p, A, B, lane, mean_a, sd_a, mean_b, sd_b);
@@ -371,7 +443,7 @@ __global__ __launch_bounds__(RBLOCK) void piv_rescue_fit_kernel(PivParams p) {
 // their non-zero samples, so a step is two broadcast reads (sample, its x) and four reads of b2 for four float64 FMAs. ------
 constexpr int AMB_R = 4;
 
-template <typename T, typename TB = T>
+template <typename T, typename TB = T, bool MASKED = false>
 __global__ __launch_bounds__(RBLOCK) void piv_rescue_amb_kernel(PivParams p) {
   extern __shared__ __attribute__((aligned(16))) double dsm[];
   __shared__ double red_v[RBLOCK / 64];
@@ -392,18 +464,31 @@ __global__ __launch_bounds__(RBLOCK) void piv_rescue_amb_kernel(PivParams p) {
     const bool g_ok = p.rescue_amb[i] < p.n_tiles;
     const T* A = window_base<T>(p, g);
     const TB* B = window_base_b<T, TB>(p, g, A);
-    double mean_a, sd_a, mean_b, sd_b;
-    pair_stats_wave<T, false, TB>(p, A, B, lane, mean_a, sd_a, mean_b, sd_b);   // every wave computes the same totals
-    const bool dead = sd_a == 0.0 || sd_b == 0.0;   // never listed; kept out of the control flow around the barriers below
-    const double sg = p.norm_clip ? (double)p.std_gain : -(double)p.std_gain;   // options "std_ddof" / "norm_clip"
-    const double inv_a = dead ? 1.0 : sg / sd_a, inv_b = dead ? 1.0 : sg / sd_b;
+    double mean_a, sd_a, mean_b, sd_b, inv_a, inv_b;
+    bool dead;   // never listed; kept out of the control flow around the barriers below
+    const uint8_t* M = nullptr;
+    if constexpr (MASKED) {   // the factors over the valid samples; masked windows are 16, 32 or 64 px: always the fast path
+      M = window_mask_base(p, g);
+      dead = !masked_factors_wave<T>(p, A, B, M, lane, mean_a, inv_a, mean_b, inv_b);
+      if (dead) { mean_a = mean_b = 0.0; inv_a = inv_b = 1.0; }
+    } else {
+      pair_stats_wave<T, false, TB>(p, A, B, lane, mean_a, sd_a, mean_b, sd_b);   // every wave computes the same totals
+      dead = sd_a == 0.0 || sd_b == 0.0;
+      const double sg = p.norm_clip ? (double)p.std_gain : -(double)p.std_gain;   // options "std_ddof" / "norm_clip"
+      inv_a = dead ? 1.0 : sg / sd_a; inv_b = dead ? 1.0 : sg / sd_b;
+    }
     double best = -1.0;
     int bi = 0x7fffffff;
     if (fast) {
       for (int e = threadIdx.x; e < n; e += RBLOCK) {
         const int y = e / wx, x = e - y * wx;
-        la[e] = a_inside(p, y, x) ? norm_clip((double)A[(int64_t)y * p.W + x], mean_a, inv_a) : 0.0;
-        const double bv = norm_clip((double)B[(int64_t)y * p.W + x], mean_b, inv_b);
+        double av = a_inside(p, y, x) ? norm_clip((double)A[(int64_t)y * p.W + x], mean_a, inv_a) : 0.0;
+        double bv = norm_clip((double)B[(int64_t)y * p.W + x], mean_b, inv_b);
+        if constexpr (MASKED) {   // excluded samples: selected to zero
+          const bool on = M[(int64_t)y * p.W + x] != 0;
+          av = on ? av : 0.0; bv = on ? bv : 0.0;
+        }
+        la[e] = av;
         lb2[y * pitch + x] = bv;
         lb2[y * pitch + wx + x] = bv;
       }
@@ -486,7 +571,8 @@ __global__ __launch_bounds__(RBLOCK) void piv_rescue_amb_kernel(PivParams p) {
     for (int k = 1; k < RBLOCK / 64; ++k) amax_merge_d(best, bi, red_v[k], red_i[k]);
     if (wave == 0 && !dead && g_ok && (fast || n <= RESCUE_GENERIC_MAX)) {
       const int ip = bi / wx, jp = bi - ip * wx;
-      fit_wave(p, A, B, p.W, mean_a, inv_a, mean_b, inv_b, g, ip, jp, lane);
+      if constexpr (MASKED) fit_wave<0, 0, true>(p, A, B, p.W, mean_a, inv_a, mean_b, inv_b, g, ip, jp, lane, M);
+      else fit_wave(p, A, B, p.W, mean_a, inv_a, mean_b, inv_b, g, ip, jp, lane);
     }
   }
 
@@ -715,6 +801,19 @@ hipError_t launch_fit_t(const PivParams& p, uint32_t blocks, hipStream_t s) {
 template <typename T, typename TB, int W> struct FitFixed { static constexpr bool ok = true; };
 template <> struct FitFixed<double, float, 32> { static constexpr bool ok = false; };   // 133 VGPRs against the generic kernel's 124
 
+// masked launches (p.mask): the generic fit kernel straight from the frames and the whole-plane kernel, both with the mask's window
+template <typename T>
+hipError_t launch_rescue_masked_t(const PivParams& p, uint32_t fit_blocks, uint32_t amb_blocks, size_t amb_lds, hipStream_t s) {
+  hipLaunchKernelGGL((piv_rescue_fit_kernel<T, T, 0, 0, true>), dim3(fit_blocks), dim3(RBLOCK), 0, s, p);
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return e;
+  e = hipFuncSetAttribute(reinterpret_cast<const void*>(&piv_rescue_amb_kernel<T, T, true>), hipFuncAttributeMaxDynamicSharedMemorySize,
+                          (int)(3 * RESCUE_LDS_SAMPLES * sizeof(double) + (RESCUE_LDS_SAMPLES + 512) * sizeof(int)));
+  if (e != hipSuccess) return e;
+  hipLaunchKernelGGL((piv_rescue_amb_kernel<T, T, true>), dim3(amb_blocks), dim3(RBLOCK), amb_lds, s, p);
+  return hipGetLastError();
+}
+
 template <typename T, typename TB = T>
 hipError_t launch_rescue_t(const PivParams& p, bool generic, hipStream_t s) {
   const int n = p.wy * p.wx;
@@ -723,6 +822,9 @@ hipError_t launch_rescue_t(const PivParams& p, bool generic, hipStream_t s) {
   // fixed grids (the record counts live on the device): empty blocks leave within microseconds
   const uint32_t fit_blocks = std::min<uint32_t>(4096u, std::max<uint32_t>(64u, p.n_tiles / 512u + 1u));
   const uint32_t amb_blocks = std::min<uint32_t>(1024u, std::max<uint32_t>(64u, p.n_tiles / 2048u + 1u));
+  if constexpr (std::is_same<T, TB>::value) {
+    if (p.mask) return (fast && !p.nw && !p.shift && !p.warped) ? launch_rescue_masked_t<T>(p, fit_blocks, amb_blocks, lds, s) : hipErrorInvalidValue;
+  }
   // the square windows of the walking / shifted / deformed families at compile-time size; a search area and every other size: run time
   const int fixed = (!generic && p.nw == 0 && p.wy == p.wx) ? p.wx : 0;
   constexpr int W16 = FitFixed<T, TB, 16>::ok ? 16 : 0, W32 = FitFixed<T, TB, 32>::ok ? 32 : 0, W64 = FitFixed<T, TB, 64>::ok ? 64 : 0;   // (0: the generic kernel)

@@ -72,6 +72,9 @@ def get_piv(frames, window_size=None, overlap=None, engine: str = "hip", ensembl
     (n x n at overlap n / 2) or a pair ``(n, overlap)``; the result stays on the grid of ``window_size`` / ``overlap``.
     ``deform_passes`` (in ``**kwargs``): 0 .. 4 window deformation passes after the chain, per-timestep mode only.
     ``spectral_filter`` (in ``**kwargs``): ``"spof"`` -- SPOF phase-filtered correlation, windows of 16, 32 or 64 px.
+    ``image_mask`` / ``mask_coverage_min`` (in ``**kwargs``): an ``(H, W)`` mask of the valid pixels, non-zero = valid, and the smallest
+    share of valid samples a window is evaluated at (default 0.25) -- every window is correlated over its valid samples only
+    (INTEGRATION.md 2h), windows of 16, 32 or 64 px, per-timestep mode.
     """
     if engine not in ENGINES:
         raise ValueError(f"Selected PIV engine {engine} does not exist.")

@@ -60,6 +60,11 @@ def piv_pairs(imgs, window_size=(32, 32), overlap=(16, 16), signal_threshold: Op
             raise NotImplementedError("spectral_filter together with a search_area_size larger than the window is not implemented")
         return piv_pairs_filtered(imgs, window_size, overlap, window_size.spectral_filter, signal_threshold, return_planes, pair_offset, out=out,
                                   scale=scale)
+    if isinstance(window_size, window.MaskedWindow):   # an image mask: the masked per-pair entry points
+        if search_area_size is not None and tuple(int(q) for q in search_area_size) != tuple(window_size):
+            raise NotImplementedError("image_mask together with a search_area_size larger than the window is not implemented")
+        return piv_pairs_masked(imgs, window_size, overlap, None, window_size.mask_coverage_min, signal_threshold, return_planes, pair_offset,
+                                out=out, scale=scale)
     window_size = window.search_spec(window_size, search_area_size)
     search = isinstance(window_size, window.SearchWindow)
     lib = _lib.load()
@@ -227,6 +232,68 @@ def piv_pairs_filtered(imgs, window_size=(32, 32), overlap=(16, 16), spectral_fi
         _lib.check(lib.lspiv_piv_spof_pairs_at(_lib.ptr(a), _lib.DTYPE_CODES[a.dtype], T, H, W, ws[0], ws[1], ov[0], ov[1],
                                                _sig(signal_threshold), int(pair_offset), _lib.ptr(res[0]), _lib.ptr(res[1]), _lib.ptr(res[2]),
                                                _lib.ptr(res[3]), _lib.ptr(planes) if planes is not None else None))
+        res = tuple(res)
+    if scale is not None:   # no fused scaling entry point for this mode: numpy's own arithmetic (ffpiv.py:418-419)
+        for k in range(2):
+            np.divide(res[k] * scale[k], dt[:, None, None], out=res[k], dtype=np.float64, casting="same_kind")
+    return (*res, planes) if return_planes else tuple(res)
+
+
+def piv_pairs_masked(imgs, window_size=(32, 32), overlap=(16, 16), image_mask=None, mask_coverage_min: float = 0.25,
+                     signal_threshold: Optional[float] = None, return_planes: bool = False, pair_offset: int = 0, out=None, scale=None):
+    """PIV of every consecutive frame pair of ``imgs`` under an image mask: :func:`piv_pairs` with every
+    window correlated over its VALID samples only -- mean, standard deviation, the signal score and the divisor of the plane are those of
+    the ``k`` samples where ``image_mask`` (``(H, W)``, bool / integer / float, non-zero = valid, one mask for every frame) is set;
+    excluded samples count as exactly zero and are never read into the arithmetic (NaN there is harmless).  A window with fewer than
+    ``max(2, ceil(mask_coverage_min * n * n))`` valid samples is NaN throughout.  Returns ``(u, v, corr_max, s2n[, planes])`` like
+    :func:`piv_pairs`.  ``window_size``: square, 16, 32 or 64 px, or a ``window.MaskedWindow`` (then ``image_mask`` stays None).
+    ``image_mask=None`` without one is :func:`piv_pairs`.  Pair-local, one window per job: every chunking gives the same bits
+    (``pair_offset`` is accepted for symmetry); the float64 rescue pass follows as on the other per-pair paths.  ``out`` / ``scale`` as in
+    :func:`piv_pairs` (the scaling is numpy's own arithmetic on the host).  Host stacks and ``DeviceFrames``."""
+    from .device import DeviceFrames
+
+    if image_mask is None and not isinstance(window_size, window.MaskedWindow):
+        window.coverage_spec(mask_coverage_min)
+        return piv_pairs(imgs, tuple(window_size), overlap, signal_threshold, return_planes, pair_offset, out=out, scale=scale)
+    a = imgs if is_device(imgs) else _lib.as_frames(imgs)
+    T, H, W = a.shape
+    spec = window.masked_spec(window_size, image_mask, mask_coverage_min, (H, W))   # ValueError: sizes, coverage, the mask's shape
+    ws = (int(spec[0]), int(spec[1]))
+    ov = (int(overlap[0]), int(overlap[1]))
+    lib = _lib.load()
+    _lib.require_device()
+    n_rows, n_cols = window.get_array_shape((H, W), ws, ov)
+    if T < 2 or n_rows < 1 or n_cols < 1:
+        raise ValueError(f"need >= 2 frames at least one window large, got {a.shape} for window {ws}")
+    P, n_win = T - 1, n_rows * n_cols
+    if out is not None:
+        out = _check_out(out, (P, n_rows, n_cols))
+    dt = None
+    if scale is not None:
+        if return_planes:
+            raise ValueError("scale and return_planes exclude each other")
+        dt = np.ascontiguousarray(scale[2], dtype=np.float64).reshape(-1)
+        if dt.shape != (P,):
+            raise ValueError(f"scale: dt must have one entry per frame pair ({P}), got shape {dt.shape}")
+    planes = None
+    if is_device(a):
+        d_mask = spec.device_mask()      # one upload per device for all chunks of the call that made `spec`
+        d_out = DeviceFrames.empty((4, P, n_win), np.float32)
+        d_planes = DeviceFrames.empty((P * n_win, ws[0], ws[1]), np.float32) if return_planes else None
+        _lib.check(lib.lspiv_piv_masked_pairs_dev_at(a.c_ptr, a.dtype_code, T, H, W, ws[0], ws[1], ov[0], ov[1], d_mask.c_ptr, spec.k_min,
+                                                     _sig(signal_threshold), int(pair_offset), d_out.c_ptr,
+                                                     d_planes.c_ptr if d_planes is not None else None, None))
+        res = _results_to_host(d_out, P, n_rows, n_cols, out)
+        if return_planes:
+            planes = d_planes.to_host().reshape(P, n_win, ws[0], ws[1])
+    else:
+        res = out if out is not None else [np.empty((P, n_rows, n_cols), dtype=np.float32) for _ in range(4)]
+        if return_planes:
+            planes = np.empty((P, n_win, ws[0], ws[1]), dtype=np.float32)
+        _lib.check(lib.lspiv_piv_masked_pairs_at(_lib.ptr(a), _lib.DTYPE_CODES[a.dtype], T, H, W, ws[0], ws[1], ov[0], ov[1],
+                                                 _lib.ptr(spec.image_mask), spec.k_min, _sig(signal_threshold), int(pair_offset),
+                                                 _lib.ptr(res[0]), _lib.ptr(res[1]), _lib.ptr(res[2]), _lib.ptr(res[3]),
+                                                 _lib.ptr(planes) if planes is not None else None))
         res = tuple(res)
     if scale is not None:   # no fused scaling entry point for this mode: numpy's own arithmetic (ffpiv.py:418-419)
         for k in range(2):
@@ -507,6 +574,9 @@ class Ensemble:
     """Device-resident ensemble-correlation accumulator (pyorc/velocimetry/ffpiv.py:182-376)."""
 
     def __init__(self, dim_size, window_size, overlap, sliding=None, shift=None, spectral_filter=None):
+        if isinstance(window_size, window.MaskedWindow):
+            raise NotImplementedError("image_mask together with ensemble_corr=True is not implemented: the ensemble kernels and their "
+                                      "float64 rescue have no masked form")
         """``sliding=(M, s)``: a sliding ensemble (INTEGRATION.md section 2c) -- outputs over windows of M pairs that advance by s
         pairs, read with :meth:`finish_sliding`; every ``accumulate`` but the last must then hold a multiple of s pairs.
         ``shift``: int16 ``(n_rows, n_cols, 2)`` = (dy, dx) per window, or a ``DeviceFrames`` holding those bytes -- a SHIFTED ensemble pass

@@ -128,6 +128,8 @@ def _wrap_get_piv(orig):
         deform = kwargs.pop("deform_passes", None)
         # ... and the phase-filtered correlation's `spectral_filter=`
         spectral = kwargs.pop("spectral_filter", None)
+        # ... and the image mask's `image_mask=` / `mask_coverage_min=`
+        masked = {k: kwargs.pop(k) for k in ("image_mask", "mask_coverage_min") if k in kwargs}
         engine, bound = kwargs.get("engine"), None
         if sig is not None and "engine" in sig.parameters:
             try:
@@ -146,6 +148,8 @@ def _wrap_get_piv(orig):
                 raise TypeError("deform_passes is a keyword of engine='hip' only")
             if spectral is not None:
                 raise TypeError("spectral_filter is a keyword of engine='hip' only")
+            if masked:
+                raise TypeError(f"{' / '.join(masked)} is a keyword of engine='hip' only")
             return orig(self, *args, **kwargs)
         # fail before any work if there is no MI355X / no library: the reference raises ValueError for an engine it cannot run
         from . import _lib
@@ -163,6 +167,12 @@ def _wrap_get_piv(orig):
 
             if window_mod.spectral_filter_spec(spectral) is not None:     # ValueError for an unknown name; "none" is today's path
                 extra["spectral_filter"] = spectral
+        if masked:
+            from . import window as window_mod
+
+            window_mod.coverage_spec(masked.get("mask_coverage_min", 0.25))     # ValueError outside (0, 1]
+            if masked.get("image_mask") is not None:                             # None is today's path
+                extra.update(masked)
         if search_area is not None or sliding or extra:
             # the reference's method body lays the grid out by the window; with a search area of its own the engine's mirror of that
             # body (pyorc_amd.frames.get_piv: same configuration copy, coordinates, attributes and encoding) runs instead -- and with the

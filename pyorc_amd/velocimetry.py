@@ -180,6 +180,8 @@ def get_ffpiv(
     coarse_passes=None,
     deform_passes=None,
     spectral_filter=None,
+    image_mask=None,
+    mask_coverage_min: float = 0.25,
 ):
     """Compute time-resolved (or ensemble) PIV on the MI355X; signature of pyorc's ``get_ffpiv`` (ffpiv.py:24-42).
 
@@ -226,12 +228,36 @@ def get_ffpiv(
     per-timestep and ensemble mode; ``corr`` / ``s2n`` are those of the filtered planes, so useful values of ``corr_min`` / ``s2n_min``
     are lower than for the plain ensemble.  Pair-local: ``chunksize=``, ``devices=``, host stacks, ``DeviceFrames`` and lazy stacks give
     the same bits.  No float64 rescue.  Not with ``coarse_passes``, ``deform_passes``, a search area or ``ensemble_window``.
+
+    ``image_mask`` (the project's own mode; None: today's path bit for bit): an ``(H, W)`` array of bool,
+    integer or float type, non-zero = valid, one static mask for every frame -- banks, piers, vegetation, the outside of the
+    orthoprojected area.  Every window is correlated over its valid samples only (mean, standard deviation, ``signal_threshold`` and the
+    divisor of the plane are those of the valid samples; excluded samples are never read into the arithmetic, NaN there is harmless); a
+    window with fewer than ``max(2, ceil(mask_coverage_min * n * n))`` valid samples is NaN.  ``mask_coverage_min`` lies in (0, 1].
+    Windows of 16, 32 or 64 px, per-timestep mode.  Pair-local: ``chunksize=``, ``devices=``, host stacks, ``DeviceFrames`` and lazy
+    stacks give the same bits; the mask goes to each device once per call.  Not with ``ensemble_corr=True``, ``coarse_passes``,
+    ``deform_passes``, a search area, ``spectral_filter`` or ``ensemble_window``.
     """
     if engine != "hip":
         raise ValueError(f"Selected PIV engine {engine} does not exist.")
     # a search area of its own: one window argument that answers for the search area wherever a grid, a plan or an alignment is asked for
     window_size = window.search_spec(window_size, search_area_size)
     flt = window.spectral_filter_spec(spectral_filter)     # ValueError for an unknown name
+    window.coverage_spec(mask_coverage_min)                # ValueError outside (0, 1]
+    if image_mask is not None:
+        if ensemble_window is not None:
+            raise NotImplementedError("image_mask together with ensemble_window is not implemented: a sliding ensemble has no masked form")
+        if ensemble_corr:
+            raise NotImplementedError("image_mask together with ensemble_corr=True is not implemented: the ensemble kernels and their "
+                                      "float64 rescue have no masked form")
+        if coarse_passes is not None and len(coarse_passes):
+            raise NotImplementedError("image_mask together with coarse_passes is not implemented: the shifted kernels have no masked form")
+        if window.deform_count(deform_passes):
+            raise NotImplementedError("image_mask together with deform_passes is not implemented: the deformation kernels have no masked form")
+        if flt is not None:
+            raise NotImplementedError("image_mask together with spectral_filter is not implemented: the filtered kernels have no masked form")
+        # (NotImplementedError with a search area, ValueError for another window, the coverage or the mask's shape)
+        window_size = window.masked_spec(window_size, image_mask, mask_coverage_min, tuple(frames[0].shape))
     if flt is not None:
         if coarse_passes is not None and len(coarse_passes):
             raise NotImplementedError("spectral_filter together with coarse_passes is not implemented: the shifted kernels have no filtered form")
@@ -285,10 +311,10 @@ def get_ffpiv(
     devs = _resolve_frames_devices(frames, devices)
     align = window.chunk_alignment(window_size, dim_size, overlap)
     stack_mode = _stack_signal_mode(signal_threshold)
-    # (a chain's later passes read every frame of a chunk at offsets of their own: a lazy stack takes the chunk-loading path; so does a
-    # filtered run, whose per-pair entry points take chunks)
+    # (a chain's later passes read every frame of a chunk at offsets of their own: a lazy stack takes the chunk-loading path; so do a
+    # filtered and a masked run, whose per-pair entry points take chunks)
     resident_run = (_is_lazy(frames) and n_frames >= 2 and not stack_mode and
-                    not isinstance(window_size, (window.MultiPassWindow, window.FilteredWindow)))
+                    not isinstance(window_size, (window.MultiPassWindow, window.FilteredWindow, window.MaskedWindow)))
     if resident_run:
         # a lazy stack: resident in HBM, loads planned against HOST memory and cut where dask cuts, launches on the anchors
         work = plan_lazy_devices(frames, n_frames, dim_size, window_size, overlap, n_win, chunksize, memory_factor, engine, prefetch, devs)
@@ -523,7 +549,7 @@ def _timestep_sink(n_pairs, n_workers, y, x, dt, res_x, res_y, window_size, over
     px = [None] * n_workers            # per worker: scratch for a launch's u, v in pixels
     # (the search-area, multi-pass and filtered entry points have no fused scaling: numpy's arithmetic on the host, the same bits)
     on_device = piv.device_scaling_is_numpys(res_x, res_y) and not isinstance(window_size, (window.SearchWindow, window.MultiPassWindow,
-                                                                                              window.FilteredWindow))
+                                                                                              window.FilteredWindow, window.MaskedWindow))
 
     def launch(k, frames, p0, p1):
         p = p1 - p0

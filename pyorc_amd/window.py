@@ -10,6 +10,8 @@ because that is what bounds a chunk on the ``hip`` engine.
 from __future__ import annotations
 
 import ctypes as C
+import math
+import threading
 from typing import Optional, Sequence, Tuple
 
 import numpy as np
@@ -212,6 +214,87 @@ def filtered_spec(window_size, spectral_filter=None):
     return FilteredWindow(spectral_filter_supported(window_size), flt)
 
 
+MASK_WINDOWS = (16, 32, 64)
+
+
+class MaskedWindow(tuple):
+    """A window correlated under an image mask, as ONE window argument of the layers below ``get_ffpiv`` /
+    ``piv_pairs``: the tuple itself is the window ``(wy, wx)`` -- grid and planes are the plain per-pair launch's --, ``.image_mask`` the
+    mask as contiguous uint8 ``(H, W)`` (non-zero = valid; converted once), ``.mask_coverage_min`` the smallest share of valid samples a
+    window is evaluated at, ``.k_min`` = ``max(2, ceil(mask_coverage_min * wy * wx))`` in float64.  The masked kernels are per-pair: the
+    chunk alignment is 1.  :meth:`device_mask` keeps one copy of the mask per device for the lifetime of this object -- one call."""
+
+    def __new__(cls, window_size, image_mask, mask_coverage_min: float = 0.25):
+        self = super().__new__(cls, (int(window_size[0]), int(window_size[1])))
+        m = np.asarray(image_mask)
+        if m.ndim != 2 or m.dtype.kind not in "buif":
+            raise ValueError(f"image_mask must be a 2-D array of bool, integer or float type, got shape {m.shape}, dtype {m.dtype}")
+        self.image_mask = np.ascontiguousarray(m != 0, dtype=np.uint8)
+        self.mask_coverage_min = coverage_spec(mask_coverage_min)
+        self.k_min = max(2, int(math.ceil(self.mask_coverage_min * float(self[0] * self[1]))))
+        self._device_masks = {}
+        self._lock = threading.Lock()
+        return self
+
+    def device_mask(self):
+        """The mask in HBM of the CURRENT device (a ``DeviceFrames`` of shape ``(1, H, W)``, uint8), uploaded on first use there."""
+        from .device import DeviceFrames, _Pool
+
+        dev = _Pool.device()
+        with self._lock:
+            d = self._device_masks.get(dev)
+            if d is None:
+                d = self._device_masks[dev] = DeviceFrames.from_host(self.image_mask[None])
+            return d
+
+
+def coverage_spec(value) -> float:
+    """``mask_coverage_min`` checked: a number in (0, 1], else a ValueError.  Host-only."""
+    try:
+        c = float(value)
+    except (TypeError, ValueError):
+        raise ValueError(f"mask_coverage_min must be a number in (0, 1], got {value!r}") from None
+    if not 0.0 < c <= 1.0:
+        raise ValueError(f"mask_coverage_min must lie in (0, 1], got {value!r}")
+    return c
+
+
+def mask_supported(window_size) -> Tuple[int, int]:
+    """``window_size`` as a pair of ints when the masked kernels serve it (``lspiv_mask_supported``: square, 16, 32 or 64), else a
+    ValueError naming the sizes.  Host-only."""
+    ws = 2 * (window_size,) if isinstance(window_size, (int, np.integer)) else tuple(window_size)
+    if len(ws) != 2 or not _lib.load().lspiv_mask_supported(int(ws[0]), int(ws[1])):
+        raise ValueError(f"window_size {window_size!r} is not supported with image_mask: the window must be square and one of {MASK_WINDOWS}")
+    return int(ws[0]), int(ws[1])
+
+
+def masked_spec(window_size, image_mask=None, mask_coverage_min: float = 0.25, dim_size=None):
+    """``window_size`` as the layers below take it: unchanged without a mask (None: today's path), else a validated
+    :class:`MaskedWindow`.  ``dim_size``: the frames' ``(H, W)``, which the mask must have (ValueError).  Not together with a search area,
+    a multi-pass chain, deformation passes or a spectral filter (NotImplementedError naming both keywords)."""
+    if isinstance(window_size, MaskedWindow):
+        if image_mask is not None:
+            raise ValueError("image_mask given twice: window_size is a MaskedWindow already")
+        spec = window_size
+    elif image_mask is None:
+        coverage_spec(mask_coverage_min)
+        return window_size
+    else:
+        if isinstance(window_size, SearchWindow):
+            raise NotImplementedError("image_mask together with a search_area_size larger than the window is not implemented: the masked "
+                                      "kernels correlate two windows of one size under one mask")
+        if isinstance(window_size, MultiPassWindow):
+            raise NotImplementedError(("image_mask together with deform_passes" if window_size.deform and len(window_size.passes) == 1
+                                       else "image_mask together with coarse_passes") + " is not implemented: the shifted and the "
+                                      "deformation kernels have no masked form")
+        if isinstance(window_size, FilteredWindow):
+            raise NotImplementedError("image_mask together with spectral_filter is not implemented: the filtered kernels have no masked form")
+        spec = MaskedWindow(mask_supported(window_size), image_mask, mask_coverage_min)
+    if dim_size is not None and spec.image_mask.shape != (int(dim_size[0]), int(dim_size[1])):
+        raise ValueError(f"image_mask has shape {spec.image_mask.shape}, the frames are {(int(dim_size[0]), int(dim_size[1]))}")
+    return spec
+
+
 MIN_STEERING_GRID = 3
 
 
@@ -273,7 +356,7 @@ def required_memory(n_frames: int, dim_size, window_size, overlap, search_area_s
     that needs most, in a chain (the multi-pass ensemble, INTEGRATION.md section 2e, runs one pass at a time).
     ``deform_passes`` (or a :class:`MultiPassWindow` that carries them): the warped frames of one batch of pairs and the nodes
     (:func:`deform_bytes`) come on top.  A :class:`FilteredWindow` answers as the plain per-pair launch of its window: the filtered
-    kernels have no workspace.
+    kernels have no workspace.  A :class:`MaskedWindow` answers as the plain per-pair launch of its window plus the bytes of the mask.
     """
     if coarse_passes or deform_count(deform_passes) or isinstance(window_size, MultiPassWindow):
         # a chain: the frames once, the largest pass's launch (results, rescue lists, the planes of the final pass), and the
@@ -293,6 +376,8 @@ def required_memory(n_frames: int, dim_size, window_size, overlap, search_area_s
     r = _lib.load().lspiv_required_bytes(n_frames, dim_size[0], dim_size[1], code, sa[0], sa[1],
                                          overlap[0], overlap[1], int(with_planes))
     need = _lib.check(r)
+    if isinstance(window_size, MaskedWindow):
+        need += int(window_size.image_mask.nbytes)
     if sliding_blocks:
         need += sliding_store_bytes(sliding_blocks, dim_size, sa, overlap)
     if ensemble_sums:
@@ -385,8 +470,8 @@ def chunk_alignment(window_size, dim_size=None, overlap=None) -> int:
     that shape are cut.  Without them the alignment that is right on EVERY grid comes back (``lspiv_chunk_alignment``, ABI 5: the
     longest anchor length of the window family, a multiple of every grid's -- 75 where ABI 4 answered 25)."""
     lib = _lib.load()
-    if isinstance(window_size, (SearchWindow, FilteredWindow)):
-        return 1   # the search-area and the filtered kernels are per-pair: any chunking gives the same bits
+    if isinstance(window_size, (SearchWindow, FilteredWindow, MaskedWindow)):
+        return 1   # the search-area, the filtered and the masked kernels are per-pair: any chunking gives the same bits
     if isinstance(window_size, MultiPassWindow):
         # pass 0 is the per-timestep path on ITS window and grid; every later pass is pair-local
         n0, o0 = window_size.passes[0]

@@ -1,0 +1,222 @@
+"""Float64 numpy reference of PIV under an image mask: one plane and the per-pair result, composed of the
+oracle's own pieces (``normalize_intensity``, ``_count_signal``, ``sliding_window_stack``, ``u_v_displacement``), all left as they are.
+The valid samples of a window are handed to ``normalize_intensity`` as one row of k samples -- its mean, its standard deviation
+("std_ddof"), its division and its clip are then those of the valid samples alone -- and scattered back into a window of zeros: an
+excluded sample is never read.  Like the rest of the PIV path it is this project's reading: unpinned against a real ffpiv.  Kernel
+orientation throughout (u column shift, v row shift, rows downward); SEMANTICS["v_sign"] is applied once, by ``u_v_displacement``.
+
+Also the inputs tests/test_masked_host.py and tests/test_gpu_masked.py share, computed once per process."""
+import functools
+import math
+import warnings
+
+import numpy as np
+
+from oracle import piv_oracle as po
+from pyorc_amd import synth
+from tests import deform_ref, multipass_ref, spof_ref
+
+MASK_WINDOWS = (16, 32, 64)
+COVERAGE_MIN = 0.25
+
+
+def k_min(n, coverage_min=COVERAGE_MIN):
+    return max(2, int(math.ceil(float(coverage_min) * float(n * n))))
+
+
+def normalize(win, M):
+    """a^ of ONE window (N, N) under M (N, N) bool: normalize_intensity of the valid samples, exactly 0 on excluded ones."""
+    out = np.zeros(win.shape, dtype=np.float64)
+    out[M] = po.normalize_intensity(np.asarray(win, dtype=np.float64)[M].reshape(1, -1)).reshape(-1)
+    return out
+
+
+def plane(A, B, M, k):
+    """The plane of ONE window pair (N, N) under M with k = M.sum(): clip(fftshift(irfft2(conj(rfft2 a^) rfft2 b^)) / k, 0, 1)."""
+    n = A.shape[-1]
+    a, b = normalize(A, M), normalize(B, M)
+    c = np.fft.irfft2(np.conj(np.fft.rfft2(a)) * np.fft.rfft2(b), s=(n, n))
+    c = np.fft.fftshift(c, axes=(-2, -1)) / float(k)
+    return np.clip(c, 0.0, 1.0)
+
+
+def window_masks(mask, n, overlap):
+    """(M (n_win, n, n) bool, k (n_win,) int) of the window grid."""
+    M = po.sliding_window_stack((np.asarray(mask) != 0)[None], (n, n), (overlap, overlap))[0]
+    return M, M.sum(axis=(-2, -1))
+
+
+def piv(imgs, n, overlap, mask, coverage_min=COVERAGE_MIN, signal_threshold=None):
+    """The per-pair result under ``mask`` (H, W): dict(u, v, corr, s2n (T-1, rows, cols), planes (T-1, n_win, n, n), k (n_win,), tie,
+    fragile (T-1, rows, cols)).  A window below k_min, a pair failing the signal threshold -- the share of signal samples among the valid
+    ones, of A and of B -- or one with a non-finite VALID sample is NaN throughout.  tie: the top two samples of the plane are equal
+    within 1e-12 relative; fragile: spof_ref.fragile_mask."""
+    imgs = np.asarray(imgs)
+    if n not in MASK_WINDOWS:
+        raise ValueError(f"window {n} not in {MASK_WINDOWS}")
+    if po.SEMANTICS["signal_mode"] == 1 or not po.SEMANTICS["norm_clip"]:
+        raise NotImplementedError("masked correlation: signal_mode = 1 and norm_clip = 0 are not supported")
+    T = imgs.shape[0]
+    rows, cols = po.get_axis_shape(imgs.shape[1], n, overlap), po.get_axis_shape(imgs.shape[2], n, overlap)
+    with np.errstate(invalid="ignore"):
+        stack = po.sliding_window_stack(imgs.astype(np.float64), (n, n), (overlap, overlap))      # (T, n_win, n, n)
+    M, k = window_masks(mask, n, overlap)
+    kmin = k_min(n, coverage_min)
+    planes = np.full((T - 1,) + stack.shape[1:], np.nan)
+    with np.errstate(all="ignore"):
+        for w in range(stack.shape[1]):
+            if k[w] < kmin:
+                continue
+            for t in range(T - 1):
+                va, vb = stack[t, w][M[w]], stack[t + 1, w][M[w]]
+                if not (np.isfinite(va).all() and np.isfinite(vb).all()):
+                    continue
+                if signal_threshold is not None:
+                    fa = po._count_signal(va.reshape(1, -1)) / k[w]
+                    fb = po._count_signal(vb.reshape(1, -1)) / k[w]
+                    if not (fa >= signal_threshold and fb >= signal_threshold):
+                        continue
+                planes[t, w] = plane(stack[t, w], stack[t + 1, w], M[w], k[w])
+    u, v = po.u_v_displacement(planes, rows, cols)
+    shape = (T - 1, rows, cols)
+    with np.errstate(all="ignore"), warnings.catch_warnings():
+        warnings.simplefilter("ignore", RuntimeWarning)
+        cm = planes.max(axis=(-2, -1))
+        s2n = cm / planes.mean(axis=(-2, -1))
+        top = np.sort(planes.reshape(T - 1, stack.shape[1], -1), axis=-1)[..., -2:]
+        tie = np.isfinite(cm) & (cm > 0) & (top[..., 1] - top[..., 0] <= 1e-12 * top[..., 1])
+    return dict(u=u, v=v, corr=cm.reshape(shape), s2n=s2n.reshape(shape), planes=planes, k=k, tie=tie.reshape(shape),
+                fragile=spof_ref.fragile_mask(planes).reshape(shape))
+
+
+def classes(k, n, coverage_min=COVERAGE_MIN):
+    """(full, partial, below) window counts of a grid's k."""
+    kmin = k_min(n, coverage_min)
+    return int((k == n * n).sum()), int(((k >= kmin) & (k < n * n)).sum()), int((k < kmin).sum())
+
+
+# ---- the shared inputs ---------------------------------------------------------------------------------------------------------------
+def parity_mask(H, W):
+    """Valid right of a wavy line, minus a disc: windows of every class (full, partial, below k_min) on the parity grids."""
+    y, x = np.mgrid[0:H, 0:W].astype(np.float64)
+    m = x >= 0.30 * W + 0.10 * W * np.sin(2 * np.pi * y / (0.61 * H)) + 0.03 * W * np.sin(2 * np.pi * y / (0.14 * H))
+    m &= np.hypot(y - 0.55 * H, x - 0.72 * W) > 0.09 * min(H, W)
+    return m
+
+
+TRUTH = (3.3, -2.4)
+BANK_DIM = (160, 200)
+BANK_INPUTS = ((5, 0.03), (5, 0.015), (6, 0.03), (6, 0.015))
+BANK_WINDOWS = ((32, 16), (64, 32))
+
+
+@functools.lru_cache(maxsize=None)
+def bank_mask():
+    H, W = BANK_DIM
+    y, x = np.mgrid[0:H, 0:W].astype(np.float64)
+    return x >= 70 + 18 * np.sin(2 * np.pi * y / 97) + 6 * np.sin(2 * np.pi * y / 23)
+
+
+@functools.lru_cache(maxsize=None)
+def bank_scene(seed, density):
+    """Tracers moving by TRUTH right of a wavy bank line, a static texture left of it (the bank); 4 frames, uint8."""
+    H, W = BANK_DIM
+    base = synth.particle_stack(4, H, W, seed=seed, density=density, uniform_shift=TRUTH).astype(np.float64)
+    kk = np.hypot(np.fft.fftfreq(H)[:, None], np.fft.fftfreq(W)[None, :])       # the texture of spof_ref.textured_stack
+    tex = np.fft.ifft2(np.fft.fft2(np.random.default_rng(1).normal(size=(H, W))) * np.exp(-(kk / 0.12) ** 2)).real
+    tex /= tex.std()
+    a = np.where(bank_mask()[None], 0.8 * base, (90 * (1 + 0.5 * tex))[None])
+    return np.clip(np.rint(a), 0, 255).astype(np.uint8)
+
+
+def share_within(u, v, sel):
+    """Share of the selected windows (a boolean of the results' shape) within 0.5 px of TRUTH; NaN counts as a miss."""
+    with np.errstate(invalid="ignore"):
+        ok = np.hypot(np.asarray(u, np.float64) - TRUTH[0], np.asarray(v, np.float64) - TRUTH[1]) <= 0.5
+    return float(ok[sel].mean())
+
+
+def partial_select(k, n, shape, lo=COVERAGE_MIN, hi=1.0):
+    """Windows with coverage in [lo, hi), broadcast over the pairs."""
+    cov = k / float(n * n)
+    return np.broadcast_to(((cov >= lo) & (cov < hi)).reshape(shape[1:]), shape)
+
+
+@functools.lru_cache(maxsize=None)
+def bank_ref(seed, density, n, overlap, masked=True):
+    a = bank_scene(seed, density)
+    if masked:
+        return piv(a, n, overlap, bank_mask())
+    r = spof_ref.piv(a, n, overlap, fn=spof_ref.ncc_plane)
+    r["k"] = window_masks(bank_mask(), n, overlap)[1]
+    return r
+
+
+PASS_CASES = deform_ref.PASS_CASES
+PASS_DTYPES = deform_ref.PASS_DTYPES
+SIGNAL_THR = deform_ref.SIGNAL_THR
+RESCUE_GEOMETRIES = multipass_ref.RESCUE_GEOMETRIES
+
+
+def case_mask(case):
+    return parity_mask(*PASS_CASES[case][2])
+
+
+@functools.lru_cache(maxsize=None)
+def pass_ref(case, dtype=np.uint8):
+    n, ov, _ = PASS_CASES[case]
+    return piv(deform_ref.pass_stack(case, dtype), n, ov, case_mask(case))
+
+
+@functools.lru_cache(maxsize=None)
+def signal_ref(case):
+    n, ov, _ = PASS_CASES[case]
+    return piv(deform_ref.signal_stack(case), n, ov, case_mask(case), signal_threshold=SIGNAL_THR)
+
+
+@functools.lru_cache(maxsize=None)
+def rescue_mask():
+    return parity_mask(*multipass_ref.RESCUE_DIM)
+
+
+@functools.lru_cache(maxsize=None)
+def rescue_ref(n, overlap, dtype=np.uint8):
+    return piv(multipass_ref.rescue_stack(dtype), n, overlap, rescue_mask())
+
+
+@functools.lru_cache(maxsize=None)
+def amb_stack(case):
+    """Two float32 frames for the whole-plane branch of the rescue pass: faint continuous noise, one bright sample in frame 0 inside a
+    partially covered window of the parity grid, and in frame 1 three bright samples of nearly equal value (2e-4 apart) at three lags of
+    it, all on valid pixels -- the planes of the windows that hold them have three samples within 1e-3 of their maximum, 1.4e-4 or more
+    apart (tests/test_masked_host.py counts them), which "rescue_tau" at its widest lists for re-evaluation of the whole plane."""
+    n, ov, (H, W) = PASS_CASES[case]
+    m = case_mask(case)
+    _, k = window_masks(m, n, ov)
+    y0, x0 = (np.asarray(q) for q in po.window_origins((H, W), (n, n), (ov, ov)))
+    a = 0.2 * np.random.default_rng(100 + n).random((2, H, W))
+    for w in np.flatnonzero((k >= k_min(n)) & (k < n * n)):
+        wr, wc = divmod(int(w), len(x0))
+        box = m[y0[wr] + 3:y0[wr] + n - 3, x0[wc] + 3:x0[wc] + n - 3]
+        ys, xs = np.nonzero(box[2:-2, 2:-2] & box[3:-1, 4:] & box[:-4, 3:-1] & box[4:, :-4])
+        if len(ys):
+            P = (y0[wr] + 5 + ys[len(ys) // 2], x0[wc] + 5 + xs[len(ys) // 2])
+            break
+    a[0, P[0], P[1]] = 250
+    for (dy, dx), val in (((1, 2), 250.05), ((-2, 1), 250.0), ((2, -2), 249.95)):
+        assert m[P[0] + dy, P[1] + dx]
+        a[1, P[0] + dy, P[1] + dx] = val
+    return a.astype(np.float32)
+
+
+@functools.lru_cache(maxsize=None)
+def amb_ref(case):
+    n, ov, _ = PASS_CASES[case]
+    return piv(amb_stack(case), n, ov, case_mask(case))
+
+
+def near_maximum(planes, tol):
+    """Per plane (P * n_win,): how many samples lie within ``tol`` (relative) of the maximum; 0 for a NaN or an all-zero plane."""
+    pl = np.nan_to_num(planes.reshape(planes.shape[0] * planes.shape[1], -1))
+    mx = pl.max(axis=1, keepdims=True)
+    return np.where(mx[:, 0] > 0, (pl >= mx * (1 - tol)).sum(axis=1), 0)
