@@ -226,14 +226,23 @@ int fill_params(lspiv::PivParams* p, const void* d_frames, int dtype, int64_t T,
 int dispatch(const lspiv::PivParams& p0, int dtype, bool ensemble, hipStream_t s, int filter = 0);
 int apply_v_sign(float* d_v, int64_t n, hipStream_t s);
 int apply_signal_mode(DeviceCtx* c, lspiv::PivParams* p, int dtype, hipStream_t s);
-// shifted passes (multi-pass PIV, multi-pass ensemble): the window is 16, 32 or 64 px square, the frame fits the int16 offsets, and the
-// options norm_clip = 0 / signal_mode = 1 are refused (LSPIV_EUNSUPPORTED)
+// what the families with kernels of a fixed size compose their checks from (LSPIV_EUNSUPPORTED / LSPIV_EINVAL, `what` names the
+// family in the message): the window is 16, 32 or 64 px square; the frame's sides fit an int16 (`what`: what has to hold them); the
+// options norm_clip = 0 and -- unless the family scores window positions like the plain kernels -- signal_mode = 1 are refused
+int check_fixed_square(int wy, int wx, const char* what);
+int check_frame_fits_int16(int64_t H, int64_t W, const char* what);
+int check_pair_options(const char* what, bool position_signal_ok = false);
+// shifted passes (multi-pass PIV, multi-pass ensemble) and SPOF-filtered correlation: the three of them
 int check_shift(int wy, int wx, int64_t H, int64_t W);
-int check_multipass_options();
-// SPOF-filtered correlation: the same windows, the same two options refused (LSPIV_EUNSUPPORTED)
+inline int check_multipass_options() { return check_pair_options("multi-pass PIV"); }
 int check_spof(int wy, int wx);
+// the kernel families, numbered as lspiv_kernel_kind reports them (include/lspiv.h)
+enum KernelKind : int {
+  kKindFft32 = 1, kKindFft64 = 2, kKindDirect = 3, kKindEmbed32 = 4, kKindEmbed64 = 5, kKindFft8or16 = 6, kKindEmbed16 = 7, kKindPfa = 8,
+  kKindDft = 9, kKindDftGlobal = 10
+};
 // window kinds served by the time-walking kernels (every even square window 6 .. 64)
-inline bool kind_walks(int kind) { return kind == 1 || kind == 2 || kind == 6 || kind == 8; }
+inline bool kind_walks(int kind) { return kind == kKindFft32 || kind == kKindFft64 || kind == kKindFft8or16 || kind == kKindPfa; }
 // the anchor length the walking kernels use on a grid of n_win windows (common.h, walk_anchor)
 int chunk_alignment_for(int wy, int wx, int64_t n_win);
 

@@ -32,19 +32,27 @@ int make_grid(int64_t H, int64_t W, int wy, int wx, int oy, int ox, Grid* g) {
   return LSPIV_OK;
 }
 
-// the rescue lists of stream `s`, large enough for a launch of n_tiles windows (a quarter of them "fit", a sixteenth "amb":
-// beyond that the excess keeps its float32 result -- imagery THAT sparse has no usable peaks)
+// the rescue lists of a launch of n_tiles windows: a quarter of them "fit" (16 bytes each), a sixteenth "amb" (4 bytes each) -- beyond that
+// the excess keeps its float32 result: imagery THAT sparse has no usable peaks -- behind a header slot
+struct RescueCaps {
+  size_t fit, amb;
+  static constexpr size_t hdr_bytes = 256;   // sizeof(RescueHdr) rounded up, keeps the lists 256-byte aligned
+  size_t bytes() const { return hdr_bytes + fit * sizeof(uint4) + amb * sizeof(uint32_t); }
+};
+static_assert(sizeof(lspiv::RescueHdr) <= RescueCaps::hdr_bytes, "header slot too small");
+static RescueCaps rescue_caps(int64_t n_tiles) { return {(size_t)std::max<int64_t>(4096, n_tiles / 4), (size_t)std::max<int64_t>(1024, n_tiles / 16)}; }
+
+// the rescue lists of stream `s`, large enough for a launch of n_tiles windows
 int rescue_ws(DeviceCtx* c, hipStream_t s, uint32_t n_tiles, lspiv::PivParams* p) {
   std::lock_guard<std::mutex> lk(locks_here().lists);
   DeviceCtx::RescueWs* ws = nullptr;
   for (auto& w : c->rescue) if (w.stream == s) ws = &w;
   if (!ws) { c->rescue.push_back({s, nullptr, 0, 0, 0}); ws = &c->rescue.back(); }
-  const uint32_t cap_fit = std::max<uint32_t>(4096u, n_tiles / 4u), cap_amb = std::max<uint32_t>(1024u, n_tiles / 16u);
-  const size_t hdr_bytes = 256;   // sizeof(RescueHdr) rounded up, keeps the lists 256-byte aligned
-  static_assert(sizeof(lspiv::RescueHdr) <= 256, "header slot too small");
-  if (cap_fit > ws->cap_fit || cap_amb > ws->cap_amb || !ws->base) {
-    const uint32_t nf = std::max(cap_fit, ws->cap_fit), na = std::max(cap_amb, ws->cap_amb);
-    const size_t bytes = hdr_bytes + (size_t)nf * sizeof(uint4) + (size_t)na * sizeof(uint32_t);
+  const RescueCaps need = rescue_caps(n_tiles);
+  const size_t hdr_bytes = RescueCaps::hdr_bytes;
+  if (need.fit > ws->cap_fit || need.amb > ws->cap_amb || !ws->base) {
+    const RescueCaps grow = {std::max<size_t>(need.fit, ws->cap_fit), std::max<size_t>(need.amb, ws->cap_amb)};
+    const size_t bytes = grow.bytes();
     void* grown = nullptr;
     HIP_TRY(hipMalloc(&grown, bytes));
     if (ws->base) {
@@ -58,7 +66,7 @@ int rescue_ws(DeviceCtx* c, hipStream_t s, uint32_t n_tiles, lspiv::PivParams* p
       HIP_TRY(hipMemsetAsync(grown, 0, hdr_bytes, s));   // ordered before the kernels of this stream
     }
     ws->base = grown;
-    ws->cap_bytes = bytes; ws->cap_fit = nf; ws->cap_amb = na;
+    ws->cap_bytes = bytes; ws->cap_fit = (uint32_t)grow.fit; ws->cap_amb = (uint32_t)grow.amb;
   }
   p->rescue_hdr = static_cast<lspiv::RescueHdr*>(ws->base);
   p->rescue_fit = reinterpret_cast<uint4*>((char*)ws->base + hdr_bytes);
@@ -106,6 +114,16 @@ int fill_params(lspiv::PivParams* p, const void* d_frames, int dtype, int64_t T,
   return LSPIV_OK;
 }
 
+// where a launch writes: tiles [t0, t0 + p->n_tiles) of a result block [u | v | corr_max | s2n] laid out for `total` tiles, and those
+// tiles' planes (plane_elems floats each) of `planes`, if there are any
+static void set_results(lspiv::PivParams* p, float* block, size_t total, size_t t0, float* planes, size_t plane_elems) {
+  p->u = block + t0;
+  p->v = block + total + t0;
+  p->cmax = block + 2 * total + t0;
+  p->s2n = block + 3 * total + t0;
+  p->planes = planes ? planes + t0 * plane_elems : nullptr;
+}
+
 // search-area mode: an even square window wy = wx = n, 4 <= n <= S - 2, of frame t inside a square search area S = say = sax of
 // frame t+1, S in {16, 32, 64}
 static bool search_shape_ok(int say, int sax, int wy, int wx) {
@@ -115,9 +133,7 @@ static int check_search(int say, int sax, int wy, int wx) {
   if (!search_shape_ok(say, sax, wy, wx))
     return fail(LSPIV_EUNSUPPORTED, "search area %dx%d with window %dx%d is not supported: the search area must be square, 16, 32 or 64, "
                 "and the window square and even with 4 <= window <= search area - 2", say, sax, wy, wx);
-  if (!g_opt_norm_clip.load())
-    return fail(LSPIV_EUNSUPPORTED, "option norm_clip = 0 is served by the block-per-window kernels only, not with a search area");
-  return LSPIV_OK;
+  return check_pair_options("a search area", true);   // (signal_mode = 1 scores the positions of the search areas)
 }
 // p filled for the search area (fill_params with wy = wx = S) -> window n inside it
 static void set_search_window(lspiv::PivParams* p, int n) {
@@ -179,45 +195,46 @@ int apply_v_sign(float* d_v, int64_t n, hipStream_t s) {
   return launch_status(lspiv::launch_negate(d_v, n, s));
 }
 
+// the families with one kernel per window size 16, 32, 64 (the entry points' checks admit no other)
+using Launcher = hipError_t (*)(const lspiv::PivParams&, int, hipStream_t);
+static int by_size(const Launcher (&l)[3], const lspiv::PivParams& p, int dtype, hipStream_t s) {
+  return launch_status(l[p.wy == 16 ? 0 : p.wy == 32 ? 1 : 2](p, dtype, s));
+}
+static const Launcher kMasked[3] = {lspiv::launch_piv_masked16, lspiv::launch_piv_masked32, lspiv::launch_piv_masked64};
+static const Launcher kSpof[3] = {lspiv::launch_piv_spof16, lspiv::launch_piv_spof32, lspiv::launch_piv_spof64};
+static const Launcher kSpofEnsemble[3] = {lspiv::launch_piv_spof_ensemble16, lspiv::launch_piv_spof_ensemble32, lspiv::launch_piv_spof_ensemble64};
+static const Launcher kDeform[3] = {lspiv::launch_piv_deform16, lspiv::launch_piv_deform32, lspiv::launch_piv_deform64};
+static const Launcher kShift[3] = {lspiv::launch_piv_shift16, lspiv::launch_piv_shift32, lspiv::launch_piv_shift64};
+static const Launcher kShiftEnsemble[3] = {lspiv::launch_piv_shift_ensemble16, lspiv::launch_piv_shift_ensemble32, lspiv::launch_piv_shift_ensemble64};
+static const Launcher kSearch[3] = {lspiv::launch_piv_search16, lspiv::launch_piv_search32, lspiv::launch_piv_search64};
+
 static int dispatch_kernels(const lspiv::PivParams& p, int dtype, bool ensemble, hipStream_t s, int filter) {
   if (p.mask) {   // image mask: the one-window-per-job kernels of piv_masked_impl.h, per pair (the rescue pass after them reads p.mask too)
     if (ensemble || filter) return fail(LSPIV_EUNSUPPORTED, "an image mask has per-pair NCC kernels only");
-    return launch_status(p.wy == 16 ? lspiv::launch_piv_masked16(p, dtype, s) : p.wy == 32 ? lspiv::launch_piv_masked32(p, dtype, s)
-                                                                                            : lspiv::launch_piv_masked64(p, dtype, s));
+    return by_size(kMasked, p, dtype, s);
   }
   if (filter) {   // SPOF phase-filtered correlation: the one-window-per-job kernels of piv_spof_impl.h, per pair or summed by one owner per window
     if (filter != LSPIV_FILTER_SPOF) return fail(LSPIV_EINVAL, "spectral filter %d not in {0: none, 1: SPOF}", filter);
-    if (ensemble)
-      return launch_status(p.wy == 16 ? lspiv::launch_piv_spof_ensemble16(p, dtype, s) : p.wy == 32 ? lspiv::launch_piv_spof_ensemble32(p, dtype, s)
-                                                                                                     : lspiv::launch_piv_spof_ensemble64(p, dtype, s));
-    return launch_status(p.wy == 16 ? lspiv::launch_piv_spof16(p, dtype, s) : p.wy == 32 ? lspiv::launch_piv_spof32(p, dtype, s)
-                                                                                          : lspiv::launch_piv_spof64(p, dtype, s));
+    return by_size(ensemble ? kSpofEnsemble : kSpof, p, dtype, s);
   }
   if (p.warped) {   // window deformation pass: the mixed-type per-pair kernels
     if (ensemble) return fail(LSPIV_EUNSUPPORTED, "ensemble mode has no deformation kernels");
-    return launch_status(p.wy == 16 ? lspiv::launch_piv_deform16(p, dtype, s) : p.wy == 32 ? lspiv::launch_piv_deform32(p, dtype, s)
-                                                                                            : lspiv::launch_piv_deform64(p, dtype, s));
+    return by_size(kDeform, p, dtype, s);
   }
-  if (p.shifted) {   // multi-pass mode: the shifted per-pair kernels
-    if (ensemble)   // multi-pass ensemble: one owner per window sums the shifted planes over the chunk's pairs
-      return launch_status(p.wy == 16 ? lspiv::launch_piv_shift_ensemble16(p, dtype, s) : p.wy == 32 ? lspiv::launch_piv_shift_ensemble32(p, dtype, s)
-                                                                                                      : lspiv::launch_piv_shift_ensemble64(p, dtype, s));
-    return launch_status(p.wy == 16 ? lspiv::launch_piv_shift16(p, dtype, s) : p.wy == 32 ? lspiv::launch_piv_shift32(p, dtype, s)
-                                                                                           : lspiv::launch_piv_shift64(p, dtype, s));
-  }
+  if (p.shifted)   // multi-pass mode: the shifted per-pair kernels; multi-pass ensemble: one owner per window sums the shifted planes over the chunk's pairs
+    return by_size(ensemble ? kShiftEnsemble : kShift, p, dtype, s);
   if (p.nw) {   // search-area mode: per-pair kernels of the search area's transform size
     if (ensemble) return fail(LSPIV_EUNSUPPORTED, "ensemble mode has no search-area kernels");
-    return launch_status(p.wy == 16 ? lspiv::launch_piv_search16(p, dtype, s) : p.wy == 32 ? lspiv::launch_piv_search32(p, dtype, s)
-                                                                                            : lspiv::launch_piv_search64(p, dtype, s));
+    return by_size(kSearch, p, dtype, s);
   }
   const int kind = lspiv_kernel_kind(p.wy, p.wx);
   hipError_t e;
   switch (kind) {
-    case 7: e = lspiv::launch_piv_embed16(p, dtype, ensemble, s); break;
-    case 4: e = lspiv::launch_piv_embed32(p, dtype, ensemble, s); break;
-    case 5: e = lspiv::launch_piv_embed64(p, dtype, ensemble, s); break;
-    case 6: e = p.wy == 8 ? lspiv::launch_piv_fft8(p, dtype, ensemble, s) : lspiv::launch_piv_fft16(p, dtype, ensemble, s); break;
-    case 8:
+    case kKindEmbed16: e = lspiv::launch_piv_embed16(p, dtype, ensemble, s); break;
+    case kKindEmbed32: e = lspiv::launch_piv_embed32(p, dtype, ensemble, s); break;
+    case kKindEmbed64: e = lspiv::launch_piv_embed64(p, dtype, ensemble, s); break;
+    case kKindFft8or16: e = p.wy == 8 ? lspiv::launch_piv_fft8(p, dtype, ensemble, s) : lspiv::launch_piv_fft16(p, dtype, ensemble, s); break;
+    case kKindPfa:
       switch (p.wy) {
 #define LSPIV_PFA_CASE(n) case n: e = lspiv::launch_piv_fft##n(p, dtype, ensemble, s); break;
         LSPIV_PFA_SIZES(LSPIV_PFA_CASE)
@@ -225,11 +242,11 @@ static int dispatch_kernels(const lspiv::PivParams& p, int dtype, bool ensemble,
         default: return fail(LSPIV_EUNSUPPORTED, "no prime-factor kernel for window %d", p.wy);
       }
       break;
-    case 1: e = lspiv::launch_piv_fft32(p, dtype, ensemble, s); break;
-    case 2: e = lspiv::launch_piv_fft64(p, dtype, ensemble, s); break;
-    case 3: e = lspiv::launch_piv_direct(p, dtype, ensemble, s); break;
-    case 9: e = lspiv::launch_piv_dft(p, dtype, ensemble, s); break;
-    case 10: {   // above 128 px: the same passes on slots of HBM scratch owned by the context (one stream at a time, like the
+    case kKindFft32: e = lspiv::launch_piv_fft32(p, dtype, ensemble, s); break;
+    case kKindFft64: e = lspiv::launch_piv_fft64(p, dtype, ensemble, s); break;
+    case kKindDirect: e = lspiv::launch_piv_direct(p, dtype, ensemble, s); break;
+    case kKindDft: e = lspiv::launch_piv_dft(p, dtype, ensemble, s); break;
+    case kKindDftGlobal: {   // above 128 px: the same passes on slots of HBM scratch owned by the context (one stream at a time, like the
                  // other context workspaces)
       DeviceCtx* c;
       LSPIV_TRY(get_ctx(&c));
@@ -271,40 +288,37 @@ int chunk_alignment_for(int wy, int wx, int64_t n_win) {
   return (int)lspiv::walk_anchor(wy, (uint32_t)std::min<int64_t>(n_win, 0x7fffffff));
 }
 
-// ---- shifted passes: what a window, a frame and the options must satisfy (multi-pass PIV and the multi-pass ensemble) ----
-static bool shift_shape_ok(int wy, int wx) { return wy == wx && (wy == 16 || wy == 32 || wy == 64); }
-int check_multipass_options() {
+// ---- what the families with kernels of a fixed size must satisfy (api_internal.h) ----
+static bool fixed_square_ok(int wy, int wx) { return wy == wx && (wy == 16 || wy == 32 || wy == 64); }
+int check_fixed_square(int wy, int wx, const char* what) {
+  if (fixed_square_ok(wy, wx)) return LSPIV_OK;
+  return fail(LSPIV_EUNSUPPORTED, "%s with window %dx%d is not supported: the window must be square and one of {16, 32, 64}", what, wy, wx);
+}
+int check_frame_fits_int16(int64_t H, int64_t W, const char* what) {
+  if (H <= 32767 && W <= 32767) return LSPIV_OK;
+  return fail(LSPIV_EINVAL, "frame (%lld,%lld): a side above 32767 does not fit %s", (long long)H, (long long)W, what);
+}
+int check_pair_options(const char* what, bool position_signal_ok) {
   if (!g_opt_norm_clip.load())
-    return fail(LSPIV_EUNSUPPORTED, "option norm_clip = 0 is served by the block-per-window kernels only, not by multi-pass PIV");
-  if (g_opt_signal_mode.load() == 1)
-    return fail(LSPIV_EUNSUPPORTED, "option signal_mode = 1 scores a window position over a chunk; a shifted window has no position of its own: "
-                "not supported by multi-pass PIV");
+    return fail(LSPIV_EUNSUPPORTED, "option norm_clip = 0 is served by the block-per-window kernels only, not by %s", what);
+  if (!position_signal_ok && g_opt_signal_mode.load() == 1)
+    return fail(LSPIV_EUNSUPPORTED, "option signal_mode = 1 scores a window position over a chunk, the kernels of %s score the two windows of a "
+                "pair: not supported", what);
   return LSPIV_OK;
 }
 int check_shift(int wy, int wx, int64_t H, int64_t W) {
-  if (!shift_shape_ok(wy, wx))
-    return fail(LSPIV_EUNSUPPORTED, "shifted pass with window %dx%d is not supported: the window must be square and one of {16, 32, 64}", wy, wx);
-  if (H > 32767 || W > 32767) return fail(LSPIV_EINVAL, "frame (%lld,%lld): a side above 32767 does not fit the int16 offsets", (long long)H, (long long)W);
+  LSPIV_TRY(check_fixed_square(wy, wx, "shifted pass"));
+  LSPIV_TRY(check_frame_fits_int16(H, W, "the int16 offsets"));
   return check_multipass_options();
 }
-// ---- SPOF phase-filtered correlation: the window is 16, 32 or 64 px square; norm_clip = 0 / signal_mode = 1 are refused like above ----
 int check_spof(int wy, int wx) {
-  if (!shift_shape_ok(wy, wx))
-    return fail(LSPIV_EUNSUPPORTED, "SPOF-filtered correlation with window %dx%d is not supported: the window must be square and one of {16, 32, 64}", wy, wx);
-  if (!g_opt_norm_clip.load())
-    return fail(LSPIV_EUNSUPPORTED, "option norm_clip = 0 is served by the block-per-window kernels only, not by SPOF-filtered correlation");
-  if (g_opt_signal_mode.load() == 1)
-    return fail(LSPIV_EUNSUPPORTED, "option signal_mode = 1 is not supported by SPOF-filtered correlation: its kernels score the two windows of a pair");
-  return LSPIV_OK;
+  LSPIV_TRY(check_fixed_square(wy, wx, "SPOF-filtered correlation"));
+  return check_pair_options("SPOF-filtered correlation");
 }
-// ---- image mask: the window is 16, 32 or 64 px square, k_min lies in 2 .. N^2; norm_clip = 0 / signal_mode = 1 are refused like above ----
+// image mask: besides, k_min lies in 2 .. N^2
 static int check_masked(int wy, int wx, const void* mask, int64_t k_min) {
-  if (!shift_shape_ok(wy, wx))
-    return fail(LSPIV_EUNSUPPORTED, "masked correlation with window %dx%d is not supported: the window must be square and one of {16, 32, 64}", wy, wx);
-  if (!g_opt_norm_clip.load())
-    return fail(LSPIV_EUNSUPPORTED, "option norm_clip = 0 is served by the block-per-window kernels only, not by masked correlation");
-  if (g_opt_signal_mode.load() == 1)
-    return fail(LSPIV_EUNSUPPORTED, "option signal_mode = 1 is not supported by masked correlation: its kernels score the valid samples of the two windows of a pair");
+  LSPIV_TRY(check_fixed_square(wy, wx, "masked correlation"));
+  LSPIV_TRY(check_pair_options("masked correlation"));
   if (!mask) return fail(LSPIV_EINVAL, "mask is NULL");
   if (k_min < 2 || k_min > (int64_t)wy * wx)
     return fail(LSPIV_EINVAL, "k_min %lld not in 2 .. %d (max(2, ceil(mask_coverage_min * window area)))", (long long)k_min, wy * wx);
@@ -364,39 +378,38 @@ int lspiv_rescue_stats(void* stream, int64_t* stats) {
 
 int lspiv_kernel_kind(int wy, int wx) {
   if (wy < 2 || wx < 2 || wy > LSPIV_MAX_WINDOW || wx > LSPIV_MAX_WINDOW) return LSPIV_EUNSUPPORTED;
-  if (wy > 64 || wx > 64) return lspiv::piv_dft_fits(wy, wx) ? 9 : 10;   // 2-D DFT of any shape: LDS-resident up to 128 x 128, HBM slots above
-  if (!g_opt_norm_clip.load()) {   // the un-clipped reading of A3 lives in the block-per-window kernels only (a switch, not a tuned path)
-    static const int min_area = getenv("LSPIV_DFT_MIN_AREA") ? atoi(getenv("LSPIV_DFT_MIN_AREA")) : 1500;
-    return wy * wx >= min_area && lspiv::piv_dft_fits(wy, wx) ? 9 : 3;
-  }
-  if (wy == 32 && wx == 32) return 1;
-  if (wy == 64 && wx == 64) return 2;
-  if (wy == 16 && wx == 16) return 6;
-  if (wy == 8 && wx == 8 && getenv("LSPIV_NO_PFA") == nullptr) return 6;
-  const bool no_pfa = getenv("LSPIV_NO_PFA") != nullptr;             // A/B switch: the P * 2^m sizes without their own FFT kernels
-  if (!no_pfa && wy == wx) {
+  if (wy > 64 || wx > 64) return lspiv::piv_dft_fits(wy, wx) ? kKindDft : kKindDftGlobal;   // 2-D DFT of any shape: LDS-resident up to 128 x 128, HBM slots above
+  // the area from which the DFT kernel takes over from the direct one (below), fixed at the first call
+  static const int dft_min_area = getenv("LSPIV_DFT_MIN_AREA") ? atoi(getenv("LSPIV_DFT_MIN_AREA")) : 1500;
+  const auto block_per_window = [&] { return wy * wx >= dft_min_area && lspiv::piv_dft_fits(wy, wx) ? kKindDft : kKindDirect; };
+  // the un-clipped reading of A3 lives in the block-per-window kernels only (a switch, not a tuned path); so do the non-square windows
+  if (!g_opt_norm_clip.load() || wy != wx) return block_per_window();
+  // A/B switches, read at every call: the P * 2^m sizes without their own FFT kernels; the direct kernel for every other size
+  const bool no_pfa = getenv("LSPIV_NO_PFA") != nullptr, no_embed = getenv("LSPIV_NO_EMBED") != nullptr;
+  if (wy == 32) return kKindFft32;
+  if (wy == 64) return kKindFft64;
+  if (wy == 16) return kKindFft8or16;
+  if (!no_pfa) {
+    if (wy == 8) return kKindFft8or16;
     switch (wy) {
 #define LSPIV_PFA_CASE(n) case n:
       LSPIV_PFA_SIZES(LSPIV_PFA_CASE)
 #undef LSPIV_PFA_CASE
-        return 8;
+        return kKindPfa;
       default: break;
     }
   }
-  const bool no_embed = getenv("LSPIV_NO_EMBED") != nullptr;   // A/B switch: direct kernel for every other size
-  if (!no_embed && wy == wx && wy >= 4 && wy <= 8) return 7;
-  if (!no_embed && wy == wx && wy >= 9 && wy <= 15) return 4;
+  if (!no_embed && wy >= 4 && wy <= 8) return kKindEmbed16;
+  if (!no_embed && wy >= 9 && wy <= 15) return kKindEmbed32;
   // 17..20: the direct kernel's N^4 multiply-adds are still cheaper than two 64-point transforms per window (measured
   // crossover between 20 and 22, tools/direct_bench.py)
-  if (!no_embed && wy == wx && wy > 20 && wy < 32) return 5;
+  if (!no_embed && wy > 20 && wy < 32) return kKindEmbed64;
   // what is left -- non-square windows, odd 17 / 19 / 33 .. 63: the direct spatial kernel costs wy wx multiply-adds per plane
   // sample, the LDS-resident DFT passes (wy + wx) complex ones, a composite length in two shorter passes.  Measured on
   // 785 x 875 frames (tools/gpu_ab_direct.sh; M window pairs/s, direct | DFT): 40 x 24 23.2 | 13.1, 35 x 35 14.0 | 12.2,
   // 48 x 32 10.4 | 11.9, 41 x 41 8.1 | 9.2, 64 x 32 6.1 | 11.3, 49 x 49 3.6 | 10.7, 63 x 63 1.6 | 7.2 -- the DFT kernel takes over
   // from 1500 samples per window (LSPIV_DFT_MIN_AREA)
-  static const int dft_min_area = getenv("LSPIV_DFT_MIN_AREA") ? atoi(getenv("LSPIV_DFT_MIN_AREA")) : 1500;
-  if (wy * wx >= dft_min_area && lspiv::piv_dft_fits(wy, wx)) return 9;
-  return 3;
+  return block_per_window();
 }
 
 int lspiv_grid_shape(int64_t H, int64_t W, int wy, int wx, int oy, int ox, int64_t* n_rows, int64_t* n_cols) {
@@ -425,8 +438,7 @@ int64_t lspiv_required_bytes(int64_t T, int64_t H, int64_t W, int dtype, int wy,
   const int64_t n_tiles = (T - 1) * g.n_rows * g.n_cols;
   int64_t b = T * H * W * (int64_t)elem_size(dtype) + 4 * n_tiles * 4;
   if (with_planes) b += n_tiles * wy * wx * 4;
-  if (g_opt_rescue.load())   // the rescue lists of the launch stream: n_tiles / 4 records of 16 bytes + n_tiles / 16 of 4 (rescue_ws)
-    b += 256 + (int64_t)std::max<int64_t>(4096, n_tiles / 4) * 16 + (int64_t)std::max<int64_t>(1024, n_tiles / 16) * 4;
+  if (g_opt_rescue.load()) b += (int64_t)rescue_caps(n_tiles).bytes();   // the rescue lists of the launch stream
   return b;
 }
 
@@ -456,57 +468,62 @@ int lspiv_chunk_alignment_grid(int64_t H, int64_t W, int wy, int wx, int oy, int
   return chunk_alignment_for(wy, wx, g.n_rows * g.n_cols);
 }
 
-// nw: 0, or the window inside the search area wy x wx (search-area mode)
-// filter: 0, or LSPIV_FILTER_SPOF (the caller has run check_spof)
-// d_mask, k_min: nullptr, or the image mask of the frames' shape on the device and the smallest count of valid samples (the caller has
-// run check_masked)
-static int piv_pairs_dev(const void* d_frames, int dtype, int64_t T, int64_t H, int64_t W, int wy, int wx, int nw, int oy,
-                         int ox, float signal_threshold, int64_t pair_offset, float* d_out, float* d_corr_planes,
-                         void* stream, int filter = 0, const uint8_t* d_mask = nullptr, int64_t k_min = 0) {
+// what a per-pair launch is besides its window, all zero for the plain one (the exported wrappers have run the mode's check):
+struct PairMode {
+  int nw = 0;                      // the window inside the search area wy x wx (search-area mode)
+  int filter = 0;                  // LSPIV_FILTER_SPOF
+  const uint8_t* mask = nullptr;   // the image mask of the frames' shape, where the entry point's frames are: HBM (_dev) or host
+  int64_t k_min = 0;               // ... and the smallest count of valid samples of a window
+  bool per_pair() const { return nw || filter || mask; }   // one window pair per job: no anchors to cut launches at
+};
+// what every device-pointer entry point checks first
+static int check_dev_call(const void* d_frames, const void* d_out, int64_t pair_offset) {
   if (!d_frames || !d_out) return fail(LSPIV_EINVAL, "d_frames / d_out is NULL");
   if (pair_offset < 0) return fail(LSPIV_EINVAL, "pair_offset %lld is negative", (long long)pair_offset);
+  return LSPIV_OK;
+}
+static int piv_pairs_dev(const void* d_frames, int dtype, int64_t T, int64_t H, int64_t W, int wy, int wx, int oy, int ox,
+                         float signal_threshold, int64_t pair_offset, float* d_out, float* d_corr_planes, void* stream, const PairMode& m) {
+  LSPIV_TRY(check_dev_call(d_frames, d_out, pair_offset));
   Grid g;
   LSPIV_TRY(make_grid(H, W, wy, wx, oy, ox, &g));
   DeviceCtx* c;
   LSPIV_TRY(get_ctx(&c));
   lspiv::PivParams p;
   LSPIV_TRY(fill_params(&p, d_frames, dtype, T, H, W, wy, wx, oy, ox, signal_threshold, g));
-  if (nw) set_search_window(&p, nw);
+  if (m.nw) set_search_window(&p, m.nw);
   p.pair_offset = pair_offset;
-  p.u = d_out;
-  p.v = d_out + (size_t)p.n_tiles;
-  p.cmax = d_out + 2 * (size_t)p.n_tiles;
-  p.s2n = d_out + 3 * (size_t)p.n_tiles;
-  p.planes = d_corr_planes;
-  p.mask = d_mask;
-  p.k_min = (uint32_t)k_min;
+  set_results(&p, d_out, p.n_tiles, 0, d_corr_planes, 0);
+  p.mask = m.mask;
+  p.k_min = (uint32_t)m.k_min;
   hipStream_t s = on_stream(c, stream);
   LSPIV_TRY(apply_signal_mode(c, &p, dtype, s));
-  LSPIV_TRY(dispatch(p, dtype, false, s, filter));
+  LSPIV_TRY(dispatch(p, dtype, false, s, m.filter));
   return apply_v_sign(p.v, (int64_t)p.n_tiles, s);
 }
 
 int lspiv_piv_pairs_dev_at(const void* d_frames, int dtype, int64_t T, int64_t H, int64_t W, int wy, int wx, int oy,
                            int ox, float signal_threshold, int64_t pair_offset, float* d_out, float* d_corr_planes,
                            void* stream) {
-  return piv_pairs_dev(d_frames, dtype, T, H, W, wy, wx, 0, oy, ox, signal_threshold, pair_offset, d_out, d_corr_planes, stream);
+  return piv_pairs_dev(d_frames, dtype, T, H, W, wy, wx, oy, ox, signal_threshold, pair_offset, d_out, d_corr_planes, stream, {});
 }
 
-int lspiv_spof_supported(int wy, int wx) { return shift_shape_ok(wy, wx) ? 1 : 0; }
+int lspiv_spof_supported(int wy, int wx) { return fixed_square_ok(wy, wx) ? 1 : 0; }
 
 int lspiv_piv_spof_pairs_dev_at(const void* d_frames, int dtype, int64_t T, int64_t H, int64_t W, int wy, int wx, int oy, int ox,
                                 float signal_threshold, int64_t pair_offset, float* d_out, float* d_corr_planes, void* stream) {
   LSPIV_TRY(check_spof(wy, wx));
-  return piv_pairs_dev(d_frames, dtype, T, H, W, wy, wx, 0, oy, ox, signal_threshold, pair_offset, d_out, d_corr_planes, stream, LSPIV_FILTER_SPOF);
+  return piv_pairs_dev(d_frames, dtype, T, H, W, wy, wx, oy, ox, signal_threshold, pair_offset, d_out, d_corr_planes, stream, {.filter = LSPIV_FILTER_SPOF});
 }
 
-int lspiv_mask_supported(int wy, int wx) { return shift_shape_ok(wy, wx) ? 1 : 0; }
+int lspiv_mask_supported(int wy, int wx) { return fixed_square_ok(wy, wx) ? 1 : 0; }
 
 int lspiv_piv_masked_pairs_dev_at(const void* d_frames, int dtype, int64_t T, int64_t H, int64_t W, int wy, int wx, int oy, int ox,
                                   const uint8_t* d_mask, int64_t k_min, float signal_threshold, int64_t pair_offset, float* d_out,
                                   float* d_corr_planes, void* stream) {
   LSPIV_TRY(check_masked(wy, wx, d_mask, k_min));
-  return piv_pairs_dev(d_frames, dtype, T, H, W, wy, wx, 0, oy, ox, signal_threshold, pair_offset, d_out, d_corr_planes, stream, 0, d_mask, k_min);
+  return piv_pairs_dev(d_frames, dtype, T, H, W, wy, wx, oy, ox, signal_threshold, pair_offset, d_out, d_corr_planes, stream,
+                       {.mask = d_mask, .k_min = k_min});
 }
 
 int lspiv_search_supported(int say, int sax, int wy, int wx) { return search_shape_ok(say, sax, wy, wx) ? 1 : 0; }
@@ -515,7 +532,7 @@ int lspiv_piv_search_pairs_dev_at(const void* d_frames, int dtype, int64_t T, in
                                   int oy, int ox, float signal_threshold, int64_t pair_offset, float* d_out, float* d_corr_planes,
                                   void* stream) {
   LSPIV_TRY(check_search(say, sax, wy, wx));
-  return piv_pairs_dev(d_frames, dtype, T, H, W, say, sax, wy, oy, ox, signal_threshold, pair_offset, d_out, d_corr_planes, stream);
+  return piv_pairs_dev(d_frames, dtype, T, H, W, say, sax, oy, ox, signal_threshold, pair_offset, d_out, d_corr_planes, stream, {.nw = wy});
 }
 
 // ---- multi-pass PIV (include/lspiv.h) ---------------------------------------------------------------
@@ -529,11 +546,7 @@ static int shift_pass(const void* d_frames, int dtype, int64_t T, int64_t H, int
   p.pair_offset = pair_offset;
   p.shifted = 1;
   p.shift = d_shift;
-  p.u = d_out;
-  p.v = d_out + (size_t)p.n_tiles;
-  p.cmax = d_out + 2 * (size_t)p.n_tiles;
-  p.s2n = d_out + 3 * (size_t)p.n_tiles;
-  p.planes = d_planes;
+  set_results(&p, d_out, p.n_tiles, 0, d_planes, 0);
   LSPIV_TRY(dispatch(p, dtype, false, s));
   LSPIV_TRY(launch_status(lspiv::launch_add_shift(p, s)));
   if (out_p) *out_p = p;
@@ -564,10 +577,10 @@ static int64_t deform_batch_pairs(int64_t n_pairs, int64_t H, int64_t W) {
   return std::max<int64_t>(1, std::min<int64_t>(std::min<int64_t>(n_pairs, fit), 65535));   // (65535: the warp's grid runs the pairs along z)
 }
 static int check_deform(int wy, int wx, int oy, int ox, int64_t H, int64_t W) {
-  if (!shift_shape_ok(wy, wx) || oy != ox)
+  if (!fixed_square_ok(wy, wx) || oy != ox)
     return fail(LSPIV_EUNSUPPORTED, "deformation pass with window %dx%d, overlap (%d,%d) is not supported: the window must be square and one of "
                 "{16, 32, 64}, the overlap the same on both axes", wy, wx, oy, ox);
-  if (H > 32767 || W > 32767) return fail(LSPIV_EINVAL, "frame (%lld,%lld): a side above 32767 does not fit the nodes' range", (long long)H, (long long)W);
+  LSPIV_TRY(check_frame_fits_int16(H, W, "the nodes' range"));
   return check_multipass_options();
 }
 // one deformation pass on stream s: d_nodes (T-1) * n_win * {v, u} -> d_out [u | v | corr_max | s2n] of all pairs (kernel orientation;
@@ -588,11 +601,7 @@ static int deform_pass(DeviceCtx* c, const void* d_frames, int dtype, int64_t T,
     const size_t t0 = (size_t)b0 * n_win;
     p.nodes = d_nodes + 2 * t0;
     p.warped = c->d_deform;
-    p.u = d_out + t0;
-    p.v = d_out + n_tiles + t0;
-    p.cmax = d_out + 2 * n_tiles + t0;
-    p.s2n = d_out + 3 * n_tiles + t0;
-    p.planes = d_planes ? d_planes + t0 * (size_t)n * n : nullptr;
+    set_results(&p, d_out, n_tiles, t0, d_planes, (size_t)n * n);
     LSPIV_TRY(launch_status(lspiv::launch_deform_warp(p, dtype, c->d_deform, s)));
     LSPIV_TRY(dispatch(p, dtype, false, s));
     LSPIV_TRY(launch_status(lspiv::launch_add_nodes(p, s)));
@@ -603,18 +612,18 @@ static int deform_pass(DeviceCtx* c, const void* d_frames, int dtype, int64_t T,
 static int multipass_dev(DeviceCtx* c, const void* d_frames, int dtype, int64_t T, int64_t H, int64_t W, int n_passes, const int* passes,
                          float signal_threshold, int64_t pair_offset, float* d_out, float* d_planes, int16_t* d_shift_out, hipStream_t s,
                          int n_deform = 0) {
-  if (!d_frames || !d_out || !passes) return fail(LSPIV_EINVAL, "d_frames / d_out / passes is NULL");
+  LSPIV_TRY(check_dev_call(d_frames, d_out, pair_offset));
+  if (!passes) return fail(LSPIV_EINVAL, "passes is NULL");
   if (n_passes < 1 || n_passes > 8) return fail(LSPIV_EINVAL, "n_passes %d not in 1..8", n_passes);
-  if (pair_offset < 0) return fail(LSPIV_EINVAL, "pair_offset %lld is negative", (long long)pair_offset);
   if (T < 2) return fail(LSPIV_ESHAPE, "need at least 2 frames, got %lld", (long long)T);
   LSPIV_TRY(check_multipass_options());
-  if (H > 32767 || W > 32767) return fail(LSPIV_EINVAL, "frame (%lld,%lld): a side above 32767 does not fit the int16 offsets", (long long)H, (long long)W);
+  LSPIV_TRY(check_frame_fits_int16(H, W, "the int16 offsets"));
   lspiv::PassGrid pg[8];
   size_t max_tiles = 0;
   for (int k = 0; k < n_passes; ++k) {
     const int* q = passes + 4 * k;
     if (q[0] != q[1]) return fail(LSPIV_EINVAL, "pass %d: window %dx%d is not square", k, q[0], q[1]);
-    if (k > 0 && !shift_shape_ok(q[0], q[1]))
+    if (k > 0 && !fixed_square_ok(q[0], q[1]))
       return fail(LSPIV_EUNSUPPORTED, "pass %d: window %dx%d is not supported: the windows of passes after the first must be one of {16, 32, 64}", k, q[0], q[1]);
     if (k > 0 && q[0] > passes[4 * (k - 1)]) return fail(LSPIV_EINVAL, "pass %d: window %d is larger than pass %d's %d", k, q[0], k - 1, passes[4 * (k - 1)]);
     LSPIV_TRY(pass_grid(H, W, q[0], q[1], q[2], q[3], &pg[k]));
@@ -649,7 +658,7 @@ static int multipass_dev(DeviceCtx* c, const void* d_frames, int dtype, int64_t 
     lspiv::PivParams p;
     LSPIV_TRY(fill_params(&p, d_frames, dtype, T, H, W, q[0], q[1], q[2], q[3], signal_threshold, g));
     p.pair_offset = pair_offset;
-    p.u = r0; p.v = r0 + (size_t)p.n_tiles; p.cmax = r0 + 2 * (size_t)p.n_tiles; p.s2n = r0 + 3 * (size_t)p.n_tiles;
+    set_results(&p, r0, p.n_tiles, 0, nullptr, 0);
     LSPIV_TRY(dispatch(p, dtype, false, s));
     if (n_passes == 1 && d_shift_out) HIP_TRY(hipMemsetAsync(d_shift_out, 0, last_tiles * 2 * sizeof(int16_t), s));
   }
@@ -673,13 +682,12 @@ static int multipass_dev(DeviceCtx* c, const void* d_frames, int dtype, int64_t 
   return apply_v_sign(d_out + last_tiles, (int64_t)last_tiles, s);
 }
 
-int lspiv_shift_supported(int wy, int wx) { return shift_shape_ok(wy, wx) ? 1 : 0; }
+int lspiv_shift_supported(int wy, int wx) { return fixed_square_ok(wy, wx) ? 1 : 0; }
 
 int lspiv_piv_shift_pairs_dev_at(const void* d_frames, int dtype, int64_t T, int64_t H, int64_t W, int wy, int wx, int oy, int ox,
                                  float signal_threshold, int64_t pair_offset, const int16_t* d_shift, float* d_out, float* d_corr_planes,
                                  void* stream) {
-  if (!d_frames || !d_out) return fail(LSPIV_EINVAL, "d_frames / d_out is NULL");
-  if (pair_offset < 0) return fail(LSPIV_EINVAL, "pair_offset %lld is negative", (long long)pair_offset);
+  LSPIV_TRY(check_dev_call(d_frames, d_out, pair_offset));
   LSPIV_TRY(check_shift(wy, wx, H, W));
   DeviceCtx* c;
   LSPIV_TRY(get_ctx(&c));
@@ -693,7 +701,7 @@ int lspiv_piv_predict_shift_dev(const float* d_u, const float* d_v, int64_t n_pa
                                 int fwy, int fwx, int foy, int fox, int16_t* d_shift, void* stream) {
   if (!d_u || !d_v || !d_shift) return fail(LSPIV_EINVAL, "NULL argument");
   if (n_pairs < 0) return fail(LSPIV_EINVAL, "n_pairs %lld is negative", (long long)n_pairs);
-  if (H > 32767 || W > 32767) return fail(LSPIV_EINVAL, "frame (%lld,%lld): a side above 32767 does not fit the int16 offsets", (long long)H, (long long)W);
+  LSPIV_TRY(check_frame_fits_int16(H, W, "the int16 offsets"));
   lspiv::PassGrid cg, fg;
   LSPIV_TRY(pass_grid(H, W, cwy, cwx, coy, cox, &cg));
   LSPIV_TRY(pass_grid(H, W, fwy, fwx, foy, fox, &fg));
@@ -710,7 +718,7 @@ int lspiv_piv_multipass_dev_at(const void* d_frames, int dtype, int64_t T, int64
                        on_stream(c, stream));
 }
 
-int lspiv_deform_supported(int wy, int wx) { return shift_shape_ok(wy, wx) ? 1 : 0; }
+int lspiv_deform_supported(int wy, int wx) { return fixed_square_ok(wy, wx) ? 1 : 0; }
 
 int64_t lspiv_deform_required_bytes(int64_t T, int64_t H, int64_t W, int wy, int wx, int oy, int ox) {
   Grid g;
@@ -730,8 +738,8 @@ int lspiv_piv_predict_deform_dev(const float* d_u, const float* d_v, int64_t n_p
 int lspiv_piv_deform_pairs_dev_at(const void* d_frames, int dtype, int64_t T, int64_t H, int64_t W, int wy, int wx, int oy, int ox,
                                   float signal_threshold, int64_t pair_offset, const int32_t* d_nodes, float* d_out, float* d_corr_planes,
                                   void* stream) {
-  if (!d_frames || !d_out || !d_nodes) return fail(LSPIV_EINVAL, "d_frames / d_nodes / d_out is NULL");
-  if (pair_offset < 0) return fail(LSPIV_EINVAL, "pair_offset %lld is negative", (long long)pair_offset);
+  LSPIV_TRY(check_dev_call(d_frames, d_out, pair_offset));
+  if (!d_nodes) return fail(LSPIV_EINVAL, "d_nodes is NULL");
   if (T < 2) return fail(LSPIV_ESHAPE, "need at least 2 frames, got %lld", (long long)T);
   LSPIV_TRY(check_deform(wy, wx, oy, ox, H, W));
   Grid g;
@@ -754,9 +762,79 @@ int lspiv_piv_multipass_deform_dev_at(const void* d_frames, int dtype, int64_t T
                        on_stream(c, stream), n_deform);
 }
 
+// ---- the host-pointer entry points -----------------------------------------------------------------------------------------------
+// What both check before they touch the device, the sizes they share, and the workspaces the frames and the planes go through: the
+// stack is copied into c->d_frames through a two-slot pinned ring in batches of whole frames.  The caller holds the `host` lock.
+struct HostStack {
+  DeviceCtx* c;
+  Grid g;
+  int dev_dtype;   // float64 is narrowed to float32 while it is staged
+  size_t frame_elems, frame_bytes, n_win, n_tiles;
+  int64_t frames_per_batch;
+  bool src_pinned;
+};
+static int host_stack(HostStack* h, const void* frames, int dtype, int64_t T, int64_t H, int64_t W, int wy, int wx, int oy, int ox,
+                      int64_t pair_offset, const float* u, const float* v, const float* corr_max, const float* s2n, const float* corr_planes) {
+  if (!frames || !u || !v || !corr_max || !s2n) return fail(LSPIV_EINVAL, "NULL buffer");
+  if (pair_offset < 0) return fail(LSPIV_EINVAL, "pair_offset %lld is negative", (long long)pair_offset);
+  LSPIV_TRY(make_grid(H, W, wy, wx, oy, ox, &h->g));
+  if (dtype < 0 || dtype > 2) return fail(LSPIV_EINVAL, "dtype %d not in {0:u8, 1:f32, 2:f64}", dtype);
+  if (T < 2) return fail(LSPIV_ESHAPE, "need at least 2 frames, got %lld", (long long)T);
+  LSPIV_TRY(get_ctx(&h->c));
+  h->dev_dtype = dtype == LSPIV_F64 ? LSPIV_F32 : dtype;
+  h->frame_elems = (size_t)H * W;
+  h->frame_bytes = h->frame_elems * elem_size(h->dev_dtype);
+  h->n_win = (size_t)h->g.n_rows * h->g.n_cols;
+  h->n_tiles = (size_t)(T - 1) * h->n_win;
+  LSPIV_TRY(ensure(&h->c->d_frames, &h->c->frames_cap, (size_t)T * h->frame_bytes));
+  if (corr_planes) LSPIV_TRY(ensure(&h->c->d_planes, &h->c->planes_cap, h->n_tiles * wy * wx * sizeof(float)));
+  LSPIV_TRY(stage_ring(h->c, h->frame_bytes));
+  h->frames_per_batch = std::max<int64_t>(1, (int64_t)(h->c->pinned_cap / h->frame_bytes));
+  h->src_pinned = dtype != LSPIV_F64 && is_pinned(frames);
+  return LSPIV_OK;
+}
+// queues what a host entry point hands back on the context's stream: the four blocks of c->d_out, the planes (plane_elems floats per
+// window), the chain's offsets
+static int results_to_host(const HostStack& h, float* u, float* v, float* corr_max, float* s2n, float* corr_planes, size_t plane_elems,
+                           int16_t* shift_out = nullptr, const int16_t* d_shift = nullptr) {
+  DeviceCtx* c = h.c;
+  float* const out[4] = {u, v, corr_max, s2n};
+  for (int k = 0; k < 4; ++k)
+    HIP_TRY(hipMemcpyAsync(out[k], c->d_out + k * h.n_tiles, h.n_tiles * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+  if (corr_planes) HIP_TRY(hipMemcpyAsync(corr_planes, c->d_planes, h.n_tiles * plane_elems * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+  if (shift_out) HIP_TRY(hipMemcpyAsync(shift_out, d_shift, h.n_tiles * 2 * sizeof(int16_t), hipMemcpyDeviceToHost, c->stream));
+  return LSPIV_OK;
+}
+
+// the chain on a host stack: the whole chunk is staged first (the later passes need every frame of a pair anyway), then the chain runs on it
 static int multipass_host(const void* frames, int dtype, int64_t T, int64_t H, int64_t W, int n_passes, const int* passes, int n_deform,
                           float signal_threshold, int64_t pair_offset, float* u, float* v, float* corr_max, float* s2n, float* corr_planes,
-                          int16_t* shift_out);
+                          int16_t* shift_out) {
+  std::lock_guard<std::mutex> host_lock(locks_here().host);
+  if (!passes) return fail(LSPIV_EINVAL, "NULL buffer");
+  if (n_passes < 1 || n_passes > 8) return fail(LSPIV_EINVAL, "n_passes %d not in 1..8", n_passes);
+  const int* last = passes + 4 * (n_passes - 1);
+  HostStack h;
+  LSPIV_TRY(host_stack(&h, frames, dtype, T, H, W, last[0], last[1], last[2], last[3], pair_offset, u, v, corr_max, s2n, corr_planes));
+  DeviceCtx* c = h.c;
+  const size_t out_bytes = (4 * h.n_tiles * sizeof(float) + 255) & ~(size_t)255;   // (the offsets follow the results, 256-byte aligned)
+  LSPIV_TRY(ensure(&c->d_out, &c->out_cap, out_bytes + (shift_out ? h.n_tiles * 2 * sizeof(int16_t) : 0)));
+  int16_t* d_shift = shift_out ? reinterpret_cast<int16_t*>((char*)c->d_out + out_bytes) : nullptr;
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  int batch = 0;
+  for (int64_t f0 = 0; f0 < T; ++batch) {
+    const int64_t f1 = std::min<int64_t>(T, f0 + h.frames_per_batch);
+    LSPIV_TRY(stage_frames(c, batch, c->d_frames, frames, dtype, h.src_pinned, h.frame_elems, f0, f1, signal_threshold));
+    f0 = f1;
+  }
+  HIP_TRY(hipStreamSynchronize(c->copy_stream));
+  const int rc = multipass_dev(c, c->d_frames, h.dev_dtype, T, H, W, n_passes, passes, signal_threshold, pair_offset, c->d_out,
+                               corr_planes ? c->d_planes : nullptr, d_shift, c->stream, n_deform);
+  if (rc != LSPIV_OK) { (void)hipStreamSynchronize(c->stream); return rc; }
+  LSPIV_TRY(results_to_host(h, u, v, corr_max, s2n, corr_planes, (size_t)last[0] * last[1], shift_out, d_shift));
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  return LSPIV_OK;
+}
 
 int lspiv_piv_multipass_deform_at(const void* frames, int dtype, int64_t T, int64_t H, int64_t W, int n_passes, const int* passes, int n_deform,
                                   float signal_threshold, int64_t pair_offset, float* u, float* v, float* corr_max, float* s2n,
@@ -769,111 +847,43 @@ int lspiv_piv_multipass_at(const void* frames, int dtype, int64_t T, int64_t H, 
   return multipass_host(frames, dtype, T, H, W, n_passes, passes, 0, signal_threshold, pair_offset, u, v, corr_max, s2n, corr_planes, shift_out);
 }
 
-static int multipass_host(const void* frames, int dtype, int64_t T, int64_t H, int64_t W, int n_passes, const int* passes, int n_deform,
-                          float signal_threshold, int64_t pair_offset, float* u, float* v, float* corr_max, float* s2n, float* corr_planes,
-                          int16_t* shift_out) {
-  std::lock_guard<std::mutex> host_lock(locks_here().host);
-  if (!frames || !u || !v || !corr_max || !s2n || !passes) return fail(LSPIV_EINVAL, "NULL buffer");
-  if (n_passes < 1 || n_passes > 8) return fail(LSPIV_EINVAL, "n_passes %d not in 1..8", n_passes);
-  if (dtype < 0 || dtype > 2) return fail(LSPIV_EINVAL, "dtype %d not in {0:u8, 1:f32, 2:f64}", dtype);
-  if (T < 2) return fail(LSPIV_ESHAPE, "need at least 2 frames, got %lld", (long long)T);
-  const int* last = passes + 4 * (n_passes - 1);
-  Grid g;
-  LSPIV_TRY(make_grid(H, W, last[0], last[1], last[2], last[3], &g));
-  DeviceCtx* c;
-  LSPIV_TRY(get_ctx(&c));
-  const int dev_dtype = dtype == LSPIV_F64 ? LSPIV_F32 : dtype;   // float64 is narrowed while it is staged
-  const size_t frame_elems = (size_t)H * W, frame_bytes = frame_elems * elem_size(dev_dtype);
-  const size_t n_tiles = (size_t)(T - 1) * g.n_rows * g.n_cols;
-  const size_t out_bytes = 4 * n_tiles * sizeof(float), shift_bytes = shift_out ? n_tiles * 2 * sizeof(int16_t) : 0;
-  LSPIV_TRY(ensure(&c->d_frames, &c->frames_cap, (size_t)T * frame_bytes));
-  LSPIV_TRY(ensure(&c->d_out, &c->out_cap, ((out_bytes + 255) & ~(size_t)255) + shift_bytes));
-  int16_t* d_shift = shift_out ? reinterpret_cast<int16_t*>((char*)c->d_out + ((out_bytes + 255) & ~(size_t)255)) : nullptr;
-  if (corr_planes) LSPIV_TRY(ensure(&c->d_planes, &c->planes_cap, n_tiles * last[0] * last[1] * sizeof(float)));
-  // the whole chunk is staged first (the chain's later passes need every frame of a pair anyway), then the chain runs on it
-  LSPIV_TRY(stage_ring(c, frame_bytes));
-  HIP_TRY(hipStreamSynchronize(c->stream));
-  const bool src_pinned = dtype != LSPIV_F64 && is_pinned(frames);
-  const int64_t fpb = std::max<int64_t>(1, (int64_t)(c->pinned_cap / frame_bytes));
-  int batch = 0;
-  for (int64_t f0 = 0; f0 < T; ++batch) {
-    const int64_t f1 = std::min<int64_t>(T, f0 + fpb);
-    LSPIV_TRY(stage_frames(c, batch, c->d_frames, frames, dtype, src_pinned, frame_elems, f0, f1, signal_threshold));
-    f0 = f1;
-  }
-  HIP_TRY(hipStreamSynchronize(c->copy_stream));
-  const int rc = multipass_dev(c, c->d_frames, dev_dtype, T, H, W, n_passes, passes, signal_threshold, pair_offset, c->d_out,
-                               corr_planes ? c->d_planes : nullptr, d_shift, c->stream, n_deform);
-  if (rc != LSPIV_OK) { (void)hipStreamSynchronize(c->stream); return rc; }
-  const size_t ob = n_tiles * sizeof(float);
-  HIP_TRY(hipMemcpyAsync(u, c->d_out, ob, hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(hipMemcpyAsync(v, c->d_out + n_tiles, ob, hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(hipMemcpyAsync(corr_max, c->d_out + 2 * n_tiles, ob, hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(hipMemcpyAsync(s2n, c->d_out + 3 * n_tiles, ob, hipMemcpyDeviceToHost, c->stream));
-  if (shift_out) HIP_TRY(hipMemcpyAsync(shift_out, d_shift, shift_bytes, hipMemcpyDeviceToHost, c->stream));
-  if (corr_planes)
-    HIP_TRY(hipMemcpyAsync(corr_planes, c->d_planes, n_tiles * last[0] * last[1] * sizeof(float), hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(hipStreamSynchronize(c->stream));
-  return LSPIV_OK;
-}
-
 int lspiv_piv_pairs_dev(const void* d_frames, int dtype, int64_t T, int64_t H, int64_t W, int wy, int wx, int oy,
                         int ox, float signal_threshold, float* d_out, float* d_corr_planes, void* stream) {
   return lspiv_piv_pairs_dev_at(d_frames, dtype, T, H, W, wy, wx, oy, ox, signal_threshold, 0, d_out, d_corr_planes, stream);
 }
 
-// the host entry point, optionally with the px -> m/s scaling of pyorc/velocimetry/ffpiv.py:418-419 applied on the device before the
-// results come back (dt != NULL: seconds per pair, T - 1 entries)
-// nw: 0, or the window inside the search area wy x wx (search-area mode)
-static int piv_pairs_host(const void* frames, int dtype, int64_t T, int64_t H, int64_t W, int wy, int wx, int nw, int oy, int ox,
+// the per-pair modes on a host stack, optionally with the px -> m/s scaling of pyorc/velocimetry/ffpiv.py:418-419 applied on the device
+// before the results come back (dt != NULL: seconds per pair, T - 1 entries)
+// Pipelined upload: the kernel for the pairs that have become resident runs while the next batch is staged and DMA'd.  Launches are cut
+// at the anchors of the walking kernels' segments (multiples of lspiv_chunk_alignment of the absolute pair index), so the pipelined run
+// issues exactly the jobs of one launch over the whole stack: same bits as lspiv_piv_pairs_dev_at.
+static int piv_pairs_host(const void* frames, int dtype, int64_t T, int64_t H, int64_t W, int wy, int wx, int oy, int ox,
                           float signal_threshold, int64_t pair_offset, float* u, float* v, float* corr_max, float* s2n,
-                          float* corr_planes, const double* dt, double res_x, double res_y, int filter = 0, const uint8_t* mask = nullptr,
-                          int64_t k_min = 0) {
+                          float* corr_planes, const PairMode& m, const double* dt = nullptr, double res_x = 1.0, double res_y = 1.0) {
   std::lock_guard<std::mutex> host_lock(locks_here().host);
-  if (!frames || !u || !v || !corr_max || !s2n) return fail(LSPIV_EINVAL, "NULL buffer");
-  if (pair_offset < 0) return fail(LSPIV_EINVAL, "pair_offset %lld is negative", (long long)pair_offset);
-  Grid g;
-  LSPIV_TRY(make_grid(H, W, wy, wx, oy, ox, &g));
-  if (dtype < 0 || dtype > 2) return fail(LSPIV_EINVAL, "dtype %d not in {0:u8, 1:f32, 2:f64}", dtype);
-  if (T < 2) return fail(LSPIV_ESHAPE, "need at least 2 frames, got %lld", (long long)T);
-  DeviceCtx* c;
-  LSPIV_TRY(get_ctx(&c));
-  const int dev_dtype = dtype == LSPIV_F64 ? LSPIV_F32 : dtype;   // float64 is narrowed while it is staged
-  const size_t fbytes = (size_t)T * H * W * elem_size(dev_dtype);
-  const size_t n_tiles = (size_t)(T - 1) * g.n_rows * g.n_cols;
-  LSPIV_TRY(ensure(&c->d_frames, &c->frames_cap, fbytes));
-  LSPIV_TRY(ensure(&c->d_out, &c->out_cap, 4 * n_tiles * sizeof(float)));
-  if (corr_planes) {
-    LSPIV_TRY(ensure(&c->d_planes, &c->planes_cap, n_tiles * wy * wx * sizeof(float)));
-  }
-  // Pipelined upload: the stack is copied through a two-slot pinned ring in sub-batches of whole frames; the kernel
-  // for the pairs that have become resident runs while the next sub-batch is staged and DMA'd.  Launches are cut at
-  // the anchors of the walking kernels' segments (multiples of lspiv_chunk_alignment of the absolute pair index), so
-  // the pipelined run issues exactly the jobs of one launch over the whole stack: same bits as lspiv_piv_pairs_dev_at.
+  HostStack h;
+  LSPIV_TRY(host_stack(&h, frames, dtype, T, H, W, wy, wx, oy, ox, pair_offset, u, v, corr_max, s2n, corr_planes));
+  DeviceCtx* c = h.c;
+  LSPIV_TRY(ensure(&c->d_out, &c->out_cap, 4 * h.n_tiles * sizeof(float)));
   lspiv::PivParams base;
-  LSPIV_TRY(fill_params(&base, c->d_frames, dev_dtype, T, H, W, wy, wx, oy, ox, signal_threshold, g));
-  if (nw) set_search_window(&base, nw);
-  if (mask) {   // the image mask goes up once, into the context's own buffer (under the host lock, like the frames' workspace), ahead of the kernels
-    LSPIV_TRY(ensure(&c->d_mask, &c->mask_cap, (size_t)H * W));
-    HIP_TRY(hipMemcpyAsync(c->d_mask, mask, (size_t)H * W, hipMemcpyHostToDevice, c->stream));
+  LSPIV_TRY(fill_params(&base, c->d_frames, h.dev_dtype, T, H, W, wy, wx, oy, ox, signal_threshold, h.g));
+  if (m.nw) set_search_window(&base, m.nw);
+  if (m.mask) {   // the image mask goes up once, into the context's own buffer (under the host lock, like the frames' workspace), ahead of the kernels
+    LSPIV_TRY(ensure(&c->d_mask, &c->mask_cap, h.frame_elems));
+    HIP_TRY(hipMemcpyAsync(c->d_mask, m.mask, h.frame_elems, hipMemcpyHostToDevice, c->stream));
     base.mask = c->d_mask;
-    base.k_min = (uint32_t)k_min;
+    base.k_min = (uint32_t)m.k_min;
   }
-  const size_t n_win = (size_t)g.n_rows * g.n_cols;
-  const size_t frame_bytes = (size_t)H * W * elem_size(dev_dtype);
-  LSPIV_TRY(stage_ring(c, frame_bytes));
-  const int64_t fpb = std::max<int64_t>(1, (int64_t)(c->pinned_cap / frame_bytes));
-  const bool src_pinned = dtype != LSPIV_F64 && is_pinned(frames);
-  const int64_t align = (nw || filter || mask) ? 1 : std::max(1, chunk_alignment_for(wy, wx, (int64_t)n_win));   // (the search-area and the filtered kernels are per-pair)
+  const int64_t align = m.per_pair() ? 1 : std::max(1, chunk_alignment_for(wy, wx, (int64_t)h.n_win));
   // "stack" signal mode scores a window position over ALL frames of the chunk: one launch once everything is resident
   const bool whole_chunk_only = g_opt_signal_mode.load() == 1 && signal_threshold >= 0.0f;
   int64_t launched = 0;   // pairs [0, launched) have been issued
-  int batch = 0;
   TraceSpan span;
   trace_begin(&span, LSPIV_TRACE_PIV_HOST, c->stream);
+  int batch = 0;
   for (int64_t f0 = 0; f0 < T; ++batch) {
-    const int64_t f1 = std::min<int64_t>(T, f0 + fpb);
-    LSPIV_TRY(stage_frames(c, batch, c->d_frames, frames, dtype, src_pinned, (size_t)H * W, f0, f1, signal_threshold));
+    const int64_t f1 = std::min<int64_t>(T, f0 + h.frames_per_batch);
+    LSPIV_TRY(stage_frames(c, batch, c->d_frames, frames, dtype, h.src_pinned, h.frame_elems, f0, f1, signal_threshold));
     HIP_TRY(hipStreamWaitEvent(c->stream, c->staged[batch & 1], 0));
     // pairs whose two frames are resident: [0, f1 - 1); issue up to the last anchor below that (everything at the end)
     int64_t p1 = f1 - 1;
@@ -881,17 +891,13 @@ static int piv_pairs_host(const void* frames, int dtype, int64_t T, int64_t H, i
     const int64_t p0 = launched;
     if (p1 > p0) {
       lspiv::PivParams p = base;
-      p.frames = (const char*)c->d_frames + (size_t)p0 * frame_bytes;
+      p.frames = (const char*)c->d_frames + (size_t)p0 * h.frame_bytes;
       p.pair_offset = pair_offset + p0;
       p.n_pairs = (uint32_t)(p1 - p0);
-      p.n_tiles = (uint32_t)((p1 - p0) * n_win);
-      p.u = c->d_out + p0 * n_win;
-      p.v = c->d_out + n_tiles + p0 * n_win;
-      p.cmax = c->d_out + 2 * n_tiles + p0 * n_win;
-      p.s2n = c->d_out + 3 * n_tiles + p0 * n_win;
-      p.planes = corr_planes ? c->d_planes + (size_t)p0 * n_win * wy * wx : nullptr;
-      LSPIV_TRY(apply_signal_mode(c, &p, dev_dtype, c->stream));
-      LSPIV_TRY(dispatch(p, dev_dtype, false, c->stream, filter));
+      p.n_tiles = (uint32_t)((p1 - p0) * h.n_win);
+      set_results(&p, c->d_out, h.n_tiles, (size_t)p0 * h.n_win, corr_planes ? c->d_planes : nullptr, (size_t)wy * wx);
+      LSPIV_TRY(apply_signal_mode(c, &p, h.dev_dtype, c->stream));
+      LSPIV_TRY(dispatch(p, h.dev_dtype, false, c->stream, m.filter));
       LSPIV_TRY(apply_v_sign(p.v, (int64_t)p.n_tiles, c->stream));
       launched = p1;
     }
@@ -902,15 +908,9 @@ static int piv_pairs_host(const void* frames, int dtype, int64_t T, int64_t H, i
     // (masks.hip, scale_velocity_kernel: bit for bit what numpy computes for a python-float resolution, tests/test_masks.py)
     LSPIV_TRY(ensure(&c->d_scratch, &c->scratch_cap, (size_t)(T - 1) * sizeof(double)));
     HIP_TRY(hipMemcpyAsync(c->d_scratch, dt, (size_t)(T - 1) * sizeof(double), hipMemcpyHostToDevice, c->stream));
-    LSPIV_TRY(launch_status(lspiv::launch_scale_velocity(c->d_out, T - 1, (int64_t)n_win, (float)res_x, (float)res_y, (const double*)c->d_scratch, c->stream)));
+    LSPIV_TRY(launch_status(lspiv::launch_scale_velocity(c->d_out, T - 1, (int64_t)h.n_win, (float)res_x, (float)res_y, (const double*)c->d_scratch, c->stream)));
   }
-  const size_t ob = n_tiles * sizeof(float);
-  HIP_TRY(hipMemcpyAsync(u, c->d_out, ob, hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(hipMemcpyAsync(v, c->d_out + n_tiles, ob, hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(hipMemcpyAsync(corr_max, c->d_out + 2 * n_tiles, ob, hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(hipMemcpyAsync(s2n, c->d_out + 3 * n_tiles, ob, hipMemcpyDeviceToHost, c->stream));
-  if (corr_planes)
-    HIP_TRY(hipMemcpyAsync(corr_planes, c->d_planes, n_tiles * wy * wx * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+  LSPIV_TRY(results_to_host(h, u, v, corr_max, s2n, corr_planes, (size_t)wy * wx));
   trace_end(&span, c->stream);
   HIP_TRY(hipStreamSynchronize(c->stream));
   return LSPIV_OK;
@@ -919,37 +919,37 @@ static int piv_pairs_host(const void* frames, int dtype, int64_t T, int64_t H, i
 int lspiv_piv_pairs_at(const void* frames, int dtype, int64_t T, int64_t H, int64_t W, int wy, int wx, int oy, int ox,
                        float signal_threshold, int64_t pair_offset, float* u, float* v, float* corr_max, float* s2n,
                        float* corr_planes) {
-  return piv_pairs_host(frames, dtype, T, H, W, wy, wx, 0, oy, ox, signal_threshold, pair_offset, u, v, corr_max, s2n, corr_planes, nullptr, 1.0, 1.0);
+  return piv_pairs_host(frames, dtype, T, H, W, wy, wx, oy, ox, signal_threshold, pair_offset, u, v, corr_max, s2n, corr_planes, {});
 }
 
 int lspiv_piv_spof_pairs_at(const void* frames, int dtype, int64_t T, int64_t H, int64_t W, int wy, int wx, int oy, int ox,
                             float signal_threshold, int64_t pair_offset, float* u, float* v, float* corr_max, float* s2n,
                             float* corr_planes) {
   LSPIV_TRY(check_spof(wy, wx));
-  return piv_pairs_host(frames, dtype, T, H, W, wy, wx, 0, oy, ox, signal_threshold, pair_offset, u, v, corr_max, s2n, corr_planes, nullptr, 1.0, 1.0,
-                        LSPIV_FILTER_SPOF);
+  return piv_pairs_host(frames, dtype, T, H, W, wy, wx, oy, ox, signal_threshold, pair_offset, u, v, corr_max, s2n, corr_planes,
+                        {.filter = LSPIV_FILTER_SPOF});
 }
 
 int lspiv_piv_masked_pairs_at(const void* frames, int dtype, int64_t T, int64_t H, int64_t W, int wy, int wx, int oy, int ox,
                               const uint8_t* mask, int64_t k_min, float signal_threshold, int64_t pair_offset, float* u, float* v,
                               float* corr_max, float* s2n, float* corr_planes) {
   LSPIV_TRY(check_masked(wy, wx, mask, k_min));
-  return piv_pairs_host(frames, dtype, T, H, W, wy, wx, 0, oy, ox, signal_threshold, pair_offset, u, v, corr_max, s2n, corr_planes, nullptr, 1.0, 1.0,
-                        0, mask, k_min);
+  return piv_pairs_host(frames, dtype, T, H, W, wy, wx, oy, ox, signal_threshold, pair_offset, u, v, corr_max, s2n, corr_planes,
+                        {.mask = mask, .k_min = k_min});
 }
 
 int lspiv_piv_search_pairs_at(const void* frames, int dtype, int64_t T, int64_t H, int64_t W, int say, int sax, int wy, int wx, int oy,
                               int ox, float signal_threshold, int64_t pair_offset, float* u, float* v, float* corr_max, float* s2n,
                               float* corr_planes) {
   LSPIV_TRY(check_search(say, sax, wy, wx));
-  return piv_pairs_host(frames, dtype, T, H, W, say, sax, wy, oy, ox, signal_threshold, pair_offset, u, v, corr_max, s2n, corr_planes, nullptr, 1.0, 1.0);
+  return piv_pairs_host(frames, dtype, T, H, W, say, sax, oy, ox, signal_threshold, pair_offset, u, v, corr_max, s2n, corr_planes, {.nw = wy});
 }
 
 int lspiv_piv_velocity_at(const void* frames, int dtype, int64_t T, int64_t H, int64_t W, int wy, int wx, int oy, int ox,
                           float signal_threshold, int64_t pair_offset, double res_x, double res_y, const double* dt, float* v_x, float* v_y,
                           float* corr_max, float* s2n) {
   if (!dt) return fail(LSPIV_EINVAL, "dt is NULL");
-  return piv_pairs_host(frames, dtype, T, H, W, wy, wx, 0, oy, ox, signal_threshold, pair_offset, v_x, v_y, corr_max, s2n, nullptr, dt, res_x, res_y);
+  return piv_pairs_host(frames, dtype, T, H, W, wy, wx, oy, ox, signal_threshold, pair_offset, v_x, v_y, corr_max, s2n, nullptr, {}, dt, res_x, res_y);
 }
 
 int lspiv_piv_pairs(const void* frames, int dtype, int64_t T, int64_t H, int64_t W, int wy, int wx, int oy, int ox,

@@ -12,6 +12,7 @@ No CPU fallback: every function needs liblspiv_hip.so and a gfx950 device.
 from __future__ import annotations
 
 import ctypes as C
+from types import SimpleNamespace
 from typing import Optional, Tuple
 
 import numpy as np
@@ -34,130 +35,23 @@ def _check_args(window_size, overlap, search_area_size, normalize, engine):
     return window.search_spec(window_size, search_area_size)   # ValueError for an unsupported combination
 
 
-def piv_pairs(imgs, window_size=(32, 32), overlap=(16, 16), signal_threshold: Optional[float] = None,
-              return_planes: bool = False, pair_offset: int = 0, out=None, scale=None, search_area_size=None):
-    """Fused PIV of every consecutive frame pair of ``imgs`` (T, H, W).
+def _to_velocity(disp: np.ndarray, res, dt: np.ndarray, out: np.ndarray) -> None:
+    """``(disp * res / dt).astype(float32)`` of ffpiv.py:418-419 with the same arithmetic (the product in whatever type numpy
+    gives it, the division in float64, one rounding to float32) but without the two float64 temporaries of the one-liner, into
+    ``out`` (``disp`` itself, or a time slice of a run's result array).  What every mode without a fused scaling entry point does."""
+    np.divide(disp * res, dt, out=out, dtype=np.float64, casting="same_kind")
 
-    Returns ``(u, v, corr_max, s2n[, planes])``: float32 arrays (T-1, n_rows, n_cols); u, v in
-    pixels (u = column shift, v = row shift).  Replaces pyorc/velocimetry/ffpiv.py:446-474.
-    ``pair_offset``: index of the chunk's first pair in the whole stack (``lspiv_piv_pairs_at``); chunks that start on
-    multiples of ``window.chunk_alignment`` reproduce the whole-stack result bit for bit.
-    ``out``: four C-contiguous float32 arrays (T-1, n_rows, n_cols) that receive u, v, corr_max, s2n (e.g. time slices of the
-    arrays of a whole run: the caller's chunk loop then needs no concatenation); they are what is returned.
-    ``scale = (res_x, res_y, dt)``: u, v come back in metres per second, ``(u * res_x / dt[:, None, None]).astype(float32)`` (ffpiv.py:
-    418-419) computed on the device before the results cross PCIe -- float32 product, float64 division, one rounding: numpy's own
-    arithmetic for PYTHON-FLOAT resolutions (the caller checks that, :func:`device_scaling_is_numpys`); ``dt``: (T-1,) float64 seconds.
-    ``search_area_size``: None / the window size (today's path), or a larger square search area of 16, 32 or 64 px in which the even
-    square window of frame t is searched in frame t+1 (INTEGRATION.md, "Extended search area"): the grid, ``overlap`` and the planes
-    (``say x sax`` each) are then those of the search area.  ``window_size`` may also be a ``window.SearchWindow``.
-    """
-    if isinstance(window_size, window.MultiPassWindow):   # a chain of passes (INTEGRATION.md section 2d): the final grid is this call's
-        if search_area_size is not None and tuple(int(q) for q in search_area_size) != tuple(window_size):
-            raise NotImplementedError("coarse_passes together with a search_area_size larger than the window is not implemented")
-        return piv_multipass(imgs, window_size, signal_threshold, return_planes, pair_offset, out=out, scale=scale)
-    if isinstance(window_size, window.FilteredWindow):   # a spectral filter (INTEGRATION.md section 2g): the filtered per-pair entry points
-        if search_area_size is not None and tuple(int(q) for q in search_area_size) != tuple(window_size):
-            raise NotImplementedError("spectral_filter together with a search_area_size larger than the window is not implemented")
-        return piv_pairs_filtered(imgs, window_size, overlap, window_size.spectral_filter, signal_threshold, return_planes, pair_offset, out=out,
-                                  scale=scale)
-    if isinstance(window_size, window.MaskedWindow):   # an image mask (INTEGRATION.md section 2h): the masked per-pair entry points
-        if search_area_size is not None and tuple(int(q) for q in search_area_size) != tuple(window_size):
-            raise NotImplementedError("image_mask together with a search_area_size larger than the window is not implemented")
-        return piv_pairs_masked(imgs, window_size, overlap, None, window_size.mask_coverage_min, signal_threshold, return_planes, pair_offset,
-                                out=out, scale=scale)
-    window_size = window.search_spec(window_size, search_area_size)
-    search = isinstance(window_size, window.SearchWindow)
-    lib = _lib.load()
-    _lib.require_device()
-    a = imgs if is_device(imgs) else _lib.as_frames(imgs)
-    T, H, W = a.shape
-    n_rows, n_cols = window.get_array_shape((H, W), window_size, overlap)
-    if T < 2 or n_rows < 1 or n_cols < 1:
-        raise ValueError(f"need >= 2 frames at least one window large, got {a.shape} for window {window_size}")
-    P = T - 1
-    if out is not None:
-        out = _check_out(out, (P, n_rows, n_cols))
-    dt = None
-    if scale is not None:
-        if return_planes:
-            raise ValueError("scale and return_planes exclude each other")
-        dt = np.ascontiguousarray(scale[2], dtype=np.float64).reshape(-1)
-        if dt.shape != (P,):
-            raise ValueError(f"scale: dt must have one entry per frame pair ({P}), got shape {dt.shape}")
-    if is_device(a):   # HBM-resident stack: no staging, one launch, only the result block crosses PCIe
-        return _piv_pairs_device(a, window_size, overlap, signal_threshold, return_planes, pair_offset, n_rows, n_cols, out,
-                                 None if scale is None else (float(scale[0]), float(scale[1]), dt))
-    if out is None:
-        out = [np.empty((P, n_rows, n_cols), dtype=np.float32) for _ in range(4)]
-    planes = None
+
+def _check_scale(scale, return_planes, P):
+    """``scale = (res_x, res_y, dt)`` checked: ``dt`` as ``(P,)`` float64; None without a scale."""
+    if scale is None:
+        return None
     if return_planes:
-        planes = np.empty((P, n_rows * n_cols, window_size[0], window_size[1]), dtype=np.float32)
-    if search:
-        n = window_size.window
-        _lib.check(lib.lspiv_piv_search_pairs_at(_lib.ptr(a), _lib.DTYPE_CODES[a.dtype], T, H, W, window_size[0], window_size[1], n[0], n[1],
-                                                 overlap[0], overlap[1], _sig(signal_threshold), int(pair_offset),
-                                                 _lib.ptr(out[0]), _lib.ptr(out[1]), _lib.ptr(out[2]), _lib.ptr(out[3]),
-                                                 _lib.ptr(planes) if planes is not None else None))
-        if scale is not None:   # no fused scaling entry point for this mode: numpy's own arithmetic (ffpiv.py:418-419)
-            for k in range(2):
-                np.divide(out[k] * scale[k], dt[:, None, None], out=out[k], dtype=np.float64, casting="same_kind")
-        return (*out, planes) if return_planes else tuple(out)
-    if scale is not None:
-        _lib.check(lib.lspiv_piv_velocity_at(_lib.ptr(a), _lib.DTYPE_CODES[a.dtype], T, H, W, window_size[0], window_size[1],
-                                             overlap[0], overlap[1], _sig(signal_threshold), int(pair_offset), float(scale[0]), float(scale[1]),
-                                             _lib.ptr(dt), _lib.ptr(out[0]), _lib.ptr(out[1]), _lib.ptr(out[2]), _lib.ptr(out[3])))
-        return tuple(out)
-    _lib.check(lib.lspiv_piv_pairs_at(_lib.ptr(a), _lib.DTYPE_CODES[a.dtype], T, H, W, window_size[0], window_size[1],
-                                      overlap[0], overlap[1], _sig(signal_threshold), int(pair_offset),
-                                      _lib.ptr(out[0]), _lib.ptr(out[1]), _lib.ptr(out[2]), _lib.ptr(out[3]),
-                                      _lib.ptr(planes) if planes is not None else None))
-    return (*out, planes) if return_planes else tuple(out)
-
-
-def device_scaling_is_numpys(res_x, res_y) -> bool:
-    """Is ``(u * res / dt).astype(float32)`` with THESE resolutions what the device computes (float32 product)?  numpy multiplies a
-    float32 array by a Python float in float32; by a numpy float64 scalar in float64 (numpy >= 2) -- then the host keeps numpy's own
-    arithmetic.  (``np.float64`` is a subclass of ``float``: the test is on the exact type.)"""
-    return type(res_x) in (float, int, np.float32) and type(res_y) in (float, int, np.float32)
-
-
-def _piv_pairs_device(a, window_size, overlap, signal_threshold, return_planes, pair_offset, n_rows, n_cols, out=None, scale=None):
-    from .device import DeviceFrames
-
-    lib = _lib.load()
-    T, H, W = a.shape
-    P, n_win = T - 1, n_rows * n_cols
-    d_out = DeviceFrames.empty((4, P, n_win), np.float32)
-    d_planes = DeviceFrames.empty((P * n_win, window_size[0], window_size[1]), np.float32) if return_planes else None
-    if isinstance(window_size, window.SearchWindow):
-        n = window_size.window
-        _lib.check(lib.lspiv_piv_search_pairs_dev_at(a.c_ptr, a.dtype_code, T, H, W, window_size[0], window_size[1], n[0], n[1],
-                                                     overlap[0], overlap[1], _sig(signal_threshold), int(pair_offset), d_out.c_ptr,
-                                                     d_planes.c_ptr if d_planes is not None else None, None))
-    else:
-        _lib.check(lib.lspiv_piv_pairs_dev_at(a.c_ptr, a.dtype_code, T, H, W, window_size[0], window_size[1], overlap[0], overlap[1],
-                                              _sig(signal_threshold), int(pair_offset), d_out.c_ptr,
-                                              d_planes.c_ptr if d_planes is not None else None, None))
-    if scale is not None:  # px / frame -> m / s in place on the [u | v] blocks (lspiv_scale_velocity_dev: the same kernel as the host entry point's)
-        _lib.check(lib.lspiv_scale_velocity_dev(d_out.c_ptr, P, n_win, scale[0], scale[1], _lib.ptr(scale[2]), None))
-    out = _results_to_host(d_out, P, n_rows, n_cols, out)
-    if return_planes:
-        return (*out, d_planes.to_host().reshape(P, n_win, window_size[0], window_size[1]))
-    return out
-
-
-# ---- multi-pass PIV (INTEGRATION.md section 2d) ---------------------------------------------------------------------------------------
-def _device_stack(imgs, signal_threshold):
-    """``imgs`` as a stack in HBM: a ``DeviceFrames`` as it is, a host stack the way the PIV host entry points bring it in (float64
-    narrowed to float32 while it is staged)."""
-    from .device import DeviceFrames
-
-    if is_device(imgs):
-        return imgs
-    a = _lib.as_frames(imgs)
-    d = DeviceFrames.empty(a.shape, DeviceFrames.device_dtype(a.dtype))
-    d.upload(0, a, signal_threshold)
-    return d
+        raise ValueError("scale and return_planes exclude each other")
+    dt = np.ascontiguousarray(scale[2], dtype=np.float64).reshape(-1)
+    if dt.shape != (P,):
+        raise ValueError(f"scale: dt must have one entry per frame pair ({P}), got shape {dt.shape}")
+    return dt
 
 
 def _check_out(out, shape):
@@ -181,24 +75,48 @@ def _results_to_host(d_out, P, n_rows, n_cols, out=None):
     return tuple(np.ascontiguousarray(res[k]) for k in range(4))
 
 
-def piv_pairs_filtered(imgs, window_size=(32, 32), overlap=(16, 16), spectral_filter="spof", signal_threshold: Optional[float] = None,
-                       return_planes: bool = False, pair_offset: int = 0, out=None, scale=None):
-    """SPOF phase-filtered PIV of every consecutive frame pair of ``imgs`` (INTEGRATION.md section 2g): :func:`piv_pairs` with every bin R
-    of the cross spectrum replaced by R / sqrt(|R|) before the inverse transform ("robust phase correlation"), for imagery whose static
-    or slow background outweighs the tracers.  Returns ``(u, v, corr_max, s2n[, planes])`` like :func:`piv_pairs`; ``corr_max`` is the
-    maximum of the filtered plane (lower than an NCC peak), ``s2n`` its ratio to the mean of the clipped plane.  ``window_size``: square,
-    16, 32 or 64 px.  ``spectral_filter``: ``"spof"``; None / ``"none"`` is :func:`piv_pairs`.  Pair-local, one window per job: every
-    chunking gives the same bits (``pair_offset`` is accepted for symmetry); no float64 rescue pass.  ``out`` / ``scale`` as in
-    :func:`piv_pairs` (the scaling is numpy's own arithmetic on the host).  Host stacks and ``DeviceFrames``."""
+def _device_stack(imgs, signal_threshold):
+    """``imgs`` as a stack in HBM: a ``DeviceFrames`` as it is, a host stack the way the PIV host entry points bring it in (float64
+    narrowed to float32 while it is staged)."""
     from .device import DeviceFrames
 
-    flt = window.spectral_filter_spec(spectral_filter)
-    if isinstance(window_size, window.FilteredWindow):
-        flt = flt or window_size.spectral_filter
-    if flt is None:
-        return piv_pairs(imgs, tuple(window_size), overlap, signal_threshold, return_planes, pair_offset, out=out, scale=scale)
-    ws = window.spectral_filter_supported(window_size)          # ValueError naming the sizes
-    ov = (int(overlap[0]), int(overlap[1]))
+    if is_device(imgs):
+        return imgs
+    a = _lib.as_frames(imgs)
+    d = DeviceFrames.empty(a.shape, DeviceFrames.device_dtype(a.dtype))
+    d.upload(0, a, signal_threshold)
+    return d
+
+
+def _per_window_input(name, value, grid, dtype):
+    """``shift`` / ``nodes`` of a pass: ``(P, n_rows, n_cols, 2)`` of ``dtype``, checked against ``grid`` and brought into HBM."""
+    from .device import DeviceFrames
+
+    arr = np.ascontiguousarray(value, dtype=dtype)
+    if arr.shape != (*grid, 2):
+        raise ValueError(f"{name} must have shape {(*grid, 2)}, got {arr.shape}")
+    d = DeviceFrames.empty((1, 1, arr.nbytes), np.uint8)
+    _lib.check(_lib.load().lspiv_memcpy_h2d(d.c_ptr, _lib.ptr(arr), arr.nbytes))
+    return d
+
+
+def _run_pairs(imgs, ws, ov, signal_threshold, return_planes, pair_offset, out, scale, entry, args, fused=False, extra=None, aux=None):
+    """The body every per-pair entry point shares: stack -> grid -> ``out`` and ``scale`` checked -> results (and planes) allocated on the
+    stack's side, host or HBM -> ONE library call -> results on the host -> scaling.  A mode supplies only what differs:
+
+    ``entry``: the names of its host-pointer and its device-pointer entry point (a ``DeviceFrames`` takes the second; None: no such side);
+    ``args(c)``: the call's arguments from ``c.frames`` (pointer, dtype code, T, H, W), ``c.at`` (signal threshold, pair offset), ``c.res``
+    (four host pointers, or the one of the [u | v | corr | s2n] block in HBM), ``c.planes``, ``c.extra``, ``c.aux`` -- pointers on the
+    stack's side, None where there is nothing -- and ``c.dt`` (host); the device side's trailing stream is added here;
+    ``fused``: ``scale`` is applied by the call itself (host) or by ``lspiv_scale_velocity_dev`` on the block in HBM (device: the same kernel
+    as the host entry point's) -- else by numpy's own arithmetic on the host (:func:`_to_velocity`);
+    ``extra(grid)``: the mode's extra input (mask, shift, nodes) for ``grid = (P, n_rows, n_cols)`` on the stack's side, an ndarray or a
+    ``DeviceFrames``, or None;
+    ``aux``: the dtype of a per-window output ``(P, n_rows, n_cols, 2)`` the call fills besides the results (the chain's offsets).
+
+    Returns ``(u, v, corr_max, s2n[, planes][, aux])``."""
+    from .device import DeviceFrames
+
     lib = _lib.load()
     _lib.require_device()
     a = imgs if is_device(imgs) else _lib.as_frames(imgs)
@@ -209,34 +127,109 @@ def piv_pairs_filtered(imgs, window_size=(32, 32), overlap=(16, 16), spectral_fi
     P, n_win = T - 1, n_rows * n_cols
     if out is not None:
         out = _check_out(out, (P, n_rows, n_cols))
-    dt = None
-    if scale is not None:
-        if return_planes:
-            raise ValueError("scale and return_planes exclude each other")
-        dt = np.ascontiguousarray(scale[2], dtype=np.float64).reshape(-1)
-        if dt.shape != (P,):
-            raise ValueError(f"scale: dt must have one entry per frame pair ({P}), got shape {dt.shape}")
-    planes = None
-    if is_device(a):
-        d_out = DeviceFrames.empty((4, P, n_win), np.float32)
-        d_planes = DeviceFrames.empty((P * n_win, ws[0], ws[1]), np.float32) if return_planes else None
-        _lib.check(lib.lspiv_piv_spof_pairs_dev_at(a.c_ptr, a.dtype_code, T, H, W, ws[0], ws[1], ov[0], ov[1], _sig(signal_threshold),
-                                                   int(pair_offset), d_out.c_ptr, d_planes.c_ptr if d_planes is not None else None, None))
-        res = _results_to_host(d_out, P, n_rows, n_cols, out)
-        if return_planes:
-            planes = d_planes.to_host().reshape(P, n_win, ws[0], ws[1])
+    dt = _check_scale(scale, return_planes, P)
+    dev = is_device(a)
+    x = extra((P, n_rows, n_cols)) if extra is not None else None
+    if aux is not None:
+        aux = np.empty((P, n_rows, n_cols, 2), dtype=aux)
+    if dev:   # HBM-resident stack: no staging, one call, only the result block crosses PCIe
+        res = DeviceFrames.empty((4, P, n_win), np.float32)
+        planes = DeviceFrames.empty((P * n_win, ws[0], ws[1]), np.float32) if return_planes else None
+        d_aux = DeviceFrames.empty((1, 1, aux.nbytes), np.uint8) if aux is not None else None
+        frames, res_ptrs, ptr = (a.c_ptr, a.dtype_code), (res.c_ptr,), lambda q: None if q is None else q.c_ptr
     else:
         res = out if out is not None else [np.empty((P, n_rows, n_cols), dtype=np.float32) for _ in range(4)]
+        planes = np.empty((P, n_win, ws[0], ws[1]), dtype=np.float32) if return_planes else None
+        d_aux = aux
+        frames, res_ptrs, ptr = (_lib.ptr(a), _lib.DTYPE_CODES[a.dtype]), tuple(_lib.ptr(r) for r in res), lambda q: None if q is None else _lib.ptr(q)
+    c = SimpleNamespace(frames=(*frames, T, H, W), at=(_sig(signal_threshold), int(pair_offset)), res=res_ptrs, planes=ptr(planes),
+                        extra=ptr(x), aux=ptr(d_aux), dt=None if dt is None else _lib.ptr(dt))
+    _lib.check(getattr(lib, entry[dev])(*args(c), *((None,) if dev else ())))
+    if dev:
+        if dt is not None and fused:  # px / frame -> m / s in place on the [u | v] blocks
+            _lib.check(lib.lspiv_scale_velocity_dev(res.c_ptr, P, n_win, float(scale[0]), float(scale[1]), c.dt, None))
+        res = _results_to_host(res, P, n_rows, n_cols, out)
         if return_planes:
-            planes = np.empty((P, n_win, ws[0], ws[1]), dtype=np.float32)
-        _lib.check(lib.lspiv_piv_spof_pairs_at(_lib.ptr(a), _lib.DTYPE_CODES[a.dtype], T, H, W, ws[0], ws[1], ov[0], ov[1],
-                                               _sig(signal_threshold), int(pair_offset), _lib.ptr(res[0]), _lib.ptr(res[1]), _lib.ptr(res[2]),
-                                               _lib.ptr(res[3]), _lib.ptr(planes) if planes is not None else None))
-        res = tuple(res)
-    if scale is not None:   # no fused scaling entry point for this mode: numpy's own arithmetic (ffpiv.py:418-419)
+            planes = planes.to_host().reshape(P, n_win, ws[0], ws[1])
+        if aux is not None:
+            _lib.check(lib.lspiv_memcpy_d2h(_lib.ptr(aux), d_aux.c_ptr, aux.nbytes))
+    if dt is not None and not fused:
         for k in range(2):
-            np.divide(res[k] * scale[k], dt[:, None, None], out=res[k], dtype=np.float64, casting="same_kind")
-    return (*res, planes) if return_planes else tuple(res)
+            _to_velocity(res[k], scale[k], dt[:, None, None], out=res[k])
+    return (*res, *((planes,) if return_planes else ()), *((aux,) if aux is not None else ()))
+
+
+# the window specs that carry a mode of their own through ``piv_pairs``: spec class -> (the keyword the messages name, that mode's call)
+_SPEC_MODES = {
+    window.MultiPassWindow: ("coarse_passes", lambda imgs, spec, overlap, *a, **kw: piv_multipass(imgs, spec, *a, **kw)),
+    window.FilteredWindow: ("spectral_filter", lambda imgs, spec, overlap, *a, **kw: piv_pairs_filtered(imgs, spec, overlap, spec.spectral_filter, *a, **kw)),
+    window.MaskedWindow: ("image_mask", lambda imgs, spec, overlap, *a, **kw: piv_pairs_masked(imgs, spec, overlap, None, spec.mask_coverage_min, *a, **kw)),
+}
+# ... and the specs whose ``scale`` is numpy's arithmetic on the host for a host stack: no fused scaling entry point
+_HOST_SCALED = (window.SearchWindow, *_SPEC_MODES)
+
+
+def piv_pairs(imgs, window_size=(32, 32), overlap=(16, 16), signal_threshold: Optional[float] = None,
+              return_planes: bool = False, pair_offset: int = 0, out=None, scale=None, search_area_size=None):
+    """Fused PIV of every consecutive frame pair of ``imgs`` (T, H, W).
+
+    Returns ``(u, v, corr_max, s2n[, planes])``: float32 arrays (T-1, n_rows, n_cols); u, v in
+    pixels (u = column shift, v = row shift).  Replaces pyorc/velocimetry/ffpiv.py:446-474.
+    ``pair_offset``: index of the chunk's first pair in the whole stack (``lspiv_piv_pairs_at``); chunks that start on
+    multiples of ``window.chunk_alignment`` reproduce the whole-stack result bit for bit.
+    ``out``: four C-contiguous float32 arrays (T-1, n_rows, n_cols) that receive u, v, corr_max, s2n (e.g. time slices of the
+    arrays of a whole run: the caller's chunk loop then needs no concatenation); they are what is returned.
+    ``scale = (res_x, res_y, dt)``: u, v come back in metres per second, ``(u * res_x / dt[:, None, None]).astype(float32)`` (ffpiv.py:
+    418-419) computed on the device before the results cross PCIe -- float32 product, float64 division, one rounding: numpy's own
+    arithmetic for PYTHON-FLOAT resolutions (the caller checks that, :func:`device_scaling_is_numpys`); ``dt``: (T-1,) float64 seconds.
+    ``search_area_size``: None / the window size (today's path), or a larger square search area of 16, 32 or 64 px in which the even
+    square window of frame t is searched in frame t+1 (INTEGRATION.md, "Extended search area"): the grid, ``overlap`` and the planes
+    (``say x sax`` each) are then those of the search area.  ``window_size`` may also be a ``window.SearchWindow``.
+    """
+    mode = _SPEC_MODES.get(type(window_size))
+    if mode is not None:   # a chain of passes, a spectral filter, an image mask (INTEGRATION.md sections 2d, 2g, 2h): the final grid is this call's
+        if search_area_size is not None and tuple(int(q) for q in search_area_size) != tuple(window_size):
+            raise NotImplementedError(f"{mode[0]} together with a search_area_size larger than the window is not implemented")
+        return mode[1](imgs, window_size, overlap, signal_threshold, return_planes, pair_offset, out=out, scale=scale)
+    ws = window.search_spec(window_size, search_area_size)
+    search, dev = isinstance(ws, window.SearchWindow), is_device(imgs)
+    if search:
+        entry = ("lspiv_piv_search_pairs_at", "lspiv_piv_search_pairs_dev_at")
+        args = lambda c: (*c.frames, *ws, *ws.window, *overlap, *c.at, *c.res, c.planes)  # noqa: E731
+    elif scale is not None and not dev:
+        entry = ("lspiv_piv_velocity_at",)
+        args = lambda c: (*c.frames, *ws, *overlap, *c.at, float(scale[0]), float(scale[1]), c.dt, *c.res)  # noqa: E731
+    else:
+        entry = ("lspiv_piv_pairs_at", "lspiv_piv_pairs_dev_at")
+        args = lambda c: (*c.frames, *ws, *overlap, *c.at, *c.res, c.planes)  # noqa: E731
+    return _run_pairs(imgs, ws, overlap, signal_threshold, return_planes, pair_offset, out, scale, entry, args, fused=dev or not search)
+
+
+def device_scaling_is_numpys(res_x, res_y) -> bool:
+    """Is ``(u * res / dt).astype(float32)`` with THESE resolutions what the device computes (float32 product)?  numpy multiplies a
+    float32 array by a Python float in float32; by a numpy float64 scalar in float64 (numpy >= 2) -- then the host keeps numpy's own
+    arithmetic.  (``np.float64`` is a subclass of ``float``: the test is on the exact type.)"""
+    return type(res_x) in (float, int, np.float32) and type(res_y) in (float, int, np.float32)
+
+
+def piv_pairs_filtered(imgs, window_size=(32, 32), overlap=(16, 16), spectral_filter="spof", signal_threshold: Optional[float] = None,
+                       return_planes: bool = False, pair_offset: int = 0, out=None, scale=None):
+    """SPOF phase-filtered PIV of every consecutive frame pair of ``imgs`` (INTEGRATION.md section 2g): :func:`piv_pairs` with every bin R
+    of the cross spectrum replaced by R / sqrt(|R|) before the inverse transform ("robust phase correlation"), for imagery whose static
+    or slow background outweighs the tracers.  Returns ``(u, v, corr_max, s2n[, planes])`` like :func:`piv_pairs`; ``corr_max`` is the
+    maximum of the filtered plane (lower than an NCC peak), ``s2n`` its ratio to the mean of the clipped plane.  ``window_size``: square,
+    16, 32 or 64 px.  ``spectral_filter``: ``"spof"``; None / ``"none"`` is :func:`piv_pairs`.  Pair-local, one window per job: every
+    chunking gives the same bits (``pair_offset`` is accepted for symmetry); no float64 rescue pass.  ``out`` / ``scale`` as in
+    :func:`piv_pairs` (the scaling is numpy's own arithmetic on the host).  Host stacks and ``DeviceFrames``."""
+    flt = window.spectral_filter_spec(spectral_filter)
+    if isinstance(window_size, window.FilteredWindow):
+        flt = flt or window_size.spectral_filter
+    if flt is None:
+        return piv_pairs(imgs, tuple(window_size), overlap, signal_threshold, return_planes, pair_offset, out=out, scale=scale)
+    ws = window.spectral_filter_supported(window_size)          # ValueError naming the sizes
+    ov = (int(overlap[0]), int(overlap[1]))
+    return _run_pairs(imgs, ws, ov, signal_threshold, return_planes, pair_offset, out, scale,
+                      ("lspiv_piv_spof_pairs_at", "lspiv_piv_spof_pairs_dev_at"), lambda c: (*c.frames, *ws, *ov, *c.at, *c.res, c.planes))
 
 
 def piv_pairs_masked(imgs, window_size=(32, 32), overlap=(16, 16), image_mask=None, mask_coverage_min: float = 0.25,
@@ -250,55 +243,18 @@ def piv_pairs_masked(imgs, window_size=(32, 32), overlap=(16, 16), image_mask=No
     ``image_mask=None`` without one is :func:`piv_pairs`.  Pair-local, one window per job: every chunking gives the same bits
     (``pair_offset`` is accepted for symmetry); the float64 rescue pass follows as on the other per-pair paths.  ``out`` / ``scale`` as in
     :func:`piv_pairs` (the scaling is numpy's own arithmetic on the host).  Host stacks and ``DeviceFrames``."""
-    from .device import DeviceFrames
-
     if image_mask is None and not isinstance(window_size, window.MaskedWindow):
         window.coverage_spec(mask_coverage_min)
         return piv_pairs(imgs, tuple(window_size), overlap, signal_threshold, return_planes, pair_offset, out=out, scale=scale)
     a = imgs if is_device(imgs) else _lib.as_frames(imgs)
-    T, H, W = a.shape
-    spec = window.masked_spec(window_size, image_mask, mask_coverage_min, (H, W))   # ValueError: sizes, coverage, the mask's shape
+    spec = window.masked_spec(window_size, image_mask, mask_coverage_min, a.shape[1:])   # ValueError: sizes, coverage, the mask's shape
     ws = (int(spec[0]), int(spec[1]))
     ov = (int(overlap[0]), int(overlap[1]))
-    lib = _lib.load()
-    _lib.require_device()
-    n_rows, n_cols = window.get_array_shape((H, W), ws, ov)
-    if T < 2 or n_rows < 1 or n_cols < 1:
-        raise ValueError(f"need >= 2 frames at least one window large, got {a.shape} for window {ws}")
-    P, n_win = T - 1, n_rows * n_cols
-    if out is not None:
-        out = _check_out(out, (P, n_rows, n_cols))
-    dt = None
-    if scale is not None:
-        if return_planes:
-            raise ValueError("scale and return_planes exclude each other")
-        dt = np.ascontiguousarray(scale[2], dtype=np.float64).reshape(-1)
-        if dt.shape != (P,):
-            raise ValueError(f"scale: dt must have one entry per frame pair ({P}), got shape {dt.shape}")
-    planes = None
-    if is_device(a):
-        d_mask = spec.device_mask()      # one upload per device for all chunks of the call that made `spec`
-        d_out = DeviceFrames.empty((4, P, n_win), np.float32)
-        d_planes = DeviceFrames.empty((P * n_win, ws[0], ws[1]), np.float32) if return_planes else None
-        _lib.check(lib.lspiv_piv_masked_pairs_dev_at(a.c_ptr, a.dtype_code, T, H, W, ws[0], ws[1], ov[0], ov[1], d_mask.c_ptr, spec.k_min,
-                                                     _sig(signal_threshold), int(pair_offset), d_out.c_ptr,
-                                                     d_planes.c_ptr if d_planes is not None else None, None))
-        res = _results_to_host(d_out, P, n_rows, n_cols, out)
-        if return_planes:
-            planes = d_planes.to_host().reshape(P, n_win, ws[0], ws[1])
-    else:
-        res = out if out is not None else [np.empty((P, n_rows, n_cols), dtype=np.float32) for _ in range(4)]
-        if return_planes:
-            planes = np.empty((P, n_win, ws[0], ws[1]), dtype=np.float32)
-        _lib.check(lib.lspiv_piv_masked_pairs_at(_lib.ptr(a), _lib.DTYPE_CODES[a.dtype], T, H, W, ws[0], ws[1], ov[0], ov[1],
-                                                 _lib.ptr(spec.image_mask), spec.k_min, _sig(signal_threshold), int(pair_offset),
-                                                 _lib.ptr(res[0]), _lib.ptr(res[1]), _lib.ptr(res[2]), _lib.ptr(res[3]),
-                                                 _lib.ptr(planes) if planes is not None else None))
-        res = tuple(res)
-    if scale is not None:   # no fused scaling entry point for this mode: numpy's own arithmetic (ffpiv.py:418-419)
-        for k in range(2):
-            np.divide(res[k] * scale[k], dt[:, None, None], out=res[k], dtype=np.float64, casting="same_kind")
-    return (*res, planes) if return_planes else tuple(res)
+    # (the mask in HBM: one upload per device for all chunks of the call that made `spec`)
+    return _run_pairs(a, ws, ov, signal_threshold, return_planes, pair_offset, out, scale,
+                      ("lspiv_piv_masked_pairs_at", "lspiv_piv_masked_pairs_dev_at"),
+                      lambda c: (*c.frames, *ws, *ov, c.extra, spec.k_min, *c.at, *c.res, c.planes),
+                      extra=lambda grid: spec.device_mask() if is_device(a) else spec.image_mask)
 
 
 def piv_pairs_shifted(imgs, window_size=(32, 32), overlap=(16, 16), shift=None, signal_threshold: Optional[float] = None,
@@ -307,35 +263,14 @@ def piv_pairs_shifted(imgs, window_size=(32, 32), overlap=(16, 16), shift=None, 
     offset ``shift[pair, row, col] = (dy, dx)`` (int16, ``(T-1, n_rows, n_cols, 2)``; None: zeros), clamped by the kernel so that the
     window stays inside the frame.  Returns ``(u, v, corr_max, s2n[, planes])`` like :func:`piv_pairs`; u, v include the clamped offset.
     ``n`` in 16, 32, 64.  Host stacks and ``DeviceFrames``."""
-    from .device import DeviceFrames
-
     lib = _lib.load()
     _lib.require_device()
     ws, ov = (int(window_size[0]), int(window_size[1])), (int(overlap[0]), int(overlap[1]))
     if not lib.lspiv_shift_supported(ws[0], ws[1]):
         raise ValueError(f"window_size {ws} is not supported by the shifted pass: the window must be square and one of {window.SHIFT_WINDOWS}")
-    a = _device_stack(imgs, signal_threshold)
-    T, H, W = a.shape
-    n_rows, n_cols = window.get_array_shape((H, W), ws, ov)
-    if T < 2 or n_rows < 1 or n_cols < 1:
-        raise ValueError(f"need >= 2 frames at least one window large, got {a.shape} for window {ws}")
-    P, n_win = T - 1, n_rows * n_cols
-    d_shift = None
-    if shift is not None:
-        sh = np.ascontiguousarray(shift, dtype=np.int16)
-        if sh.shape != (P, n_rows, n_cols, 2):
-            raise ValueError(f"shift must have shape {(P, n_rows, n_cols, 2)}, got {sh.shape}")
-        d_shift = DeviceFrames.empty((1, 1, sh.size * 2), np.uint8)
-        _lib.check(lib.lspiv_memcpy_h2d(d_shift.c_ptr, _lib.ptr(sh), sh.nbytes))
-    d_out = DeviceFrames.empty((4, P, n_win), np.float32)
-    d_planes = DeviceFrames.empty((P * n_win, ws[0], ws[1]), np.float32) if return_planes else None
-    _lib.check(lib.lspiv_piv_shift_pairs_dev_at(a.c_ptr, a.dtype_code, T, H, W, ws[0], ws[1], ov[0], ov[1], _sig(signal_threshold),
-                                                int(pair_offset), d_shift.c_ptr if d_shift is not None else None, d_out.c_ptr,
-                                                d_planes.c_ptr if d_planes is not None else None, None))
-    res = _results_to_host(d_out, P, n_rows, n_cols)
-    if return_planes:
-        return (*res, d_planes.to_host().reshape(P, n_win, ws[0], ws[1]))
-    return res
+    return _run_pairs(_device_stack(imgs, signal_threshold), ws, ov, signal_threshold, return_planes, pair_offset, None, None,
+                      (None, "lspiv_piv_shift_pairs_dev_at"), lambda c: (*c.frames, *ws, *ov, *c.at, c.extra, *c.res, c.planes),
+                      extra=lambda grid: None if shift is None else _per_window_input("shift", shift, grid, np.int16))
 
 
 def predict_shift(u, v, dim_size, coarse, fine):
@@ -401,34 +336,15 @@ def piv_pairs_deformed(imgs, window_size=(32, 32), overlap=(16, 16), nodes=None,
     centre, :func:`predict_deform`; None: zeros) at 1 / 64 px, bilinearly, the edge replicated; then every ``n x n`` window of frame t
     meets the window at the SAME position of the warped frame.  Returns ``(u, v, corr_max, s2n[, planes])`` like :func:`piv_pairs`;
     u, v include the window's own node.  ``n`` in 16, 32, 64, one overlap for both axes.  Host stacks and ``DeviceFrames``."""
-    from .device import DeviceFrames
-
     lib = _lib.load()
     _lib.require_device()
     ws, ov = (int(window_size[0]), int(window_size[1])), (int(overlap[0]), int(overlap[1]))
     if not lib.lspiv_deform_supported(ws[0], ws[1]) or ov[0] != ov[1]:
         raise ValueError(f"window_size {ws}, overlap {ov} is not supported by the deformation pass: the window must be square and one of "
                          f"{window.DEFORM_WINDOWS}, at one overlap for both axes")
-    a = _device_stack(imgs, signal_threshold)
-    T, H, W = a.shape
-    n_rows, n_cols = window.get_array_shape((H, W), ws, ov)
-    if T < 2 or n_rows < 1 or n_cols < 1:
-        raise ValueError(f"need >= 2 frames at least one window large, got {a.shape} for window {ws}")
-    P, n_win = T - 1, n_rows * n_cols
-    nd = np.zeros((P, n_rows, n_cols, 2), dtype=np.int32) if nodes is None else np.ascontiguousarray(nodes, dtype=np.int32)
-    if nd.shape != (P, n_rows, n_cols, 2):
-        raise ValueError(f"nodes must have shape {(P, n_rows, n_cols, 2)}, got {nd.shape}")
-    d_nodes = DeviceFrames.empty((1, 1, nd.nbytes), np.uint8)
-    _lib.check(lib.lspiv_memcpy_h2d(d_nodes.c_ptr, _lib.ptr(nd), nd.nbytes))
-    d_out = DeviceFrames.empty((4, P, n_win), np.float32)
-    d_planes = DeviceFrames.empty((P * n_win, ws[0], ws[1]), np.float32) if return_planes else None
-    _lib.check(lib.lspiv_piv_deform_pairs_dev_at(a.c_ptr, a.dtype_code, T, H, W, ws[0], ws[1], ov[0], ov[1], _sig(signal_threshold),
-                                                 int(pair_offset), d_nodes.c_ptr, d_out.c_ptr,
-                                                 d_planes.c_ptr if d_planes is not None else None, None))
-    res = _results_to_host(d_out, P, n_rows, n_cols)
-    if return_planes:
-        return (*res, d_planes.to_host().reshape(P, n_win, ws[0], ws[1]))
-    return res
+    return _run_pairs(_device_stack(imgs, signal_threshold), ws, ov, signal_threshold, return_planes, pair_offset, None, None,
+                      (None, "lspiv_piv_deform_pairs_dev_at"), lambda c: (*c.frames, *ws, *ov, *c.at, c.extra, *c.res, c.planes),
+                      extra=lambda grid: _per_window_input("nodes", np.zeros((*grid, 2), np.int32) if nodes is None else nodes, grid, np.int32))
 
 
 def piv_multipass(imgs, passes, signal_threshold: Optional[float] = None, return_planes: bool = False, pair_offset: int = 0,
@@ -447,8 +363,6 @@ def piv_multipass(imgs, passes, signal_threshold: Optional[float] = None, return
     ``(u, v, corr_max, s2n, nodes)`` (nodes int32 ``(T-1, n_rows, n_cols, 2)`` = (v, u) in 1 / 128 px), composed from
     :func:`predict_deform` and :func:`piv_pairs_deformed`.  One pass roughly halves the median error of the final field on sheared
     flows; a second one neither helps nor hurts on the stacks tried."""
-    from .device import DeviceFrames
-
     spec = passes if isinstance(passes, window.MultiPassWindow) else None
     if spec is None:
         passes = [(int(n), int(o)) for n, o in passes]
@@ -461,56 +375,15 @@ def piv_multipass(imgs, passes, signal_threshold: Optional[float] = None, return
         raise ValueError("deform_passes given twice: passes is a MultiPassWindow already")
     passes = list(spec.passes)
     n_deform = spec.deform
-    lib = _lib.load()
-    _lib.require_device()
-    host = not is_device(imgs)
-    a = imgs if not host else _lib.as_frames(imgs)
-    T, H, W = a.shape
     n, ov = passes[-1]
-    n_rows, n_cols = window.get_array_shape((H, W), (n, n), (ov, ov))
-    if T < 2 or n_rows < 1 or n_cols < 1:
-        raise ValueError(f"need >= 2 frames at least one window large, got {a.shape} for window {(n, n)}")
-    P, n_win = T - 1, n_rows * n_cols
-    if out is not None:
-        out = _check_out(out, (P, n_rows, n_cols))
-    dt = None
-    if scale is not None:
-        if return_planes:
-            raise ValueError("scale and return_planes exclude each other")
-        dt = np.ascontiguousarray(scale[2], dtype=np.float64).reshape(-1)
-        if dt.shape != (P,):
-            raise ValueError(f"scale: dt must have one entry per frame pair ({P}), got shape {dt.shape}")
     arr = (C.c_int * (4 * len(passes)))(*[q for m, o in passes for q in (m, m, o, o)])
-    shift = np.empty((P, n_rows, n_cols, 2), dtype=np.int16) if (return_shift or return_passes) else None
-    planes = None
-    if host and not return_passes:
-        res = out if out is not None else [np.empty((P, n_rows, n_cols), dtype=np.float32) for _ in range(4)]
-        planes = np.empty((P, n_win, n, n), dtype=np.float32) if return_planes else None
-        _lib.check(lib.lspiv_piv_multipass_deform_at(_lib.ptr(a), _lib.DTYPE_CODES[a.dtype], T, H, W, len(passes), arr, n_deform,
-                                              _sig(signal_threshold), int(pair_offset), _lib.ptr(res[0]), _lib.ptr(res[1]), _lib.ptr(res[2]), _lib.ptr(res[3]),
-                                              _lib.ptr(planes) if planes is not None else None, _lib.ptr(shift) if shift is not None else None))
-        res = tuple(res)
-    else:
-        d = _device_stack(a, signal_threshold)
-        d_out = DeviceFrames.empty((4, P, n_win), np.float32)
-        d_planes = DeviceFrames.empty((P * n_win, n, n), np.float32) if return_planes else None
-        d_shift = DeviceFrames.empty((1, 1, shift.nbytes), np.uint8) if shift is not None else None
-        _lib.check(lib.lspiv_piv_multipass_deform_dev_at(d.c_ptr, d.dtype_code, T, H, W, len(passes), arr, n_deform, _sig(signal_threshold),
-                                                  int(pair_offset), d_out.c_ptr, d_planes.c_ptr if d_planes is not None else None,
-                                                  d_shift.c_ptr if d_shift is not None else None, None))
-        res = _results_to_host(d_out, P, n_rows, n_cols, out)
-        if return_planes:
-            planes = d_planes.to_host().reshape(P, n_win, n, n)
-        if shift is not None:
-            _lib.check(lib.lspiv_memcpy_d2h(_lib.ptr(shift), d_shift.c_ptr, shift.nbytes))
-    if scale is not None:   # no fused scaling entry point for this mode: numpy's own arithmetic (ffpiv.py:418-419)
-        for k in range(2):
-            np.divide(res[k] * scale[k], dt[:, None, None], out=res[k], dtype=np.float64, casting="same_kind")
-    ret = list(res)
-    if return_planes:
-        ret.append(planes)
-    if return_shift:
-        ret.append(shift)
+    d = _device_stack(imgs, signal_threshold) if return_passes else imgs      # (the diagnostic chain below runs on the stack in HBM)
+    ret = list(_run_pairs(d, (n, n), (ov, ov), signal_threshold, return_planes, pair_offset, out, scale,
+                          ("lspiv_piv_multipass_deform_at", "lspiv_piv_multipass_deform_dev_at"),
+                          lambda c: (*c.frames, len(passes), arr, n_deform, *c.at, *c.res, c.planes, c.aux),
+                          aux=np.int16 if (return_shift or return_passes) else None))
+    if return_passes and not return_shift:      # (the one call of the diagnostic writes its offsets all the same)
+        ret.pop()
     if return_passes:
         # the chain again, call by call on the stack in HBM, in the kernels' orientation (a v_sign of the per-call entry points is undone:
         # a negation is exact)
@@ -521,7 +394,7 @@ def piv_multipass(imgs, passes, signal_threshold: Optional[float] = None, return
                 u, v, cm, sn = piv_pairs(d, (m, m), (o, o), signal_threshold, pair_offset=pair_offset)
                 sh = None
             else:
-                sh = predict_shift(prev[0], prev[1], (H, W), passes[k - 1], (m, o))
+                sh = predict_shift(prev[0], prev[1], d.shape[1:], passes[k - 1], (m, o))
                 u, v, cm, sn = piv_pairs_shifted(d, (m, m), (o, o), sh, signal_threshold, pair_offset=pair_offset)
             if flip:
                 v = -v

@@ -514,11 +514,7 @@ def _merge_stats(per_device, devices) -> dict:
     return {k: (round(v, 6) if isinstance(v, float) else v) for k, v in out.items()}
 
 
-def _to_velocity(disp: np.ndarray, res, dt_chunk: np.ndarray, out: np.ndarray) -> None:
-    """``(disp * res / dt).astype(float32)`` of ffpiv.py:418-419 with the same arithmetic (the product in whatever type numpy
-    gives it, the division in float64, one rounding to float32) but without the two float64 temporaries of the one-liner, into
-    ``out`` (a time slice of the run's result array)."""
-    np.divide(disp * res, dt_chunk, out=out, dtype=np.float64, casting="same_kind")
+_to_velocity = piv._to_velocity      # (disp * res / dt).astype(float32) with numpy's own arithmetic, into a slice of the run's arrays
 
 
 # ---------------------------------------------------------------------------------------------------------------------------------
@@ -547,9 +543,8 @@ def _timestep_sink(n_pairs, n_workers, y, x, dt, res_x, res_y, window_size, over
     full = {k: np.empty((n_pairs, len(y), len(x)), dtype=np.float32) for k in ("s2n", "corr", "v_x", "v_y")}
     done = []
     px = [None] * n_workers            # per worker: scratch for a launch's u, v in pixels
-    # (the search-area, multi-pass and filtered entry points have no fused scaling: numpy's arithmetic on the host, the same bits)
-    on_device = piv.device_scaling_is_numpys(res_x, res_y) and not isinstance(window_size, (window.SearchWindow, window.MultiPassWindow,
-                                                                                              window.FilteredWindow, window.MaskedWindow))
+    # (the modes whose entry points have no fused scaling: numpy's arithmetic on the host, the same bits)
+    on_device = piv.device_scaling_is_numpys(res_x, res_y) and not isinstance(window_size, piv._HOST_SCALED)
 
     def launch(k, frames, p0, p1):
         p = p1 - p0
