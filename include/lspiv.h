@@ -739,6 +739,10 @@ int lspiv_debug_narrow(const double* frames, int64_t frame_elems, int64_t n_fram
  * conventions (forward exp(-2 pi i jk/n), inverse exp(+...), both unnormalised); in / out: host arrays of count*n
  * interleaved (re, im) float pairs; n = 8, 16, 32, 64 or any even length 6..62 (the sizes lspiv_kernel_kind maps to 6 / 8). */
 int lspiv_debug_fft(int n, int inverse, const float* in, float* out, int64_t count);
+/* The same with the twiddle path of n = 16, 32, 64 chosen by name: form 0 = what the kernels use (lspiv_debug_fft), 1 = twiddles as
+ * separate complex multiplies, 2 = twiddle scales folded into the next butterfly level (fft_regs.h).  Other n with form 1 / 2, or
+ * another form: LSPIV_EUNSUPPORTED. */
+int lspiv_debug_fft_form(int n, int form, int inverse, const float* in, float* out, int64_t count);
 /* Test hook (host only): how the time-walking kernels cut a chunk of n_pairs pairs that starts at absolute pair index
  * pair_offset into segments of seg_len pairs anchored at multiples of seg_len: pairs in the first segment, segment count. */
 int lspiv_debug_segments(int64_t n_pairs, int64_t pair_offset, int seg_len, int64_t* seg_first, int64_t* n_seg);

@@ -541,7 +541,7 @@ int lspiv_debug_segments(int64_t n_pairs, int64_t pair_offset, int seg_len, int6
   return LSPIV_OK;
 }
 
-int lspiv_debug_fft(int n, int inverse, const float* in, float* out, int64_t count) {
+static int debug_fft(int n, int form, int inverse, const float* in, float* out, int64_t count) {
   if (!in || !out || count < 1 || count > (1 << 20)) return fail(LSPIV_EINVAL, "bad argument");
   DeviceCtx* c;
   LSPIV_TRY(get_ctx(&c));
@@ -550,12 +550,17 @@ int lspiv_debug_fft(int n, int inverse, const float* in, float* out, int64_t cou
   float* d_in = (float*)c->d_scratch;
   float* d_out = d_in + (size_t)count * 2 * n;
   HIP_TRY(hipMemcpyAsync(d_in, in, bytes, hipMemcpyHostToDevice, c->stream));
-  hipError_t e = lspiv::launch_fft_debug(n, inverse != 0, d_in, d_out, (int)count, c->stream);
-  if (e == hipErrorInvalidValue) return fail(LSPIV_EUNSUPPORTED, "no register FFT of length %d", n);
+  hipError_t e = lspiv::launch_fft_debug_form(n, form, inverse != 0, d_in, d_out, (int)count, c->stream);
+  if (e == hipErrorInvalidValue) return fail(LSPIV_EUNSUPPORTED, "no register FFT of length %d in form %d", n, form);
   LSPIV_TRY(launch_status(e));
   HIP_TRY(hipMemcpyAsync(out, d_out, bytes, hipMemcpyDeviceToHost, c->stream));
   HIP_TRY(hipStreamSynchronize(c->stream));
   return LSPIV_OK;
+}
+int lspiv_debug_fft(int n, int inverse, const float* in, float* out, int64_t count) { return debug_fft(n, 0, inverse, in, out, count); }
+int lspiv_debug_fft_form(int n, int form, int inverse, const float* in, float* out, int64_t count) {
+  if (n < 1 || n > 64) return fail(LSPIV_EUNSUPPORTED, "no register FFT of length %d", n);
+  return debug_fft(n, form, inverse, in, out, count);
 }
 
 }  // extern "C"

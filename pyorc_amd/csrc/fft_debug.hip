@@ -1,26 +1,32 @@
 // Test hook: the register FFTs of fft_regs.h, one transform per thread, so the parity suite can hold every length the
 // PIV kernels instantiate (8, 16, 32, 64 and the prime-factor lengths P * 2^m) against numpy.fft directly.
+// FORM 0 is the transform the kernels use (fft_n); 1 and 2 are the un-folded and the folded twiddle path of 16 / 32 / 64 by name,
+// whichever of them the length has adopted, so that one library can hold the two against each other.
 #include "piv_fft_impl.h"
 
 namespace lspiv {
 
-template <int N, bool INV>
+template <bool INV, int FORM> __device__ __forceinline__ void fft_form(float (&r)[16], float (&i)[16]) { fft16<INV, false, FORM == 2>(r, i); }
+template <bool INV, int FORM> __device__ __forceinline__ void fft_form(float (&r)[32], float (&i)[32]) { fft32<INV, false, FORM == 2>(r, i); }
+template <bool INV, int FORM> __device__ __forceinline__ void fft_form(float (&r)[64], float (&i)[64]) { fft64<INV, false, FORM == 2>(r, i); }
+
+template <int N, bool INV, int FORM = 0>
 __global__ void fft_debug_kernel(const float* in, float* out, int count) {
   const int t = blockIdx.x * blockDim.x + threadIdx.x;
   if (t >= count) return;
   float r[N], i[N];
 #pragma unroll
   for (int j = 0; j < N; ++j) { r[j] = in[(size_t)t * 2 * N + 2 * j]; i[j] = in[(size_t)t * 2 * N + 2 * j + 1]; }
-  fft_n<INV>(r, i);
+  if constexpr (FORM == 0) fft_n<INV>(r, i); else fft_form<INV, FORM>(r, i);
 #pragma unroll
   for (int j = 0; j < N; ++j) { out[(size_t)t * 2 * N + 2 * j] = r[j]; out[(size_t)t * 2 * N + 2 * j + 1] = i[j]; }
 }
 
-template <int N>
+template <int N, int FORM = 0>
 static hipError_t launch_one(bool inverse, const float* in, float* out, int count, hipStream_t s) {
   const dim3 grid((count + 63) / 64), block(64);
-  if (inverse) hipLaunchKernelGGL((fft_debug_kernel<N, true>), grid, block, 0, s, in, out, count);
-  else hipLaunchKernelGGL((fft_debug_kernel<N, false>), grid, block, 0, s, in, out, count);
+  if (inverse) hipLaunchKernelGGL((fft_debug_kernel<N, true, FORM>), grid, block, 0, s, in, out, count);
+  else hipLaunchKernelGGL((fft_debug_kernel<N, false, FORM>), grid, block, 0, s, in, out, count);
   return hipGetLastError();
 }
 
@@ -33,6 +39,17 @@ hipError_t launch_fft_debug(int n, bool inverse, const float* in, float* out, in
 #define LSPIV_PFA_CASE(m) case m: return launch_one<m>(inverse, in, out, count, s);
     LSPIV_PFA_SIZES(LSPIV_PFA_CASE)
 #undef LSPIV_PFA_CASE
+    default: return hipErrorInvalidValue;
+  }
+}
+
+hipError_t launch_fft_debug_form(int n, int form, bool inverse, const float* in, float* out, int count, hipStream_t s) {
+  if (form == 0) return launch_fft_debug(n, inverse, in, out, count, s);
+  if (form != 1 && form != 2) return hipErrorInvalidValue;
+  switch (n) {
+    case 16: return form == 1 ? launch_one<16, 1>(inverse, in, out, count, s) : launch_one<16, 2>(inverse, in, out, count, s);
+    case 32: return form == 1 ? launch_one<32, 1>(inverse, in, out, count, s) : launch_one<32, 2>(inverse, in, out, count, s);
+    case 64: return form == 1 ? launch_one<64, 1>(inverse, in, out, count, s) : launch_one<64, 2>(inverse, in, out, count, s);
     default: return hipErrorInvalidValue;
   }
 }

@@ -66,14 +66,11 @@ __device__ __forceinline__ void twiddle64(float& xr, float& xi) {
 template <bool CLAMP>
 __device__ __forceinline__ float out01(float x) { return CLAMP ? __builtin_amdgcn_fmed3f(x, 0.0f, 1.0f) : x; }
 
-// radix-4 butterfly, natural-order outputs
-template <bool INV, bool CLAMP = false>
-__device__ __forceinline__ void bfly4(float& r0, float& i0, float& r1, float& i1,
-                                      float& r2, float& i2, float& r3, float& i3) {
-  float ar = r0 + r2, ai = i0 + i2;
-  float br = r0 - r2, bi = i0 - i2;
-  float cr = r1 + r3, ci = i1 + i3;
-  float dr = r1 - r3, di = i1 - i3;
+// second level of the radix-4 butterfly: a = x0 + x2, b = x0 - x2, c = x1 + x3, d = x1 - x3 in, natural-order outputs
+template <bool INV, bool CLAMP>
+__device__ __forceinline__ void bfly4_tail(float ar, float ai, float br, float bi, float cr, float ci, float dr, float di,
+                                           float& r0, float& i0, float& r1, float& i1,
+                                           float& r2, float& i2, float& r3, float& i3) {
   r0 = out01<CLAMP>(ar + cr); i0 = out01<CLAMP>(ai + ci);
   r2 = out01<CLAMP>(ar - cr); i2 = out01<CLAMP>(ai - ci);
   if constexpr (!INV) {  // X1 = b - i d, X3 = b + i d
@@ -85,12 +82,20 @@ __device__ __forceinline__ void bfly4(float& r0, float& i0, float& r1, float& i1
   }
 }
 
-// radix-8 butterfly on 8 values (natural order in, natural order out)
+// radix-4 butterfly, natural-order outputs
 template <bool INV, bool CLAMP = false>
-__device__ __forceinline__ void bfly8(float (&r)[8], float (&i)[8]) {
-  // even / odd radix-4
-  bfly4<INV>(r[0], i[0], r[2], i[2], r[4], i[4], r[6], i[6]);  // E0..E3 in slots 0,2,4,6
-  bfly4<INV>(r[1], i[1], r[3], i[3], r[5], i[5], r[7], i[7]);  // O0..O3 in slots 1,3,5,7
+__device__ __forceinline__ void bfly4(float& r0, float& i0, float& r1, float& i1,
+                                      float& r2, float& i2, float& r3, float& i3) {
+  float ar = r0 + r2, ai = i0 + i2;
+  float br = r0 - r2, bi = i0 - i2;
+  float cr = r1 + r3, ci = i1 + i3;
+  float dr = r1 - r3, di = i1 - i3;
+  bfly4_tail<INV, CLAMP>(ar, ai, br, bi, cr, ci, dr, di, r0, i0, r1, i1, r2, i2, r3, i3);
+}
+
+// radix-8 butterfly after its even / odd radix-4s: E0..E3 in slots 0,2,4,6 and O0..O3 in slots 1,3,5,7
+template <bool INV, bool CLAMP>
+__device__ __forceinline__ void bfly8_tail(float (&r)[8], float (&i)[8]) {
   // O1 *= W8^1, O2 *= W8^2, O3 *= W8^3
   {
     float tr = r[3], ti = i[3];
@@ -111,6 +116,15 @@ __device__ __forceinline__ void bfly8(float (&r)[8], float (&i)[8]) {
   }
 }
 
+// radix-8 butterfly on 8 values (natural order in, natural order out)
+template <bool INV, bool CLAMP = false>
+__device__ __forceinline__ void bfly8(float (&r)[8], float (&i)[8]) {
+  // even / odd radix-4
+  bfly4<INV>(r[0], i[0], r[2], i[2], r[4], i[4], r[6], i[6]);  // E0..E3 in slots 0,2,4,6
+  bfly4<INV>(r[1], i[1], r[3], i[3], r[5], i[5], r[7], i[7]);  // O0..O3 in slots 1,3,5,7
+  bfly8_tail<INV, CLAMP>(r, i);
+}
+
 template <bool INV, int N2, int K1, int STEP>
 struct TwiddleRow {
   // x[n2] *= W^(STEP * n2 * K1) for n2 = 1..7 (W = 64th root); unrolled at compile time
@@ -123,13 +137,116 @@ struct TwiddleRow {
   }
 };
 
+// ---- folded twiddles ------------------------------------------------------------------------------------------------
+// W v = k u with  u = (v_r - v_i t, v_i + v_r t), k = c, t = sigma / c            (|sigma| <= |c|)
+//              or  u = (v_i - v_r t, v_r + v_i t), k = (-sigma, +sigma), t = c / sigma   (|sigma| >  |c|: W = i sigma (1 - i t)),
+// so |t| <= 1 and u costs two FMAs.  The scale is not applied: it rides on the first add / sub level of the butterfly that
+// consumes u,  x +- k u_y = fma(u_y, +-k, x)  and, with both inputs twiddled,  p = k_x u_x;  fma(u_y, +-k_y, p)  -- two
+// instructions less per pair than multiply-then-add.  Every FMA is two registers and a literal (v_fmamk / v_fmac), written
+// as fmaf so that the contraction is not the compiler's choice.  Exponents that are multiples of 16 keep twiddle64's swaps
+// and negations and count as un-twiddled.
+// LSPIV_FFT_FOLD=0/1 forces the path for every kernel of every length (A/B builds); left alone, the adoption is that of DESIGN.md
+// 3.3: a length folds when none of its kernels pays for it in registers, scratch or waves.  16 does; 32 and 64 do not as lengths,
+// but the walking per-pair kernel of 32 x 32 (the flagship) is clean in all its instantiations and folds on its own (kFftFoldWalk32).
+#ifdef LSPIV_FFT_FOLD
+constexpr bool kFftFold16 = LSPIV_FFT_FOLD, kFftFold32 = LSPIV_FFT_FOLD, kFftFold64 = LSPIV_FFT_FOLD, kFftFoldWalk32 = LSPIV_FFT_FOLD;
+#else
+constexpr bool kFftFold16 = true, kFftFold32 = false, kFftFold64 = false, kFftFoldWalk32 = true;
+#endif
+template <int N> constexpr bool kFftFoldLen = N == 16 ? kFftFold16 : N == 32 ? kFftFold32 : N == 64 ? kFftFold64 : false;
+template <int N> constexpr bool kFftFoldWalk = N == 32 ? kFftFoldWalk32 : kFftFoldLen<N>;
+
+template <bool INV, int M>
+struct FoldTw {
+  static constexpr int m = M & 63;
+  static constexpr bool triv = (m % 16) == 0;
+  static constexpr double c = cos64(m), s = INV ? sin64(m) : -sin64(m);   // the table's floats, exactly
+  static constexpr bool sform = (s < 0 ? -s : s) > (c < 0 ? -c : c);
+  static constexpr float t = triv ? 0.0f : (float)(sform ? c / s : s / c);   // quotient in double, rounded once
+  static constexpr float kr = triv ? 1.0f : (float)(sform ? -s : c);        // scale of u's real part
+  static constexpr float ki = triv ? 1.0f : (float)(sform ? s : c);         // ... of its imaginary part
+};
+
+// v -> u in place (a trivial exponent: v -> W v)
+template <bool INV, int M>
+__device__ __forceinline__ void fold_u(float& vr, float& vi) {
+  using T = FoldTw<INV, M>;
+  if constexpr (T::triv) {
+    twiddle64<INV, M>(vr, vi);
+  } else if constexpr (!T::sform) {
+    const float ur = fmaf(vi, -T::t, vr), ui = fmaf(vr, T::t, vi);
+    vr = ur; vi = ui;
+  } else {
+    const float ur = fmaf(vr, -T::t, vi), ui = fmaf(vi, T::t, vr);
+    vr = ur; vi = ui;
+  }
+}
+
+// one component of a folded pair: sum = kx x + ky y, dif = kx x - ky y (a trivial side has k = 1 and is not multiplied)
+template <bool TRIVX, bool TRIVY>
+__device__ __forceinline__ void fold_pair(float x, float kx, float y, float ky, float& sum, float& dif) {
+  if constexpr (TRIVX && TRIVY) {
+    sum = x + y; dif = x - y;
+  } else if constexpr (TRIVY) {
+    const float p = kx * x;
+    sum = p + y; dif = p - y;
+  } else {
+    const float p = TRIVX ? x : kx * x;
+    sum = fmaf(y, ky, p); dif = fmaf(y, -ky, p);
+  }
+}
+
+// radix-4 butterfly of W^E0 x0 .. W^E3 x3 (W = 64th root)
+template <bool INV, bool CLAMP, int E0, int E1, int E2, int E3>
+__device__ __forceinline__ void bfly4_fold(float& r0, float& i0, float& r1, float& i1,
+                                           float& r2, float& i2, float& r3, float& i3) {
+  using T0 = FoldTw<INV, E0>; using T1 = FoldTw<INV, E1>; using T2 = FoldTw<INV, E2>; using T3 = FoldTw<INV, E3>;
+  fold_u<INV, E0>(r0, i0); fold_u<INV, E1>(r1, i1); fold_u<INV, E2>(r2, i2); fold_u<INV, E3>(r3, i3);
+  float ar, ai, br, bi, cr, ci, dr, di;
+  fold_pair<T0::triv, T2::triv>(r0, T0::kr, r2, T2::kr, ar, br);
+  fold_pair<T0::triv, T2::triv>(i0, T0::ki, i2, T2::ki, ai, bi);
+  fold_pair<T1::triv, T3::triv>(r1, T1::kr, r3, T3::kr, cr, dr);
+  fold_pair<T1::triv, T3::triv>(i1, T1::ki, i3, T3::ki, ci, di);
+  bfly4_tail<INV, CLAMP>(ar, ai, br, bi, cr, ci, dr, di, r0, i0, r1, i1, r2, i2, r3, i3);
+}
+
+// radix-8 butterfly of x[n2] W^(STEP n2 K1), n2 = 0..7: TwiddleRow + bfly8, folded or not
+template <bool INV, bool CLAMP, bool FOLD, int K1, int STEP>
+__device__ __forceinline__ void twiddled_bfly8(float (&r)[8], float (&i)[8]) {
+  if constexpr (FOLD) {
+    constexpr int E = STEP * K1;
+    bfly4_fold<INV, false, 0, 2 * E, 4 * E, 6 * E>(r[0], i[0], r[2], i[2], r[4], i[4], r[6], i[6]);
+    bfly4_fold<INV, false, E, 3 * E, 5 * E, 7 * E>(r[1], i[1], r[3], i[3], r[5], i[5], r[7], i[7]);
+    bfly8_tail<INV, CLAMP>(r, i);
+  } else {
+    TwiddleRow<INV, 8, K1, STEP>::template apply<1>(r, i);
+    bfly8<INV, CLAMP>(r, i);
+  }
+}
+
 // ---- length-16 transform: n = 4 n1 + n2, k = k1 + 4 k2 ------------------------------------------------
 //   X[k1 + 4 k2] = DFT4_{n2}( W16^{n2 k1} * DFT4_{n1} x[4 n1 + n2] ),  W16 = W64^4
-template <bool INV, bool CLAMP = false>
+template <bool INV, bool CLAMP, int K1>
+__device__ __forceinline__ void fft16_row_fold(const float (&xr)[16], const float (&xi)[16], float (&yr)[16], float (&yi)[16]) {
+  float r0 = xr[4 * K1], i0 = xi[4 * K1], r1 = xr[4 * K1 + 1], i1 = xi[4 * K1 + 1];
+  float r2 = xr[4 * K1 + 2], i2 = xi[4 * K1 + 2], r3 = xr[4 * K1 + 3], i3 = xi[4 * K1 + 3];
+  bfly4_fold<INV, CLAMP, 0, 4 * K1, 8 * K1, 12 * K1>(r0, i0, r1, i1, r2, i2, r3, i3);
+  yr[K1] = r0; yi[K1] = i0; yr[K1 + 4] = r1; yi[K1 + 4] = i1; yr[K1 + 8] = r2; yi[K1 + 8] = i2; yr[K1 + 12] = r3; yi[K1 + 12] = i3;
+}
+
+template <bool INV, bool CLAMP = false, bool FOLD = kFftFold16>
 __device__ __forceinline__ void fft16(float (&xr)[16], float (&xi)[16]) {
 #pragma unroll
   for (int n2 = 0; n2 < 4; ++n2)
     bfly4<INV>(xr[n2], xi[n2], xr[4 + n2], xi[4 + n2], xr[8 + n2], xi[8 + n2], xr[12 + n2], xi[12 + n2]);   // slot (k1, n2) = 4 k1 + n2
+  if constexpr (FOLD) {
+    float yr[16], yi[16];
+    fft16_row_fold<INV, CLAMP, 0>(xr, xi, yr, yi); fft16_row_fold<INV, CLAMP, 1>(xr, xi, yr, yi);
+    fft16_row_fold<INV, CLAMP, 2>(xr, xi, yr, yi); fft16_row_fold<INV, CLAMP, 3>(xr, xi, yr, yi);
+#pragma unroll
+    for (int k = 0; k < 16; ++k) { xr[k] = yr[k]; xi[k] = yi[k]; }
+    return;
+  }
   twiddle64<INV, 4 * 1 * 1>(xr[4 + 1], xi[4 + 1]);  twiddle64<INV, 4 * 2 * 1>(xr[4 + 2], xi[4 + 2]);  twiddle64<INV, 4 * 3 * 1>(xr[4 + 3], xi[4 + 3]);
   twiddle64<INV, 4 * 1 * 2>(xr[8 + 1], xi[8 + 1]);  twiddle64<INV, 4 * 2 * 2>(xr[8 + 2], xi[8 + 2]);  twiddle64<INV, 4 * 3 * 2>(xr[8 + 3], xi[8 + 3]);
   twiddle64<INV, 4 * 1 * 3>(xr[12 + 1], xi[12 + 1]); twiddle64<INV, 4 * 2 * 3>(xr[12 + 2], xi[12 + 2]); twiddle64<INV, 4 * 3 * 3>(xr[12 + 3], xi[12 + 3]);
@@ -147,7 +264,7 @@ __device__ __forceinline__ void fft16(float (&xr)[16], float (&xi)[16]) {
 
 // ---- length-32 transform, in place, natural order in and out --------------------------------
 // n = 8 n1 + n2, k = k1 + 4 k2:  X[k1 + 4 k2] = DFT8_{n2}( W32^{n2 k1} * DFT4_{n1} x[8 n1 + n2] )
-template <bool INV, bool CLAMP = false>
+template <bool INV, bool CLAMP = false, bool FOLD = kFftFold32>
 __device__ __forceinline__ void fft32(float (&xr)[32], float (&xi)[32]) {
 #pragma unroll
   for (int n2 = 0; n2 < 8; ++n2)
@@ -166,8 +283,7 @@ __device__ __forceinline__ void fft32(float (&xr)[32], float (&xi)[32]) {
     float r[8], i[8];
 #pragma unroll
     for (int n2 = 0; n2 < 8; ++n2) { r[n2] = xr[8 + n2]; i[n2] = xi[8 + n2]; }
-    TwiddleRow<INV, 8, 1, 2>::template apply<1>(r, i);
-    bfly8<INV, CLAMP>(r, i);
+    twiddled_bfly8<INV, CLAMP, FOLD, 1, 2>(r, i);
 #pragma unroll
     for (int k2 = 0; k2 < 8; ++k2) { yr[1 + 4 * k2] = r[k2]; yi[1 + 4 * k2] = i[k2]; }
   }
@@ -175,8 +291,7 @@ __device__ __forceinline__ void fft32(float (&xr)[32], float (&xi)[32]) {
     float r[8], i[8];
 #pragma unroll
     for (int n2 = 0; n2 < 8; ++n2) { r[n2] = xr[16 + n2]; i[n2] = xi[16 + n2]; }
-    TwiddleRow<INV, 8, 2, 2>::template apply<1>(r, i);
-    bfly8<INV, CLAMP>(r, i);
+    twiddled_bfly8<INV, CLAMP, FOLD, 2, 2>(r, i);
 #pragma unroll
     for (int k2 = 0; k2 < 8; ++k2) { yr[2 + 4 * k2] = r[k2]; yi[2 + 4 * k2] = i[k2]; }
   }
@@ -184,8 +299,7 @@ __device__ __forceinline__ void fft32(float (&xr)[32], float (&xi)[32]) {
     float r[8], i[8];
 #pragma unroll
     for (int n2 = 0; n2 < 8; ++n2) { r[n2] = xr[24 + n2]; i[n2] = xi[24 + n2]; }
-    TwiddleRow<INV, 8, 3, 2>::template apply<1>(r, i);
-    bfly8<INV, CLAMP>(r, i);
+    twiddled_bfly8<INV, CLAMP, FOLD, 3, 2>(r, i);
 #pragma unroll
     for (int k2 = 0; k2 < 8; ++k2) { yr[3 + 4 * k2] = r[k2]; yi[3 + 4 * k2] = i[k2]; }
   }
@@ -194,14 +308,13 @@ __device__ __forceinline__ void fft32(float (&xr)[32], float (&xi)[32]) {
 }
 
 // ---- length-64 transform: n = 8 n1 + n2, k = k1 + 8 k2 --------------------------------------
-template <bool INV, int K1, bool CLAMP = false>
+template <bool INV, int K1, bool CLAMP = false, bool FOLD = false>
 __device__ __forceinline__ void fft64_col(const float (&xr)[64], const float (&xi)[64],
                                           float (&yr)[64], float (&yi)[64]) {
   float r[8], i[8];
 #pragma unroll
   for (int n2 = 0; n2 < 8; ++n2) { r[n2] = xr[8 * K1 + n2]; i[n2] = xi[8 * K1 + n2]; }
-  TwiddleRow<INV, 8, K1, 1>::template apply<1>(r, i);
-  bfly8<INV, CLAMP>(r, i);
+  twiddled_bfly8<INV, CLAMP, FOLD, K1, 1>(r, i);
 #pragma unroll
   for (int k2 = 0; k2 < 8; ++k2) { yr[K1 + 8 * k2] = r[k2]; yi[K1 + 8 * k2] = i[k2]; }
 }
@@ -215,7 +328,7 @@ __device__ __forceinline__ void fft64_col(const float (&xr)[64], const float (&x
 #define LSPIV_FFT64_PRIO 0
 #endif
 #define LSPIV_FFT64_BAR do { if (LSPIV_FFT64_SB) __builtin_amdgcn_sched_barrier(0); } while (0)
-template <bool INV, bool CLAMP = false>
+template <bool INV, bool CLAMP = false, bool FOLD = kFftFold64>
 __device__ __forceinline__ void fft64(float (&xr)[64], float (&xi)[64]) {
 #pragma unroll
   for (int n2 = 0; n2 < 8; ++n2) {
@@ -231,14 +344,14 @@ __device__ __forceinline__ void fft64(float (&xr)[64], float (&xi)[64]) {
 #if LSPIV_FFT64_PRIO
   __builtin_amdgcn_s_setprio(1);   // A/B variant: the second radix stage ahead of a neighbour's first
 #endif
-  fft64_col<INV, 0, CLAMP>(xr, xi, yr, yi); LSPIV_FFT64_BAR;
-  fft64_col<INV, 1, CLAMP>(xr, xi, yr, yi); LSPIV_FFT64_BAR;
-  fft64_col<INV, 2, CLAMP>(xr, xi, yr, yi); LSPIV_FFT64_BAR;
-  fft64_col<INV, 3, CLAMP>(xr, xi, yr, yi); LSPIV_FFT64_BAR;
-  fft64_col<INV, 4, CLAMP>(xr, xi, yr, yi); LSPIV_FFT64_BAR;
-  fft64_col<INV, 5, CLAMP>(xr, xi, yr, yi); LSPIV_FFT64_BAR;
-  fft64_col<INV, 6, CLAMP>(xr, xi, yr, yi); LSPIV_FFT64_BAR;
-  fft64_col<INV, 7, CLAMP>(xr, xi, yr, yi); LSPIV_FFT64_BAR;
+  fft64_col<INV, 0, CLAMP, FOLD>(xr, xi, yr, yi); LSPIV_FFT64_BAR;
+  fft64_col<INV, 1, CLAMP, FOLD>(xr, xi, yr, yi); LSPIV_FFT64_BAR;
+  fft64_col<INV, 2, CLAMP, FOLD>(xr, xi, yr, yi); LSPIV_FFT64_BAR;
+  fft64_col<INV, 3, CLAMP, FOLD>(xr, xi, yr, yi); LSPIV_FFT64_BAR;
+  fft64_col<INV, 4, CLAMP, FOLD>(xr, xi, yr, yi); LSPIV_FFT64_BAR;
+  fft64_col<INV, 5, CLAMP, FOLD>(xr, xi, yr, yi); LSPIV_FFT64_BAR;
+  fft64_col<INV, 6, CLAMP, FOLD>(xr, xi, yr, yi); LSPIV_FFT64_BAR;
+  fft64_col<INV, 7, CLAMP, FOLD>(xr, xi, yr, yi); LSPIV_FFT64_BAR;
 #if LSPIV_FFT64_PRIO
   __builtin_amdgcn_s_setprio(0);
 #endif
@@ -394,7 +507,7 @@ template <bool INV> __device__ __forceinline__ void fft_pow2(float (&r)[2], floa
 }
 template <bool INV> __device__ __forceinline__ void fft_pow2(float (&r)[4], float (&i)[4]) { bfly4<INV>(r[0], i[0], r[1], i[1], r[2], i[2], r[3], i[3]); }
 template <bool INV> __device__ __forceinline__ void fft_pow2(float (&r)[8], float (&i)[8]) { bfly8<INV>(r, i); }
-template <bool INV> __device__ __forceinline__ void fft_pow2(float (&r)[16], float (&i)[16]) { fft16<INV>(r, i); }
+template <bool INV> __device__ __forceinline__ void fft_pow2(float (&r)[16], float (&i)[16]) { fft16<INV, false, false>(r, i); }   // 48 = 3 x 16 stays un-folded
 
 template <bool INV> __device__ __forceinline__ void fft_pow2(float (&r)[5], float (&i)[5]) { dft_small<INV>(r, i); }   // second factor of 15
 template <bool INV> __device__ __forceinline__ void fft_pow2(float (&r)[7], float (&i)[7]) { dft_small<INV>(r, i); }   // ... of 21
