@@ -131,6 +131,12 @@ int         lspiv_synchronize(void);                    /* hipDeviceSynchronize 
  *                      (tests/test_gpu_rescue_fixed_size.py);
  *   "rescue_fit_size"  read-only (lspiv_get_option): the compile-time window size of the fit kernel the last rescue pass of the
  *                      process launched, 0 the run-time-geometry kernel, -1 no pass yet.  For tests of the dispatch.
+ * Batched sub-pixel fit of the 32 x 32 time-walking kernels:
+ *   "defer_fit"        1 (default; environment LSPIV_DEFER_FIT) an iteration stops after the arg-max search and the peak's samples, and
+ *                      after every 16th iteration each lane of a window's lane group fits one of the 32 staged planes | 0 every plane is
+ *                      fitted inside its own iteration.  The same expressions on the same operands: results and rescue records are
+ *                      the same bit for bit (tests/test_gpu_walk_defer.py); float64 frames with a signal threshold run the 0 form
+ *                      either way.
  * float64 HOST stacks are narrowed to float32 while they are staged (the kernels compute in float32).  A frame that rides on a
  * DC offset far above its contrast would lose the low bits of its texture in that conversion, where the reference normalises
  * every window in float64; the per-window normalisation does not see a constant added to a frame, so:
@@ -746,6 +752,11 @@ int lspiv_debug_fft_form(int n, int form, int inverse, const float* in, float* o
 /* Test hook (host only): how the time-walking kernels cut a chunk of n_pairs pairs that starts at absolute pair index
  * pair_offset into segments of seg_len pairs anchored at multiples of seg_len: pairs in the first segment, segment count. */
 int lspiv_debug_segments(int64_t n_pairs, int64_t pair_offset, int seg_len, int64_t* seg_first, int64_t* n_seg);
+/* Test hook: the rescue lists the LAST per-timestep launch on `stream` (NULL: the library's own) left behind, after synchronising with it.
+ * counts[0 .. 1] = "fit" / "amb" records of that launch; the first min(count, cap) of them are copied: a "fit" record is four words
+ * (result index inside the launch, ip << 16 | jp, the other arg-max candidate or ~0, 0), an "amb" record the result index.  The order of
+ * a list is whatever the kernel's waves made it. */
+int lspiv_debug_rescue_lists(void* stream, uint32_t* fit, int64_t cap_fit, uint32_t* amb, int64_t cap_amb, int64_t* counts);
 
 /* Measurement (round 5): with lspiv_set_option("time_kernel", 1) every launch records HIP events on its own stream right before and
  * right after its PIV kernel(s) -- not around the rescue kernels that follow.  lspiv_kernel_times returns the durations [ms] of the

@@ -158,6 +158,7 @@ std::atomic<int> g_opt_std_ddof{env_opt("LSPIV_STD_DDOF", 0, 1)};
 std::atomic<int> g_opt_round_odd{env_opt("LSPIV_ROUND_ODD", 0, 2)};
 std::atomic<int> g_opt_rescue{env_opt_def("LSPIV_RESCUE", 0, 1, 1)};
 std::atomic<int> g_opt_rescue_generic{env_opt("LSPIV_RESCUE_GENERIC", 0, 1)};
+static std::atomic<int> g_opt_defer_fit{env_opt_def("LSPIV_DEFER_FIT", 0, 1, 1)};
 std::atomic<int> g_rescue_fit_size{-1};
 std::atomic<int> g_opt_narrow_offset{env_opt_def("LSPIV_NARROW_OFFSET", -1, 1 << 30, 1024)};
 std::atomic<int> g_opt_rescue_kappa{env_opt_def("LSPIV_RESCUE_KAPPA", 0, 1000000, 500)};
@@ -184,6 +185,8 @@ static const Option kOptions[] = {
     {"std_ddof", &g_opt_std_ddof, 0, 1, "std_ddof must be 0 (population standard deviation) or 1 (sample)"},
     {"round_odd", &g_opt_round_odd, 0, 2, "round_odd must be 0 (half-even of x / 2), 1 (up) or 2 (down)"},
     {"rescue", &g_opt_rescue, 0, 1, "rescue must be 0 (float32 results as they are) or 1 (float64 rescue pass)"},
+    {"defer_fit", &g_opt_defer_fit, 0, 1,
+     "defer_fit must be 1 (32 x 32 walking kernels fit 32 planes at once) or 0 (every plane in its own iteration; same results)"},
     {"rescue_generic", &g_opt_rescue_generic, 0, 1,
      "rescue_generic must be 0 (fixed-size fit kernels for square 16 / 32 / 64 px windows) or 1 (run-time geometry for every launch)"},
     {"narrow_offset", &g_opt_narrow_offset, -1, INT_MAX,
@@ -240,6 +243,8 @@ int lspiv::walk_setting() {
   const char* e = getenv("LSPIV_WALK");
   return e ? atoi(e) : 1;
 }
+
+int lspiv::defer_fit_setting() { return g_opt_defer_fit.load(); }
 
 extern "C" {
 

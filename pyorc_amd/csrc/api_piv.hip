@@ -376,6 +376,34 @@ int lspiv_rescue_stats(void* stream, int64_t* stats) {
   return LSPIV_OK;
 }
 
+int lspiv_debug_rescue_lists(void* stream, uint32_t* fit, int64_t cap_fit, uint32_t* amb, int64_t cap_amb, int64_t* counts) {
+  if (!counts || cap_fit < 0 || cap_amb < 0 || (cap_fit && !fit) || (cap_amb && !amb)) return fail(LSPIV_EINVAL, "counts is NULL, or a list without its buffer");
+  DeviceCtx* c;
+  LSPIV_TRY(get_ctx(&c));
+  hipStream_t s = on_stream(c, stream);
+  std::lock_guard<std::mutex> launch_lock(locks_here().dispatch);   // no launch regrows or refills the lists meanwhile
+  void* base = nullptr;
+  size_t ws_cap_fit = 0, ws_cap_amb = 0;
+  {
+    std::lock_guard<std::mutex> lk(locks_here().lists);
+    for (auto& w : c->rescue) if (w.stream == s) { base = w.base; ws_cap_fit = w.cap_fit; ws_cap_amb = w.cap_amb; }
+  }
+  counts[0] = counts[1] = 0;
+  if (!base) return LSPIV_OK;   // no pass has run on this stream
+  lspiv::RescueHdr h;
+  HIP_TRY(hipMemcpyAsync(&h, base, sizeof(h), hipMemcpyDeviceToHost, s));
+  HIP_TRY(hipStreamSynchronize(s));
+  const size_t n_fit = std::min<size_t>(h.last_fit, ws_cap_fit), n_amb = std::min<size_t>(h.last_amb, ws_cap_amb);
+  counts[0] = (int64_t)n_fit; counts[1] = (int64_t)n_amb;
+  const char* d_fit = (const char*)base + RescueCaps::hdr_bytes;
+  const char* d_amb = d_fit + ws_cap_fit * sizeof(uint4);
+  const size_t c_fit = std::min<size_t>(n_fit, (size_t)cap_fit), c_amb = std::min<size_t>(n_amb, (size_t)cap_amb);
+  if (c_fit) HIP_TRY(hipMemcpyAsync(fit, d_fit, c_fit * sizeof(uint4), hipMemcpyDeviceToHost, s));
+  if (c_amb) HIP_TRY(hipMemcpyAsync(amb, d_amb, c_amb * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+  HIP_TRY(hipStreamSynchronize(s));
+  return LSPIV_OK;
+}
+
 int lspiv_kernel_kind(int wy, int wx) {
   if (wy < 2 || wx < 2 || wy > LSPIV_MAX_WINDOW || wx > LSPIV_MAX_WINDOW) return LSPIV_EUNSUPPORTED;
   if (wy > 64 || wx > 64) return lspiv::piv_dft_fits(wy, wx) ? kKindDft : kKindDftGlobal;   // 2-D DFT of any shape: LDS-resident up to 128 x 128, HBM slots above

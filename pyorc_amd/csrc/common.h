@@ -547,6 +547,9 @@ hipError_t launch_window_signal(const void* frames, int dtype, int64_t T, const 
 // LSPIV_WALK as an integer (0 per-pair kernels, 1 default walking kernels, n > 1 forced segment length): the value set
 // through lspiv_set_option("walk", v) if any, else the environment variable read at every launch, else 1
 int walk_setting();
+// option "defer_fit" (LSPIV_DEFER_FIT presets it): 1 = the 32 x 32 walking kernels fit 32 planes at once (piv_fft_impl.h, DEFER), 0 = every
+// plane in its own iteration; same bits either way
+int defer_fit_setting();
 // Segments of the time-walking kernels.  A job walks one window through a run of consecutive frame pairs and shares
 // every frame's spectrum between the two pairs it belongs to; which frames share transforms depends on where a run
 // starts, so the runs ("segments") are ANCHORED: they start at the absolute pair indices k * kWalkAnchor of the caller's

@@ -1787,8 +1787,124 @@ __device__ __forceinline__ void walk_iteration(const PivParams& p, const T* row,
   c.prev_dead = dead1; c.prev_finite = fin1; c.prev_nz = nz1;
 }
 
+// ---- 32 x 32 walking kernel: the sub-pixel fits of 32 planes at once, one plane per lane (DEFER) ---------------------------------
+// find_peak needs the group's 32 lanes (one per row) for the maxima, the arg-max, the near-tie test and the LDS samples; what follows --
+// five + kEpsPeak, five v_log_f32, two v_rcp_f32, peak_cond, border_result, vmax * rcp(mean), the dead / skip overrides, four stores -- is
+// ONE computation per plane issued 64 lanes wide: about 95 VALU per plane, 8 of them transcendental, and most of the epilogue's scalar
+// instructions and exec-masked regions.  With DEFER an iteration stops after the samples: lane 0 of the group writes the plane's record
+// (kDeferRecDwords: vmax, the four raw neighbours, the mean, a packed word, the result index) into a slot of the job's staging area behind
+// the tiles, and after every 16th iteration of the wave (and after the loop) lane s of the group fits the plane of slot s -- the former
+// expressions on the former operands through the same inline functions, so the bits stay --, stores its four results and appends its
+// "fit" rescue record.  The "amb" cold path needs the parked plane and stays in the iteration (peak_cond: amb = vmax > 0 && near_tie,
+// and an "amb" window is never a "fit" one).  A slot's VALID bit is cleared when it is consumed: a group that has left the loop keeps its
+// last slots until the flush behind the loop and must not see them twice.  The slot index and the flush hang on the WAVE's iteration
+// count, never on one group's frame index: the two groups of a wave can sit in segments of different lengths.
+// Per kernel by the resource rule of the un-pack batch above (no VGPR above the three-wave step, no scratch, no wave lost against the
+// kernel without it; tools/kres.py); the "defer_fit" option picks the form at launch.  -DLSPIV_WALK_DEFER=0 / 1 forces it off / on.
+#ifndef LSPIV_WALK_DEFER
+#define LSPIV_WALK_DEFER -1
+#endif
+constexpr int kDeferSlots = 32, kDeferRecDwords = 8;   // 16 iterations x 2 planes = one slot per lane of the group; two ds_write_b128
+// [sample type][PLANES][WANT_NZ]; float64 with the score: 195 -> 201 and 194 -> 205 VGPRs, above the 168 of the three-wave step
+constexpr bool kWalkDefer32[3][2][2] = {{{true, true}, {true, true}}, {{true, true}, {true, true}}, {{true, false}, {true, false}}};
 template <typename T, int N, bool PLANES, bool WANT_NZ>
+constexpr bool kWalkDefer = N == 32 && (LSPIV_WALK_DEFER >= 0 ? LSPIV_WALK_DEFER != 0 : kWalkDefer32[kSampleKind<T>][PLANES][WANT_NZ]);
+// the packed word of a record: ip | jp << 8 | flags
+constexpr uint32_t kDeferNearTie = 1u << 16, kDeferDead = 1u << 17, kDeferSkip = 1u << 18, kDeferValid = 1u << 19, kDeferNote = 1u << 20;
+
+// The part of find_peak that needs the group: park, arg-max, near-tie test, the four neighbours, the "amb" cold path -- then the record.
+template <int N>
+__device__ __forceinline__ void peak_search_stage(float* buf, int lg, const float (&c)[N], float vmax, float row_max, const PivParams& p, bool note,
+                                                  uint32_t g, int ip_known, float mean, bool dead, bool skip, bool valid, uint32_t* rec) {
+  int ip, jp;
+  constexpr int LR = Geo<N>::LDS_ROW;
+  constexpr int C = N / 2, NONE = 1 << 12;
+  const bool active = lane_active<N>(lg);
+  const int lr = row_of<N>(lg);
+  if (active) lds_row_write<N>(buf + lg * LR, c);
+  __builtin_amdgcn_wave_barrier();
+  const int sh = wrap_n<N>(lr + C);
+  ip = ip_known >= 0 ? ip_known : peak_row<N>(lg, vmax, row_max);
+  const int y = wrap_n<N>(ip + C);
+  const float rowv = buf[y * LR + lr];
+  jp = group_min_i<N>((active && rowv == vmax) ? sh : NONE);
+  const float thr = vmax * (1.0f - p.rescue_tau);
+  const bool near_tie = group_any<N>(active && ((row_max >= thr && sh != ip) || (rowv >= thr && sh != jp)));
+  const int x = wrap_n<N>(jp + C);
+  const int ym = wrap_n<N>(ip + C - 1), yp = wrap_n<N>(ip + C + 1);
+  const int xm = wrap_n<N>(jp + C - 1), xp = wrap_n<N>(jp + C + 1);
+  const float nl = buf[ym * LR + x];
+  const float nr = buf[yp * LR + x];
+  const float nd = buf[y * LR + xm];
+  const float nu = buf[y * LR + xp];
+  __builtin_amdgcn_wave_barrier();
+  if (note) {
+    const bool amb = vmax > 0.0f && near_tie;
+    if (__builtin_amdgcn_ballot_w64(amb) != 0) {   // cold path, as in find_peak
+      uint32_t pos2 = 0xffffffffu;
+      const int pos1 = (ip << 16) | jp;
+      int cnt = 0, other = 0x7fffffff;
+#pragma unroll 1
+      for (int yy = 0; yy < N; ++yy) {
+        const bool cand = active && buf[yy * LR + lr] >= thr;
+        const int pos = (wrap_n<N>(yy + C) << 16) | sh;
+        cnt += cand ? 1 : 0;
+        other = (cand && pos != pos1) ? min(other, pos) : other;
+      }
+      cnt = group_sum_i<N>(cnt);
+      other = group_min_i<N>(other);
+      if (cnt == 2) pos2 = (uint32_t)other;
+      if (lg == 0 && amb) rescue_note(p.rescue_hdr, p.rescue_fit, p.rescue_cap_fit, p.rescue_amb, p.rescue_cap_amb, g, PeakCond{true, false}, ip, jp, pos2);
+    }
+  }
+  if (lg == 0) {
+    const uint32_t packed = (uint32_t)ip | ((uint32_t)jp << 8) | (near_tie ? kDeferNearTie : 0u) | (dead ? kDeferDead : 0u) | (skip ? kDeferSkip : 0u) |
+                            (valid ? kDeferValid : 0u) | (note ? kDeferNote : 0u);
+    uint4* r = reinterpret_cast<uint4*>(rec);
+    r[0] = make_uint4(__builtin_bit_cast(uint32_t, vmax), __builtin_bit_cast(uint32_t, nl), __builtin_bit_cast(uint32_t, nr), __builtin_bit_cast(uint32_t, nd));
+    r[1] = make_uint4(__builtin_bit_cast(uint32_t, nu), __builtin_bit_cast(uint32_t, mean), packed, g);
+  }
+}
+
+// Lane s of the group fits the plane of slot s: find_peak's arithmetic from the + kEpsPeak on, and the kernel's result tail.
+template <int N>
+__device__ __forceinline__ void defer_flush(uint32_t* stage, int lg, const PivParams& p) {
+  static_assert(Geo<N>::LG == kDeferSlots, "one slot per lane of the group");
+  constexpr int M = N - 1, C = N / 2;
+  __builtin_amdgcn_wave_barrier();
+  const uint4* r = reinterpret_cast<const uint4*>(stage + lg * kDeferRecDwords);
+  const uint4 r0 = r[0], r1 = r[1];
+  const uint32_t packed = r1.z, g = r1.w;
+  if (packed & kDeferValid) {
+    stage[lg * kDeferRecDwords + 6] = 0u;   // consumed
+    const float vmax = __builtin_bit_cast(float, r0.x), mean = __builtin_bit_cast(float, r1.y);
+    const int ip = (int)(packed & 0xffu), jp = (int)((packed >> 8) & 0xffu);
+    const bool near_tie = (packed & kDeferNearTie) != 0;
+    const bool border = (ip == 0 || ip == M || jp == 0 || jp == M);
+    const float c0 = vmax + kEpsPeak;
+    const float cl = __builtin_bit_cast(float, r0.y) + kEpsPeak;
+    const float cr = __builtin_bit_cast(float, r0.z) + kEpsPeak;
+    const float cd = __builtin_bit_cast(float, r0.w) + kEpsPeak;
+    const float cu = __builtin_bit_cast(float, r1.x) + kEpsPeak;
+    const float l0 = __builtin_amdgcn_logf(c0);
+    float den_v, den_u;
+    float v = (float)ip + gauss_offset_fast(__builtin_amdgcn_logf(cl), l0, __builtin_amdgcn_logf(cr), den_v) - (float)C;
+    float u = (float)jp + gauss_offset_fast(__builtin_amdgcn_logf(cd), l0, __builtin_amdgcn_logf(cu), den_u) - (float)C;
+    const PeakCond pc = peak_cond(vmax, near_tie, border, cl, cr, den_v, v, cd, cu, den_u, u, p.rescue_k);
+    if ((packed & kDeferNote) && pc.fit) rescue_note(p.rescue_hdr, p.rescue_fit, p.rescue_cap_fit, p.rescue_amb, p.rescue_cap_amb, g, pc, ip, jp);
+    if (border) border_result(p.border_mode, jp - C, ip - C, u, v);
+    const float nanv = __builtin_nanf("");
+    float cm = vmax, sn = vmax * __builtin_amdgcn_rcpf(mean);
+    if (packed & kDeferDead) { u = v = sn = nanv; cm = 0.0f; }   // zero-variance window, as in the kernel
+    if (packed & kDeferSkip) u = v = cm = sn = nanv;
+    p.u[g] = u; p.v[g] = v; p.cmax[g] = cm; p.s2n[g] = sn;
+  }
+  __builtin_amdgcn_wave_barrier();
+}
+
+template <typename T, int N, bool PLANES, bool WANT_NZ, bool DEFER = false>
 __global__ __launch_bounds__(BLOCK, (kWalkWaves<T, N>)) void piv_fft_walk_kernel(PivParams p) {
+  static_assert(!DEFER || (N == 32 && !kTwoPlaneEpilogue<N>), "the batched fit is built for two groups of 32 lanes");
   const uint32_t seg_len = p.seg_len, n_seg = p.n_seg;
   extern __shared__ __attribute__((aligned(16))) float smem[];
   using G = Geo<N>;
@@ -1798,6 +1914,10 @@ __global__ __launch_bounds__(BLOCK, (kWalkWaves<T, N>)) void piv_fft_walk_kernel
   const int lg = lane & (G::LG - 1);
   float* buf = smem + (wave * G::GROUPS + grp) * G::LDS_JOB;
   float* mini = smem + WAVES_PER_BLOCK * G::GROUPS * G::LDS_JOB + (wave * G::GROUPS + grp) * 3 * G::LDS_ROW;   // plane b's three rows (64 x 64)
+  // DEFER: the job's kDeferSlots records behind the tiles
+  uint32_t* stage = reinterpret_cast<uint32_t*>(smem + WAVES_PER_BLOCK * G::GROUPS * G::LDS_JOB) + (wave * G::GROUPS + grp) * kDeferSlots * kDeferRecDwords;
+  if constexpr (DEFER) stage[lg * kDeferRecDwords + 6] = 0u;
+  uint32_t it = 0;   // DEFER: iterations of the WAVE so far
   const int partner_byte = partner_byte_of<N>(lane, lg);
   const int lane0_byte = lane0_byte_of<N>();
 
@@ -1864,6 +1984,23 @@ __global__ __launch_bounds__(BLOCK, (kWalkWaves<T, N>)) void piv_fft_walk_kernel
         if (valid_b && lg == 0) { p.u[g_b] = u; p.v[g_b] = v; p.cmax[g_b] = cm; p.s2n[g_b] = sn; }
       }
       __builtin_amdgcn_wave_barrier();   // the parked samples are read before the next iteration's transposes reuse the tile
+    } else if constexpr (DEFER) {
+      // search now, fit later (defer_flush): plane b's maximum and peak row first, as below
+      float row_max_b;
+      const float vmax_b = plane_max<N>(xi, row_max_b);
+      const int ip_b = peak_row<N>(lg, vmax_b, row_max_b);
+      uint32_t* rec = stage + (it & (kDeferSlots / 2 - 1)) * 2 * kDeferRecDwords;
+      {
+        float row_max;
+        const uint32_t g = (f - 1) * p.n_win + win;
+        const float vmax = plane_max<N>(xr, row_max);
+        peak_search_stage<N>(buf, lg, xr, vmax, row_max, p, p.rescue_hdr && valid_a && !dead_a && !skip_a, g, -1, mean_a, dead_a, skip_a, valid_a, rec);
+      }
+      {
+        const uint32_t g = f * p.n_win + win;
+        peak_search_stage<N>(buf, lg, xi, vmax_b, row_max_b, p, p.rescue_hdr && valid_b && !dead_b && !skip_b, g, ip_b, mean_b, dead_b, skip_b, valid_b,
+                             rec + kDeferRecDwords);
+      }
     } else {
       // plane b's maximum and peak row first: register-only work the scheduler can slot into the LDS waits of plane a's fit
       float row_max_b;
@@ -1898,7 +2035,12 @@ __global__ __launch_bounds__(BLOCK, (kWalkWaves<T, N>)) void piv_fft_walk_kernel
       if (valid_a) store_plane_rows<N>(p.planes + ((size_t)(f - 1) * p.n_win + win) * G::NN, lg, xr, skip_a, dead_a);
       if (valid_b) store_plane_rows<N>(p.planes + ((size_t)f * p.n_win + win) * G::NN, lg, xi, skip_b, dead_b);
     }
+    if constexpr (DEFER) {
+      ++it;
+      if ((it & (kDeferSlots / 2 - 1)) == 0) defer_flush<N>(stage, lg, p);   // the groups still in the loop; every slot of theirs is written
+    }
   }
+  if constexpr (DEFER) defer_flush<N>(stage, lg, p);   // what is left, of both groups; nothing where the last iteration flushed
 }
 
 // ---- embedded mode epilogue: corr_max, mean, np.argmax and the sub-pixel fit over the n x n corner ----------------
@@ -2633,10 +2775,26 @@ static hipError_t launch_t(const PivParams& p, bool ensemble, hipStream_t s) {
     q.xcd_by_windows = walk_xcd_by_windows();
     const uint32_t wblocks = walk_blocks(w.n_seg, p.n_win, jobs_per_block, q.xcd_by_windows);
     constexpr size_t walk_lds = G::LDS_BYTES + (kTwoPlaneEpilogue<N> ? (size_t)WAVES_PER_BLOCK * G::GROUPS * 3 * G::LDS_ROW * 4 : 0);   // + plane b's three rows
-    if (p.planes)
+    // the batched fit (kWalkDefer, option "defer_fit"): + the jobs' staging records
+    constexpr size_t defer_lds = walk_lds + (size_t)jobs_per_block * kDeferSlots * kDeferRecDwords * 4;
+    const bool defer = defer_fit_setting() != 0;
+    if (p.planes) {
+      if constexpr (kWalkDefer<T, N, true, WANT_NZ>) {
+        if (defer) {
+          hipLaunchKernelGGL((piv_fft_walk_kernel<T, N, true, WANT_NZ, true>), dim3(wblocks), dim3(BLOCK), defer_lds, s, q);
+          return hipGetLastError();
+        }
+      }
       hipLaunchKernelGGL((piv_fft_walk_kernel<T, N, true, WANT_NZ>), dim3(wblocks), dim3(BLOCK), walk_lds, s, q);
-    else
+    } else {
+      if constexpr (kWalkDefer<T, N, false, WANT_NZ>) {
+        if (defer) {
+          hipLaunchKernelGGL((piv_fft_walk_kernel<T, N, false, WANT_NZ, true>), dim3(wblocks), dim3(BLOCK), defer_lds, s, q);
+          return hipGetLastError();
+        }
+      }
       hipLaunchKernelGGL((piv_fft_walk_kernel<T, N, false, WANT_NZ>), dim3(wblocks), dim3(BLOCK), walk_lds, s, q);
+    }
     return hipGetLastError();
   }
   const uint32_t jobs = p.n_pairs * ((p.n_win + 1) / 2);
