@@ -46,7 +46,8 @@ extern "C" {
                                * lspiv_piv_deform_pairs_dev_at / lspiv_piv_multipass_deform_dev_at / lspiv_piv_multipass_deform_at; SPOF phase-filtered
                                * correlation, lspiv_spof_supported / lspiv_piv_spof_pairs_dev_at / lspiv_piv_spof_pairs_at /
                                * lspiv_ensemble_set_spectral_filter / _get_spectral_filter; the image mask, lspiv_mask_supported /
-                               * lspiv_piv_masked_pairs_dev_at / lspiv_piv_masked_pairs_at)
+                               * lspiv_piv_masked_pairs_dev_at / lspiv_piv_masked_pairs_at; the second correlation peak, lspiv_peak2_supported /
+                               * lspiv_piv_peak2_pairs_dev_at / lspiv_piv_peak2_pairs_at / lspiv_second_peak_dev / lspiv_second_peak)
                                * 5 (round 6): lspiv_chunk_alignment(wy, wx) without a grid now returns the alignment that is right on EVERY grid (75
                                * where it returned 25: callers that cut chunks on it stay bit-reproducible on large grids); additions:
                                * lspiv_upload_frames, lspiv_trace / lspiv_trace_read; the host-pointer projection entry points no longer
@@ -387,6 +388,41 @@ int lspiv_piv_masked_pairs_at(const void* frames, int dtype, int64_t T, int64_t 
                               int wy, int wx, int oy, int ox, const uint8_t* mask, int64_t k_min,
                               float signal_threshold, int64_t pair_offset,
                               float* u, float* v, float* corr_max, float* s2n, float* corr_planes);
+
+/* ---- Second correlation peak (additions, no ABI version change) ------------------------------------------
+ * How far a vector can be trusted: the height of the second highest correlation peak, the PEAK RATIO p1 / corr2 PIV practice validates
+ * with, and the runner-up vector that replaces a rejected one -- per window and pair, without the planes leaving the device.
+ * On the fft-shifted plane (the orientation of lspiv_u_v_displacement), with (ip, jp) the primary peak (first maximum in row-major order),
+ * p1 its height and r = peak_exclusion, 1 <= r <= N / 4: a sample s at (i, j) is a CANDIDATE when (1) s >= 1e-5 (five times the plane
+ * gate of 2e-6: float32 noise around an isolated peak is no peak), (2) (i, j) lies outside the box |i - ip| <= r and |j - jp| <= r, which
+ * is clipped at the plane edge and does not wrap, and (3) s >= each of its existing 4-neighbours -- a neighbour outside the plane does
+ * not exist, one inside the box counts; this is what takes out the flank of the primary peak.  The second peak is the candidate with the
+ * largest value, the first in row-major order among equals.  Per window the block peak2 holds four consecutive floats
+ *   {u2, v2, corr2, peak_ratio}: corr2 its height, peak_ratio = p1 / corr2, (u2, v2) its displacement by the primary's rule -- the
+ *   three-point log-Gaussian fit on plane + 1e-7 inside, "border_peak" on the plane border, "v_sign" on v2.
+ * No candidate: corr2 = 0, peak_ratio = +inf, u2 = v2 = NaN.  A skipped window (signal_threshold, non-finite input; a NaN plane) is NaN
+ * in all four.  The second peak is taken on the float32 plane at the float32 arg-max: the float64 rescue pass ("rescue") corrects u, v as
+ * after every per-pair kernel and leaves the four alone.
+ *
+ * lspiv_peak2_supported: 1 for wy = wx in {16, 32, 64}, else 0.  Host-only.
+ * lspiv_piv_peak2_pairs_dev_at: lspiv_piv_shift_pairs_dev_at without offsets -- d_out, d_corr_planes as lspiv_piv_pairs_dev_at lays them
+ * out, the same bits as that call with d_shift = NULL -- plus d_peak2: (T - 1) * n_win * 4 floats, 16-byte aligned.  One window per job,
+ * pair-local: every chunking gives the same bits; pair_offset is accepted for symmetry.  Options "norm_clip" = 0 and "signal_mode" = 1
+ * and every other window are LSPIV_EUNSUPPORTED; peak_exclusion outside 1 .. N / 4 is LSPIV_EINVAL.
+ * lspiv_piv_peak2_pairs_at: the host-fed twin, staged like lspiv_piv_pairs_at.
+ * lspiv_second_peak_dev / lspiv_second_peak: the same rule and the same fit on planes that already exist -- n_planes (P * n_win)
+ * fft-shifted float32 planes of wy x wx, 4 .. 4096 px per side, any shape, 1 <= peak_exclusion <= min(wy, wx) / 4 -- lspiv_piv_pairs'
+ * corr_planes, an ensemble's mean planes; p1 is the plane's first maximum.  On the planes lspiv_piv_peak2_pairs_dev_at returns, the four
+ * outputs are that call's bits. */
+int lspiv_peak2_supported(int wy, int wx);
+int lspiv_piv_peak2_pairs_dev_at(const void* d_frames, int dtype, int64_t T, int64_t H, int64_t W,
+                                 int wy, int wx, int oy, int ox, float signal_threshold, int64_t pair_offset, int peak_exclusion,
+                                 float* d_out, float* d_peak2, float* d_corr_planes, void* stream);
+int lspiv_piv_peak2_pairs_at(const void* frames, int dtype, int64_t T, int64_t H, int64_t W,
+                             int wy, int wx, int oy, int ox, float signal_threshold, int64_t pair_offset, int peak_exclusion,
+                             float* u, float* v, float* corr_max, float* s2n, float* peak2, float* corr_planes);
+int lspiv_second_peak_dev(const float* d_planes, int64_t n_planes, int wy, int wx, int peak_exclusion, float* d_peak2, void* stream);
+int lspiv_second_peak(const float* corr_planes, int64_t P, int64_t n_win, int wy, int wx, int peak_exclusion, float* peak2);
 
 /* Host frames into a slice of an HBM-resident stack, the way lspiv_piv_pairs brings them in -- pinned ring, staging threads,
  * float64 narrowed to float32 with the "narrow_offset" guard (so d_dst receives n_frames * H * W samples of LSPIV_F32 for LSPIV_F64

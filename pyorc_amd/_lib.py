@@ -96,6 +96,11 @@ SIGNATURES = {
     "lspiv_piv_masked_pairs_dev_at": (_i32, [_vp, _i32, _i64, _i64, _i64, _i32, _i32, _i32, _i32, _vp, _i64, _f32, _i64, _vp, _vp, _vp]),
     "lspiv_piv_masked_pairs_at": (_i32, [_vp, _i32, _i64, _i64, _i64, _i32, _i32, _i32, _i32, _vp, _i64, _f32, _i64, _vp, _vp, _vp, _vp, _vp]),
     "lspiv_u_v_displacement": (_i32, [_vp, _i64, _i64, _i32, _i32, _vp, _vp]),
+    "lspiv_peak2_supported": (_i32, [_i32, _i32]),
+    "lspiv_piv_peak2_pairs_dev_at": (_i32, [_vp, _i32, _i64, _i64, _i64, _i32, _i32, _i32, _i32, _f32, _i64, _i32, _vp, _vp, _vp, _vp]),
+    "lspiv_piv_peak2_pairs_at": (_i32, [_vp, _i32, _i64, _i64, _i64, _i32, _i32, _i32, _i32, _f32, _i64, _i32, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "lspiv_second_peak_dev": (_i32, [_vp, _i64, _i32, _i32, _i32, _vp, _vp]),
+    "lspiv_second_peak": (_i32, [_vp, _i64, _i64, _i32, _i32, _i32, _vp]),
     "lspiv_ensemble_begin": (_i32, [_i64, _i64, _i32, _i32, _i32, _i32, C.POINTER(_vp)]),
     "lspiv_ensemble_accumulate": (_i32, [_vp, _vp, _i32, _i64, _f32, _f32, _f32, _vp, _vp]),
     "lspiv_ensemble_accumulate_dev": (_i32, [_vp, _vp, _i32, _i64, _f32, _f32, _f32, _vp, _vp]),

@@ -66,6 +66,7 @@ struct DeviceCtx {
   uint8_t* d_keep = nullptr; size_t keep_cap = 0;      // per-window flags of the "stack" signal mode
   void* d_mp = nullptr; size_t mp_cap = 0;             // multi-pass chains: the intermediate passes' results and offsets (grow-only)
   uint8_t* d_mask = nullptr; size_t mask_cap = 0;      // the image mask of a host-fed masked launch (grow-only; under the host lock)
+  float* d_peak2 = nullptr; size_t peak2_cap = 0;      // the second-peak block of a host-fed launch (grow-only; under the host lock)
   float* d_deform = nullptr; size_t deform_cap = 0;    // deformation passes: the warped frames of one batch of pairs (grow-only; under the multipass lock)
   // float64 rescue pass: one set of lists per launch stream (a stream orders its own PIV kernel -> rescue kernel pairs;
   // two streams must not share counters), grow-only

@@ -2,6 +2,7 @@
 // pass after it, the chunk alignment, the device-pointer and host-pointer PIV entry points.
 #include "api_internal.h"
 #include "piv_masked.h"
+#include "piv_peak2.h"
 #include "piv_spof.h"
 
 #include <algorithm>
@@ -201,6 +202,7 @@ static int by_size(const Launcher (&l)[3], const lspiv::PivParams& p, int dtype,
   return launch_status(l[p.wy == 16 ? 0 : p.wy == 32 ? 1 : 2](p, dtype, s));
 }
 static const Launcher kMasked[3] = {lspiv::launch_piv_masked16, lspiv::launch_piv_masked32, lspiv::launch_piv_masked64};
+static const Launcher kPeak2[3] = {lspiv::launch_piv_peak2_16, lspiv::launch_piv_peak2_32, lspiv::launch_piv_peak2_64};
 static const Launcher kSpof[3] = {lspiv::launch_piv_spof16, lspiv::launch_piv_spof32, lspiv::launch_piv_spof64};
 static const Launcher kSpofEnsemble[3] = {lspiv::launch_piv_spof_ensemble16, lspiv::launch_piv_spof_ensemble32, lspiv::launch_piv_spof_ensemble64};
 static const Launcher kDeform[3] = {lspiv::launch_piv_deform16, lspiv::launch_piv_deform32, lspiv::launch_piv_deform64};
@@ -209,6 +211,10 @@ static const Launcher kShiftEnsemble[3] = {lspiv::launch_piv_shift_ensemble16, l
 static const Launcher kSearch[3] = {lspiv::launch_piv_search16, lspiv::launch_piv_search32, lspiv::launch_piv_search64};
 
 static int dispatch_kernels(const lspiv::PivParams& p, int dtype, bool ensemble, hipStream_t s, int filter) {
+  if (p.peak2) {   // second correlation peak: the one-window-per-job kernels of piv_peak2_impl.h, per pair, the plain rescue pass after them
+    if (ensemble || filter || p.mask || p.warped || p.shifted || p.nw) return fail(LSPIV_EUNSUPPORTED, "the second correlation peak has plain per-pair NCC kernels only");
+    return by_size(kPeak2, p, dtype, s);
+  }
   if (p.mask) {   // image mask: the one-window-per-job kernels of piv_masked_impl.h, per pair (the rescue pass after them reads p.mask too)
     if (ensemble || filter) return fail(LSPIV_EUNSUPPORTED, "an image mask has per-pair NCC kernels only");
     return by_size(kMasked, p, dtype, s);
@@ -314,6 +320,25 @@ int check_shift(int wy, int wx, int64_t H, int64_t W) {
 int check_spof(int wy, int wx) {
   LSPIV_TRY(check_fixed_square(wy, wx, "SPOF-filtered correlation"));
   return check_pair_options("SPOF-filtered correlation");
+}
+// second correlation peak: besides, the exclusion radius lies in 1 .. N / 4 and the output block is there, one aligned float4 per window
+static int check_peak2(int wy, int wx, int peak_exclusion, const void* peak2, bool in_hbm) {
+  LSPIV_TRY(check_fixed_square(wy, wx, "the second correlation peak"));
+  LSPIV_TRY(check_pair_options("the second correlation peak"));
+  if (peak_exclusion < 1 || peak_exclusion > wy / 4)
+    return fail(LSPIV_EINVAL, "peak_exclusion %d not in 1 .. %d (a quarter of the window)", peak_exclusion, wy / 4);
+  if (!peak2) return fail(LSPIV_EINVAL, "peak2 is NULL");
+  if (in_hbm && ((uintptr_t)peak2 & 15u)) return fail(LSPIV_EINVAL, "d_peak2 is not 16-byte aligned");   // (a host block goes through the context's own)
+  return LSPIV_OK;
+}
+// ... on planes: any plane of 4 .. 4096 px per side, the radius within a quarter of the shorter side
+static int check_second_peak(const void* planes, const void* peak2, int64_t n_planes, int wy, int wx, int peak_exclusion) {
+  if (!planes || !peak2) return fail(LSPIV_EINVAL, "NULL buffer");
+  if (n_planes < 0 || n_planes >= (int64_t)1 << 31) return fail(LSPIV_EINVAL, "%lld planes: not in 0 .. 2^31 - 1", (long long)n_planes);
+  if (wy < 4 || wx < 4 || wy > 4096 || wx > 4096) return fail(LSPIV_EINVAL, "plane %dx%d outside 4 .. 4096", wy, wx);
+  if (peak_exclusion < 1 || peak_exclusion > std::min(wy, wx) / 4)
+    return fail(LSPIV_EINVAL, "peak_exclusion %d not in 1 .. %d (a quarter of the plane)", peak_exclusion, std::min(wy, wx) / 4);
+  return LSPIV_OK;
 }
 // image mask: besides, k_min lies in 2 .. N^2
 static int check_masked(int wy, int wx, const void* mask, int64_t k_min) {
@@ -502,7 +527,9 @@ struct PairMode {
   int filter = 0;                  // LSPIV_FILTER_SPOF
   const uint8_t* mask = nullptr;   // the image mask of the frames' shape, where the entry point's frames are: HBM (_dev) or host
   int64_t k_min = 0;               // ... and the smallest count of valid samples of a window
-  bool per_pair() const { return nw || filter || mask; }   // one window pair per job: no anchors to cut launches at
+  float* peak2 = nullptr;          // the second-peak block n_tiles x {u2, v2, corr2, peak_ratio}, where the entry point's results are: HBM (_dev) or host
+  int peak_excl = 0;               // ... and the exclusion radius around the primary peak
+  bool per_pair() const { return nw || filter || mask || peak2; }   // one window pair per job: no anchors to cut launches at
 };
 // what every device-pointer entry point checks first
 static int check_dev_call(const void* d_frames, const void* d_out, int64_t pair_offset) {
@@ -524,6 +551,9 @@ static int piv_pairs_dev(const void* d_frames, int dtype, int64_t T, int64_t H, 
   set_results(&p, d_out, p.n_tiles, 0, d_corr_planes, 0);
   p.mask = m.mask;
   p.k_min = (uint32_t)m.k_min;
+  p.peak2 = m.peak2;
+  p.peak_excl = m.peak_excl;
+  p.peak2_v_neg = m.peak2 ? g_opt_v_sign.load() : 0;
   hipStream_t s = on_stream(c, stream);
   LSPIV_TRY(apply_signal_mode(c, &p, dtype, s));
   LSPIV_TRY(dispatch(p, dtype, false, s, m.filter));
@@ -552,6 +582,23 @@ int lspiv_piv_masked_pairs_dev_at(const void* d_frames, int dtype, int64_t T, in
   LSPIV_TRY(check_masked(wy, wx, d_mask, k_min));
   return piv_pairs_dev(d_frames, dtype, T, H, W, wy, wx, oy, ox, signal_threshold, pair_offset, d_out, d_corr_planes, stream,
                        {.mask = d_mask, .k_min = k_min});
+}
+
+int lspiv_peak2_supported(int wy, int wx) { return fixed_square_ok(wy, wx) ? 1 : 0; }
+
+int lspiv_piv_peak2_pairs_dev_at(const void* d_frames, int dtype, int64_t T, int64_t H, int64_t W, int wy, int wx, int oy, int ox,
+                                 float signal_threshold, int64_t pair_offset, int peak_exclusion, float* d_out, float* d_peak2,
+                                 float* d_corr_planes, void* stream) {
+  LSPIV_TRY(check_peak2(wy, wx, peak_exclusion, d_peak2, true));
+  return piv_pairs_dev(d_frames, dtype, T, H, W, wy, wx, oy, ox, signal_threshold, pair_offset, d_out, d_corr_planes, stream,
+                       {.peak2 = d_peak2, .peak_excl = peak_exclusion});
+}
+
+int lspiv_second_peak_dev(const float* d_planes, int64_t n_planes, int wy, int wx, int peak_exclusion, float* d_peak2, void* stream) {
+  LSPIV_TRY(check_second_peak(d_planes, d_peak2, n_planes, wy, wx, peak_exclusion));
+  return launch_on(stream, [&](hipStream_t s) {
+    return lspiv::launch_second_peak(d_planes, (uint32_t)n_planes, wy, wx, peak_exclusion, g_opt_border.load(), g_opt_v_sign.load(), d_peak2, s);
+  });
 }
 
 int lspiv_search_supported(int say, int sax, int wy, int wx) { return search_shape_ok(say, sax, wy, wx) ? 1 : 0; }
@@ -902,6 +949,11 @@ static int piv_pairs_host(const void* frames, int dtype, int64_t T, int64_t H, i
     base.mask = c->d_mask;
     base.k_min = (uint32_t)m.k_min;
   }
+  if (m.peak2) {   // the second-peak block of the whole stack in the context's own buffer: every launch writes its windows' float4s
+    LSPIV_TRY(ensure(&c->d_peak2, &c->peak2_cap, 4 * h.n_tiles * sizeof(float)));
+    base.peak_excl = m.peak_excl;
+    base.peak2_v_neg = g_opt_v_sign.load();
+  }
   const int64_t align = m.per_pair() ? 1 : std::max(1, chunk_alignment_for(wy, wx, (int64_t)h.n_win));
   // "stack" signal mode scores a window position over ALL frames of the chunk: one launch once everything is resident
   const bool whole_chunk_only = g_opt_signal_mode.load() == 1 && signal_threshold >= 0.0f;
@@ -924,6 +976,7 @@ static int piv_pairs_host(const void* frames, int dtype, int64_t T, int64_t H, i
       p.n_pairs = (uint32_t)(p1 - p0);
       p.n_tiles = (uint32_t)((p1 - p0) * h.n_win);
       set_results(&p, c->d_out, h.n_tiles, (size_t)p0 * h.n_win, corr_planes ? c->d_planes : nullptr, (size_t)wy * wx);
+      if (m.peak2) p.peak2 = c->d_peak2 + 4 * (size_t)p0 * h.n_win;
       LSPIV_TRY(apply_signal_mode(c, &p, h.dev_dtype, c->stream));
       LSPIV_TRY(dispatch(p, h.dev_dtype, false, c->stream, m.filter));
       LSPIV_TRY(apply_v_sign(p.v, (int64_t)p.n_tiles, c->stream));
@@ -939,6 +992,7 @@ static int piv_pairs_host(const void* frames, int dtype, int64_t T, int64_t H, i
     LSPIV_TRY(launch_status(lspiv::launch_scale_velocity(c->d_out, T - 1, (int64_t)h.n_win, (float)res_x, (float)res_y, (const double*)c->d_scratch, c->stream)));
   }
   LSPIV_TRY(results_to_host(h, u, v, corr_max, s2n, corr_planes, (size_t)wy * wx));
+  if (m.peak2) HIP_TRY(hipMemcpyAsync(m.peak2, c->d_peak2, 4 * h.n_tiles * sizeof(float), hipMemcpyDeviceToHost, c->stream));
   trace_end(&span, c->stream);
   HIP_TRY(hipStreamSynchronize(c->stream));
   return LSPIV_OK;
@@ -964,6 +1018,14 @@ int lspiv_piv_masked_pairs_at(const void* frames, int dtype, int64_t T, int64_t 
   LSPIV_TRY(check_masked(wy, wx, mask, k_min));
   return piv_pairs_host(frames, dtype, T, H, W, wy, wx, oy, ox, signal_threshold, pair_offset, u, v, corr_max, s2n, corr_planes,
                         {.mask = mask, .k_min = k_min});
+}
+
+int lspiv_piv_peak2_pairs_at(const void* frames, int dtype, int64_t T, int64_t H, int64_t W, int wy, int wx, int oy, int ox,
+                             float signal_threshold, int64_t pair_offset, int peak_exclusion, float* u, float* v, float* corr_max, float* s2n,
+                             float* peak2, float* corr_planes) {
+  LSPIV_TRY(check_peak2(wy, wx, peak_exclusion, peak2, false));
+  return piv_pairs_host(frames, dtype, T, H, W, wy, wx, oy, ox, signal_threshold, pair_offset, u, v, corr_max, s2n, corr_planes,
+                        {.peak2 = peak2, .peak_excl = peak_exclusion});
 }
 
 int lspiv_piv_search_pairs_at(const void* frames, int dtype, int64_t T, int64_t H, int64_t W, int say, int sax, int wy, int wx, int oy,
@@ -1004,6 +1066,18 @@ int lspiv_u_v_displacement(const float* corr_planes, int64_t P, int64_t n_win, i
   HIP_TRY(hipMemcpyAsync(v, c->d_out + n, n * sizeof(float), hipMemcpyDeviceToHost, c->stream));
   HIP_TRY(hipStreamSynchronize(c->stream));
   return LSPIV_OK;
+}
+
+int lspiv_second_peak(const float* corr_planes, int64_t P, int64_t n_win, int wy, int wx, int peak_exclusion, float* peak2) {
+  if (P < 0 || n_win < 0 || (n_win > 0 && P > (((int64_t)1 << 31) - 1) / n_win)) return fail(LSPIV_EINVAL, "bad shape");
+  const int64_t n = P * n_win;
+  LSPIV_TRY(check_second_peak(corr_planes, peak2, n, wy, wx, peak_exclusion));
+  if (n == 0) return LSPIV_OK;
+  const size_t pb = (size_t)n * wy * wx * sizeof(float);
+  RoundTrip io{corr_planes, pb, peak2, 4 * (size_t)n * sizeof(float)};
+  return host_roundtrip(__func__, io, [&](void* d_in, void* d_out, hipStream_t s) {
+    return lspiv_second_peak_dev((const float*)d_in, n, wy, wx, peak_exclusion, (float*)d_out, s);
+  });
 }
 
 }  // extern "C"

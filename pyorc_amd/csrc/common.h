@@ -128,6 +128,12 @@ struct PivParams {
   // below k_min of them (k_min >= 2, formed on the host)
   const uint8_t* mask;
   uint32_t k_min;
+  // second correlation peak (piv_peak2_impl.h): peak2 != nullptr selects the second-peak per-pair kernels --
+  // n_tiles x {u2, v2, corr2, peak_ratio}, 16-byte aligned, one float4 per result g; peak_excl = the half side r of the box around the
+  // primary peak in which no second peak is looked for, 1 .. N / 4; peak2_v_neg: "v_sign", v2 is written negated
+  float* peak2;
+  int peak_excl;
+  int peak2_v_neg;
 };
 
 // The offset of result g = pair * n_win + window (shifted ensemble pass: g = window; grid row wrow, column wcol), clamped so that the shifted window stays inside

@@ -75,6 +75,10 @@ def get_piv(frames, window_size=None, overlap=None, engine: str = "hip", ensembl
     ``image_mask`` / ``mask_coverage_min`` (in ``**kwargs``): an ``(H, W)`` mask of the valid pixels, non-zero = valid, and the smallest
     share of valid samples a window is evaluated at (default 0.25) -- every window is correlated over its valid samples only
     (INTEGRATION.md 2h), windows of 16, 32 or 64 px, per-timestep mode.
+    ``peak_ratio`` / ``peak_exclusion`` (in ``**kwargs``): ``peak_ratio=True`` adds ``peak_ratio``, ``corr2``, ``v_x2``, ``v_y2`` to the
+    result -- the ratio of the two highest correlation peaks, the second one's height and the runner-up vector (INTEGRATION.md 2i);
+    ``peak_exclusion`` (default 2) is the half side of the box around the primary peak that holds no second peak.  Windows of 16, 32 or
+    64 px, per-timestep mode.
     """
     if engine not in ENGINES:
         raise ValueError(f"Selected PIV engine {engine} does not exist.")

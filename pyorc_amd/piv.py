@@ -112,7 +112,8 @@ def _run_pairs(imgs, ws, ov, signal_threshold, return_planes, pair_offset, out, 
     as the host entry point's) -- else by numpy's own arithmetic on the host (:func:`_to_velocity`);
     ``extra(grid)``: the mode's extra input (mask, shift, nodes) for ``grid = (P, n_rows, n_cols)`` on the stack's side, an ndarray or a
     ``DeviceFrames``, or None;
-    ``aux``: the dtype of a per-window output ``(P, n_rows, n_cols, 2)`` the call fills besides the results (the chain's offsets).
+    ``aux``: the dtype of a per-window output ``(P, n_rows, n_cols, 2)`` the call fills besides the results (the chain's offsets), or
+    ``(dtype, width)`` for another trailing width (the second peak's four floats).
 
     Returns ``(u, v, corr_max, s2n[, planes][, aux])``."""
     from .device import DeviceFrames
@@ -131,7 +132,8 @@ def _run_pairs(imgs, ws, ov, signal_threshold, return_planes, pair_offset, out, 
     dev = is_device(a)
     x = extra((P, n_rows, n_cols)) if extra is not None else None
     if aux is not None:
-        aux = np.empty((P, n_rows, n_cols, 2), dtype=aux)
+        aux_dtype, aux_width = aux if isinstance(aux, tuple) else (aux, 2)
+        aux = np.empty((P, n_rows, n_cols, aux_width), dtype=aux_dtype)
     if dev:   # HBM-resident stack: no staging, one call, only the result block crosses PCIe
         res = DeviceFrames.empty((4, P, n_win), np.float32)
         planes = DeviceFrames.empty((P * n_win, ws[0], ws[1]), np.float32) if return_planes else None
@@ -164,6 +166,7 @@ _SPEC_MODES = {
     window.MultiPassWindow: ("coarse_passes", lambda imgs, spec, overlap, *a, **kw: piv_multipass(imgs, spec, *a, **kw)),
     window.FilteredWindow: ("spectral_filter", lambda imgs, spec, overlap, *a, **kw: piv_pairs_filtered(imgs, spec, overlap, spec.spectral_filter, *a, **kw)),
     window.MaskedWindow: ("image_mask", lambda imgs, spec, overlap, *a, **kw: piv_pairs_masked(imgs, spec, overlap, None, spec.mask_coverage_min, *a, **kw)),
+    window.PeakRatioWindow: ("peak_ratio", lambda imgs, spec, overlap, *a, **kw: piv_pairs_peak2(imgs, spec, overlap, spec.peak_exclusion, *a, **kw)),
 }
 # ... and the specs whose ``scale`` is numpy's arithmetic on the host for a host stack: no fused scaling entry point
 _HOST_SCALED = (window.SearchWindow, *_SPEC_MODES)
@@ -187,7 +190,7 @@ def piv_pairs(imgs, window_size=(32, 32), overlap=(16, 16), signal_threshold: Op
     (``say x sax`` each) are then those of the search area.  ``window_size`` may also be a ``window.SearchWindow``.
     """
     mode = _SPEC_MODES.get(type(window_size))
-    if mode is not None:   # a chain of passes, a spectral filter, an image mask (INTEGRATION.md sections 2d, 2g, 2h): the final grid is this call's
+    if mode is not None:   # a chain of passes, a spectral filter, an image mask, the second peak (INTEGRATION.md sections 2d, 2g, 2h, 2i): the final grid is this call's
         if search_area_size is not None and tuple(int(q) for q in search_area_size) != tuple(window_size):
             raise NotImplementedError(f"{mode[0]} together with a search_area_size larger than the window is not implemented")
         return mode[1](imgs, window_size, overlap, signal_threshold, return_planes, pair_offset, out=out, scale=scale)
@@ -255,6 +258,57 @@ def piv_pairs_masked(imgs, window_size=(32, 32), overlap=(16, 16), image_mask=No
                       ("lspiv_piv_masked_pairs_at", "lspiv_piv_masked_pairs_dev_at"),
                       lambda c: (*c.frames, *ws, *ov, c.extra, spec.k_min, *c.at, *c.res, c.planes),
                       extra=lambda grid: spec.device_mask() if is_device(a) else spec.image_mask)
+
+
+def piv_pairs_peak2(imgs, window_size=(32, 32), overlap=(16, 16), peak_exclusion: int = 2, signal_threshold: Optional[float] = None,
+                    return_planes: bool = False, pair_offset: int = 0, out=None, scale=None):
+    """PIV of every consecutive frame pair of ``imgs`` with the SECOND correlation peak of every window.
+    Returns ``(u, v, corr_max, s2n, peak2[, planes])``: the first four (and the planes) are the bits of :func:`piv_pairs_shifted` without
+    offsets; ``peak2`` is float32 ``(T-1, n_rows, n_cols, 4)`` = ``(u2, v2, corr2, peak_ratio)`` -- the runner-up vector in pixels, the
+    height of the second highest peak and ``corr_max / corr2``.  On the fft-shifted plane a sample is a candidate when it is at least
+    1e-5, lies outside the box of half side ``peak_exclusion`` (1 .. n // 4) around the primary peak (clipped at the edge, no wrap) and
+    is no smaller than any of its existing 4-neighbours; the second peak is the largest candidate, the first in row-major order.  No
+    candidate: ``corr2 = 0``, ``peak_ratio = inf``, ``u2 = v2 = NaN``; a skipped window is NaN in all four.  ``(u2, v2)`` follow the
+    primary's rule (log-Gaussian fit inside, "border_peak" on the border, "v_sign").  The float64 rescue pass corrects u, v and leaves
+    ``peak2`` alone.  ``window_size``: square, 16, 32 or 64 px, or a ``window.PeakRatioWindow`` (which carries its own radius).
+    Pair-local, one window per job: every chunking gives the same bits (``pair_offset`` is accepted for symmetry).  ``out`` / ``scale``
+    as in :func:`piv_pairs` (the scaling is numpy's own arithmetic on the host, on u, v and on u2, v2).  Host stacks and ``DeviceFrames``."""
+    if isinstance(window_size, window.PeakRatioWindow):
+        spec = window_size
+    else:
+        spec = window.peak_ratio_spec(window_size, True, peak_exclusion)   # ValueError: sizes, radius; NotImplementedError: another mode's spec
+    ws, r = (int(spec[0]), int(spec[1])), int(spec.peak_exclusion)
+    ov = (int(overlap[0]), int(overlap[1]))
+    ret = _run_pairs(imgs, ws, ov, signal_threshold, return_planes, pair_offset, out, scale,
+                     ("lspiv_piv_peak2_pairs_at", "lspiv_piv_peak2_pairs_dev_at"),
+                     lambda c: (*c.frames, *ws, *ov, *c.at, r, *c.res, c.aux, c.planes), aux=(np.float32, 4))
+    peak2 = ret[-1]
+    if scale is not None:
+        dt = np.ascontiguousarray(scale[2], dtype=np.float64).reshape(-1)[:, None, None]
+        for k in range(2):
+            _to_velocity(peak2[..., k], scale[k], dt, out=peak2[..., k])
+    return (*ret[:4], peak2, *ret[4:-1])
+
+
+def second_peak(planes, peak_exclusion: int = 2) -> np.ndarray:
+    """The second correlation peak of planes that already exist (mirrors :func:`u_v_displacement`): ``planes``
+    ``(P, n_win, wy, wx)`` (or ``(n_win, wy, wx)``) float32, fft-shifted -- :func:`cross_corr` output, ``return_planes``, an ensemble's mean
+    planes -- -> float32 ``(P, n_win, 4)`` = ``(u2, v2, corr2, peak_ratio)`` by the rule and the fit of :func:`piv_pairs_peak2`, on the
+    device.  Any plane shape of 4 .. 4096 px per side; ``peak_exclusion`` in 1 .. min(wy, wx) // 4.  A NaN plane is NaN in all four."""
+    c = np.ascontiguousarray(planes, dtype=np.float32)
+    if c.ndim == 3:
+        c = c[None]
+    if c.ndim != 4:
+        raise ValueError(f"planes must have shape (P, n_win, wy, wx), got {c.shape}")
+    P, n_win, wy, wx = c.shape
+    if min(wy, wx) < 4 or max(wy, wx) > 4096:
+        raise ValueError(f"planes of {wy} x {wx}: a side outside 4 .. 4096")
+    r = window.exclusion_spec(peak_exclusion, min(wy, wx))
+    lib = _lib.load()
+    _lib.require_device()
+    out = np.empty((P, n_win, 4), dtype=np.float32)
+    _lib.check(lib.lspiv_second_peak(_lib.ptr(c), P, n_win, wy, wx, r, _lib.ptr(out)))
+    return out
 
 
 def piv_pairs_shifted(imgs, window_size=(32, 32), overlap=(16, 16), shift=None, signal_threshold: Optional[float] = None,
@@ -447,9 +501,6 @@ class Ensemble:
     """Device-resident ensemble-correlation accumulator (pyorc/velocimetry/ffpiv.py:182-376)."""
 
     def __init__(self, dim_size, window_size, overlap, sliding=None, shift=None, spectral_filter=None):
-        if isinstance(window_size, window.MaskedWindow):
-            raise NotImplementedError("image_mask together with ensemble_corr=True is not implemented: the ensemble kernels and their "
-                                      "float64 rescue have no masked form")
         """``sliding=(M, s)``: a sliding ensemble (INTEGRATION.md section 2c) -- outputs over windows of M pairs that advance by s
         pairs, read with :meth:`finish_sliding`; every ``accumulate`` but the last must then hold a multiple of s pairs.
         ``shift``: int16 ``(n_rows, n_cols, 2)`` = (dy, dx) per window, or a ``DeviceFrames`` holding those bytes -- a SHIFTED ensemble pass
@@ -459,6 +510,12 @@ class Ensemble:
         ``window_size`` carries its own) -- the planes summed are the SPOF phase-filtered ones of :func:`piv_pairs_filtered`; ``corr_min`` /
         ``s2n_min`` keep their meaning, their useful values are lower.  Windows of 16, 32 or 64 px; every chunking gives the same bits;
         no float64 rescue of the final fit.  Not together with ``sliding`` or ``shift``."""
+        if isinstance(window_size, window.MaskedWindow):
+            raise NotImplementedError("image_mask together with ensemble_corr=True is not implemented: the ensemble kernels and their "
+                                      "float64 rescue have no masked form")
+        if isinstance(window_size, window.PeakRatioWindow):
+            raise NotImplementedError("peak_ratio together with ensemble_corr=True is not implemented: the ensemble kernels have no "
+                                      "second-peak form; use piv.second_peak on the mean planes of finish(return_mean=True) instead")
         flt = window.spectral_filter_spec(spectral_filter)
         if isinstance(window_size, window.FilteredWindow):
             flt = flt or window_size.spectral_filter

@@ -130,6 +130,8 @@ def _wrap_get_piv(orig):
         spectral = kwargs.pop("spectral_filter", None)
         # ... and the image mask's `image_mask=` / `mask_coverage_min=`
         masked = {k: kwargs.pop(k) for k in ("image_mask", "mask_coverage_min") if k in kwargs}
+        # ... and the second correlation peak's `peak_ratio=` / `peak_exclusion=`
+        second = {k: kwargs.pop(k) for k in ("peak_ratio", "peak_exclusion") if k in kwargs}
         engine, bound = kwargs.get("engine"), None
         if sig is not None and "engine" in sig.parameters:
             try:
@@ -150,6 +152,8 @@ def _wrap_get_piv(orig):
                 raise TypeError("spectral_filter is a keyword of engine='hip' only")
             if masked:
                 raise TypeError(f"{' / '.join(masked)} is a keyword of engine='hip' only")
+            if second:
+                raise TypeError(f"{' / '.join(second)} is a keyword of engine='hip' only")
             return orig(self, *args, **kwargs)
         # fail before any work if there is no MI355X / no library: the reference raises ValueError for an engine it cannot run
         from . import _lib
@@ -173,6 +177,8 @@ def _wrap_get_piv(orig):
             window_mod.coverage_spec(masked.get("mask_coverage_min", 0.25))     # ValueError outside (0, 1]
             if masked.get("image_mask") is not None:                             # None is today's path
                 extra.update(masked)
+        if second.get("peak_ratio"):                                             # False is today's path
+            extra.update(second)
         if search_area is not None or sliding or extra:
             # the reference's method body lays the grid out by the window; with a search area of its own the engine's mirror of that
             # body (pyorc_amd.frames.get_piv: same configuration copy, coordinates, attributes and encoding) runs instead -- and with the

@@ -70,6 +70,9 @@ def _no_multipass(window_size) -> None:
     """A multi-pass chain (``window.MultiPassWindow``) is not sharded over ranks."""
     from . import window
 
+    if isinstance(window_size, window.PeakRatioWindow):
+        raise NotImplementedError("peak_ratio with pyorc_amd.shard is not implemented: run it through get_ffpiv (devices=), or use "
+                                  "piv.second_peak on the planes instead")
     if isinstance(window_size, window.MaskedWindow):
         raise NotImplementedError("image_mask with pyorc_amd.shard is not implemented: run the masked correlation through get_ffpiv (devices=)")
     if isinstance(window_size, window.FilteredWindow):

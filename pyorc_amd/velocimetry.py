@@ -182,6 +182,8 @@ def get_ffpiv(
     spectral_filter=None,
     image_mask=None,
     mask_coverage_min: float = 0.25,
+    peak_ratio: bool = False,
+    peak_exclusion: int = 2,
 ):
     """Compute time-resolved (or ensemble) PIV on the MI355X; signature of pyorc's ``get_ffpiv`` (ffpiv.py:24-42).
 
@@ -237,6 +239,16 @@ def get_ffpiv(
     Windows of 16, 32 or 64 px, per-timestep mode.  Pair-local: ``chunksize=``, ``devices=``, host stacks, ``DeviceFrames`` and lazy
     stacks give the same bits; the mask goes to each device once per call.  Not with ``ensemble_corr=True``, ``coarse_passes``,
     ``deform_passes``, a search area, ``spectral_filter`` or ``ensemble_window``.
+
+    ``peak_ratio`` (the project's own mode; False: today's path bit for bit): the result gains ``peak_ratio``
+    (height of the highest correlation peak over the second highest: what PIV practice validates a vector with), ``corr2`` (that second
+    height) and ``v_x2``, ``v_y2`` (the runner-up vector, scaled like ``v_x``, ``v_y``: the usual substitute for a rejected one).  The
+    second peak is the largest sample of the plane that is at least 1e-5, lies outside the box of half side ``peak_exclusion`` (1 ..
+    n // 4, default 2) around the primary peak and is no smaller than its 4-neighbours; without one ``corr2`` = 0, ``peak_ratio`` = inf
+    and the vector NaN.  ``s2n``, ``corr``, ``v_x``, ``v_y`` are those of ``peak_ratio=False`` up to the last float32 bit of the
+    one-window-per-job kernels.  Windows of 16, 32 or 64 px, per-timestep mode.  Pair-local: ``chunksize=``, ``devices=``, host stacks,
+    ``DeviceFrames`` and lazy stacks give the same bits.  Not with ``image_mask``, ``spectral_filter``, ``coarse_passes``,
+    ``deform_passes``, a search area or ``ensemble_corr=True`` (NotImplementedError): ``piv.second_peak`` on their planes serves those.
     """
     if engine != "hip":
         raise ValueError(f"Selected PIV engine {engine} does not exist.")
@@ -286,6 +298,12 @@ def get_ffpiv(
                                   "serve per-timestep mode only")
     if flt is not None:
         window_size = window.filtered_spec(window_size, flt)     # NotImplementedError with a search area, ValueError for another window
+    if peak_ratio:
+        if ensemble_corr:
+            raise NotImplementedError("peak_ratio together with ensemble_corr=True is not implemented: the ensemble kernels have no "
+                                      "second-peak form; use piv.second_peak on the mean planes instead")
+        # (NotImplementedError naming the other keyword for another mode's window, ValueError for another window or radius)
+        window_size = window.peak_ratio_spec(window_size, True, peak_exclusion)
     sliding = window.sliding_spec(ensemble_corr, ensemble_window, ensemble_stride)
     n_frames = len(frames)
     dim_size = tuple(frames[0].shape)
@@ -312,9 +330,9 @@ def get_ffpiv(
     align = window.chunk_alignment(window_size, dim_size, overlap)
     stack_mode = _stack_signal_mode(signal_threshold)
     # (a chain's later passes read every frame of a chunk at offsets of their own: a lazy stack takes the chunk-loading path; so do a
-    # filtered and a masked run, whose per-pair entry points take chunks)
+    # filtered, a masked and a second-peak run, whose per-pair entry points take chunks)
     resident_run = (_is_lazy(frames) and n_frames >= 2 and not stack_mode and
-                    not isinstance(window_size, (window.MultiPassWindow, window.FilteredWindow, window.MaskedWindow)))
+                    not isinstance(window_size, (window.MultiPassWindow, window.FilteredWindow, window.MaskedWindow, window.PeakRatioWindow)))
     if resident_run:
         # a lazy stack: resident in HBM, loads planned against HOST memory and cut where dask cuts, launches on the anchors
         work = plan_lazy_devices(frames, n_frames, dim_size, window_size, overlap, n_win, chunksize, memory_factor, engine, prefetch, devs)
@@ -540,7 +558,9 @@ def _timestep_sink(n_pairs, n_workers, y, x, dt, res_x, res_y, window_size, over
     launch writes its time slice of them (corr, s2n straight from the library, v_x / v_y through the px -> m/s scaling): no per-chunk
     arrays to concatenate at the end (the reference's xr.concat, ffpiv.py:442 -- 125 KB per pair, i.e. as many bytes again as a uint8
     chunk's upload at 32 x 32)."""
-    full = {k: np.empty((n_pairs, len(y), len(x)), dtype=np.float32) for k in ("s2n", "corr", "v_x", "v_y")}
+    peak2 = isinstance(window_size, window.PeakRatioWindow)     # (INTEGRATION.md section 2i: four more variables)
+    names = ("s2n", "corr", "v_x", "v_y") + (("peak_ratio", "corr2", "v_x2", "v_y2") if peak2 else ())
+    full = {k: np.empty((n_pairs, len(y), len(x)), dtype=np.float32) for k in names}
     done = []
     px = [None] * n_workers            # per worker: scratch for a launch's u, v in pixels
     # (the modes whose entry points have no fused scaling: numpy's arithmetic on the host, the same bits)
@@ -559,11 +579,17 @@ def _timestep_sink(n_pairs, n_workers, y, x, dt, res_x, res_y, window_size, over
             if px[k] is None or px[k][0].shape[0] < p:
                 px[k] = [np.empty((p, len(y), len(x)), dtype=np.float32) for _ in range(2)]
             uv, scale = (px[k][0][:p], px[k][1][:p]), None
-        piv.piv_pairs(frames, window_size, overlap, signal_threshold, pair_offset=p0, scale=scale,
-                      out=uv + (full["corr"][p0:p1], full["s2n"][p0:p1]))
+        ret = piv.piv_pairs(frames, window_size, overlap, signal_threshold, pair_offset=p0, scale=scale,
+                            out=uv + (full["corr"][p0:p1], full["s2n"][p0:p1]))
         if scale is None:
             _to_velocity(uv[0], res_x, dt_chunk[:, None, None], out=full["v_x"][p0:p1])
             _to_velocity(uv[1], res_y, dt_chunk[:, None, None], out=full["v_y"][p0:p1])
+        if peak2:     # (u2, v2, corr2, peak_ratio) per window: the runner-up vector scaled like u, v (host arithmetic: scale is None here)
+            second = ret[4]
+            _to_velocity(second[..., 0], res_x, dt_chunk[:, None, None], out=full["v_x2"][p0:p1])
+            _to_velocity(second[..., 1], res_y, dt_chunk[:, None, None], out=full["v_y2"][p0:p1])
+            full["corr2"][p0:p1] = second[..., 2]
+            full["peak_ratio"][p0:p1] = second[..., 3]
         done.append((p0, p1))
 
     def result(time, like):

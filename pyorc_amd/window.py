@@ -295,6 +295,60 @@ def masked_spec(window_size, image_mask=None, mask_coverage_min: float = 0.25, d
     return spec
 
 
+PEAK2_WINDOWS = (16, 32, 64)
+
+
+class PeakRatioWindow(tuple):
+    """A window whose launch also hands out the second correlation peak, as ONE window argument of the layers
+    below ``get_ffpiv`` / ``piv_pairs``: the tuple itself is the window ``(wy, wx)`` -- grid and planes are the plain per-pair launch's --,
+    ``.peak_exclusion`` the half side r of the box around the primary peak in which no second peak is looked for.  The second-peak
+    kernels are per-pair: the chunk alignment is 1."""
+
+    def __new__(cls, window_size, peak_exclusion: int = 2):
+        self = super().__new__(cls, (int(window_size[0]), int(window_size[1])))
+        self.peak_exclusion = exclusion_spec(peak_exclusion, min(self))
+        return self
+
+
+def exclusion_spec(value, n: int) -> int:
+    """``peak_exclusion`` checked for a plane whose shorter side is ``n``: a whole number in 1 .. n // 4, else a ValueError.  Host-only."""
+    if isinstance(value, bool) or not isinstance(value, (int, np.integer)) or not 1 <= int(value) <= int(n) // 4:
+        raise ValueError(f"peak_exclusion must be a whole number in 1 .. {int(n) // 4} (a quarter of the {int(n)} px plane), got {value!r}")
+    return int(value)
+
+
+def peak2_supported(window_size) -> Tuple[int, int]:
+    """``window_size`` as a pair of ints when the second-peak kernels serve it (``lspiv_peak2_supported``: square, 16, 32 or 64), else a
+    ValueError naming the sizes.  Host-only."""
+    ws = 2 * (window_size,) if isinstance(window_size, (int, np.integer)) else tuple(window_size)
+    if len(ws) != 2 or not _lib.load().lspiv_peak2_supported(int(ws[0]), int(ws[1])):
+        raise ValueError(f"window_size {window_size!r} is not supported with peak_ratio: the window must be square and one of {PEAK2_WINDOWS}")
+    return int(ws[0]), int(ws[1])
+
+
+def peak_ratio_spec(window_size, peak_ratio: bool = False, peak_exclusion: int = 2):
+    """``window_size`` as the layers below take it: unchanged without ``peak_ratio`` (today's path), else a validated
+    :class:`PeakRatioWindow`.  Not together with a search area, a multi-pass chain, deformation passes, a spectral filter or an image mask
+    (NotImplementedError naming both keywords): ``piv.second_peak`` on their planes serves those."""
+    if isinstance(window_size, PeakRatioWindow):
+        return window_size
+    if not peak_ratio:
+        return window_size
+    hint = "; use piv.second_peak on its planes instead"
+    if isinstance(window_size, SearchWindow):
+        raise NotImplementedError("peak_ratio together with a search_area_size larger than the window is not implemented: the second-peak "
+                                  "kernels correlate two windows of one size" + hint)
+    if isinstance(window_size, MultiPassWindow):
+        raise NotImplementedError(("peak_ratio together with deform_passes" if window_size.deform and len(window_size.passes) == 1
+                                   else "peak_ratio together with coarse_passes") + " is not implemented: the shifted and the "
+                                  "deformation kernels have no second-peak form" + hint)
+    if isinstance(window_size, FilteredWindow):
+        raise NotImplementedError("peak_ratio together with spectral_filter is not implemented: the filtered kernels have no second-peak form" + hint)
+    if isinstance(window_size, MaskedWindow):
+        raise NotImplementedError("peak_ratio together with image_mask is not implemented: the masked kernels have no second-peak form" + hint)
+    return PeakRatioWindow(peak2_supported(window_size), peak_exclusion)
+
+
 MIN_STEERING_GRID = 3
 
 
@@ -356,7 +410,8 @@ def required_memory(n_frames: int, dim_size, window_size, overlap, search_area_s
     that needs most, in a chain (the multi-pass ensemble, INTEGRATION.md section 2e, runs one pass at a time).
     ``deform_passes`` (or a :class:`MultiPassWindow` that carries them): the warped frames of one batch of pairs and the nodes
     (:func:`deform_bytes`) come on top.  A :class:`FilteredWindow` answers as the plain per-pair launch of its window: the filtered
-    kernels have no workspace.  A :class:`MaskedWindow` answers as the plain per-pair launch of its window plus the bytes of the mask.
+    kernels have no workspace.  A :class:`MaskedWindow` answers as the plain per-pair launch of its window plus the bytes of the mask, a
+    :class:`PeakRatioWindow` plus the four floats of the second peak per window and pair.
     """
     if coarse_passes or deform_count(deform_passes) or isinstance(window_size, MultiPassWindow):
         # a chain: the frames once, the largest pass's launch (results, rescue lists, the planes of the final pass), and the
@@ -378,6 +433,8 @@ def required_memory(n_frames: int, dim_size, window_size, overlap, search_area_s
     need = _lib.check(r)
     if isinstance(window_size, MaskedWindow):
         need += int(window_size.image_mask.nbytes)
+    if isinstance(window_size, PeakRatioWindow):
+        need += 16 * (int(n_frames) - 1) * int(np.prod(get_array_shape(dim_size, sa, overlap)))
     if sliding_blocks:
         need += sliding_store_bytes(sliding_blocks, dim_size, sa, overlap)
     if ensemble_sums:
@@ -470,8 +527,8 @@ def chunk_alignment(window_size, dim_size=None, overlap=None) -> int:
     that shape are cut.  Without them the alignment that is right on EVERY grid comes back (``lspiv_chunk_alignment``, ABI 5: the
     longest anchor length of the window family, a multiple of every grid's -- 75 where ABI 4 answered 25)."""
     lib = _lib.load()
-    if isinstance(window_size, (SearchWindow, FilteredWindow, MaskedWindow)):
-        return 1   # the search-area, the filtered and the masked kernels are per-pair: any chunking gives the same bits
+    if isinstance(window_size, (SearchWindow, FilteredWindow, MaskedWindow, PeakRatioWindow)):
+        return 1   # the search-area, the filtered, the masked and the second-peak kernels are per-pair: any chunking gives the same bits
     if isinstance(window_size, MultiPassWindow):
         # pass 0 is the per-timestep path on ITS window and grid; every later pass is pair-local
         n0, o0 = window_size.passes[0]
