@@ -101,13 +101,18 @@ def warp_stack(imgs, n, overlap, nodes):
 
 
 def deformed_piv(imgs, n, overlap, nodes=None, signal_threshold=None):
-    """One deformation pass: the plain oracle between frame t and the warped frame t+1 on the grid (n, overlap), plus the window's own
+    """One deformation pass (``overlap`` an int, or a pair (oy, ox) with oy == ox: like the library's, the node grid of this pass has one
+    stride for both axes): the plain oracle between frame t and the warped frame t+1 on the grid (n, overlap), plus the window's own
     node.  dict(u, v, corr, s2n (T-1, rows, cols), planes (T-1, n_win, n, n), tie, nodes, warped, x, y).  ``imgs`` in the stack's own
     sample type (the warp of float frames is float32 arithmetic)."""
     imgs = np.asarray(imgs)
     T, H, W = imgs.shape
     if n not in DEFORM_WINDOWS:
         raise ValueError(f"window {n} not in {DEFORM_WINDOWS}")
+    oy, ox = mp.overlap_pair(overlap)
+    if oy != ox:
+        raise ValueError(f"overlap {(oy, ox)}: the deformation pass takes one overlap for both axes")
+    overlap = oy
     if po.SEMANTICS["signal_mode"] == 1 or not po.SEMANTICS["norm_clip"]:
         raise NotImplementedError("deformation pass: signal_mode = 1 and norm_clip = 0 are not supported")
     x, y = po.get_rect_coordinates((H, W), (n, n), (overlap, overlap))

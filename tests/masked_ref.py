@@ -42,13 +42,13 @@ def plane(A, B, M, k):
 
 def window_masks(mask, n, overlap):
     """(M (n_win, n, n) bool, k (n_win,) int) of the window grid."""
-    M = po.sliding_window_stack((np.asarray(mask) != 0)[None], (n, n), (overlap, overlap))[0]
+    M = po.sliding_window_stack((np.asarray(mask) != 0)[None], (n, n), multipass_ref.overlap_pair(overlap))[0]
     return M, M.sum(axis=(-2, -1))
 
 
 def piv(imgs, n, overlap, mask, coverage_min=COVERAGE_MIN, signal_threshold=None):
-    """The per-pair result under ``mask`` (H, W): dict(u, v, corr, s2n (T-1, rows, cols), planes (T-1, n_win, n, n), k (n_win,), tie,
-    fragile (T-1, rows, cols)).  A window below k_min, a pair failing the signal threshold -- the share of signal samples among the valid
+    """The per-pair result under ``mask`` (H, W), ``overlap`` an int or a pair (oy, ox): dict(u, v, corr, s2n (T-1, rows, cols),
+    planes (T-1, n_win, n, n), k (n_win,), tie, fragile (T-1, rows, cols)).  A window below k_min, a pair failing the signal threshold -- the share of signal samples among the valid
     ones, of A and of B -- or one with a non-finite VALID sample is NaN throughout.  tie: the top two samples of the plane are equal
     within 1e-12 relative; fragile: spof_ref.fragile_mask."""
     imgs = np.asarray(imgs)
@@ -57,9 +57,10 @@ def piv(imgs, n, overlap, mask, coverage_min=COVERAGE_MIN, signal_threshold=None
     if po.SEMANTICS["signal_mode"] == 1 or not po.SEMANTICS["norm_clip"]:
         raise NotImplementedError("masked correlation: signal_mode = 1 and norm_clip = 0 are not supported")
     T = imgs.shape[0]
-    rows, cols = po.get_axis_shape(imgs.shape[1], n, overlap), po.get_axis_shape(imgs.shape[2], n, overlap)
+    oy, ox = multipass_ref.overlap_pair(overlap)
+    rows, cols = po.get_axis_shape(imgs.shape[1], n, oy), po.get_axis_shape(imgs.shape[2], n, ox)
     with np.errstate(invalid="ignore"):
-        stack = po.sliding_window_stack(imgs.astype(np.float64), (n, n), (overlap, overlap))      # (T, n_win, n, n)
+        stack = po.sliding_window_stack(imgs.astype(np.float64), (n, n), (oy, ox))                # (T, n_win, n, n)
     M, k = window_masks(mask, n, overlap)
     kmin = k_min(n, coverage_min)
     planes = np.full((T - 1,) + stack.shape[1:], np.nan)

@@ -14,9 +14,17 @@ from oracle import piv_oracle as po
 SHIFT_WINDOWS = (16, 32, 64)
 
 
+def overlap_pair(overlap):
+    """``overlap`` as (oy, ox): an int stands for both axes."""
+    if isinstance(overlap, (int, np.integer)):
+        return int(overlap), int(overlap)
+    oy, ox = overlap
+    return int(oy), int(ox)
+
+
 def grid_origins(dim_size, n, overlap):
-    """(y0 (rows,), x0 (cols,)) of the n x n windows at the given overlap."""
-    y0, x0 = po.window_origins(dim_size, (n, n), (overlap, overlap))
+    """(y0 (rows,), x0 (cols,)) of the n x n windows at the given overlap, an int or a pair (oy, ox)."""
+    y0, x0 = po.window_origins(dim_size, (n, n), overlap_pair(overlap))
     return np.asarray(y0, dtype=np.int64), np.asarray(x0, dtype=np.int64)
 
 
@@ -31,20 +39,20 @@ def clamp_shift(shift, dim_size, n, overlap):
 
 
 def shifted_piv(imgs, n, overlap, shift=None, signal_threshold=None):
-    """One shifted pass.  dict(u, v, corr, s2n (T-1, rows, cols), planes (T-1, n_win, n, n), tie, shift = the CLAMPED offsets, x, y).
-    A = window of frame t at (y0, x0), B = window of frame t+1 at (y0 + dy, x0 + dx); everything else is the plain path's.  ``tie``
+    """One shifted pass; ``overlap`` an int or a pair (oy, ox).  dict(u, v, corr, s2n (T-1, rows, cols), planes (T-1, n_win, n, n), tie,
+    shift = the CLAMPED offsets, x, y).  A = window of frame t at (y0, x0), B = window of frame t+1 at (y0 + dy, x0 + dx); everything else is the plain path's.  ``tie``
     marks the windows whose arg-max is a matter of rounding in any implementation (an exact float64 tie for the plane maximum)."""
     imgs = np.asarray(imgs)
     T, H, W = imgs.shape
     if po.SEMANTICS["signal_mode"] == 1 or not po.SEMANTICS["norm_clip"]:
         raise NotImplementedError("multi-pass PIV: signal_mode = 1 and norm_clip = 0 are not supported")
-    x, y = po.get_rect_coordinates((H, W), (n, n), (overlap, overlap))
+    x, y = po.get_rect_coordinates((H, W), (n, n), overlap_pair(overlap))
     y0, x0 = grid_origins((H, W), n, overlap)
     rows, cols = len(y0), len(x0)
     if shift is None:
         shift = np.zeros((T - 1, rows, cols, 2), dtype=np.int64)
     sh = clamp_shift(np.asarray(shift).reshape(T - 1, rows, cols, 2), (H, W), n, overlap)
-    stack = po.sliding_window_stack(imgs, (n, n), (overlap, overlap))                      # (T, n_win, n, n)
+    stack = po.sliding_window_stack(imgs, (n, n), overlap_pair(overlap))                   # (T, n_win, n, n)
     planes = np.full((T - 1, rows * cols, n, n), np.nan)
     ar = np.arange(n)
     for t in range(T - 1):

@@ -138,8 +138,8 @@ def on_planes(planes, r, with_fragile=True):
 
 
 def piv(imgs, n, overlap, r=2, signal_threshold=None):
-    """``spof_ref.piv(..., fn=spof_ref.ncc_plane)`` plus the second peak of every plane: u2, v2, corr2, ratio, found, i2, j2 as
-    (P, rows, cols), ``fragile2`` = the windows left out of the gates (``spof_ref.fragile_mask`` or :func:`fragile_plane`)."""
+    """``spof_ref.piv(..., fn=spof_ref.ncc_plane)`` (``overlap`` an int or a pair (oy, ox)) plus the second peak of every plane: u2, v2,
+    corr2, ratio, found, i2, j2 as (P, rows, cols), ``fragile2`` = the windows left out of the gates (``spof_ref.fragile_mask`` or :func:`fragile_plane`)."""
     res = dict(spof_ref.piv(imgs, n, overlap, signal_threshold, fn=spof_ref.ncc_plane))
     shape = res["corr"].shape
     second = on_planes(res["planes"], r)

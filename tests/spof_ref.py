@@ -12,7 +12,7 @@ import numpy as np
 
 from oracle import piv_oracle as po
 from pyorc_amd import synth
-from tests import deform_ref
+from tests import deform_ref, multipass_ref
 
 SPOF_WINDOWS = (16, 32, 64)
 
@@ -42,7 +42,7 @@ def _planes(imgs, n, overlap, signal_threshold, fn):
     if po.SEMANTICS["signal_mode"] == 1 or not po.SEMANTICS["norm_clip"]:
         raise NotImplementedError("filtered correlation: signal_mode = 1 and norm_clip = 0 are not supported")
     T = imgs.shape[0]
-    stack = po.sliding_window_stack(imgs.astype(np.float64), (n, n), (overlap, overlap))      # (T, n_win, n, n)
+    stack = po.sliding_window_stack(imgs.astype(np.float64), (n, n), multipass_ref.overlap_pair(overlap))       # (T, n_win, n, n)
     out = np.full((T - 1,) + stack.shape[1:], np.nan)
     with np.errstate(all="ignore"):
         for t in range(T - 1):
@@ -54,7 +54,8 @@ def _planes(imgs, n, overlap, signal_threshold, fn):
 
 
 def _grid(dim_size, n, overlap):
-    return po.get_axis_shape(dim_size[0], n, overlap), po.get_axis_shape(dim_size[1], n, overlap)
+    oy, ox = multipass_ref.overlap_pair(overlap)
+    return po.get_axis_shape(dim_size[0], n, oy), po.get_axis_shape(dim_size[1], n, ox)
 
 
 def fragile_mask(planes):
@@ -81,7 +82,7 @@ def fragile_mask(planes):
 
 
 def piv(imgs, n, overlap, signal_threshold=None, fn=plane):
-    """The per-pair result: dict(u, v, corr, s2n (T-1, rows, cols), planes (T-1, n_win, n, n), fragile (T-1, rows, cols)).  corr = max of
+    """The per-pair result (``overlap`` an int or a pair (oy, ox)): dict(u, v, corr, s2n (T-1, rows, cols), planes (T-1, n_win, n, n), fragile (T-1, rows, cols)).  corr = max of
     the plane, s2n = max / mean of the clipped plane; a pair failing the signal threshold, or with a non-finite sample, is NaN throughout.
     ``fn``: :func:`plane` (the filter) or :func:`ncc_plane` (the unfiltered path, for comparisons)."""
     imgs = np.asarray(imgs)
