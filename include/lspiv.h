@@ -782,8 +782,8 @@ int lspiv_debug_narrow(const double* frames, int64_t frame_elems, int64_t n_fram
  * interleaved (re, im) float pairs; n = 8, 16, 32, 64 or any even length 6..62 (the sizes lspiv_kernel_kind maps to 6 / 8). */
 int lspiv_debug_fft(int n, int inverse, const float* in, float* out, int64_t count);
 /* The same with the twiddle path of n = 16, 32, 64 chosen by name: form 0 = what the kernels use (lspiv_debug_fft), 1 = twiddles as
- * separate complex multiplies, 2 = twiddle scales folded into the next butterfly level (fft_regs.h).  Other n with form 1 / 2, or
- * another form: LSPIV_EUNSUPPORTED. */
+ * separate complex multiplies, 2 = twiddle scales folded into the next butterfly level, 4 = conjugate-pair split radix (fft_regs.h;
+ * one bit per form, so 3 is none).  Other n with form 1 / 2 / 4, or another form: LSPIV_EUNSUPPORTED. */
 int lspiv_debug_fft_form(int n, int form, int inverse, const float* in, float* out, int64_t count);
 /* Test hook (host only): how the time-walking kernels cut a chunk of n_pairs pairs that starts at absolute pair index
  * pair_offset into segments of seg_len pairs anchored at multiples of seg_len: pairs in the first segment, segment count. */

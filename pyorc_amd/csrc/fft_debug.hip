@@ -1,14 +1,15 @@
 // Test hook: the register FFTs of fft_regs.h, one transform per thread, so the parity suite can hold every length the
 // PIV kernels instantiate (8, 16, 32, 64 and the prime-factor lengths P * 2^m) against numpy.fft directly.
 // FORM 0 is the transform the kernels use (fft_n); 1 and 2 are the un-folded and the folded twiddle path of 16 / 32 / 64 by name,
-// whichever of them the length has adopted, so that one library can hold the two against each other.
+// whichever of them the length has adopted, and 4 is the conjugate-pair split-radix form, so that one library can hold them against each
+// other (3 is not a form: the values are one bit each).
 #include "piv_fft_impl.h"
 
 namespace lspiv {
 
-template <bool INV, int FORM> __device__ __forceinline__ void fft_form(float (&r)[16], float (&i)[16]) { fft16<INV, false, FORM == 2>(r, i); }
-template <bool INV, int FORM> __device__ __forceinline__ void fft_form(float (&r)[32], float (&i)[32]) { fft32<INV, false, FORM == 2>(r, i); }
-template <bool INV, int FORM> __device__ __forceinline__ void fft_form(float (&r)[64], float (&i)[64]) { fft64<INV, false, FORM == 2>(r, i); }
+template <bool INV, int FORM> __device__ __forceinline__ void fft_form(float (&r)[16], float (&i)[16]) { fft16<INV, false, FORM == 2, FORM == 4>(r, i); }
+template <bool INV, int FORM> __device__ __forceinline__ void fft_form(float (&r)[32], float (&i)[32]) { fft32<INV, false, FORM == 2, FORM == 4>(r, i); }
+template <bool INV, int FORM> __device__ __forceinline__ void fft_form(float (&r)[64], float (&i)[64]) { fft64<INV, false, FORM == 2, FORM == 4>(r, i); }
 
 template <int N, bool INV, int FORM = 0>
 __global__ void fft_debug_kernel(const float* in, float* out, int count) {
@@ -45,11 +46,11 @@ hipError_t launch_fft_debug(int n, bool inverse, const float* in, float* out, in
 
 hipError_t launch_fft_debug_form(int n, int form, bool inverse, const float* in, float* out, int count, hipStream_t s) {
   if (form == 0) return launch_fft_debug(n, inverse, in, out, count, s);
-  if (form != 1 && form != 2) return hipErrorInvalidValue;
+  if (form != 1 && form != 2 && form != 4) return hipErrorInvalidValue;
   switch (n) {
-    case 16: return form == 1 ? launch_one<16, 1>(inverse, in, out, count, s) : launch_one<16, 2>(inverse, in, out, count, s);
-    case 32: return form == 1 ? launch_one<32, 1>(inverse, in, out, count, s) : launch_one<32, 2>(inverse, in, out, count, s);
-    case 64: return form == 1 ? launch_one<64, 1>(inverse, in, out, count, s) : launch_one<64, 2>(inverse, in, out, count, s);
+    case 16: return form == 1 ? launch_one<16, 1>(inverse, in, out, count, s) : form == 2 ? launch_one<16, 2>(inverse, in, out, count, s) : launch_one<16, 4>(inverse, in, out, count, s);
+    case 32: return form == 1 ? launch_one<32, 1>(inverse, in, out, count, s) : form == 2 ? launch_one<32, 2>(inverse, in, out, count, s) : launch_one<32, 4>(inverse, in, out, count, s);
+    case 64: return form == 1 ? launch_one<64, 1>(inverse, in, out, count, s) : form == 2 ? launch_one<64, 2>(inverse, in, out, count, s) : launch_one<64, 4>(inverse, in, out, count, s);
     default: return hipErrorInvalidValue;
   }
 }

@@ -3,7 +3,9 @@
 // A lane owns a whole row (or column) of an interrogation tile in VGPRs, so a length-N
 // transform is straight-line VALU code: no LDS, no cross-lane traffic, twiddles are
 // compile-time literals.  N = 16 is 4 radix-4 -> 9 twiddles -> 4 radix-4; N = 32 is 8 radix-4 butterflies ->
-// 21 twiddle multiplies -> 4 radix-8 butterflies; N = 64 is 8 radix-8 -> 49 twiddles -> 8 radix-8.
+// 21 twiddle multiplies -> 4 radix-8 butterflies; N = 64 is 8 radix-8 -> 49 twiddles -> 8 radix-8.  The twiddle scales may be folded
+// into the next butterfly level (FOLD), and the same lengths have a conjugate-pair split-radix form with fewer instructions (SR, fft_sr);
+// which kernel runs on which is DESIGN.md 3.3.
 //
 // There is no reference kernel to mirror: pyorc delegates the FFT to rocket_fft/pocketfft on
 // the CPU.  Sign convention matches numpy: forward = exp(-2 pi i nk/N),
@@ -39,7 +41,7 @@ constexpr float kSqrtHalf = 0.70710678118654757f;
 
 // x *= exp(-/+ 2 pi i m / 64)   (forward: minus; INV: plus)
 template <bool INV, int M>
-__device__ __forceinline__ void twiddle64(float& xr, float& xi) {
+__host__ __device__ __forceinline__ void twiddle64(float& xr, float& xi) {
   constexpr int m = M & 63;
   if constexpr (m == 0) {
     return;
@@ -63,12 +65,20 @@ __device__ __forceinline__ void twiddle64(float& xr, float& xi) {
 // CLAMP: the outputs of the LAST butterfly stage of an inverse transform are correlation-plane samples, which the
 // caller clips to [0, 1]; written as med3(x, 0, 1) of the final add / sub, the clip folds into the VALU clamp modifier of
 // that instruction (v_add_f32 ... clamp) and costs nothing.
+// (The power-of-two transforms are __host__ __device__ so that a host program can hold them against a float64 DFT; the host clips in
+// plain C++.)
 template <bool CLAMP>
-__device__ __forceinline__ float out01(float x) { return CLAMP ? __builtin_amdgcn_fmed3f(x, 0.0f, 1.0f) : x; }
+__host__ __device__ __forceinline__ float out01(float x) {
+#if defined(__HIP_DEVICE_COMPILE__)
+  return CLAMP ? __builtin_amdgcn_fmed3f(x, 0.0f, 1.0f) : x;
+#else
+  return CLAMP ? (x < 0.0f ? 0.0f : x > 1.0f ? 1.0f : x) : x;
+#endif
+}
 
 // second level of the radix-4 butterfly: a = x0 + x2, b = x0 - x2, c = x1 + x3, d = x1 - x3 in, natural-order outputs
 template <bool INV, bool CLAMP>
-__device__ __forceinline__ void bfly4_tail(float ar, float ai, float br, float bi, float cr, float ci, float dr, float di,
+__host__ __device__ __forceinline__ void bfly4_tail(float ar, float ai, float br, float bi, float cr, float ci, float dr, float di,
                                            float& r0, float& i0, float& r1, float& i1,
                                            float& r2, float& i2, float& r3, float& i3) {
   r0 = out01<CLAMP>(ar + cr); i0 = out01<CLAMP>(ai + ci);
@@ -84,7 +94,7 @@ __device__ __forceinline__ void bfly4_tail(float ar, float ai, float br, float b
 
 // radix-4 butterfly, natural-order outputs
 template <bool INV, bool CLAMP = false>
-__device__ __forceinline__ void bfly4(float& r0, float& i0, float& r1, float& i1,
+__host__ __device__ __forceinline__ void bfly4(float& r0, float& i0, float& r1, float& i1,
                                       float& r2, float& i2, float& r3, float& i3) {
   float ar = r0 + r2, ai = i0 + i2;
   float br = r0 - r2, bi = i0 - i2;
@@ -95,7 +105,7 @@ __device__ __forceinline__ void bfly4(float& r0, float& i0, float& r1, float& i1
 
 // radix-8 butterfly after its even / odd radix-4s: E0..E3 in slots 0,2,4,6 and O0..O3 in slots 1,3,5,7
 template <bool INV, bool CLAMP>
-__device__ __forceinline__ void bfly8_tail(float (&r)[8], float (&i)[8]) {
+__host__ __device__ __forceinline__ void bfly8_tail(float (&r)[8], float (&i)[8]) {
   // O1 *= W8^1, O2 *= W8^2, O3 *= W8^3
   {
     float tr = r[3], ti = i[3];
@@ -118,7 +128,7 @@ __device__ __forceinline__ void bfly8_tail(float (&r)[8], float (&i)[8]) {
 
 // radix-8 butterfly on 8 values (natural order in, natural order out)
 template <bool INV, bool CLAMP = false>
-__device__ __forceinline__ void bfly8(float (&r)[8], float (&i)[8]) {
+__host__ __device__ __forceinline__ void bfly8(float (&r)[8], float (&i)[8]) {
   // even / odd radix-4
   bfly4<INV>(r[0], i[0], r[2], i[2], r[4], i[4], r[6], i[6]);  // E0..E3 in slots 0,2,4,6
   bfly4<INV>(r[1], i[1], r[3], i[3], r[5], i[5], r[7], i[7]);  // O0..O3 in slots 1,3,5,7
@@ -129,7 +139,7 @@ template <bool INV, int N2, int K1, int STEP>
 struct TwiddleRow {
   // x[n2] *= W^(STEP * n2 * K1) for n2 = 1..7 (W = 64th root); unrolled at compile time
   template <int n2>
-  static __device__ __forceinline__ void apply(float (&r)[8], float (&i)[8]) {
+  static __host__ __device__ __forceinline__ void apply(float (&r)[8], float (&i)[8]) {
     if constexpr (n2 < N2) {
       twiddle64<INV, STEP * n2 * K1>(r[n2], i[n2]);
       apply<n2 + 1>(r, i);
@@ -147,7 +157,8 @@ struct TwiddleRow {
 // and negations and count as un-twiddled.
 // LSPIV_FFT_FOLD=0/1 forces the path for every kernel of every length (A/B builds); left alone, the adoption is that of DESIGN.md
 // 3.3: a length folds when none of its kernels pays for it in registers, scratch or waves.  16 does; 32 and 64 do not as lengths,
-// but the walking per-pair kernel of 32 x 32 (the flagship) is clean in all its instantiations and folds on its own (kFftFoldWalk32).
+// but the walking per-pair kernel of 32 x 32 (the flagship) is clean in all its instantiations and folds on its own (kFftFoldWalk32) --
+// which is what LSPIV_FFT_SR=0 leaves it on: by default it runs on the split-radix form below, and SR goes before FOLD.
 #ifdef LSPIV_FFT_FOLD
 constexpr bool kFftFold16 = LSPIV_FFT_FOLD, kFftFold32 = LSPIV_FFT_FOLD, kFftFold64 = LSPIV_FFT_FOLD, kFftFoldWalk32 = LSPIV_FFT_FOLD;
 #else
@@ -169,7 +180,7 @@ struct FoldTw {
 
 // v -> u in place (a trivial exponent: v -> W v)
 template <bool INV, int M>
-__device__ __forceinline__ void fold_u(float& vr, float& vi) {
+__host__ __device__ __forceinline__ void fold_u(float& vr, float& vi) {
   using T = FoldTw<INV, M>;
   if constexpr (T::triv) {
     twiddle64<INV, M>(vr, vi);
@@ -184,7 +195,7 @@ __device__ __forceinline__ void fold_u(float& vr, float& vi) {
 
 // one component of a folded pair: sum = kx x + ky y, dif = kx x - ky y (a trivial side has k = 1 and is not multiplied)
 template <bool TRIVX, bool TRIVY>
-__device__ __forceinline__ void fold_pair(float x, float kx, float y, float ky, float& sum, float& dif) {
+__host__ __device__ __forceinline__ void fold_pair(float x, float kx, float y, float ky, float& sum, float& dif) {
   if constexpr (TRIVX && TRIVY) {
     sum = x + y; dif = x - y;
   } else if constexpr (TRIVY) {
@@ -198,7 +209,7 @@ __device__ __forceinline__ void fold_pair(float x, float kx, float y, float ky, 
 
 // radix-4 butterfly of W^E0 x0 .. W^E3 x3 (W = 64th root)
 template <bool INV, bool CLAMP, int E0, int E1, int E2, int E3>
-__device__ __forceinline__ void bfly4_fold(float& r0, float& i0, float& r1, float& i1,
+__host__ __device__ __forceinline__ void bfly4_fold(float& r0, float& i0, float& r1, float& i1,
                                            float& r2, float& i2, float& r3, float& i3) {
   using T0 = FoldTw<INV, E0>; using T1 = FoldTw<INV, E1>; using T2 = FoldTw<INV, E2>; using T3 = FoldTw<INV, E3>;
   fold_u<INV, E0>(r0, i0); fold_u<INV, E1>(r1, i1); fold_u<INV, E2>(r2, i2); fold_u<INV, E3>(r3, i3);
@@ -212,7 +223,7 @@ __device__ __forceinline__ void bfly4_fold(float& r0, float& i0, float& r1, floa
 
 // radix-8 butterfly of x[n2] W^(STEP n2 K1), n2 = 0..7: TwiddleRow + bfly8, folded or not
 template <bool INV, bool CLAMP, bool FOLD, int K1, int STEP>
-__device__ __forceinline__ void twiddled_bfly8(float (&r)[8], float (&i)[8]) {
+__host__ __device__ __forceinline__ void twiddled_bfly8(float (&r)[8], float (&i)[8]) {
   if constexpr (FOLD) {
     constexpr int E = STEP * K1;
     bfly4_fold<INV, false, 0, 2 * E, 4 * E, 6 * E>(r[0], i[0], r[2], i[2], r[4], i[4], r[6], i[6]);
@@ -224,18 +235,111 @@ __device__ __forceinline__ void twiddled_bfly8(float (&r)[8], float (&i)[8]) {
   }
 }
 
+// ---- conjugate-pair split radix ---------------------------------------------------------------------------------------
+// X = FFT_N(x) from E = FFT_{N/2}(x[2n]), Z = FFT_{N/4}(x[4n+1]) and Z' = FFT_{N/4}(x[4n-1]) (indices mod N), k = 0 .. N/4 - 1:
+//   X[k]        = E[k]       +   (w^k Z[k] + w^-k Z'[k])        X[k + N/2]  = E[k]       -   (...)
+//   X[k + N/4]  = E[k + N/4] - i (w^k Z[k] - w^-k Z'[k])        X[k + 3N/4] = E[k + N/4] + i (...)
+// The pair w^k, w^-k shares |cos| and |sin|, so with the folding above taken one step further both products leave ONE scale behind:
+// w^k Z = k u, w^-k Z' = k u' (two FMAs each, |t| <= 1), S = u + u', D = u - u', and the scale rides on the four output FMAs --
+// 16 instructions for four outputs, 12 add / sub at k = 0.  No multiply and no three-register FMA anywhere: 144 / 372 / 912 VALU at
+// 16 / 32 / 64 against 150 / 394 / 970 of the folded radix-4 x 8 forms.  The inverse transform is the forward one with re and im
+// swapped on the way in and out (free in registers).  Input x[(OFF + n STRIDE) mod NT] of the top-level arrays, output in natural
+// order, out of place, all indices static; N STRIDE == NT at every level.
+// LSPIV_FFT_SR=0/1 forces the form off / on for every kernel of every length (A/B builds; 0 is the former instruction stream of every
+// kernel); left alone, the adoption is DESIGN.md 3.3: by the resource rule 64 and 32 as lengths do not qualify (scratch at 256 VGPRs;
+// the 32 x 32 ensemble kernels sit at 168), 16 does but for one search kernel and was no faster with the rescue pass off, and the
+// walking per-pair kernel of 32 x 32 -- clean in all twelve instantiations, faster in every run -- takes it on its own (kFftSrWalk32).
+#ifdef LSPIV_FFT_SR
+constexpr bool kFftSr16 = LSPIV_FFT_SR, kFftSr32 = LSPIV_FFT_SR, kFftSr64 = LSPIV_FFT_SR, kFftSrWalk32 = LSPIV_FFT_SR;
+#else
+constexpr bool kFftSr16 = false, kFftSr32 = false, kFftSr64 = false, kFftSrWalk32 = true;
+#endif
+template <int N> constexpr bool kFftSrLen = N == 16 ? kFftSr16 : N == 32 ? kFftSr32 : N == 64 ? kFftSr64 : false;
+template <int N> constexpr bool kFftSrWalk = N == 32 ? kFftSrWalk32 : kFftSrLen<N>;
+
+template <int N, int NT, int OFF, int STRIDE, bool CLAMP>
+__host__ __device__ __forceinline__ void sr_fft(const float (&xr)[NT], const float (&xi)[NT], float (&yr)[N], float (&yi)[N]);
+
+// outputs k, k + N/4, k + N/2, k + 3N/4 of one level, K = k
+template <int N, int K, bool CLAMP>
+__host__ __device__ __forceinline__ void sr_step(const float (&er)[N / 2], const float (&ei)[N / 2], const float (&zr)[N / 4], const float (&zi)[N / 4],
+                                                 const float (&wr)[N / 4], const float (&wi)[N / 4], float (&yr)[N], float (&yi)[N]) {
+  constexpr int Q = N / 4, m = K * (64 / N);   // theta = 2 pi K / N = 2 pi m / 64, m < 16: c > 0, s >= 0
+  if constexpr (K == 0) {
+    const float sr = zr[0] + wr[0], si = zi[0] + wi[0], dr = zr[0] - wr[0], di = zi[0] - wi[0];
+    yr[0] = out01<CLAMP>(er[0] + sr);         yi[0] = out01<CLAMP>(ei[0] + si);
+    yr[2 * Q] = out01<CLAMP>(er[0] - sr);     yi[2 * Q] = out01<CLAMP>(ei[0] - si);
+    yr[Q] = out01<CLAMP>(er[Q] + di);         yi[Q] = out01<CLAMP>(ei[Q] - dr);
+    yr[3 * Q] = out01<CLAMP>(er[Q] - di);     yi[3 * Q] = out01<CLAMP>(ei[Q] + dr);
+  } else {
+    constexpr double c = cos64(m), s = sin64(m);   // the table's floats, exactly
+    if constexpr (s <= c) {
+      constexpr float t = (float)(s / c), k = (float)c;   // quotient in double, rounded once
+      const float ur = fmaf(zi[K], t, zr[K]), ui = fmaf(zr[K], -t, zi[K]);
+      const float vr = fmaf(wi[K], -t, wr[K]), vi = fmaf(wr[K], t, wi[K]);
+      const float sr = ur + vr, si = ui + vi, dr = ur - vr, di = ui - vi;
+      yr[K] = out01<CLAMP>(fmaf(sr, k, er[K]));              yi[K] = out01<CLAMP>(fmaf(si, k, ei[K]));
+      yr[K + 2 * Q] = out01<CLAMP>(fmaf(sr, -k, er[K]));     yi[K + 2 * Q] = out01<CLAMP>(fmaf(si, -k, ei[K]));
+      yr[K + Q] = out01<CLAMP>(fmaf(di, k, er[K + Q]));      yi[K + Q] = out01<CLAMP>(fmaf(dr, -k, ei[K + Q]));
+      yr[K + 3 * Q] = out01<CLAMP>(fmaf(di, -k, er[K + Q])); yi[K + 3 * Q] = out01<CLAMP>(fmaf(dr, k, ei[K + Q]));
+    } else {
+      // w^k Z = s (u_r, -u_i), w^-k Z' = s (-u'_r, u'_i):  S = s (u_r - u'_r, u'_i - u_i),  D = s (u_r + u'_r, -(u_i + u'_i)) -- the
+      // negation of D's imaginary part is in the sign of the literal
+      constexpr float t = (float)(c / s), k = (float)s;
+      const float ur = fmaf(zr[K], t, zi[K]), ui = fmaf(zi[K], -t, zr[K]);
+      const float vr = fmaf(wr[K], -t, wi[K]), vi = fmaf(wi[K], t, wr[K]);
+      const float sr = ur - vr, si = vi - ui, dr = ur + vr, dn = ui + vi;
+      yr[K] = out01<CLAMP>(fmaf(sr, k, er[K]));              yi[K] = out01<CLAMP>(fmaf(si, k, ei[K]));
+      yr[K + 2 * Q] = out01<CLAMP>(fmaf(sr, -k, er[K]));     yi[K + 2 * Q] = out01<CLAMP>(fmaf(si, -k, ei[K]));
+      yr[K + Q] = out01<CLAMP>(fmaf(dn, -k, er[K + Q]));     yi[K + Q] = out01<CLAMP>(fmaf(dr, -k, ei[K + Q]));
+      yr[K + 3 * Q] = out01<CLAMP>(fmaf(dn, k, er[K + Q]));  yi[K + 3 * Q] = out01<CLAMP>(fmaf(dr, k, ei[K + Q]));
+    }
+  }
+  if constexpr (K + 1 < Q) sr_step<N, K + 1, CLAMP>(er, ei, zr, zi, wr, wi, yr, yi);
+}
+
+template <int N, int NT, int OFF, int STRIDE, bool CLAMP>
+__host__ __device__ __forceinline__ void sr_fft(const float (&xr)[NT], const float (&xi)[NT], float (&yr)[N], float (&yi)[N]) {
+  static_assert(N * STRIDE == NT && (N & (N - 1)) == 0 && N <= 64, "a power of two, and the strides of its own recursion");
+  constexpr int o0 = OFF & (NT - 1);
+  if constexpr (N == 1) {
+    yr[0] = out01<CLAMP>(xr[o0]); yi[0] = out01<CLAMP>(xi[o0]);
+  } else if constexpr (N == 2) {
+    constexpr int o1 = (OFF + STRIDE) & (NT - 1);
+    yr[0] = out01<CLAMP>(xr[o0] + xr[o1]); yi[0] = out01<CLAMP>(xi[o0] + xi[o1]);
+    yr[1] = out01<CLAMP>(xr[o0] - xr[o1]); yi[1] = out01<CLAMP>(xi[o0] - xi[o1]);
+  } else {
+    float er[N / 2], ei[N / 2], zr[N / 4], zi[N / 4], wr[N / 4], wi[N / 4];
+    sr_fft<N / 2, NT, OFF, 2 * STRIDE, false>(xr, xi, er, ei);
+    sr_fft<N / 4, NT, OFF + STRIDE, 4 * STRIDE, false>(xr, xi, zr, zi);
+    sr_fft<N / 4, NT, OFF - STRIDE + NT, 4 * STRIDE, false>(xr, xi, wr, wi);
+    sr_step<N, 0, CLAMP>(er, ei, zr, zi, wr, wi, yr, yi);
+  }
+}
+
+// in place, natural order in and out, as fft16 / fft32 / fft64
+template <bool INV, bool CLAMP, int N>
+__host__ __device__ __forceinline__ void fft_sr(float (&xr)[N], float (&xi)[N]) {
+  float yr[N], yi[N];
+  if constexpr (INV) sr_fft<N, N, 0, 1, CLAMP>(xi, xr, yi, yr);
+  else sr_fft<N, N, 0, 1, CLAMP>(xr, xi, yr, yi);
+#pragma unroll
+  for (int k = 0; k < N; ++k) { xr[k] = yr[k]; xi[k] = yi[k]; }
+}
+
 // ---- length-16 transform: n = 4 n1 + n2, k = k1 + 4 k2 ------------------------------------------------
 //   X[k1 + 4 k2] = DFT4_{n2}( W16^{n2 k1} * DFT4_{n1} x[4 n1 + n2] ),  W16 = W64^4
 template <bool INV, bool CLAMP, int K1>
-__device__ __forceinline__ void fft16_row_fold(const float (&xr)[16], const float (&xi)[16], float (&yr)[16], float (&yi)[16]) {
+__host__ __device__ __forceinline__ void fft16_row_fold(const float (&xr)[16], const float (&xi)[16], float (&yr)[16], float (&yi)[16]) {
   float r0 = xr[4 * K1], i0 = xi[4 * K1], r1 = xr[4 * K1 + 1], i1 = xi[4 * K1 + 1];
   float r2 = xr[4 * K1 + 2], i2 = xi[4 * K1 + 2], r3 = xr[4 * K1 + 3], i3 = xi[4 * K1 + 3];
   bfly4_fold<INV, CLAMP, 0, 4 * K1, 8 * K1, 12 * K1>(r0, i0, r1, i1, r2, i2, r3, i3);
   yr[K1] = r0; yi[K1] = i0; yr[K1 + 4] = r1; yi[K1 + 4] = i1; yr[K1 + 8] = r2; yi[K1 + 8] = i2; yr[K1 + 12] = r3; yi[K1 + 12] = i3;
 }
 
-template <bool INV, bool CLAMP = false, bool FOLD = kFftFold16>
-__device__ __forceinline__ void fft16(float (&xr)[16], float (&xi)[16]) {
+template <bool INV, bool CLAMP = false, bool FOLD = kFftFold16, bool SR = kFftSr16>
+__host__ __device__ __forceinline__ void fft16(float (&xr)[16], float (&xi)[16]) {
+  if constexpr (SR) { fft_sr<INV, CLAMP>(xr, xi); return; }
 #pragma unroll
   for (int n2 = 0; n2 < 4; ++n2)
     bfly4<INV>(xr[n2], xi[n2], xr[4 + n2], xi[4 + n2], xr[8 + n2], xi[8 + n2], xr[12 + n2], xi[12 + n2]);   // slot (k1, n2) = 4 k1 + n2
@@ -264,8 +368,9 @@ __device__ __forceinline__ void fft16(float (&xr)[16], float (&xi)[16]) {
 
 // ---- length-32 transform, in place, natural order in and out --------------------------------
 // n = 8 n1 + n2, k = k1 + 4 k2:  X[k1 + 4 k2] = DFT8_{n2}( W32^{n2 k1} * DFT4_{n1} x[8 n1 + n2] )
-template <bool INV, bool CLAMP = false, bool FOLD = kFftFold32>
-__device__ __forceinline__ void fft32(float (&xr)[32], float (&xi)[32]) {
+template <bool INV, bool CLAMP = false, bool FOLD = kFftFold32, bool SR = kFftSr32>
+__host__ __device__ __forceinline__ void fft32(float (&xr)[32], float (&xi)[32]) {
+  if constexpr (SR) { fft_sr<INV, CLAMP>(xr, xi); return; }
 #pragma unroll
   for (int n2 = 0; n2 < 8; ++n2)
     bfly4<INV>(xr[n2], xi[n2], xr[8 + n2], xi[8 + n2], xr[16 + n2], xi[16 + n2], xr[24 + n2], xi[24 + n2]);
@@ -309,7 +414,7 @@ __device__ __forceinline__ void fft32(float (&xr)[32], float (&xi)[32]) {
 
 // ---- length-64 transform: n = 8 n1 + n2, k = k1 + 8 k2 --------------------------------------
 template <bool INV, int K1, bool CLAMP = false, bool FOLD = false>
-__device__ __forceinline__ void fft64_col(const float (&xr)[64], const float (&xi)[64],
+__host__ __device__ __forceinline__ void fft64_col(const float (&xr)[64], const float (&xi)[64],
                                           float (&yr)[64], float (&yi)[64]) {
   float r[8], i[8];
 #pragma unroll
@@ -327,9 +432,14 @@ __device__ __forceinline__ void fft64_col(const float (&xr)[64], const float (&x
 #ifndef LSPIV_FFT64_PRIO
 #define LSPIV_FFT64_PRIO 0
 #endif
+#if defined(__HIP_DEVICE_COMPILE__)
 #define LSPIV_FFT64_BAR do { if (LSPIV_FFT64_SB) __builtin_amdgcn_sched_barrier(0); } while (0)
-template <bool INV, bool CLAMP = false, bool FOLD = kFftFold64>
-__device__ __forceinline__ void fft64(float (&xr)[64], float (&xi)[64]) {
+#else
+#define LSPIV_FFT64_BAR do { } while (0)
+#endif
+template <bool INV, bool CLAMP = false, bool FOLD = kFftFold64, bool SR = kFftSr64>
+__host__ __device__ __forceinline__ void fft64(float (&xr)[64], float (&xi)[64]) {
+  if constexpr (SR) { fft_sr<INV, CLAMP>(xr, xi); return; }
 #pragma unroll
   for (int n2 = 0; n2 < 8; ++n2) {
     float r[8], i[8];
@@ -338,10 +448,10 @@ __device__ __forceinline__ void fft64(float (&xr)[64], float (&xi)[64]) {
     bfly8<INV>(r, i);
 #pragma unroll
     for (int k1 = 0; k1 < 8; ++k1) { xr[8 * k1 + n2] = r[k1]; xi[8 * k1 + n2] = i[k1]; }
-    if (LSPIV_FFT64_SB) __builtin_amdgcn_sched_barrier(0);
+    LSPIV_FFT64_BAR;
   }
   float yr[64], yi[64];
-#if LSPIV_FFT64_PRIO
+#if LSPIV_FFT64_PRIO && defined(__HIP_DEVICE_COMPILE__)
   __builtin_amdgcn_s_setprio(1);   // A/B variant: the second radix stage ahead of a neighbour's first
 #endif
   fft64_col<INV, 0, CLAMP, FOLD>(xr, xi, yr, yi); LSPIV_FFT64_BAR;
@@ -352,7 +462,7 @@ __device__ __forceinline__ void fft64(float (&xr)[64], float (&xi)[64]) {
   fft64_col<INV, 5, CLAMP, FOLD>(xr, xi, yr, yi); LSPIV_FFT64_BAR;
   fft64_col<INV, 6, CLAMP, FOLD>(xr, xi, yr, yi); LSPIV_FFT64_BAR;
   fft64_col<INV, 7, CLAMP, FOLD>(xr, xi, yr, yi); LSPIV_FFT64_BAR;
-#if LSPIV_FFT64_PRIO
+#if LSPIV_FFT64_PRIO && defined(__HIP_DEVICE_COMPILE__)
   __builtin_amdgcn_s_setprio(0);
 #endif
 #pragma unroll
@@ -507,7 +617,7 @@ template <bool INV> __device__ __forceinline__ void fft_pow2(float (&r)[2], floa
 }
 template <bool INV> __device__ __forceinline__ void fft_pow2(float (&r)[4], float (&i)[4]) { bfly4<INV>(r[0], i[0], r[1], i[1], r[2], i[2], r[3], i[3]); }
 template <bool INV> __device__ __forceinline__ void fft_pow2(float (&r)[8], float (&i)[8]) { bfly8<INV>(r, i); }
-template <bool INV> __device__ __forceinline__ void fft_pow2(float (&r)[16], float (&i)[16]) { fft16<INV, false, false>(r, i); }   // 48 = 3 x 16 stays un-folded
+template <bool INV> __device__ __forceinline__ void fft_pow2(float (&r)[16], float (&i)[16]) { fft16<INV, false, false, false>(r, i); }   // 48 = 3 x 16 stays un-folded
 
 template <bool INV> __device__ __forceinline__ void fft_pow2(float (&r)[5], float (&i)[5]) { dft_small<INV>(r, i); }   // second factor of 15
 template <bool INV> __device__ __forceinline__ void fft_pow2(float (&r)[7], float (&i)[7]) { dft_small<INV>(r, i); }   // ... of 21

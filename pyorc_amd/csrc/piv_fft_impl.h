@@ -795,14 +795,15 @@ template <bool INV> __device__ __forceinline__ void fft_n(float (&xr)[44], float
 template <bool INV> __device__ __forceinline__ void fft_n(float (&xr)[52], float (&xi)[52]) { fft_pfa<INV, 13, 4>(xr, xi); }
 template <bool INV> __device__ __forceinline__ void fft_n(float (&xr)[56], float (&xi)[56]) { fft_pfa<INV, 7, 8>(xr, xi); }
 template <bool INV> __device__ __forceinline__ void fft_n(float (&xr)[60], float (&xi)[60]) { fft_pfa<INV, 15, 4>(xr, xi); }
-// the transforms of a walking iteration: FOLD is the calling kernel's twiddle path at 16 / 32 / 64 (fft_regs.h: a kernel may fold where
+// the transforms of a walking iteration: FOLD / SR are the calling kernel's twiddle path at 16 / 32 / 64 (fft_regs.h: a kernel may fold, or
+// take the split-radix form, where
 // its length as a whole does not); CLAMP: the last inverse transform, clipped as ifft_clamped clips
-template <bool INV, bool CLAMP, bool FOLD, int N>
+template <bool INV, bool CLAMP, bool FOLD, bool SR, int N>
 __device__ __forceinline__ void fft_walk(float (&xr)[N], float (&xi)[N]) {
   static_assert(INV || !CLAMP, "only the inverse transform clips");
-  if constexpr (N == 16) fft16<INV, CLAMP, FOLD>(xr, xi);
-  else if constexpr (N == 32) fft32<INV, CLAMP, FOLD>(xr, xi);
-  else if constexpr (N == 64) fft64<INV, CLAMP, FOLD>(xr, xi);
+  if constexpr (N == 16) fft16<INV, CLAMP, FOLD, SR>(xr, xi);
+  else if constexpr (N == 32) fft32<INV, CLAMP, FOLD, SR>(xr, xi);
+  else if constexpr (N == 64) fft64<INV, CLAMP, FOLD, SR>(xr, xi);
   else if constexpr (CLAMP) ifft_clamped(xr, xi);
   else fft_n<INV>(xr, xi);
 }
@@ -1650,7 +1651,7 @@ __device__ __forceinline__ void unpack_step(int ky, float mr, float mi, int part
 // (pair f), their means (DC bins) and NaN flags; the carry moves on to frame f + 1.
 // RELAX: without the scheduling barriers between the phases (a caller with registers to spare: the 32 x 32 ensemble kernel runs two
 // waves per SIMD for its register accumulator and may use 256 VGPRs)
-template <typename T, int N, bool WANT_NZ, bool RELAX = false, bool HALF_TILE = false, int UB = 1, bool U8_EARLY = false, bool FOLD = kFftFoldLen<N>>
+template <typename T, int N, bool WANT_NZ, bool RELAX = false, bool HALF_TILE = false, int UB = 1, bool U8_EARLY = false, bool FOLD = kFftFoldLen<N>, bool SR = kFftSrLen<N>>
 __device__ __forceinline__ void walk_iteration(const PivParams& p, const T* row, bool has2, float* buf, int lg,
                                                int partner_byte, int lane0_byte, WalkCarry<N>& c, float (&xr)[N],
                                                float (&xi)[N], float& mean_a, float& mean_b, bool& skip_a, bool& skip_b,
@@ -1708,13 +1709,13 @@ __device__ __forceinline__ void walk_iteration(const PivParams& p, const T* row,
   }
   LSPIV_WALK_SB;
   LSPIV_SETPRIO(0);
-  fft_walk<false, false, FOLD>(xr, xi);   // along x
+  fft_walk<false, false, FOLD, SR>(xr, xi);   // along x
   LSPIV_WALK_SB;
   LSPIV_SETPRIO(LSPIV_PRIO_T);
   transpose2<N, HALF_TILE>(buf, lg, xr, xi);    // lane = kx, regs = y
   LSPIV_WALK_SB;
   LSPIV_SETPRIO(0);
-  fft_walk<false, false, FOLD>(xr, xi);   // along y -> Z[ky][kx]
+  fft_walk<false, false, FOLD, SR>(xr, xi);   // along y -> Z[ky][kx]
   LSPIV_WALK_SB;
   LSPIV_SETPRIO(LSPIV_PRIO_U);
   // un-pack the two spectra, form both cross spectra and pack them for the shared inverse, one ky at a time (a
@@ -1748,7 +1749,7 @@ __device__ __forceinline__ void walk_iteration(const PivParams& p, const T* row,
   mean_b = bperm_f(lane0_byte, xi[0]);
   __builtin_amdgcn_sched_barrier(0);
   LSPIV_SETPRIO(0);
-  fft_walk<true, false, FOLD>(xr, xi);    // along ky
+  fft_walk<true, false, FOLD, SR>(xr, xi);    // along ky
   LSPIV_WALK_SB;
   LSPIV_SETPRIO(LSPIV_PRIO_T);
   transpose2<N, HALF_TILE>(buf, lg, xr, xi);      // lane = y, regs = kx
@@ -1765,10 +1766,10 @@ __device__ __forceinline__ void walk_iteration(const PivParams& p, const T* row,
     // clip [0, 1] rides on the last butterfly stage (clamp modifier).  A pair with a zero-variance window has an
     // exactly-zero cross spectrum, but its plane shares the inverse transform with the other pair's and would come out
     // as rounding noise of that one: the callers override such a pair's results (corr 0, s2n / u / v NaN, zero plane)
-    fft_walk<true, true, FOLD>(xr, xi);   // along kx -> c_a + i c_b
+    fft_walk<true, true, FOLD, SR>(xr, xi);   // along kx -> c_a + i c_b
     LSPIV_WALK_SB;
   } else {
-    fft_walk<true, false, FOLD>(xr, xi);
+    fft_walk<true, false, FOLD, SR>(xr, xi);
     LSPIV_WALK_SB;
     const float hi_a = dead_a ? 0.0f : 1.0f, hi_b = dead_b ? 0.0f : 1.0f;
 #pragma unroll
@@ -1942,7 +1943,7 @@ __global__ __launch_bounds__(BLOCK, (kWalkWaves<T, N>)) void piv_fft_walk_kernel
     const bool has2 = f + 1 <= p1;
     float xr[N], xi[N], mean_a, mean_b;
     bool skip_a, skip_b, dead_a, dead_b;
-    walk_iteration<T, N, WANT_NZ, kWalkRelax<T, N>, false, kWalkUnpackBatch<T, N, PLANES, WANT_NZ>, kWalkU8Early<N, PLANES, WANT_NZ>, kFftFoldWalk<N>>(
+    walk_iteration<T, N, WANT_NZ, kWalkRelax<T, N>, false, kWalkUnpackBatch<T, N, PLANES, WANT_NZ>, kWalkU8Early<N, PLANES, WANT_NZ>, kFftFoldWalk<N>, kFftSrWalk<N>>(
         p, row, has2, buf, lg, partner_byte, lane0_byte, carry, xr, xi, mean_a, mean_b, skip_a, skip_b, dead_a, dead_b);
     if (WANT_NZ && win_dropped) skip_a = skip_b = true;
     const bool valid_a = job_valid && f > p0, valid_b = job_valid && has2;
