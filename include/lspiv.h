@@ -47,7 +47,8 @@ extern "C" {
                                * correlation, lspiv_spof_supported / lspiv_piv_spof_pairs_dev_at / lspiv_piv_spof_pairs_at /
                                * lspiv_ensemble_set_spectral_filter / _get_spectral_filter; the image mask, lspiv_mask_supported /
                                * lspiv_piv_masked_pairs_dev_at / lspiv_piv_masked_pairs_at; the second correlation peak, lspiv_peak2_supported /
-                               * lspiv_piv_peak2_pairs_dev_at / lspiv_piv_peak2_pairs_at / lspiv_second_peak_dev / lspiv_second_peak)
+                               * lspiv_piv_peak2_pairs_dev_at / lspiv_piv_peak2_pairs_at / lspiv_second_peak_dev / lspiv_second_peak; vector validation,
+                               * lspiv_validate_dev / lspiv_validate)
                                * 5 (round 6): lspiv_chunk_alignment(wy, wx) without a grid now returns the alignment that is right on EVERY grid (75
                                * where it returned 25: callers that cut chunks on it stay bit-reproducible on large grids); additions:
                                * lspiv_upload_frames, lspiv_trace / lspiv_trace_read; the host-pointer projection entry points no longer
@@ -700,6 +701,36 @@ int lspiv_window_replace_dev(float* d_fields, int64_t T, int64_t R, int64_t C, i
                              int y_max, int iter, void* stream);
 int lspiv_scale_velocity_dev(float* d_fields, int64_t T, int64_t n_vec, double res_x, double res_y, const double* dt,
                              void* stream);
+
+/* ---- Vector validation (additions, no ABI version change) ------------------------------------------------
+ * The normalised median test (Westerweel & Scarano 2005) on the fields u, v (T, R, C) float32 while they are still in HBM, with the
+ * runner-up vector of the second correlation peak as the first substitute for a rejected one.  Every iteration reads the field of the
+ * iteration before it only (Jacobi): the result does not depend on the order in which vectors are visited.  For every (t, i, j):
+ *   neighbours  the up to eight positions (i + di, j + dj) of the same t inside the grid whose u AND v are finite (no wrap across row
+ *               ends or time steps); n their count
+ *   med(x)      of n values sorted ascending: the middle one for odd n, 0.5f * (x[n/2-1] + x[n/2]) for even n
+ *   limits      um = med(u_k), vm = med(v_k); ru = med(|u_k - um|), rv = med(|v_k - vm|); lu = threshold * (ru + epsilon), lv alike --
+ *               every operation one correctly rounded float32 operation
+ *   judged      a vector that is finite in both components and has n >= min_neighbours; anything else keeps value and flag (NaN is
+ *               never filled: lspiv_window_replace does that)
+ *   outlier     |u0 - um| > lu or |v0 - vm| > lv
+ *   action      (1) with peak2, a vector that is still the primary one (flag 0) whose (u2, v2) are finite and no outlier against the same
+ *               um, vm, lu, lv becomes (u2, v2), flag 2; else (2) replace = LSPIV_VALIDATE_NAN: NaN / NaN, flag 1; (3) replace =
+ *               LSPIV_VALIDATE_MEDIAN: (um, vm), flag 3.  A flag-2 or flag-3 vector is judged again by a later iteration like any other and
+ *               can only fall to (2) or (3); the flag is the last action taken.
+ * flag: uint8 (T, R, C): 0 kept or unjudged, 1 rejected, 2 substituted, 3 median.  Units: those of the fields (epsilon 0.1 is meant for
+ * pixels: validate before lspiv_scale_velocity_dev).  peak2: (T, R, C, 4) = {u2, v2, corr2, ratio} as lspiv_piv_peak2_pairs_dev_at writes
+ * it, read only.  threshold > 0, epsilon >= 0, min_neighbours 1 .. 8, iterations 1 .. 8; a parameter outside its range, or T, R or C < 1,
+ * is LSPIV_EINVAL.  Both calls work in place on u, v; d_peak2 / peak2 and d_flag / flag may be NULL.  One kernel launch per iteration;
+ * the ping-pong workspace (8 bytes per vector) is the library's, grow-only.  lspiv_validate_dev is asynchronous on `stream`.
+ * lspiv_validate: the host twin -- upload, the same kernels, download. */
+#define LSPIV_VALIDATE_NAN 0
+#define LSPIV_VALIDATE_MEDIAN 1
+int lspiv_validate_dev(float* d_u, float* d_v, const float* d_peak2, int64_t T, int64_t R, int64_t C,
+                       float threshold, float epsilon, int min_neighbours, int replace, int iterations,
+                       uint8_t* d_flag, void* stream);
+int lspiv_validate(float* u, float* v, const float* peak2, int64_t T, int64_t R, int64_t C,
+                   float threshold, float epsilon, int min_neighbours, int replace, int iterations, uint8_t* flag);
 
 /* N4 -- on-disk packing of the result variables (pyorc/const.py:80-83: int16, scale_factor 0.01,
  * _FillValue -9999; arithmetic of xarray's encoder: float32 x / float32 scale, NaN -> fill, round half even). */

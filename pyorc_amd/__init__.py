@@ -10,6 +10,7 @@ interfaces around it:
   pyorc_amd.frames        <-> pyorc.api.frames        (get_piv, engine="hip")
   pyorc_amd.shard / comm                               (frame-pair sharding over the GPUs of a node, RCCL through the C ABI)
   pyorc_amd.device                                     (DeviceFrames: HBM-resident stacks, so normalize -> project -> get_piv never leaves the GPU)
+  pyorc_amd.validate                                   (median_test: the normalised median test on the result block, runner-up substitution)
   pyorc_amd.executor                                   (chunk executor: lazy chunks are materialised ahead of the launches that consume them)
   pyorc_amd.plugin                                     (install(): engine="hip" inside an installed, unmodified pyorc -- called on import when pyorc is found)
 """

@@ -68,6 +68,9 @@ struct DeviceCtx {
   uint8_t* d_mask = nullptr; size_t mask_cap = 0;      // the image mask of a host-fed masked launch (grow-only; under the host lock)
   float* d_peak2 = nullptr; size_t peak2_cap = 0;      // the second-peak block of a host-fed launch (grow-only; under the host lock)
   float* d_deform = nullptr; size_t deform_cap = 0;    // deformation passes: the warped frames of one batch of pairs (grow-only; under the multipass lock)
+  // vector validation: the ping-pong fields [u | v] and the flags of a call without a flag buffer (grow-only; under the validate lock);
+  // the event marks the end of the last call's kernels, which the next call's stream waits for before it reuses the workspace
+  void* d_validate = nullptr; size_t validate_cap = 0; hipEvent_t validate_done = nullptr;
   // float64 rescue pass: one set of lists per launch stream (a stream orders its own PIV kernel -> rescue kernel pairs;
   // two streams must not share counters), grow-only
   struct RescueWs { hipStream_t stream; void* base; size_t cap_bytes; uint32_t cap_fit, cap_amb; };
@@ -98,9 +101,10 @@ struct DeviceCtx {
 //   multipass: the passes of ONE chain share the device's multi-pass workspace (DeviceCtx::d_mp): a chain is issued under it, so that
 //             two host threads launching chains on the same stream cannot interleave their passes
 //   project:  one per projection slot (DeviceCtx::proj): the host-pointer projection entry points; never nested with the others
-// Order when nested: host -> multipass -> dispatch -> lists.
+//   validate: the iterations of ONE lspiv_validate_dev call share the device's validation workspace (DeviceCtx::d_validate); innermost
+// Order when nested: host -> multipass -> dispatch -> lists; host -> validate.
 constexpr int kMaxDevices = 64;
-struct DeviceLocks { std::mutex host, multipass, dispatch, lists, project[DeviceCtx::kProjSlots]; std::atomic<unsigned> next_project{0}; };
+struct DeviceLocks { std::mutex host, multipass, dispatch, lists, validate, project[DeviceCtx::kProjSlots]; std::atomic<unsigned> next_project{0}; };
 extern DeviceLocks g_locks[kMaxDevices];
 int current_device_slot();
 inline DeviceLocks& locks_here() { return g_locks[current_device_slot()]; }

@@ -6,6 +6,7 @@
 #include <cstdlib>
 
 #include "project_tile.h"   // launch_blur_clip
+#include "validate.h"
 
 namespace lspiv_api __attribute__((visibility("hidden"))) {
 
@@ -165,6 +166,92 @@ int lspiv_scale_velocity_dev(float* d_fields, int64_t T, int64_t n_vec, double r
   if (e == hipSuccess) e = hipStreamSynchronize(s);  // dt is a host array and the temporary is freed below
   hipFree(d_dt);
   return launch_status(e, "scale_velocity failed");
+}
+
+// ---- vector validation (normalised median test, runner-up substitution) ---------------------------------
+namespace {
+int check_validate(const void* u, const void* v, int64_t T, int64_t R, int64_t C, float threshold, float epsilon, int min_neighbours,
+                   int replace, int iterations) {
+  if (!u || !v) return fail(LSPIV_EINVAL, "NULL argument");
+  if (T < 1 || R < 1 || C < 1) return fail(LSPIV_EINVAL, "bad field shape (%lld, %lld, %lld)", (long long)T, (long long)R, (long long)C);
+  if (R >= (1 << 30) || C >= (1 << 30) || T >= ((int64_t)1 << 38) || T * R * C >= ((int64_t)1 << 38))
+    return fail(LSPIV_ESHAPE, "field shape (%lld, %lld, %lld) too large", (long long)T, (long long)R, (long long)C);
+  if (!(threshold > 0.0f) || std::isinf(threshold)) return fail(LSPIV_EINVAL, "threshold %g must be a positive number", threshold);
+  if (!(epsilon >= 0.0f) || std::isinf(epsilon)) return fail(LSPIV_EINVAL, "epsilon %g must be a number >= 0", epsilon);
+  if (min_neighbours < 1 || min_neighbours > 8) return fail(LSPIV_EINVAL, "min_neighbours %d not in 1 .. 8", min_neighbours);
+  if (replace != LSPIV_VALIDATE_NAN && replace != LSPIV_VALIDATE_MEDIAN) return fail(LSPIV_EINVAL, "unknown replace mode %d", replace);
+  if (iterations < 1 || iterations > 8) return fail(LSPIV_EINVAL, "iterations %d not in 1 .. 8", iterations);
+  return LSPIV_OK;
+}
+}  // namespace
+
+int lspiv_validate_dev(float* d_u, float* d_v, const float* d_peak2, int64_t T, int64_t R, int64_t C, float threshold, float epsilon,
+                       int min_neighbours, int replace, int iterations, uint8_t* d_flag, void* stream) {
+  LSPIV_TRY(check_validate(d_u, d_v, T, R, C, threshold, epsilon, min_neighbours, replace, iterations));
+  DeviceCtx* c;
+  LSPIV_TRY(get_ctx(&c));
+  hipStream_t s = on_stream(c, stream);
+  const int64_t N = T * R * C;
+  const size_t fb = (((size_t)N * sizeof(float)) + 255) & ~(size_t)255;
+  // every iteration reads the field of the one before it: the fields ping-pong between the caller's buffers and the workspace, arranged
+  // so that the last iteration writes the caller's (an odd count starts from a copy in the workspace); a lane owns its flag
+  std::lock_guard<std::mutex> ws_lock(locks_here().validate);
+  if (!c->validate_done) HIP_TRY(hipEventCreateWithFlags(&c->validate_done, hipEventDisableTiming));
+  else HIP_TRY(hipStreamWaitEvent(s, c->validate_done, 0));
+  if (2 * fb + (size_t)N > c->validate_cap) HIP_TRY(hipEventSynchronize(c->validate_done));   // (a never-recorded event is complete)
+  LSPIV_TRY(ensure(&c->d_validate, &c->validate_cap, 2 * fb + (size_t)N));
+  float *w_u = (float*)c->d_validate, *w_v = (float*)((char*)c->d_validate + fb);
+  uint8_t* flag = d_flag ? d_flag : (uint8_t*)c->d_validate + 2 * fb;
+  const lspiv::ValidateParams p{threshold, epsilon, min_neighbours, replace};
+  hipError_t e = hipSuccess;
+  bool in_ws = false;   // where the current field is
+  if (iterations % 2) {
+    e = hipMemcpyAsync(w_u, d_u, (size_t)N * sizeof(float), hipMemcpyDeviceToDevice, s);
+    if (e == hipSuccess) e = hipMemcpyAsync(w_v, d_v, (size_t)N * sizeof(float), hipMemcpyDeviceToDevice, s);
+    in_ws = true;
+  }
+  for (int it = 0; it < iterations && e == hipSuccess; ++it) {
+    e = in_ws ? lspiv::launch_validate(w_u, w_v, d_peak2, T, (int)R, (int)C, p, it == 0, d_u, d_v, flag, s)
+              : lspiv::launch_validate(d_u, d_v, d_peak2, T, (int)R, (int)C, p, it == 0, w_u, w_v, flag, s);
+    in_ws = !in_ws;
+  }
+  const hipError_t rec = hipEventRecord(c->validate_done, s);
+  return launch_status(e != hipSuccess ? e : rec, "validate failed");
+}
+
+int lspiv_validate(float* u, float* v, const float* peak2, int64_t T, int64_t R, int64_t C, float threshold, float epsilon,
+                   int min_neighbours, int replace, int iterations, uint8_t* flag) {
+  LSPIV_TRY(check_validate(u, v, T, R, C, threshold, epsilon, min_neighbours, replace, iterations));
+  // the host twin: [u | v | flag] through the context's frame buffer, peak2 through its plane buffer, the same kernels in between
+  const size_t N = (size_t)T * R * C, fb = N * sizeof(float);
+  std::lock_guard<std::mutex> host_lock(locks_here().host);
+  DeviceCtx* c;
+  LSPIV_TRY(get_ctx(&c));
+  LSPIV_TRY(ensure(&c->d_frames, &c->frames_cap, 2 * fb + N));
+  if (peak2) LSPIV_TRY(ensure(&c->d_planes, &c->planes_cap, 4 * fb));
+  float *d_u = (float*)c->d_frames, *d_v = d_u + N;
+  uint8_t* d_flag = (uint8_t*)c->d_frames + 2 * fb;
+  const char* step = "upload";
+  hipError_t e = hipMemcpyAsync(d_u, u, fb, hipMemcpyHostToDevice, c->stream);
+  if (e == hipSuccess) e = hipMemcpyAsync(d_v, v, fb, hipMemcpyHostToDevice, c->stream);
+  if (e == hipSuccess && peak2) e = hipMemcpyAsync(c->d_planes, peak2, 4 * fb, hipMemcpyHostToDevice, c->stream);
+  const int rc = e == hipSuccess ? lspiv_validate_dev(d_u, d_v, peak2 ? c->d_planes : nullptr, T, R, C, threshold, epsilon, min_neighbours,
+                                                      replace, iterations, flag ? d_flag : nullptr, c->stream)
+                                 : LSPIV_OK;
+  if (e == hipSuccess && rc == LSPIV_OK) {
+    step = "download";
+    e = hipMemcpyAsync(u, d_u, fb, hipMemcpyDeviceToHost, c->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(v, d_v, fb, hipMemcpyDeviceToHost, c->stream);
+    if (e == hipSuccess && flag) e = hipMemcpyAsync(flag, d_flag, N, hipMemcpyDeviceToHost, c->stream);
+  }
+  // every exit from here waits for the stream: the caller's buffers are released only once its copies are done
+  const hipError_t sync = hipStreamSynchronize(c->stream);
+  if (e != hipSuccess || rc != LSPIV_OK) {   // the first error is the one reported
+    if (sync != hipSuccess) (void)hipGetLastError();
+    return rc != LSPIV_OK ? rc : fail(hip_code(e), "%s: %s failed: %s", __func__, step, hipGetErrorString(e));
+  }
+  if (sync != hipSuccess) return fail(hip_code(sync), "%s: synchronisation failed: %s", __func__, hipGetErrorString(sync));
+  return LSPIV_OK;
 }
 
 // ---- element-wise filters (N2) ---------------------------------------------------------------------

@@ -79,6 +79,9 @@ def get_piv(frames, window_size=None, overlap=None, engine: str = "hip", ensembl
     result -- the ratio of the two highest correlation peaks, the second one's height and the runner-up vector (INTEGRATION.md 2i);
     ``peak_exclusion`` (default 2) is the half side of the box around the primary peak that holds no second peak.  Windows of 16, 32 or
     64 px, per-timestep mode.
+    ``validate`` (in ``**kwargs``): True or a dict of ``validate.median_test``'s keywords -- the normalised median test on the
+    displacement in pixels, on the device, before the scaling; the result gains the uint8 variable ``flag`` and, with
+    ``peak_ratio=True``, rejected vectors are replaced by their runner-up where that one passes.  Per-timestep mode, no chain of passes.
     """
     if engine not in ENGINES:
         raise ValueError(f"Selected PIV engine {engine} does not exist.")

@@ -100,7 +100,8 @@ def _per_window_input(name, value, grid, dtype):
     return d
 
 
-def _run_pairs(imgs, ws, ov, signal_threshold, return_planes, pair_offset, out, scale, entry, args, fused=False, extra=None, aux=None):
+def _run_pairs(imgs, ws, ov, signal_threshold, return_planes, pair_offset, out, scale, entry, args, fused=False, extra=None, aux=None,
+               validate=None):
     """The body every per-pair entry point shares: stack -> grid -> ``out`` and ``scale`` checked -> results (and planes) allocated on the
     stack's side, host or HBM -> ONE library call -> results on the host -> scaling.  A mode supplies only what differs:
 
@@ -113,9 +114,13 @@ def _run_pairs(imgs, ws, ov, signal_threshold, return_planes, pair_offset, out, 
     ``extra(grid)``: the mode's extra input (mask, shift, nodes) for ``grid = (P, n_rows, n_cols)`` on the stack's side, an ndarray or a
     ``DeviceFrames``, or None;
     ``aux``: the dtype of a per-window output ``(P, n_rows, n_cols, 2)`` the call fills besides the results (the chain's offsets), or
-    ``(dtype, width)`` for another trailing width (the second peak's four floats).
+    ``(dtype, width)`` for another trailing width (the second peak's four floats);
+    ``validate``: a ``validate.ValidateSpec`` -- the median test on the displacement in pixels, between the
+    library call and the scaling: ``lspiv_validate_dev`` on the block in HBM, ``lspiv_validate`` on the host arrays; with ``aux`` (only the
+    second-peak mode passes both) the runner-up is offered for substitution.  A mode whose host entry point scales by itself must not be
+    given one together with ``fused``.
 
-    Returns ``(u, v, corr_max, s2n[, planes][, aux])``."""
+    Returns ``(u, v, corr_max, s2n[, planes][, aux][, flag])``."""
     from .device import DeviceFrames
 
     lib = _lib.load()
@@ -147,6 +152,17 @@ def _run_pairs(imgs, ws, ov, signal_threshold, return_planes, pair_offset, out, 
     c = SimpleNamespace(frames=(*frames, T, H, W), at=(_sig(signal_threshold), int(pair_offset)), res=res_ptrs, planes=ptr(planes),
                         extra=ptr(x), aux=ptr(d_aux), dt=None if dt is None else _lib.ptr(dt))
     _lib.check(getattr(lib, entry[dev])(*args(c), *((None,) if dev else ())))
+    flag = None
+    if validate is not None:
+        from . import validate as validate_mod
+
+        flag = np.empty((P, n_rows, n_cols), dtype=np.uint8)
+        if dev:      # on the result block while it is still in HBM
+            d_flag = DeviceFrames.empty((1, 1, flag.nbytes), np.uint8)
+            validate_mod.run_dev(validate, res.c_ptr, C.c_void_p(res.ptr + P * n_win * 4), c.aux, (P, n_rows, n_cols), d_flag.c_ptr)
+            _lib.check(lib.lspiv_memcpy_d2h(_lib.ptr(flag), d_flag.c_ptr, flag.nbytes))
+        else:        # the host twin, right after the call
+            validate_mod.run_host(validate, res[0], res[1], aux, flag)
     if dev:
         if dt is not None and fused:  # px / frame -> m / s in place on the [u | v] blocks
             _lib.check(lib.lspiv_scale_velocity_dev(res.c_ptr, P, n_win, float(scale[0]), float(scale[1]), c.dt, None))
@@ -158,7 +174,7 @@ def _run_pairs(imgs, ws, ov, signal_threshold, return_planes, pair_offset, out, 
     if dt is not None and not fused:
         for k in range(2):
             _to_velocity(res[k], scale[k], dt[:, None, None], out=res[k])
-    return (*res, *((planes,) if return_planes else ()), *((aux,) if aux is not None else ()))
+    return (*res, *((planes,) if return_planes else ()), *((aux,) if aux is not None else ()), *((flag,) if flag is not None else ()))
 
 
 # the window specs that carry a mode of their own through ``piv_pairs``: spec class -> (the keyword the messages name, that mode's call)
@@ -173,7 +189,7 @@ _HOST_SCALED = (window.SearchWindow, *_SPEC_MODES)
 
 
 def piv_pairs(imgs, window_size=(32, 32), overlap=(16, 16), signal_threshold: Optional[float] = None,
-              return_planes: bool = False, pair_offset: int = 0, out=None, scale=None, search_area_size=None):
+              return_planes: bool = False, pair_offset: int = 0, out=None, scale=None, search_area_size=None, validate=None):
     """Fused PIV of every consecutive frame pair of ``imgs`` (T, H, W).
 
     Returns ``(u, v, corr_max, s2n[, planes])``: float32 arrays (T-1, n_rows, n_cols); u, v in
@@ -188,24 +204,36 @@ def piv_pairs(imgs, window_size=(32, 32), overlap=(16, 16), signal_threshold: Op
     ``search_area_size``: None / the window size (today's path), or a larger square search area of 16, 32 or 64 px in which the even
     square window of frame t is searched in frame t+1 ("Extended search area"): the grid, ``overlap`` and the planes
     (``say x sax`` each) are then those of the search area.  ``window_size`` may also be a ``window.SearchWindow``.
+    ``validate``: None (today's path bit for bit), True, a dict of ``validate.median_test``'s keywords or a ``validate.ValidateSpec`` --
+    the median test on u, v in pixels, before any ``scale``; the returned tuple then ends with ``flag``,
+    uint8 (T-1, n_rows, n_cols).  Not with a chain of passes (NotImplementedError).
     """
+    if validate is not None:
+        from .validate import validate_spec
+
+        validate = validate_spec(validate)      # ValueError for a value outside its range
     mode = _SPEC_MODES.get(type(window_size))
     if mode is not None:   # a chain of passes, a spectral filter, an image mask, the second peak (INTEGRATION.md sections 2d, 2g, 2h, 2i): the final grid is this call's
         if search_area_size is not None and tuple(int(q) for q in search_area_size) != tuple(window_size):
             raise NotImplementedError(f"{mode[0]} together with a search_area_size larger than the window is not implemented")
-        return mode[1](imgs, window_size, overlap, signal_threshold, return_planes, pair_offset, out=out, scale=scale)
+        if validate is not None and isinstance(window_size, window.MultiPassWindow):
+            raise NotImplementedError("validate together with coarse_passes / deform_passes is not implemented: run validate.median_test "
+                                      "on the result instead")
+        return mode[1](imgs, window_size, overlap, signal_threshold, return_planes, pair_offset, out=out, scale=scale,
+                       **({} if validate is None else {"validate": validate}))
     ws = window.search_spec(window_size, search_area_size)
     search, dev = isinstance(ws, window.SearchWindow), is_device(imgs)
     if search:
         entry = ("lspiv_piv_search_pairs_at", "lspiv_piv_search_pairs_dev_at")
         args = lambda c: (*c.frames, *ws, *ws.window, *overlap, *c.at, *c.res, c.planes)  # noqa: E731
-    elif scale is not None and not dev:
+    elif scale is not None and not dev and validate is None:      # (the fused host call scales before a validation could run)
         entry = ("lspiv_piv_velocity_at",)
         args = lambda c: (*c.frames, *ws, *overlap, *c.at, float(scale[0]), float(scale[1]), c.dt, *c.res)  # noqa: E731
     else:
         entry = ("lspiv_piv_pairs_at", "lspiv_piv_pairs_dev_at")
         args = lambda c: (*c.frames, *ws, *overlap, *c.at, *c.res, c.planes)  # noqa: E731
-    return _run_pairs(imgs, ws, overlap, signal_threshold, return_planes, pair_offset, out, scale, entry, args, fused=dev or not search)
+    return _run_pairs(imgs, ws, overlap, signal_threshold, return_planes, pair_offset, out, scale, entry, args,
+                      fused=dev or (not search and validate is None), validate=validate)
 
 
 def device_scaling_is_numpys(res_x, res_y) -> bool:
@@ -216,7 +244,7 @@ def device_scaling_is_numpys(res_x, res_y) -> bool:
 
 
 def piv_pairs_filtered(imgs, window_size=(32, 32), overlap=(16, 16), spectral_filter="spof", signal_threshold: Optional[float] = None,
-                       return_planes: bool = False, pair_offset: int = 0, out=None, scale=None):
+                       return_planes: bool = False, pair_offset: int = 0, out=None, scale=None, validate=None):
     """SPOF phase-filtered PIV of every consecutive frame pair of ``imgs``: :func:`piv_pairs` with every bin R
     of the cross spectrum replaced by R / sqrt(|R|) before the inverse transform ("robust phase correlation"), for imagery whose static
     or slow background outweighs the tracers.  Returns ``(u, v, corr_max, s2n[, planes])`` like :func:`piv_pairs`; ``corr_max`` is the
@@ -227,16 +255,23 @@ def piv_pairs_filtered(imgs, window_size=(32, 32), overlap=(16, 16), spectral_fi
     flt = window.spectral_filter_spec(spectral_filter)
     if isinstance(window_size, window.FilteredWindow):
         flt = flt or window_size.spectral_filter
+    if validate is not None:
+        from .validate import validate_spec
+
+        validate = validate_spec(validate)
     if flt is None:
-        return piv_pairs(imgs, tuple(window_size), overlap, signal_threshold, return_planes, pair_offset, out=out, scale=scale)
+        return piv_pairs(imgs, tuple(window_size), overlap, signal_threshold, return_planes, pair_offset, out=out, scale=scale,
+                         **({} if validate is None else {"validate": validate}))
     ws = window.spectral_filter_supported(window_size)          # ValueError naming the sizes
     ov = (int(overlap[0]), int(overlap[1]))
     return _run_pairs(imgs, ws, ov, signal_threshold, return_planes, pair_offset, out, scale,
-                      ("lspiv_piv_spof_pairs_at", "lspiv_piv_spof_pairs_dev_at"), lambda c: (*c.frames, *ws, *ov, *c.at, *c.res, c.planes))
+                      ("lspiv_piv_spof_pairs_at", "lspiv_piv_spof_pairs_dev_at"), lambda c: (*c.frames, *ws, *ov, *c.at, *c.res, c.planes),
+                      validate=validate)
 
 
 def piv_pairs_masked(imgs, window_size=(32, 32), overlap=(16, 16), image_mask=None, mask_coverage_min: float = 0.25,
-                     signal_threshold: Optional[float] = None, return_planes: bool = False, pair_offset: int = 0, out=None, scale=None):
+                     signal_threshold: Optional[float] = None, return_planes: bool = False, pair_offset: int = 0, out=None, scale=None,
+                     validate=None):
     """PIV of every consecutive frame pair of ``imgs`` under an image mask: :func:`piv_pairs` with every
     window correlated over its VALID samples only -- mean, standard deviation, the signal score and the divisor of the plane are those of
     the ``k`` samples where ``image_mask`` (``(H, W)``, bool / integer / float, non-zero = valid, one mask for every frame) is set;
@@ -246,9 +281,14 @@ def piv_pairs_masked(imgs, window_size=(32, 32), overlap=(16, 16), image_mask=No
     ``image_mask=None`` without one is :func:`piv_pairs`.  Pair-local, one window per job: every chunking gives the same bits
     (``pair_offset`` is accepted for symmetry); the float64 rescue pass follows as on the other per-pair paths.  ``out`` / ``scale`` as in
     :func:`piv_pairs` (the scaling is numpy's own arithmetic on the host).  Host stacks and ``DeviceFrames``."""
+    if validate is not None:
+        from .validate import validate_spec
+
+        validate = validate_spec(validate)
     if image_mask is None and not isinstance(window_size, window.MaskedWindow):
         window.coverage_spec(mask_coverage_min)
-        return piv_pairs(imgs, tuple(window_size), overlap, signal_threshold, return_planes, pair_offset, out=out, scale=scale)
+        return piv_pairs(imgs, tuple(window_size), overlap, signal_threshold, return_planes, pair_offset, out=out, scale=scale,
+                         **({} if validate is None else {"validate": validate}))
     a = imgs if is_device(imgs) else _lib.as_frames(imgs)
     spec = window.masked_spec(window_size, image_mask, mask_coverage_min, a.shape[1:])   # ValueError: sizes, coverage, the mask's shape
     ws = (int(spec[0]), int(spec[1]))
@@ -257,11 +297,11 @@ def piv_pairs_masked(imgs, window_size=(32, 32), overlap=(16, 16), image_mask=No
     return _run_pairs(a, ws, ov, signal_threshold, return_planes, pair_offset, out, scale,
                       ("lspiv_piv_masked_pairs_at", "lspiv_piv_masked_pairs_dev_at"),
                       lambda c: (*c.frames, *ws, *ov, c.extra, spec.k_min, *c.at, *c.res, c.planes),
-                      extra=lambda grid: spec.device_mask() if is_device(a) else spec.image_mask)
+                      extra=lambda grid: spec.device_mask() if is_device(a) else spec.image_mask, validate=validate)
 
 
 def piv_pairs_peak2(imgs, window_size=(32, 32), overlap=(16, 16), peak_exclusion: int = 2, signal_threshold: Optional[float] = None,
-                    return_planes: bool = False, pair_offset: int = 0, out=None, scale=None):
+                    return_planes: bool = False, pair_offset: int = 0, out=None, scale=None, validate=None):
     """PIV of every consecutive frame pair of ``imgs`` with the SECOND correlation peak of every window.
     Returns ``(u, v, corr_max, s2n, peak2[, planes])``: the first four (and the planes) are the bits of :func:`piv_pairs_shifted` without
     offsets; ``peak2`` is float32 ``(T-1, n_rows, n_cols, 4)`` = ``(u2, v2, corr2, peak_ratio)`` -- the runner-up vector in pixels, the
@@ -272,7 +312,13 @@ def piv_pairs_peak2(imgs, window_size=(32, 32), overlap=(16, 16), peak_exclusion
     primary's rule (log-Gaussian fit inside, "border_peak" on the border, "v_sign").  The float64 rescue pass corrects u, v and leaves
     ``peak2`` alone.  ``window_size``: square, 16, 32 or 64 px, or a ``window.PeakRatioWindow`` (which carries its own radius).
     Pair-local, one window per job: every chunking gives the same bits (``pair_offset`` is accepted for symmetry).  ``out`` / ``scale``
-    as in :func:`piv_pairs` (the scaling is numpy's own arithmetic on the host, on u, v and on u2, v2).  Host stacks and ``DeviceFrames``."""
+    as in :func:`piv_pairs` (the scaling is numpy's own arithmetic on the host, on u, v and on u2, v2).  Host stacks and ``DeviceFrames``.
+    ``validate`` as in :func:`piv_pairs`: the median test on u, v with the runner-up ``(u2, v2)`` offered for substitution; ``peak2`` stays
+    as it is and ``flag`` ends the returned tuple."""
+    if validate is not None:
+        from .validate import validate_spec
+
+        validate = validate_spec(validate)
     if isinstance(window_size, window.PeakRatioWindow):
         spec = window_size
     else:
@@ -281,13 +327,15 @@ def piv_pairs_peak2(imgs, window_size=(32, 32), overlap=(16, 16), peak_exclusion
     ov = (int(overlap[0]), int(overlap[1]))
     ret = _run_pairs(imgs, ws, ov, signal_threshold, return_planes, pair_offset, out, scale,
                      ("lspiv_piv_peak2_pairs_at", "lspiv_piv_peak2_pairs_dev_at"),
-                     lambda c: (*c.frames, *ws, *ov, *c.at, r, *c.res, c.aux, c.planes), aux=(np.float32, 4))
+                     lambda c: (*c.frames, *ws, *ov, *c.at, r, *c.res, c.aux, c.planes), aux=(np.float32, 4), validate=validate)
+    tail = () if validate is None else (ret[-1],)      # the flags of the median test
+    ret = ret if validate is None else ret[:-1]
     peak2 = ret[-1]
     if scale is not None:
         dt = np.ascontiguousarray(scale[2], dtype=np.float64).reshape(-1)[:, None, None]
         for k in range(2):
             _to_velocity(peak2[..., k], scale[k], dt, out=peak2[..., k])
-    return (*ret[:4], peak2, *ret[4:-1])
+    return (*ret[:4], peak2, *ret[4:-1], *tail)
 
 
 def second_peak(planes, peak_exclusion: int = 2) -> np.ndarray:

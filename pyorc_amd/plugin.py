@@ -132,6 +132,8 @@ def _wrap_get_piv(orig):
         masked = {k: kwargs.pop(k) for k in ("image_mask", "mask_coverage_min") if k in kwargs}
         # ... and the second correlation peak's `peak_ratio=` / `peak_exclusion=`
         second = {k: kwargs.pop(k) for k in ("peak_ratio", "peak_exclusion") if k in kwargs}
+        # ... and the vector validation's `validate=`
+        validate = kwargs.pop("validate", None)
         engine, bound = kwargs.get("engine"), None
         if sig is not None and "engine" in sig.parameters:
             try:
@@ -154,6 +156,8 @@ def _wrap_get_piv(orig):
                 raise TypeError(f"{' / '.join(masked)} is a keyword of engine='hip' only")
             if second:
                 raise TypeError(f"{' / '.join(second)} is a keyword of engine='hip' only")
+            if validate is not None:
+                raise TypeError("validate is a keyword of engine='hip' only")
             return orig(self, *args, **kwargs)
         # fail before any work if there is no MI355X / no library: the reference raises ValueError for an engine it cannot run
         from . import _lib
@@ -179,6 +183,11 @@ def _wrap_get_piv(orig):
                 extra.update(masked)
         if second.get("peak_ratio"):                                             # False is today's path
             extra.update(second)
+        if validate is not None:
+            from . import validate as validate_mod
+
+            if validate_mod.validate_spec(validate) is not None:                 # ValueError outside the ranges; None / False is today's path
+                extra["validate"] = validate
         if search_area is not None or sliding or extra:
             # the reference's method body lays the grid out by the window; with a search area of its own the engine's mirror of that
             # body (pyorc_amd.frames.get_piv: same configuration copy, coordinates, attributes and encoding) runs instead -- and with the

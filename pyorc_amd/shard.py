@@ -82,9 +82,16 @@ def _no_multipass(window_size) -> None:
                                   " with pyorc_amd.shard is not implemented: run the chain through get_ffpiv (devices=)")
 
 
+def _no_validate(validate) -> None:
+    """The vector validation is not run on a rank's block: the gathered fields are validated as a whole."""
+    if validate is not None and validate is not False:
+        raise NotImplementedError("validate with pyorc_amd.shard is not implemented: run validate.median_test on the gathered result "
+                                  "instead, or run the validation through get_ffpiv (devices=)")
+
+
 def sharded_piv(load_frames: Callable[[int, int], np.ndarray], n_pairs: int, window_size, overlap, comm,
                 compute: Optional[Callable] = None, signal_threshold=None, align: Optional[int] = None,
-                frame_shape=None) -> np.ndarray:
+                frame_shape=None, validate=None) -> np.ndarray:
     """Every rank computes its pair block and all ranks receive the full (4, n_pairs, n_rows, n_cols) block.
 
     ``load_frames(start, stop)`` returns frames [start, stop) as (T, H, W) -- each rank only ever touches its
@@ -94,6 +101,7 @@ def sharded_piv(load_frames: Callable[[int, int], np.ndarray], n_pairs: int, win
     large grids); without it on the longest anchor of the window family, which is right for every grid.
     """
     _no_multipass(window_size)
+    _no_validate(validate)
     if compute is None:
         from . import piv
 
@@ -345,12 +353,14 @@ class ShardedPivDev:
             self.send = self.recv = []
 
 
-def sharded_piv_dev(block, n_pairs: int, window_size, overlap, comm, signal_threshold=None, align: Optional[int] = None) -> np.ndarray:
+def sharded_piv_dev(block, n_pairs: int, window_size, overlap, comm, signal_threshold=None, align: Optional[int] = None,
+                    validate=None) -> np.ndarray:
     """One sharded pass with the rank's frames already in HBM: ``block`` = DeviceFrames of this rank's ``frame_block`` (its
     pairs + the halo frame; a rank without pairs passes an empty ``(0, H, W)`` stack -- the frame shape is still needed for the
     exchange --, ``None`` raises ValueError).  Returns (4, n_pairs, n_rows, n_cols) on every rank --
     bit-identical to ``piv.piv_pairs`` over the whole stack on one GPU."""
     _no_multipass(window_size)
+    _no_validate(validate)
     if block is None:
         raise ValueError("sharded_piv_dev needs this rank's DeviceFrames block (ranks without pairs pass an empty (0, H, W) stack)")
     plan = ShardedPivDev(comm, n_pairs, block.shape[1:], window_size, overlap, signal_threshold, align)

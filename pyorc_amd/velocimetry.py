@@ -184,6 +184,7 @@ def get_ffpiv(
     mask_coverage_min: float = 0.25,
     peak_ratio: bool = False,
     peak_exclusion: int = 2,
+    validate=None,
 ):
     """Compute time-resolved (or ensemble) PIV on the MI355X; signature of pyorc's ``get_ffpiv`` (ffpiv.py:24-42).
 
@@ -249,9 +250,31 @@ def get_ffpiv(
     one-window-per-job kernels.  Windows of 16, 32 or 64 px, per-timestep mode.  Pair-local: ``chunksize=``, ``devices=``, host stacks,
     ``DeviceFrames`` and lazy stacks give the same bits.  Not with ``image_mask``, ``spectral_filter``, ``coarse_passes``,
     ``deform_passes``, a search area or ``ensemble_corr=True`` (NotImplementedError): ``piv.second_peak`` on their planes serves those.
+
+    ``validate`` (the project's own option; None: today's path bit for bit): True, or a dict of
+    ``validate.median_test``'s keywords (``threshold`` 2.0, ``epsilon`` 0.1 px, ``min_neighbours`` 3, ``replace`` "nan" | "median",
+    ``iterations`` 1) -- the normalised median test over the 3 x 3 neighbourhood of every vector, on the displacement in PIXELS before the
+    px -> m/s scaling: on the result block in HBM for a ``DeviceFrames`` or lazy stack, through the host twin right after the call for a
+    host stack; both give the bits of ``median_test`` on the unscaled fields followed by the scaling.  The result gains the uint8
+    variable ``flag``: 0 kept or unjudged, 1 rejected (NaN), 2 substituted by the runner-up, 3 replaced by the neighbourhood median.  With
+    ``peak_ratio=True`` the runner-up vector is the first substitute for an outlier; ``v_x2``, ``v_y2``, ``corr2``, ``peak_ratio``,
+    ``corr`` and ``s2n`` stay as they are.  Pair-local: ``chunksize=``, ``devices=``, host stacks, ``DeviceFrames`` and lazy stacks give the
+    same bits.  With the plain path, ``search_area_size``, ``spectral_filter``, ``image_mask`` and ``peak_ratio``; not with
+    ``ensemble_corr=True``, ``coarse_passes`` or ``deform_passes`` (NotImplementedError): ``validate.median_test`` on the result serves those.
     """
     if engine != "hip":
         raise ValueError(f"Selected PIV engine {engine} does not exist.")
+    if validate is not None:
+        from .validate import validate_spec
+
+        validate = validate_spec(validate)     # ValueError for a value outside its range; False is None
+    if validate is not None:
+        if ensemble_corr:
+            raise NotImplementedError("validate together with ensemble_corr=True is not implemented: the ensemble has one field and no "
+                                      "per-pair result block; use validate.median_test on the result instead")
+        if (coarse_passes is not None and len(coarse_passes)) or window.deform_count(deform_passes):
+            raise NotImplementedError("validate together with coarse_passes / deform_passes is not implemented: no validation runs between "
+                                      "or after the passes of a chain; use validate.median_test on the result instead")
     # a search area of its own: one window argument that answers for the search area wherever a grid, a plan or an alignment is asked for
     window_size = window.search_spec(window_size, search_area_size)
     flt = window.spectral_filter_spec(spectral_filter)     # ValueError for an unknown name
@@ -344,7 +367,8 @@ def get_ffpiv(
         return _run_ensemble_chain(frames, work, devs, time, window_size, dim_size, y, x, dt_arr, res_x, res_y, signal_threshold, corr_min,
                                    s2n_min, count_min, ref_slices)
     args = (n_frames - 1, len(work), y, x, dt_arr, res_x, res_y, window_size, overlap, signal_threshold)
-    sink = _ensemble_sink(*args, corr_min, s2n_min, count_min, ref_slices) if ensemble_corr else _timestep_sink(*args)
+    sink = (_ensemble_sink(*args, corr_min, s2n_min, count_min, ref_slices) if ensemble_corr else
+            _timestep_sink(*args, **({} if validate is None else {"validate": validate})))
     if resident_run:
         return _run_resident(frames, work, sink, devs, time, signal_threshold)
     depth = (executor.default_depth() if prefetch is None else int(prefetch)) if hasattr(frames, "load") else 0
@@ -553,7 +577,7 @@ def _delivered(full, done):
     return {k: np.concatenate([v[i:j] for i, j in done], axis=0) for k, v in full.items()}
 
 
-def _timestep_sink(n_pairs, n_workers, y, x, dt, res_x, res_y, window_size, overlap, signal_threshold):
+def _timestep_sink(n_pairs, n_workers, y, x, dt, res_x, res_y, window_size, overlap, signal_threshold, validate=None):
     """Per-timestep PIV (pyorc/velocimetry/ffpiv.py:379-443).  The four result variables of the WHOLE run are allocated once and every
     launch writes its time slice of them (corr, s2n straight from the library, v_x / v_y through the px -> m/s scaling): no per-chunk
     arrays to concatenate at the end (the reference's xr.concat, ffpiv.py:442 -- 125 KB per pair, i.e. as many bytes again as a uint8
@@ -561,6 +585,8 @@ def _timestep_sink(n_pairs, n_workers, y, x, dt, res_x, res_y, window_size, over
     peak2 = isinstance(window_size, window.PeakRatioWindow)     # (four more variables)
     names = ("s2n", "corr", "v_x", "v_y") + (("peak_ratio", "corr2", "v_x2", "v_y2") if peak2 else ())
     full = {k: np.empty((n_pairs, len(y), len(x)), dtype=np.float32) for k in names}
+    if validate is not None:      # (the median test's flags)
+        full["flag"] = np.empty((n_pairs, len(y), len(x)), dtype=np.uint8)
     done = []
     px = [None] * n_workers            # per worker: scratch for a launch's u, v in pixels
     # (the modes whose entry points have no fused scaling: numpy's arithmetic on the host, the same bits)
@@ -580,7 +606,10 @@ def _timestep_sink(n_pairs, n_workers, y, x, dt, res_x, res_y, window_size, over
                 px[k] = [np.empty((p, len(y), len(x)), dtype=np.float32) for _ in range(2)]
             uv, scale = (px[k][0][:p], px[k][1][:p]), None
         ret = piv.piv_pairs(frames, window_size, overlap, signal_threshold, pair_offset=p0, scale=scale,
-                            out=uv + (full["corr"][p0:p1], full["s2n"][p0:p1]))
+                            out=uv + (full["corr"][p0:p1], full["s2n"][p0:p1]),
+                            **({} if validate is None else {"validate": validate}))
+        if validate is not None:      # validated in pixels inside the call, before either scaling
+            full["flag"][p0:p1] = ret[-1]
         if scale is None:
             _to_velocity(uv[0], res_x, dt_chunk[:, None, None], out=full["v_x"][p0:p1])
             _to_velocity(uv[1], res_y, dt_chunk[:, None, None], out=full["v_y"][p0:p1])
