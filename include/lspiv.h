@@ -139,6 +139,11 @@ int         lspiv_synchronize(void);                    /* hipDeviceSynchronize 
  *                      fitted inside its own iteration.  The same expressions on the same operands: results and rescue records are
  *                      the same bit for bit (tests/test_gpu_walk_defer.py); float64 frames with a signal threshold run the 0 form
  *                      either way.
+ * Un-packing of the 32 x 32 time-walking kernels (per frame pair):
+ *   "unpack_dpp"       1 (default; environment LSPIV_UNPACK_DPP_OPT) between its two transposes an iteration keeps the columns kx and -kx
+ *                      in adjacent lanes and exchanges them through DPP | 0 columns in natural order, exchanged through LDS
+ *                      (ds_bpermute).  The same expressions on the same operands: results and rescue records are the same bit for
+ *                      bit (tests/test_gpu_unpack_dpp.py).
  * float64 HOST stacks are narrowed to float32 while they are staged (the kernels compute in float32).  A frame that rides on a
  * DC offset far above its contrast would lose the low bits of its texture in that conversion, where the reference normalises
  * every window in float64; the per-window normalisation does not see a constant added to a frame, so:
@@ -824,6 +829,10 @@ int lspiv_debug_segments(int64_t n_pairs, int64_t pair_offset, int seg_len, int6
  * (result index inside the launch, ip << 16 | jp, the other arg-max candidate or ~0, 0), an "amb" record the result index.  The order of
  * a list is whatever the kernel's waves made it. */
 int lspiv_debug_rescue_lists(void* stream, uint32_t* fit, int64_t cap_fit, uint32_t* amb, int64_t cap_amb, int64_t* counts);
+/* Test hook (host only): the column-to-lane map of the 32 x 32 walking kernels under "unpack_dpp", as the kernels compile it.  For
+ * 0 <= i < 32: *col = the column lane i holds (compile-time form), *col_rt = the same from the branch-free run-time form the second
+ * transpose uses, *lane = the lane that holds column i.  LSPIV_EINVAL outside the range. */
+int lspiv_debug_unpack_map(int i, int* col, int* col_rt, int* lane);
 
 /* Measurement (round 5): with lspiv_set_option("time_kernel", 1) every launch records HIP events on its own stream right before and
  * right after its PIV kernel(s) -- not around the rescue kernels that follow.  lspiv_kernel_times returns the durations [ms] of the

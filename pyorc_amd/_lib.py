@@ -63,6 +63,7 @@ SIGNATURES = {
     "lspiv_get_option": (_i32, [C.c_char_p, C.POINTER(_i32)]),
     "lspiv_rescue_stats": (_i32, [_vp, _pi64]),
     "lspiv_debug_rescue_lists": (_i32, [_vp, _vp, _i64, _vp, _i64, _pi64]),
+    "lspiv_debug_unpack_map": (_i32, [_i32, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "lspiv_kernel_kind": (_i32, [_i32, _i32]),
     "lspiv_grid_shape": (_i32, [_i64, _i64, _i32, _i32, _i32, _i32, _pi64, _pi64]),
     "lspiv_grid_coords": (_i32, [_i64, _i64, _i32, _i32, _i32, _i32, _pi64, _pi64]),

@@ -159,6 +159,7 @@ std::atomic<int> g_opt_round_odd{env_opt("LSPIV_ROUND_ODD", 0, 2)};
 std::atomic<int> g_opt_rescue{env_opt_def("LSPIV_RESCUE", 0, 1, 1)};
 std::atomic<int> g_opt_rescue_generic{env_opt("LSPIV_RESCUE_GENERIC", 0, 1)};
 static std::atomic<int> g_opt_defer_fit{env_opt_def("LSPIV_DEFER_FIT", 0, 1, 1)};
+static std::atomic<int> g_opt_unpack_dpp{env_opt_def("LSPIV_UNPACK_DPP_OPT", 0, 1, 1)};
 std::atomic<int> g_rescue_fit_size{-1};
 std::atomic<int> g_opt_narrow_offset{env_opt_def("LSPIV_NARROW_OFFSET", -1, 1 << 30, 1024)};
 std::atomic<int> g_opt_rescue_kappa{env_opt_def("LSPIV_RESCUE_KAPPA", 0, 1000000, 500)};
@@ -187,6 +188,8 @@ static const Option kOptions[] = {
     {"rescue", &g_opt_rescue, 0, 1, "rescue must be 0 (float32 results as they are) or 1 (float64 rescue pass)"},
     {"defer_fit", &g_opt_defer_fit, 0, 1,
      "defer_fit must be 1 (32 x 32 walking kernels fit 32 planes at once) or 0 (every plane in its own iteration; same results)"},
+    {"unpack_dpp", &g_opt_unpack_dpp, 0, 1,
+     "unpack_dpp must be 1 (32 x 32 walking kernels exchange mirrored columns through DPP) or 0 (through LDS; same results)"},
     {"rescue_generic", &g_opt_rescue_generic, 0, 1,
      "rescue_generic must be 0 (fixed-size fit kernels for square 16 / 32 / 64 px windows) or 1 (run-time geometry for every launch)"},
     {"narrow_offset", &g_opt_narrow_offset, -1, INT_MAX,
@@ -245,6 +248,7 @@ int lspiv::walk_setting() {
 }
 
 int lspiv::defer_fit_setting() { return g_opt_defer_fit.load(); }
+int lspiv::unpack_dpp_setting() { return g_opt_unpack_dpp.load(); }
 
 extern "C" {
 

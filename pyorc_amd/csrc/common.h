@@ -556,6 +556,9 @@ int walk_setting();
 // option "defer_fit" (LSPIV_DEFER_FIT presets it): 1 = the 32 x 32 walking kernels fit 32 planes at once (piv_fft_impl.h, DEFER), 0 = every
 // plane in its own iteration; same bits either way
 int defer_fit_setting();
+// option "unpack_dpp" (LSPIV_UNPACK_DPP_OPT presets it): 1 = the per-pair 32 x 32 walking kernels exchange the un-packing's mirrored columns
+// through DPP (piv_fft_impl.h, UDPP), 0 = through ds_bpermute; same bits either way
+int unpack_dpp_setting();
 // Segments of the time-walking kernels.  A job walks one window through a run of consecutive frame pairs and shares
 // every frame's spectrum between the two pairs it belongs to; which frames share transforms depends on where a run
 // starts, so the runs ("segments") are ANCHORED: they start at the absolute pair indices k * kWalkAnchor of the caller's

@@ -32,6 +32,7 @@
 #pragma once
 #include <algorithm>
 #include <cstdlib>
+#include <type_traits>
 
 #include "common.h"
 #include "fft_regs.h"
@@ -747,9 +748,55 @@ __device__ __forceinline__ void transpose_plane_half64(float* buf, int lg, float
     __builtin_amdgcn_wave_barrier();
   }
 }
-template <int N, bool HALF = false>
+// ---- 32 x 32 walking kernels: mirrored columns in adjacent lanes (UDPP, walk_iteration) -----------------------------------------
+// Between the two transposes of an iteration lane l of a group holds column kx = unpack_col(l) instead of kx = l:
+//   col(0) = 0, col(1) = 16, col(2 j) = j, col(2 j + 1) = 32 - j  (j = 1 .. 15)
+// a bijection in which kx and -kx mod 32 sit in lanes l and l ^ 1, the two columns that mirror onto themselves (0 and 16) next to
+// each other in lanes 0 and 1.  The un-packing's exchange with the mirrored lane is then a DPP quad_perm:[1,0,3,2] instead of a
+// ds_bpermute.  The map costs the transposes nothing: the first one scatters register j (column j) into buffer row unpack_lane(j)
+// -- a compile-time row, the same 32 rows as before -- and reads row l as before; the second one scatters down buffer column
+// unpack_col(l) -- the 32 lanes of a group still hit 32 consecutive banks -- and reads row y as before.  Outside the two transposes
+// the layout is lane = y, natural order.
+constexpr int unpack_col(int l) { return l == 0 ? 0 : l == 1 ? 16 : (l & 1) ? 32 - (l >> 1) : (l >> 1); }
+constexpr int unpack_lane(int kx) { return kx == 0 ? 0 : kx == 16 ? 1 : kx < 16 ? 2 * kx : 2 * (32 - kx) + 1; }
+// unpack_col of a run-time lane without branches (written with ?: the compiler splits the iteration into basic blocks around it)
+__host__ __device__ __forceinline__ int unpack_col_of(int l) {
+  const int m = -(l & 1), h = l >> 1;              // odd lanes: 32 - h, even lanes: h
+  return ((h ^ m) - m) + (32 & m) - ((int)(l == 1) << 4);
+}
+enum class ColMap { kNatural, kToPaired, kFromPaired };
+template <ColMap MAP>
+__device__ __forceinline__ void transpose_plane_paired32(float* buf, int lg, float (&x)[32]) {
+  constexpr int LR = Geo<32>::LDS_ROW;
+  float* wcol = buf + (MAP == ColMap::kToPaired ? lg : unpack_col_of(lg));
+#pragma unroll
+  for (int j = 0; j < 32; ++j) wcol[(MAP == ColMap::kToPaired ? unpack_lane(j) : j) * LR] = x[j];
+  __builtin_amdgcn_wave_barrier();
+  lds_row_read<32>(buf + lg * LR, x);
+  __builtin_amdgcn_wave_barrier();
+}
+// The mirrored lane's values of a and b under the paired map; the lanes of self_mask (0 and 1 of a group) mirror onto themselves.
+// Each value is ONE instruction: v_cndmask_b32_dpp d, v, v, vcc = the lane's own v where vcc is set, the quad neighbour's elsewhere.
+// Written out because the compiler keeps the lane mask in an SGPR pair and selects with the VOP3 form, which has no DPP on this target:
+// v_mov_b32_dpp + v_cndmask_b32_e64 per value, 128 instead of 64 extra VALU per iteration.  s_mov + s_nop are the two wait states
+// between a VALU write of a VGPR and a DPP read of it, which the compiler does not insert in front of an asm statement.
+__device__ __forceinline__ void mirror_dpp2(uint64_t self_mask, float a, float b, float& ma, float& mb) {
+  asm("s_mov_b64 vcc, %4\n\t"
+      "s_nop 0\n\t"
+      "v_cndmask_b32_dpp %0, %2, %2, vcc quad_perm:[1,0,3,2] row_mask:0xf bank_mask:0xf\n\t"
+      "v_cndmask_b32_dpp %1, %3, %3, vcc quad_perm:[1,0,3,2] row_mask:0xf bank_mask:0xf"
+      : "=&v"(ma), "=v"(mb)
+      : "v"(a), "v"(b), "s"(self_mask)
+      : "vcc");
+}
+
+template <int N, bool HALF = false, ColMap MAP = ColMap::kNatural>
 __device__ __forceinline__ void transpose2(float* buf, int lg, float (&xr)[N], float (&xi)[N]) {
-  if constexpr (HALF && N == 64) {
+  if constexpr (MAP != ColMap::kNatural) {
+    static_assert(N == 32 && !HALF, "the paired column map is built for 32 x 32");
+    transpose_plane_paired32<MAP>(buf, lg, xr);
+    transpose_plane_paired32<MAP>(buf, lg, xi);
+  } else if constexpr (HALF && N == 64) {
     transpose_plane_half64(buf, lg, xr);
     transpose_plane_half64(buf, lg, xi);
   } else {
@@ -1628,8 +1675,9 @@ struct WalkCarry {
 
 // One ky of the un-packing: mr / mi = registers N - ky of the mirrored lane's xr / xi.  Both cross spectra of the step, packed for
 // the shared inverse; the carry moves on.
-template <int N>
-__device__ __forceinline__ void unpack_step(int ky, float mr, float mi, int partner_byte, WalkCarry<N>& c, float (&xr)[N], float (&xi)[N]) {
+// UDPP: the mirrored lane is the quad neighbour (unpack_col), self_mask = the lanes that mirror onto themselves
+template <int N, bool UDPP = false>
+__device__ __forceinline__ void unpack_step(int ky, float mr, float mi, int partner_byte, WalkCarry<N>& c, float (&xr)[N], float (&xi)[N], uint64_t self_mask = 0) {
   constexpr int H = N / 2;
   const int kn = (N - ky) % N;
   const float pr = xr[ky] + mr, pi = xi[ky] - mi;     // 2 F_f      (each with its frame's 1 / (2 N^2))
@@ -1642,8 +1690,15 @@ __device__ __forceinline__ void unpack_step(int ky, float mr, float mi, int part
   xr[ky] = ar - bi;                // (R_a + i R_b)[ky][kx]
   xi[ky] = ai + br;
   if (ky >= 1 && ky < H) {         // rows above N/2: conj of (R_a - i R_b) at the mirrored lane
-    xr[kn] = bperm_f(partner_byte, ar + bi);
-    xi[kn] = -bperm_f(partner_byte, ai - br);
+    if constexpr (UDPP) {
+      float er, ei;
+      mirror_dpp2(self_mask, ar + bi, ai - br, er, ei);
+      xr[kn] = er;
+      xi[kn] = -ei;
+    } else {
+      xr[kn] = bperm_f(partner_byte, ar + bi);
+      xi[kn] = -bperm_f(partner_byte, ai - br);
+    }
   }
 }
 
@@ -1651,7 +1706,9 @@ __device__ __forceinline__ void unpack_step(int ky, float mr, float mi, int part
 // (pair f), their means (DC bins) and NaN flags; the carry moves on to frame f + 1.
 // RELAX: without the scheduling barriers between the phases (a caller with registers to spare: the 32 x 32 ensemble kernel runs two
 // waves per SIMD for its register accumulator and may use 256 VGPRs)
-template <typename T, int N, bool WANT_NZ, bool RELAX = false, bool HALF_TILE = false, int UB = 1, bool U8_EARLY = false, bool FOLD = kFftFoldLen<N>, bool SR = kFftSrLen<N>>
+// UDPP: between the transposes the columns sit in the lanes of unpack_col, and the un-packing exchanges through DPP (kWalkUnpackDpp)
+template <typename T, int N, bool WANT_NZ, bool RELAX = false, bool HALF_TILE = false, int UB = 1, bool U8_EARLY = false, bool FOLD = kFftFoldLen<N>, bool SR = kFftSrLen<N>,
+          bool UDPP = false>
 __device__ __forceinline__ void walk_iteration(const PivParams& p, const T* row, bool has2, float* buf, int lg,
                                                int partner_byte, int lane0_byte, WalkCarry<N>& c, float (&xr)[N],
                                                float (&xi)[N], float& mean_a, float& mean_b, bool& skip_a, bool& skip_b,
@@ -1712,7 +1769,7 @@ __device__ __forceinline__ void walk_iteration(const PivParams& p, const T* row,
   fft_walk<false, false, FOLD, SR>(xr, xi);   // along x
   LSPIV_WALK_SB;
   LSPIV_SETPRIO(LSPIV_PRIO_T);
-  transpose2<N, HALF_TILE>(buf, lg, xr, xi);    // lane = kx, regs = y
+  transpose2<N, HALF_TILE, UDPP ? ColMap::kToPaired : ColMap::kNatural>(buf, lg, xr, xi);    // lane = kx (UDPP: unpack_col(lane)), regs = y
   LSPIV_WALK_SB;
   LSPIV_SETPRIO(0);
   fft_walk<false, false, FOLD, SR>(xr, xi);   // along y -> Z[ky][kx]
@@ -1720,7 +1777,18 @@ __device__ __forceinline__ void walk_iteration(const PivParams& p, const T* row,
   LSPIV_SETPRIO(LSPIV_PRIO_U);
   // un-pack the two spectra, form both cross spectra and pack them for the shared inverse, one ky at a time (a
   // step only touches registers ky and N - ky of this lane and of the mirrored lane, so it can run in place)
-  if constexpr (UB <= 1) {
+  if constexpr (UDPP) {
+    // the mirrored lane is the quad neighbour: no LDS instruction, no round trip to batch
+    constexpr uint64_t self_mask = 0x0000000300000003ull;   // lanes 0 and 1 of both groups: columns 0 and 16
+#pragma unroll
+    for (int ky = 0; ky <= H; ++ky) {
+      const int kn = (N - ky) % N;
+      float mr, mi;
+      mirror_dpp2(self_mask, xr[kn], xi[kn], mr, mi);
+      unpack_step<N, true>(ky, mr, mi, partner_byte, c, xr, xi, self_mask);
+    }
+    __builtin_amdgcn_sched_barrier(0);
+  } else if constexpr (UB <= 1) {
 #pragma unroll
     for (int ky = 0; ky <= H; ++ky) {
       const int kn = (N - ky) % N;
@@ -1752,7 +1820,7 @@ __device__ __forceinline__ void walk_iteration(const PivParams& p, const T* row,
   fft_walk<true, false, FOLD, SR>(xr, xi);    // along ky
   LSPIV_WALK_SB;
   LSPIV_SETPRIO(LSPIV_PRIO_T);
-  transpose2<N, HALF_TILE>(buf, lg, xr, xi);      // lane = y, regs = kx
+  transpose2<N, HALF_TILE, UDPP ? ColMap::kFromPaired : ColMap::kNatural>(buf, lg, xr, xi);      // lane = y, regs = kx
   if constexpr (kEnsLdsRmw<N>) {
     // 64 x 64 ensemble kernel: the job's tile is free from here to the next iteration's first transpose -- the running partial
     // sum of the job starts its way from HBM into it now (asynchronously, no registers) and is there when the planes are final
@@ -1810,6 +1878,25 @@ constexpr int kDeferSlots = 32, kDeferRecDwords = 8;   // 16 iterations x 2 plan
 constexpr bool kWalkDefer32[3][2][2] = {{{true, true}, {true, true}}, {{true, true}, {true, true}}, {{true, false}, {true, false}}};
 template <typename T, int N, bool PLANES, bool WANT_NZ>
 constexpr bool kWalkDefer = N == 32 && (LSPIV_WALK_DEFER >= 0 ? LSPIV_WALK_DEFER != 0 : kWalkDefer32[kSampleKind<T>][PLANES][WANT_NZ]);
+// The un-packing through DPP (UDPP, unpack_col): per kernel by the same resource rule, the "unpack_dpp" option picks the form at launch;
+// -DLSPIV_UNPACK_DPP=0 / 1 forces it off / on for every per-pair 32 x 32 walking kernel.  [sample type][PLANES][WANT_NZ]; all twelve, in
+// both forms of the fit, need no more VGPRs than the LDS form (up to 8 fewer: the batch's transient registers go), no scratch, no wave lost
+#ifndef LSPIV_UNPACK_DPP
+#define LSPIV_UNPACK_DPP -1
+#endif
+constexpr bool kWalkUnpackDpp32[3][2][2] = {{{true, true}, {true, true}}, {{true, true}, {true, true}}, {{true, true}, {true, true}}};
+template <typename T, int N, bool PLANES, bool WANT_NZ>
+constexpr bool kWalkUnpackDpp = N == 32 && (LSPIV_UNPACK_DPP >= 0 ? LSPIV_UNPACK_DPP != 0 : kWalkUnpackDpp32[kSampleKind<T>][PLANES][WANT_NZ]);
+// The first iteration of a wave has no pair f - 1 in either group (f == p0): with LSPIV_SKIP_FIRST_A the 32 x 32 kernels leave out the
+// maximum, the search and the fit of its plane a -- nothing of it is stored, and a record slot that is not written stays invalid.
+#ifndef LSPIV_SKIP_FIRST_A
+#define LSPIV_SKIP_FIRST_A 1
+#endif
+// Per kernel by the resource rule again: the branch keeps plane a's registers live across plane b's maximum, and without PLANES (where they
+// are live up to the plane stores anyway) only the uint8 kernels without the score stay free of scratch (149 -> 167 VGPRs); the float32
+// ones spill 8 - 32 bytes, the float64 one loses its third wave (167 -> 178).
+template <typename T, int N, bool PLANES, bool WANT_NZ>
+constexpr bool kWalkSkipFirstA = LSPIV_SKIP_FIRST_A && N == 32 && (PLANES || (sizeof(T) == 1 && !WANT_NZ));
 // the packed word of a record: ip | jp << 8 | flags
 constexpr uint32_t kDeferNearTie = 1u << 16, kDeferDead = 1u << 17, kDeferSkip = 1u << 18, kDeferValid = 1u << 19, kDeferNote = 1u << 20;
 
@@ -1903,9 +1990,10 @@ __device__ __forceinline__ void defer_flush(uint32_t* stage, int lg, const PivPa
   __builtin_amdgcn_wave_barrier();
 }
 
-template <typename T, int N, bool PLANES, bool WANT_NZ, bool DEFER = false>
+template <typename T, int N, bool PLANES, bool WANT_NZ, bool DEFER = false, bool UDPP = false>
 __global__ __launch_bounds__(BLOCK, (kWalkWaves<T, N>)) void piv_fft_walk_kernel(PivParams p) {
   static_assert(!DEFER || (N == 32 && !kTwoPlaneEpilogue<N>), "the batched fit is built for two groups of 32 lanes");
+  static_assert(!UDPP || N == 32, "the paired column map is built for 32 x 32");
   const uint32_t seg_len = p.seg_len, n_seg = p.n_seg;
   extern __shared__ __attribute__((aligned(16))) float smem[];
   using G = Geo<N>;
@@ -1918,7 +2006,7 @@ __global__ __launch_bounds__(BLOCK, (kWalkWaves<T, N>)) void piv_fft_walk_kernel
   // DEFER: the job's kDeferSlots records behind the tiles
   uint32_t* stage = reinterpret_cast<uint32_t*>(smem + WAVES_PER_BLOCK * G::GROUPS * G::LDS_JOB) + (wave * G::GROUPS + grp) * kDeferSlots * kDeferRecDwords;
   if constexpr (DEFER) stage[lg * kDeferRecDwords + 6] = 0u;
-  uint32_t it = 0;   // DEFER: iterations of the WAVE so far
+  uint32_t it = 0;   // DEFER, kWalkSkipFirstA: iterations of the WAVE so far
   const int partner_byte = partner_byte_of<N>(lane, lg);
   const int lane0_byte = lane0_byte_of<N>();
 
@@ -1943,9 +2031,10 @@ __global__ __launch_bounds__(BLOCK, (kWalkWaves<T, N>)) void piv_fft_walk_kernel
     const bool has2 = f + 1 <= p1;
     float xr[N], xi[N], mean_a, mean_b;
     bool skip_a, skip_b, dead_a, dead_b;
-    walk_iteration<T, N, WANT_NZ, kWalkRelax<T, N>, false, kWalkUnpackBatch<T, N, PLANES, WANT_NZ>, kWalkU8Early<N, PLANES, WANT_NZ>, kFftFoldWalk<N>, kFftSrWalk<N>>(
+    walk_iteration<T, N, WANT_NZ, kWalkRelax<T, N>, false, kWalkUnpackBatch<T, N, PLANES, WANT_NZ>, kWalkU8Early<N, PLANES, WANT_NZ>, kFftFoldWalk<N>, kFftSrWalk<N>, UDPP>(
         p, row, has2, buf, lg, partner_byte, lane0_byte, carry, xr, xi, mean_a, mean_b, skip_a, skip_b, dead_a, dead_b);
     if (WANT_NZ && win_dropped) skip_a = skip_b = true;
+    const bool with_a = !kWalkSkipFirstA<T, N, PLANES, WANT_NZ> || it != 0;   // wave-uniform: no group has a pair f - 1 in the wave's first iteration
     const bool valid_a = job_valid && f > p0, valid_b = job_valid && has2;
     if constexpr (kTwoPlaneEpilogue<N>) {
       // both planes side by side (PeakFit above): maxima and peak rows from registers, plane a parked whole in the tile, plane b's
@@ -1991,7 +2080,7 @@ __global__ __launch_bounds__(BLOCK, (kWalkWaves<T, N>)) void piv_fft_walk_kernel
       const float vmax_b = plane_max<N>(xi, row_max_b);
       const int ip_b = peak_row<N>(lg, vmax_b, row_max_b);
       uint32_t* rec = stage + (it & (kDeferSlots / 2 - 1)) * 2 * kDeferRecDwords;
-      {
+      if (with_a) {
         float row_max;
         const uint32_t g = (f - 1) * p.n_win + win;
         const float vmax = plane_max<N>(xr, row_max);
@@ -2007,7 +2096,7 @@ __global__ __launch_bounds__(BLOCK, (kWalkWaves<T, N>)) void piv_fft_walk_kernel
       float row_max_b;
       const float vmax_b = plane_max<N>(xi, row_max_b);
       const int ip_b = peak_row<N>(lg, vmax_b, row_max_b);
-      {
+      if (with_a) {
         float row_max, u, v;
         const uint32_t g = (f - 1) * p.n_win + win;
         const float vmax = plane_max<N>(xr, row_max);
@@ -2039,6 +2128,8 @@ __global__ __launch_bounds__(BLOCK, (kWalkWaves<T, N>)) void piv_fft_walk_kernel
     if constexpr (DEFER) {
       ++it;
       if ((it & (kDeferSlots / 2 - 1)) == 0) defer_flush<N>(stage, lg, p);   // the groups still in the loop; every slot of theirs is written
+    } else if constexpr (kWalkSkipFirstA<T, N, PLANES, WANT_NZ>) {
+      it = 1;
     }
   }
   if constexpr (DEFER) defer_flush<N>(stage, lg, p);   // what is left, of both groups; nothing where the last iteration flushed
@@ -2779,23 +2870,31 @@ static hipError_t launch_t(const PivParams& p, bool ensemble, hipStream_t s) {
     // the batched fit (kWalkDefer, option "defer_fit"): + the jobs' staging records
     constexpr size_t defer_lds = walk_lds + (size_t)jobs_per_block * kDeferSlots * kDeferRecDwords * 4;
     const bool defer = defer_fit_setting() != 0;
-    if (p.planes) {
-      if constexpr (kWalkDefer<T, N, true, WANT_NZ>) {
+    // the un-packing through DPP (kWalkUnpackDpp, option "unpack_dpp"), in either form of the fit
+    const bool udpp = unpack_dpp_setting() != 0;
+    auto launch_walk = [&](auto planes_c) {
+      constexpr bool PLANES = decltype(planes_c)::value;
+      if constexpr (kWalkDefer<T, N, PLANES, WANT_NZ>) {
         if (defer) {
-          hipLaunchKernelGGL((piv_fft_walk_kernel<T, N, true, WANT_NZ, true>), dim3(wblocks), dim3(BLOCK), defer_lds, s, q);
-          return hipGetLastError();
+          if constexpr (kWalkUnpackDpp<T, N, PLANES, WANT_NZ>) {
+            if (udpp) {
+              hipLaunchKernelGGL((piv_fft_walk_kernel<T, N, PLANES, WANT_NZ, true, true>), dim3(wblocks), dim3(BLOCK), defer_lds, s, q);
+              return;
+            }
+          }
+          hipLaunchKernelGGL((piv_fft_walk_kernel<T, N, PLANES, WANT_NZ, true>), dim3(wblocks), dim3(BLOCK), defer_lds, s, q);
+          return;
         }
       }
-      hipLaunchKernelGGL((piv_fft_walk_kernel<T, N, true, WANT_NZ>), dim3(wblocks), dim3(BLOCK), walk_lds, s, q);
-    } else {
-      if constexpr (kWalkDefer<T, N, false, WANT_NZ>) {
-        if (defer) {
-          hipLaunchKernelGGL((piv_fft_walk_kernel<T, N, false, WANT_NZ, true>), dim3(wblocks), dim3(BLOCK), defer_lds, s, q);
-          return hipGetLastError();
+      if constexpr (kWalkUnpackDpp<T, N, PLANES, WANT_NZ>) {
+        if (udpp) {
+          hipLaunchKernelGGL((piv_fft_walk_kernel<T, N, PLANES, WANT_NZ, false, true>), dim3(wblocks), dim3(BLOCK), walk_lds, s, q);
+          return;
         }
       }
-      hipLaunchKernelGGL((piv_fft_walk_kernel<T, N, false, WANT_NZ>), dim3(wblocks), dim3(BLOCK), walk_lds, s, q);
-    }
+      hipLaunchKernelGGL((piv_fft_walk_kernel<T, N, PLANES, WANT_NZ>), dim3(wblocks), dim3(BLOCK), walk_lds, s, q);
+    };
+    if (p.planes) launch_walk(std::true_type{}); else launch_walk(std::false_type{});
     return hipGetLastError();
   }
   const uint32_t jobs = p.n_pairs * ((p.n_win + 1) / 2);
