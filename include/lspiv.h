@@ -144,6 +144,12 @@ int         lspiv_synchronize(void);                    /* hipDeviceSynchronize 
  *                      in adjacent lanes and exchanges them through DPP | 0 columns in natural order, exchanged through LDS
  *                      (ds_bpermute).  The same expressions on the same operands: results and rescue records are the same bit for
  *                      bit (tests/test_gpu_unpack_dpp.py).
+ * Cross-row reductions and un-pack lane masks of the 32 x 32 time-walking kernels (per frame pair):
+ *   "lds_light"        1 (default; environment LSPIV_LDS_LIGHT) the 32-lane reductions of an iteration join their two 16-lane rows with
+ *                      v_permlane16_swap, the integer ones that come in pairs in one chain | 0 the rows are joined through LDS
+ *                      (ds_swizzle).  Only on top of "unpack_dpp" = 1 and
+ *                      "defer_fit" = 1; ignored otherwise.  Results and rescue records are the same bit for bit
+ *                      (tests/test_gpu_lds_light.py).
  * float64 HOST stacks are narrowed to float32 while they are staged (the kernels compute in float32).  A frame that rides on a
  * DC offset far above its contrast would lose the low bits of its texture in that conversion, where the reference normalises
  * every window in float64; the per-window normalisation does not see a constant added to a frame, so:
@@ -821,6 +827,13 @@ int lspiv_debug_fft(int n, int inverse, const float* in, float* out, int64_t cou
  * separate complex multiplies, 2 = twiddle scales folded into the next butterfly level, 4 = conjugate-pair split radix (fft_regs.h;
  * one bit per form, so 3 is none).  Other n with form 1 / 2 / 4, or another form: LSPIV_EUNSUPPORTED. */
 int lspiv_debug_fft_form(int n, int form, int inverse, const float* in, float* out, int64_t count);
+/* Test hook: the 32-lane reductions of the kernels (csrc/common.h) on `count` whole waves of 64 lanes; in / out: host arrays of count * 64
+ * 32-bit words, out[l] = what lane l holds after the reduction over its 32-lane half.  op 0 = float sum (bits), 1 = integer sum, 2 =
+ * signed minimum, 3 = signed maximum (what the maxima of the clipped planes are taken with); form 0 = the two 16-lane rows joined through
+ * ds_swizzle, 1 = through v_permlane16_swap ("lds_light"), 2 / 3 (integer ops) = the paired reduction of "lds_light" on (the lane's value,
+ * the value of the same lane of the other half): 2 returns the first result, 3 the second -- which is what the other half's lanes hold
+ * after forms 0 and 1.  Another op or form: LSPIV_EUNSUPPORTED. */
+int lspiv_debug_half_reduce(int op, int form, const uint32_t* in, uint32_t* out, int64_t count);
 /* Test hook (host only): how the time-walking kernels cut a chunk of n_pairs pairs that starts at absolute pair index
  * pair_offset into segments of seg_len pairs anchored at multiples of seg_len: pairs in the first segment, segment count. */
 int lspiv_debug_segments(int64_t n_pairs, int64_t pair_offset, int seg_len, int64_t* seg_first, int64_t* n_seg);

@@ -268,22 +268,68 @@ __device__ __forceinline__ float swz16_f(float x) {
 }
 __device__ __forceinline__ int swz16_i(int x) { return __builtin_amdgcn_ds_swizzle(x, SWZ_XOR16); }
 
+// The two 16-lane rows of a 32-lane half joined with gfx950's v_permlane16_swap (it swaps the odd rows of its first register with the
+// even rows of its second): after permlane16_swap(a, b) on a = b = x every lane holds the pair (a, b) = (x of the even row's lane,
+// x of the odd row's lane) -- ONE VALU instruction where ds_swizzle(SWAP,16) is a trip through the LDS pipe plus an
+// s_waitcnt lgkmcnt(0), which also drains every other LDS operation in flight.  Both rows combine the pair in the same operand order
+// (even, odd); for integer +, min, max and for float + that gives the bits of the swizzle form (the pair16 forms below: S16).
+// Inline assembly for the reason given at permlane32_swap below, with the two wait states between a VALU write and this read.
+__device__ __forceinline__ void permlane16_swap(unsigned& a, unsigned& b) {   // a[odd 16-lane rows] <-> b[even 16-lane rows]
+  asm("s_nop 1\n\tv_permlane16_swap_b32 %0, %1" : "+v"(a), "+v"(b));
+}
+struct RowPair { unsigned ev, od; };
+__device__ __forceinline__ RowPair row_pair(unsigned x) {
+  RowPair r = {x, x};
+  permlane16_swap(r.ev, r.od);   // ev = the even row's values in both rows, od = the odd row's
+  return r;
+}
+__device__ __forceinline__ float pair16_sum(float x) {
+  const RowPair r = row_pair(__builtin_bit_cast(unsigned, x));
+  return __builtin_bit_cast(float, r.ev) + __builtin_bit_cast(float, r.od);
+}
+__device__ __forceinline__ int pair16_sum_i(int x) { const RowPair r = row_pair((unsigned)x); return (int)(r.ev + r.od); }
+__device__ __forceinline__ int pair16_min_i(int x) { const RowPair r = row_pair((unsigned)x); return min((int)r.ev, (int)r.od); }
+__device__ __forceinline__ int pair16_max_i(int x) { const RowPair r = row_pair((unsigned)x); return max((int)r.ev, (int)r.od); }
+
 // sum over the 32 lanes of a half-wave; every lane gets the total (fixed order => deterministic)
+// S16: the last step through v_permlane16_swap instead of ds_swizzle (same bits)
+template <bool S16 = false>
 __device__ __forceinline__ float half_sum(float x) {
   x += dpp_f<DPP_XOR1>(x);
   x += dpp_f<DPP_XOR2>(x);
   x += dpp_f<DPP_HALF_MIRROR>(x);
   x += dpp_f<DPP_MIRROR>(x);
-  x += swz16_f(x);
+  if constexpr (S16) x = pair16_sum(x); else x += swz16_f(x);
   return x;
 }
+template <bool S16 = false>
 __device__ __forceinline__ int half_sum_i(int x) {
   x += dpp_i<DPP_XOR1>(x);
   x += dpp_i<DPP_XOR2>(x);
   x += dpp_i<DPP_HALF_MIRROR>(x);
   x += dpp_i<DPP_MIRROR>(x);
-  x += swz16_i(x);
+  if constexpr (S16) x = pair16_sum_i(x); else x += swz16_i(x);
   return x;
+}
+// TWO integer reductions over a half-wave for little more than one: the rows are joined FIRST -- after permlane16_swap(x, y) the even rows
+// hold (x of the even row, x of the odd row) and the odd rows (y of the even row, y of the odd row) -- so ONE chain of four DPP steps
+// reduces x in the even rows and y in the odd rows, and a second swap hands both results to every lane.  8 VALU for the pair, where two
+// reductions cost 10 + two ds_swizzle in the swizzle form and 14 in the S16 form.  Integer +, min and max are associative and
+// commutative, so the bits are those of the single reductions; float sums keep their fixed order and cannot take this form.
+enum class RedOp { kSum, kMin, kMax };
+template <RedOp OP> __device__ __forceinline__ int red_i(int a, int b) { return OP == RedOp::kSum ? a + b : OP == RedOp::kMin ? min(a, b) : max(a, b); }
+template <RedOp OP>
+__device__ __forceinline__ void half_reduce2_i(int& x, int& y) {
+  unsigned a = (unsigned)x, b = (unsigned)y;
+  permlane16_swap(a, b);
+  int t = red_i<OP>((int)a, (int)b);
+  t = red_i<OP>(t, dpp_i<DPP_XOR1>(t));
+  t = red_i<OP>(t, dpp_i<DPP_XOR2>(t));
+  t = red_i<OP>(t, dpp_i<DPP_HALF_MIRROR>(t));
+  t = red_i<OP>(t, dpp_i<DPP_MIRROR>(t));
+  const RowPair r = row_pair((unsigned)t);
+  x = (int)r.ev;
+  y = (int)r.od;
 }
 // the same over one DPP row of 16 lanes (16 x 16 windows: four jobs per wave)
 __device__ __forceinline__ float row_sum(float x) {
@@ -370,15 +416,17 @@ __device__ __forceinline__ float gauss_offset_fast(float lm, float l0, float lp,
   den = 2.0f * lm - 4.0f * l0 + 2.0f * lp;
   return den != 0.0f ? nom * __builtin_amdgcn_rcpf(den) : 0.0f;
 }
-// min over the 32 lanes of a half-wave
+// min over the 32 lanes of a half-wave (S16: as half_sum)
+template <bool S16 = false>
 __device__ __forceinline__ int half_min_i(int x) {
   x = min(x, dpp_i<DPP_XOR1>(x));
   x = min(x, dpp_i<DPP_XOR2>(x));
   x = min(x, dpp_i<DPP_HALF_MIRROR>(x));
   x = min(x, dpp_i<DPP_MIRROR>(x));
-  x = min(x, swz16_i(x));
+  if constexpr (S16) x = pair16_min_i(x); else x = min(x, swz16_i(x));
   return x;
 }
+// (signed floats: fmaxf can see -0 against +0, where the operand order decides the sign -- this one stays on ds_swizzle)
 __device__ __forceinline__ float half_max(float x) {
   x = fmaxf(x, dpp_f<DPP_XOR1>(x));
   x = fmaxf(x, dpp_f<DPP_XOR2>(x));
@@ -392,12 +440,13 @@ __device__ __forceinline__ float half_max(float x) {
 // cost three instructions per step (fmaxf has to quiet signalling NaNs: v_mov_dpp + v_max(x, x) + v_max), so the maxima of
 // NON-NEGATIVE floats -- clipped correlation planes -- are taken on their bit patterns, which order like the values (a NaN
 // ranks above every finite value and survives, as with fmaxf of a quiet NaN in every lane)
+template <bool S16 = false>
 __device__ __forceinline__ int half_max_i(int x) {
   x = max(x, dpp_i<DPP_XOR1>(x));
   x = max(x, dpp_i<DPP_XOR2>(x));
   x = max(x, dpp_i<DPP_HALF_MIRROR>(x));
   x = max(x, dpp_i<DPP_MIRROR>(x));
-  x = max(x, swz16_i(x));
+  if constexpr (S16) x = pair16_max_i(x); else x = max(x, swz16_i(x));
   return x;
 }
 __device__ __forceinline__ int row_max_i(int x) {
@@ -559,6 +608,10 @@ int defer_fit_setting();
 // option "unpack_dpp" (LSPIV_UNPACK_DPP_OPT presets it): 1 = the per-pair 32 x 32 walking kernels exchange the un-packing's mirrored columns
 // through DPP (piv_fft_impl.h, UDPP), 0 = through ds_bpermute; same bits either way
 int unpack_dpp_setting();
+// option "lds_light" (LSPIV_LDS_LIGHT presets it): 1 = the per-pair 32 x 32 walking kernels in their shipped form of the fit and with
+// "unpack_dpp" end their 32-lane reductions in v_permlane16_swap and set the un-packing's lane mask once per group of values
+// (piv_fft_impl.h, LITE), 0 = ds_swizzle and a mask per two values; same bits either way.  Ignored with unpack_dpp = 0 or defer_fit = 0
+int lds_light_setting();
 // Segments of the time-walking kernels.  A job walks one window through a run of consecutive frame pairs and shares
 // every frame's spectrum between the two pairs it belongs to; which frames share transforms depends on where a run
 // starts, so the runs ("segments") are ANCHORED: they start at the absolute pair indices k * kWalkAnchor of the caller's
@@ -669,6 +722,8 @@ hipError_t launch_scale_velocity(float* f, int64_t T, int64_t n, float res_x, fl
 // test hook: `count` independent length-n register FFTs (fft_debug.hip); interleaved re/im, n = 8, 16, 32, 64 or a prime-factor length
 hipError_t launch_fft_debug(int n, bool inverse, const float* in, float* out, int count, hipStream_t s);
 hipError_t launch_fft_debug_form(int n, int form, bool inverse, const float* in, float* out, int count, hipStream_t s);
+// test hook (fft_debug.hip): `count` waves of 64 values through a 32-lane reduction, form 0 = ds_swizzle, 1 = v_permlane16_swap, 2 / 3 = paired
+hipError_t launch_half_reduce_debug(int op, int form, const uint32_t* in, uint32_t* out, int count, hipStream_t s);
 // synthetic particle-image stack (bench / test utility)
 hipError_t launch_synth_particles(uint8_t* d_frames, int64_t T, int H, int W, uint64_t seed, float density,
                                   hipStream_t s);

@@ -55,4 +55,50 @@ hipError_t launch_fft_debug_form(int n, int form, bool inverse, const float* in,
   }
 }
 
+// Test hook: the 32-lane reductions of common.h on whole waves, one wave of 64 lanes per block.  OP 0 = half_sum (float bits), 1 =
+// half_sum_i, 2 = half_min_i, 3 = half_max_i; FORM 0 = the ds_swizzle form, 1 = the v_permlane16_swap form, 2 / 3 = the paired form
+// (half_reduce2_i, integers only) on x = the lane's value and y = the value of the same lane of the wave's OTHER half: 2 stores the
+// result for x, 3 the one for y -- which is what the other half's lanes get for their x
+template <int OP, int FORM>
+__global__ __launch_bounds__(64) void half_reduce_debug_kernel(const uint32_t* in, uint32_t* out) {
+  const size_t t = (size_t)blockIdx.x * 64 + threadIdx.x;   // the grid is `count` blocks of 64 lanes over count * 64 values
+  const uint32_t x = in[t];
+  uint32_t r;
+  if constexpr (FORM >= 2) {
+    static_assert(OP >= 1 && OP <= 3, "the paired form is for integers");
+    int a = (int)x, b = (int)in[t ^ 32];
+    half_reduce2_i<OP == 1 ? RedOp::kSum : OP == 2 ? RedOp::kMin : RedOp::kMax>(a, b);
+    r = (uint32_t)(FORM == 2 ? a : b);
+  } else {
+    constexpr bool S16 = FORM == 1;
+    if constexpr (OP == 0) r = __builtin_bit_cast(uint32_t, half_sum<S16>(__builtin_bit_cast(float, x)));
+    else if constexpr (OP == 1) r = (uint32_t)half_sum_i<S16>((int)x);
+    else if constexpr (OP == 2) r = (uint32_t)half_min_i<S16>((int)x);
+    else r = (uint32_t)half_max_i<S16>((int)x);
+  }
+  out[t] = r;
+}
+template <int OP>
+static hipError_t launch_half_reduce(int form, const uint32_t* in, uint32_t* out, int count, hipStream_t s) {
+  if (form == 0) hipLaunchKernelGGL((half_reduce_debug_kernel<OP, 0>), dim3(count), dim3(64), 0, s, in, out);
+  else if (form == 1) hipLaunchKernelGGL((half_reduce_debug_kernel<OP, 1>), dim3(count), dim3(64), 0, s, in, out);
+  else if constexpr (OP >= 1) {
+    if (form == 2) hipLaunchKernelGGL((half_reduce_debug_kernel<OP, 2>), dim3(count), dim3(64), 0, s, in, out);
+    else hipLaunchKernelGGL((half_reduce_debug_kernel<OP, 3>), dim3(count), dim3(64), 0, s, in, out);
+  } else {
+    return hipErrorInvalidValue;
+  }
+  return hipGetLastError();
+}
+hipError_t launch_half_reduce_debug(int op, int form, const uint32_t* in, uint32_t* out, int count, hipStream_t s) {
+  if (form < 0 || form > 3) return hipErrorInvalidValue;
+  switch (op) {
+    case 0: return launch_half_reduce<0>(form, in, out, count, s);
+    case 1: return launch_half_reduce<1>(form, in, out, count, s);
+    case 2: return launch_half_reduce<2>(form, in, out, count, s);
+    case 3: return launch_half_reduce<3>(form, in, out, count, s);
+    default: return hipErrorInvalidValue;
+  }
+}
+
 }  // namespace lspiv

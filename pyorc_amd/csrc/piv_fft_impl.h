@@ -95,10 +95,15 @@ __device__ __forceinline__ float bperm_f(int addr, float v) {
 }
 
 // ---- reductions over the N lanes of a group ----------------------------------------------------
-template <int N> __device__ __forceinline__ float group_sum(float x) { return Geo<N>::LG == 16 ? row_sum(x) : Geo<N>::LG == 32 ? half_sum(x) : wave_sum(x); }
-template <int N> __device__ __forceinline__ int group_sum_i(int x) {
+// S16 (32-lane groups): the step across the two 16-lane rows through v_permlane16_swap instead of ds_swizzle (common.h, permlane16_swap)
+template <int N, bool S16 = false> __device__ __forceinline__ float group_sum(float x) {
+  static_assert(!S16 || Geo<N>::LG == 32, "the pair16 forms are adopted for groups of 32 lanes");
+  return Geo<N>::LG == 16 ? row_sum(x) : Geo<N>::LG == 32 ? half_sum<S16>(x) : wave_sum(x);
+}
+template <int N, bool S16 = false> __device__ __forceinline__ int group_sum_i(int x) {
+  static_assert(!S16 || Geo<N>::LG == 32, "the pair16 forms are adopted for groups of 32 lanes");
   if (Geo<N>::LG == 16) return row_sum_i(x);
-  x = half_sum_i(x);
+  x = half_sum_i<S16>(x);
   if (Geo<N>::LG == 64) x = cross_half_sum_i(x);
   return x;
 }
@@ -109,10 +114,11 @@ template <int N> __device__ __forceinline__ float group_max(float x) {
   return x;
 }
 // maximum of NON-NEGATIVE floats (clipped planes) over the group, on the bit patterns (common.h, half_max_i)
-template <int N> __device__ __forceinline__ float group_max_nonneg(float x) {
+template <int N, bool S16 = false> __device__ __forceinline__ float group_max_nonneg(float x) {
+  static_assert(!S16 || Geo<N>::LG == 32, "the pair16 forms are adopted for groups of 32 lanes");
   int b = __builtin_bit_cast(int, x);
   if (Geo<N>::LG == 16) return __builtin_bit_cast(float, row_max_i(b));
-  b = half_max_i(b);
+  b = half_max_i<S16>(b);
   if (Geo<N>::LG == 64) b = cross_half_max_i(b);
   return __builtin_bit_cast(float, b);
 }
@@ -123,9 +129,10 @@ template <int N> __device__ __forceinline__ bool group_any(bool cond) {
   else if constexpr (Geo<N>::LG == 32) return ((threadIdx.x & 32u) ? (uint32_t)(m >> 32) : (uint32_t)m) != 0u;
   else return ((m >> (threadIdx.x & 48u)) & 0xffffull) != 0ull;
 }
-template <int N> __device__ __forceinline__ int group_min_i(int x) {
+template <int N, bool S16 = false> __device__ __forceinline__ int group_min_i(int x) {
+  static_assert(!S16 || Geo<N>::LG == 32, "the pair16 forms are adopted for groups of 32 lanes");
   if (Geo<N>::LG == 16) return row_min_i(x);
-  x = half_min_i(x);
+  x = half_min_i<S16>(x);
   if (Geo<N>::LG == 64) x = cross_half_min_i(x);
   return x;
 }
@@ -217,7 +224,7 @@ struct RowStats {
 // ffpiv normalize_intensity (A3): (a - mean)/std (0 if std == 0), clipped to >= 0.
 // uint8: sum and sum of squares are exact integers (v_dot4_u32_u8 on the packed bytes), variance from
 // n sum(x^2) - (sum x)^2 in 64 bits -- no per-sample arithmetic besides convert / fma / clip.
-template <int N>
+template <int N, bool S16 = false>
 __device__ __forceinline__ RowStats stats_u8(const RowRaw<uint8_t, N>& raw, bool want_nz, int& nonzero) {
   constexpr int NN = Geo<N>::NN;
   uint32_t s = 0, q = 0;
@@ -233,10 +240,17 @@ __device__ __forceinline__ RowStats stats_u8(const RowRaw<uint8_t, N>& raw, bool
       const uint32_t t = ~(((raw.w[k] & 0x7F7F7F7Fu) + 0x7F7F7F7Fu) | raw.w[k] | 0x7F7F7F7Fu);
       nz += 4 - __builtin_popcount(t);
     }
-    nonzero = group_sum_i<N>(nz);
+    nonzero = group_sum_i<N, S16>(nz);
   }
-  const uint32_t S = (uint32_t)group_sum_i<N>((int)s);  // <= 255 N^2
-  const uint32_t Q = (uint32_t)group_sum_i<N>((int)q);  // <= 255^2 N^2 < 2^31 for N <= 64
+  int si = (int)s, qi = (int)q;
+  if constexpr (S16) {
+    half_reduce2_i<RedOp::kSum>(si, qi);   // both sums in one chain (common.h): integers, the same bits
+  } else {
+    si = group_sum_i<N>(si);
+    qi = group_sum_i<N>(qi);
+  }
+  const uint32_t S = (uint32_t)si;  // <= 255 N^2
+  const uint32_t Q = (uint32_t)qi;  // <= 255^2 N^2 < 2^31 for N <= 64
   RowStats st;
   st.mean = (float)S * (1.0f / NN);                      // exact
   const uint64_t n2var = (uint64_t)Q * NN - (uint64_t)S * (uint64_t)S;
@@ -268,7 +282,7 @@ __device__ __forceinline__ void center_u8(const RowRaw<uint8_t, N>& raw, float m
 }
 
 // float rows: pairwise sum (a constant window gives its value, hence zero variance, exactly)
-template <int N, bool DEFER_CLIP = false>
+template <int N, bool DEFER_CLIP = false, bool S16 = false>
 __device__ __forceinline__ float center_clip_f(float (&x)[N], bool want_nz, bool nz_pos, int& nonzero, bool& finite) {
   constexpr float inv_nn = 1.0f / Geo<N>::NN;
   const bool active = lane_active<N>(group_lane<N>());   // constant true for the power-of-two sizes
@@ -276,14 +290,14 @@ __device__ __forceinline__ float center_clip_f(float (&x)[N], bool want_nz, bool
     int c = 0;
 #pragma unroll
     for (int k = 0; k < N; ++k) c += (nz_pos ? x[k] > 0.0f : x[k] != 0.0f) ? 1 : 0;   // "non-zero" | "above zero" (A7)
-    nonzero = group_sum_i<N>(active ? c : 0);
+    nonzero = group_sum_i<N, S16>(active ? c : 0);
   }
   if constexpr (!Geo<N>::POW2) {   // N^2 is no power of two: shifted mean, so a constant window has exactly zero variance
     const float x0 = bperm_f(lane0_byte_of<N>(), x[0]);
 #pragma unroll
     for (int k = 0; k < N; ++k) x[k] -= x0;
   }
-  const float s = group_sum<N>(active ? tree_sum<N>(x) : 0.0f);
+  const float s = group_sum<N, S16>(active ? tree_sum<N>(x) : 0.0f);
   const float mean = s * inv_nn;
   float acc[4] = {0.0f, 0.0f, 0.0f, 0.0f};
 #pragma unroll
@@ -292,7 +306,7 @@ __device__ __forceinline__ float center_clip_f(float (&x)[N], bool want_nz, bool
     acc[k & 3] = fmaf(d, d, acc[k & 3]);
     x[k] = DEFER_CLIP ? d : fmaxf(d, 0.0f);   // DEFER_CLIP: the caller clips while it scales (prepare_one)
   }
-  const float ssq = group_sum<N>(active ? (acc[0] + acc[1]) + (acc[2] + acc[3]) : 0.0f);
+  const float ssq = group_sum<N, S16>(active ? (acc[0] + acc[1]) + (acc[2] + acc[3]) : 0.0f);
   finite = finite && (fabsf(s) <= 3.0e38f) && (ssq <= 3.0e38f);
   const float var = ssq * inv_nn;
   return var > 0.0f ? __builtin_amdgcn_rsqf(var) : 0.0f;
@@ -306,13 +320,13 @@ __device__ __forceinline__ void load_row_f32(const float* p, float (&x)[N]) {
   }
   if constexpr (N % 4 == 2) { x[N - 2] = p[N - 2]; x[N - 1] = p[N - 1]; }
 }
-template <int N, bool DEFER_CLIP = false>
+template <int N, bool DEFER_CLIP = false, bool S16 = false>
 __device__ __forceinline__ float load_center(const RowRaw<float, N>& raw, float (&x)[N], bool want_nz, bool nz_pos,
                                              int& nonzero, bool& finite) {
   load_row_f32<N>(raw.p, x);
-  return center_clip_f<N, DEFER_CLIP>(x, want_nz, nz_pos, nonzero, finite);
+  return center_clip_f<N, DEFER_CLIP, S16>(x, want_nz, nz_pos, nonzero, finite);
 }
-template <int N, bool DEFER_CLIP = false>
+template <int N, bool DEFER_CLIP = false, bool S16 = false>
 __device__ __forceinline__ float load_center(const RowRaw<double, N>& raw, float (&x)[N], bool want_nz, bool nz_pos,
                                              int& nonzero, bool& finite) {
 #pragma unroll
@@ -320,7 +334,7 @@ __device__ __forceinline__ float load_center(const RowRaw<double, N>& raw, float
     const f64x2 v = *reinterpret_cast<const f64x2_u*>(raw.p + 2 * k);
     x[2 * k + 0] = (float)v[0]; x[2 * k + 1] = (float)v[1];
   }
-  return center_clip_f<N, DEFER_CLIP>(x, want_nz, nz_pos, nonzero, finite);
+  return center_clip_f<N, DEFER_CLIP, S16>(x, want_nz, nz_pos, nonzero, finite);
 }
 
 // Both windows of a pair -> xr = a'' (mean-offset, zero-clipped), xi = rho b''.
@@ -789,6 +803,77 @@ __device__ __forceinline__ void mirror_dpp2(uint64_t self_mask, float a, float b
       : "v"(a), "v"(b), "s"(self_mask)
       : "vcc");
 }
+// The same exchange for a GROUP of values behind ONE s_mov_b64 vcc + s_nop (mirror_dpp2 pays them for every two values: 32 statements
+// per iteration, and an s_nop 0 is four cycles of the wave's own issue stream).  IN PLACE: every lane reads its quad neighbour's
+// register before any lane writes, and the un-packing never reads a lane's OWN copy of the registers it exchanges -- rows 17 .. 31
+// are read only as the mirrored lane's operand of step N - ky, and the outgoing ar + bi, ai - br of a step only by the inverse
+// transform (walk_iteration, UG) -- so a group needs no transient register.
+#define LSPIV_DPP_IP(k) "v_cndmask_b32_dpp %" #k ", %" #k ", %" #k ", vcc quad_perm:[1,0,3,2] row_mask:0xf bank_mask:0xf\n\t"
+__device__ __forceinline__ void mirror_dpp_ip2(uint64_t self_mask, float& a, float& b) {
+  asm("s_mov_b64 vcc, %2\n\t"
+      "s_nop 0\n\t" LSPIV_DPP_IP(0) LSPIV_DPP_IP(1)
+      : "+v"(a), "+v"(b)
+      : "s"(self_mask)
+      : "vcc");
+}
+__device__ __forceinline__ void mirror_dpp_ip4(uint64_t self_mask, float& a, float& b, float& c, float& d) {
+  asm("s_mov_b64 vcc, %4\n\t"
+      "s_nop 0\n\t" LSPIV_DPP_IP(0) LSPIV_DPP_IP(1) LSPIV_DPP_IP(2) LSPIV_DPP_IP(3)
+      : "+v"(a), "+v"(b), "+v"(c), "+v"(d)
+      : "s"(self_mask)
+      : "vcc");
+}
+__device__ __forceinline__ void mirror_dpp_ip8(uint64_t self_mask, float& x0, float& x1, float& x2, float& x3, float& y0, float& y1, float& y2, float& y3) {
+  asm("s_mov_b64 vcc, %8\n\t"
+      "s_nop 0\n\t" LSPIV_DPP_IP(0) LSPIV_DPP_IP(1) LSPIV_DPP_IP(2) LSPIV_DPP_IP(3) LSPIV_DPP_IP(4) LSPIV_DPP_IP(5) LSPIV_DPP_IP(6) LSPIV_DPP_IP(7)
+      : "+v"(x0), "+v"(x1), "+v"(x2), "+v"(x3), "+v"(y0), "+v"(y1), "+v"(y2), "+v"(y3)
+      : "s"(self_mask)
+      : "vcc");
+}
+__device__ __forceinline__ void mirror_dpp_ip16(uint64_t self_mask, float& x0, float& x1, float& x2, float& x3, float& x4, float& x5, float& x6, float& x7,
+                                                float& y0, float& y1, float& y2, float& y3, float& y4, float& y5, float& y6, float& y7) {
+  asm("s_mov_b64 vcc, %16\n\t"
+      "s_nop 0\n\t" LSPIV_DPP_IP(0) LSPIV_DPP_IP(1) LSPIV_DPP_IP(2) LSPIV_DPP_IP(3) LSPIV_DPP_IP(4) LSPIV_DPP_IP(5) LSPIV_DPP_IP(6) LSPIV_DPP_IP(7)
+      LSPIV_DPP_IP(8) LSPIV_DPP_IP(9) LSPIV_DPP_IP(10) LSPIV_DPP_IP(11) LSPIV_DPP_IP(12) LSPIV_DPP_IP(13) LSPIV_DPP_IP(14) LSPIV_DPP_IP(15)
+      : "+v"(x0), "+v"(x1), "+v"(x2), "+v"(x3), "+v"(x4), "+v"(x5), "+v"(x6), "+v"(x7), "+v"(y0), "+v"(y1), "+v"(y2), "+v"(y3), "+v"(y4), "+v"(y5),
+        "+v"(y6), "+v"(y7)
+      : "s"(self_mask)
+      : "vcc");
+}
+#undef LSPIV_DPP_IP
+// four values into registers of their own (the steps ky = 0 and N / 2 read both a row and its mirrored copy)
+__device__ __forceinline__ void mirror_dpp4(uint64_t self_mask, float a, float b, float c, float d, float& ma, float& mb, float& mc, float& md) {
+  asm("s_mov_b64 vcc, %8\n\t"
+      "s_nop 0\n\t"
+      "v_cndmask_b32_dpp %0, %4, %4, vcc quad_perm:[1,0,3,2] row_mask:0xf bank_mask:0xf\n\t"
+      "v_cndmask_b32_dpp %1, %5, %5, vcc quad_perm:[1,0,3,2] row_mask:0xf bank_mask:0xf\n\t"
+      "v_cndmask_b32_dpp %2, %6, %6, vcc quad_perm:[1,0,3,2] row_mask:0xf bank_mask:0xf\n\t"
+      "v_cndmask_b32_dpp %3, %7, %7, vcc quad_perm:[1,0,3,2] row_mask:0xf bank_mask:0xf"
+      : "=&v"(ma), "=&v"(mb), "=&v"(mc), "=v"(md)
+      : "v"(a), "v"(b), "v"(c), "v"(d), "s"(self_mask)
+      : "vcc");
+}
+// rows [r0, r0 + n) of x and of y exchanged in place, at most UG values (UG / 2 rows of each) behind one mask set; r0, n: compile-time
+// after unrolling
+template <int N, int UG>
+__device__ __forceinline__ void mirror_rows_ip(uint64_t self_mask, float (&x)[N], float (&y)[N], int r0, int n) {
+  static_assert(UG == 4 || UG == 8 || UG == 16, "values per mask set");
+  int r = r0;
+  if constexpr (UG >= 16) {
+#pragma unroll
+    for (; r + 8 <= r0 + n; r += 8)
+      mirror_dpp_ip16(self_mask, x[r], x[r + 1], x[r + 2], x[r + 3], x[r + 4], x[r + 5], x[r + 6], x[r + 7], y[r], y[r + 1], y[r + 2], y[r + 3], y[r + 4],
+                      y[r + 5], y[r + 6], y[r + 7]);
+  }
+  if constexpr (UG >= 8) {
+#pragma unroll
+    for (; r + 4 <= r0 + n; r += 4) mirror_dpp_ip8(self_mask, x[r], x[r + 1], x[r + 2], x[r + 3], y[r], y[r + 1], y[r + 2], y[r + 3]);
+  }
+#pragma unroll
+  for (; r + 2 <= r0 + n; r += 2) mirror_dpp_ip4(self_mask, x[r], x[r + 1], y[r], y[r + 1]);
+#pragma unroll
+  for (; r < r0 + n; ++r) mirror_dpp_ip2(self_mask, x[r], y[r]);
+}
 
 template <int N, bool HALF = false, ColMap MAP = ColMap::kNatural>
 __device__ __forceinline__ void transpose2(float* buf, int lg, float (&xr)[N], float (&xi)[N]) {
@@ -984,7 +1069,7 @@ __device__ __forceinline__ void correlate_job(const PivParams& p, const TileRef 
 
 // Row maximum of a plane held as lane = y, reg = x (v_max3 tree) reduced over the group -> plane maximum.
 template <int N>
-__device__ __forceinline__ float plane_max(const float (&c)[N], float& row_max) {
+__device__ __forceinline__ float plane_row_max(const float (&c)[N]) {
   // v_max3 tree from the first level on: N values -> ceil(N / 3) -> ... (32 values: 11 + 4 + 2 instructions)
   float m[N];
 #pragma unroll
@@ -998,8 +1083,30 @@ __device__ __forceinline__ float plane_max(const float (&c)[N], float& row_max) 
     if (rem == 2) m[t] = fmaxf(m[t], m[3 * t + 1]);
     w = t + (rem ? 1 : 0);
   }
-  row_max = m[0];
-  return group_max_nonneg<N>(row_max);   // the planes are clipped to [0, 1]
+  return m[0];
+}
+template <int N, bool S16 = false>
+__device__ __forceinline__ float plane_max(const float (&c)[N], float& row_max) {
+  row_max = plane_row_max<N>(c);
+  return group_max_nonneg<N, S16>(row_max);   // the planes are clipped to [0, 1]
+}
+// S16: the maxima and the peak rows of BOTH planes of an iteration, each pair in one reduction chain (common.h, half_reduce2_i) -- the
+// maxima on the bit patterns of the clipped planes (group_max_nonneg), the rows as in peak_row
+template <int N>
+__device__ __forceinline__ void plane_max_row2(int lg, const float (&ca)[N], const float (&cb)[N], float& row_max_a, float& row_max_b, float& vmax_a,
+                                               float& vmax_b, int& ip_a, int& ip_b) {
+  static_assert(Geo<N>::LG == 32 && Geo<N>::FULL, "two planes per half-wave");
+  constexpr int C = N / 2, NONE = 1 << 12;
+  row_max_a = plane_row_max<N>(ca);
+  row_max_b = plane_row_max<N>(cb);
+  int ma = __builtin_bit_cast(int, row_max_a), mb = __builtin_bit_cast(int, row_max_b);
+  half_reduce2_i<RedOp::kMax>(ma, mb);
+  vmax_a = __builtin_bit_cast(float, ma);
+  vmax_b = __builtin_bit_cast(float, mb);
+  const int sh = wrap_n<N>(lg + C);
+  ip_a = row_max_a == vmax_a ? sh : NONE;
+  ip_b = row_max_b == vmax_b ? sh : NONE;
+  half_reduce2_i<RedOp::kMin>(ip_a, ip_b);
 }
 
 // Peak of one plane: parks the plane in LDS (row y at buf[y * LDS_ROW + x]), finds np.argmax of the
@@ -1013,13 +1120,13 @@ __device__ __forceinline__ float plane_max(const float (&c)[N], float& row_max) 
 // NODES (deformation pass): u, v are a residual against the window's node p.nodes[g]; the flag's tolerance is relative to the FULL
 // displacement node / 128 + residual, the value the pass hands out (a residual of a few hundredths of a pixel would otherwise flag
 // most windows for an accuracy nobody asks of the sum)
-template <int N>
+template <int N, bool S16 = false>
 __device__ __forceinline__ int peak_row(int lg, float vmax, float row_max) {
   constexpr int C = N / 2, NONE = 1 << 12;
   const int sh = wrap_n<N>(row_of<N>(lg) + C);
-  return group_min_i<N>((lane_active<N>(lg) && row_max == vmax) ? sh : NONE);
+  return group_min_i<N, S16>((lane_active<N>(lg) && row_max == vmax) ? sh : NONE);
 }
-template <int N, bool NODES = false>
+template <int N, bool NODES = false, bool S16 = false>
 __device__ __forceinline__ void find_peak(float* buf, int lg, const float (&c)[N], float vmax, float row_max, const PivParams& p,
                                           float& u, float& v, bool note, uint32_t g, int ip_known = -1) {
   const int border_mode = p.border_mode;
@@ -1031,10 +1138,10 @@ __device__ __forceinline__ void find_peak(float* buf, int lg, const float (&c)[N
   if (active) lds_row_write<N>(buf + lg * LR, c);
   __builtin_amdgcn_wave_barrier();
   const int sh = wrap_n<N>(lr + C);                                                  // this lane's shifted row AND column
-  ip = ip_known >= 0 ? ip_known : peak_row<N>(lg, vmax, row_max);                    // first shifted row with the maximum
+  ip = ip_known >= 0 ? ip_known : peak_row<N, S16>(lg, vmax, row_max);               // first shifted row with the maximum
   const int y = wrap_n<N>(ip + C);
   const float rowv = buf[y * LR + lr];                                               // the peak row, one sample per lane
-  jp = group_min_i<N>((active && rowv == vmax) ? sh : NONE);                         // first shifted column in that row
+  jp = group_min_i<N, S16>((active && rowv == vmax) ? sh : NONE);                    // first shifted column in that row
   // is any sample other than (ip, jp) within tau of the maximum?  The other rows through their maxima, the rest of the peak
   // row through this lane's sample of it
   const float thr = vmax * (1.0f - p.rescue_tau);
@@ -1074,8 +1181,8 @@ __device__ __forceinline__ void find_peak(float* buf, int lg, const float (&c)[N
         cnt += cand ? 1 : 0;
         other = (cand && pos != pos1) ? min(other, pos) : other;
       }
-      cnt = group_sum_i<N>(cnt);
-      other = group_min_i<N>(other);
+      cnt = group_sum_i<N, S16>(cnt);
+      other = group_min_i<N, S16>(other);
       if (cnt == 2) pos2 = (uint32_t)other;
     }
     if (lg == 0 && (pc.amb || pc.fit))
@@ -1301,7 +1408,7 @@ __global__ __launch_bounds__(BLOCK, (kWavesPerSimd<T, N>)) void piv_fft_kernel(P
 // have enough jobs; a segment's first iteration has no F_prev and yields one plane.  Which frame a window shares its
 // transforms with depends on where the segment starts, so results are bit-reproducible for a given chunk but differ
 // in the last float32 bit between different chunkings (the per-pair kernel does not; LSPIV_WALK=0 selects it).
-template <typename T, int N, bool WANT_NZ>
+template <typename T, int N, bool WANT_NZ, bool S16 = false>
 __device__ __forceinline__ void prepare_one(const RowRaw<T, N>& raw, float (&x)[N], bool nz_pos, float std_gain, int& nonzero,
                                             bool& finite, bool& dead) {
   // every frame carries 1 / (2 N^2) on top of 1 / std, so each cross spectrum (a product of two frames' spectra)
@@ -1309,12 +1416,12 @@ __device__ __forceinline__ void prepare_one(const RowRaw<T, N>& raw, float (&x)[
   // N = 8 ... 64, i.e. the same bits as scaling the product
   const float kHalf = std_gain * (1.0f / (2.0f * (float)Geo<N>::NN));   // std_gain: 1, or sqrt((n - 1) / n) under the "std_ddof" option
   if constexpr (sizeof(T) == 1) {
-    const RowStats st = stats_u8<N>(raw, WANT_NZ, nonzero);
+    const RowStats st = stats_u8<N, S16>(raw, WANT_NZ, nonzero);
     center_u8<N, true>(raw, st.mean, st.inv_std * kHalf, x);   // max((byte - mean) / std, 0) / (2 N^2) < 1; all zero for a constant window
     dead = st.inv_std == 0.0f;
   } else {
     // max(d, 0) * g == max(d * g, 0) exactly (g >= 0), and d * g < 1 (see center_u8): the clip rides on the multiply
-    const float inv = load_center<N, true>(raw, x, WANT_NZ, nz_pos, nonzero, finite);
+    const float inv = load_center<N, true, S16>(raw, x, WANT_NZ, nz_pos, nonzero, finite);
     const float g = inv * kHalf;
 #pragma unroll
     for (int j = 0; j < N; ++j) x[j] = __builtin_amdgcn_fmed3f(x[j] * g, 0.0f, 1.0f);
@@ -1676,7 +1783,8 @@ struct WalkCarry {
 // One ky of the un-packing: mr / mi = registers N - ky of the mirrored lane's xr / xi.  Both cross spectra of the step, packed for
 // the shared inverse; the carry moves on.
 // UDPP: the mirrored lane is the quad neighbour (unpack_col), self_mask = the lanes that mirror onto themselves
-template <int N, bool UDPP = false>
+// RAW_OUT (UDPP in groups): rows N - ky get the step's own ar + bi, ai - br; the caller exchanges them a group at a time and negates xi
+template <int N, bool UDPP = false, bool RAW_OUT = false>
 __device__ __forceinline__ void unpack_step(int ky, float mr, float mi, int partner_byte, WalkCarry<N>& c, float (&xr)[N], float (&xi)[N], uint64_t self_mask = 0) {
   constexpr int H = N / 2;
   const int kn = (N - ky) % N;
@@ -1690,7 +1798,10 @@ __device__ __forceinline__ void unpack_step(int ky, float mr, float mi, int part
   xr[ky] = ar - bi;                // (R_a + i R_b)[ky][kx]
   xi[ky] = ai + br;
   if (ky >= 1 && ky < H) {         // rows above N/2: conj of (R_a - i R_b) at the mirrored lane
-    if constexpr (UDPP) {
+    if constexpr (RAW_OUT) {
+      xr[kn] = ar + bi;
+      xi[kn] = ai - br;
+    } else if constexpr (UDPP) {
       float er, ei;
       mirror_dpp2(self_mask, ar + bi, ai - br, er, ei);
       xr[kn] = er;
@@ -1707,8 +1818,10 @@ __device__ __forceinline__ void unpack_step(int ky, float mr, float mi, int part
 // RELAX: without the scheduling barriers between the phases (a caller with registers to spare: the 32 x 32 ensemble kernel runs two
 // waves per SIMD for its register accumulator and may use 256 VGPRs)
 // UDPP: between the transposes the columns sit in the lanes of unpack_col, and the un-packing exchanges through DPP (kWalkUnpackDpp)
+// S16: the 32-lane reductions of the conversion end in v_permlane16_swap (kWalkSwap16); UG > 2 (with UDPP): UG exchanged values per mask
+// set, in place (kWalkUnpackGroup, mirror_rows_ip)
 template <typename T, int N, bool WANT_NZ, bool RELAX = false, bool HALF_TILE = false, int UB = 1, bool U8_EARLY = false, bool FOLD = kFftFoldLen<N>, bool SR = kFftSrLen<N>,
-          bool UDPP = false>
+          bool UDPP = false, bool S16 = false, int UG = 2>
 __device__ __forceinline__ void walk_iteration(const PivParams& p, const T* row, bool has2, float* buf, int lg,
                                                int partner_byte, int lane0_byte, WalkCarry<N>& c, float (&xr)[N],
                                                float (&xi)[N], float& mean_a, float& mean_b, bool& skip_a, bool& skip_b,
@@ -1726,13 +1839,13 @@ __device__ __forceinline__ void walk_iteration(const PivParams& p, const T* row,
     const float* r1 = has2 ? r0 + p.frame_elems : r0;
     load_row_f32<N>(r0, xr);
     load_row_f32<N>(r1, xi);
-    const float inv0 = center_clip_f<N, true>(xr, WANT_NZ, p.nz_positive != 0, nz0, fin0);
+    const float inv0 = center_clip_f<N, true, S16>(xr, WANT_NZ, p.nz_positive != 0, nz0, fin0);
     const float g0 = inv0 * kHalf;
 #pragma unroll
     for (int j = 0; j < N; ++j) xr[j] = __builtin_amdgcn_fmed3f(xr[j] * g0, 0.0f, 1.0f);
     dead0 = inv0 == 0.0f;
     LSPIV_WALK_SB;
-    const float inv1 = center_clip_f<N, true>(xi, WANT_NZ, p.nz_positive != 0, nz1, fin1);
+    const float inv1 = center_clip_f<N, true, S16>(xi, WANT_NZ, p.nz_positive != 0, nz1, fin1);
     const float g1 = inv1 * kHalf;
 #pragma unroll
     for (int j = 0; j < N; ++j) xi[j] = __builtin_amdgcn_fmed3f(xi[j] * g1, 0.0f, 1.0f);
@@ -1752,9 +1865,9 @@ __device__ __forceinline__ void walk_iteration(const PivParams& p, const T* row,
       raw0.fetch(row);
       raw1.fetch(has2 ? row + p.frame_elems : row);
     }
-    prepare_one<T, N, WANT_NZ>(raw0, xr, p.nz_positive != 0, p.std_gain, nz0, fin0, dead0);
+    prepare_one<T, N, WANT_NZ, S16>(raw0, xr, p.nz_positive != 0, p.std_gain, nz0, fin0, dead0);
     LSPIV_WALK_SB;
-    prepare_one<T, N, WANT_NZ>(raw1, xi, p.nz_positive != 0, p.std_gain, nz1, fin1, dead1);
+    prepare_one<T, N, WANT_NZ, S16>(raw1, xi, p.nz_positive != 0, p.std_gain, nz1, fin1, dead1);
   }
   if constexpr (kEnsLdsRmw<N>) {
     if (one_job_per_wave_ens) {   // (compile-time false in the per-timestep kernel)
@@ -1777,7 +1890,28 @@ __device__ __forceinline__ void walk_iteration(const PivParams& p, const T* row,
   LSPIV_SETPRIO(LSPIV_PRIO_U);
   // un-pack the two spectra, form both cross spectra and pack them for the shared inverse, one ky at a time (a
   // step only touches registers ky and N - ky of this lane and of the mirrored lane, so it can run in place)
-  if constexpr (UDPP) {
+  if constexpr (UDPP && UG > 2) {
+    // as below, UG values per mask set: the steps ky = 0 and N / 2 read a row and its mirrored copy (four values into registers of
+    // their own, up front: no step before ky = N / 2 writes row N / 2); a group of steps 1 .. N / 2 - 1 has its rows N - ky exchanged in
+    // place, runs in ascending ky as ever, leaves ar + bi, ai - br in those rows and has them exchanged in place again
+    constexpr uint64_t self_mask = 0x0000000300000003ull;
+    constexpr int S = UG / 2;
+    float m0r, m0i, mhr, mhi;
+    mirror_dpp4(self_mask, xr[0], xi[0], xr[H], xi[H], m0r, m0i, mhr, mhi);
+    unpack_step<N, true, true>(0, m0r, m0i, partner_byte, c, xr, xi, self_mask);
+#pragma unroll
+    for (int k0 = 1; k0 < H; k0 += S) {
+      const int n = k0 + S <= H ? S : H - k0, r0 = N - k0 - n + 1;   // steps k0 .. k0 + n - 1, rows N - ky = r0 .. r0 + n - 1
+      mirror_rows_ip<N, UG>(self_mask, xr, xi, r0, n);
+#pragma unroll
+      for (int b = 0; b < n; ++b) unpack_step<N, true, true>(k0 + b, xr[N - k0 - b], xi[N - k0 - b], partner_byte, c, xr, xi, self_mask);
+      mirror_rows_ip<N, UG>(self_mask, xr, xi, r0, n);
+#pragma unroll
+      for (int b = 0; b < n; ++b) xi[r0 + b] = -xi[r0 + b];
+    }
+    unpack_step<N, true, true>(H, mhr, mhi, partner_byte, c, xr, xi, self_mask);
+    __builtin_amdgcn_sched_barrier(0);
+  } else if constexpr (UDPP) {
     // the mirrored lane is the quad neighbour: no LDS instruction, no round trip to batch
     constexpr uint64_t self_mask = 0x0000000300000003ull;   // lanes 0 and 1 of both groups: columns 0 and 16
 #pragma unroll
@@ -1887,6 +2021,33 @@ constexpr bool kWalkDefer = N == 32 && (LSPIV_WALK_DEFER >= 0 ? LSPIV_WALK_DEFER
 constexpr bool kWalkUnpackDpp32[3][2][2] = {{{true, true}, {true, true}}, {{true, true}, {true, true}}, {{true, true}, {true, true}}};
 template <typename T, int N, bool PLANES, bool WANT_NZ>
 constexpr bool kWalkUnpackDpp = N == 32 && (LSPIV_UNPACK_DPP >= 0 ? LSPIV_UNPACK_DPP != 0 : kWalkUnpackDpp32[kSampleKind<T>][PLANES][WANT_NZ]);
+// "LDS-light" form of the per-pair 32 x 32 walking kernels (LITE, option "lds_light"), on top of the shipped DEFER / UDPP choices only:
+//  * kWalkSwap16: the ten 32-lane reductions of an iteration (sums and sums of squares of the two frames; plane maximum, peak row and
+//    peak column of the two planes) join their two 16-lane rows with v_permlane16_swap instead of ds_swizzle(SWAP,16) + s_waitcnt
+//    lgkmcnt(0) (common.h, permlane16_swap): no LDS instruction, no wait that also drains the plane park, same bits.  The integer ones
+//    that come in pairs -- sum and sum of squares of a uint8 frame, the two planes' maxima, the two planes' peak rows (with the batched
+//    fit) -- share one reduction chain (half_reduce2_i), which brings the VALU count back to the ds_swizzle form's.
+//    -DLSPIV_SWAP16=0 / 1 forces it.
+//  * kWalkUnpackGroup: exchanged values of the un-packing per s_mov_b64 vcc + s_nop (mirror_rows_ip); 2 = one mirror_dpp2 per two values,
+//    the former form.  -DLSPIV_UNPACK_GROUP=n forces n (2, 4, 8 or 16).
+// Per kernel by the resource rule of the un-pack batch above (tools/kres.py): no more VGPRs than the three-wave step allows, no scratch
+// byte, no wave lost; of the admissible group sizes the one with the fewest scalar instructions in the un-pack segment.
+// [sample type][PLANES][WANT_NZ].  A kernel with neither (all switches off) has no LITE instantiation.
+#ifndef LSPIV_SWAP16
+#define LSPIV_SWAP16 -1
+#endif
+#ifndef LSPIV_UNPACK_GROUP
+#define LSPIV_UNPACK_GROUP -1
+#endif
+constexpr bool kWalkSwap16_32[3][2][2] = {{{true, true}, {true, true}}, {{true, true}, {true, true}}, {{true, true}, {true, true}}};
+// (16 is admissible for all twelve and measured -0.2 ... -0.4 % on top of kWalkSwap16 with overlapping runs: not a gain, so every entry is 2)
+constexpr int kWalkUnpackGroup32[3][2][2] = {{{2, 2}, {2, 2}}, {{2, 2}, {2, 2}}, {{2, 2}, {2, 2}}};
+template <typename T, int N, bool PLANES, bool WANT_NZ>
+constexpr bool kWalkSwap16 = N == 32 && (LSPIV_SWAP16 >= 0 ? LSPIV_SWAP16 != 0 : kWalkSwap16_32[kSampleKind<T>][PLANES][WANT_NZ]);
+template <typename T, int N, bool PLANES, bool WANT_NZ>
+constexpr int kWalkUnpackGroup = N != 32 ? 2 : LSPIV_UNPACK_GROUP >= 0 ? LSPIV_UNPACK_GROUP : kWalkUnpackGroup32[kSampleKind<T>][PLANES][WANT_NZ];
+template <typename T, int N, bool PLANES, bool WANT_NZ>
+constexpr bool kWalkLite = kWalkUnpackDpp<T, N, PLANES, WANT_NZ> && (kWalkSwap16<T, N, PLANES, WANT_NZ> || kWalkUnpackGroup<T, N, PLANES, WANT_NZ> > 2);
 // The first iteration of a wave has no pair f - 1 in either group (f == p0): with LSPIV_SKIP_FIRST_A the 32 x 32 kernels leave out the
 // maximum, the search and the fit of its plane a -- nothing of it is stored, and a record slot that is not written stays invalid.
 #ifndef LSPIV_SKIP_FIRST_A
@@ -1901,7 +2062,7 @@ constexpr bool kWalkSkipFirstA = LSPIV_SKIP_FIRST_A && N == 32 && (PLANES || (si
 constexpr uint32_t kDeferNearTie = 1u << 16, kDeferDead = 1u << 17, kDeferSkip = 1u << 18, kDeferValid = 1u << 19, kDeferNote = 1u << 20;
 
 // The part of find_peak that needs the group: park, arg-max, near-tie test, the four neighbours, the "amb" cold path -- then the record.
-template <int N>
+template <int N, bool S16 = false>
 __device__ __forceinline__ void peak_search_stage(float* buf, int lg, const float (&c)[N], float vmax, float row_max, const PivParams& p, bool note,
                                                   uint32_t g, int ip_known, float mean, bool dead, bool skip, bool valid, uint32_t* rec) {
   int ip, jp;
@@ -1912,10 +2073,11 @@ __device__ __forceinline__ void peak_search_stage(float* buf, int lg, const floa
   if (active) lds_row_write<N>(buf + lg * LR, c);
   __builtin_amdgcn_wave_barrier();
   const int sh = wrap_n<N>(lr + C);
-  ip = ip_known >= 0 ? ip_known : peak_row<N>(lg, vmax, row_max);
+  if constexpr (S16) ip = ip_known;   // both planes' rows come from plane_max_row2
+  else ip = ip_known >= 0 ? ip_known : peak_row<N>(lg, vmax, row_max);
   const int y = wrap_n<N>(ip + C);
   const float rowv = buf[y * LR + lr];
-  jp = group_min_i<N>((active && rowv == vmax) ? sh : NONE);
+  jp = group_min_i<N, S16>((active && rowv == vmax) ? sh : NONE);
   const float thr = vmax * (1.0f - p.rescue_tau);
   const bool near_tie = group_any<N>(active && ((row_max >= thr && sh != ip) || (rowv >= thr && sh != jp)));
   const int x = wrap_n<N>(jp + C);
@@ -1939,8 +2101,8 @@ __device__ __forceinline__ void peak_search_stage(float* buf, int lg, const floa
         cnt += cand ? 1 : 0;
         other = (cand && pos != pos1) ? min(other, pos) : other;
       }
-      cnt = group_sum_i<N>(cnt);
-      other = group_min_i<N>(other);
+      cnt = group_sum_i<N, S16>(cnt);
+      other = group_min_i<N, S16>(other);
       if (cnt == 2) pos2 = (uint32_t)other;
       if (lg == 0 && amb) rescue_note(p.rescue_hdr, p.rescue_fit, p.rescue_cap_fit, p.rescue_amb, p.rescue_cap_amb, g, PeakCond{true, false}, ip, jp, pos2);
     }
@@ -1990,10 +2152,14 @@ __device__ __forceinline__ void defer_flush(uint32_t* stage, int lg, const PivPa
   __builtin_amdgcn_wave_barrier();
 }
 
-template <typename T, int N, bool PLANES, bool WANT_NZ, bool DEFER = false, bool UDPP = false>
+// LITE: the LDS-light form (kWalkLite); a trailing argument, so that a kernel's name still starts as it did
+template <typename T, int N, bool PLANES, bool WANT_NZ, bool DEFER = false, bool UDPP = false, bool LITE = false>
 __global__ __launch_bounds__(BLOCK, (kWalkWaves<T, N>)) void piv_fft_walk_kernel(PivParams p) {
   static_assert(!DEFER || (N == 32 && !kTwoPlaneEpilogue<N>), "the batched fit is built for two groups of 32 lanes");
   static_assert(!UDPP || N == 32, "the paired column map is built for 32 x 32");
+  static_assert(!LITE || (UDPP && N == 32), "the LDS-light form sits on top of the un-packing through DPP");
+  constexpr bool S16 = LITE && kWalkSwap16<T, N, PLANES, WANT_NZ>;
+  constexpr int UG = LITE ? kWalkUnpackGroup<T, N, PLANES, WANT_NZ> : 2;
   const uint32_t seg_len = p.seg_len, n_seg = p.n_seg;
   extern __shared__ __attribute__((aligned(16))) float smem[];
   using G = Geo<N>;
@@ -2031,7 +2197,7 @@ __global__ __launch_bounds__(BLOCK, (kWalkWaves<T, N>)) void piv_fft_walk_kernel
     const bool has2 = f + 1 <= p1;
     float xr[N], xi[N], mean_a, mean_b;
     bool skip_a, skip_b, dead_a, dead_b;
-    walk_iteration<T, N, WANT_NZ, kWalkRelax<T, N>, false, kWalkUnpackBatch<T, N, PLANES, WANT_NZ>, kWalkU8Early<N, PLANES, WANT_NZ>, kFftFoldWalk<N>, kFftSrWalk<N>, UDPP>(
+    walk_iteration<T, N, WANT_NZ, kWalkRelax<T, N>, false, kWalkUnpackBatch<T, N, PLANES, WANT_NZ>, kWalkU8Early<N, PLANES, WANT_NZ>, kFftFoldWalk<N>, kFftSrWalk<N>, UDPP, S16, UG>(
         p, row, has2, buf, lg, partner_byte, lane0_byte, carry, xr, xi, mean_a, mean_b, skip_a, skip_b, dead_a, dead_b);
     if (WANT_NZ && win_dropped) skip_a = skip_b = true;
     const bool with_a = !kWalkSkipFirstA<T, N, PLANES, WANT_NZ> || it != 0;   // wave-uniform: no group has a pair f - 1 in the wave's first iteration
@@ -2076,31 +2242,44 @@ __global__ __launch_bounds__(BLOCK, (kWalkWaves<T, N>)) void piv_fft_walk_kernel
       __builtin_amdgcn_wave_barrier();   // the parked samples are read before the next iteration's transposes reuse the tile
     } else if constexpr (DEFER) {
       // search now, fit later (defer_flush): plane b's maximum and peak row first, as below
-      float row_max_b;
-      const float vmax_b = plane_max<N>(xi, row_max_b);
-      const int ip_b = peak_row<N>(lg, vmax_b, row_max_b);
+      float row_max_b, vmax_b;
+      int ip_b;
       uint32_t* rec = stage + (it & (kDeferSlots / 2 - 1)) * 2 * kDeferRecDwords;
-      if (with_a) {
-        float row_max;
-        const uint32_t g = (f - 1) * p.n_win + win;
-        const float vmax = plane_max<N>(xr, row_max);
-        peak_search_stage<N>(buf, lg, xr, vmax, row_max, p, p.rescue_hdr && valid_a && !dead_a && !skip_a, g, -1, mean_a, dead_a, skip_a, valid_a, rec);
+      if constexpr (S16) {
+        // both planes' maxima and peak rows together; in a wave's first iteration plane a is the plane of no pair, and what comes
+        // out for it is not used
+        float row_max, vmax;
+        int ip_a;
+        plane_max_row2<N>(lg, xr, xi, row_max, row_max_b, vmax, vmax_b, ip_a, ip_b);
+        if (with_a) {
+          const uint32_t g = (f - 1) * p.n_win + win;
+          peak_search_stage<N, S16>(buf, lg, xr, vmax, row_max, p, p.rescue_hdr && valid_a && !dead_a && !skip_a, g, ip_a, mean_a, dead_a, skip_a, valid_a, rec);
+        }
+      } else {
+        vmax_b = plane_max<N>(xi, row_max_b);
+        ip_b = peak_row<N>(lg, vmax_b, row_max_b);
+        if (with_a) {
+          float row_max;
+          const uint32_t g = (f - 1) * p.n_win + win;
+          const float vmax = plane_max<N>(xr, row_max);
+          peak_search_stage<N>(buf, lg, xr, vmax, row_max, p, p.rescue_hdr && valid_a && !dead_a && !skip_a, g, -1, mean_a, dead_a, skip_a, valid_a, rec);
+        }
       }
       {
         const uint32_t g = f * p.n_win + win;
-        peak_search_stage<N>(buf, lg, xi, vmax_b, row_max_b, p, p.rescue_hdr && valid_b && !dead_b && !skip_b, g, ip_b, mean_b, dead_b, skip_b, valid_b,
+        peak_search_stage<N, S16>(buf, lg, xi, vmax_b, row_max_b, p, p.rescue_hdr && valid_b && !dead_b && !skip_b, g, ip_b, mean_b, dead_b, skip_b, valid_b,
                              rec + kDeferRecDwords);
       }
     } else {
       // plane b's maximum and peak row first: register-only work the scheduler can slot into the LDS waits of plane a's fit
       float row_max_b;
-      const float vmax_b = plane_max<N>(xi, row_max_b);
-      const int ip_b = peak_row<N>(lg, vmax_b, row_max_b);
+      const float vmax_b = plane_max<N, S16>(xi, row_max_b);
+      const int ip_b = peak_row<N, S16>(lg, vmax_b, row_max_b);
       if (with_a) {
         float row_max, u, v;
         const uint32_t g = (f - 1) * p.n_win + win;
-        const float vmax = plane_max<N>(xr, row_max);
-        find_peak<N>(buf, lg, xr, vmax, row_max, p, u, v, p.rescue_hdr && valid_a && !dead_a && !skip_a, g);
+        const float vmax = plane_max<N, S16>(xr, row_max);
+        find_peak<N, false, S16>(buf, lg, xr, vmax, row_max, p, u, v, p.rescue_hdr && valid_a && !dead_a && !skip_a, g);
         float cm = vmax, sn = vmax * __builtin_amdgcn_rcpf(mean_a);
         if (dead_a) { u = v = sn = nanv; cm = 0.0f; }   // zero-variance window: an exactly-zero plane (corr 0, s2n 0/0, peak on the border)
         if (skip_a) u = v = cm = sn = nanv;
@@ -2112,7 +2291,7 @@ __global__ __launch_bounds__(BLOCK, (kWalkWaves<T, N>)) void piv_fft_walk_kernel
         float u, v;
         const uint32_t g = f * p.n_win + win;
         const float vmax = vmax_b, row_max = row_max_b;
-        find_peak<N>(buf, lg, xi, vmax, row_max, p, u, v, p.rescue_hdr && valid_b && !dead_b && !skip_b, g, ip_b);
+        find_peak<N, false, S16>(buf, lg, xi, vmax, row_max, p, u, v, p.rescue_hdr && valid_b && !dead_b && !skip_b, g, ip_b);
         float cm = vmax, sn = vmax * __builtin_amdgcn_rcpf(mean_b);
         if (dead_b) { u = v = sn = nanv; cm = 0.0f; }
         if (skip_b) u = v = cm = sn = nanv;
@@ -2872,8 +3051,17 @@ static hipError_t launch_t(const PivParams& p, bool ensemble, hipStream_t s) {
     const bool defer = defer_fit_setting() != 0;
     // the un-packing through DPP (kWalkUnpackDpp, option "unpack_dpp"), in either form of the fit
     const bool udpp = unpack_dpp_setting() != 0;
+    // the LDS-light form (kWalkLite, option "lds_light"): only on top of the shipped form of the fit and the un-packing through DPP
+    const bool lite = lds_light_setting() != 0;
     auto launch_walk = [&](auto planes_c) {
       constexpr bool PLANES = decltype(planes_c)::value;
+      if constexpr (kWalkLite<T, N, PLANES, WANT_NZ>) {
+        constexpr bool DEFER = kWalkDefer<T, N, PLANES, WANT_NZ>;
+        if (lite && udpp && (defer || !DEFER)) {
+          hipLaunchKernelGGL((piv_fft_walk_kernel<T, N, PLANES, WANT_NZ, DEFER, true, true>), dim3(wblocks), dim3(BLOCK), DEFER ? defer_lds : walk_lds, s, q);
+          return;
+        }
+      }
       if constexpr (kWalkDefer<T, N, PLANES, WANT_NZ>) {
         if (defer) {
           if constexpr (kWalkUnpackDpp<T, N, PLANES, WANT_NZ>) {

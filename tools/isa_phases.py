@@ -10,7 +10,7 @@ many of them are v_fma / v_mul / v_add / v_sub = arithmetic of the transforms, v
 transcendental), LDS, VMEM, scratch, SALU, waitcnt, and the LDS ROUND TRIPS the segment waits for: an `s_waitcnt lgkmcnt(n)` counts as one
 when the newest operation it needs was issued after the previous such wait -- the wave then sits out a whole LDS / crossbar latency,
 while a wait for an operation that was already in flight behind the one the previous wait needed only trails it (rt = all of them,
-rt_perm = those whose awaited operation is a ds_bpermute).  A last line gives the position of the loop's VMEM loads relative to the first
+rt_perm = those whose awaited operation is a ds_bpermute; lds_swz = the ds_swizzle among the lds_perm instructions).  A last line gives the position of the loop's VMEM loads relative to the first
 `s_waitcnt vmcnt` behind the first of them.
 
     --asm FILE   read the assembly from FILE (an `hipcc -S --cuda-device-only` output) instead of compiling"""
@@ -79,6 +79,8 @@ def classify(l):
         c["lds"] += 1
         if "bpermute" in op or "swizzle" in op:
             c["lds_perm"] += 1
+        if "swizzle" in op:
+            c["lds_swz"] += 1
     elif op.startswith("scratch_"):
         c["scratch"] += 1
     elif op.startswith(("global_", "buffer_", "flat_")):
@@ -117,7 +119,7 @@ for l in body:
             cur["rt_perm"] += 1 if issued[newest] else 0
         needed, mark = newest + 1, len(issued)
 segs.append((prio, cur))
-cols = ["valu", "arith_f32", "cvt", "mov", "cndmask", "int/bit", "minmax/cmp", "trans", "dpp", "other_valu", "lds", "lds_perm", "vmem", "scratch", "salu", "waitcnt", "rt", "rt_perm"]
+cols = ["valu", "arith_f32", "cvt", "mov", "cndmask", "int/bit", "minmax/cmp", "trans", "dpp", "other_valu", "lds", "lds_perm", "lds_swz", "vmem", "scratch", "salu", "waitcnt", "rt", "rt_perm"]
 print(f"loop body: {len(body)} instructions, {len(segs)} segments (priority after the s_setprio that opens the segment)")
 print("seg prio " + " ".join(f"{c:>10s}" for c in cols))
 tot = collections.Counter()
