@@ -133,6 +133,12 @@ int         lspiv_synchronize(void);                    /* hipDeviceSynchronize 
  *                      (tests/test_gpu_rescue_fixed_size.py);
  *   "rescue_fit_size"  read-only (lspiv_get_option): the compile-time window size of the fit kernel the last rescue pass of the
  *                      process launched, 0 the run-time-geometry kernel, -1 no pass yet.  For tests of the dispatch.
+ * Planes with no frames behind them -- lspiv_u_v_displacement, and lspiv_ensemble_finish / lspiv_ensemble_sliding_finish on a sum whose
+ * frames are not all at hand (an imported state, a chunk that could not be retained) -- have nothing to be re-evaluated from and need
+ * nothing: their float32 samples are the input, only the float32 arithmetic of the fit errs.  With "rescue" = 1 the windows the flag
+ * model marks get the 3-point fit of their five samples in float64 instead; the others keep the bits of the float32 fit.
+ * lspiv_ensemble_stats still counts them as flagged and left without a re-evaluation from the frames.
+ *   "peaks_refitted"   read-only: the planes the last lspiv_u_v_displacement of the process fitted in float64.
  * Batched sub-pixel fit of the 32 x 32 time-walking kernels:
  *   "defer_fit"        1 (default; environment LSPIV_DEFER_FIT) an iteration stops after the arg-max search and the peak's samples, and
  *                      after every 16th iteration each lane of a window's lane group fits one of the 32 staged planes | 0 every plane is
@@ -478,14 +484,16 @@ int lspiv_ensemble_finish(lspiv_ensemble* handle, float count_min, float n_frame
  * FRAMES, over the pairs that were added to the sum, and u, v are overwritten.  The frames therefore have to be reachable at
  * finish:
  *   - lspiv_ensemble_accumulate (host frames) keeps its upload buffers in HBM until finish / destroy, as long as they fit
- *     LSPIV_ENSEMBLE_RETAIN_BYTES (default: a quarter of the device memory); beyond that the float32 fits stay;
- *   - lspiv_ensemble_accumulate_dev keeps nothing by default (LSPIV_RETAIN_NONE: float32 fits, as in round 3);
+ *     LSPIV_ENSEMBLE_RETAIN_BYTES (default: a quarter of the device memory); beyond that nothing is re-evaluated from frames;
+ *   - lspiv_ensemble_accumulate_dev keeps nothing by default (LSPIV_RETAIN_NONE: no re-evaluation from frames);
  *     LSPIV_RETAIN_COPY makes the handle copy every chunk (same budget), LSPIV_RETAIN_BORROW only records the caller's pointer --
  *     the caller then guarantees that every chunk handed to accumulate_dev stays valid and unchanged until finish;
- *   - a state brought in with lspiv_ensemble_import holds pairs whose frames this handle never saw: lspiv_ensemble_finish keeps the
- *     float32 fits then (the staged finish below is the multi-GPU way).
+ *   - a state brought in with lspiv_ensemble_import holds pairs whose frames this handle never saw: lspiv_ensemble_finish
+ *     re-evaluates nothing from frames then (the staged finish below is the multi-GPU way).
+ * Without the frames the flagged windows get the float64 fit of the five samples of the float32 mean plane (the 3-point fit's own
+ * arithmetic, not the plane, is then exact; "peaks_refitted" above).
  * Set the mode before the first accumulate call.  lspiv_ensemble_stats after finish: stats[0..5] = windows flagged, windows
- * re-evaluated, windows left with their float32 fit (no frames / more than four arg-max candidates / list limit), chunks kept,
+ * re-evaluated from the frames, windows left without that (no frames / more than four arg-max candidates / list limit), chunks kept,
  * bytes kept, 1 if every chunk could be kept. */
 #define LSPIV_RETAIN_NONE   0
 #define LSPIV_RETAIN_COPY   1

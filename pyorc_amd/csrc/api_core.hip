@@ -162,6 +162,7 @@ static std::atomic<int> g_opt_defer_fit{env_opt_def("LSPIV_DEFER_FIT", 0, 1, 1)}
 static std::atomic<int> g_opt_unpack_dpp{env_opt_def("LSPIV_UNPACK_DPP_OPT", 0, 1, 1)};
 static std::atomic<int> g_opt_lds_light{env_opt_def("LSPIV_LDS_LIGHT", 0, 1, 1)};
 std::atomic<int> g_rescue_fit_size{-1};
+std::atomic<int> g_peaks_refitted{0};
 std::atomic<int> g_opt_narrow_offset{env_opt_def("LSPIV_NARROW_OFFSET", -1, 1 << 30, 1024)};
 std::atomic<int> g_opt_rescue_kappa{env_opt_def("LSPIV_RESCUE_KAPPA", 0, 1000000, 500)};
 std::atomic<int> g_opt_rescue_tau{env_opt_def("LSPIV_RESCUE_TAU", 0, 1000000, 4000)};
@@ -288,6 +289,7 @@ int lspiv_set_option(const char* name, int value) {
     return LSPIV_OK;
   }
   if (strcmp(name, "rescue_fit_size") == 0) return fail(LSPIV_EINVAL, "rescue_fit_size is read-only");
+  if (strcmp(name, "peaks_refitted") == 0) return fail(LSPIV_EINVAL, "peaks_refitted is read-only");
   const Option* o = find_option(name);
   if (!o) return fail(LSPIV_EINVAL, "unknown option '%s'", name);
   if (value < o->lo || value > o->hi) return fail(LSPIV_EINVAL, "%s", o->range);
@@ -298,6 +300,7 @@ int lspiv_get_option(const char* name, int* value) {
   if (!name || !value) return fail(LSPIV_EINVAL, "NULL argument");
   if (strcmp(name, "walk") == 0) { *value = lspiv::walk_setting(); return LSPIV_OK; }
   if (strcmp(name, "rescue_fit_size") == 0) { *value = g_rescue_fit_size.load(); return LSPIV_OK; }
+  if (strcmp(name, "peaks_refitted") == 0) { *value = g_peaks_refitted.load(); return LSPIV_OK; }
   const Option* o = find_option(name);
   if (!o) return fail(LSPIV_EINVAL, "unknown option '%s'", name);
   *value = o->value->load();

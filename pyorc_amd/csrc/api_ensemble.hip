@@ -33,7 +33,7 @@ struct lspiv_ensemble {
   // that accumulated, recorded after each accumulate, waited for by every reader of the sums and of the kept records
   struct AccEvent { hipStream_t stream; hipEvent_t ev; };
   std::vector<AccEvent> acc_events;
-  bool retain_complete;     // false: some chunk could not be kept (budget, mode NONE, imported state) -> float32 fits stay
+  bool retain_complete;     // false: some chunk could not be kept (budget, mode NONE, imported state) -> no rescue from frames (ensemble_refit_planes)
   void* d_rescue; size_t rescue_cap;     // EnsRescueHdr (256 B) + records
   double* d_partial; size_t partial_cap;
   double* d_totals; size_t totals_cap;   // (n_rec, kEnsMaxCand * 5): the partial sums merged over this handle's pair-blocks
@@ -488,6 +488,22 @@ static int ensemble_mean_fit(lspiv_ensemble* h, DeviceCtx* c, float min_count) {
   return launch_status(lspiv::launch_peaks_from_planes(c->d_planes, (uint32_t)n_win, h->wy, h->wx, g_opt_border.load(), c->d_out,
                                                        c->d_out + n_win, c->stream));
 }
+// flag model of the per-pair epilogues (fill_params); the block-per-window kernels (kinds 3 / 9 / 10) assume twice the plane noise
+// of the fused FFT kernels there, and so does the mean of their planes here
+static float ensemble_flag_k(const lspiv_ensemble* h) {
+  const int kind = lspiv_kernel_kind(h->wy, h->wx);
+  const double noise_mult = (kind == 3 || kind == 9 || kind == 10) ? 2.0 : 1.0;
+  return (float)(noise_mult * 2.0 * g_opt_rescue_kappa.load() * 1e-9 / (0.6931471805599453 * 1e-4));
+}
+// The flagged windows of a sum whose frames are not all at hand (an imported state, a chunk that could not be retained): nothing to
+// re-evaluate them from, but the mean planes in c->d_planes are what the caller gets and what the fit is a function of -- the fit of
+// their five samples in float64 (piv_peaks.h) over c->d_out [u | v]; windows the model does not flag keep their bits.  The counters keep
+// their meaning: these windows stay "flagged" and "skipped" (left without a re-evaluation from the frames).
+static int ensemble_refit_planes(lspiv_ensemble* h, DeviceCtx* c, size_t n_planes = 0) {
+  const size_t n_win = n_planes ? n_planes : (size_t)h->g.n_rows * h->g.n_cols;
+  return launch_status(lspiv::launch_peaks_from_planes(c->d_planes, (uint32_t)n_win, h->wy, h->wx, g_opt_border.load(), c->d_out,
+                                                       c->d_out + n_win, ensemble_flag_k(h), nullptr, c->stream));
+}
 static lspiv::EnsRescueRec* ensemble_recs(lspiv_ensemble* h) { return reinterpret_cast<lspiv::EnsRescueRec*>((char*)h->d_rescue + 256); }
 
 // flag the windows whose float32 fit (c->d_out, of the mean planes in c->d_planes) cannot be trusted to 1e-4; the records end
@@ -501,11 +517,7 @@ static int ensemble_flag(lspiv_ensemble* h, DeviceCtx* c, uint32_t n_planes = 0)
   LSPIV_TRY(ensure(&h->d_rescue, &h->rescue_cap, hdr_bytes + (size_t)n_win * sizeof(lspiv::EnsRescueRec)));
   lspiv::EnsRescueHdr* d_hdr = static_cast<lspiv::EnsRescueHdr*>(h->d_rescue);
   HIP_TRY(hipMemsetAsync(d_hdr, 0, hdr_bytes, c->stream));
-  // flag model of the per-pair epilogues (fill_params); the block-per-window kernels (kinds 3 / 9 / 10) assume twice the plane noise
-  // of the fused FFT kernels there, and so does the mean of their planes here
-  const int kind = lspiv_kernel_kind(h->wy, h->wx);
-  const double noise_mult = (kind == 3 || kind == 9 || kind == 10) ? 2.0 : 1.0;
-  const float k = (float)(noise_mult * 2.0 * g_opt_rescue_kappa.load() * 1e-9 / (0.6931471805599453 * 1e-4));
+  const float k = ensemble_flag_k(h);
   LSPIV_TRY(launch_status(lspiv::launch_ens_flag(c->d_planes, n_win, h->wy, h->wx, c->d_out, c->d_out + n_win, k, (float)(g_opt_rescue_tau.load() * 1e-9),
                                                 d_hdr, ensemble_recs(h), n_win, c->stream)));
   lspiv::EnsRescueHdr hdr;
@@ -690,7 +702,10 @@ int lspiv_ensemble_finish(lspiv_ensemble* h, float count_min, float n_frames, fl
     bool complete = false;
     if (h->n_rec && !h->foreign) LSPIV_TRY(ensemble_partials(h, c, &complete));
     if (h->n_rec && complete) LSPIV_TRY(ensemble_final(h, c, h->d_totals));
-    else h->last_skipped = h->last_flagged;
+    else {
+      h->last_skipped = h->last_flagged;
+      if (h->last_flagged) LSPIV_TRY(ensemble_refit_planes(h, c));
+    }
   }
   return ensemble_deliver(h, c, u, v, corr_count, corr_mean);
 }
@@ -834,7 +849,10 @@ int lspiv_ensemble_sliding_finish(lspiv_ensemble* h, float count_min, int64_t fi
       bool complete = false;
       if (h->n_rec) LSPIV_TRY(ensemble_partials(h, c, &complete, d_cnt, j0));
       if (h->n_rec && complete) LSPIV_TRY(ensemble_final(h, c, h->d_totals, d_cnt, n_planes));
-      else h->last_skipped = h->last_flagged;
+      else {
+        h->last_skipped = h->last_flagged;
+        if (h->last_flagged) LSPIV_TRY(ensemble_refit_planes(h, c, n_planes));
+      }
       flagged += h->last_flagged; rescued += h->last_rescued; skipped += h->last_skipped;
     }
     LSPIV_TRY(apply_v_sign(c->d_out + n_planes, (int64_t)n_planes, c->stream));

@@ -14,6 +14,7 @@
 
 #include "common.h"
 #include "host_stage.h"
+#include "piv_peaks.h"
 #include "rescue_options.h"
 
 namespace lspiv_api __attribute__((visibility("hidden"))) {
@@ -215,6 +216,8 @@ extern std::atomic<int> g_opt_rescue;
 extern std::atomic<int> g_opt_rescue_kappa;
 extern std::atomic<int> g_opt_rescue_tau;
 // ("rescue_generic" and the read-only "rescue_fit_size": rescue_options.h, shared with piv_rescue.hip)
+// "peaks_refitted" (read-only): planes the last lspiv_u_v_displacement of this process fitted again in float64 (piv_peaks.h)
+extern std::atomic<int> g_peaks_refitted;
 // float64 host stacks: a frame whose DC offset (host_stage.h, frame_offset) reaches this magnitude has it taken off while it is
 // narrowed to float32 -- PIV entry points only (the per-window normalisation does not see it), and only without a signal threshold
 // (which counts samples != 0).  -1: never.

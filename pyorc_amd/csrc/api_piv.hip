@@ -1058,13 +1058,22 @@ int lspiv_u_v_displacement(const float* corr_planes, int64_t P, int64_t n_win, i
   LSPIV_TRY(get_ctx(&c));
   const size_t pb = (size_t)n * wy * wx * sizeof(float);
   LSPIV_TRY(ensure(&c->d_planes, &c->planes_cap, pb));
-  LSPIV_TRY(ensure(&c->d_out, &c->out_cap, 2 * (size_t)n * sizeof(float)));
+  LSPIV_TRY(ensure(&c->d_out, &c->out_cap, (2 * (size_t)n + 1) * sizeof(float)));   // [u | v | planes re-fitted]
   HIP_TRY(hipMemcpyAsync(c->d_planes, corr_planes, pb, hipMemcpyHostToDevice, c->stream));
-  LSPIV_TRY(launch_status(lspiv::launch_peaks_from_planes(c->d_planes, (uint32_t)n, wy, wx, g_opt_border.load(), c->d_out, c->d_out + n, c->stream)));
+  // no frames behind these planes, so no rescue pass: the windows its criterion flags (no plane noise here: the allowance of the fused
+  // kernels, not doubled) get the float64 fit of their five samples instead (piv_peaks.h); "rescue" = 0 keeps the float32 fits
+  const float refit_k = g_opt_rescue.load() ? (float)(2.0 * g_opt_rescue_kappa.load() * 1e-9 / (0.6931471805599453 * 1e-4)) : 0.0f;
+  uint32_t* const d_refit = reinterpret_cast<uint32_t*>(c->d_out + 2 * n);
+  uint32_t n_refit = 0;
+  HIP_TRY(hipMemsetAsync(d_refit, 0, sizeof(uint32_t), c->stream));
+  LSPIV_TRY(launch_status(lspiv::launch_peaks_from_planes(c->d_planes, (uint32_t)n, wy, wx, g_opt_border.load(), c->d_out, c->d_out + n, refit_k,
+                                                          d_refit, c->stream)));
   LSPIV_TRY(apply_v_sign(c->d_out + n, n, c->stream));
   HIP_TRY(hipMemcpyAsync(u, c->d_out, n * sizeof(float), hipMemcpyDeviceToHost, c->stream));
   HIP_TRY(hipMemcpyAsync(v, c->d_out + n, n * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(hipMemcpyAsync(&n_refit, d_refit, sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
   HIP_TRY(hipStreamSynchronize(c->stream));
+  g_peaks_refitted.store((int)std::min<uint32_t>(n_refit, 0x7fffffffu));
   return LSPIV_OK;
 }
 

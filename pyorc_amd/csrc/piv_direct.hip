@@ -15,6 +15,7 @@
 
 #include "common.h"
 #include "fft_regs.h"
+#include "piv_peaks.h"
 
 namespace lspiv {
 
@@ -957,32 +958,81 @@ hipError_t launch_piv_direct(const PivParams& p, int dtype, bool ensemble, hipSt
 }
 
 // ---- ffpiv.u_v_displacement on a plane volume in HBM (pyorc/velocimetry/ffpiv.py:324,471) ------
-// np.argmax semantics: first maximum in row-major order, NaN counts as maximum.
+// np.argmax semantics: the first NaN if the plane holds one (np.argmax([1, inf, nan, inf]) is 2), else the first maximum in row-major
+// order, -0.0 equal to +0.0.  The samples are ranked by an integer key that orders like that: NaN above +inf, the float's own order below.
+__device__ __forceinline__ int argmax_key(float x) {
+  if (x != x) return 0x7fffffff;
+  const int b = __builtin_bit_cast(int, x);
+  return b < 0 ? (int)(0x80000000u - (uint32_t)b) : b;   // negative floats: the larger magnitude ranks lower; -0.0 -> 0
+}
+__device__ __forceinline__ void wave_argmax_key(int& key, int& idx) {
+#pragma unroll
+  for (int o = 32; o >= 1; o >>= 1) {
+    const int pk = __shfl_xor(key, o, 64);
+    const int pi = __shfl_xor(idx, o, 64);
+    const bool take = (pk > key) || (pk == key && pi < idx);
+    key = take ? pk : key;
+    idx = take ? pi : idx;
+  }
+}
+
+// ffpiv's peak_position in float64: zero denominator -> zero offset
+__device__ __forceinline__ double gauss_offset_f64(double lm, double l0, double lp) {
+  const double nom = lm - lp;
+  const double den = 2.0 * lm - 4.0 * l0 + 2.0 * lp;
+  return den != 0.0 ? nom / den : 0.0;
+}
+
+// refit_k > 0 (piv_peaks.h): a plane whose float32 fit common.h's peak_cond flags at that k is fitted again in float64 from its five
+// float32 samples by lane 0; the others keep the float32 bits
 __global__ __launch_bounds__(64) void peaks_kernel(const float* planes, uint32_t n_planes, int wy, int wx, int border_mode,
-                                                   float* u, float* v) {
+                                                   float* u, float* v, float refit_k, uint32_t* n_refit) {
   const uint32_t g = blockIdx.x;
   const int lane = threadIdx.x;
   const int n = wy * wx;
   const float* pl = planes + (size_t)g * n;
-  float best = -__builtin_inff();
+  int best = (int)0x80000000;   // below every key: the first sample of a lane always wins
   int bi = 0x7fffffff;
   for (int o = lane; o < n; o += 64) {
-    float x = pl[o];
-    x = (x != x) ? __builtin_inff() : x;  // NaN ranks as the maximum, first one wins
-    if (x > best || bi == 0x7fffffff) { best = x; bi = o; }
+    const int key = argmax_key(pl[o]);
+    if (key > best) { best = key; bi = o; }
   }
-  wave_argmax(best, bi);
+  wave_argmax_key(best, bi);
   float uu, vv;
   // a NaN plane (a window skipped by the signal threshold) stays NaN whatever the border mode
-  subpixel_generic([&](int o) { return pl[o]; }, wy, wx, bi, pl[bi] != pl[bi] ? 0 : border_mode, uu, vv);
-  if (lane == 0) { u[g] = uu; v[g] = vv; }
+  const float vmax = pl[bi];
+  subpixel_generic([&](int o) { return pl[o]; }, wy, wx, bi, vmax != vmax ? 0 : border_mode, uu, vv);
+  if (lane != 0) return;
+  const int i = bi / wx, j = bi - i * wx;
+  if (refit_k > 0.0f && i > 0 && i < wy - 1 && j > 0 && j < wx - 1) {
+    const float cl = pl[bi - wx] + kEpsPeak, cr = pl[bi + wx] + kEpsPeak, cd = pl[bi - 1] + kEpsPeak, cu = pl[bi + 1] + kEpsPeak;
+    const float l0 = __builtin_amdgcn_logf(vmax + kEpsPeak);
+    float den_v, den_u;
+    gauss_offset_fast(__builtin_amdgcn_logf(cl), l0, __builtin_amdgcn_logf(cr), den_v);
+    gauss_offset_fast(__builtin_amdgcn_logf(cd), l0, __builtin_amdgcn_logf(cu), den_u);
+    if (peak_cond(vmax, false, false, cl, cr, den_v, vv, cd, cu, den_u, uu, refit_k).fit) {
+      const double eps = 1e-7;
+      const double d0 = log((double)vmax + eps);
+      const double dv = gauss_offset_f64(log((double)pl[bi - wx] + eps), d0, log((double)pl[bi + wx] + eps));
+      const double du = gauss_offset_f64(log((double)pl[bi - 1] + eps), d0, log((double)pl[bi + 1] + eps));
+      vv = (float)((double)i + dv - (double)(wy / 2));
+      uu = (float)((double)j + du - (double)(wx / 2));
+      if (n_refit) atomicAdd(n_refit, 1u);
+    }
+  }
+  u[g] = uu;
+  v[g] = vv;
 }
 
 hipError_t launch_peaks_from_planes(const float* planes, uint32_t n_planes, int wy, int wx, int border_mode, float* u, float* v,
-                                    hipStream_t s) {
+                                    float refit_k, uint32_t* n_refit, hipStream_t s) {
   if (n_planes == 0) return hipSuccess;
-  hipLaunchKernelGGL(peaks_kernel, dim3(n_planes), dim3(64), 0, s, planes, n_planes, wy, wx, border_mode, u, v);
+  hipLaunchKernelGGL(peaks_kernel, dim3(n_planes), dim3(64), 0, s, planes, n_planes, wy, wx, border_mode, u, v, refit_k, n_refit);
   return hipGetLastError();
+}
+hipError_t launch_peaks_from_planes(const float* planes, uint32_t n_planes, int wy, int wx, int border_mode, float* u, float* v,
+                                    hipStream_t s) {
+  return launch_peaks_from_planes(planes, n_planes, wy, wx, border_mode, u, v, 0.0f, nullptr, s);
 }
 
 // ---- "stack" signal mode (second reading of pyorc/velocimetry/ffpiv.py:93-97) ----------

@@ -1043,7 +1043,9 @@ def _speckle_and_particles(T, H, W, seed):
 def test_ensemble_rescue_of_the_final_fit(gpu, monkeypatch):
     """Round 4: lspiv_ensemble_finish re-evaluates the ill-conditioned fits of the MEAN planes in float64 from the retained frames
     (csrc/piv_rescue.hip, ens_*): every window within 1e-4 of the oracle; the host entry point keeps its upload buffers, the
-    device entry point copies / borrows on request, and without frames (mode NONE, budget, imported state) the float32 fits stay."""
+    device entry point copies / borrows on request; without frames (mode NONE, budget, imported state) nothing is re-evaluated from
+    frames: the windows nobody flagged keep their float32 bits, the flagged ones get the float64 fit of the mean plane's five samples
+    (csrc/piv_peaks.h; tests/test_gpu_peaks_planes.py holds that fit to the gate), the same bits on all three paths."""
     import pyorc_amd.piv as P
     from pyorc_amd import DeviceFrames, _lib
 
@@ -1063,6 +1065,13 @@ def test_ensemble_rescue_of_the_final_fit(gpu, monkeypatch):
     def check(u, v):
         assert np.array_equal(np.isnan(u), np.isnan(uo)) and np.array_equal(np.isnan(v), np.isnan(vo))
         return max(rel_err(u, uo), rel_err(v, vo))
+
+    def frameless(u, v, st_):
+        """Without frames: float32 bits (u0, v0) except on at most `flagged` windows, whose fit was redone on the mean plane."""
+        differ = ~(((u == u0) | (np.isnan(u) & np.isnan(u0))) & ((v == v0) | (np.isnan(v) & np.isnan(v0))))
+        assert np.array_equal(np.isnan(u), np.isnan(u0)) and np.array_equal(np.isnan(v), np.isnan(v0))
+        assert st_["rescued"] == 0 and st_["float32_kept"] == st_["flagged"] == st["flagged"] and differ.sum() <= st_["flagged"], (st_, differ.sum())
+        return u.tobytes() + v.tobytes()
 
     ens = P.Ensemble((H, W), ws, ov)                                 # host frames, one chunk
     ens.accumulate(fr, kw["corr_min"], kw["s2n_min"])
@@ -1096,20 +1105,20 @@ def test_ensemble_rescue_of_the_final_fit(gpu, monkeypatch):
         if rescued:
             assert np.array_equal(u4, u1, equal_nan=True) and np.array_equal(v4, v1, equal_nan=True) and st4["bytes_kept"] >= fr.nbytes
         else:
-            assert st4["flagged"] == st["flagged"] and st4["rescued"] == 0 and st4["float32_kept"] == st4["flagged"] and not st4["retain_complete"]
-            assert np.array_equal(u4, u0, equal_nan=True) and np.array_equal(v4, v0, equal_nan=True)
+            assert not st4["retain_complete"]
+            bits4 = frameless(u4, v4, st4)
     monkeypatch.setenv("LSPIV_ENSEMBLE_RETAIN_BYTES", "1000")        # budget too small for the chunk: float32 fits, nothing breaks
     ens = P.Ensemble((H, W), ws, ov)
     ens.accumulate(fr, kw["corr_min"], kw["s2n_min"])
     u5, v5, st5 = finish(ens)
-    assert not st5["retain_complete"] and st5["rescued"] == 0 and np.array_equal(u5, u0, equal_nan=True)
+    assert not st5["retain_complete"] and frameless(u5, v5, st5) == bits4
     monkeypatch.delenv("LSPIV_ENSEMBLE_RETAIN_BYTES")
     ens = P.Ensemble((H, W), ws, ov)                                 # an imported state has no frames behind it
     ens.accumulate(fr, kw["corr_min"], kw["s2n_min"])
     s, k = ens.export_state()
     ens.import_state(s, k)
     u6, v6, st6 = finish(ens)
-    assert st6["rescued"] == 0 and np.array_equal(u6, u0, equal_nan=True)
+    assert frameless(u6, v6, st6) == bits4
 
 
 @pytest.mark.parametrize("ws,dtype,wide", [(64, np.uint8, 0), (64, np.float32, 0), (24, np.float64, 0), (9, np.uint8, 0), (40, np.float32, 0), (96, np.uint8, 0),
