@@ -156,6 +156,12 @@ int         lspiv_synchronize(void);                    /* hipDeviceSynchronize 
  *                      (ds_swizzle).  Only on top of "unpack_dpp" = 1 and
  *                      "defer_fit" = 1; ignored otherwise.  Results and rescue records are the same bit for bit
  *                      (tests/test_gpu_lds_light.py).
+ * Group-uniform work of the peak search of the 32 x 32 time-walking kernels (per frame pair):
+ *   "scalar_epilogue"  1 (default; environment LSPIV_SCALAR_EPILOGUE) the first-match searches for the peak's row and column, the
+ *                      near-tie test, the wrapped neighbour indices and the record word of a plane are taken from ballots on the
+ *                      scalar unit, one value per 32-lane group | 0 they are computed 64 lanes wide in vector registers.  Only on
+ *                      top of "lds_light" = 1 where that applies; ignored otherwise.  Integer first-match and index arithmetic:
+ *                      results and rescue records are the same bit for bit (tests/test_gpu_scalar_epilogue.py).
  * float64 HOST stacks are narrowed to float32 while they are staged (the kernels compute in float32).  A frame that rides on a
  * DC offset far above its contrast would lose the low bits of its texture in that conversion, where the reference normalises
  * every window in float64; the per-window normalisation does not see a constant added to a frame, so:
@@ -842,6 +848,11 @@ int lspiv_debug_fft_form(int n, int form, int inverse, const float* in, float* o
  * the value of the same lane of the other half): 2 returns the first result, 3 the second -- which is what the other half's lanes hold
  * after forms 0 and 1.  Another op or form: LSPIV_EUNSUPPORTED. */
 int lspiv_debug_half_reduce(int op, int form, const uint32_t* in, uint32_t* out, int64_t count);
+/* Test hook: the first-match search of the 32 x 32 peak search on `count` whole waves; in: count * 64 flags (non-zero = the lane matches),
+ * out[l] = the smallest shifted index (lane + 16) & 31 among the matching lanes of lane l's 32-lane half, 1 << 12 where there is none.
+ * form 0 = DPP arg-min, 1 = ballot and bit scan ("scalar_epilogue"), 2 = the paired DPP chain of "lds_light".  Another form:
+ * LSPIV_EUNSUPPORTED. */
+int lspiv_debug_first_match(int form, const uint32_t* in, uint32_t* out, int64_t count);
 /* Test hook (host only): how the time-walking kernels cut a chunk of n_pairs pairs that starts at absolute pair index
  * pair_offset into segments of seg_len pairs anchored at multiples of seg_len: pairs in the first segment, segment count. */
 int lspiv_debug_segments(int64_t n_pairs, int64_t pair_offset, int seg_len, int64_t* seg_first, int64_t* n_seg);

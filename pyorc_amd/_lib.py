@@ -195,6 +195,7 @@ SIGNATURES = {
     "lspiv_debug_fft": (_i32, [_i32, _i32, _vp, _vp, _i64]),
     "lspiv_debug_fft_form": (_i32, [_i32, _i32, _i32, _vp, _vp, _i64]),
     "lspiv_debug_half_reduce": (_i32, [_i32, _i32, _vp, _vp, _i64]),
+    "lspiv_debug_first_match": (_i32, [_i32, _vp, _vp, _i64]),
     "lspiv_debug_narrow": (_i32, [_vp, _i64, _i64, _i32, _vp, _vp]),
     "lspiv_debug_segments": (_i32, [_i64, _i64, _i32, _pi64, _pi64]),
     "lspiv_debug_hold_lock": (_i32, [_i32, _i32, _i32]),

@@ -161,6 +161,7 @@ std::atomic<int> g_opt_rescue_generic{env_opt("LSPIV_RESCUE_GENERIC", 0, 1)};
 static std::atomic<int> g_opt_defer_fit{env_opt_def("LSPIV_DEFER_FIT", 0, 1, 1)};
 static std::atomic<int> g_opt_unpack_dpp{env_opt_def("LSPIV_UNPACK_DPP_OPT", 0, 1, 1)};
 static std::atomic<int> g_opt_lds_light{env_opt_def("LSPIV_LDS_LIGHT", 0, 1, 1)};
+static std::atomic<int> g_opt_scalar_epilogue{env_opt_def("LSPIV_SCALAR_EPILOGUE", 0, 1, 1)};
 std::atomic<int> g_rescue_fit_size{-1};
 std::atomic<int> g_peaks_refitted{0};
 std::atomic<int> g_opt_narrow_offset{env_opt_def("LSPIV_NARROW_OFFSET", -1, 1 << 30, 1024)};
@@ -194,6 +195,8 @@ static const Option kOptions[] = {
      "unpack_dpp must be 1 (32 x 32 walking kernels exchange mirrored columns through DPP) or 0 (through LDS; same results)"},
     {"lds_light", &g_opt_lds_light, 0, 1,
      "lds_light must be 1 (32 x 32 walking kernels join the rows of their reductions with v_permlane16_swap) or 0 (ds_swizzle; same results)"},
+    {"scalar_epilogue", &g_opt_scalar_epilogue, 0, 1,
+     "scalar_epilogue must be 1 (32 x 32 walking kernels search the peak on ballots and the scalar unit) or 0 (in vector registers; same results)"},
     {"rescue_generic", &g_opt_rescue_generic, 0, 1,
      "rescue_generic must be 0 (fixed-size fit kernels for square 16 / 32 / 64 px windows) or 1 (run-time geometry for every launch)"},
     {"narrow_offset", &g_opt_narrow_offset, -1, INT_MAX,
@@ -254,6 +257,7 @@ int lspiv::walk_setting() {
 int lspiv::defer_fit_setting() { return g_opt_defer_fit.load(); }
 int lspiv::unpack_dpp_setting() { return g_opt_unpack_dpp.load(); }
 int lspiv::lds_light_setting() { return g_opt_lds_light.load(); }
+int lspiv::scalar_epilogue_setting() { return g_opt_scalar_epilogue.load(); }
 
 extern "C" {
 
@@ -585,6 +589,22 @@ int lspiv_debug_half_reduce(int op, int form, const uint32_t* in, uint32_t* out,
   HIP_TRY(hipMemcpyAsync(d_in, in, bytes, hipMemcpyHostToDevice, c->stream));
   hipError_t e = lspiv::launch_half_reduce_debug(op, form, d_in, d_out, (int)count, c->stream);
   if (e == hipErrorInvalidValue) return fail(LSPIV_EUNSUPPORTED, "no half-wave reduction %d in form %d", op, form);
+  LSPIV_TRY(launch_status(e));
+  HIP_TRY(hipMemcpyAsync(out, d_out, bytes, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  return LSPIV_OK;
+}
+int lspiv_debug_first_match(int form, const uint32_t* in, uint32_t* out, int64_t count) {
+  if (!in || !out || count < 1 || count > (1 << 16)) return fail(LSPIV_EINVAL, "bad argument");
+  DeviceCtx* c;
+  LSPIV_TRY(get_ctx(&c));
+  const size_t bytes = (size_t)count * 64 * sizeof(uint32_t);
+  LSPIV_TRY(ensure(&c->d_scratch, &c->scratch_cap, 2 * bytes));
+  uint32_t* d_in = (uint32_t*)c->d_scratch;
+  uint32_t* d_out = d_in + (size_t)count * 64;
+  HIP_TRY(hipMemcpyAsync(d_in, in, bytes, hipMemcpyHostToDevice, c->stream));
+  hipError_t e = lspiv::launch_first_match_debug(form, d_in, d_out, (int)count, c->stream);
+  if (e == hipErrorInvalidValue) return fail(LSPIV_EUNSUPPORTED, "no first-match search in form %d", form);
   LSPIV_TRY(launch_status(e));
   HIP_TRY(hipMemcpyAsync(out, d_out, bytes, hipMemcpyDeviceToHost, c->stream));
   HIP_TRY(hipStreamSynchronize(c->stream));

@@ -331,6 +331,45 @@ __device__ __forceinline__ void half_reduce2_i(int& x, int& y) {
   x = (int)r.ev;
   y = (int)r.od;
 }
+// ---- one value per 32-lane group, on the scalar unit (piv_fft_impl.h, SCAL) ---------------------------------------------------------
+// A wave holds two groups of 32 lanes; a ballot (one v_cmp into an SGPR pair) carries a predicate of both, one half each, and what is
+// derived from it -- first match, "any", indices, addresses -- is the same for all lanes of a group: SALU work on SGPRs.
+struct GroupInts { int g0, g1; };   // the lower and the upper group's value, both wave-uniform
+// One group's half of a ballot as a 32-bit scalar.  The empty asm statement pins it to an SGPR and keeps the optimiser from reasoning
+// about it as a part of the 64-bit value: "the upper half is zero" would become an ordered 64-bit compare, which this target has on the
+// vector unit only.
+__device__ __forceinline__ uint32_t ballot_half(uint64_t ballot, int group) {
+  uint32_t h = (uint32_t)(ballot >> (32 * group));
+  asm("" : "+s"(h));
+  return h;
+}
+// First match of a half in SHIFTED order: lane l holds shifted index (l + 16) & 31, so the half rotated by 16 has the lane of shifted
+// index s in bit s; s_ff1 of it is what min over (match ? shifted index : NONE) gives, and an empty half gives NONE as that does.
+// There is no scalar rotate -- written as one it becomes v_alignbit + v_readfirstlane --, hence the pinned part: shift, shift, or.
+constexpr int kNoMatch = 1 << 12;
+__device__ __forceinline__ int first_shifted32(uint32_t half) {
+  uint32_t up = half >> 16;
+  asm("" : "+s"(up));
+  const uint32_t rot = up | (half << 16);
+  return rot ? __builtin_ctz(rot) : kNoMatch;
+}
+__device__ __forceinline__ GroupInts first_shifted(uint64_t ballot) { return {first_shifted32(ballot_half(ballot, 0)), first_shifted32(ballot_half(ballot, 1))}; }
+// the lane's own group's value: one select on "upper half"
+__device__ __forceinline__ int group_pick(GroupInts v, bool upper) { return upper ? v.g1 : v.g0; }
+// g0 in lane 0 (and in every lane but 32), g1 in lane 32: for what only lane 0 of each group uses.  v_mov + v_writelane; written out
+// because the compiler has no builtin for v_writelane, and a select on "upper half" between two SGPRs costs three VALU on this target
+// (one SGPR per VALU instruction, and the lane mask is one)
+__device__ __forceinline__ uint32_t group_lane0(uint32_t g0, uint32_t g1) {
+  uint32_t v = g0;
+  asm("v_writelane_b32 %0, %1, 32" : "+v"(v) : "s"(g1));
+  return v;
+}
+// Both groups' values side by side in ONE register, 16 bits each: index arithmetic that stays inside the fields (adds and masks with
+// the constant in both halves, a multiplication whose products stay below 1 << 16) then costs one SALU instruction for the two groups,
+// and a lane takes its own group's field with one v_bfe_u32 on lane_shift = 0 (lower group) or 16 (upper group).
+__device__ __forceinline__ uint32_t group_pack16(GroupInts v) { return (uint32_t)v.g0 | ((uint32_t)v.g1 << 16); }
+__device__ __forceinline__ uint32_t group_field16(uint32_t pair, uint32_t lane_shift) { return __builtin_amdgcn_ubfe(pair, lane_shift, 16u); }
+
 // the same over one DPP row of 16 lanes (16 x 16 windows: four jobs per wave)
 __device__ __forceinline__ float row_sum(float x) {
   x += dpp_f<DPP_XOR1>(x);
@@ -612,6 +651,10 @@ int unpack_dpp_setting();
 // "unpack_dpp" end their 32-lane reductions in v_permlane16_swap and set the un-packing's lane mask once per group of values
 // (piv_fft_impl.h, LITE), 0 = ds_swizzle and a mask per two values; same bits either way.  Ignored with unpack_dpp = 0 or defer_fit = 0
 int lds_light_setting();
+// option "scalar_epilogue" (LSPIV_SCALAR_EPILOGUE presets it): 1 = the per-pair 32 x 32 walking kernels in their "lds_light" form do the
+// group-uniform work of the peak search -- first-match searches, near-tie test, neighbour indices, record word -- on ballots and SGPRs
+// (piv_fft_impl.h, SCAL), 0 = 64 lanes wide in VGPRs; same bits either way.  Ignored where "lds_light" does not apply
+int scalar_epilogue_setting();
 // Segments of the time-walking kernels.  A job walks one window through a run of consecutive frame pairs and shares
 // every frame's spectrum between the two pairs it belongs to; which frames share transforms depends on where a run
 // starts, so the runs ("segments") are ANCHORED: they start at the absolute pair indices k * kWalkAnchor of the caller's
@@ -724,6 +767,8 @@ hipError_t launch_fft_debug(int n, bool inverse, const float* in, float* out, in
 hipError_t launch_fft_debug_form(int n, int form, bool inverse, const float* in, float* out, int count, hipStream_t s);
 // test hook (fft_debug.hip): `count` waves of 64 values through a 32-lane reduction, form 0 = ds_swizzle, 1 = v_permlane16_swap, 2 / 3 = paired
 hipError_t launch_half_reduce_debug(int op, int form, const uint32_t* in, uint32_t* out, int count, hipStream_t s);
+// test hook (fft_debug.hip): `count` waves of 64 flags, first match of each 32-lane group in shifted order; form 0 = DPP arg-min, 1 = ballot + bit scan
+hipError_t launch_first_match_debug(int form, const uint32_t* in, uint32_t* out, int count, hipStream_t s);
 // synthetic particle-image stack (bench / test utility)
 hipError_t launch_synth_particles(uint8_t* d_frames, int64_t T, int H, int W, uint64_t seed, float density,
                                   hipStream_t s);

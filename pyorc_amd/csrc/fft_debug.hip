@@ -101,4 +101,33 @@ hipError_t launch_half_reduce_debug(int op, int form, const uint32_t* in, uint32
   }
 }
 
+// Test hook: the first-match search of the 32 x 32 peak search on whole waves, one wave per block.  in = one flag per lane (non-zero =
+// the lane matches); out = what every lane of the group gets: the smallest SHIFTED index (lane + 16) & 31 among the group's matching
+// lanes, 1 << 12 where the group has none.  FORM 0 = the DPP arg-min (half_min_i in its v_permlane16_swap form), 1 = one ballot and a bit
+// scan per group (first_shifted), 2 = the paired DPP chain (half_reduce2_i) on the lane's flag and that of the same lane of the other half
+template <int FORM>
+__global__ __launch_bounds__(64) void first_match_debug_kernel(const uint32_t* in, uint32_t* out) {
+  const size_t t = (size_t)blockIdx.x * 64 + threadIdx.x;
+  const bool match = in[t] != 0u;
+  const int sh = (int)((threadIdx.x + 16u) & 31u);
+  int r;
+  if constexpr (FORM == 0) {
+    r = half_min_i<true>(match ? sh : kNoMatch);
+  } else if constexpr (FORM == 1) {
+    r = group_pick(first_shifted(__builtin_amdgcn_ballot_w64(match)), (threadIdx.x & 32u) != 0u);
+  } else {
+    int b = in[t ^ 32] != 0u ? sh : kNoMatch;
+    r = match ? sh : kNoMatch;
+    half_reduce2_i<RedOp::kMin>(r, b);
+  }
+  out[t] = (uint32_t)r;
+}
+hipError_t launch_first_match_debug(int form, const uint32_t* in, uint32_t* out, int count, hipStream_t s) {
+  if (form == 0) hipLaunchKernelGGL((first_match_debug_kernel<0>), dim3(count), dim3(64), 0, s, in, out);
+  else if (form == 1) hipLaunchKernelGGL((first_match_debug_kernel<1>), dim3(count), dim3(64), 0, s, in, out);
+  else if (form == 2) hipLaunchKernelGGL((first_match_debug_kernel<2>), dim3(count), dim3(64), 0, s, in, out);
+  else return hipErrorInvalidValue;
+  return hipGetLastError();
+}
+
 }  // namespace lspiv

@@ -1820,8 +1820,10 @@ __device__ __forceinline__ void unpack_step(int ky, float mr, float mi, int part
 // UDPP: between the transposes the columns sit in the lanes of unpack_col, and the un-packing exchanges through DPP (kWalkUnpackDpp)
 // S16: the 32-lane reductions of the conversion end in v_permlane16_swap (kWalkSwap16); UG > 2 (with UDPP): UG exchanged values per mask
 // set, in place (kWalkUnpackGroup, mirror_rows_ip)
+// OWN_MEAN (with UDPP): the plane means are handed out as the lane's OWN DC bins -- lane 0 of a group holds column 0 under either column
+// map, and a caller that uses the means in lane 0 only (the record of the batched fit) needs no ds_bpermute for them
 template <typename T, int N, bool WANT_NZ, bool RELAX = false, bool HALF_TILE = false, int UB = 1, bool U8_EARLY = false, bool FOLD = kFftFoldLen<N>, bool SR = kFftSrLen<N>,
-          bool UDPP = false, bool S16 = false, int UG = 2>
+          bool UDPP = false, bool S16 = false, int UG = 2, bool OWN_MEAN = false>
 __device__ __forceinline__ void walk_iteration(const PivParams& p, const T* row, bool has2, float* buf, int lg,
                                                int partner_byte, int lane0_byte, WalkCarry<N>& c, float (&xr)[N],
                                                float (&xi)[N], float& mean_a, float& mean_b, bool& skip_a, bool& skip_b,
@@ -1947,8 +1949,13 @@ __device__ __forceinline__ void walk_iteration(const PivParams& p, const T* row,
       __builtin_amdgcn_sched_barrier(0);
     }
   }
-  mean_a = bperm_f(lane0_byte, xr[0]);   // plane means = DC bins
-  mean_b = bperm_f(lane0_byte, xi[0]);
+  if constexpr (OWN_MEAN) {
+    mean_a = xr[0];
+    mean_b = xi[0];
+  } else {
+    mean_a = bperm_f(lane0_byte, xr[0]);   // plane means = DC bins
+    mean_b = bperm_f(lane0_byte, xi[0]);
+  }
   __builtin_amdgcn_sched_barrier(0);
   LSPIV_SETPRIO(0);
   fft_walk<true, false, FOLD, SR>(xr, xi);    // along ky
@@ -2048,6 +2055,21 @@ template <typename T, int N, bool PLANES, bool WANT_NZ>
 constexpr int kWalkUnpackGroup = N != 32 ? 2 : LSPIV_UNPACK_GROUP >= 0 ? LSPIV_UNPACK_GROUP : kWalkUnpackGroup32[kSampleKind<T>][PLANES][WANT_NZ];
 template <typename T, int N, bool PLANES, bool WANT_NZ>
 constexpr bool kWalkLite = kWalkUnpackDpp<T, N, PLANES, WANT_NZ> && (kWalkSwap16<T, N, PLANES, WANT_NZ> || kWalkUnpackGroup<T, N, PLANES, WANT_NZ> > 2);
+// "Scalar epilogue" form (SCAL, option "scalar_epilogue"), on top of DEFER + UDPP + LITE (kWalkSwap16) only.  What the peak search computes
+// 64 lanes wide although its value is the same for the 32 lanes of a group moves to ballots and the scalar unit, which an iteration
+// leaves about 97 % idle (common.h, GroupInts): the first-match searches for ip and jp are one v_cmp into an SGPR pair and an s_ff1 per
+// group instead of a DPP min chain, the near-tie test is two bit counts, the wrapped neighbour indices and their LDS offsets are SALU on
+// both groups' values side by side in one register (group_pack16), and a lane takes its group's field with one v_bfe.  Integer first-match and index
+// arithmetic: the bits stay.  Per kernel by the resource rule of the un-pack batch above (tools/kres.py); -DLSPIV_WALK_SCALAR=0 / 1
+// forces it off / on.  [sample type][PLANES][WANT_NZ]; all ten kernels with a batched fit stay inside the step (147 ... 166 VGPRs, no
+// scratch, three waves); float64 with the score has no batched fit to sit on
+#ifndef LSPIV_WALK_SCALAR
+#define LSPIV_WALK_SCALAR -1
+#endif
+constexpr bool kWalkScalar32[3][2][2] = {{{true, true}, {true, true}}, {{true, true}, {true, true}}, {{true, false}, {true, false}}};
+template <typename T, int N, bool PLANES, bool WANT_NZ>
+constexpr bool kWalkScalar = kWalkLite<T, N, PLANES, WANT_NZ> && kWalkSwap16<T, N, PLANES, WANT_NZ> && kWalkDefer<T, N, PLANES, WANT_NZ> &&
+                             (LSPIV_WALK_SCALAR >= 0 ? LSPIV_WALK_SCALAR != 0 : kWalkScalar32[kSampleKind<T>][PLANES][WANT_NZ]);
 // The first iteration of a wave has no pair f - 1 in either group (f == p0): with LSPIV_SKIP_FIRST_A the 32 x 32 kernels leave out the
 // maximum, the search and the fit of its plane a -- nothing of it is stored, and a record slot that is not written stays invalid.
 #ifndef LSPIV_SKIP_FIRST_A
@@ -2116,6 +2138,95 @@ __device__ __forceinline__ void peak_search_stage(float* buf, int lg, const floa
   }
 }
 
+// ---- the same search with the group-uniform part on the scalar unit (SCAL) --------------------------------------------------------
+// plane_max_row2 with the peak rows as first matches of two ballots: one value per group
+template <int N>
+__device__ __forceinline__ void plane_max_row2_scal(const float (&ca)[N], const float (&cb)[N], float& row_max_a, float& row_max_b, float& vmax_a,
+                                                    float& vmax_b, GroupInts& ip_a, GroupInts& ip_b) {
+  static_assert(Geo<N>::LG == 32 && Geo<N>::FULL, "two planes per half-wave");
+  row_max_a = plane_row_max<N>(ca);
+  row_max_b = plane_row_max<N>(cb);
+  int ma = __builtin_bit_cast(int, row_max_a), mb = __builtin_bit_cast(int, row_max_b);
+  half_reduce2_i<RedOp::kMax>(ma, mb);   // a ballot cannot take a maximum
+  vmax_a = __builtin_bit_cast(float, ma);
+  vmax_b = __builtin_bit_cast(float, mb);
+  ip_a = first_shifted(__builtin_amdgcn_ballot_w64(row_max_a == vmax_a));
+  ip_b = first_shifted(__builtin_amdgcn_ballot_w64(row_max_b == vmax_b));
+}
+// "Another sample of the group within tau of the maximum", from the group's halves of the ballots of row_max >= thr and rowv >= thr.
+// peak_search_stage asks for a lane of the first other than the peak row's and a lane of the second other than the peak column's.  The
+// peak row's lane is IN the first ballot whenever there is a peak row (its row_max == vmax, and thr = vmax * (1 - tau) <= vmax: tau is in
+// [0, 1e-3], the planes are clipped to [0, 1], rounding is monotonic), and without one vmax is a NaN and both ballots are empty; the same
+// holds for the peak column in the second.  So "a lane other than that one" is "more than one lane": two s_bcnt1 and a compare.
+__device__ __forceinline__ bool group_near_tie(uint32_t rows_thr, uint32_t cols_thr) {
+  return max(__builtin_popcount(rows_thr), __builtin_popcount(cols_thr)) > 1;
+}
+// lane_shift: 0 in the lanes of the wave's lower group, 16 in the upper group's (group_field16)
+template <int N>
+__device__ __forceinline__ void peak_search_stage_scal(float* buf, int lg, uint32_t lane_shift, const float (&c)[N], float vmax, float row_max,
+                                                       const PivParams& p, bool note, uint32_t g, GroupInts ip, float mean, bool dead, bool skip, bool valid,
+                                                       uint32_t* rec) {
+  static_assert(Geo<N>::LG == 32 && Geo<N>::FULL && Geo<N>::POW2, "two groups of 32 lanes, one per tile row");
+  constexpr int LR = Geo<N>::LDS_ROW;
+  constexpr uint32_t RB = LR * 4, C = N / 2, kEach = 0x00010001u, kWrap = (N - 1) * kEach;
+  static_assert(N * RB < 65536u, "a byte offset into the tile fits a 16-bit field");
+  const char* tile = reinterpret_cast<const char*>(buf);
+  lds_row_write<N>(buf + lg * LR, c);
+  __builtin_amdgcn_wave_barrier();
+  // y, ym, yp of both groups at once (group_pack16: ip is at most NONE = 1 << 12, so nothing carries into the upper field), as byte
+  // offsets of their tile rows
+  const uint32_t ip2 = group_pack16(ip);
+  const uint32_t row = ((ip2 + C * kEach) & kWrap) * RB, row_m = ((ip2 + (C - 1) * kEach) & kWrap) * RB, row_p = ((ip2 + (C + 1) * kEach) & kWrap) * RB;
+  const float rowv = *reinterpret_cast<const float*>(tile + lg * 4 + group_field16(row, lane_shift));
+  const float thr = vmax * (1.0f - p.rescue_tau);
+  const uint64_t match = __builtin_amdgcn_ballot_w64(rowv == vmax);
+  const uint64_t rows_thr = __builtin_amdgcn_ballot_w64(row_max >= thr), cols_thr = __builtin_amdgcn_ballot_w64(rowv >= thr);
+  const GroupInts jp = first_shifted(match);
+  const bool near0 = group_near_tie(ballot_half(rows_thr, 0), ballot_half(cols_thr, 0));
+  const bool near1 = group_near_tie(ballot_half(rows_thr, 1), ballot_half(cols_thr, 1));
+  // x, xm, xp of both groups, times four; then the four neighbours' byte offsets
+  const uint32_t jp2 = group_pack16(jp);
+  const uint32_t col = ((jp2 + C * kEach) & kWrap) << 2, col_m = ((jp2 + (C - 1) * kEach) & kWrap) << 2, col_p = ((jp2 + (C + 1) * kEach) & kWrap) << 2;
+  const uint32_t at_l = row_m + col, at_r = row_p + col, at_d = row + col_m, at_u = row + col_p;
+  const uint32_t word0 = (uint32_t)ip.g0 | ((uint32_t)jp.g0 << 8) | (near0 ? kDeferNearTie : 0u);
+  const uint32_t word1 = (uint32_t)ip.g1 | ((uint32_t)jp.g1 << 8) | (near1 ? kDeferNearTie : 0u);
+  // lane 0 of each group reads its group's four neighbours and writes the record: same ds_write_b128 pair, same layout
+  if (lg == 0) {
+    const float nl = *reinterpret_cast<const float*>(tile + group_field16(at_l, lane_shift));
+    const float nr = *reinterpret_cast<const float*>(tile + group_field16(at_r, lane_shift));
+    const float nd = *reinterpret_cast<const float*>(tile + group_field16(at_d, lane_shift));
+    const float nu = *reinterpret_cast<const float*>(tile + group_field16(at_u, lane_shift));
+    const uint32_t packed = group_lane0(word0, word1) | (dead ? kDeferDead : 0u) | (skip ? kDeferSkip : 0u) | (valid ? kDeferValid : 0u) | (note ? kDeferNote : 0u);
+    uint4* r = reinterpret_cast<uint4*>(rec);
+    r[0] = make_uint4(__builtin_bit_cast(uint32_t, vmax), __builtin_bit_cast(uint32_t, nl), __builtin_bit_cast(uint32_t, nr), __builtin_bit_cast(uint32_t, nd));
+    r[1] = make_uint4(__builtin_bit_cast(uint32_t, nu), __builtin_bit_cast(uint32_t, mean), packed, g);
+  }
+  __builtin_amdgcn_wave_barrier();
+  if (near0 || near1) {   // scalar; "amb" = note && vmax > 0 && near_tie as in peak_search_stage, which sees the same ip, jp and thr
+    const bool upper = lane_shift != 0u;
+    const bool amb = note && vmax > 0.0f && (upper ? near1 : near0);
+    if (__builtin_amdgcn_ballot_w64(amb) != 0) {
+      constexpr int C = N / 2;
+      const int ipv = group_pick(ip, upper), jpv = group_pick(jp, upper);
+      const int sh = wrap_n<N>(lg + C);
+      uint32_t pos2 = 0xffffffffu;
+      const int pos1 = (ipv << 16) | jpv;
+      int cnt = 0, other = 0x7fffffff;
+#pragma unroll 1
+      for (int yy = 0; yy < N; ++yy) {
+        const bool cand = buf[yy * LR + lg] >= thr;
+        const int pos = (wrap_n<N>(yy + C) << 16) | sh;
+        cnt += cand ? 1 : 0;
+        other = (cand && pos != pos1) ? min(other, pos) : other;
+      }
+      cnt = group_sum_i<N, true>(cnt);
+      other = group_min_i<N, true>(other);
+      if (cnt == 2) pos2 = (uint32_t)other;
+      if (lg == 0 && amb) rescue_note(p.rescue_hdr, p.rescue_fit, p.rescue_cap_fit, p.rescue_amb, p.rescue_cap_amb, g, PeakCond{true, false}, ipv, jpv, pos2);
+    }
+  }
+}
+
 // Lane s of the group fits the plane of slot s: find_peak's arithmetic from the + kEpsPeak on, and the kernel's result tail.
 template <int N>
 __device__ __forceinline__ void defer_flush(uint32_t* stage, int lg, const PivParams& p) {
@@ -2152,14 +2263,15 @@ __device__ __forceinline__ void defer_flush(uint32_t* stage, int lg, const PivPa
   __builtin_amdgcn_wave_barrier();
 }
 
-// LITE: the LDS-light form (kWalkLite); a trailing argument, so that a kernel's name still starts as it did
-template <typename T, int N, bool PLANES, bool WANT_NZ, bool DEFER = false, bool UDPP = false, bool LITE = false>
+// LITE: the LDS-light form (kWalkLite), SCAL: the scalar epilogue (kWalkScalar); trailing arguments, so that a kernel's name still starts as it did
+template <typename T, int N, bool PLANES, bool WANT_NZ, bool DEFER = false, bool UDPP = false, bool LITE = false, bool SCAL = false>
 __global__ __launch_bounds__(BLOCK, (kWalkWaves<T, N>)) void piv_fft_walk_kernel(PivParams p) {
   static_assert(!DEFER || (N == 32 && !kTwoPlaneEpilogue<N>), "the batched fit is built for two groups of 32 lanes");
   static_assert(!UDPP || N == 32, "the paired column map is built for 32 x 32");
   static_assert(!LITE || (UDPP && N == 32), "the LDS-light form sits on top of the un-packing through DPP");
   constexpr bool S16 = LITE && kWalkSwap16<T, N, PLANES, WANT_NZ>;
   constexpr int UG = LITE ? kWalkUnpackGroup<T, N, PLANES, WANT_NZ> : 2;
+  static_assert(!SCAL || (LITE && DEFER && S16), "the scalar epilogue sits on top of the batched fit and the lane-swap reductions");
   const uint32_t seg_len = p.seg_len, n_seg = p.n_seg;
   extern __shared__ __attribute__((aligned(16))) float smem[];
   using G = Geo<N>;
@@ -2175,6 +2287,7 @@ __global__ __launch_bounds__(BLOCK, (kWalkWaves<T, N>)) void piv_fft_walk_kernel
   uint32_t it = 0;   // DEFER, kWalkSkipFirstA: iterations of the WAVE so far
   const int partner_byte = partner_byte_of<N>(lane, lg);
   const int lane0_byte = lane0_byte_of<N>();
+  const uint32_t lane_shift = 16u * (uint32_t)grp;   // SCAL: the lane's own field of a pair of group scalars (group_field16)
 
   // XCD-aware job order (walk_job): which segment, which window
   const WalkJob wj = walk_job<WAVES_PER_BLOCK * G::GROUPS>((uint32_t)(wave * G::GROUPS + grp), n_seg, p.n_win, p.div_nwin, p.xcd_by_windows);
@@ -2197,7 +2310,7 @@ __global__ __launch_bounds__(BLOCK, (kWalkWaves<T, N>)) void piv_fft_walk_kernel
     const bool has2 = f + 1 <= p1;
     float xr[N], xi[N], mean_a, mean_b;
     bool skip_a, skip_b, dead_a, dead_b;
-    walk_iteration<T, N, WANT_NZ, kWalkRelax<T, N>, false, kWalkUnpackBatch<T, N, PLANES, WANT_NZ>, kWalkU8Early<N, PLANES, WANT_NZ>, kFftFoldWalk<N>, kFftSrWalk<N>, UDPP, S16, UG>(
+    walk_iteration<T, N, WANT_NZ, kWalkRelax<T, N>, false, kWalkUnpackBatch<T, N, PLANES, WANT_NZ>, kWalkU8Early<N, PLANES, WANT_NZ>, kFftFoldWalk<N>, kFftSrWalk<N>, UDPP, S16, UG, SCAL>(
         p, row, has2, buf, lg, partner_byte, lane0_byte, carry, xr, xi, mean_a, mean_b, skip_a, skip_b, dead_a, dead_b);
     if (WANT_NZ && win_dropped) skip_a = skip_b = true;
     const bool with_a = !kWalkSkipFirstA<T, N, PLANES, WANT_NZ> || it != 0;   // wave-uniform: no group has a pair f - 1 in the wave's first iteration
@@ -2245,7 +2358,19 @@ __global__ __launch_bounds__(BLOCK, (kWalkWaves<T, N>)) void piv_fft_walk_kernel
       float row_max_b, vmax_b;
       int ip_b;
       uint32_t* rec = stage + (it & (kDeferSlots / 2 - 1)) * 2 * kDeferRecDwords;
-      if constexpr (S16) {
+      if constexpr (SCAL) {
+        // as below, with the peak rows of both planes as one scalar per group
+        float row_max, vmax;
+        GroupInts ips_a, ips_b;
+        plane_max_row2_scal<N>(xr, xi, row_max, row_max_b, vmax, vmax_b, ips_a, ips_b);
+        if (with_a) {
+          const uint32_t g = (f - 1) * p.n_win + win;
+          peak_search_stage_scal<N>(buf, lg, lane_shift, xr, vmax, row_max, p, p.rescue_hdr && valid_a && !dead_a && !skip_a, g, ips_a, mean_a, dead_a, skip_a, valid_a, rec);
+        }
+        const uint32_t g = f * p.n_win + win;
+        peak_search_stage_scal<N>(buf, lg, lane_shift, xi, vmax_b, row_max_b, p, p.rescue_hdr && valid_b && !dead_b && !skip_b, g, ips_b, mean_b, dead_b, skip_b, valid_b,
+                                  rec + kDeferRecDwords);
+      } else if constexpr (S16) {
         // both planes' maxima and peak rows together; in a wave's first iteration plane a is the plane of no pair, and what comes
         // out for it is not used
         float row_max, vmax;
@@ -2265,7 +2390,7 @@ __global__ __launch_bounds__(BLOCK, (kWalkWaves<T, N>)) void piv_fft_walk_kernel
           peak_search_stage<N>(buf, lg, xr, vmax, row_max, p, p.rescue_hdr && valid_a && !dead_a && !skip_a, g, -1, mean_a, dead_a, skip_a, valid_a, rec);
         }
       }
-      {
+      if constexpr (!SCAL) {
         const uint32_t g = f * p.n_win + win;
         peak_search_stage<N, S16>(buf, lg, xi, vmax_b, row_max_b, p, p.rescue_hdr && valid_b && !dead_b && !skip_b, g, ip_b, mean_b, dead_b, skip_b, valid_b,
                              rec + kDeferRecDwords);
@@ -3053,8 +3178,16 @@ static hipError_t launch_t(const PivParams& p, bool ensemble, hipStream_t s) {
     const bool udpp = unpack_dpp_setting() != 0;
     // the LDS-light form (kWalkLite, option "lds_light"): only on top of the shipped form of the fit and the un-packing through DPP
     const bool lite = lds_light_setting() != 0;
+    // the scalar epilogue (kWalkScalar, option "scalar_epilogue"): only on top of the LDS-light form with the batched fit
+    const bool scal = scalar_epilogue_setting() != 0;
     auto launch_walk = [&](auto planes_c) {
       constexpr bool PLANES = decltype(planes_c)::value;
+      if constexpr (kWalkScalar<T, N, PLANES, WANT_NZ>) {
+        if (scal && lite && udpp && defer) {
+          hipLaunchKernelGGL((piv_fft_walk_kernel<T, N, PLANES, WANT_NZ, true, true, true, true>), dim3(wblocks), dim3(BLOCK), defer_lds, s, q);
+          return;
+        }
+      }
       if constexpr (kWalkLite<T, N, PLANES, WANT_NZ>) {
         constexpr bool DEFER = kWalkDefer<T, N, PLANES, WANT_NZ>;
         if (lite && udpp && (defer || !DEFER)) {
