@@ -48,7 +48,8 @@ extern "C" {
                                * lspiv_ensemble_set_spectral_filter / _get_spectral_filter; the image mask, lspiv_mask_supported /
                                * lspiv_piv_masked_pairs_dev_at / lspiv_piv_masked_pairs_at; the second correlation peak, lspiv_peak2_supported /
                                * lspiv_piv_peak2_pairs_dev_at / lspiv_piv_peak2_pairs_at / lspiv_second_peak_dev / lspiv_second_peak; vector validation,
-                               * lspiv_validate_dev / lspiv_validate)
+                               * lspiv_validate_dev / lspiv_validate; the per-window frame lag, lspiv_lag_supported /
+                               * lspiv_piv_lag_pairs_dev_at / lspiv_piv_lag_pairs_at / lspiv_lag_predict_dev / lspiv_lag_predict)
                                * 5 (round 6): lspiv_chunk_alignment(wy, wx) without a grid now returns the alignment that is right on EVERY grid (75
                                * where it returned 25: callers that cut chunks on it stay bit-reproducible on large grids); additions:
                                * lspiv_upload_frames, lspiv_trace / lspiv_trace_read; the host-pointer projection entry points no longer
@@ -314,6 +315,62 @@ int lspiv_piv_multipass_dev_at(const void* d_frames, int dtype, int64_t T, int64
 int lspiv_piv_multipass_at(const void* frames, int dtype, int64_t T, int64_t H, int64_t W,
                            int n_passes, const int* passes, float signal_threshold, int64_t pair_offset,
                            float* u, float* v, float* corr_max, float* s2n, float* corr_planes, int16_t* shift_out);
+
+/* Per-window frame lag, multi-frame PIV for slow flow (the project's own semantics, unpinned): pair t, window w
+ * is correlated against frame t + k[t, w], k in 1 .. 16, and the displacement is divided by k -- the absolute error of a correlation peak
+ * does not shrink with the displacement, so a window that moves 0.2 px per frame interval is measured four times better over four
+ * intervals.  A = the window of frame t at its grid origin (y0, x0); B = the window of frame t + k at (y0 + dy, x0 + dx), the int16
+ * offset clamped exactly as lspiv_piv_shift_pairs_dev_at clamps it; plane, corr_max, s2n, the first maximum, the three-point fit,
+ * "border_peak" and the signal threshold are that entry point's.  u = (clamped dx + residual u) / k, v = (clamped dy + residual v) / k:
+ * the float32 sum, then ONE correctly rounded float32 division by (float)k; a NaN stays NaN; "v_sign" last.  Velocities stay in px per
+ * frame interval.  Kernel orientation throughout.  Option "norm_clip" = 0 and "signal_mode" = 1 are LSPIV_EUNSUPPORTED.
+ *
+ * lspiv_lag_supported: 1 for wy = wx in {16, 32, 64}, else 0.  Host-only.
+ *
+ * lspiv_piv_lag_pairs_dev_at: d_frames points at T frames AVAILABLE to this call; pairs 0 .. n_pairs - 1 of that pointer are computed,
+ * 1 <= n_pairs <= T - 1.  The lag of pair t is clipped to T - 1 - t OF THIS CALL, so a caller that cuts a stack into chunks must hand
+ * over, with every chunk, the frames up to min(last pair of the chunk + 16, end of the stack): then the clip is the one of the absolute
+ * frame count and no chunking changes a result.  No lag reads past frame T - 1: the library writes the table the kernels read.
+ * lag_form selects where the lags come from:
+ *   LSPIV_LAG_UNIFORM   k[t, w] = min(k, T - 1 - t), k in 1 .. 16;
+ *   LSPIV_LAG_WINDOW    d_lag: n_win bytes, one lag per window, values clamped to 1 .. 16, the same clip;
+ *   LSPIV_LAG_TABLE     d_lag: n_pairs * n_win bytes, one lag per (pair, window), clamped and clipped likewise;
+ *   LSPIV_LAG_ADAPTIVE  pass 0 is lspiv_piv_pairs_dev_at on the same grid at lag 1 (its bits, at the same pair_offset), then
+ *                       lspiv_lag_predict_dev with k_max = k and target128 turns pair t's field into (k, dy, dx) per window; d_lag and
+ *                       d_shift must be NULL.
+ * d_shift: NULL (zero offsets) or n_pairs * n_win * 2 int16 {dy, dx}.  d_out: 4 * n_pairs * n_win floats [u | v | corr_max | s2n], laid
+ * out as lspiv_piv_pairs_dev_at lays them out for n_pairs pairs; d_corr_planes: NULL or n_pairs * n_win * wy * wx floats; d_lag_out:
+ * n_pairs * n_win bytes, REQUIRED -- the effective lags, and the table the kernels read; d_shift_out: NULL or n_pairs * n_win * 2 int16,
+ * the clamped offsets (may be d_shift itself).  With every lag 1 and no offsets the result is lspiv_piv_shift_pairs_dev_at's without
+ * offsets bit for bit (not lspiv_piv_pairs_dev_at's: that is another kernel).  One window per job: a window's result depends on its own
+ * samples, lag and offset alone.  The adaptive form uses a per-device workspace: one stream at a time.
+ * lspiv_piv_lag_pairs_at: the host-fed twin -- all T frames are staged like lspiv_piv_pairs_at stages them (float64 narrowed to
+ * float32), lag / shift / lag_out / shift_out are host arrays of the same sizes (lag_out required, shift_out may be NULL).
+ *
+ * lspiv_lag_predict_dev: the lag predictor alone.  d_u, d_v: n_pairs * n_win float32 of a lag-1 pass on the grid (kernel orientation).
+ * Per pair t and window: valid = u and v finite; q = rint(64 x) (float32: the product is exact, the rint half to even) clamped to
+ * +-32767 * 64, for u and v; M2 = twice the median of q over the valid vectors of the 3 x 3 neighbourhood clipped at the grid's edges,
+ * centre included (even count: the sum of the two middle values; none: 0), in 1 / 128 px; mag = max(|M2u|, |M2v|); k = clamp(floor(
+ * target128 / max(mag, 1)), 1, k_max), then k = min(k, T - 1 - t); dx = floor((k M2u + 64) / 128), dy likewise; the frame clamp above.
+ * target128 = rint(128 * target in px), 1 .. 64 * window.  Exact integer arithmetic after the rint.  d_lag: n_pairs * n_win bytes,
+ * d_shift: n_pairs * n_win * 2 int16.  lspiv_lag_predict: the host-fed twin. */
+#define LSPIV_LAG_UNIFORM 0
+#define LSPIV_LAG_WINDOW 1
+#define LSPIV_LAG_TABLE 2
+#define LSPIV_LAG_ADAPTIVE 3
+int lspiv_lag_supported(int wy, int wx);
+int lspiv_piv_lag_pairs_dev_at(const void* d_frames, int dtype, int64_t T, int64_t n_pairs, int64_t H, int64_t W,
+                               int wy, int wx, int oy, int ox, float signal_threshold, int64_t pair_offset,
+                               int lag_form, int k, int target128, const uint8_t* d_lag, const int16_t* d_shift,
+                               float* d_out, float* d_corr_planes, uint8_t* d_lag_out, int16_t* d_shift_out, void* stream);
+int lspiv_piv_lag_pairs_at(const void* frames, int dtype, int64_t T, int64_t n_pairs, int64_t H, int64_t W,
+                           int wy, int wx, int oy, int ox, float signal_threshold, int64_t pair_offset,
+                           int lag_form, int k, int target128, const uint8_t* lag, const int16_t* shift,
+                           float* u, float* v, float* corr_max, float* s2n, float* corr_planes, uint8_t* lag_out, int16_t* shift_out);
+int lspiv_lag_predict_dev(const float* d_u, const float* d_v, int64_t n_pairs, int64_t T, int64_t H, int64_t W,
+                          int wy, int wx, int oy, int ox, int k_max, int target128, uint8_t* d_lag, int16_t* d_shift, void* stream);
+int lspiv_lag_predict(const float* u, const float* v, int64_t n_pairs, int64_t T, int64_t H, int64_t W,
+                      int wy, int wx, int oy, int ox, int k_max, int target128, uint8_t* lag, int16_t* shift);
 
 /* Window deformation passes (the project's own semantics, unpinned): after a chain, D passes on the FINAL grid,
  * each between frame t and frame t+1 WARPED by the field of the pass before it at 1 / 64 px, so that the pass measures a residual of

@@ -84,6 +84,13 @@ SIGNATURES = {
     "lspiv_piv_predict_shift_dev": (_i32, [_vp, _vp, _i64, _i64, _i64, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _vp, _vp]),
     "lspiv_piv_multipass_dev_at": (_i32, [_vp, _i32, _i64, _i64, _i64, _i32, _vp, _f32, _i64, _vp, _vp, _vp, _vp]),
     "lspiv_piv_multipass_at": (_i32, [_vp, _i32, _i64, _i64, _i64, _i32, _vp, _f32, _i64, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "lspiv_lag_supported": (_i32, [_i32, _i32]),
+    "lspiv_piv_lag_pairs_dev_at": (_i32, [_vp, _i32, _i64, _i64, _i64, _i64, _i32, _i32, _i32, _i32, _f32, _i64, _i32, _i32, _i32, _vp, _vp, _vp, _vp,
+                                          _vp, _vp, _vp]),
+    "lspiv_piv_lag_pairs_at": (_i32, [_vp, _i32, _i64, _i64, _i64, _i64, _i32, _i32, _i32, _i32, _f32, _i64, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp,
+                                      _vp, _vp, _vp, _vp]),
+    "lspiv_lag_predict_dev": (_i32, [_vp, _vp, _i64, _i64, _i64, _i64, _i32, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _vp]),
+    "lspiv_lag_predict": (_i32, [_vp, _vp, _i64, _i64, _i64, _i64, _i32, _i32, _i32, _i32, _i32, _i32, _vp, _vp]),
     "lspiv_deform_supported": (_i32, [_i32, _i32]),
     "lspiv_deform_required_bytes": (_i64, [_i64, _i64, _i64, _i32, _i32, _i32, _i32]),
     "lspiv_piv_predict_deform_dev": (_i32, [_vp, _vp, _i64, _i64, _i64, _vp, _vp]),
@@ -244,7 +251,7 @@ def load() -> C.CDLL:
     return lib
 
 
-KERNEL_SOURCES = ("piv_fft_impl.h", "fft_regs.h", "common.h", "piv_rescue.hip", "piv_multipass.hip")
+KERNEL_SOURCES = ("piv_fft_impl.h", "fft_regs.h", "common.h", "piv_rescue.hip", "piv_multipass.hip", "piv_predict.h", "piv_lag_impl.h")
 
 
 def _hash_files(paths) -> str:

@@ -207,6 +207,7 @@ static const Launcher kSpof[3] = {lspiv::launch_piv_spof16, lspiv::launch_piv_sp
 static const Launcher kSpofEnsemble[3] = {lspiv::launch_piv_spof_ensemble16, lspiv::launch_piv_spof_ensemble32, lspiv::launch_piv_spof_ensemble64};
 static const Launcher kDeform[3] = {lspiv::launch_piv_deform16, lspiv::launch_piv_deform32, lspiv::launch_piv_deform64};
 static const Launcher kShift[3] = {lspiv::launch_piv_shift16, lspiv::launch_piv_shift32, lspiv::launch_piv_shift64};
+static const Launcher kLag[3] = {lspiv::launch_piv_lag16, lspiv::launch_piv_lag32, lspiv::launch_piv_lag64};
 static const Launcher kShiftEnsemble[3] = {lspiv::launch_piv_shift_ensemble16, lspiv::launch_piv_shift_ensemble32, lspiv::launch_piv_shift_ensemble64};
 static const Launcher kSearch[3] = {lspiv::launch_piv_search16, lspiv::launch_piv_search32, lspiv::launch_piv_search64};
 
@@ -226,6 +227,10 @@ static int dispatch_kernels(const lspiv::PivParams& p, int dtype, bool ensemble,
   if (p.warped) {   // window deformation pass: the mixed-type per-pair kernels
     if (ensemble) return fail(LSPIV_EUNSUPPORTED, "ensemble mode has no deformation kernels");
     return by_size(kDeform, p, dtype, s);
+  }
+  if (p.lag) {   // per-window frame lag: the shifted job with window B cut from frame t + lag (piv_lag_impl.h), per pair
+    if (ensemble) return fail(LSPIV_EUNSUPPORTED, "ensemble mode has no lag kernels");
+    return by_size(kLag, p, dtype, s);
   }
   if (p.shifted)   // multi-pass mode: the shifted per-pair kernels; multi-pass ensemble: one owner per window sums the shifted planes over the chunk's pairs
     return by_size(ensemble ? kShiftEnsemble : kShift, p, dtype, s);
@@ -785,6 +790,93 @@ int lspiv_piv_predict_shift_dev(const float* d_u, const float* d_v, int64_t n_pa
   return launch_on(stream, [&](hipStream_t s) { return lspiv::launch_predict_shift(d_u, d_v, (uint32_t)n_pairs, (int)H, (int)W, cg, fg, d_shift, s); });
 }
 
+// ---- per-window frame lag (include/lspiv.h) ----------------------------------------------------------------
+int lspiv_lag_supported(int wy, int wx) { return fixed_square_ok(wy, wx) ? 1 : 0; }
+
+static int check_lag(int wy, int wx, int64_t H, int64_t W, int64_t T, int64_t n_pairs, int lag_form, int k, int target128, const void* lag_in,
+                     const void* shift_in) {
+  LSPIV_TRY(check_fixed_square(wy, wx, "a frame lag"));
+  LSPIV_TRY(check_frame_fits_int16(H, W, "the int16 offsets"));
+  LSPIV_TRY(check_pair_options("a frame lag"));
+  if (n_pairs < 1 || n_pairs > T - 1) return fail(LSPIV_ESHAPE, "n_pairs %lld not in 1 .. T - 1 = %lld", (long long)n_pairs, (long long)(T - 1));
+  if (lag_form < LSPIV_LAG_UNIFORM || lag_form > LSPIV_LAG_ADAPTIVE) return fail(LSPIV_EINVAL, "lag_form %d not in 0 .. 3", lag_form);
+  if ((lag_form == LSPIV_LAG_UNIFORM || lag_form == LSPIV_LAG_ADAPTIVE) && (k < 1 || k > lspiv::kMaxLag))
+    return fail(LSPIV_EINVAL, "lag %d not in 1 .. %d", k, lspiv::kMaxLag);
+  if ((lag_form == LSPIV_LAG_WINDOW || lag_form == LSPIV_LAG_TABLE) && !lag_in) return fail(LSPIV_EINVAL, "lag_form %d without a lag array", lag_form);
+  if (lag_form == LSPIV_LAG_ADAPTIVE) {
+    if (shift_in || lag_in) return fail(LSPIV_EINVAL, "the adaptive form predicts its own lags and offsets: d_lag and d_shift must be NULL");
+    if (target128 < 1 || target128 > 64 * wy) return fail(LSPIV_EINVAL, "target %d / 128 px not in (0, window / 2]", target128);
+  }
+  return LSPIV_OK;
+}
+
+// the pass itself on stream s: the table, the lag kernel + rescue pass (both write the residual of the frame pair (t, t + lag)), then the
+// offset is added and the sum divided by the lag.  p_lag1: the lag-1 pass of the adaptive form (d_out holds its field, overwritten here)
+static int lag_pass(DeviceCtx* c, const void* d_frames, int dtype, int64_t T, int64_t n_pairs, int64_t H, int64_t W, int wy, int wx, int oy, int ox,
+                    float signal_threshold, int64_t pair_offset, int lag_form, int k, int target128, const uint8_t* d_lag_in,
+                    const int16_t* d_shift_in, float* d_out, float* d_planes, uint8_t* d_lag_out, int16_t* d_shift_out, hipStream_t s) {
+  Grid g;
+  LSPIV_TRY(make_grid(H, W, wy, wx, oy, ox, &g));
+  lspiv::PivParams p;
+  LSPIV_TRY(fill_params(&p, d_frames, dtype, n_pairs + 1, H, W, wy, wx, oy, ox, signal_threshold, g));   // n_pairs pairs; the frames behind them are the lags'
+  p.pair_offset = pair_offset;
+  set_results(&p, d_out, p.n_tiles, 0, nullptr, 0);
+  const int16_t* shift = d_shift_in;
+  if (lag_form == LSPIV_LAG_ADAPTIVE) {
+    // pass 0: the plain per-timestep path at lag 1 on this grid (lspiv_piv_pairs_dev_at's launch, kernel orientation: no v_sign)
+    LSPIV_TRY(apply_signal_mode(c, &p, dtype, s));
+    LSPIV_TRY(dispatch(p, dtype, false, s));
+    int16_t* ws_shift = d_shift_out;
+    if (!ws_shift) {
+      LSPIV_TRY(ensure(&c->d_mp, &c->mp_cap, (size_t)p.n_tiles * 2 * sizeof(int16_t)));
+      ws_shift = static_cast<int16_t*>(c->d_mp);
+    }
+    lspiv::PassGrid pg;
+    LSPIV_TRY(pass_grid(H, W, wy, wx, oy, ox, &pg));
+    LSPIV_TRY(launch_status(lspiv::launch_lag_predict(p.u, p.v, p.n_pairs, T, (int)H, (int)W, pg, k, target128, d_lag_out, ws_shift, s)));
+    shift = ws_shift;
+  } else {
+    LSPIV_TRY(launch_status(lspiv::launch_lag_fill(lag_form, k, d_lag_in, p.n_pairs, p.n_win, T, d_lag_out, s)));
+  }
+  p.planes = d_planes;
+  p.shifted = 1;
+  p.shift = shift;
+  p.lag = d_lag_out;
+  LSPIV_TRY(dispatch(p, dtype, false, s));
+  LSPIV_TRY(launch_status(lspiv::launch_lag_divide(p, d_shift_out, s)));
+  return apply_v_sign(p.v, (int64_t)p.n_tiles, s);
+}
+
+int lspiv_piv_lag_pairs_dev_at(const void* d_frames, int dtype, int64_t T, int64_t n_pairs, int64_t H, int64_t W, int wy, int wx, int oy, int ox,
+                               float signal_threshold, int64_t pair_offset, int lag_form, int k, int target128, const uint8_t* d_lag,
+                               const int16_t* d_shift, float* d_out, float* d_corr_planes, uint8_t* d_lag_out, int16_t* d_shift_out,
+                               void* stream) {
+  LSPIV_TRY(check_dev_call(d_frames, d_out, pair_offset));
+  if (!d_lag_out) return fail(LSPIV_EINVAL, "d_lag_out is NULL");
+  LSPIV_TRY(check_lag(wy, wx, H, W, T, n_pairs, lag_form, k, target128, d_lag, d_shift));
+  DeviceCtx* c;
+  LSPIV_TRY(get_ctx(&c));
+  std::lock_guard<std::mutex> chain_lock(locks_here().multipass);   // (the adaptive form's offsets may live in the multi-pass workspace)
+  return lag_pass(c, d_frames, dtype, T, n_pairs, H, W, wy, wx, oy, ox, signal_threshold, pair_offset, lag_form, k, target128, d_lag, d_shift,
+                  d_out, d_corr_planes, d_lag_out, d_shift_out, on_stream(c, stream));
+}
+
+int lspiv_lag_predict_dev(const float* d_u, const float* d_v, int64_t n_pairs, int64_t T, int64_t H, int64_t W, int wy, int wx, int oy, int ox,
+                          int k_max, int target128, uint8_t* d_lag, int16_t* d_shift, void* stream) {
+  if (!d_u || !d_v || !d_lag || !d_shift) return fail(LSPIV_EINVAL, "NULL argument");
+  LSPIV_TRY(check_fixed_square(wy, wx, "a frame lag"));
+  LSPIV_TRY(check_frame_fits_int16(H, W, "the int16 offsets"));
+  if (n_pairs < 0 || n_pairs > T - 1) return fail(LSPIV_ESHAPE, "n_pairs %lld not in 0 .. T - 1 = %lld", (long long)n_pairs, (long long)(T - 1));
+  if (k_max < 1 || k_max > lspiv::kMaxLag) return fail(LSPIV_EINVAL, "k_max %d not in 1 .. %d", k_max, lspiv::kMaxLag);
+  if (target128 < 1 || target128 > 64 * wy) return fail(LSPIV_EINVAL, "target %d / 128 px not in (0, window / 2]", target128);
+  lspiv::PassGrid pg;
+  LSPIV_TRY(pass_grid(H, W, wy, wx, oy, ox, &pg));
+  if (n_pairs * (int64_t)pg.n_rows * pg.n_cols >= (int64_t)1 << 31) return fail(LSPIV_EINVAL, "too many windows for one launch (limit 2^31)");
+  return launch_on(stream, [&](hipStream_t s) {
+    return lspiv::launch_lag_predict(d_u, d_v, (uint32_t)n_pairs, T, (int)H, (int)W, pg, k_max, target128, d_lag, d_shift, s);
+  });
+}
+
 int lspiv_piv_multipass_dev_at(const void* d_frames, int dtype, int64_t T, int64_t H, int64_t W, int n_passes, const int* passes,
                                float signal_threshold, int64_t pair_offset, float* d_out, float* d_corr_planes, int16_t* d_shift_out, void* stream) {
   DeviceCtx* c;
@@ -920,6 +1012,76 @@ int lspiv_piv_multipass_deform_at(const void* frames, int dtype, int64_t T, int6
 int lspiv_piv_multipass_at(const void* frames, int dtype, int64_t T, int64_t H, int64_t W, int n_passes, const int* passes, float signal_threshold,
                            int64_t pair_offset, float* u, float* v, float* corr_max, float* s2n, float* corr_planes, int16_t* shift_out) {
   return multipass_host(frames, dtype, T, H, W, n_passes, passes, 0, signal_threshold, pair_offset, u, v, corr_max, s2n, corr_planes, shift_out);
+}
+
+// a lagged pass on a host stack: the T frames are staged first (a pair needs frames up to 16 on), the tables go up next to the results,
+// the pass runs, results, lags and clamped offsets come back
+int lspiv_piv_lag_pairs_at(const void* frames, int dtype, int64_t T, int64_t n_pairs, int64_t H, int64_t W, int wy, int wx, int oy, int ox,
+                           float signal_threshold, int64_t pair_offset, int lag_form, int k, int target128, const uint8_t* lag, const int16_t* shift,
+                           float* u, float* v, float* corr_max, float* s2n, float* corr_planes, uint8_t* lag_out, int16_t* shift_out) {
+  std::lock_guard<std::mutex> host_lock(locks_here().host);
+  if (!lag_out) return fail(LSPIV_EINVAL, "NULL buffer");
+  LSPIV_TRY(check_lag(wy, wx, H, W, T, n_pairs, lag_form, k, target128, lag, shift));
+  HostStack h;
+  LSPIV_TRY(host_stack(&h, frames, dtype, T, H, W, wy, wx, oy, ox, pair_offset, u, v, corr_max, s2n, corr_planes));
+  h.n_tiles = (size_t)n_pairs * h.n_win;   // (the workspaces above are sized for T - 1 pairs: never smaller)
+  DeviceCtx* c = h.c;
+  // behind the four result blocks, each 256-byte aligned: the lags handed out, the lags handed in, the offsets (in and out share one block)
+  const size_t out_bytes = (4 * h.n_tiles * sizeof(float) + 255) & ~(size_t)255;
+  const size_t lag_bytes = (h.n_tiles + 255) & ~(size_t)255;
+  LSPIV_TRY(ensure(&c->d_out, &c->out_cap, out_bytes + 2 * lag_bytes + h.n_tiles * 2 * sizeof(int16_t)));
+  uint8_t* d_lag_out = reinterpret_cast<uint8_t*>((char*)c->d_out + out_bytes);
+  uint8_t* d_lag_in = d_lag_out + lag_bytes;
+  int16_t* d_shift = reinterpret_cast<int16_t*>(d_lag_in + lag_bytes);
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  int batch = 0;
+  for (int64_t f0 = 0; f0 < T; ++batch) {
+    const int64_t f1 = std::min<int64_t>(T, f0 + h.frames_per_batch);
+    LSPIV_TRY(stage_frames(c, batch, c->d_frames, frames, dtype, h.src_pinned, h.frame_elems, f0, f1, signal_threshold));
+    f0 = f1;
+  }
+  HIP_TRY(hipStreamSynchronize(c->copy_stream));
+  const bool lag_up = lag_form == LSPIV_LAG_WINDOW || lag_form == LSPIV_LAG_TABLE;
+  if (lag_up) HIP_TRY(hipMemcpyAsync(d_lag_in, lag, lag_form == LSPIV_LAG_WINDOW ? h.n_win : h.n_tiles, hipMemcpyHostToDevice, c->stream));
+  if (shift) HIP_TRY(hipMemcpyAsync(d_shift, shift, h.n_tiles * 2 * sizeof(int16_t), hipMemcpyHostToDevice, c->stream));
+  int rc;
+  {
+    std::lock_guard<std::mutex> chain_lock(locks_here().multipass);
+    rc = lag_pass(c, c->d_frames, h.dev_dtype, T, n_pairs, H, W, wy, wx, oy, ox, signal_threshold, pair_offset, lag_form, k, target128,
+                  lag_up ? d_lag_in : nullptr, shift ? d_shift : nullptr, c->d_out, corr_planes ? c->d_planes : nullptr, d_lag_out, d_shift, c->stream);
+  }
+  if (rc != LSPIV_OK) { (void)hipStreamSynchronize(c->stream); return rc; }
+  LSPIV_TRY(results_to_host(h, u, v, corr_max, s2n, corr_planes, (size_t)wy * wx, shift_out, d_shift));
+  HIP_TRY(hipMemcpyAsync(lag_out, d_lag_out, h.n_tiles, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  return LSPIV_OK;
+}
+
+int lspiv_lag_predict(const float* u, const float* v, int64_t n_pairs, int64_t T, int64_t H, int64_t W, int wy, int wx, int oy, int ox, int k_max,
+                      int target128, uint8_t* lag, int16_t* shift) {
+  if (!u || !v || !lag || !shift) return fail(LSPIV_EINVAL, "NULL buffer");
+  Grid g;
+  LSPIV_TRY(make_grid(H, W, wy, wx, oy, ox, &g));
+  if (n_pairs < 0 || n_pairs > T - 1) return fail(LSPIV_ESHAPE, "n_pairs %lld not in 0 .. T - 1 = %lld", (long long)n_pairs, (long long)(T - 1));
+  const size_t n = (size_t)n_pairs * g.n_rows * g.n_cols;
+  if (n == 0) return LSPIV_OK;
+  const size_t fb = (n * sizeof(float) + 255) & ~(size_t)255, lb = (n + 255) & ~(size_t)255;
+  std::lock_guard<std::mutex> host_lock(locks_here().host);
+  DeviceCtx* c;
+  LSPIV_TRY(get_ctx(&c));
+  LSPIV_TRY(ensure(&c->d_out, &c->out_cap, 2 * fb + lb + n * 2 * sizeof(int16_t)));
+  float* d_u = c->d_out;
+  float* d_v = reinterpret_cast<float*>((char*)c->d_out + fb);
+  uint8_t* d_lag = reinterpret_cast<uint8_t*>((char*)c->d_out + 2 * fb);
+  int16_t* d_shift = reinterpret_cast<int16_t*>(d_lag + lb);
+  HIP_TRY(hipMemcpyAsync(d_u, u, n * sizeof(float), hipMemcpyHostToDevice, c->stream));
+  HIP_TRY(hipMemcpyAsync(d_v, v, n * sizeof(float), hipMemcpyHostToDevice, c->stream));
+  const int rc = lspiv_lag_predict_dev(d_u, d_v, n_pairs, T, H, W, wy, wx, oy, ox, k_max, target128, d_lag, d_shift, c->stream);
+  if (rc != LSPIV_OK) { (void)hipStreamSynchronize(c->stream); return rc; }
+  HIP_TRY(hipMemcpyAsync(lag, d_lag, n, hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(hipMemcpyAsync(shift, d_shift, n * 2 * sizeof(int16_t), hipMemcpyDeviceToHost, c->stream));
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  return LSPIV_OK;
 }
 
 int lspiv_piv_pairs_dev(const void* d_frames, int dtype, int64_t T, int64_t H, int64_t W, int wy, int wx, int oy,

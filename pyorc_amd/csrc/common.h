@@ -134,6 +134,11 @@ struct PivParams {
   float* peak2;
   int peak_excl;
   int peak2_v_neg;
+  // per-window frame lag (piv_lag_impl.h): lag != nullptr selects the lag kernels and the lagged branch of the
+  // rescue pass -- n_tiles bytes, result g's window B is cut from frame t + lag[g] (1 .. 16, t + lag[g] inside the stack: the fill
+  // kernel and the predictor of piv_lag_tables.hip write no other value) at the clamped offset of p.shift; u, v are the RESIDUAL of
+  // that frame pair, launch_lag_divide adds the offset and divides by the lag
+  const uint8_t* lag;
 };
 
 // The offset of result g = pair * n_win + window (shifted ensemble pass: g = window; grid row wrow, column wcol), clamped so that the shifted window stays inside
@@ -613,6 +618,21 @@ hipError_t launch_clamp_shift(const PivParams& p, int16_t* out, hipStream_t s);
 struct PassGrid { int wy, wx, sy, sx, n_rows, n_cols; };   // window, strides, grid
 hipError_t launch_predict_shift(const float* u, const float* v, uint32_t n_pairs, int H, int W, const PassGrid& coarse, const PassGrid& fine,
                                 int16_t* shift, hipStream_t s);
+// per-window frame lag: the shifted kernel's job with window B cut from frame t + p.lag[g] (piv_lag_impl.h);
+// n = p.wy = p.wx = 16 / 32 / 64, per-timestep mode only; u, v are the residual of that frame pair
+constexpr int kMaxLag = 16;
+hipError_t launch_piv_lag16(const PivParams& p, int dtype, hipStream_t s);
+hipError_t launch_piv_lag32(const PivParams& p, int dtype, hipStream_t s);
+hipError_t launch_piv_lag64(const PivParams& p, int dtype, hipStream_t s);
+// the lag tables (piv_lag_tables.hip).  n_frames = the frames the launch may read; pair t's lag is clipped to n_frames - 1 - t.
+// fill: lag[t * n_win + w] = clip(form 0: k | form 1: src[w] | form 2: src[t * n_win + w]) (src may be lag itself for form 2)
+hipError_t launch_lag_fill(int form, int k, const uint8_t* src, uint32_t n_pairs, uint32_t n_win, int64_t n_frames, uint8_t* lag, hipStream_t s);
+// predict: (u, v) of a lag-1 pass on the grid (kernel orientation) -> lag (1 .. k_max, clipped) and the clamped int16 offsets {dy, dx}
+hipError_t launch_lag_predict(const float* u, const float* v, uint32_t n_pairs, int64_t n_frames, int H, int W, const PassGrid& g, int k_max,
+                              int t128, uint8_t* lag, int16_t* shift, hipStream_t s);
+// after the rescue pass: u = (u + clamped dx) / lag, v = (v + clamped dy) / lag, one correctly rounded float32 division each;
+// shift_out: nullptr, or n_tiles x {dy, dx} that receive the clamped offsets (may be p.shift itself)
+hipError_t launch_lag_divide(const PivParams& p, int16_t* shift_out, hipStream_t s);
 // window deformation pass: the mixed-type kernels (p.warped, p.nodes; n = p.wy = p.wx = 16 / 32 / 64; u, v are
 // the residual), the node predictor (u, v of a pass -> int32 nodes {v, u} in 1 / 128 px on the same grid), the warp of every pair's
 // frame t+1 into p.warped, and u += nodes.u / 128, v += nodes.v / 128 after the rescue pass (piv_multipass.hip)

@@ -962,10 +962,12 @@ __device__ __forceinline__ void cross_spectrum_half(int partner_byte, const floa
 // register = column x;  skip[k] = plane k is NaN (signal pre-mask / non-finite input).
 // SHIFT (multi-pass mode): the plain pair, but frame t+1's window sits at the window's own clamped offset (window_shift), ONE window per job
 // SHIFT_WIN (shifted ensemble pass): the offsets are one field for every pair of the run, indexed by the window alone
-template <typename T, int N, bool WANT_NZ, bool EMBED = false, bool SEARCH = false, bool SHIFT = false, bool SHIFT_WIN = false>
+// LAG (per-window frame lag, piv_lag_impl.h; with SHIFT): frame t+1 becomes frame t + p.lag[g], one byte per result
+template <typename T, int N, bool WANT_NZ, bool EMBED = false, bool SEARCH = false, bool SHIFT = false, bool SHIFT_WIN = false, bool LAG = false>
 __device__ __forceinline__ void correlate_job(const PivParams& p, const TileRef (&t)[2], float* buf, int lg,
                                               int partner_byte, float (&xr)[N], float (&xi)[N], bool (&skip)[2],
                                               float (&mean)[2]) {
+  static_assert(!LAG || (SHIFT && !SHIFT_WIN), "a lag is a property of the per-pair shifted job");
   constexpr int H = N / 2;
   float R1r[H + 1], R1i[H + 1];  // s1 * 4 conj(A1) B1, ky = 0..N/2 (Hermitian half)
   float hi[2];                   // clip ceiling: 1, or 0 for a zero-variance window (plane exactly 0)
@@ -981,6 +983,7 @@ __device__ __forceinline__ void correlate_job(const PivParams& p, const TileRef 
     if constexpr (SHIFT) {   // the only new work of the shifted kernel: the address of frame t+1's rows
       const WinShift ws = window_shift(p, SHIFT_WIN ? t[k].win : t[k].pair * p.n_win + t[k].win, wrow, wcol);
       offb += (int64_t)ws.dy * p.W + ws.dx;
+      if constexpr (LAG) offb += (int64_t)(p.lag[t[k].pair * p.n_win + t[k].win] - 1u) * p.frame_elems;
     }
     raw[k][0].fetch(frames + off);
     raw[k][1].fetch(frames + offb);
@@ -2769,6 +2772,8 @@ static hipError_t launch_search(const PivParams& p, int dtype, hipStream_t s) {
 // 16-point 52 - 55 | 57 - 69 | 61 - 74 VGPRs, 32-point 92 - 93 | 96 - 100 | 110 - 112, 64-point 184 - 186 | 184 - 206 | 201 - 208: inside the
 // bounds of piv_fft_kernel (kWavesPerSimd) at every size.  Float rows are loaded one window after the other (prepare_pair, SEQ): both rows
 // of 64 float64 samples in flight next to the signal score took 256 VGPRs and 32 - 40 bytes of scratch
+// (piv_lag_impl.h holds a copy of this body with LAG set: a shared __device__ body was tried and moved 92 instruction lines of the 32-point
+// shifted unit, so the copy stays -- a fix here belongs there too.)
 template <typename T, int N, bool PLANES, bool WANT_NZ>
 __global__ __launch_bounds__(BLOCK, (kWavesPerSimd<T, N>)) void piv_fft_shift_kernel(PivParams p) {
   extern __shared__ __attribute__((aligned(16))) float smem[];

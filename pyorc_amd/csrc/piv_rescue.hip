@@ -285,7 +285,8 @@ __device__ __forceinline__ const T* window_base(const PivParams& p, uint32_t g) 
   return static_cast<const T*>(p.frames) + ((int64_t)pair * p.H + (int64_t)wrow * p.sy) * p.W + (int64_t)wcol * p.sx;
 }
 
-// the window of frame t+1 of result g: one frame on, and -- multi-pass mode -- at the window's clamped offset (common.h, window_shift).
+// the window of frame t+1 of result g: one frame on (p.lag[g] frames on in a lagged launch), and -- multi-pass mode and lagged launches -- at
+// the window's clamped offset (common.h, window_shift).
 // (The ensemble's partial sums below index the offsets by the window alone: a shifted ensemble pass has one field for every pair.)
 template <typename T>
 __device__ __forceinline__ const T* window_base_b_frames(const PivParams& p, uint32_t g, const T* A);
@@ -303,7 +304,7 @@ __device__ __forceinline__ const TB* window_base_b(const PivParams& p, uint32_t 
 }
 template <typename T>
 __device__ __forceinline__ const T* window_base_b_frames(const PivParams& p, uint32_t g, const T* A) {
-  const T* B = A + p.frame_elems;
+  const T* B = A + (p.lag ? (int64_t)p.lag[g] : (int64_t)1) * p.frame_elems;   // (a lagged launch, INTEGRATION.md section 2k: frame t + lag[g])
   if (p.shift) {
     const uint32_t pair = g / p.n_win, win = g - pair * p.n_win;
     const uint32_t wrow = win / (uint32_t)p.n_cols, wcol = win - wrow * (uint32_t)p.n_cols;

@@ -82,6 +82,10 @@ def get_piv(frames, window_size=None, overlap=None, engine: str = "hip", ensembl
     ``validate`` (in ``**kwargs``): True or a dict of ``validate.median_test``'s keywords -- the normalised median test on the
     displacement in pixels, on the device, before the scaling; the result gains the uint8 variable ``flag`` and, with
     ``peak_ratio=True``, rejected vectors are replaced by their runner-up where that one passes.  Per-timestep mode, no chain of passes.
+    ``pair_step`` / ``pair_step_max`` / ``pair_step_target`` (in ``**kwargs``): multi-frame PIV for slow flow -- a lag
+    of k frames for every window, a lag per window ``(rows, cols)``, or ``"adaptive"`` (a lag-1 pass picks each window's lag, at most
+    ``pair_step_max``, so that it moves about ``pair_step_target`` px); velocities stay per frame interval and the result gains the
+    uint8 variable ``pair_step``.  Windows of 16, 32 or 64 px, per-timestep mode, materialised stacks on one device.
     """
     if engine not in ENGINES:
         raise ValueError(f"Selected PIV engine {engine} does not exist.")

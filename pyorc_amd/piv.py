@@ -101,7 +101,7 @@ def _per_window_input(name, value, grid, dtype):
 
 
 def _run_pairs(imgs, ws, ov, signal_threshold, return_planes, pair_offset, out, scale, entry, args, fused=False, extra=None, aux=None,
-               validate=None):
+               validate=None, aux2=None, pairs=None):
     """The body every per-pair entry point shares: stack -> grid -> ``out`` and ``scale`` checked -> results (and planes) allocated on the
     stack's side, host or HBM -> ONE library call -> results on the host -> scaling.  A mode supplies only what differs:
 
@@ -114,13 +114,15 @@ def _run_pairs(imgs, ws, ov, signal_threshold, return_planes, pair_offset, out, 
     ``extra(grid)``: the mode's extra input (mask, shift, nodes) for ``grid = (P, n_rows, n_cols)`` on the stack's side, an ndarray or a
     ``DeviceFrames``, or None;
     ``aux``: the dtype of a per-window output ``(P, n_rows, n_cols, 2)`` the call fills besides the results (the chain's offsets), or
-    ``(dtype, width)`` for another trailing width (the second peak's four floats);
+    ``(dtype, width)`` for another trailing width (the second peak's four floats); ``aux2``: a second such output (``c.aux2``; the lagged
+    pass hands out its lags and its clamped offsets), returned right after ``aux``;
+    ``pairs``: the call computes the first ``pairs`` pairs of the stack only (``c.pairs``; the frames behind them are a lagged pass's halo);
     ``validate``: a ``validate.ValidateSpec`` -- the median test on the displacement in pixels, between the
     library call and the scaling: ``lspiv_validate_dev`` on the block in HBM, ``lspiv_validate`` on the host arrays; with ``aux`` (only the
     second-peak mode passes both) the runner-up is offered for substitution.  A mode whose host entry point scales by itself must not be
     given one together with ``fused``.
 
-    Returns ``(u, v, corr_max, s2n[, planes][, aux][, flag])``."""
+    Returns ``(u, v, corr_max, s2n[, planes][, aux][, aux2][, flag])``."""
     from .device import DeviceFrames
 
     lib = _lib.load()
@@ -130,7 +132,9 @@ def _run_pairs(imgs, ws, ov, signal_threshold, return_planes, pair_offset, out, 
     n_rows, n_cols = window.get_array_shape((H, W), ws, ov)
     if T < 2 or n_rows < 1 or n_cols < 1:
         raise ValueError(f"need >= 2 frames at least one window large, got {a.shape} for window {ws}")
-    P, n_win = T - 1, n_rows * n_cols
+    P, n_win = T - 1 if pairs is None else int(pairs), n_rows * n_cols
+    if not 1 <= P <= T - 1:
+        raise ValueError(f"pairs must lie in 1 .. {T - 1} for a stack of {T} frames, got {pairs!r}")
     if out is not None:
         out = _check_out(out, (P, n_rows, n_cols))
     dt = _check_scale(scale, return_planes, P)
@@ -139,18 +143,21 @@ def _run_pairs(imgs, ws, ov, signal_threshold, return_planes, pair_offset, out, 
     if aux is not None:
         aux_dtype, aux_width = aux if isinstance(aux, tuple) else (aux, 2)
         aux = np.empty((P, n_rows, n_cols, aux_width), dtype=aux_dtype)
+    if aux2 is not None:
+        aux2 = np.empty((P, n_rows, n_cols, aux2[1]), dtype=aux2[0])
     if dev:   # HBM-resident stack: no staging, one call, only the result block crosses PCIe
         res = DeviceFrames.empty((4, P, n_win), np.float32)
         planes = DeviceFrames.empty((P * n_win, ws[0], ws[1]), np.float32) if return_planes else None
         d_aux = DeviceFrames.empty((1, 1, aux.nbytes), np.uint8) if aux is not None else None
+        d_aux2 = DeviceFrames.empty((1, 1, aux2.nbytes), np.uint8) if aux2 is not None else None
         frames, res_ptrs, ptr = (a.c_ptr, a.dtype_code), (res.c_ptr,), lambda q: None if q is None else q.c_ptr
     else:
         res = out if out is not None else [np.empty((P, n_rows, n_cols), dtype=np.float32) for _ in range(4)]
         planes = np.empty((P, n_win, ws[0], ws[1]), dtype=np.float32) if return_planes else None
-        d_aux = aux
+        d_aux, d_aux2 = aux, aux2
         frames, res_ptrs, ptr = (_lib.ptr(a), _lib.DTYPE_CODES[a.dtype]), tuple(_lib.ptr(r) for r in res), lambda q: None if q is None else _lib.ptr(q)
-    c = SimpleNamespace(frames=(*frames, T, H, W), at=(_sig(signal_threshold), int(pair_offset)), res=res_ptrs, planes=ptr(planes),
-                        extra=ptr(x), aux=ptr(d_aux), dt=None if dt is None else _lib.ptr(dt))
+    c = SimpleNamespace(frames=(*frames, T, H, W), pairs=P, at=(_sig(signal_threshold), int(pair_offset)), res=res_ptrs, planes=ptr(planes),
+                        extra=ptr(x), aux=ptr(d_aux), aux2=ptr(d_aux2), dt=None if dt is None else _lib.ptr(dt))
     _lib.check(getattr(lib, entry[dev])(*args(c), *((None,) if dev else ())))
     flag = None
     if validate is not None:
@@ -171,10 +178,13 @@ def _run_pairs(imgs, ws, ov, signal_threshold, return_planes, pair_offset, out, 
             planes = planes.to_host().reshape(P, n_win, ws[0], ws[1])
         if aux is not None:
             _lib.check(lib.lspiv_memcpy_d2h(_lib.ptr(aux), d_aux.c_ptr, aux.nbytes))
+        if aux2 is not None:
+            _lib.check(lib.lspiv_memcpy_d2h(_lib.ptr(aux2), d_aux2.c_ptr, aux2.nbytes))
     if dt is not None and not fused:
         for k in range(2):
             _to_velocity(res[k], scale[k], dt[:, None, None], out=res[k])
-    return (*res, *((planes,) if return_planes else ()), *((aux,) if aux is not None else ()), *((flag,) if flag is not None else ()))
+    return (*res, *((planes,) if return_planes else ()), *((aux,) if aux is not None else ()), *((aux2,) if aux2 is not None else ()),
+            *((flag,) if flag is not None else ()))
 
 
 # the window specs that carry a mode of their own through ``piv_pairs``: spec class -> (the keyword the messages name, that mode's call)
@@ -373,6 +383,85 @@ def piv_pairs_shifted(imgs, window_size=(32, 32), overlap=(16, 16), shift=None, 
     return _run_pairs(_device_stack(imgs, signal_threshold), ws, ov, signal_threshold, return_planes, pair_offset, None, None,
                       (None, "lspiv_piv_shift_pairs_dev_at"), lambda c: (*c.frames, *ws, *ov, *c.at, c.extra, *c.res, c.planes),
                       extra=lambda grid: None if shift is None else _per_window_input("shift", shift, grid, np.int16))
+
+
+def piv_pairs_lagged(imgs, window_size=(32, 32), overlap=(16, 16), pair_step=2, pair_step_max: int = 4, pair_step_target=None,
+                     signal_threshold: Optional[float] = None, return_planes: bool = False, pair_offset: int = 0, out=None, scale=None,
+                     pairs=None, return_shift: bool = False):
+    """Multi-frame PIV: per pair t and window the ``n x n`` window of frame t against the window of frame
+    ``t + k`` at an integer offset, the displacement divided by ``k`` -- for flow of a fraction of a pixel per frame interval, whose
+    relative error a lag of one frame leaves at tens of per cent.  ``pair_step``: a whole number ``k`` in 1 .. 16 (every window, zero
+    offsets); an integer array ``(rows, cols)`` of lags 1 .. 16 (zero offsets); or ``"adaptive"``: pass 0 is :func:`piv_pairs` at lag 1 on
+    the same grid, then an integer predictor picks per window the largest lag ``<= pair_step_max`` (1 .. 16) that keeps the median
+    displacement of the 3 x 3 neighbourhood at or below ``pair_step_target`` px (default ``n / 4``; ``0 < target <= n / 2``) and the
+    integer offset that goes with it.  Every lag is clipped to the frames left: ``k[t] <= T - 1 - t``.  Returns ``(u, v, corr_max, s2n,
+    lag[, planes][, shift])``: u, v in px per frame interval, ``lag`` uint8 ``(P, rows, cols)`` the effective lags, ``shift`` int16 ``(P,
+    rows, cols, 2)`` the clamped offsets ``(dy, dx)`` with ``return_shift``.  A whole number 1 is :func:`piv_pairs` bit for bit plus the
+    all-ones ``lag``; an all-ones ARRAY runs the lag kernel and gives :func:`piv_pairs_shifted`'s bits without offsets.  ``n`` in 16, 32,
+    64.  ``pairs``: compute only the first ``pairs`` pairs of ``imgs``; the frames behind them serve the lags (a chunk of a longer stack
+    with its halo of ``min(largest lag, frames to the end of the stack)`` frames then gives the bits of the whole stack's call; the
+    adaptive form's pass 0 needs chunks cut on ``window.chunk_alignment`` as :func:`piv_pairs` does).  ``out`` / ``scale`` as in
+    :func:`piv_pairs` (numpy's arithmetic on the host).  Host stacks and ``DeviceFrames``."""
+    a = imgs if is_device(imgs) else _lib.as_frames(imgs)
+    ov = (int(overlap[0]), int(overlap[1]))
+    ws0 = (int(window_size[0]), int(window_size[1]))
+    grid = window.get_array_shape(a.shape[1:], ws0, ov)
+    spec = window.lag_spec(pair_step, ws0, grid, pair_step_max, pair_step_target)   # ValueError: sizes, ranges, the array's shape
+    if spec is None:   # a lag of one frame: today's path
+        if pairs is None:
+            ret = piv_pairs(a, ws0, ov, signal_threshold, return_planes, pair_offset, out=out, scale=scale)
+        else:          # the plain entry points on the first pairs + 1 frames
+            ret = _run_pairs(a, ws0, ov, signal_threshold, return_planes, pair_offset, out, scale, ("lspiv_piv_pairs_at", "lspiv_piv_pairs_dev_at"),
+                             lambda c: (*c.frames[:2], c.pairs + 1, *c.frames[3:], *ws0, *ov, *c.at, *c.res, c.planes), fused=is_device(a),
+                             pairs=pairs)
+        lag = np.ones(ret[0].shape, dtype=np.uint8)
+        return (*ret[:4], lag, *ret[4:], *((np.zeros((*lag.shape, 2), dtype=np.int16),) if return_shift else ()))
+    ws = window.lag_supported(ws0)
+
+    def lags(grid3):
+        if spec.array is None:
+            return None
+        if not is_device(a):
+            return spec.array
+        from .device import DeviceFrames
+
+        d = DeviceFrames.empty((1, 1, spec.array.nbytes), np.uint8)
+        _lib.check(_lib.load().lspiv_memcpy_h2d(d.c_ptr, _lib.ptr(spec.array), spec.array.nbytes))
+        return d
+
+    ret = _run_pairs(a, ws, ov, signal_threshold, return_planes, pair_offset, out, scale,
+                     ("lspiv_piv_lag_pairs_at", "lspiv_piv_lag_pairs_dev_at"),
+                     lambda c: (*c.frames[:3], c.pairs, *c.frames[3:], *ws, *ov, *c.at, spec.form, spec.k, spec.target128, c.extra, None, *c.res,
+                                c.planes, c.aux, c.aux2),
+                     extra=lags, aux=(np.uint8, 1), aux2=(np.int16, 2), pairs=pairs)
+    lag, shift = ret[-2][..., 0], ret[-1]
+    return (*ret[:4], np.ascontiguousarray(lag), *ret[4:-2], *((shift,) if return_shift else ()))
+
+
+def predict_lag(u, v, dim_size, window_size, overlap, n_frames: int, pair_step_max: int = 4, pair_step_target=None):
+    """The lag predictor of ``pair_step="adaptive"`` alone, on the device: ``(u, v)`` ``(P, rows, cols)`` of a
+    lag-1 pass (kernel orientation: before any ``v_sign``) of a stack of ``n_frames`` frames -> ``(lag, shift)``, uint8 ``(P, rows,
+    cols)`` and int16 ``(P, rows, cols, 2)`` = (dy, dx) clamped to the frame: rint(64 x), twice the 3 x 3 median, the largest lag that
+    keeps it at or below the target, the offset at that lag -- exact integer arithmetic after the rint."""
+    lib = _lib.load()
+    _lib.require_device()
+    ov = (int(overlap[0]), int(overlap[1]))
+    ws = window.lag_supported(window_size)
+    spec = window.lag_spec("adaptive", ws, None, pair_step_max, pair_step_target)
+    H, W = int(dim_size[0]), int(dim_size[1])
+    rows, cols = window.get_array_shape((H, W), ws, ov)
+    uu = np.ascontiguousarray(u, dtype=np.float32).reshape(-1, rows, cols)
+    vv = np.ascontiguousarray(v, dtype=np.float32).reshape(-1, rows, cols)
+    if uu.shape != vv.shape:
+        raise ValueError(f"u {uu.shape} and v {vv.shape} differ")
+    P = uu.shape[0]
+    if P > int(n_frames) - 1:
+        raise ValueError(f"{P} pairs need at least {P + 1} frames, got n_frames = {n_frames}")
+    lag = np.empty((P, rows, cols), dtype=np.uint8)
+    shift = np.empty((P, rows, cols, 2), dtype=np.int16)
+    _lib.check(lib.lspiv_lag_predict(_lib.ptr(uu), _lib.ptr(vv), P, int(n_frames), H, W, *ws, *ov, spec.k, spec.target128, _lib.ptr(lag),
+                                     _lib.ptr(shift)))
+    return lag, shift
 
 
 def predict_shift(u, v, dim_size, coarse, fine):

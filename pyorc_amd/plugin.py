@@ -134,6 +134,8 @@ def _wrap_get_piv(orig):
         second = {k: kwargs.pop(k) for k in ("peak_ratio", "peak_exclusion") if k in kwargs}
         # ... and the vector validation's `validate=`
         validate = kwargs.pop("validate", None)
+        # ... and the per-window frame lag's `pair_step=` / `pair_step_max=` / `pair_step_target=`
+        lagged = {k: kwargs.pop(k) for k in ("pair_step", "pair_step_max", "pair_step_target") if k in kwargs}
         engine, bound = kwargs.get("engine"), None
         if sig is not None and "engine" in sig.parameters:
             try:
@@ -158,6 +160,8 @@ def _wrap_get_piv(orig):
                 raise TypeError(f"{' / '.join(second)} is a keyword of engine='hip' only")
             if validate is not None:
                 raise TypeError("validate is a keyword of engine='hip' only")
+            if lagged:
+                raise TypeError(f"{' / '.join(lagged)} is a keyword of engine='hip' only")
             return orig(self, *args, **kwargs)
         # fail before any work if there is no MI355X / no library: the reference raises ValueError for an engine it cannot run
         from . import _lib
@@ -188,6 +192,8 @@ def _wrap_get_piv(orig):
 
             if validate_mod.validate_spec(validate) is not None:                 # ValueError outside the ranges; None / False is today's path
                 extra["validate"] = validate
+        if lagged.get("pair_step") is not None:                                      # None is today's path
+            extra.update(lagged)
         if search_area is not None or sliding or extra:
             # the reference's method body lays the grid out by the window; with a search area of its own the engine's mirror of that
             # body (pyorc_amd.frames.get_piv: same configuration copy, coordinates, attributes and encoding) runs instead -- and with the

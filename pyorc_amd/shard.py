@@ -89,9 +89,16 @@ def _no_validate(validate) -> None:
                                   "instead, or run the validation through get_ffpiv (devices=)")
 
 
+def _no_pair_step(pair_step) -> None:
+    """A frame lag is not sharded over ranks: a rank's block of frames has ONE halo frame."""
+    if pair_step is not None and not (isinstance(pair_step, (int, np.integer)) and not isinstance(pair_step, bool) and int(pair_step) == 1):
+        raise NotImplementedError("pair_step with pyorc_amd.shard is not implemented: a rank's frame block carries one halo frame; run the "
+                                  "lagged correlation through get_ffpiv on one device")
+
+
 def sharded_piv(load_frames: Callable[[int, int], np.ndarray], n_pairs: int, window_size, overlap, comm,
                 compute: Optional[Callable] = None, signal_threshold=None, align: Optional[int] = None,
-                frame_shape=None, validate=None) -> np.ndarray:
+                frame_shape=None, validate=None, pair_step=None) -> np.ndarray:
     """Every rank computes its pair block and all ranks receive the full (4, n_pairs, n_rows, n_cols) block.
 
     ``load_frames(start, stop)`` returns frames [start, stop) as (T, H, W) -- each rank only ever touches its
@@ -102,6 +109,7 @@ def sharded_piv(load_frames: Callable[[int, int], np.ndarray], n_pairs: int, win
     """
     _no_multipass(window_size)
     _no_validate(validate)
+    _no_pair_step(pair_step)
     if compute is None:
         from . import piv
 
@@ -354,13 +362,14 @@ class ShardedPivDev:
 
 
 def sharded_piv_dev(block, n_pairs: int, window_size, overlap, comm, signal_threshold=None, align: Optional[int] = None,
-                    validate=None) -> np.ndarray:
+                    validate=None, pair_step=None) -> np.ndarray:
     """One sharded pass with the rank's frames already in HBM: ``block`` = DeviceFrames of this rank's ``frame_block`` (its
     pairs + the halo frame; a rank without pairs passes an empty ``(0, H, W)`` stack -- the frame shape is still needed for the
     exchange --, ``None`` raises ValueError).  Returns (4, n_pairs, n_rows, n_cols) on every rank --
     bit-identical to ``piv.piv_pairs`` over the whole stack on one GPU."""
     _no_multipass(window_size)
     _no_validate(validate)
+    _no_pair_step(pair_step)
     if block is None:
         raise ValueError("sharded_piv_dev needs this rank's DeviceFrames block (ranks without pairs pass an empty (0, H, W) stack)")
     plan = ShardedPivDev(comm, n_pairs, block.shape[1:], window_size, overlap, signal_threshold, align)

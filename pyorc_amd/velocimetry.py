@@ -185,6 +185,9 @@ def get_ffpiv(
     peak_ratio: bool = False,
     peak_exclusion: int = 2,
     validate=None,
+    pair_step=None,
+    pair_step_max: int = 4,
+    pair_step_target: Optional[float] = None,
 ):
     """Compute time-resolved (or ensemble) PIV on the MI355X; signature of pyorc's ``get_ffpiv`` (ffpiv.py:24-42).
 
@@ -261,6 +264,19 @@ def get_ffpiv(
     ``corr`` and ``s2n`` stay as they are.  Pair-local: ``chunksize=``, ``devices=``, host stacks, ``DeviceFrames`` and lazy stacks give the
     same bits.  With the plain path, ``search_area_size``, ``spectral_filter``, ``image_mask`` and ``peak_ratio``; not with
     ``ensemble_corr=True``, ``coarse_passes`` or ``deform_passes`` (NotImplementedError): ``validate.median_test`` on the result serves those.
+
+    ``pair_step`` (the project's own mode; None: today's path bit for bit): multi-frame PIV for slow flow --
+    pair t, window w is correlated against frame ``t + k[t, w]`` and the displacement divided by k, so ``v_x``, ``v_y`` keep their
+    meaning, the T - 1 outputs and the time axis stay, and the result gains the uint8 variable ``pair_step``, the effective lags.  A
+    whole number k in 1 .. 16 (1: today's path and its bits plus the all-ones variable); an integer array ``(rows, cols)`` of lags 1 ..
+    16; or ``"adaptive"``: a lag-1 pass, then per window the largest lag ``<= pair_step_max`` (1 .. 16, default 4) that keeps the median
+    displacement of its 3 x 3 neighbourhood at or below ``pair_step_target`` px (default window / 4, at most window / 2), with the
+    integer window offset that goes with it.  Every lag is clipped to the frames left in the stack.  Windows of 16, 32 or 64 px,
+    per-timestep mode, materialised stacks (numpy, ``DeviceFrames``) on one device; every chunk carries a halo of min(largest lag,
+    frames to the end of the stack) frames, and every chunking gives the same bits.  A lag multiplies the shear inside a window: where the
+    velocity changes by more than about 1 px per frame across a window, long lags hurt -- that is what ``pair_step_target`` is for.  Not
+    with ``ensemble_corr=True``, ``ensemble_window``, ``coarse_passes``, ``deform_passes``, ``spectral_filter``, ``image_mask``,
+    ``peak_ratio``, ``validate``, a search area larger than the window, lazy stacks or ``devices=`` (NotImplementedError).
     """
     if engine != "hip":
         raise ValueError(f"Selected PIV engine {engine} does not exist.")
@@ -275,6 +291,22 @@ def get_ffpiv(
         if (coarse_passes is not None and len(coarse_passes)) or window.deform_count(deform_passes):
             raise NotImplementedError("validate together with coarse_passes / deform_passes is not implemented: no validation runs between "
                                       "or after the passes of a chain; use validate.median_test on the result instead")
+    lag = window.lag_spec(pair_step, window_size, (len(y), len(x)), pair_step_max, pair_step_target)     # ValueError: sizes, ranges, shapes
+    if lag is not None:
+        return _get_ffpiv_lagged(frames, y, x, dt, window_size, overlap, search_area_size, res_y, res_x, chunksize, memory_factor, engine,
+                                 signal_threshold, time, devices, lag,
+                                 dict(ensemble_window=ensemble_window is not None, ensemble_corr=ensemble_corr,
+                                      coarse_passes=coarse_passes is not None and len(coarse_passes) > 0,
+                                      deform_passes=window.deform_count(deform_passes) > 0,
+                                      spectral_filter=window.spectral_filter_spec(spectral_filter) is not None,
+                                      image_mask=image_mask is not None, peak_ratio=peak_ratio, validate=validate is not None))
+    if pair_step is not None:     # a lag of one frame: today's path, and the variable that says so
+        res = get_ffpiv(frames, y, x, dt, window_size, overlap, search_area_size, res_y, res_x, chunksize, memory_factor, engine, ensemble_corr,
+                        corr_min, s2n_min, count_min, signal_threshold, time, prefetch, devices, ensemble_window, ensemble_stride,
+                        coarse_passes, deform_passes, spectral_filter, image_mask, mask_coverage_min, peak_ratio, peak_exclusion, validate)
+        if np.ndim(res["v_x"]) == 3:
+            _add_variable(res, "pair_step", np.ones(np.shape(res["v_x"]), dtype=np.uint8))
+        return res
     # a search area of its own: one window argument that answers for the search area wherever a grid, a plan or an alignment is asked for
     window_size = window.search_spec(window_size, search_area_size)
     flt = window.spectral_filter_spec(spectral_filter)     # ValueError for an unknown name
@@ -373,6 +405,74 @@ def get_ffpiv(
         return _run_resident(frames, work, sink, devs, time, signal_threshold)
     depth = (executor.default_depth() if prefetch is None else int(prefetch)) if hasattr(frames, "load") else 0
     return _run_chunks(frames, work, sink, depth, devs, time, window_size, overlap, (n_rows, n_cols))
+
+
+def _add_variable(res, name, values):
+    """One more (time, y, x) variable on a result of :func:`get_ffpiv`."""
+    if isinstance(res, PivResult):
+        res[name] = values
+    else:
+        res[name] = (["time", "y", "x"], values)
+
+
+def lagged_slices(slices, n_frames: int, halo: int):
+    """The frame slices ``[(a, b), ...]`` of :func:`aligned_slices` (pairs a .. b - 2, ONE halo frame) as lagged launches ``[(first pair,
+    pairs, end frame), ...]``: the same pairs, frames ``[a, end)`` with a halo of min(``halo``, frames to the end of the stack) frames
+    behind the last pair's frame t, so that no chunking changes a lag's clip."""
+    return [(a, b - 1 - a, min(b - 1 + int(halo), n_frames)) for a, b in slices]
+
+
+def _get_ffpiv_lagged(frames, y, x, dt, window_size, overlap, search_area_size, res_y, res_x, chunksize, memory_factor, engine, signal_threshold,
+                      time, devices, lag, others):
+    """``get_ffpiv`` with ``pair_step`` (INTEGRATION.md section 2k): one ``piv.piv_pairs_lagged`` call per chunk, every chunk with its halo;
+    the adaptive form's chunks are cut on the anchors of its lag-1 pass.  ``others``: which of the modes without a lagged form were asked for."""
+    why = {"ensemble_corr": "the ensemble kernels have no lagged form", "ensemble_window": "a sliding ensemble has no lagged form",
+           "coarse_passes": "a chain's shifted passes pair frame t with frame t+1", "deform_passes": "the deformation kernels have no lagged form",
+           "spectral_filter": "the filtered kernels have no lagged form", "image_mask": "the masked kernels have no lagged form",
+           "peak_ratio": "the second-peak kernels have no lagged form", "validate": "run validate.median_test on the result instead"}
+    for key, asked in others.items():
+        if asked:
+            raise NotImplementedError(f"pair_step together with {key}{'=True' if key in ('ensemble_corr', 'peak_ratio') else ''} is not "
+                                      f"implemented: {why[key]}")
+    ws, ov = window.lag_supported(window_size), (int(overlap[0]), int(overlap[1]))
+    if search_area_size is not None and tuple(int(q) for q in search_area_size) != ws:
+        raise NotImplementedError("pair_step together with a search_area_size larger than the window is not implemented: the lag kernels "
+                                  "correlate two windows of one size")
+    if devices is not None:
+        raise NotImplementedError("pair_step together with devices= is not implemented: the block cuts of several devices assume one halo frame")
+    if _is_lazy(frames):
+        raise NotImplementedError("pair_step with a lazy stack is not implemented: load the stack (numpy or DeviceFrames) first -- the "
+                                  "loaders' block cuts assume one halo frame")
+    n_frames, dim_size = len(frames), tuple(frames[0].shape)
+    dtype = frames.dtype if np.dtype(frames.dtype) in (np.dtype(np.uint8), np.dtype(np.float32)) else np.float64
+    n_pairs, grid = n_frames - 1, (len(y), len(x))
+    n_win = grid[0] * grid[1]
+    if tuple(window.get_array_shape(dim_size, ws, ov)) != grid:
+        raise ValueError(f"grid {tuple(window.get_array_shape(dim_size, ws, ov))} does not match coordinates {grid}")
+    dt_arr = np.asarray(_values(dt), dtype=np.float64)
+    if dt_arr.shape != (n_pairs,):
+        raise ValueError(f"dt must have one entry per frame pair ({n_pairs}), got shape {dt_arr.shape}")
+    if time is None:
+        time = frames["time"] if _is_xr(frames) else np.arange(n_frames)
+
+    def need(n):   # HBM bytes of a launch of n - 1 pairs with its halo, the tables and -- adaptive -- the lag-1 field (in the result block)
+        return window.lag_required_memory(n - 1, min(lag.halo, n_frames - 1), dim_size, ws, ov, dtype, lag)
+
+    avail = window.available_memory() / memory_factor
+    cs, _ = plan_chunks(n_frames, need(n_frames), avail, chunksize, engine, n_win=n_win)
+    align = window.chunk_alignment(ws, dim_size, ov) if lag.form == window.LAG_ADAPTIVE else 1
+    launches = lagged_slices(aligned_slices(n_frames, cs, align, n_win=n_win, fits=lambda n: need(n) <= avail), n_frames, lag.halo)
+    full = {k: np.empty((n_pairs, *grid), dtype=np.float32) for k in ("s2n", "corr", "v_x", "v_y")}
+    full["pair_step"] = np.empty((n_pairs, *grid), dtype=np.uint8)
+    for a, p, end in launches:
+        u, v, cm, sn, k = piv.piv_pairs_lagged(_values(load_frame_chunk(frames[a:end])), ws, ov, lag, signal_threshold=signal_threshold, pair_offset=a,
+                                               out=(full["v_x"][a:a + p], full["v_y"][a:a + p], full["corr"][a:a + p], full["s2n"][a:a + p]),
+                                               pairs=p)
+        _to_velocity(u, res_x, dt_arr[a:a + p, None, None], out=u)
+        _to_velocity(v, res_y, dt_arr[a:a + p, None, None], out=v)
+        full["pair_step"][a:a + p] = k
+    t = time[1:]
+    return _dataset(full, t, y, x, frames)
 
 
 def _run_ensemble_chain(frames, work, devices, time, spec, dim_size, y, x, dt, res_x, res_y, signal_threshold, corr_min, s2n_min, count_min,

@@ -349,6 +349,78 @@ def peak_ratio_spec(window_size, peak_ratio: bool = False, peak_exclusion: int =
     return PeakRatioWindow(peak2_supported(window_size), peak_exclusion)
 
 
+LAG_WINDOWS = (16, 32, 64)
+MAX_LAG = 16
+# the forms of ``pair_step`` as the C ABI numbers them (include/lspiv.h, LSPIV_LAG_*)
+LAG_UNIFORM, LAG_WINDOW, LAG_TABLE, LAG_ADAPTIVE = 0, 1, 2, 3
+
+
+class LagSpec:
+    """``pair_step`` checked: ``.form`` (``LAG_UNIFORM`` / ``LAG_WINDOW`` / ``LAG_ADAPTIVE``), ``.k`` (the
+    uniform lag, or ``pair_step_max`` of the adaptive form), ``.array`` (the per-window lags, uint8 ``(rows, cols)``, else None),
+    ``.target128`` (``rint(128 * pair_step_target)``, adaptive form) and ``.halo``: the largest lag a pair can get, i.e. how many
+    frames behind a chunk's last pair a launch needs (fewer at the end of the stack)."""
+
+    def __init__(self, form, k, array=None, target128=0):
+        self.form, self.k, self.array, self.target128 = form, k, array, target128
+        self.halo = int(array.max()) if array is not None else k
+
+
+def lag_supported(window_size) -> Tuple[int, int]:
+    """``window_size`` as a pair of ints when the lag kernels serve it (``lspiv_lag_supported``: square, 16, 32 or 64), else a ValueError
+    naming the sizes.  Host-only."""
+    ws = 2 * (window_size,) if isinstance(window_size, (int, np.integer)) else tuple(window_size)
+    if len(ws) != 2 or int(ws[0]) != int(ws[1]) or int(ws[0]) not in LAG_WINDOWS:
+        raise ValueError(f"window_size {window_size!r} is not supported with pair_step: the window must be square and one of {LAG_WINDOWS}")
+    return int(ws[0]), int(ws[1])
+
+
+def _whole(value, lo, hi, name):
+    if isinstance(value, bool) or not isinstance(value, (int, np.integer)) or not lo <= int(value) <= hi:
+        raise ValueError(f"{name} must be a whole number in {lo} .. {hi}, got {value!r}")
+    return int(value)
+
+
+def lag_spec(pair_step, window_size, grid=None, pair_step_max: int = 4, pair_step_target=None):
+    """``pair_step`` / ``pair_step_max`` / ``pair_step_target`` checked for the square window ``window_size`` and, for an array, the grid
+    ``(rows, cols)``: None for ``pair_step`` None or 1 (today's path), else a :class:`LagSpec`.  ValueError for a window other than 16,
+    32 or 64 px square, a lag outside 1 .. 16, an array of another shape or type, a target outside (0, window / 2].  Host-only."""
+    if isinstance(pair_step, LagSpec):
+        return pair_step
+    k_max = _whole(pair_step_max, 1, MAX_LAG, "pair_step_max")
+    if pair_step is None:
+        return None
+    what = f"pair_step must be a whole number in 1 .. {MAX_LAG}, an integer array (rows, cols) or 'adaptive', got "
+    if isinstance(pair_step, str):
+        if pair_step != "adaptive":
+            raise ValueError(what + repr(pair_step))
+        n = lag_supported(window_size)[0]
+        target = n / 4 if pair_step_target is None else pair_step_target   # the quarter rule
+        if isinstance(target, bool) or not isinstance(target, (int, float, np.integer, np.floating)) or not 0 < float(target) <= n / 2:
+            raise ValueError(f"pair_step_target must be a number in (0, {n / 2}] px (half the {n} px window), got {pair_step_target!r}")
+        t128 = int(np.rint(128.0 * float(target)))
+        if t128 < 1:
+            raise ValueError(f"pair_step_target {pair_step_target!r} is below 1 / 256 px")
+        return LagSpec(LAG_ADAPTIVE, k_max, None, t128)
+    if pair_step_target is not None:
+        raise ValueError("pair_step_target belongs to pair_step='adaptive'")
+    if isinstance(pair_step, (int, np.integer)) and not isinstance(pair_step, bool):
+        k = _whole(pair_step, 1, MAX_LAG, "pair_step")
+        if k == 1:
+            return None
+        lag_supported(window_size)
+        return LagSpec(LAG_UNIFORM, k)
+    arr = np.asarray(pair_step)
+    if arr.dtype == bool or not np.issubdtype(arr.dtype, np.integer) or arr.ndim != 2:
+        raise ValueError(what + (f"an array of {arr.dtype} {arr.shape}" if arr.ndim else repr(pair_step)))
+    lag_supported(window_size)
+    if grid is not None and arr.shape != tuple(grid):
+        raise ValueError(f"pair_step must have the grid's shape {tuple(grid)}, got {arr.shape}")
+    if arr.size == 0 or arr.min() < 1 or arr.max() > MAX_LAG:
+        raise ValueError(f"pair_step: every lag must lie in 1 .. {MAX_LAG}")
+    return LagSpec(LAG_WINDOW, 0, np.ascontiguousarray(arr, dtype=np.uint8))
+
+
 MIN_STEERING_GRID = 3
 
 
@@ -440,6 +512,15 @@ def required_memory(n_frames: int, dim_size, window_size, overlap, search_area_s
     if ensemble_sums:
         need += ensemble_sums_bytes(dim_size, sa, overlap)
     return need
+
+
+def lag_required_memory(n_pairs: int, halo: int, dim_size, window_size, overlap, dtype=np.uint8, spec=None) -> int:
+    """HBM bytes one lagged launch of ``n_pairs`` pairs with ``halo`` frames behind its last pair's frame t needs (INTEGRATION.md section
+    2k): the plain launch on ``n_pairs + halo`` frames (the frames, a result block that large -- never less than the launch's own, and the
+    block pass 0 of the adaptive form writes its field into --, the rescue lists) plus the two tables, one lag byte and two int16 per
+    window and pair."""
+    n_win = int(np.prod(get_array_shape(dim_size, window_size, overlap)))
+    return required_memory(int(n_pairs) + max(int(halo), 1), dim_size, tuple(window_size), overlap, dtype=dtype) + 5 * int(n_pairs) * n_win
 
 
 def deform_bytes(n_frames: int, dim_size, window_size, overlap) -> int:
