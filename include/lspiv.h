@@ -49,7 +49,8 @@ extern "C" {
                                * lspiv_piv_masked_pairs_dev_at / lspiv_piv_masked_pairs_at; the second correlation peak, lspiv_peak2_supported /
                                * lspiv_piv_peak2_pairs_dev_at / lspiv_piv_peak2_pairs_at / lspiv_second_peak_dev / lspiv_second_peak; vector validation,
                                * lspiv_validate_dev / lspiv_validate; the per-window frame lag, lspiv_lag_supported /
-                               * lspiv_piv_lag_pairs_dev_at / lspiv_piv_lag_pairs_at / lspiv_lag_predict_dev / lspiv_lag_predict)
+                               * lspiv_piv_lag_pairs_dev_at / lspiv_piv_lag_pairs_at / lspiv_lag_predict_dev / lspiv_lag_predict; frame stabilisation,
+                               * lspiv_stabilize_fit[_dev] / lspiv_stabilize_chain[_dev] / lspiv_warp_affine[_dev])
                                * 5 (round 6): lspiv_chunk_alignment(wy, wx) without a grid now returns the alignment that is right on EVERY grid (75
                                * where it returned 25: callers that cut chunks on it stay bit-reproducible on large grids); additions:
                                * lspiv_upload_frames, lspiv_trace / lspiv_trace_read; the host-pointer projection entry points no longer
@@ -813,6 +814,47 @@ int lspiv_validate_dev(float* d_u, float* d_v, const float* d_peak2, int64_t T, 
                        uint8_t* d_flag, void* stream);
 int lspiv_validate(float* u, float* v, const float* peak2, int64_t T, int64_t R, int64_t C,
                    float threshold, float epsilon, int min_neighbours, int replace, int iterations, uint8_t* flag);
+
+/* ---- Frame stabilisation (additions, no ABI version change) -------------------------------------------------
+ * Replaces pyorc/cv.py's stabilisation behind Video(stabilize=...) -- feature tracks on the banks, one transform per frame -- and the
+ * cv2.warpAffine it applies to every frame on the CPU.  The semantics are this project's own (unpinned against pyorc and OpenCV):
+ *   vectors  those of lspiv_piv_masked_pairs_dev_at under a static mask (non-zero = does not move in the world), window n x n; u column
+ *            shift, v row shift, rows downward (a caller under the "v_sign" option = 1 negates v first); a window's position is its
+ *            centre xc = col (n - ox) + (n - 1) / 2, yc = row (n - oy) + (n - 1) / 2.
+ *   fit      lspiv_stabilize_fit*: P_t (2 x 3, float64) of every pair with x_{t+1} = P_t (x_t, y_t, 1) for a static point, i.e.
+ *            (u, v) = (P - I)(x, y, 1), by least squares through the normal equations with float64 sums, coordinates relative to
+ *            ((W - 1) / 2, (H - 1) / 2) inside the fit.  model: translation (2 unknowns), similarity (4: u = a x - b y + c, v = b x + a y + d)
+ *            or affine (6).  Three rounds, each over a subset of the FINITE vectors: all; those within reject0 px of round 1's prediction;
+ *            those within reject1 px of round 2's.  A round with fewer than min_vectors vectors or a singular normal matrix (determinant
+ *            <= 1e-9 x the product of the matrix's diagonal) makes the pair's P the identity and n_used 0; else n_used = round 3's count.
+ *            u, v: (pairs, rows, cols) float32; (rows, cols) must be the grid of (H, W, n, oy, ox); n 16, 32 or 64; reject0 > reject1 > 0.
+ *            One launch for all pairs and all three rounds; the reduction order depends on the grid alone.
+ *   chain    lspiv_stabilize_chain*: A_0 = carry_in (NULL: the identity), [A_{t+1}; 0 0 1] = [P_t; 0 0 1] [A_t; 0 0 1], sequentially, every
+ *            product and sum a separately rounded float64 operation.  A: (pairs + 1, 2, 3); carry_out (may be NULL) = A_pairs.  A_t maps a
+ *            pixel of the reference frame (frame 0 of the run) to its position in frame t: the map the warp needs, nothing is inverted.
+ *            Cutting a run anywhere with a one-frame halo and carry_in = the pose at the chunk's first frame gives the same bits.
+ *   warp     lspiv_warp_affine*: out[t](y, x) = the bilinear sample of frames[t] at A_t (x, y, 1), OpenCV's fixed-point walk: with
+ *            xb = 64 (x / 64), x1 = x - xb: fX = ((A00 xb + A01 y + A02) + A00 x1) 32, every operation rounded on its own; NaN -> 0,
+ *            clipped to int32, round half to even; integer part X >> 5, fraction X & 31; Y alike.  LSPIV_U8: integer weights,
+ *            (acc + 2^14) >> 15; LSPIV_F32: the float32 weight table, added left to right.  A neighbour outside the frame counts as 0.
+ *            frames, out: (T, H, W), different buffers, sides up to 32767; A: (T, 2, 3) float64 (for the "_dev" call in HBM).
+ * "_dev" calls take device pointers and are asynchronous on `stream`: fit -> chain -> warp queue up without a host round trip.  The
+ * host twins upload, run the same kernels and download.  A bad argument is LSPIV_EINVAL with a message. */
+#define LSPIV_STABILIZE_TRANSLATION 0
+#define LSPIV_STABILIZE_SIMILARITY 1
+#define LSPIV_STABILIZE_AFFINE 2
+int lspiv_stabilize_fit_dev(const float* d_u, const float* d_v, int64_t pairs, int64_t rows, int64_t cols, int n, int oy, int ox,
+                            int64_t H, int64_t W, int model, double reject0, double reject1, int min_vectors,
+                            double* d_P, int32_t* d_n_used, void* stream);
+int lspiv_stabilize_fit(const float* u, const float* v, int64_t pairs, int64_t rows, int64_t cols, int n, int oy, int ox,
+                        int64_t H, int64_t W, int model, double reject0, double reject1, int min_vectors,
+                        double* P, int32_t* n_used);
+int lspiv_stabilize_chain_dev(const double* d_P, int64_t pairs, const double* d_carry_in, double* d_A, double* d_carry_out,
+                              void* stream);
+int lspiv_stabilize_chain(const double* P, int64_t pairs, const double* carry_in, double* A, double* carry_out);
+int lspiv_warp_affine_dev(const void* d_frames, int dtype, int64_t T, int64_t H, int64_t W, const double* d_A, void* d_out,
+                          void* stream);
+int lspiv_warp_affine(const void* frames, int dtype, int64_t T, int64_t H, int64_t W, const double* A, void* out);
 
 /* N4 -- on-disk packing of the result variables (pyorc/const.py:80-83: int16, scale_factor 0.01,
  * _FillValue -9999; arithmetic of xarray's encoder: float32 x / float32 scale, NaN -> fill, round half even). */

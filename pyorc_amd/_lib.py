@@ -169,6 +169,12 @@ SIGNATURES = {
     "lspiv_scale_velocity_dev": (_i32, [_vp, _i64, _i64, C.c_double, C.c_double, _vp, _vp]),
     "lspiv_validate_dev": (_i32, [_vp, _vp, _vp, _i64, _i64, _i64, _f32, _f32, _i32, _i32, _i32, _vp, _vp]),
     "lspiv_validate": (_i32, [_vp, _vp, _vp, _i64, _i64, _i64, _f32, _f32, _i32, _i32, _i32, _vp]),
+    "lspiv_stabilize_fit_dev": (_i32, [_vp, _vp, _i64, _i64, _i64, _i32, _i32, _i32, _i64, _i64, _i32, C.c_double, C.c_double, _i32, _vp, _vp, _vp]),
+    "lspiv_stabilize_fit": (_i32, [_vp, _vp, _i64, _i64, _i64, _i32, _i32, _i32, _i64, _i64, _i32, C.c_double, C.c_double, _i32, _vp, _vp]),
+    "lspiv_stabilize_chain_dev": (_i32, [_vp, _i64, _vp, _vp, _vp, _vp]),
+    "lspiv_stabilize_chain": (_i32, [_vp, _i64, _vp, _vp, _vp]),
+    "lspiv_warp_affine_dev": (_i32, [_vp, _i32, _i64, _i64, _i64, _vp, _vp, _vp]),
+    "lspiv_warp_affine": (_i32, [_vp, _i32, _i64, _i64, _i64, _vp, _vp]),
     "lspiv_pack_int16": (_i32, [_vp, _i64, _f32, _i32, _vp]),
     "lspiv_pack_int16_dev": (_i32, [_vp, _i64, _f32, _i32, _vp, _vp]),
     "lspiv_dev_malloc": (_i32, [C.POINTER(_vp), _sz]),
