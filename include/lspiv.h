@@ -50,7 +50,8 @@ extern "C" {
                                * lspiv_piv_peak2_pairs_dev_at / lspiv_piv_peak2_pairs_at / lspiv_second_peak_dev / lspiv_second_peak; vector validation,
                                * lspiv_validate_dev / lspiv_validate; the per-window frame lag, lspiv_lag_supported /
                                * lspiv_piv_lag_pairs_dev_at / lspiv_piv_lag_pairs_at / lspiv_lag_predict_dev / lspiv_lag_predict; frame stabilisation,
-                               * lspiv_stabilize_fit[_dev] / lspiv_stabilize_chain[_dev] / lspiv_warp_affine[_dev])
+                               * lspiv_stabilize_fit[_dev] / lspiv_stabilize_chain[_dev] / lspiv_warp_affine[_dev]; space-time image
+                               * velocimetry, lspiv_sti_gather[_dev] / lspiv_sti_orientation[_dev])
                                * 5 (round 6): lspiv_chunk_alignment(wy, wx) without a grid now returns the alignment that is right on EVERY grid (75
                                * where it returned 25: callers that cut chunks on it stay bit-reproducible on large grids); additions:
                                * lspiv_upload_frames, lspiv_trace / lspiv_trace_read; the host-pointer projection entry points no longer
@@ -855,6 +856,43 @@ int lspiv_stabilize_chain(const double* P, int64_t pairs, const double* carry_in
 int lspiv_warp_affine_dev(const void* d_frames, int dtype, int64_t T, int64_t H, int64_t W, const double* d_A, void* d_out,
                           void* stream);
 int lspiv_warp_affine(const void* frames, int dtype, int64_t T, int64_t H, int64_t W, const double* A, void* out);
+
+/* ---- Space-time image velocimetry, STIV (additions, no ABI version change) ----------------------------------
+ * The other standard method of image-based river gauging next to PIV (Fujita et al.; Fudaa-LSPIV, Hydro-STIV and RIVeR offer it; pyorc
+ * has none, so nothing is replaced and the semantics are this project's own, stated in float64 / float32 numpy by tests/stiv_ref.py):
+ * the brightness along a search line laid along the flow, sampled in every frame, is stacked into a space-time image, and the speed
+ * along the line is the orientation of the streaks in that image.
+ *   gather   lspiv_sti_gather*: sti[s, t_offset + t, i] (float32, (S, T_total, L)) = the bilinear sample of frame t at point (s, i).
+ *            points: (S, L, 2) float64 (x, y) in pixels, a HOST pointer in both forms (the entry point checks every point and prepares
+ *            the sample table once per call); L >= 3; every point finite with 0 <= x <= W - 1, 0 <= y <= H - 1, else LSPIV_EINVAL with
+ *            a message that names the point and its line.  ix = min(floor(x), W - 2), fx = float32(x - ix), y alike (x = W - 1 has
+ *            fx = 1: nothing outside the frame is read); with the neighbours a, b (row iy) and c, d (row iy + 1) as float32:
+ *            top = a + fx (b - a), bot = c + fx (d - c), value = top + fy (bot - top), every operation one correctly rounded float32
+ *            operation.  A NaN sample propagates.  frames: (T, H, W), LSPIV_U8 or LSPIV_F32, sides 2 .. 32767.  Only rows
+ *            [t_offset, t_offset + T) of sti are written: a video that goes through in chunks fills one space-time image, the same bits
+ *            as one call.  The host twin stages the frames in chunks.  The "_dev" form keeps its sample table in the context's scratch
+ *            buffer: calls that overlap in time share one stream (as with lspiv_normalize_dev).
+ *   orientation  lspiv_sti_orientation*: per line s and time window k = 0 .. K - 1, K = (T - time_window) / time_stride + 1, rows
+ *            k time_stride .. k time_stride + time_window - 1 of sti (S, T, L).  All arithmetic in float64 on the float32 samples.
+ *            detrend != 0: every column's mean over the window (summed with t ascending, divided by time_window) is taken off it.
+ *            Gradients by integer-tap separable filters, smooth = k in 0 .. 3 (k passes of the 3 x 3 binomial before a Sobel pair, the
+ *            common scale dropped): Gx = dx_k(i) (x) b_{2k+2}(t), Gt = b_{2k+2}(i) (x) dx_k(t), b_m the binomial row of order m,
+ *            dx_k = [-1, 0, 1] * b_{2k}; only positions whose whole (2k + 3) x (2k + 3) stencil lies inside the window count; L or
+ *            time_window below 2k + 3 is LSPIV_EINVAL.  tensor (S, K, 3) = (Jxx, Jtt, Jxt) = (sum Gx^2, sum Gt^2, sum Gx Gt), float64
+ *            sums in an order that depends on the shape alone.  With d = Jxx - Jtt, r = sqrt(d^2 + 4 Jxt^2): slope (S, K) =
+ *            -2 Jxt / (d + r), in samples per frame, positive from point 0 towards point L - 1 (the total-least-squares orientation in
+ *            its half-angle form); coherency (S, K) = r / (Jxx + Jtt).  A constant window or one with a NaN gives NaN for both.
+ * "_dev" calls take device pointers (except points) and are asynchronous on `stream`: gather -> orientation queue up without a host
+ * round trip.  The host twins upload, run the same kernels and download.  A bad argument is LSPIV_EINVAL with a message; nothing is
+ * launched then. */
+int lspiv_sti_gather_dev(const void* d_frames, int dtype, int64_t T, int64_t H, int64_t W, const double* points, int64_t S, int64_t L,
+                         float* d_sti, int64_t t_offset, int64_t T_total, void* stream);
+int lspiv_sti_gather(const void* frames, int dtype, int64_t T, int64_t H, int64_t W, const double* points, int64_t S, int64_t L,
+                     float* sti, int64_t t_offset, int64_t T_total);
+int lspiv_sti_orientation_dev(const float* d_sti, int64_t S, int64_t T, int64_t L, int64_t time_window, int64_t time_stride, int smooth,
+                              int detrend, double* d_tensor, double* d_slope, double* d_coherency, void* stream);
+int lspiv_sti_orientation(const float* sti, int64_t S, int64_t T, int64_t L, int64_t time_window, int64_t time_stride, int smooth,
+                          int detrend, double* tensor, double* slope, double* coherency);
 
 /* N4 -- on-disk packing of the result variables (pyorc/const.py:80-83: int16, scale_factor 0.01,
  * _FillValue -9999; arithmetic of xarray's encoder: float32 x / float32 scale, NaN -> fill, round half even). */

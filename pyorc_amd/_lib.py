@@ -175,6 +175,10 @@ SIGNATURES = {
     "lspiv_stabilize_chain": (_i32, [_vp, _i64, _vp, _vp, _vp]),
     "lspiv_warp_affine_dev": (_i32, [_vp, _i32, _i64, _i64, _i64, _vp, _vp, _vp]),
     "lspiv_warp_affine": (_i32, [_vp, _i32, _i64, _i64, _i64, _vp, _vp]),
+    "lspiv_sti_gather_dev": (_i32, [_vp, _i32, _i64, _i64, _i64, _vp, _i64, _i64, _vp, _i64, _i64, _vp]),
+    "lspiv_sti_gather": (_i32, [_vp, _i32, _i64, _i64, _i64, _vp, _i64, _i64, _vp, _i64, _i64]),
+    "lspiv_sti_orientation_dev": (_i32, [_vp, _i64, _i64, _i64, _i64, _i64, _i32, _i32, _vp, _vp, _vp, _vp]),
+    "lspiv_sti_orientation": (_i32, [_vp, _i64, _i64, _i64, _i64, _i64, _i32, _i32, _vp, _vp, _vp]),
     "lspiv_pack_int16": (_i32, [_vp, _i64, _f32, _i32, _vp]),
     "lspiv_pack_int16_dev": (_i32, [_vp, _i64, _f32, _i32, _vp, _vp]),
     "lspiv_dev_malloc": (_i32, [C.POINTER(_vp), _sz]),

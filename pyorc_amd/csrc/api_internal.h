@@ -198,6 +198,17 @@ int host_roundtrip(const char* name, const RoundTrip& io, Run&& run) {
   return LSPIV_OK;
 }
 
+// the tail of a host twin: the stream is waited for on every exit; the first error is the one reported
+inline int finish_host(const char* name, const char* step, hipError_t e, int rc, hipStream_t s) {
+  const hipError_t sync = hipStreamSynchronize(s);
+  if (e != hipSuccess || rc != LSPIV_OK) {
+    if (sync != hipSuccess) (void)hipGetLastError();
+    return rc != LSPIV_OK ? rc : fail(hip_code(e), "%s: %s failed: %s", name, step, hipGetErrorString(e));
+  }
+  if (sync != hipSuccess) return fail(hip_code(sync), "%s: synchronisation failed: %s", name, hipGetErrorString(sync));
+  return LSPIV_OK;
+}
+
 // ---- run-time options (api_core.hip: lspiv_set_option / lspiv_get_option, initial values from the environment) ---------------
 // the engine semantics that could not be pinned on a real ffpiv run, defaults = the oracle's reading
 extern std::atomic<int> g_opt_border;        // 0 NaN, 1 plane centre, 2 integer peak

@@ -40,17 +40,6 @@ int check_warp(const void* frames, int dtype, int64_t T, int64_t H, int64_t W, c
   return LSPIV_OK;
 }
 
-// the tail of a host twin: the stream is waited for on every exit; the first error is the one reported
-int finish_host(const char* name, const char* step, hipError_t e, int rc, hipStream_t s) {
-  const hipError_t sync = hipStreamSynchronize(s);
-  if (e != hipSuccess || rc != LSPIV_OK) {
-    if (sync != hipSuccess) (void)hipGetLastError();
-    return rc != LSPIV_OK ? rc : fail(hip_code(e), "%s: %s failed: %s", name, step, hipGetErrorString(e));
-  }
-  if (sync != hipSuccess) return fail(hip_code(sync), "%s: synchronisation failed: %s", name, hipGetErrorString(sync));
-  return LSPIV_OK;
-}
-
 }  // namespace
 
 }  // namespace lspiv_api
