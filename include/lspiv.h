@@ -51,7 +51,8 @@ extern "C" {
                                * lspiv_validate_dev / lspiv_validate; the per-window frame lag, lspiv_lag_supported /
                                * lspiv_piv_lag_pairs_dev_at / lspiv_piv_lag_pairs_at / lspiv_lag_predict_dev / lspiv_lag_predict; frame stabilisation,
                                * lspiv_stabilize_fit[_dev] / lspiv_stabilize_chain[_dev] / lspiv_warp_affine[_dev]; space-time image
-                               * velocimetry, lspiv_sti_gather[_dev] / lspiv_sti_orientation[_dev])
+                               * velocimetry, lspiv_sti_gather[_dev] / lspiv_sti_orientation[_dev]; pyramidal Lucas-Kanade point tracking,
+                               * lspiv_pyr_down[_dev] / lspiv_lk_track[_dev])
                                * 5 (round 6): lspiv_chunk_alignment(wy, wx) without a grid now returns the alignment that is right on EVERY grid (75
                                * where it returned 25: callers that cut chunks on it stay bit-reproducible on large grids); additions:
                                * lspiv_upload_frames, lspiv_trace / lspiv_trace_read; the host-pointer projection entry points no longer
@@ -893,6 +894,53 @@ int lspiv_sti_orientation_dev(const float* d_sti, int64_t S, int64_t T, int64_t 
                               int detrend, double* d_tensor, double* d_slope, double* d_coherency, void* stream);
 int lspiv_sti_orientation(const float* sti, int64_t S, int64_t T, int64_t L, int64_t time_window, int64_t time_stride, int smooth,
                           int detrend, double* tensor, double* slope, double* coherency);
+
+/* ---- Pyramidal Lucas-Kanade point tracking (additions, no ABI version change) ----------------------------------
+ * The third family of image-based river gauging next to PIV and STIV (KLT-IV, OTV, every OpenCV-based LSPTV script): the displacement
+ * of a small window around a point between two frames, refined from the coarsest level of a Gaussian pyramid down to the frame (Lucas &
+ * Kanade; the forward additive iteration of Bouguet).  Unpinned against OpenCV: the semantics are this project's own, stated in float32 /
+ * float64 numpy by tests/track_ref.py.
+ *   pyramid  lspiv_pyr_down*: out (T, (H + 1) / 2, (W + 1) / 2) float32 from frames (T, H, W), LSPIV_U8 or LSPIV_F32, sides 3 .. 32767.
+ *            Taps [1, 4, 6, 4, 1] along x on every source row, then along y; source index 2 x + j - 2 reflected without repeating the
+ *            edge (-1 -> 1, n -> n - 2); each pass ((a0 + a4) + 4 (a1 + a3)) + 6 a2, the result times 2^-8; every operation one correctly
+ *            rounded float32 operation.  NaN propagates.  Level 0 of a tracker's pyramid is the frame as float32, level l is pyr_down of
+ *            level l - 1; a level that pyr_down reads needs both sides >= 3, every level both >= 2.
+ *   tracker  lspiv_lk_track*: pairs (t, t + 1), t = 0 .. T - 2, of frames (T >= 2, H, W); N points (x, y) float64 per pair: points
+ *            (N, 2) for every pair (points_per_pair = 0) or (T - 1, N, 2) (points_per_pair != 0); guess: NULL (start at 0), or initial
+ *            (u, v) in pixels of the frame, shaped like points by guess_per_pair.  window: odd, 5 .. 31 (w, r = (w - 1) / 2); levels:
+ *            1 .. 5 (L; a stack too small for it is LSPIV_EINVAL with the level that fails); max_iter: 1 .. 100; eps >= 0; min_eig >= 0.
+ *            Sampling at level l: a position q = (qx, qy) (float64; the point is p 2^-l) has ix = floor(qx), fx = float32(qx - ix), y
+ *            alike; the sample at integer offset (i, j) has the neighbours at columns clamp(ix + j, 0, W_l - 1), clamp(ix + j + 1, 0,
+ *            W_l - 1) and rows alike (the level is edge replicated: nothing outside it is read); top = a + fx (b - a), bot = c + fx (d - c),
+ *            value = top + fy (bot - top), single float32 operations.
+ *            Per level, from L - 1 down to 0: the template I on the (w + 2)^2 patch around the point, Ix = 0.5f (I[i, j + 1] - I[i, j - 1]),
+ *            Iy alike; Gxx = sum Ix^2, Gyy = sum Iy^2, Gxy = sum Ix Iy over the w^2 window, exact float64 products, float64 sums in an
+ *            order that depends on w alone.  det = Gxx Gyy - Gxy Gxy, lambda = (Gxx + Gyy - sqrt((Gxx - Gyy)^2 + 4 Gxy^2)) / (2 w^2).  The
+ *            point is lost (status 2) unless det > 1e-9 Gxx Gyy and lambda >= min_eig.  Iterations: d starts at guess 2^-(L - 1) (or 0);
+ *            J on the window at q = p 2^-l + d, e = I - J (float32), bx = sum e Ix, by = sum e Iy, delta = ((Gyy bx - Gxy by) / det,
+ *            (Gxx by - Gxy bx) / det), every operation rounded on its own; d += delta; q outside [0, W_l - 1] x [0, H_l - 1] after the
+ *            update is status 3; stop when |delta|^2 < eps^2 or after max_iter iterations at this level; between levels d <- 2 d.
+ *            Outputs, (T - 1, N) each: u, v = d at level 0 (float64, pixels per frame); err = sum |I - J| / w^2 at the final d; min_eig =
+ *            lambda of level 0 (NaN if the point never got there); n_iter (int32): the iterations of all levels; status (uint8): 0
+ *            converged, 1 level 0 ended on max_iter (still a vector), 2 lost (see above), 3 walked out, 4 a sum that is not finite (a NaN
+ *            sample), 5 the point itself is not finite.  Status 2 .. 5 have NaN in u, v, err.
+ *            chain != 0 (a trajectory): points is (N, 2), the positions in frame 0, and xy (T, N, 2) is written: row 0 = points, row
+ *            t + 1 = row t + (u, v) of pair t, which is tracked from row t -- pair after pair in stream order inside the call, nothing
+ *            goes through the host; NaN once a point is lost.  The bits of T - 1 one-pair calls.
+ *            Levels >= 1 live in a workspace the library owns (at most 1 GiB; LSPIV_TRACK_WS_BYTES, a test hook, overrides the cap):
+ *            a longer run goes through it in batches of pairs with one frame of halo, the same bits.
+ * "_dev" calls take device pointers throughout (the points, the guess and xy as well) and are asynchronous on `stream`; calls that
+ * overlap in time share one stream (the workspace).  The host twins upload (the frames in chunks with one frame of halo), run the same
+ * kernels and download.  A bad argument is LSPIV_EINVAL with a message; nothing is launched then. */
+int lspiv_pyr_down_dev(const void* d_frames, int dtype, int64_t T, int64_t H, int64_t W, float* d_out, void* stream);
+int lspiv_pyr_down(const void* frames, int dtype, int64_t T, int64_t H, int64_t W, float* out);
+int lspiv_lk_track_dev(const void* d_frames, int dtype, int64_t T, int64_t H, int64_t W, const double* d_points, int64_t N,
+                       int points_per_pair, const double* d_guess, int guess_per_pair, int window, int levels, int max_iter, double eps,
+                       double min_eig, int chain, double* d_u, double* d_v, double* d_err, double* d_min_eig, int32_t* d_n_iter,
+                       uint8_t* d_status, double* d_xy, void* stream);
+int lspiv_lk_track(const void* frames, int dtype, int64_t T, int64_t H, int64_t W, const double* points, int64_t N, int points_per_pair,
+                   const double* guess, int guess_per_pair, int window, int levels, int max_iter, double eps, double min_eig, int chain,
+                   double* u, double* v, double* err, double* min_eig_out, int32_t* n_iter, uint8_t* status, double* xy);
 
 /* N4 -- on-disk packing of the result variables (pyorc/const.py:80-83: int16, scale_factor 0.01,
  * _FillValue -9999; arithmetic of xarray's encoder: float32 x / float32 scale, NaN -> fill, round half even). */

@@ -13,6 +13,7 @@ interfaces around it:
   pyorc_amd.validate                                   (median_test: the normalised median test on the result block, runner-up substitution)
   pyorc_amd.stabilize                                  (estimate / warp / stabilize: camera shake from PIV on the banks, every frame warped onto frame 0)
   pyorc_amd.stiv                                       (space_time_images / orientation / stiv / lines_across: space-time image velocimetry along search lines)
+  pyorc_amd.track                                      (track_pairs / track_grid / trajectories / pyr_down: pyramidal Lucas-Kanade point tracking, one wave per point and pair)
   pyorc_amd.executor                                   (chunk executor: lazy chunks are materialised ahead of the launches that consume them)
   pyorc_amd.plugin                                     (install(): engine="hip" inside an installed, unmodified pyorc -- called on import when pyorc is found)
 """
@@ -25,6 +26,7 @@ from ._lib import get_option, pinned_empty, set_option  # noqa: F401,E402
 from .device import DeviceFrames  # noqa: F401,E402
 from . import stabilize  # noqa: F401,E402
 from . import stiv  # noqa: F401,E402
+from . import track  # noqa: F401,E402
 from .plugin import install, uninstall  # noqa: F401,E402
 from . import plugin as _plugin  # noqa: E402
 

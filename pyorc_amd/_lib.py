@@ -179,6 +179,12 @@ SIGNATURES = {
     "lspiv_sti_gather": (_i32, [_vp, _i32, _i64, _i64, _i64, _vp, _i64, _i64, _vp, _i64, _i64]),
     "lspiv_sti_orientation_dev": (_i32, [_vp, _i64, _i64, _i64, _i64, _i64, _i32, _i32, _vp, _vp, _vp, _vp]),
     "lspiv_sti_orientation": (_i32, [_vp, _i64, _i64, _i64, _i64, _i64, _i32, _i32, _vp, _vp, _vp]),
+    "lspiv_pyr_down_dev": (_i32, [_vp, _i32, _i64, _i64, _i64, _vp, _vp]),
+    "lspiv_pyr_down": (_i32, [_vp, _i32, _i64, _i64, _i64, _vp]),
+    "lspiv_lk_track_dev": (_i32, [_vp, _i32, _i64, _i64, _i64, _vp, _i64, _i32, _vp, _i32, _i32, _i32, _i32, C.c_double, C.c_double, _i32, _vp, _vp, _vp,
+                                  _vp, _vp, _vp, _vp, _vp]),
+    "lspiv_lk_track": (_i32, [_vp, _i32, _i64, _i64, _i64, _vp, _i64, _i32, _vp, _i32, _i32, _i32, _i32, C.c_double, C.c_double, _i32, _vp, _vp, _vp, _vp,
+                              _vp, _vp, _vp]),
     "lspiv_pack_int16": (_i32, [_vp, _i64, _f32, _i32, _vp]),
     "lspiv_pack_int16_dev": (_i32, [_vp, _i64, _f32, _i32, _vp, _vp]),
     "lspiv_dev_malloc": (_i32, [C.POINTER(_vp), _sz]),
