@@ -871,8 +871,9 @@ int lspiv_warp_affine(const void* frames, int dtype, int64_t T, int64_t H, int64
  *            top = a + fx (b - a), bot = c + fx (d - c), value = top + fy (bot - top), every operation one correctly rounded float32
  *            operation.  A NaN sample propagates.  frames: (T, H, W), LSPIV_U8 or LSPIV_F32, sides 2 .. 32767.  Only rows
  *            [t_offset, t_offset + T) of sti are written: a video that goes through in chunks fills one space-time image, the same bits
- *            as one call.  The host twin stages the frames in chunks.  The "_dev" form keeps its sample table in the context's scratch
- *            buffer: calls that overlap in time share one stream (as with lspiv_normalize_dev).
+ *            as one call.  The host twin stages the frames in chunks (at most 256 MiB; LSPIV_HOST_CHUNK_BYTES, a test hook, overrides
+ *            it).  The "_dev" form keeps its sample table in the context's scratch buffer: calls that overlap in time share one
+ *            stream (as with lspiv_normalize_dev).
  *   orientation  lspiv_sti_orientation*: per line s and time window k = 0 .. K - 1, K = (T - time_window) / time_stride + 1, rows
  *            k time_stride .. k time_stride + time_window - 1 of sti (S, T, L).  All arithmetic in float64 on the float32 samples.
  *            detrend != 0: every column's mean over the window (summed with t ascending, divided by time_window) is taken off it.
@@ -930,8 +931,8 @@ int lspiv_sti_orientation(const float* sti, int64_t S, int64_t T, int64_t L, int
  *            Levels >= 1 live in a workspace the library owns (at most 1 GiB; LSPIV_TRACK_WS_BYTES, a test hook, overrides the cap):
  *            a longer run goes through it in batches of pairs with one frame of halo, the same bits.
  * "_dev" calls take device pointers throughout (the points, the guess and xy as well) and are asynchronous on `stream`; calls that
- * overlap in time share one stream (the workspace).  The host twins upload (the frames in chunks with one frame of halo), run the same
- * kernels and download.  A bad argument is LSPIV_EINVAL with a message; nothing is launched then. */
+ * overlap in time share one stream (the workspace).  The host twins upload (the frames in chunks of at most 256 MiB with one frame of halo;
+ * LSPIV_HOST_CHUNK_BYTES, a test hook, overrides the size), run the same kernels and download.  A bad argument is LSPIV_EINVAL with a message; nothing is launched then. */
 int lspiv_pyr_down_dev(const void* d_frames, int dtype, int64_t T, int64_t H, int64_t W, float* d_out, void* stream);
 int lspiv_pyr_down(const void* frames, int dtype, int64_t T, int64_t H, int64_t W, float* out);
 int lspiv_lk_track_dev(const void* d_frames, int dtype, int64_t T, int64_t H, int64_t W, const double* d_points, int64_t N,

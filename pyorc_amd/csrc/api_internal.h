@@ -1,5 +1,5 @@
 // What the host files of the C ABI share (api_*.hip): the error report, the per-device contexts and locks, the workspaces, the
-// trace spans, the run-time options and the helpers of the entry points.  Host logic only.  Everything here has hidden visibility:
+// trace spans, the staged call of the host twins (HostCall), the run-time options and the helpers of the entry points.  Host logic only.  Everything here has hidden visibility:
 // the library exports the lspiv_* entry points of include/lspiv.h, not these.
 #pragma once
 
@@ -9,10 +9,13 @@
 
 #include <atomic>
 #include <cstdint>
+#include <cstdlib>
+#include <initializer_list>
 #include <mutex>
 #include <vector>
 
 #include "common.h"
+#include "host_slots.h"
 #include "host_stage.h"
 #include "piv_peaks.h"
 #include "rescue_options.h"
@@ -162,51 +165,89 @@ int ensure(P** ptr, size_t* cap, size_t bytes) {
   return LSPIV_OK;
 }
 
-// The host-pointer row entry points (masks, filters, int16 packing): under the device's `host` lock, `in_bytes` of `in` go into the
-// context's d_frames and, if given, `aux_bytes` of `aux` into d_planes; run(d_frames, d_planes, stream) calls the "_dev" twin; then
-// `out_bytes` come back into `out` from d_planes, or from d_frames for a twin that works in place.  Pageable hipMemcpyAsync on the
-// context's stream, as before the pinned ring existed; once a copy is queued, every exit synchronises that stream.  A failed copy
-// is reported under `name`, the entry point's.
-struct RoundTrip {
-  const void* in; size_t in_bytes;
-  void* out; size_t out_bytes;
-  bool in_place = false;                              // the twin updates d_frames, which goes back (no output buffer)
-  const void* aux = nullptr; size_t aux_bytes = 0;    // a second input, into d_planes
-};
-template <class Run>
-int host_roundtrip(const char* name, const RoundTrip& io, Run&& run) {
-  std::lock_guard<std::mutex> host_lock(locks_here().host);
-  DeviceCtx* c;
-  LSPIV_TRY(get_ctx(&c));
-  LSPIV_TRY(ensure(&c->d_frames, &c->frames_cap, io.in_bytes));
-  LSPIV_TRY(ensure(&c->d_planes, &c->planes_cap, io.in_place ? io.aux_bytes : io.out_bytes));
-  const char* step = "upload";
-  hipError_t e = hipMemcpyAsync(c->d_frames, io.in, io.in_bytes, hipMemcpyHostToDevice, c->stream);
-  if (e == hipSuccess && io.aux) e = hipMemcpyAsync(c->d_planes, io.aux, io.aux_bytes, hipMemcpyHostToDevice, c->stream);
-  const int rc = e == hipSuccess ? run(c->d_frames, (void*)c->d_planes, c->stream) : LSPIV_OK;
-  if (e == hipSuccess && rc == LSPIV_OK) {
-    step = "download";
-    e = hipMemcpyAsync(io.out, io.in_place ? c->d_frames : (void*)c->d_planes, io.out_bytes, hipMemcpyDeviceToHost, c->stream);
-  }
-  // every exit from here waits for the stream: the caller's buffers are released only once its copies are done
-  const hipError_t sync = hipStreamSynchronize(c->stream);
-  if (e != hipSuccess || rc != LSPIV_OK) {   // the first error is the one reported
-    if (sync != hipSuccess) (void)hipGetLastError();
-    return rc != LSPIV_OK ? rc : fail(hip_code(e), "%s: %s failed: %s", name, step, hipGetErrorString(e));
-  }
-  if (sync != hipSuccess) return fail(hip_code(sync), "%s: synchronisation failed: %s", name, hipGetErrorString(sync));
-  return LSPIV_OK;
+// a byte count from the environment, read per call (test hooks); `dflt` when it is unset or no number
+inline size_t env_bytes(const char* name, size_t dflt) {
+  const char* e = std::getenv(name);
+  char* end = nullptr;
+  const unsigned long long v = e && *e ? std::strtoull(e, &end, 10) : 0;
+  return end && !*end ? (size_t)v : dflt;
 }
+// host frame stacks go up in chunks of at most this size (lspiv_sti_gather, lspiv_lk_track); LSPIV_HOST_CHUNK_BYTES (a test hook) overrides it
+inline size_t host_chunk_bytes() { return env_bytes("LSPIV_HOST_CHUNK_BYTES", (size_t)256 << 20); }
 
-// the tail of a host twin: the stream is waited for on every exit; the first error is the one reported
-inline int finish_host(const char* name, const char* step, hipError_t e, int rc, hipStream_t s) {
-  const hipError_t sync = hipStreamSynchronize(s);
-  if (e != hipSuccess || rc != LSPIV_OK) {
-    if (sync != hipSuccess) (void)hipGetLastError();
-    return rc != LSPIV_OK ? rc : fail(hip_code(e), "%s: %s failed: %s", name, step, hipGetErrorString(e));
+// ---- the host twins: one staged call ------------------------------------------------------------------------------------------
+// A host-pointer entry point checks its arguments, then stages through the context's workspaces under the device's `host` lock:
+//   HostCall hc({inputs}, {outputs});   the lock, the context, one slot per buffer (host_slots.h): inputs in d_frames, outputs in d_planes
+//   if (hc.upload()) hc.ran(launch(hc.in<T>(i) .., hc.out<T>(j) .., hc.stream()));   the input copies, then the "_dev" twin or its launcher
+//   return hc.finish(__func__);         the output copies if everything so far succeeded, the wait, the first error
+// Pageable hipMemcpyAsync on the context's stream, as before the pinned ring existed.  Once a copy is queued, every exit synchronises
+// that stream: the caller's buffers are released only once its copies are done.  A NULL host pointer is an optional argument that was
+// not given: no slot, no copy, a NULL device pointer.  An output with `in` >= 0 IS that input's slot (a twin that works in place).
+// `copy` = false: room only -- the chunked twins feed and drain such a slot themselves with copy_in / copy_out.
+struct HostIn { const void* host = nullptr; size_t bytes = 0; bool copy = true; };
+struct HostOut { void* host = nullptr; size_t bytes = 0; int in = -1; bool copy = true; };
+class HostCall {
+ public:
+  static constexpr int kMaxSlots = 8;
+  HostCall(std::initializer_list<HostIn> in, std::initializer_list<HostOut> out) : lock_(locks_here().host) {
+    size_t bytes[kMaxSlots], off[kMaxSlots];
+    bool present[kMaxSlots];
+    if ((rc_ = get_ctx(&c_)) != LSPIV_OK) return;
+    for (const HostIn& a : in) { bytes[n_in_] = a.bytes; present[n_in_] = a.host != nullptr; in_[n_in_++] = a; }
+    if ((rc_ = ensure(&c_->d_frames, &c_->frames_cap, slot_layout(bytes, present, n_in_, off))) != LSPIV_OK) return;
+    for (int i = 0; i < n_in_; ++i) d_in_[i] = present[i] ? (char*)c_->d_frames + off[i] : nullptr;
+    for (const HostOut& a : out) { bytes[n_out_] = a.bytes; present[n_out_] = a.host != nullptr && a.in < 0; out_[n_out_++] = a; }
+    if ((rc_ = ensure(&c_->d_planes, &c_->planes_cap, slot_layout(bytes, present, n_out_, off))) != LSPIV_OK) return;
+    for (int i = 0; i < n_out_; ++i) d_out_[i] = out_[i].in >= 0 ? d_in_[out_[i].in] : present[i] ? (char*)c_->d_planes + off[i] : nullptr;
   }
-  if (sync != hipSuccess) return fail(hip_code(sync), "%s: synchronisation failed: %s", name, hipGetErrorString(sync));
-  return LSPIV_OK;
+  template <class T = void> T* in(int i) const { return (T*)d_in_[i]; }
+  template <class T = void> T* out(int i) const { return (T*)d_out_[i]; }
+  DeviceCtx* ctx() const { return c_; }
+  hipStream_t stream() const { return c_->stream; }
+  bool ok() const { return e_ == hipSuccess && rc_ == LSPIV_OK; }
+  // the status of what the caller ran on stream() -- the first failure is kept; true while everything succeeded
+  bool ran(int rc) { if (rc_ == LSPIV_OK) rc_ = rc; return ok(); }
+  // one copy on the stream, skipped after a failure (device to device: `step` as it stands)
+  bool copy(void* dst, const void* src, size_t bytes, hipMemcpyKind kind, const char* step = nullptr) {
+    if (ok()) { if (step) step_ = step; queued_ = true; e_ = hipMemcpyAsync(dst, src, bytes, kind, c_->stream); }
+    return ok();
+  }
+  bool copy_in(void* dst, const void* src, size_t bytes) { return copy(dst, src, bytes, hipMemcpyHostToDevice, "upload"); }
+  bool copy_out(void* dst, const void* src, size_t bytes) { return copy(dst, src, bytes, hipMemcpyDeviceToHost, "download"); }
+  bool upload() {
+    for (int i = 0; i < n_in_; ++i) if (d_in_[i] && in_[i].copy && in_[i].bytes) copy_in(d_in_[i], in_[i].host, in_[i].bytes);
+    return ok();
+  }
+  int finish(const char* name) {
+    for (int i = 0; i < n_out_; ++i) if (out_[i].host && out_[i].copy && out_[i].bytes) copy_out(out_[i].host, d_out_[i], out_[i].bytes);
+    if (!queued_) return rc_;   // nothing of the caller's is in flight
+    const hipError_t sync = hipStreamSynchronize(c_->stream);
+    if (!ok()) {   // the first error is the one reported
+      if (sync != hipSuccess) (void)hipGetLastError();
+      return rc_ != LSPIV_OK ? rc_ : fail(hip_code(e_), "%s: %s failed: %s", name, step_, hipGetErrorString(e_));
+    }
+    if (sync != hipSuccess) return fail(hip_code(sync), "%s: synchronisation failed: %s", name, hipGetErrorString(sync));
+    return LSPIV_OK;
+  }
+
+ private:
+  std::lock_guard<std::mutex> lock_;
+  DeviceCtx* c_ = nullptr;
+  HostIn in_[kMaxSlots]; HostOut out_[kMaxSlots];
+  void *d_in_[kMaxSlots] = {}, *d_out_[kMaxSlots] = {};
+  int n_in_ = 0, n_out_ = 0, rc_ = LSPIV_OK;
+  hipError_t e_ = hipSuccess;
+  const char* step_ = "upload";
+  bool queued_ = false;
+};
+
+// the twins with one input, one optional second input and one output: run(d_in, d_other, stream) calls the "_dev" twin, d_other being
+// the output's slot or, for a twin that works in place (out.in = 0), the second input's
+template <class Run>
+int host_roundtrip(const char* name, HostIn in, HostOut out, Run&& run, HostIn aux = {}) {
+  HostCall hc({in, aux}, {out});
+  if (hc.upload()) hc.ran(run(hc.in(0), out.in == 0 ? hc.in(1) : hc.out(0), hc.stream()));
+  return hc.finish(name);
 }
 
 // ---- run-time options (api_core.hip: lspiv_set_option / lspiv_get_option, initial values from the environment) ---------------
@@ -250,6 +291,9 @@ int apply_signal_mode(DeviceCtx* c, lspiv::PivParams* p, int dtype, hipStream_t 
 // options norm_clip = 0 and -- unless the family scores window positions like the plain kernels -- signal_mode = 1 are refused
 int check_fixed_square(int wy, int wx, const char* what);
 int check_frame_fits_int16(int64_t H, int64_t W, const char* what);
+// the frame stack of the families that address pixels with 16 bits (warp_affine, sti_gather, pyr_down, lk_track; api_track.hip): uint8 or
+// float32, T_min .. 2^31 - 1 frames, sides side_min .. 32767; LSPIV_EINVAL, `what` names the family in the message
+int check_frames(const char* what, int dtype, int64_t T, int64_t T_min, int64_t H, int64_t W, int64_t side_min);
 int check_pair_options(const char* what, bool position_signal_ok = false);
 // shifted passes (multi-pass PIV, multi-pass ensemble) and SPOF-filtered correlation: the three of them
 int check_shift(int wy, int wx, int64_t H, int64_t W);

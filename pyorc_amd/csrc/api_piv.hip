@@ -1210,33 +1210,23 @@ int lspiv_piv_pairs(const void* frames, int dtype, int64_t T, int64_t H, int64_t
 }
 
 int lspiv_u_v_displacement(const float* corr_planes, int64_t P, int64_t n_win, int wy, int wx, float* u, float* v) {
-  std::lock_guard<std::mutex> host_lock(locks_here().host);
   if (!corr_planes || !u || !v) return fail(LSPIV_EINVAL, "NULL buffer");
   if (P < 0 || n_win < 0 || wy < 1 || wx < 1 || wy > 4096 || wx > 4096) return fail(LSPIV_EINVAL, "bad shape");
   const int64_t n = P * n_win;
   if (n == 0) return LSPIV_OK;
   if (n >= (int64_t)1 << 31) return fail(LSPIV_EINVAL, "too many planes for one launch");
-  DeviceCtx* c;
-  LSPIV_TRY(get_ctx(&c));
-  const size_t pb = (size_t)n * wy * wx * sizeof(float);
-  LSPIV_TRY(ensure(&c->d_planes, &c->planes_cap, pb));
-  LSPIV_TRY(ensure(&c->d_out, &c->out_cap, (2 * (size_t)n + 1) * sizeof(float)));   // [u | v | planes re-fitted]
-  HIP_TRY(hipMemcpyAsync(c->d_planes, corr_planes, pb, hipMemcpyHostToDevice, c->stream));
+  uint32_t n_refit = 0;   // planes re-fitted: a device counter that comes back with the results
+  HostCall hc({{corr_planes, (size_t)n * wy * wx * sizeof(float)}}, {{u, n * sizeof(float)}, {v, n * sizeof(float)}, {&n_refit, sizeof(uint32_t)}});
   // no frames behind these planes, so no rescue pass: the windows its criterion flags (no plane noise here: the allowance of the fused
   // kernels, not doubled) get the float64 fit of their five samples instead (piv_peaks.h); "rescue" = 0 keeps the float32 fits
   const float refit_k = g_opt_rescue.load() ? (float)(2.0 * g_opt_rescue_kappa.load() * 1e-9 / (0.6931471805599453 * 1e-4)) : 0.0f;
-  uint32_t* const d_refit = reinterpret_cast<uint32_t*>(c->d_out + 2 * n);
-  uint32_t n_refit = 0;
-  HIP_TRY(hipMemsetAsync(d_refit, 0, sizeof(uint32_t), c->stream));
-  LSPIV_TRY(launch_status(lspiv::launch_peaks_from_planes(c->d_planes, (uint32_t)n, wy, wx, g_opt_border.load(), c->d_out, c->d_out + n, refit_k,
-                                                          d_refit, c->stream)));
-  LSPIV_TRY(apply_v_sign(c->d_out + n, n, c->stream));
-  HIP_TRY(hipMemcpyAsync(u, c->d_out, n * sizeof(float), hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(hipMemcpyAsync(v, c->d_out + n, n * sizeof(float), hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(hipMemcpyAsync(&n_refit, d_refit, sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
-  HIP_TRY(hipStreamSynchronize(c->stream));
-  g_peaks_refitted.store((int)std::min<uint32_t>(n_refit, 0x7fffffffu));
-  return LSPIV_OK;
+  if (hc.upload() && hc.ran(launch_status(hipMemsetAsync(hc.out(2), 0, sizeof(uint32_t), hc.stream()), "hipMemsetAsync failed")) &&
+      hc.ran(launch_status(lspiv::launch_peaks_from_planes(hc.in<float>(0), (uint32_t)n, wy, wx, g_opt_border.load(), hc.out<float>(0), hc.out<float>(1),
+                                                           refit_k, hc.out<uint32_t>(2), hc.stream()))))
+    hc.ran(apply_v_sign(hc.out<float>(1), n, hc.stream()));
+  const int rc = hc.finish(__func__);   // waits for the stream on every exit: u, v and n_refit are the caller's and this frame's
+  if (rc == LSPIV_OK) g_peaks_refitted.store((int)std::min<uint32_t>(n_refit, 0x7fffffffu));
+  return rc;
 }
 
 int lspiv_second_peak(const float* corr_planes, int64_t P, int64_t n_win, int wy, int wx, int peak_exclusion, float* peak2) {
@@ -1245,8 +1235,7 @@ int lspiv_second_peak(const float* corr_planes, int64_t P, int64_t n_win, int wy
   LSPIV_TRY(check_second_peak(corr_planes, peak2, n, wy, wx, peak_exclusion));
   if (n == 0) return LSPIV_OK;
   const size_t pb = (size_t)n * wy * wx * sizeof(float);
-  RoundTrip io{corr_planes, pb, peak2, 4 * (size_t)n * sizeof(float)};
-  return host_roundtrip(__func__, io, [&](void* d_in, void* d_out, hipStream_t s) {
+  return host_roundtrip(__func__, {corr_planes, pb}, {peak2, 4 * (size_t)n * sizeof(float)}, [&](void* d_in, void* d_out, hipStream_t s) {
     return lspiv_second_peak_dev((const float*)d_in, n, wy, wx, peak_exclusion, (float*)d_out, s);
   });
 }

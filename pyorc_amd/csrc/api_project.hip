@@ -936,7 +936,7 @@ int lspiv_pack_int16_dev(const float* d_values, int64_t n, float scale, int fill
 int lspiv_pack_int16(const float* values, int64_t n, float scale, int fill, int16_t* packed) {
   if (!values || !packed) return fail(LSPIV_EINVAL, "NULL argument");
   if (n <= 0) return n == 0 ? LSPIV_OK : fail(LSPIV_EINVAL, "bad n");
-  return host_roundtrip(__func__, {values, (size_t)n * sizeof(float), packed, (size_t)n * sizeof(int16_t)}, [&](void* d_in, void* d_out, hipStream_t s) {
+  return host_roundtrip(__func__, {values, (size_t)n * sizeof(float)}, {packed, (size_t)n * sizeof(int16_t)}, [&](void* d_in, void* d_out, hipStream_t s) {
     return lspiv_pack_int16_dev((const float*)d_in, n, scale, fill, (int16_t*)d_out, s);
   });
 }

@@ -1,5 +1,6 @@
 // C ABI of liblspiv_hip.so, the row entry points (api_core.hip has the overview): post-PIV masks, element-wise filters, normalize,
-// reduce_rolling and the Gaussian filters, each as a "_dev" entry point on device pointers and, through host_roundtrip, on host ones.
+// reduce_rolling and the Gaussian filters, each as a "_dev" entry point on device pointers and, through HostCall (api_internal.h), on host
+// ones.
 #include "api_internal.h"
 
 #include <cmath>
@@ -42,7 +43,7 @@ static int blur_common_host(const char* name, const void* frames, int dtype, int
   if (!frames || !out) return fail(LSPIV_EINVAL, "NULL argument");
   if (dtype < 0 || dtype > 2 || T < 1 || H <= 0 || W <= 0) return fail(LSPIV_EINVAL, "bad argument");
   const size_t ib = (size_t)T * H * W * elem_size(dtype), ob = (size_t)T * H * W * sizeof(float);
-  return host_roundtrip(name, {frames, ib, out, ob}, [&](void* d_in, void* d_out, hipStream_t s) {
+  return host_roundtrip(name, {frames, ib}, {out, ob}, [&](void* d_in, void* d_out, hipStream_t s) {
     return blur_common_dev(d_in, dtype, T, H, W, k1, k2, (float*)d_out, s);
   });
 }
@@ -87,7 +88,7 @@ int lspiv_mask(const float* fields, int64_t T, int64_t R, int64_t C, int kind, c
                uint8_t* mask) {
   LSPIV_TRY(check_fields(fields, mask, T, R, C));
   const size_t fb = (size_t)4 * T * R * C * sizeof(float), mb = (size_t)(mask_is_2d(kind) ? 1 : T) * R * C;
-  return host_roundtrip(__func__, {fields, fb, mask, mb}, [&](void* d_in, void* d_out, hipStream_t s) {
+  return host_roundtrip(__func__, {fields, fb}, {mask, mb}, [&](void* d_in, void* d_out, hipStream_t s) {
     return lspiv_mask_dev((const float*)d_in, T, R, C, kind, params, n_params, (uint8_t*)d_out, s);
   });
 }
@@ -101,10 +102,9 @@ int lspiv_mask_apply_dev(float* d_fields, int64_t T, int64_t R, int64_t C, const
 int lspiv_mask_apply(float* fields, int64_t T, int64_t R, int64_t C, const uint8_t* mask, int mask_has_time) {
   LSPIV_TRY(check_fields(fields, mask, T, R, C));
   const size_t fb = (size_t)4 * T * R * C * sizeof(float), mb = (size_t)(mask_has_time ? T : 1) * R * C;
-  const RoundTrip io{fields, fb, /*out=*/fields, fb, /*in_place=*/true, /*aux=*/mask, mb};
-  return host_roundtrip(__func__, io, [&](void* d_fields, void* d_mask, hipStream_t s) {
+  return host_roundtrip(__func__, {fields, fb}, {fields, fb, /*in=*/0}, [&](void* d_fields, void* d_mask, hipStream_t s) {
     return lspiv_mask_apply_dev((float*)d_fields, T, R, C, (const uint8_t*)d_mask, mask_has_time, s);
-  });
+  }, /*aux=*/{mask, mb});
 }
 
 int lspiv_time_mean_dev(const float* d_fields, int64_t T, int64_t R, int64_t C, float* d_out, void* stream) {
@@ -115,7 +115,7 @@ int lspiv_time_mean_dev(const float* d_fields, int64_t T, int64_t R, int64_t C, 
 int lspiv_time_mean(const float* fields, int64_t T, int64_t R, int64_t C, float* out) {
   LSPIV_TRY(check_fields(fields, out, T, R, C));
   const size_t fb = (size_t)4 * T * R * C * sizeof(float), ob = (size_t)4 * R * C * sizeof(float);
-  return host_roundtrip(__func__, {fields, fb, out, ob}, [&](void* d_in, void* d_out, hipStream_t s) {
+  return host_roundtrip(__func__, {fields, fb}, {out, ob}, [&](void* d_in, void* d_out, hipStream_t s) {
     return lspiv_time_mean_dev((const float*)d_in, T, R, C, (float*)d_out, s);
   });
 }
@@ -147,7 +147,7 @@ int lspiv_window_replace(float* fields, int64_t T, int64_t R, int64_t C, int x_m
                          int iter) {
   LSPIV_TRY(check_fields(fields, fields, T, R, C));
   const size_t fb = (size_t)4 * T * R * C * sizeof(float);
-  return host_roundtrip(__func__, {fields, fb, /*out=*/fields, fb, /*in_place=*/true}, [&](void* d_fields, void*, hipStream_t s) {
+  return host_roundtrip(__func__, {fields, fb}, {fields, fb, /*in=*/0}, [&](void* d_fields, void*, hipStream_t s) {
     return lspiv_window_replace_dev((float*)d_fields, T, R, C, x_min, x_max, y_min, y_max, iter, s);
   });
 }
@@ -222,36 +222,13 @@ int lspiv_validate_dev(float* d_u, float* d_v, const float* d_peak2, int64_t T, 
 int lspiv_validate(float* u, float* v, const float* peak2, int64_t T, int64_t R, int64_t C, float threshold, float epsilon,
                    int min_neighbours, int replace, int iterations, uint8_t* flag) {
   LSPIV_TRY(check_validate(u, v, T, R, C, threshold, epsilon, min_neighbours, replace, iterations));
-  // the host twin: [u | v | flag] through the context's frame buffer, peak2 through its plane buffer, the same kernels in between
+  // the host twin: u, v and the flags work in place in their slots, the same kernels in between
   const size_t N = (size_t)T * R * C, fb = N * sizeof(float);
-  std::lock_guard<std::mutex> host_lock(locks_here().host);
-  DeviceCtx* c;
-  LSPIV_TRY(get_ctx(&c));
-  LSPIV_TRY(ensure(&c->d_frames, &c->frames_cap, 2 * fb + N));
-  if (peak2) LSPIV_TRY(ensure(&c->d_planes, &c->planes_cap, 4 * fb));
-  float *d_u = (float*)c->d_frames, *d_v = d_u + N;
-  uint8_t* d_flag = (uint8_t*)c->d_frames + 2 * fb;
-  const char* step = "upload";
-  hipError_t e = hipMemcpyAsync(d_u, u, fb, hipMemcpyHostToDevice, c->stream);
-  if (e == hipSuccess) e = hipMemcpyAsync(d_v, v, fb, hipMemcpyHostToDevice, c->stream);
-  if (e == hipSuccess && peak2) e = hipMemcpyAsync(c->d_planes, peak2, 4 * fb, hipMemcpyHostToDevice, c->stream);
-  const int rc = e == hipSuccess ? lspiv_validate_dev(d_u, d_v, peak2 ? c->d_planes : nullptr, T, R, C, threshold, epsilon, min_neighbours,
-                                                      replace, iterations, flag ? d_flag : nullptr, c->stream)
-                                 : LSPIV_OK;
-  if (e == hipSuccess && rc == LSPIV_OK) {
-    step = "download";
-    e = hipMemcpyAsync(u, d_u, fb, hipMemcpyDeviceToHost, c->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(v, d_v, fb, hipMemcpyDeviceToHost, c->stream);
-    if (e == hipSuccess && flag) e = hipMemcpyAsync(flag, d_flag, N, hipMemcpyDeviceToHost, c->stream);
-  }
-  // every exit from here waits for the stream: the caller's buffers are released only once its copies are done
-  const hipError_t sync = hipStreamSynchronize(c->stream);
-  if (e != hipSuccess || rc != LSPIV_OK) {   // the first error is the one reported
-    if (sync != hipSuccess) (void)hipGetLastError();
-    return rc != LSPIV_OK ? rc : fail(hip_code(e), "%s: %s failed: %s", __func__, step, hipGetErrorString(e));
-  }
-  if (sync != hipSuccess) return fail(hip_code(sync), "%s: synchronisation failed: %s", __func__, hipGetErrorString(sync));
-  return LSPIV_OK;
+  HostCall hc({{u, fb}, {v, fb}, {peak2, 4 * fb}, {flag, N, /*copy=*/false}}, {{u, fb, 0}, {v, fb, 1}, {flag, N, 3}});
+  if (hc.upload())
+    hc.ran(lspiv_validate_dev(hc.in<float>(0), hc.in<float>(1), hc.in<float>(2), T, R, C, threshold, epsilon, min_neighbours, replace, iterations,
+                              hc.in<uint8_t>(3), hc.stream()));
+  return hc.finish(__func__);
 }
 
 // ---- element-wise filters (N2) ---------------------------------------------------------------------
@@ -264,7 +241,7 @@ int lspiv_time_diff_dev(const void* d_frames, int dtype, int64_t T, int64_t H, i
 int lspiv_time_diff(const void* frames, int dtype, int64_t T, int64_t H, int64_t W, float thres, int use_abs, float* out) {
   LSPIV_TRY(check_stack(frames, out, dtype, T, H, W, 2));
   const size_t ib = (size_t)T * H * W * elem_size(dtype), ob = (size_t)(T - 1) * H * W * sizeof(float);
-  return host_roundtrip(__func__, {frames, ib, out, ob}, [&](void* d_in, void* d_out, hipStream_t s) {
+  return host_roundtrip(__func__, {frames, ib}, {out, ob}, [&](void* d_in, void* d_out, hipStream_t s) {
     return lspiv_time_diff_dev(d_in, dtype, T, H, W, thres, use_abs, (float*)d_out, s);
   });
 }
@@ -277,7 +254,7 @@ int lspiv_time_range_dev(const void* d_frames, int dtype, int64_t T, int64_t H, 
 int lspiv_time_range(const void* frames, int dtype, int64_t T, int64_t H, int64_t W, void* out) {
   LSPIV_TRY(check_stack(frames, out, dtype, T, H, W, 1));
   const size_t ib = (size_t)T * H * W * elem_size(dtype), ob = (size_t)H * W * elem_size(dtype);
-  return host_roundtrip(__func__, {frames, ib, out, ob}, [&](void* d_in, void* d_out, hipStream_t s) {
+  return host_roundtrip(__func__, {frames, ib}, {out, ob}, [&](void* d_in, void* d_out, hipStream_t s) {
     return lspiv_time_range_dev(d_in, dtype, T, H, W, d_out, s);
   });
 }
@@ -292,7 +269,7 @@ int lspiv_minmax(const float* frames, int64_t n, float lo, float hi, float* out)
   if (!frames || !out) return fail(LSPIV_EINVAL, "NULL argument");
   if (n <= 0) return n == 0 ? LSPIV_OK : fail(LSPIV_EINVAL, "bad n");
   const size_t b = (size_t)n * sizeof(float);
-  return host_roundtrip(__func__, {frames, b, out, b, /*in_place=*/true}, [&](void* d_buf, void*, hipStream_t s) {
+  return host_roundtrip(__func__, {frames, b}, {out, b, /*in=*/0}, [&](void* d_buf, void*, hipStream_t s) {
     return lspiv_minmax_dev((const float*)d_buf, n, lo, hi, (float*)d_buf, s);   // in place, one workspace
   });
 }
@@ -346,7 +323,7 @@ int lspiv_normalize(const uint8_t* frames, int64_t T, int64_t H, int64_t W, int 
   if (!frames || !out) return fail(LSPIV_EINVAL, "NULL argument");
   if (T < 1 || H <= 0 || W <= 0) return fail(LSPIV_ESHAPE, "bad shape");
   const size_t b = (size_t)T * H * W;
-  return host_roundtrip(__func__, {frames, b, out, b}, [&](void* d_in, void* d_out, hipStream_t s) {
+  return host_roundtrip(__func__, {frames, b}, {out, b}, [&](void* d_in, void* d_out, hipStream_t s) {
     return lspiv_normalize_dev((const uint8_t*)d_in, T, H, W, samples, (uint8_t*)d_out, s);
   });
 }
@@ -366,7 +343,7 @@ int lspiv_reduce_rolling(const uint8_t* frames, int64_t T, int64_t H, int64_t W,
   if (!frames || !out) return fail(LSPIV_EINVAL, "NULL argument");
   if (T < 1 || H <= 0 || W <= 0) return fail(LSPIV_ESHAPE, "bad shape");
   const size_t b = (size_t)T * H * W;
-  return host_roundtrip(__func__, {frames, b, out, b}, [&](void* d_in, void* d_out, hipStream_t s) {
+  return host_roundtrip(__func__, {frames, b}, {out, b}, [&](void* d_in, void* d_out, hipStream_t s) {
     return lspiv_reduce_rolling_dev((const uint8_t*)d_in, T, H, W, samples, (uint8_t*)d_out, s);
   });
 }

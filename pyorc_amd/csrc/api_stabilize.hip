@@ -1,7 +1,8 @@
 // C ABI of liblspiv_hip.so, frame stabilisation (api_core.hip has the overview): the transform fit over the vectors of the static part of
 // the image, the chain of poses and the per-frame affine warp, each as a "_dev" entry point on device pointers and as a host twin that
-// stages through the context's workspaces.  Replaces pyorc/cv.py's stabilisation (feature tracks + estimateAffinePartial2D) and the
-// cv2.warpAffine per frame of pyorc's Video(stabilize=...); the semantics are this project's own.
+// stages through the context's workspaces (api_internal.h, HostCall).  Replaces pyorc/cv.py's stabilisation (feature tracks +
+// estimateAffinePartial2D) and the cv2.warpAffine per frame of pyorc's Video(stabilize=...); the semantics are this project's own
+// (INTEGRATION.md section 2l).
 #include "api_internal.h"
 
 #include <cmath>
@@ -33,9 +34,7 @@ int check_fit(const void* u, const void* v, int64_t pairs, int64_t rows, int64_t
 
 int check_warp(const void* frames, int dtype, int64_t T, int64_t H, int64_t W, const void* A, const void* out) {
   if (!frames || !A || !out) return fail(LSPIV_EINVAL, "NULL argument");
-  if (dtype != LSPIV_U8 && dtype != LSPIV_F32) return fail(LSPIV_EINVAL, "warp_affine: dtype %d not in {0:u8, 1:f32}", dtype);
-  if (T < 1 || H < 1 || W < 1 || H > 32767 || W > 32767 || T > 0x7fffffff)
-    return fail(LSPIV_EINVAL, "warp_affine: bad shape (%lld, %lld, %lld) (sides up to 32767)", (long long)T, (long long)H, (long long)W);
+  LSPIV_TRY(check_frames("warp_affine", dtype, T, 1, H, W, 1));
   if (frames == out) return fail(LSPIV_EINVAL, "warp_affine: out must be another buffer than frames");
   return LSPIV_OK;
 }
@@ -71,71 +70,30 @@ int lspiv_stabilize_fit(const float* u, const float* v, int64_t pairs, int64_t r
                         int model, double reject0, double reject1, int min_vectors, double* P, int32_t* n_used) {
   lspiv::StabilizeFitParams p;
   LSPIV_TRY(check_fit(u, v, pairs, rows, cols, n, oy, ox, H, W, model, reject0, reject1, min_vectors, P, n_used, &p));
-  // [u | v] through the context's frame buffer, [P | n_used] through its plane buffer
   const size_t fb = (size_t)pairs * rows * cols * sizeof(float), pb = (size_t)pairs * 6 * sizeof(double), nb = (size_t)pairs * sizeof(int32_t);
-  std::lock_guard<std::mutex> host_lock(locks_here().host);
-  DeviceCtx* c;
-  LSPIV_TRY(get_ctx(&c));
-  LSPIV_TRY(ensure(&c->d_frames, &c->frames_cap, 2 * fb));
-  LSPIV_TRY(ensure(&c->d_planes, &c->planes_cap, pb + nb));
-  float *d_u = (float*)c->d_frames, *d_v = (float*)((char*)c->d_frames + fb);
-  double* d_P = (double*)c->d_planes;
-  int32_t* d_n = (int32_t*)((char*)c->d_planes + pb);
-  const char* step = "upload";
-  hipError_t e = hipMemcpyAsync(d_u, u, fb, hipMemcpyHostToDevice, c->stream);
-  if (e == hipSuccess) e = hipMemcpyAsync(d_v, v, fb, hipMemcpyHostToDevice, c->stream);
-  const int rc = e == hipSuccess ? launch_status(lspiv::launch_stabilize_fit(d_u, d_v, pairs, p, d_P, d_n, c->stream)) : LSPIV_OK;
-  if (e == hipSuccess && rc == LSPIV_OK) {
-    step = "download";
-    e = hipMemcpyAsync(P, d_P, pb, hipMemcpyDeviceToHost, c->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(n_used, d_n, nb, hipMemcpyDeviceToHost, c->stream);
-  }
-  return finish_host(__func__, step, e, rc, c->stream);
+  HostCall hc({{u, fb}, {v, fb}}, {{P, pb}, {n_used, nb}});
+  if (hc.upload())
+    hc.ran(launch_status(lspiv::launch_stabilize_fit(hc.in<float>(0), hc.in<float>(1), pairs, p, hc.out<double>(0), hc.out<int32_t>(1), hc.stream())));
+  return hc.finish(__func__);
 }
 
 int lspiv_stabilize_chain(const double* P, int64_t pairs, const double* carry_in, double* A, double* carry_out) {
   if (!A || (pairs > 0 && !P)) return fail(LSPIV_EINVAL, "NULL argument");
   if (pairs < 0 || pairs > 0x7fffffff) return fail(LSPIV_EINVAL, "stabilize: %lld pairs", (long long)pairs);
-  // [P | carry_in] through the context's frame buffer, [A | carry_out] through its plane buffer
   const size_t six = 6 * sizeof(double), pb = (size_t)pairs * six, ab = (size_t)(pairs + 1) * six;
-  std::lock_guard<std::mutex> host_lock(locks_here().host);
-  DeviceCtx* c;
-  LSPIV_TRY(get_ctx(&c));
-  LSPIV_TRY(ensure(&c->d_frames, &c->frames_cap, pb + six));
-  LSPIV_TRY(ensure(&c->d_planes, &c->planes_cap, ab + six));
-  double *d_P = (double*)c->d_frames, *d_cin = (double*)((char*)c->d_frames + pb);
-  double *d_A = (double*)c->d_planes, *d_cout = (double*)((char*)c->d_planes + ab);
-  const char* step = "upload";
-  hipError_t e = pairs > 0 ? hipMemcpyAsync(d_P, P, pb, hipMemcpyHostToDevice, c->stream) : hipSuccess;
-  if (e == hipSuccess && carry_in) e = hipMemcpyAsync(d_cin, carry_in, six, hipMemcpyHostToDevice, c->stream);
-  const int rc = e == hipSuccess ? launch_status(lspiv::launch_stabilize_chain(d_P, pairs, carry_in ? d_cin : nullptr, d_A, d_cout, c->stream)) : LSPIV_OK;
-  if (e == hipSuccess && rc == LSPIV_OK) {
-    step = "download";
-    e = hipMemcpyAsync(A, d_A, ab, hipMemcpyDeviceToHost, c->stream);
-    if (e == hipSuccess && carry_out) e = hipMemcpyAsync(carry_out, d_cout, six, hipMemcpyDeviceToHost, c->stream);
-  }
-  return finish_host(__func__, step, e, rc, c->stream);
+  HostCall hc({{P, pb}, {carry_in, six}}, {{A, ab}, {carry_out, six}});
+  if (hc.upload())
+    hc.ran(launch_status(lspiv::launch_stabilize_chain(hc.in<double>(0), pairs, hc.in<double>(1), hc.out<double>(0), hc.out<double>(1), hc.stream())));
+  return hc.finish(__func__);
 }
 
 int lspiv_warp_affine(const void* frames, int dtype, int64_t T, int64_t H, int64_t W, const double* A, void* out) {
   LSPIV_TRY(check_warp(frames, dtype, T, H, W, A, out));
-  // the frames through the context's frame buffer; [out | A] through its plane buffer
-  const size_t fb = (size_t)T * H * W * elem_size(dtype), fb8 = (fb + 7) & ~(size_t)7, ab = (size_t)T * 6 * sizeof(double);
-  std::lock_guard<std::mutex> host_lock(locks_here().host);
-  DeviceCtx* c;
-  LSPIV_TRY(get_ctx(&c));
-  LSPIV_TRY(ensure(&c->d_frames, &c->frames_cap, fb));
-  LSPIV_TRY(ensure(&c->d_planes, &c->planes_cap, fb8 + ab));
-  double* d_A = (double*)((char*)c->d_planes + fb8);
-  const char* step = "upload";
-  hipError_t e = hipMemcpyAsync(c->d_frames, frames, fb, hipMemcpyHostToDevice, c->stream);
-  if (e == hipSuccess) e = hipMemcpyAsync(d_A, A, ab, hipMemcpyHostToDevice, c->stream);
-  const int rc = e == hipSuccess ? launch_status(lspiv::launch_warp_affine(c->d_frames, dtype, T, (int)H, (int)W, d_A, c->d_planes, c->stream)) : LSPIV_OK;
-  if (e == hipSuccess && rc == LSPIV_OK) {
-    step = "download";
-    e = hipMemcpyAsync(out, c->d_planes, fb, hipMemcpyDeviceToHost, c->stream);
-  }
-  return finish_host(__func__, step, e, rc, c->stream);
+  const size_t fb = (size_t)T * H * W * elem_size(dtype), ab = (size_t)T * 6 * sizeof(double);
+  HostCall hc({{frames, fb}, {A, ab}}, {{out, fb}});
+  if (hc.upload())
+    hc.ran(launch_status(lspiv::launch_warp_affine(hc.in(0), dtype, T, (int)H, (int)W, hc.in<double>(1), hc.out(0), hc.stream())));
+  return hc.finish(__func__);
 }
 
 }  // extern "C"

@@ -1,6 +1,7 @@
 // C ABI of liblspiv_hip.so, space-time image velocimetry (api_core.hip has the overview): the gather of the space-time images along
 // the search lines and the orientation of their streaks, each as a "_dev" entry point on device pointers and as a host twin that stages
-// through the context's workspaces.  pyorc has no counterpart; the semantics are this project's own.
+// through the context's workspaces (api_internal.h, HostCall).  pyorc has no counterpart; the semantics are this project's own
+// (INTEGRATION.md section 2m).
 #include "api_internal.h"
 
 #include <algorithm>
@@ -13,14 +14,10 @@ namespace lspiv_api __attribute__((visibility("hidden"))) {
 
 namespace {
 
-constexpr size_t kStiStageBytes = (size_t)256 << 20;   // host frames go up in chunks of at most this size
-
 int check_gather(const void* frames, int dtype, int64_t T, int64_t H, int64_t W, const double* points, int64_t S, int64_t L, const void* sti,
                  int64_t t_offset, int64_t T_total) {
   if (!frames || !points || !sti) return fail(LSPIV_EINVAL, "NULL argument");
-  if (dtype != LSPIV_U8 && dtype != LSPIV_F32) return fail(LSPIV_EINVAL, "sti_gather: dtype %d not in {0:u8, 1:f32}", dtype);
-  if (T < 1 || H < 2 || W < 2 || H > 32767 || W > 32767 || T > 0x7fffffff)
-    return fail(LSPIV_EINVAL, "sti_gather: bad shape (%lld, %lld, %lld) (sides 2 .. 32767)", (long long)T, (long long)H, (long long)W);
+  LSPIV_TRY(check_frames("sti_gather", dtype, T, 1, H, W, 2));
   if (S < 1 || L < 3 || S > 0x7fffffff / L) return fail(LSPIV_EINVAL, "sti_gather: %lld lines of %lld samples (at least 3 per line)", (long long)S, (long long)L);
   if (t_offset < 0 || T_total > 0x7fffffff || t_offset > T_total - T)
     return fail(LSPIV_EINVAL, "sti_gather: rows [%lld, %lld) do not fit a space-time image of %lld rows", (long long)t_offset,
@@ -102,30 +99,20 @@ int lspiv_sti_gather(const void* frames, int dtype, int64_t T, int64_t H, int64_
   LSPIV_TRY(check_gather(frames, dtype, T, H, W, points, S, L, sti, t_offset, T_total));
   std::vector<char> table;
   LSPIV_TRY(sti_prepare_points(points, S, L, H, W, &table));
-  // the frames through the context's frame buffer, a chunk at a time; the rows of this call, (S, T, L), through its plane buffer
+  // the frames a chunk at a time through one slot; the rows of this call, (S, T, L), gathered in another and sent to their lines' rows
   const size_t frame_bytes = (size_t)H * W * elem_size(dtype), row_bytes = (size_t)T * L * sizeof(float);
-  const int64_t chunk = std::max<int64_t>(1, std::min<int64_t>(T, (int64_t)(kStiStageBytes / frame_bytes)));
-  std::lock_guard<std::mutex> host_lock(locks_here().host);
-  DeviceCtx* c;
-  LSPIV_TRY(get_ctx(&c));
-  LSPIV_TRY(ensure(&c->d_frames, &c->frames_cap, (size_t)chunk * frame_bytes));
-  LSPIV_TRY(ensure(&c->d_planes, &c->planes_cap, (size_t)S * row_bytes));
+  const int64_t chunk = std::max<int64_t>(1, std::min<int64_t>(T, (int64_t)(host_chunk_bytes() / frame_bytes)));
+  HostCall hc({{frames, (size_t)chunk * frame_bytes, /*copy=*/false}}, {{sti, (size_t)S * row_bytes, -1, /*copy=*/false}});
   lspiv::StiTable t;
-  LSPIV_TRY(upload_table(c, table, S * L, c->stream, &t));
-  const char* step = "upload";
-  hipError_t e = hipSuccess;
-  int rc = LSPIV_OK;
-  for (int64_t f0 = 0; f0 < T && e == hipSuccess && rc == LSPIV_OK; f0 += chunk) {
+  if (hc.ok()) hc.ran(upload_table(hc.ctx(), table, S * L, hc.stream(), &t));
+  for (int64_t f0 = 0; f0 < T && hc.ok(); f0 += chunk) {
     const int64_t n = std::min(chunk, T - f0);
-    e = hipMemcpyAsync(c->d_frames, (const char*)frames + (size_t)f0 * frame_bytes, (size_t)n * frame_bytes, hipMemcpyHostToDevice, c->stream);
-    if (e == hipSuccess) rc = launch_status(lspiv::launch_sti_gather(c->d_frames, dtype, n, (int)H, (int)W, t, S, (int)L, c->d_planes, f0, T, c->stream));
+    if (hc.copy_in(hc.in(0), (const char*)frames + (size_t)f0 * frame_bytes, (size_t)n * frame_bytes))
+      hc.ran(launch_status(lspiv::launch_sti_gather(hc.in(0), dtype, n, (int)H, (int)W, t, S, (int)L, hc.out<float>(0), f0, T, hc.stream())));
   }
-  if (e == hipSuccess && rc == LSPIV_OK) {
-    step = "download";
-    for (int64_t line = 0; line < S && e == hipSuccess; ++line)
-      e = hipMemcpyAsync(sti + (line * T_total + t_offset) * L, c->d_planes + line * T * L, row_bytes, hipMemcpyDeviceToHost, c->stream);
-  }
-  return finish_host(__func__, step, e, rc, c->stream);
+  for (int64_t line = 0; line < S && hc.ok(); ++line)
+    hc.copy_out(sti + (line * T_total + t_offset) * L, hc.out<float>(0) + line * T * L, row_bytes);
+  return hc.finish(__func__);
 }
 
 int lspiv_sti_orientation_dev(const float* d_sti, int64_t S, int64_t T, int64_t L, int64_t time_window, int64_t time_stride, int smooth,
@@ -141,26 +128,12 @@ int lspiv_sti_orientation(const float* sti, int64_t S, int64_t T, int64_t L, int
                           double* tensor, double* slope, double* coherency) {
   int64_t K;
   LSPIV_TRY(check_orientation(sti, S, T, L, time_window, time_stride, smooth, tensor, slope, coherency, &K));
-  // the space-time images through the context's frame buffer, [tensor | slope | coherency] through its plane buffer
   const size_t sb = (size_t)S * T * L * sizeof(float), nb = (size_t)S * K * sizeof(double);
-  std::lock_guard<std::mutex> host_lock(locks_here().host);
-  DeviceCtx* c;
-  LSPIV_TRY(get_ctx(&c));
-  LSPIV_TRY(ensure(&c->d_frames, &c->frames_cap, sb));
-  LSPIV_TRY(ensure(&c->d_planes, &c->planes_cap, 5 * nb));
-  double *d_tensor = (double*)c->d_planes, *d_slope = d_tensor + 3 * S * K, *d_coh = d_slope + S * K;
-  const char* step = "upload";
-  hipError_t e = hipMemcpyAsync(c->d_frames, sti, sb, hipMemcpyHostToDevice, c->stream);
-  const int rc = e == hipSuccess ? launch_status(lspiv::launch_sti_orientation((const float*)c->d_frames, S, T, (int)L, time_window, time_stride, K,
-                                                                               smooth, detrend != 0, d_tensor, d_slope, d_coh, c->stream))
-                                 : LSPIV_OK;
-  if (e == hipSuccess && rc == LSPIV_OK) {
-    step = "download";
-    e = hipMemcpyAsync(tensor, d_tensor, 3 * nb, hipMemcpyDeviceToHost, c->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(slope, d_slope, nb, hipMemcpyDeviceToHost, c->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(coherency, d_coh, nb, hipMemcpyDeviceToHost, c->stream);
-  }
-  return finish_host(__func__, step, e, rc, c->stream);
+  HostCall hc({{sti, sb}}, {{tensor, 3 * nb}, {slope, nb}, {coherency, nb}});
+  if (hc.upload())
+    hc.ran(launch_status(lspiv::launch_sti_orientation(hc.in<float>(0), S, T, (int)L, time_window, time_stride, K, smooth, detrend != 0,
+                                                       hc.out<double>(0), hc.out<double>(1), hc.out<double>(2), hc.stream())));
+  return hc.finish(__func__);
 }
 
 }  // extern "C"

@@ -1,6 +1,6 @@
 // C ABI of liblspiv_hip.so, pyramidal Lucas-Kanade point tracking (api_core.hip has the overview): the Gaussian pyramid step and the
-// tracker, each as a "_dev" entry point on device pointers and as a host twin that stages through the context's workspaces.  The
-// semantics are this project's own (tests/track_ref.py).
+// tracker, each as a "_dev" entry point on device pointers and as a host twin that stages through the context's workspaces
+// (api_internal.h, HostCall).  The semantics are this project's own (tests/track_ref.py).
 #include "api_internal.h"
 
 #include <algorithm>
@@ -11,9 +11,16 @@
 
 namespace lspiv_api __attribute__((visibility("hidden"))) {
 
+int check_frames(const char* what, int dtype, int64_t T, int64_t T_min, int64_t H, int64_t W, int64_t side_min) {
+  if (dtype != LSPIV_U8 && dtype != LSPIV_F32) return fail(LSPIV_EINVAL, "%s: dtype %d not in {0:u8, 1:f32}", what, dtype);
+  if (T < T_min || T > 0x7fffffff || H < side_min || W < side_min || H > 32767 || W > 32767)
+    return fail(LSPIV_EINVAL, "%s: bad shape (%lld, %lld, %lld) (at least %lld frames, sides %lld .. 32767)", what, (long long)T, (long long)H,
+                (long long)W, (long long)T_min, (long long)side_min);
+  return LSPIV_OK;
+}
+
 namespace {
 
-constexpr size_t kTrackStageBytes = (size_t)256 << 20;   // host frames go up in chunks of at most this size
 constexpr size_t kTrackWsDefault = (size_t)1 << 30;      // the pyramid workspace's cap; LSPIV_TRACK_WS_BYTES (a test hook) overrides it
 
 // The pyramid levels >= 1 of the frames of one batch of pairs: library-owned, per device, grow-only up to the cap.  Calls are issued
@@ -21,23 +28,12 @@ constexpr size_t kTrackWsDefault = (size_t)1 << 30;      // the pyramid workspac
 struct TrackWs { void* p = nullptr; size_t cap = 0; std::mutex lock; };
 TrackWs g_track_ws[kMaxDevices];
 
-size_t ws_limit() {
-  const char* e = std::getenv("LSPIV_TRACK_WS_BYTES");
-  if (e && *e) {
-    char* end = nullptr;
-    const unsigned long long v = std::strtoull(e, &end, 10);
-    if (end && !*end) return (size_t)v;
-  }
-  return kTrackWsDefault;
-}
+size_t ws_limit() { return env_bytes("LSPIV_TRACK_WS_BYTES", kTrackWsDefault); }
 
 int check_stack(const char* what, const void* frames, int dtype, int64_t T, int64_t T_min, int64_t H, int64_t W, int levels) {
   if (!frames) return fail(LSPIV_EINVAL, "NULL argument");
-  if (dtype != LSPIV_U8 && dtype != LSPIV_F32) return fail(LSPIV_EINVAL, "%s: dtype %d not in {0:u8, 1:f32}", what, dtype);
   if (levels < 1 || levels > lspiv::kTrackMaxLevels) return fail(LSPIV_EINVAL, "%s: levels %d outside 1 .. %d", what, levels, lspiv::kTrackMaxLevels);
-  if (T < T_min || T > 0x7fffffff || H < 1 || W < 1 || H > 32767 || W > 32767)
-    return fail(LSPIV_EINVAL, "%s: bad shape (%lld, %lld, %lld) (at least %lld frames, sides up to 32767)", what, (long long)T, (long long)H,
-                (long long)W, (long long)T_min);
+  LSPIV_TRY(check_frames(what, dtype, T, T_min, H, W, 1));
   // a level that pyr_down reads needs both sides >= 3 (the reflection -1 -> 1, n -> n - 2), every level both >= 2
   int64_t h = H, w = W;
   for (int l = 0; l < levels; ++l) {
@@ -144,7 +140,7 @@ int lspiv_pyr_down(const void* frames, int dtype, int64_t T, int64_t H, int64_t 
   LSPIV_TRY(check_stack("pyr_down", frames, dtype, T, 1, H, W, 2));
   if (!out) return fail(LSPIV_EINVAL, "NULL argument");
   const size_t in_bytes = (size_t)T * H * W * elem_size(dtype), out_bytes = (size_t)T * ((H + 1) / 2) * ((W + 1) / 2) * sizeof(float);
-  return host_roundtrip(__func__, RoundTrip{frames, in_bytes, out, out_bytes}, [&](void* d_in, void* d_o, hipStream_t s) {
+  return host_roundtrip(__func__, {frames, in_bytes}, {out, out_bytes}, [&](void* d_in, void* d_o, hipStream_t s) {
     return launch_status(lspiv::launch_pyr_down(d_in, dtype, T, (int)H, (int)W, (float*)d_o, s));
   });
 }
@@ -171,45 +167,20 @@ int lspiv_lk_track(const void* frames, int dtype, int64_t T, int64_t H, int64_t 
   LSPIV_TRY(check_track(a, frames));
   const int64_t P = T - 1;
   const size_t frame_bytes = (size_t)H * W * elem_size(dtype);
-  const int64_t chunk = std::max<int64_t>(1, std::min<int64_t>(P, (int64_t)(kTrackStageBytes / frame_bytes) - 1));   // pairs per upload
-  // [points | guess] through the context's scratch buffer; [u | v | err | min_eig | xy | n_iter | status] through its plane buffer
-  const size_t pb = (size_t)(points_per_pair ? P : 1) * N * 2 * sizeof(double), gb = guess ? (size_t)(guess_per_pair ? P : 1) * N * 2 * sizeof(double) : 0;
-  const size_t ob = (size_t)P * N * sizeof(double), xb = chain ? (size_t)T * N * 2 * sizeof(double) : 0, ib = (size_t)P * N * sizeof(int32_t),
-               sb = (size_t)P * N;
-  std::lock_guard<std::mutex> host_lock(locks_here().host);
-  DeviceCtx* c;
-  LSPIV_TRY(get_ctx(&c));
-  LSPIV_TRY(ensure(&c->d_frames, &c->frames_cap, (size_t)(chunk + 1) * frame_bytes));
-  LSPIV_TRY(ensure(&c->d_planes, &c->planes_cap, 4 * ob + xb + ib + sb));
-  LSPIV_TRY(ensure(&c->d_scratch, &c->scratch_cap, pb + gb));
-  char* o = (char*)c->d_planes;
-  a.u = (double*)o; a.v = a.u + P * N; a.err = a.v + P * N; a.lam = a.err + P * N;
-  a.xy = chain ? a.lam + P * N : nullptr;
-  a.n_iter = (int32_t*)(o + 4 * ob + xb);
-  a.status = (uint8_t*)(o + 4 * ob + xb + ib);
-  a.points = (const double*)c->d_scratch;
-  a.guess = guess ? (const double*)((const char*)c->d_scratch + pb) : nullptr;
-  const char* step = "upload";
-  hipError_t e = hipMemcpyAsync(c->d_scratch, points, pb, hipMemcpyHostToDevice, c->stream);
-  if (e == hipSuccess && guess) e = hipMemcpyAsync((char*)c->d_scratch + pb, guess, gb, hipMemcpyHostToDevice, c->stream);
-  if (e == hipSuccess && chain) e = hipMemcpyAsync(a.xy, c->d_scratch, (size_t)N * 2 * sizeof(double), hipMemcpyDeviceToDevice, c->stream);
-  int rc = LSPIV_OK;
-  for (int64_t p0 = 0; p0 < P && e == hipSuccess && rc == LSPIV_OK; p0 += chunk) {   // frames p0 .. p0 + n: one frame of halo
+  const int64_t chunk = std::max<int64_t>(1, std::min<int64_t>(P, (int64_t)(host_chunk_bytes() / frame_bytes) - 1));   // pairs per upload
+  const size_t pb = (size_t)(points_per_pair ? P : 1) * N * 2 * sizeof(double), gb = (size_t)(guess_per_pair ? P : 1) * N * 2 * sizeof(double);
+  const size_t ob = (size_t)P * N * sizeof(double), xb = (size_t)T * N * 2 * sizeof(double);
+  HostCall hc({{points, pb}, {guess, gb}, {frames, (size_t)(chunk + 1) * frame_bytes, /*copy=*/false}},
+              {{u, ob}, {v, ob}, {err, ob}, {min_eig_out, ob}, {n_iter, (size_t)P * N * sizeof(int32_t)}, {status, (size_t)P * N}, {chain ? xy : nullptr, xb}});
+  a.points = hc.in<double>(0); a.guess = hc.in<double>(1);
+  a.u = hc.out<double>(0); a.v = hc.out<double>(1); a.err = hc.out<double>(2); a.lam = hc.out<double>(3);
+  a.n_iter = hc.out<int32_t>(4); a.status = hc.out<uint8_t>(5); a.xy = hc.out<double>(6);
+  if (hc.upload() && chain) hc.copy(a.xy, a.points, (size_t)N * 2 * sizeof(double), hipMemcpyDeviceToDevice);   // row 0
+  for (int64_t p0 = 0; p0 < P && hc.ok(); p0 += chunk) {   // frames p0 .. p0 + n: one frame of halo
     const int64_t n = std::min(chunk, P - p0);
-    e = hipMemcpyAsync(c->d_frames, (const char*)frames + (size_t)p0 * frame_bytes, (size_t)(n + 1) * frame_bytes, hipMemcpyHostToDevice, c->stream);
-    if (e == hipSuccess) rc = run_pairs(a, c->d_frames, p0, n, c->stream);
+    if (hc.copy_in(hc.in(2), (const char*)frames + (size_t)p0 * frame_bytes, (size_t)(n + 1) * frame_bytes)) hc.ran(run_pairs(a, hc.in(2), p0, n, hc.stream()));
   }
-  if (e == hipSuccess && rc == LSPIV_OK) {
-    step = "download";
-    e = hipMemcpyAsync(u, a.u, ob, hipMemcpyDeviceToHost, c->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(v, a.v, ob, hipMemcpyDeviceToHost, c->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(err, a.err, ob, hipMemcpyDeviceToHost, c->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(min_eig_out, a.lam, ob, hipMemcpyDeviceToHost, c->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(n_iter, a.n_iter, ib, hipMemcpyDeviceToHost, c->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(status, a.status, sb, hipMemcpyDeviceToHost, c->stream);
-    if (e == hipSuccess && chain) e = hipMemcpyAsync(xy, a.xy, xb, hipMemcpyDeviceToHost, c->stream);
-  }
-  return finish_host(__func__, step, e, rc, c->stream);
+  return hc.finish(__func__);
 }
 
 }  // extern "C"

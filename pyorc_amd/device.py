@@ -19,7 +19,7 @@ Slicing along time (``f[a:b]``) is a view (pointer arithmetic), which is all the
 from __future__ import annotations
 
 import ctypes as C
-from typing import Tuple
+from typing import Optional, Tuple
 
 import numpy as np
 
@@ -228,3 +228,52 @@ class _FrameView:
 
 def is_device(obj) -> bool:
     return isinstance(obj, DeviceFrames)
+
+
+def buffer(arr: Optional[np.ndarray] = None, nbytes: int = 0) -> DeviceFrames:
+    """A raw HBM block of ``nbytes`` (at least one byte), or of the size of the C-contiguous ``arr`` and filled from it: what a
+    ``*_dev`` entry point takes for an argument that is no frame stack.  ``.c_ptr`` is its pointer, ``download`` / ``download_into`` read it back."""
+    if arr is not None:
+        nbytes = arr.nbytes
+    d = DeviceFrames.empty((1, 1, max(int(nbytes), 1)), np.uint8)
+    if arr is not None and arr.nbytes:
+        _lib.check(_lib.load().lspiv_memcpy_h2d(d.c_ptr, _lib.ptr(arr), arr.nbytes))
+    return d
+
+
+def download_into(d: DeviceFrames, out: np.ndarray) -> np.ndarray:
+    """The first ``out.nbytes`` bytes of the block ``d`` into the C-contiguous host array ``out``, which is returned."""
+    if out.nbytes:
+        _lib.check(_lib.load().lspiv_memcpy_d2h(_lib.ptr(out), d.c_ptr, out.nbytes))
+    return out
+
+
+def download(d: DeviceFrames, shape, dtype) -> np.ndarray:
+    """The first bytes of the block ``d`` as a new host array of ``shape`` and ``dtype``."""
+    return download_into(d, np.empty(shape, dtype=dtype))
+
+
+_STACK_DTYPES = (np.dtype(np.uint8), np.dtype(np.float32))
+
+
+def check_stack(frames, what: str, t_min: int = 0, side_min: int = 0):
+    """``frames`` as what the kernels of ``what`` (stabilize, stiv, track) take: a (T, H, W) ``DeviceFrames`` as it is or a host array made
+    C-contiguous, uint8 or float32 (anything else is a TypeError that names the dtype), at least ``t_min`` frames, sides of at least
+    ``side_min``."""
+    a = frames if is_device(frames) else np.asarray(frames)
+    if len(a.shape) != 3:
+        raise ValueError(f"frames must be (T, H, W), got shape {tuple(a.shape)}")
+    if np.dtype(a.dtype) not in _STACK_DTYPES:
+        raise TypeError(f"{what} works on uint8 and float32 stacks, got {np.dtype(a.dtype)}")
+    if a.shape[0] < t_min:
+        raise ValueError(f"{a.shape[0]} frames: at least {t_min} are needed")
+    if min(a.shape[1:]) < side_min:
+        raise ValueError(f"frames of {tuple(a.shape[1:])} are smaller than {side_min} x {side_min}")
+    return a if is_device(a) else np.ascontiguousarray(a)
+
+
+def out_fits(out, dev: bool, dtype) -> bool:
+    """``out`` can take the result of a call on a stack of the same kind: a ``DeviceFrames`` for one in HBM (``dev``), else a writable
+    C-contiguous array, of ``dtype``.  The shape is the caller's to check."""
+    kind_ok = is_device(out) if dev else isinstance(out, np.ndarray) and out.flags.c_contiguous and out.flags.writeable
+    return bool(kind_ok) and np.dtype(out.dtype) == np.dtype(dtype)

@@ -17,7 +17,7 @@ from typing import Optional, Tuple
 
 import numpy as np
 
-from . import _lib, window
+from . import _lib, device, window
 from .device import is_device
 
 ENGINES = ("hip",)
@@ -90,14 +90,10 @@ def _device_stack(imgs, signal_threshold):
 
 def _per_window_input(name, value, grid, dtype):
     """``shift`` / ``nodes`` of a pass: ``(P, n_rows, n_cols, 2)`` of ``dtype``, checked against ``grid`` and brought into HBM."""
-    from .device import DeviceFrames
-
     arr = np.ascontiguousarray(value, dtype=dtype)
     if arr.shape != (*grid, 2):
         raise ValueError(f"{name} must have shape {(*grid, 2)}, got {arr.shape}")
-    d = DeviceFrames.empty((1, 1, arr.nbytes), np.uint8)
-    _lib.check(_lib.load().lspiv_memcpy_h2d(d.c_ptr, _lib.ptr(arr), arr.nbytes))
-    return d
+    return device.buffer(arr)
 
 
 def _run_pairs(imgs, ws, ov, signal_threshold, return_planes, pair_offset, out, scale, entry, args, fused=False, extra=None, aux=None,
@@ -148,8 +144,8 @@ def _run_pairs(imgs, ws, ov, signal_threshold, return_planes, pair_offset, out, 
     if dev:   # HBM-resident stack: no staging, one call, only the result block crosses PCIe
         res = DeviceFrames.empty((4, P, n_win), np.float32)
         planes = DeviceFrames.empty((P * n_win, ws[0], ws[1]), np.float32) if return_planes else None
-        d_aux = DeviceFrames.empty((1, 1, aux.nbytes), np.uint8) if aux is not None else None
-        d_aux2 = DeviceFrames.empty((1, 1, aux2.nbytes), np.uint8) if aux2 is not None else None
+        d_aux = device.buffer(nbytes=aux.nbytes) if aux is not None else None
+        d_aux2 = device.buffer(nbytes=aux2.nbytes) if aux2 is not None else None
         frames, res_ptrs, ptr = (a.c_ptr, a.dtype_code), (res.c_ptr,), lambda q: None if q is None else q.c_ptr
     else:
         res = out if out is not None else [np.empty((P, n_rows, n_cols), dtype=np.float32) for _ in range(4)]
@@ -165,9 +161,9 @@ def _run_pairs(imgs, ws, ov, signal_threshold, return_planes, pair_offset, out, 
 
         flag = np.empty((P, n_rows, n_cols), dtype=np.uint8)
         if dev:      # on the result block while it is still in HBM
-            d_flag = DeviceFrames.empty((1, 1, flag.nbytes), np.uint8)
+            d_flag = device.buffer(nbytes=flag.nbytes)
             validate_mod.run_dev(validate, res.c_ptr, C.c_void_p(res.ptr + P * n_win * 4), c.aux, (P, n_rows, n_cols), d_flag.c_ptr)
-            _lib.check(lib.lspiv_memcpy_d2h(_lib.ptr(flag), d_flag.c_ptr, flag.nbytes))
+            device.download_into(d_flag, flag)
         else:        # the host twin, right after the call
             validate_mod.run_host(validate, res[0], res[1], aux, flag)
     if dev:
@@ -177,9 +173,9 @@ def _run_pairs(imgs, ws, ov, signal_threshold, return_planes, pair_offset, out, 
         if return_planes:
             planes = planes.to_host().reshape(P, n_win, ws[0], ws[1])
         if aux is not None:
-            _lib.check(lib.lspiv_memcpy_d2h(_lib.ptr(aux), d_aux.c_ptr, aux.nbytes))
+            device.download_into(d_aux, aux)
         if aux2 is not None:
-            _lib.check(lib.lspiv_memcpy_d2h(_lib.ptr(aux2), d_aux2.c_ptr, aux2.nbytes))
+            device.download_into(d_aux2, aux2)
     if dt is not None and not fused:
         for k in range(2):
             _to_velocity(res[k], scale[k], dt[:, None, None], out=res[k])
@@ -421,13 +417,7 @@ def piv_pairs_lagged(imgs, window_size=(32, 32), overlap=(16, 16), pair_step=2, 
     def lags(grid3):
         if spec.array is None:
             return None
-        if not is_device(a):
-            return spec.array
-        from .device import DeviceFrames
-
-        d = DeviceFrames.empty((1, 1, spec.array.nbytes), np.uint8)
-        _lib.check(_lib.load().lspiv_memcpy_h2d(d.c_ptr, _lib.ptr(spec.array), spec.array.nbytes))
-        return d
+        return device.buffer(spec.array) if is_device(a) else spec.array
 
     ret = _run_pairs(a, ws, ov, signal_threshold, return_planes, pair_offset, out, scale,
                      ("lspiv_piv_lag_pairs_at", "lspiv_piv_lag_pairs_dev_at"),
@@ -485,12 +475,10 @@ def predict_shift(u, v, dim_size, coarse, fine):
     _lib.check(lib.lspiv_memcpy_h2d(d_uv.c_ptr, _lib.ptr(uu), uu.nbytes))
     _lib.check(lib.lspiv_memcpy_h2d(C.c_void_p(d_uv.ptr + uu.nbytes), _lib.ptr(vv), vv.nbytes))
     out = np.empty((P, rf, cf, 2), dtype=np.int16)
-    d_shift = DeviceFrames.empty((1, 1, max(out.nbytes, 1)), np.uint8)
+    d_shift = device.buffer(nbytes=out.nbytes)
     _lib.check(lib.lspiv_piv_predict_shift_dev(d_uv.c_ptr, C.c_void_p(d_uv.ptr + uu.nbytes), P, H, W, nc, nc, oc, oc, nf, nf, of, of,
                                                d_shift.c_ptr, None))
-    if out.size:
-        _lib.check(lib.lspiv_memcpy_d2h(_lib.ptr(out), d_shift.c_ptr, out.nbytes))
-    return out
+    return device.download_into(d_shift, out)
 
 
 def predict_deform(u, v):
@@ -510,14 +498,12 @@ def predict_deform(u, v):
     P, rows, cols = uu.shape
     out = np.empty((P, rows, cols, 2), dtype=np.int32)
     d_uv = DeviceFrames.empty((2, max(P, 1), rows * cols), np.float32)
-    d_nodes = DeviceFrames.empty((1, 1, max(out.nbytes, 1)), np.uint8)
+    d_nodes = device.buffer(nbytes=out.nbytes)
     if out.size:
         _lib.check(lib.lspiv_memcpy_h2d(d_uv.c_ptr, _lib.ptr(uu), uu.nbytes))
         _lib.check(lib.lspiv_memcpy_h2d(C.c_void_p(d_uv.ptr + uu.nbytes), _lib.ptr(vv), vv.nbytes))
     _lib.check(lib.lspiv_piv_predict_deform_dev(d_uv.c_ptr, C.c_void_p(d_uv.ptr + uu.nbytes), P, rows, cols, d_nodes.c_ptr, None))
-    if out.size:
-        _lib.check(lib.lspiv_memcpy_d2h(_lib.ptr(out), d_nodes.c_ptr, out.nbytes))
-    return out
+    return device.download_into(d_nodes, out)
 
 
 def piv_pairs_deformed(imgs, window_size=(32, 32), overlap=(16, 16), nodes=None, signal_threshold: Optional[float] = None,

@@ -15,18 +15,16 @@ for bit what one call over the whole stack gives.
 
 from __future__ import annotations
 
-import ctypes as C
 import warnings
 from typing import NamedTuple, Optional
 
 import numpy as np
 
-from . import _lib, piv
+from . import _lib, device, piv
 from .device import DeviceFrames, is_device
 
 WINDOWS = (16, 32, 64)
 MODELS = {"translation": 0, "similarity": 1, "affine": 2}
-_DTYPES = (np.dtype(np.uint8), np.dtype(np.float32))
 
 
 class Transforms(NamedTuple):
@@ -37,33 +35,6 @@ class Transforms(NamedTuple):
     pairwise: np.ndarray
     n_used: np.ndarray
     carry: np.ndarray
-
-
-def _check_stack(frames):
-    """A (T, H, W) host array or ``DeviceFrames`` of uint8 or float32; anything else is a TypeError that names the dtype."""
-    a = frames if is_device(frames) else np.asarray(frames)
-    if a.ndim != 3:
-        raise ValueError(f"frames must be (T, H, W), got shape {a.shape}")
-    if np.dtype(a.dtype) not in _DTYPES:
-        raise TypeError(f"stabilize works on uint8 and float32 stacks, got {np.dtype(a.dtype)}")
-    return a if is_device(a) else np.ascontiguousarray(a)
-
-
-def _device_buffer(arr: Optional[np.ndarray] = None, nbytes: int = 0) -> DeviceFrames:
-    """A raw HBM block, filled from ``arr`` if given."""
-    if arr is not None:
-        nbytes = arr.nbytes
-    d = DeviceFrames.empty((1, 1, max(int(nbytes), 8)), np.uint8)
-    if arr is not None and arr.nbytes:
-        _lib.check(_lib.load().lspiv_memcpy_h2d(d.c_ptr, _lib.ptr(arr), arr.nbytes))
-    return d
-
-
-def _download(d: DeviceFrames, shape, dtype) -> np.ndarray:
-    out = np.empty(shape, dtype=dtype)
-    if out.nbytes:
-        _lib.check(_lib.load().lspiv_memcpy_d2h(_lib.ptr(out), d.c_ptr, out.nbytes))
-    return out
 
 
 def estimate(frames, stable_mask, window_size: int = 32, overlap: Optional[int] = None, model: str = "similarity",
@@ -79,7 +50,7 @@ def estimate(frames, stable_mask, window_size: int = 32, overlap: Optional[int] 
     once per call.  ``carry``: the pose (2, 3) of the first frame, ``Transforms.carry`` of the chunk before (default: the identity).
     The shake between two frames must stay below about half a window less the width of the correlation peak."""
     lib = _lib.load()
-    a = _check_stack(frames)
+    a = device.check_stack(frames, "stabilize")
     T, H, W = a.shape
     n = int(window_size)
     if n not in WINDOWS or n != window_size:
@@ -112,14 +83,14 @@ def estimate(frames, stable_mask, window_size: int = 32, overlap: Optional[int] 
         v = -v
     P_, rows, cols = u.shape
     # vectors up, fit -> chain on the library's stream, transforms down: no host round trip between the two kernels
-    d_u, d_v = _device_buffer(np.ascontiguousarray(u)), _device_buffer(np.ascontiguousarray(v))
-    d_P, d_n, d_A, d_c = (_device_buffer(nbytes=q) for q in (P_ * 48, P_ * 4, T * 48, 48))
-    d_carry = _device_buffer(carry_in) if carry_in is not None else None
+    d_u, d_v = device.buffer(np.ascontiguousarray(u)), device.buffer(np.ascontiguousarray(v))
+    d_P, d_n, d_A, d_c = (device.buffer(nbytes=q) for q in (P_ * 48, P_ * 4, T * 48, 48))
+    d_carry = device.buffer(carry_in) if carry_in is not None else None
     _lib.check(lib.lspiv_stabilize_fit_dev(d_u.c_ptr, d_v.c_ptr, P_, rows, cols, n, o, o, H, W, MODELS[model], r0, r1, int(min_vectors),
                                            d_P.c_ptr, d_n.c_ptr, None))
     _lib.check(lib.lspiv_stabilize_chain_dev(d_P.c_ptr, P_, None if d_carry is None else d_carry.c_ptr, d_A.c_ptr, d_c.c_ptr, None))
-    tr = Transforms(_download(d_A, (T, 2, 3), np.float64), _download(d_P, (P_, 2, 3), np.float64), _download(d_n, (P_,), np.int32),
-                    _download(d_c, (2, 3), np.float64))
+    tr = Transforms(device.download(d_A, (T, 2, 3), np.float64), device.download(d_P, (P_, 2, 3), np.float64), device.download(d_n, (P_,), np.int32),
+                    device.download(d_c, (2, 3), np.float64))
     if (tr.n_used == 0).any():
         warnings.warn(f"stabilize.estimate: {int((tr.n_used == 0).sum())} of {P_} pairs had too few consistent vectors on the stable mask "
                       f"for model {model!r}; their transform is the identity", RuntimeWarning, stacklevel=2)
@@ -132,7 +103,7 @@ def warp(frames, A, out=None):
     or a ``DeviceFrames`` (a ``DeviceFrames`` comes back, the same bits); ``A``: (T, 2, 3).  ``out``: a stack of the same kind, shape and
     dtype to write into (not ``frames`` itself)."""
     lib = _lib.load()
-    a = _check_stack(frames)
+    a = device.check_stack(frames, "stabilize")
     T, H, W = a.shape
     A = np.ascontiguousarray(A, dtype=np.float64)
     if A.shape != (T, 2, 3):
@@ -140,15 +111,14 @@ def warp(frames, A, out=None):
     dev = is_device(a)
     if out is None:
         out = DeviceFrames.empty(a.shape, a.dtype) if dev else np.empty(a.shape, dtype=a.dtype)
-    elif is_device(out) != dev or tuple(out.shape) != a.shape or np.dtype(out.dtype) != np.dtype(a.dtype) or \
-            (not dev and not (isinstance(out, np.ndarray) and out.flags.c_contiguous and out.flags.writeable)):
+    elif not device.out_fits(out, dev, a.dtype) or tuple(out.shape) != a.shape:
         raise ValueError(f"out must be a writable C-contiguous {'DeviceFrames' if dev else 'array'} of shape {a.shape} and dtype {a.dtype}")
     if T == 0:
         return out
     _lib.require_device()
     code = _lib.DTYPE_CODES[np.dtype(a.dtype)]
     if dev:
-        d_A = _device_buffer(A)
+        d_A = device.buffer(A)
         _lib.check(lib.lspiv_warp_affine_dev(a.c_ptr, code, T, H, W, d_A.c_ptr, out.c_ptr, None))
     else:
         if np.shares_memory(a, out):

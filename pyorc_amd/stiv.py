@@ -21,12 +21,10 @@ from typing import NamedTuple, Optional
 
 import numpy as np
 
-from . import _lib
+from . import _lib, device
 from .device import DeviceFrames, is_device
-from .stabilize import _device_buffer, _download
 
 MAX_SMOOTH = 3
-_DTYPES = (np.dtype(np.uint8), np.dtype(np.float32))
 
 
 class Orientation(NamedTuple):
@@ -107,17 +105,6 @@ def lines_across(transect_xy, length: float, direction=None) -> np.ndarray:
     return np.concatenate([p - h * n, p + h * n], axis=1)
 
 
-def _check_stack(frames):
-    a = frames if is_device(frames) else np.asarray(frames)
-    if a.ndim != 3:
-        raise ValueError(f"frames must be (T, H, W), got shape {a.shape}")
-    if np.dtype(a.dtype) not in _DTYPES:
-        raise TypeError(f"stiv works on uint8 and float32 stacks, got {np.dtype(a.dtype)}")
-    if a.shape[1] < 2 or a.shape[2] < 2:
-        raise ValueError(f"frames of {a.shape[1:]} are smaller than 2 x 2")
-    return a if is_device(a) else np.ascontiguousarray(a)
-
-
 def _check_points(points, lines, H, W):
     """Every point finite and inside [0, W - 1] x [0, H - 1]: the ValueError names the first line that is not."""
     ok = (points[..., 0] >= 0.0) & (points[..., 0] <= W - 1) & (points[..., 1] >= 0.0) & (points[..., 1] <= H - 1)   # False for NaN
@@ -136,7 +123,7 @@ def space_time_images(frames, lines, samples: int, out=None, t_offset: int = 0):
     inside [0, W - 1] x [0, H - 1]; ``samples``: L >= 3 points per line, end points included.  ``out``: a space-time image
     (S, T_total, L) of the same kind to write rows ``[t_offset, t_offset + T)`` of -- the other rows are left alone, so a video that comes
     in chunks fills one image."""
-    a = _check_stack(frames)
+    a = device.check_stack(frames, "stiv", side_min=2)
     T, H, W = a.shape
     ln, L = _check_lines(lines, samples)
     S = len(ln)
@@ -150,8 +137,7 @@ def space_time_images(frames, lines, samples: int, out=None, t_offset: int = 0):
         if t_offset:
             raise ValueError(f"t_offset {t_offset} needs out, the space-time image it is a row of")
         out = DeviceFrames.empty((S, T, L), np.float32) if dev else np.empty((S, T, L), dtype=np.float32)
-    elif not (is_device(out) or isinstance(out, np.ndarray)) or is_device(out) != dev or len(out.shape) != 3 or (out.shape[0], out.shape[2]) != (S, L) or out.shape[1] < t_offset + T or \
-            np.dtype(out.dtype) != np.float32 or (not dev and not (out.flags.c_contiguous and out.flags.writeable)):
+    elif not device.out_fits(out, dev, np.float32) or len(out.shape) != 3 or (out.shape[0], out.shape[2]) != (S, L) or out.shape[1] < t_offset + T:
         raise ValueError(f"out must be a writable C-contiguous float32 {'DeviceFrames' if dev else 'array'} of shape ({S}, >= {t_offset + T}, {L}), "
                          f"got {type(out).__name__} {getattr(out, 'shape', None)} {getattr(out, 'dtype', None)}")
     if T == 0 or S == 0:
@@ -212,9 +198,9 @@ def orientation(sti, time_window: Optional[int] = None, time_stride: Optional[in
     lib = _lib.load()
     _lib.require_device()
     if is_device(a):
-        d_t, d_s, d_c = (_device_buffer(nbytes=q.nbytes) for q in (tensor, slope, coh))
+        d_t, d_s, d_c = (device.buffer(nbytes=q.nbytes) for q in (tensor, slope, coh))
         _lib.check(lib.lspiv_sti_orientation_dev(a.c_ptr, S, T, L, Tw, stride, int(smooth), int(bool(detrend)), d_t.c_ptr, d_s.c_ptr, d_c.c_ptr, None))
-        return Orientation(_download(d_t, tensor.shape, np.float64), _download(d_s, slope.shape, np.float64), _download(d_c, coh.shape, np.float64))
+        return Orientation(*(device.download(d, q.shape, np.float64) for d, q in ((d_t, tensor), (d_s, slope), (d_c, coh))))
     a = np.ascontiguousarray(a)
     _lib.check(lib.lspiv_sti_orientation(_lib.ptr(a), S, T, L, Tw, stride, int(smooth), int(bool(detrend)), _lib.ptr(tensor), _lib.ptr(slope),
                                          _lib.ptr(coh)))
@@ -233,7 +219,7 @@ def stiv(frames, lines, samples: int, time_window: Optional[int] = None, time_st
         raise ValueError(f"resolution {resolution!r} must be positive")
     if not (np.isfinite(dt) and dt > 0.0):
         raise ValueError(f"dt {dt!r} must be positive")
-    a = _check_stack(frames)
+    a = device.check_stack(frames, "stiv", side_min=2)
     ln, L = _check_lines(lines, samples)
     time_windows(a.shape[0], L, time_window, time_stride, smooth)      # the window errors before any work
     o = orientation(space_time_images(a, ln, L), time_window, time_stride, smooth, detrend)

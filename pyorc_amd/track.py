@@ -20,13 +20,11 @@ from typing import NamedTuple, Optional
 
 import numpy as np
 
-from . import _lib
+from . import _lib, device
 from .device import DeviceFrames, is_device
-from .stabilize import _device_buffer, _download
 
 MIN_WINDOW, MAX_WINDOW, MAX_LEVELS, MAX_ITER = 5, 31, 5, 100
 STATUS_OK, STATUS_MAX_ITER, STATUS_LOST, STATUS_OUT, STATUS_NOT_FINITE, STATUS_BAD_POINT = 0, 1, 2, 3, 4, 5
-_DTYPES = (np.dtype(np.uint8), np.dtype(np.float32))
 
 
 class Tracks(NamedTuple):
@@ -78,17 +76,6 @@ def level_shapes(H: int, W: int, levels: int):
     return out
 
 
-def _check_stack(frames, t_min: int):
-    a = frames if is_device(frames) else np.asarray(frames)
-    if len(a.shape) != 3:
-        raise ValueError(f"frames must be (T, H, W), got shape {tuple(a.shape)}")
-    if np.dtype(a.dtype) not in _DTYPES:
-        raise TypeError(f"track works on uint8 and float32 stacks, got {np.dtype(a.dtype)}")
-    if a.shape[0] < t_min:
-        raise ValueError(f"{a.shape[0]} frames: at least {t_min} are needed")
-    return a if is_device(a) else np.ascontiguousarray(a)
-
-
 def _check_levels(H, W, levels):
     if isinstance(levels, bool) or not isinstance(levels, (int, np.integer)):
         raise TypeError(f"levels must be an integer, got {levels!r}")
@@ -138,7 +125,7 @@ def pyr_down(frames):
     """One pyramid step: (T, H, W) uint8 or float32 -> (T, (H + 1) // 2, (W + 1) // 2) float32, a host array for a host array and a
     ``DeviceFrames`` for a ``DeviceFrames`` (the same bits).  Taps [1, 4, 6, 4, 1] / 16 along x, then along y, on every second sample,
     the source reflected without repeating the edge; both sides at least 3."""
-    a = _check_stack(frames, 0)
+    a = device.check_stack(frames, "track")
     T, H, W = (int(q) for q in a.shape)
     if min(H, W) < 3:
         raise ValueError(f"frames of {H} x {W} are smaller than 3 x 3")
@@ -171,15 +158,15 @@ def _run(a, pts, per_pair, guess, guess_per_pair, window, levels, max_iter, eps,
     code = _lib.DTYPE_CODES[np.dtype(a.dtype)]
     args = (window, levels, max_iter, eps, min_eig, int(chain))
     if is_device(a):
-        d_p = _device_buffer(pts)
-        d_g = None if guess is None else _device_buffer(guess)
-        d = [_device_buffer(nbytes=q.nbytes) for q in (u, v, err, lam, n_iter, status)]
-        d_xy = _device_buffer(nbytes=xy.nbytes) if chain else None
+        d_p = device.buffer(pts)
+        d_g = None if guess is None else device.buffer(guess)
+        d = [device.buffer(nbytes=q.nbytes) for q in (u, v, err, lam, n_iter, status)]
+        d_xy = device.buffer(nbytes=xy.nbytes) if chain else None
         _lib.check(lib.lspiv_lk_track_dev(a.c_ptr, code, T, H, W, d_p.c_ptr, N, per_pair, None if d_g is None else d_g.c_ptr, guess_per_pair, *args,
                                           *(q.c_ptr for q in d), None if d_xy is None else d_xy.c_ptr, None))
-        u, v, err, lam, n_iter, status = (_download(q, h.shape, h.dtype) for q, h in zip(d, (u, v, err, lam, n_iter, status)))
+        u, v, err, lam, n_iter, status = (device.download(q, h.shape, h.dtype) for q, h in zip(d, (u, v, err, lam, n_iter, status)))
         if chain:
-            xy = _download(d_xy, xy.shape, np.float64)
+            xy = device.download(d_xy, xy.shape, np.float64)
     else:
         _lib.check(lib.lspiv_lk_track(_lib.ptr(a), code, T, H, W, _lib.ptr(pts), N, per_pair, None if guess is None else _lib.ptr(guess),
                                       guess_per_pair, *args, _lib.ptr(u), _lib.ptr(v), _lib.ptr(err), _lib.ptr(lam), _lib.ptr(n_iter), _lib.ptr(status),
@@ -188,7 +175,7 @@ def _run(a, pts, per_pair, guess, guess_per_pair, window, levels, max_iter, eps,
 
 
 def _prepare(frames, points, window, levels, max_iter, eps, min_eig, guess, chain=False):
-    a = _check_stack(frames, 2)
+    a = device.check_stack(frames, "track", t_min=2)
     T, H, W = (int(q) for q in a.shape)
     window, max_iter, eps, min_eig = _check_params(window, max_iter, eps, min_eig)
     levels = _check_levels(H, W, levels)
@@ -223,7 +210,7 @@ def track_grid(frames, window_size: int, overlap: Optional[int] = None, **kw) ->
     ``min_eig``, ``guess`` ((T - 1, rows, cols, 2) or (rows, cols, 2))."""
     from . import window as _window
 
-    a = _check_stack(frames, 2)
+    a = device.check_stack(frames, "track", t_min=2)
     H, W = int(a.shape[1]), int(a.shape[2])
     ov = int(window_size) // 2 if overlap is None else int(overlap)
     x, y = _window.get_rect_coordinates((H, W), (int(window_size),) * 2, (ov, ov))

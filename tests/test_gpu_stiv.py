@@ -91,6 +91,21 @@ def test_chunks_through_t_offset_fill_the_same_image(gpu, dtype):
         assert _same_bits(got[:, 2:T + 2], want) and (got[:, :2] == -7.0).all() and (got[:, T + 2:] == -7.0).all()
 
 
+@pytest.mark.parametrize("dtype", [np.uint8, np.float32], ids=["uint8", "float32"])
+def test_host_upload_chunks_give_the_references_bits(gpu, monkeypatch, dtype):
+    """The host twin's frames go up in chunks (LSPIV_HOST_CHUNK_BYTES, default 256 MiB): 2 + 2 + 2 + 1 frames, then one frame at a time."""
+    shape, T, L = SHAPES[1], 7, 65
+    lines = _lines(*shape)
+    f = _frames(dtype, T, shape)
+    want = sr.space_time_images(f, sr.line_points(lines, L))
+    for chunk_bytes in (2 * f[0].nbytes, 1):                           # two frames; below one frame: chunks of one frame
+        monkeypatch.setenv("LSPIV_HOST_CHUNK_BYTES", str(chunk_bytes))
+        assert _same_bits(stiv.space_time_images(f, lines, L), want), chunk_bytes
+        out = np.full((len(lines), T + 3, L), -7.0, dtype=np.float32)
+        assert stiv.space_time_images(f, lines, L, out=out, t_offset=2) is out
+        assert _same_bits(out[:, 2:T + 2], want) and (out[:, :2] == -7.0).all() and (out[:, T + 2:] == -7.0).all(), chunk_bytes
+
+
 # ---- orientation ------------------------------------------------------------------------------------------------------------------------
 def _within_gates(got, ref):
     """NaN exactly where the reference has it, everything else within the gates; returns the worst tensor error over the trace."""

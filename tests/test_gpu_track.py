@@ -171,6 +171,20 @@ def test_workspace_batches_give_the_same_bits(gpu, monkeypatch):
         assert _same_bits(t.xy, whole_traj.xy) and _same_tracks(t, whole_traj), frames_fit
 
 
+def test_host_upload_chunks_give_the_same_bits(gpu, monkeypatch):
+    """The host twin's frames go up in chunks with one frame of halo (LSPIV_HOST_CHUNK_BYTES, default 256 MiB): pairs 2 + 2, then 1 + 1 + 1 + 1."""
+    shape, kind, T, N, w, L = ti.CHUNK_CASE
+    f, p = ti.scene(shape, T, kind), ti.points(shape, N)
+    g = ti.guess_for(ti.CHUNK_CASE)
+    whole = track.track_pairs(f, p, window=w, levels=L, guess=g)
+    whole_traj = track.trajectories(f, p, window=w, levels=L)
+    for chunk_bytes in (3 * f[0].nbytes, 0):                           # three frames: two pairs per upload; below two frames: one pair
+        monkeypatch.setenv("LSPIV_HOST_CHUNK_BYTES", str(chunk_bytes))
+        assert _same_tracks(track.track_pairs(f, p, window=w, levels=L, guess=g), whole), chunk_bytes
+        t = track.trajectories(f, p, window=w, levels=L)
+        assert _same_bits(t.xy, whole_traj.xy) and _same_tracks(t, whole_traj), chunk_bytes
+
+
 @pytest.mark.parametrize("device", [False, True], ids=["host", "DeviceFrames"])
 def test_trajectories_are_the_loop_of_one_pair_calls(gpu, device):
     shape, kind, T, N, w, L = ti.TRAJ_CASE

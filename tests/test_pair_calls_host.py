@@ -1,5 +1,5 @@
 """What the per-pair PIV wrappers of ``pyorc_amd.piv`` send to the library, pinned call by call.  Host-only: ``_lib.load`` is replaced
-by a recording fake, no native code is loaded and no kernel is looked at.
+by a recording fake (tests/fake_lib.py), no native code is loaded and no kernel is looked at.
 
 Every case runs one public call on a 4-frame 96 x 112 stack (host uint8, host float64, ``DeviceFrames``) and compares the list of
 library calls it made -- name and arguments -- with a literal below.  Scalars are recorded as they are (floats rounded to 6 places,
@@ -13,95 +13,17 @@ reference goes, which is no property of the calls); instead every block a case a
 The order of the ``lspiv_dev_malloc`` calls is kept as it was, so the block indices need no translation into roles.
 """
 
-import ctypes as C
 import gc
 
 import numpy as np
 import pytest
 
-from pyorc_amd import _lib, device, piv, window
+from pyorc_amd import device, piv, window
+from tests.fake_lib import fake  # noqa: F401  (the fixture)
 
 T, H, W = 4, 96, 112
 P = T - 1
 GRID = (5, 6)        # 32 px windows at overlap 16 on 96 x 112
-_QUERIES = ("lspiv_device_count", "lspiv_get_device", "lspiv_get_option", "lspiv_grid_shape")   # answered like `*_supported`, not recorded
-
-
-class FakeLib:
-    """Stands in for the ctypes library: every attribute is a function that records its call and returns 0."""
-
-    def __init__(self):
-        self.calls, self.blocks, self.freed, self.arrays = [], [], [], {}
-        self._next = 1 << 40      # far from every host address
-
-    def _ptr(self, p):
-        v = p.value if isinstance(p, C.c_void_p) else int(p)
-        if not v:
-            return None
-        for k, (base, size) in enumerate(self.blocks):
-            if base <= v < base + size:
-                return (k, v - base)
-        for name, a in self.arrays.items():
-            if a.ctypes.data <= v < a.ctypes.data + max(a.nbytes, 1):
-                return name if v == a.ctypes.data else (name, v - a.ctypes.data)
-        return "host"
-
-    def _norm(self, a):
-        if a is None:
-            return None
-        if isinstance(a, C.c_void_p):
-            return self._ptr(a)
-        if isinstance(a, C.Array):
-            return tuple(a)
-        if isinstance(a, (bool, np.bool_)):
-            return bool(a)
-        if isinstance(a, (float, np.floating)):
-            return round(float(a), 6)
-        if isinstance(a, (int, np.integer)):
-            return int(a)
-        if isinstance(a, bytes):
-            return a.decode()
-        return "ref"      # ctypes.byref(...)
-
-    def __getattr__(self, name):
-        def call(*args):
-            if name == "lspiv_device_count":
-                args[0]._obj.value = 1
-            elif name == "lspiv_get_device":
-                args[0]._obj.value = 0
-            elif name == "lspiv_get_option":
-                args[1]._obj.value = 1 if args[0] == b"norm_clip" else 0
-            elif name == "lspiv_grid_shape":
-                dim_y, dim_x, wy, wx, oy, ox = (int(q) for q in args[:6])
-                args[6]._obj.value = 0 if dim_y < wy else (dim_y - wy) // (wy - oy) + 1
-                args[7]._obj.value = 0 if dim_x < wx else (dim_x - wx) // (wx - ox) + 1
-            if name.endswith("_supported"):
-                return 1
-            if name in _QUERIES:
-                return 0
-            if name == "lspiv_dev_free":
-                self.freed.append(self._ptr(args[0]))
-                return 0
-            if name == "lspiv_dev_malloc":
-                size = int(args[1])
-                args[0]._obj.value = self._next
-                self.blocks.append((self._next, size))
-                self._next += max(1 << 20, (size + 0xfffff) & ~0xfffff)
-                self.calls.append((name, "ref", size))
-                return 0
-            self.calls.append((name,) + tuple(self._norm(a) for a in args))
-            return 0
-        return call
-
-
-@pytest.fixture
-def fake(monkeypatch):
-    lib = FakeLib()
-    monkeypatch.setattr(_lib, "load", lambda: lib)
-    pool = device._Pool()
-    pool.limit = 0        # no cached blocks: every DeviceFrames.empty is one lspiv_dev_malloc, every release one lspiv_dev_free
-    monkeypatch.setattr(device, "_pool", pool)
-    return lib
 
 
 def _arrays(kind):
