@@ -1,7 +1,10 @@
 """GPU tests of pyramidal Lucas-Kanade point tracking against tests/track_ref.py, on the inputs that
 tests/test_track_host.py qualified: the pyramid bit for bit; the tracker with fixed iteration counts (unconverged states, where any
 arithmetic slip shows) and converged, with status and n_iter equal on every point and u, v within 1e-9 px; the same bits from run to
-run, from the host twin and DeviceFrames, from time slices, from workspace batches, and from trajectories against one-pair calls."""
+run, from the host twin and DeviceFrames, from time slices, from workspace batches, and from trajectories against one-pair calls.
+Every one of the 28 (window, dtype) instances of the kernel runs against the reference in four modes and, against the reference summed
+in the kernel's order, bit for bit in two (ti.VARIANT_CASES); so do scenes with a NaN, +inf or -inf sample and guesses beyond the index
+clamp; five levels go through the batch, chunk and chain loops."""
 
 import numpy as np
 import pytest
@@ -114,6 +117,63 @@ def test_the_kernels_sums_are_the_lane_trees_bits(gpu):
         assert all(_same_bits(getattr(got, n), ref[n]) for n in FIELDS)
 
 
+# ---- every instance of the kernel: ti.VARIANT_CASES, one (window, dtype) per id ------------------------------------------------------------
+def _run(case, mode):
+    shape, kind, T, N, w, L = case
+    return track.track_pairs(ti.scene(shape, T, kind), ti.points(shape, N), **ti.kwargs(case, mode))
+
+
+def _parity(case, modes):
+    """Every mode against the float64 reference; eps = 0: no level ever converges, so every level runs max_iter iterations."""
+    family = "registers" if case[4] <= ti.REG_WINDOW else "patch"
+    for mode in modes:
+        got, ref = _run(case, mode), ti.reference(case, mode)
+        worst = _check_against_reference(got, ref, case, mode)
+        print(ti.case_id(case), mode, f"({family})", "largest difference:", ", ".join(f"{k} {v:.1e}" for k, v in worst.items()))
+        for lost in (tr.STATUS_OUT, tr.STATUS_NOT_FINITE):
+            assert (got.status[ref["status"] == lost] == lost).all()
+        if mode == "fixed2":
+            alive = got.status < 2
+            assert (got.status[alive] == 1).all() and (got.n_iter[alive] == case[5] * 2).all()
+
+
+def _lane_bits(case, modes):
+    """With the reference's sums in the kernel's order nothing is left to differ: the same bits in every field."""
+    for mode in modes:
+        got, ref = _run(case, mode), ti.reference(case, mode, "lanes")
+        for n in FIELDS:
+            assert _same_bits(getattr(got, n), ref[n]), (mode, n)
+
+
+@pytest.mark.parametrize("case", ti.VARIANT_CASES, ids=ti.case_id)
+def test_every_instance_is_the_references(gpu, case):
+    _parity(case, ti.VARIANT_MODES)
+
+
+@pytest.mark.parametrize("case", ti.VARIANT_CASES, ids=ti.case_id)
+def test_every_instances_sums_are_the_lane_trees_bits(gpu, case):
+    _lane_bits(case, ti.LANE_MODES)
+
+
+@pytest.mark.parametrize("case", ti.NOT_FINITE_CASES, ids=ti.case_id)
+def test_a_sample_that_is_not_finite_is_status_4_where_the_reference_has_it(gpu, case):
+    _parity(case, ti.VARIANT_MODES)
+    _lane_bits(case, ti.LANE_MODES)
+    got = _run(case, "converge")
+    assert (got.status == tr.STATUS_NOT_FINITE).any(axis=1).all()       # in pair 0 (the sample is in J) and in pair 1 (in the template)
+    assert np.isnan(got.u[got.status == tr.STATUS_NOT_FINITE]).all()
+
+
+@pytest.mark.parametrize("case", ti.FAR_CASES, ids=ti.case_id)
+def test_a_guess_beyond_the_index_clamp_walks_out_after_one_iteration(gpu, case):
+    """Guesses of 1e12 and -3e9 px: split() clamps the position at +-2^30 and bilinear() the indices to the level, as the reference does."""
+    _parity(case, ("far-guess",))
+    _lane_bits(case, ("far-guess",))
+    got = _run(case, "far-guess")
+    far = sorted(ti.FAR_POINTS)
+    assert (got.status[:, far] == tr.STATUS_OUT).all() and (got.n_iter[:, far] == 1).all() and np.isnan(got.u[:, far]).all()
+
+
 def test_a_point_that_is_not_finite_has_status_5_through_the_c_abi(gpu):
     shape, T, N = (33, 47), 3, 5
     f = ti.scene(shape, T, "uint8")
@@ -183,6 +243,44 @@ def test_host_upload_chunks_give_the_same_bits(gpu, monkeypatch):
         assert _same_tracks(track.track_pairs(f, p, window=w, levels=L, guess=g), whole), chunk_bytes
         t = track.trajectories(f, p, window=w, levels=L)
         assert _same_bits(t.xy, whole_traj.xy) and _same_tracks(t, whole_traj), chunk_bytes
+
+
+# ---- five levels (MAX_LEVELS) through the batch, chunk and chain loops: ti.FIVE_LEVEL_CASE, three frames ---------------------------------------
+def test_five_levels_in_workspace_batches_give_the_same_bits(gpu, monkeypatch):
+    """per_frame sums four levels: a cap of three frames (both pairs in one batch), of two frames (one pair per batch) and of 0 (below
+    the minimum of two frames)."""
+    shape, kind, T, N, w, L = ti.FIVE_LEVEL_CASE
+    f, p = ti.scene(shape, T, kind), ti.points(shape, N)
+    kw = ti.kwargs(ti.FIVE_LEVEL_CASE, "converge-guess")
+    whole = track.track_pairs(f, p, **kw)
+    assert L == 5 == track.MAX_LEVELS and len(track.level_shapes(*shape, L)) == 5
+    per_frame = sum(h * ww for h, ww in track.level_shapes(*shape, L)[1:]) * 4
+    for frames_fit in (3, 2, 0):
+        monkeypatch.setenv("LSPIV_TRACK_WS_BYTES", str(frames_fit * per_frame))
+        assert _same_tracks(track.track_pairs(f, p, **kw), whole), frames_fit
+        assert _same_tracks(track.track_pairs(DeviceFrames.from_host(f), p, **kw), whole), frames_fit
+
+
+def test_five_levels_in_host_upload_chunks_give_the_same_bits(gpu, monkeypatch):
+    """LSPIV_HOST_CHUNK_BYTES at three frames (both pairs in one upload) and at 0 (one pair per upload)."""
+    shape, kind, T, N, w, L = ti.FIVE_LEVEL_CASE
+    f, p = ti.scene(shape, T, kind), ti.points(shape, N)
+    kw = ti.kwargs(ti.FIVE_LEVEL_CASE, "converge-guess")
+    whole = track.track_pairs(f, p, **kw)
+    for chunk_bytes in (3 * f[0].nbytes, 0):
+        monkeypatch.setenv("LSPIV_HOST_CHUNK_BYTES", str(chunk_bytes))
+        assert _same_tracks(track.track_pairs(f, p, **kw), whole), chunk_bytes
+
+
+@pytest.mark.parametrize("device", [False, True], ids=["host", "DeviceFrames"])
+def test_five_level_trajectories_are_the_references(gpu, device):
+    shape, kind, T, N, w, L = ti.FIVE_LEVEL_CASE
+    f, p0 = ti.scene(shape, T, kind), ti.points(shape, N)
+    got = track.trajectories(DeviceFrames.from_host(f) if device else f, p0, window=w, levels=L)
+    ref = ti.reference_trajectories(ti.FIVE_LEVEL_CASE)
+    assert np.array_equal(got.status, ref["status"]) and np.array_equal(got.n_iter, ref["n_iter"])
+    assert np.array_equal(np.isnan(got.xy), np.isnan(ref["xy"])) and np.nanmax(np.abs(got.xy - ref["xy"])) <= (T - 1) * GATE_D
+    assert _same_bits(got.xy[0], p0) and (got.status[-1] < 2).any() and (got.status == tr.STATUS_BAD_POINT).any()
 
 
 @pytest.mark.parametrize("device", [False, True], ids=["host", "DeviceFrames"])

@@ -13,7 +13,8 @@ from tests import track_inputs as ti
 from tests import track_ref as tr
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-ALL_RUNS = [(c, m) for c in ti.CASES for m in ti.MODES]
+VARIANT_RUNS = [(c, m) for c in ti.VARIANT_CASES for m in ti.VARIANT_MODES]
+ALL_RUNS = [(c, m) for c in ti.CASES for m in ti.MODES] + VARIANT_RUNS + ti.EXTRA_RUNS
 RUN_IDS = [f"{ti.case_id(c)}-{m}" for c, m in ALL_RUNS]
 
 
@@ -31,7 +32,7 @@ def test_no_decision_of_a_shared_input_sits_on_its_threshold(case, mode):
 @pytest.mark.parametrize("case,mode", ALL_RUNS, ids=RUN_IDS)
 def test_the_order_of_the_float64_sums_moves_nothing_that_counts(case, mode):
     """numpy's pairwise sums against the kernel's order (64 lanes, k ascending on a lane, then the halving tree): the same status and
-    n_iter on every point, d within 1e-9 px (measured: at most 7e-16)."""
+    n_iter on every point, d within 1e-9 px (measured: at most 7e-16 on CASES, 1.1e-15 on the variant, non-finite and far-guess runs)."""
     a, b = ti.reference(case, mode), ti.reference(case, mode, "lanes")
     assert np.array_equal(a["status"], b["status"]) and np.array_equal(a["n_iter"], b["n_iter"])
     worst = 0.0
@@ -66,6 +67,88 @@ def test_the_shared_inputs_cover_every_status_and_kind_of_point():
     assert lost_more > 0                                         # min_eig > 0 drops points that the determinant test keeps
     bad = tr.track_pairs(ti.scene(shape, 2, "uint8"), np.array([[5.0, np.nan], [20.0, 20.0]]), window=9, levels=2)
     assert bad["status"][0, 0] == tr.STATUS_BAD_POINT and np.isnan(bad["min_eig"][0, 0]) and bad["status"][0, 1] < 2
+
+
+def test_the_variant_cases_cover_every_instance_of_the_kernel_and_keep_their_points():
+    """The 28 (window, dtype) instances once each; five levels in both families and both dtypes; and caps on the lost points that the
+    reference alone must meet: in mode "converge" at least half of every case's points are tracked, 60 % at five levels."""
+    pairs = [(c[4], c[1]) for c in ti.VARIANT_CASES]
+    assert sorted(pairs) == sorted((w, kind) for w in range(tr.MIN_WINDOW, tr.MAX_WINDOW + 1, 2) for kind in ("uint8", "float32")) and len(pairs) == 28
+    assert tr.MAX_LEVELS == 5
+    for kind in ("uint8", "float32"):
+        assert any(c[1] == kind and c[5] == 5 and c[4] <= ti.REG_WINDOW for c in ti.VARIANT_CASES), kind
+        assert any(c[1] == kind and c[5] == 5 and c[4] > ti.REG_WINDOW for c in ti.VARIANT_CASES), kind
+    assert ti.FIVE_LEVEL_CASE in ti.VARIANT_CASES and ti.FIVE_LEVEL_CASE[5] == 5 and ti.FIVE_LEVEL_CASE[2] == 3
+    assert {c[5] for c in ti.VARIANT_CASES} == {1, 2, 3, 4, 5} and {c[2] for c in ti.VARIANT_CASES} == {2, 3}
+    for case in ti.VARIANT_CASES:
+        shape, kind, T, N, w, L = case
+        assert N == ti.VARIANT_N == 65 and max(shape) <= 128           # (the scene's periodic canvas has 128 samples a side)
+        tracked = float((ti.reference(case, "converge")["status"] < 2).mean())
+        print(ti.case_id(case), f"tracked in mode converge: {tracked:.3f}")
+        assert tracked >= (0.6 if L == 5 else 0.5), (case, tracked)
+
+
+@pytest.mark.parametrize("case", ti.VARIANT_CASES, ids=ti.case_id)
+def test_the_variant_cases_min_eig_splits_the_points(case):
+    """A condition on the input: of the points that pass the determinant test without min_eig (status other than 2 in mode "converge"),
+    the case's own min_eig loses at least 10 % (status 2) and keeps at least 10 %, so `lam < min_eig` is taken both ways."""
+    plain, own = ti.reference(case, "converge")["status"], ti.reference(case, "converge-min-eig")["status"]
+    assert ti.kwargs(case, "converge-min-eig")["min_eig"] == ti.min_eig_for(case) > 0.0
+    passed = plain != tr.STATUS_LOST
+    lost = float((own[passed] == tr.STATUS_LOST).mean())
+    print(ti.case_id(case), f"min_eig {ti.min_eig_for(case):.4g}: loses {lost:.3f} of {passed.sum()} points")
+    assert lost >= 0.1 and 1.0 - lost >= 0.1
+    assert not (own[~passed] != tr.STATUS_LOST).any()                 # (min_eig only ever loses points)
+    assert all(ti.kwargs(c, "converge-min-eig")["min_eig"] == 30.0 for c in ti.CASES)
+
+
+@pytest.mark.parametrize("case", ti.NOT_FINITE_CASES, ids=ti.case_id)
+def test_a_sample_that_is_not_finite_reaches_some_windows_and_spares_others(case):
+    """Conditions on the non-finite scenes: in every mode some point has status 4 and at least a third of the points are tracked."""
+    shape, kind, T, N, w, L = case
+    value, at = ti.NOT_FINITE[kind]
+    f = ti.scene(shape, T, kind)
+    bad = ~np.isfinite(f)
+    assert bad.sum() == 1 and bad[(1,) + at(*shape)] and T == 3 and L in (1, 2)
+    assert np.isnan(value) or f[(1,) + at(*shape)] == value
+    for mode in ti.VARIANT_MODES:
+        st = ti.reference(case, mode)["status"]
+        print(ti.case_id(case), mode, "points per status:", np.bincount(st.ravel(), minlength=6))
+        assert (st == tr.STATUS_NOT_FINITE).any(axis=1).all()           # in pair 0 (the sample is in J) and in pair 1 (in the template)
+        assert (st < 2).mean() >= 1.0 / 3.0
+
+
+def test_the_non_finite_and_far_guess_runs_cover_both_families():
+    for kind in ti.NOT_FINITE:
+        ws = [c[4] for c in ti.NOT_FINITE_CASES if c[1] == kind]
+        assert len(ws) == 2 and min(ws) <= ti.REG_WINDOW < max(ws), kind
+    assert {c[5] for c in ti.NOT_FINITE_CASES if c[4] <= ti.REG_WINDOW} == {1, 2} == {c[5] for c in ti.NOT_FINITE_CASES if c[4] > ti.REG_WINDOW}
+    assert len(ti.FAR_CASES) == 2 and min(c[4] for c in ti.FAR_CASES) <= ti.REG_WINDOW < max(c[4] for c in ti.FAR_CASES)
+    for case in ti.FAR_CASES:
+        assert case in ti.VARIANT_CASES and case[5] == 3
+        far = sorted(ti.FAR_POINTS)
+        g = ti.kwargs(case, "far-guess")["guess"]
+        assert np.abs(g[:, far]).max() == 1e12 and np.abs(np.ldexp(g[:, far], -2)).max(axis=2).min() > 2.0 ** 29   # (split() clamps at 2^30)
+        near, r = ti.reference(case, "converge-guess"), ti.reference(case, "far-guess")
+        assert (near["status"][:, far] < 2).all()                       # tracked with the plain guess
+        assert (r["status"][:, far] == tr.STATUS_OUT).all() and (r["n_iter"][:, far] == 1).all()
+        rest = np.setdiff1d(np.arange(case[3]), far)
+        assert all(np.array_equal(near[n][:, rest], r[n][:, rest], equal_nan=n != "n_iter" and n != "status") for n in ("u", "v", "status", "n_iter"))
+    # the reference's own clamp holds up to the largest guesses: no error, the same status
+    case = ti.FAR_CASES[0]
+    shape, kind, T, N, w, L = case
+    g = ti.guess_for(case)
+    g[:, 0], g[:, 8] = (1e300, -1e300), (-1e300, 0.3)
+    r = tr.track_pairs(ti.scene(shape, T, kind), ti.points(shape, N), window=w, levels=L, guess=g)
+    assert (r["status"][:, [0, 8]] == tr.STATUS_OUT).all() and (r["n_iter"][:, [0, 8]] == 1).all()
+
+
+def test_trajectories_of_the_reference_at_five_levels_keep_their_margins():
+    shape, kind, T, N, w, L = ti.FIVE_LEVEL_CASE
+    r = ti.reference_trajectories(ti.FIVE_LEVEL_CASE)
+    print(ti.case_id(ti.FIVE_LEVEL_CASE), r["margins"], "points per status:", np.bincount(r["status"].ravel(), minlength=6))
+    assert r["margins"].smallest() > 1e-8
+    assert (r["status"][-1] < 2).mean() >= 0.5 and (r["status"] == tr.STATUS_BAD_POINT).any()
 
 
 def test_trajectories_of_the_reference_chain_the_pairs():
