@@ -323,9 +323,8 @@ static int ensemble_launch(lspiv_ensemble* h, DeviceCtx* c, const void* d_frames
     LSPIV_TRY(sliding_reserve(h, (size_t)(blk0 + nb), s));
     // the slot layout is the store's for the whole run: what the first call wrote is what lspiv_ensemble_sliding_finish decodes
     const bool walking = kind_walks(kind) && walk != 0;
-    int lane_major = 0; bool split = false;
-    if (walking) lspiv::walk_ensemble_slot_layout(h->wy, &lane_major, &split);
-    if (split) return fail(LSPIV_EUNSUPPORTED, "sliding ensemble: not available in a build with LSPIV_ENS_SPLIT_HALVES (the split slot layout depends on the call)");
+    int lane_major = 0;
+    if (walking) lspiv::walk_ensemble_slot_layout(h->wy, &lane_major);
     const int layout = lane_major ? 2 : 1;
     if (h->sl_layout && h->sl_layout != layout)
       return fail(LSPIV_EINVAL, "sliding ensemble: the 'walk' setting (LSPIV_WALK) changed between accumulate calls; the block store of a %d x %d window holds %s slots and this call would write %s ones",

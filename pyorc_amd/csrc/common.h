@@ -718,14 +718,13 @@ inline WalkSegments walk_segments(uint32_t n_pairs, int64_t pair_offset, uint32_
 // concurrent lane groups of a kernel that runs `waves_per_simd` waves with `groups` jobs per wave (CU count queried once)
 uint32_t job_slots(int waves_per_simd, int groups);
 // lane_major_n: 0 = the partial sums are fft-shifted row-major planes like corr_sum; N = the N x N slots of the 64 x 64 walking
-// ensemble kernel, element (row y, column x) at slot[(x / 4) * 4 N + y * 4 + x % 4], un-shifted (piv_fft_impl.h, slot_accumulate);
-// split_halves: the first and the second half of every slot live in two arrays, all first halves, then all second halves (kEnsSplitHalves)
+// ensemble kernel, element (row y, column x) at slot[(x / 4) * 4 N + y * 4 + x % 4], un-shifted (piv_fft_impl.h, slot_accumulate_half)
 hipError_t launch_ensemble_merge(const float* part_sum, const float* part_cnt, uint32_t n_seg, uint32_t n_win, int plane_elems,
-                                 float* corr_sum, float* corr_count, hipStream_t s, int lane_major_n = 0, bool split_halves = false);
+                                 float* corr_sum, float* corr_count, hipStream_t s, int lane_major_n = 0);
 hipError_t launch_ensemble_mean(const float* sum, const float* count, float min_count, uint32_t n_win,
                                 int plane_elems, float* mean, hipStream_t s);
-// the slot layout the walking ensemble kernel of an n x n window writes (the lane_major_n / split_halves of launch_ensemble_merge)
-void walk_ensemble_slot_layout(int n, int* lane_major_n, bool* split_halves);
+// the slot layout the walking ensemble kernel of an n x n window writes (the lane_major_n of launch_ensemble_merge)
+void walk_ensemble_slot_layout(int n, int* lane_major_n);
 // sliding ensemble: for the outputs j0 .. j0 + n_out - 1, mean[(j - j0) * n_win + w] = the fft-shifted row-major mean plane of the q
 // block slots (j .. j + q - 1, w) of `store` added in block order, NaN where the added counts are < min_count; count_out likewise
 hipError_t launch_ensemble_sliding_mean(const float* store, const float* store_cnt, uint32_t q, int64_t j0, uint32_t n_out, uint32_t n_win,

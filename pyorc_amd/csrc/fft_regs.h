@@ -159,6 +159,7 @@ struct TwiddleRow {
 // 3.3: a length folds when none of its kernels pays for it in registers, scratch or waves.  16 does; 32 and 64 do not as lengths,
 // but the walking per-pair kernel of 32 x 32 (the flagship) is clean in all its instantiations and folds on its own (kFftFoldWalk32) --
 // which is what LSPIV_FFT_SR=0 leaves it on: by default it runs on the split-radix form below, and SR goes before FOLD.
+// (override kept: tools/kres.py applies the resource rule to a new compiler through it)
 #ifdef LSPIV_FFT_FOLD
 constexpr bool kFftFold16 = LSPIV_FFT_FOLD, kFftFold32 = LSPIV_FFT_FOLD, kFftFold64 = LSPIV_FFT_FOLD, kFftFoldWalk32 = LSPIV_FFT_FOLD;
 #else
@@ -249,6 +250,7 @@ __host__ __device__ __forceinline__ void twiddled_bfly8(float (&r)[8], float (&i
 // kernel); left alone, the adoption is DESIGN.md 3.3: by the resource rule 64 and 32 as lengths do not qualify (scratch at 256 VGPRs;
 // the 32 x 32 ensemble kernels sit at 168), 16 does but for one search kernel and was no faster with the rescue pass off, and the
 // walking per-pair kernel of 32 x 32 -- clean in all twelve instantiations, faster in every run -- takes it on its own (kFftSrWalk32).
+// (override kept: tools/kres.py applies the resource rule to a new compiler through it)
 #ifdef LSPIV_FFT_SR
 constexpr bool kFftSr16 = LSPIV_FFT_SR, kFftSr32 = LSPIV_FFT_SR, kFftSr64 = LSPIV_FFT_SR, kFftSrWalk32 = LSPIV_FFT_SR;
 #else
@@ -424,16 +426,11 @@ __host__ __device__ __forceinline__ void fft64_col(const float (&xr)[64], const 
   for (int k2 = 0; k2 < 8; ++k2) { yr[K1 + 8 * k2] = r[k2]; yi[K1 + 8 * k2] = i[k2]; }
 }
 
-// LSPIV_FFT64_SB: scheduling barriers between the butterflies of the two stages -- left alone the scheduler interleaves
-// several column transforms for ILP, which stretches live ranges in the register-bound 64 x 64 kernels
-#ifndef LSPIV_FFT64_SB
-#define LSPIV_FFT64_SB 1
-#endif
-#ifndef LSPIV_FFT64_PRIO
-#define LSPIV_FFT64_PRIO 0
-#endif
+// Scheduling barriers between the butterflies of the two stages -- left alone the scheduler interleaves several column transforms
+// for ILP, which stretches live ranges in the register-bound 64 x 64 kernels.  (Raising the second stage's priority with s_setprio
+// was an A/B variant after round 3 and was not adopted.)
 #if defined(__HIP_DEVICE_COMPILE__)
-#define LSPIV_FFT64_BAR do { if (LSPIV_FFT64_SB) __builtin_amdgcn_sched_barrier(0); } while (0)
+#define LSPIV_FFT64_BAR __builtin_amdgcn_sched_barrier(0)
 #else
 #define LSPIV_FFT64_BAR do { } while (0)
 #endif
@@ -451,9 +448,6 @@ __host__ __device__ __forceinline__ void fft64(float (&xr)[64], float (&xi)[64])
     LSPIV_FFT64_BAR;
   }
   float yr[64], yi[64];
-#if LSPIV_FFT64_PRIO && defined(__HIP_DEVICE_COMPILE__)
-  __builtin_amdgcn_s_setprio(1);   // A/B variant: the second radix stage ahead of a neighbour's first
-#endif
   fft64_col<INV, 0, CLAMP, FOLD>(xr, xi, yr, yi); LSPIV_FFT64_BAR;
   fft64_col<INV, 1, CLAMP, FOLD>(xr, xi, yr, yi); LSPIV_FFT64_BAR;
   fft64_col<INV, 2, CLAMP, FOLD>(xr, xi, yr, yi); LSPIV_FFT64_BAR;
@@ -462,9 +456,6 @@ __host__ __device__ __forceinline__ void fft64(float (&xr)[64], float (&xi)[64])
   fft64_col<INV, 5, CLAMP, FOLD>(xr, xi, yr, yi); LSPIV_FFT64_BAR;
   fft64_col<INV, 6, CLAMP, FOLD>(xr, xi, yr, yi); LSPIV_FFT64_BAR;
   fft64_col<INV, 7, CLAMP, FOLD>(xr, xi, yr, yi); LSPIV_FFT64_BAR;
-#if LSPIV_FFT64_PRIO && defined(__HIP_DEVICE_COMPILE__)
-  __builtin_amdgcn_s_setprio(0);
-#endif
 #pragma unroll
   for (int k = 0; k < 64; ++k) { xr[k] = yr[k]; xi[k] = yi[k]; }
 }

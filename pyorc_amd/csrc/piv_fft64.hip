@@ -7,8 +7,7 @@ hipError_t launch_piv_fft64(const PivParams& p, int dtype, bool ensemble, hipStr
   return launch_fft<64>(p, dtype, ensemble, s);
 }
 // what launch_t hands launch_ensemble_merge: only the 64 x 64 kernel departs from fft-shifted row-major slots
-void walk_ensemble_slot_layout(int n, int* lane_major_n, bool* split_halves) {
-  *lane_major_n = (n == 64 && kEnsLdsRmw<64>) ? 64 : 0;
-  *split_halves = n == 64 && kEnsSplitHalves<64>;
+void walk_ensemble_slot_layout(int n, int* lane_major_n) {
+  *lane_major_n = (n == 64 && kEnsHalfAcc<64>) ? 64 : 0;
 }
 }  // namespace lspiv

@@ -162,12 +162,6 @@ __device__ __forceinline__ float tree_sum(const float (&x)[N]) {
   return s[0];
 }
 
-#ifndef LSPIV_ENS64_NT
-#define LSPIV_ENS64_NT 0   // 1: non-temporal frame loads in the 64 x 64 ensemble kernel (RowRaw::fetch<NT>).  Measured and left OFF (round 6):
-                           // written bytes 26.9 -> 21.4 GB only, fetched 3.3 -> 15.4 GB (the 75 % overlap of the windows lives on L2 hits
-                           // of the frame lines, which non-temporal loads give up), 28.7 -> 31.5 ms.  What evicts the slots is their own
-                           // address pattern, not the frames: see kEnsSplitHalves below
-#endif
 // ---- one tile row as fetched from HBM -----------------------------------------------------------
 // uint8 rows are N/4 dwords, cheap enough to prefetch for BOTH windows of a job before any arithmetic
 // starts; float rows are N..2N dwords, so only their address is kept and the load is issued where the
@@ -182,13 +176,10 @@ template <int N>
 struct RowRaw<uint8_t, N> {
   static constexpr int W = (N + 3) / 4;   // N % 4 == 2: the last word holds two samples and two zero bytes
   uint32_t w[W];
-  // NT: non-temporal loads -- the frame bytes stream through the L2 without displacing what lives there (an A/B switch of the 64 x 64
-  // ensemble kernel, LSPIV_ENS64_NT; off: it costs the frame lines' own reuse more than it saves)
-  template <bool NT = false>
   __device__ __forceinline__ void fetch(const uint8_t* q) {
 #pragma unroll
     for (int k = 0; k < N / 16; ++k) {
-      const u32x4 v = NT ? __builtin_nontemporal_load(reinterpret_cast<const u32x4_u*>(q + 16 * k)) : *reinterpret_cast<const u32x4_u*>(q + 16 * k);
+      const u32x4 v = *reinterpret_cast<const u32x4_u*>(q + 16 * k);
       w[4 * k] = v[0]; w[4 * k + 1] = v[1]; w[4 * k + 2] = v[2]; w[4 * k + 3] = v[3];
     }
     constexpr int done = N / 16 * 16;
@@ -1304,29 +1295,11 @@ __device__ __forceinline__ void store_plane_rows(float* dst, int lg, const float
 // one box: 111.0 k pairs/s at 4 waves vs 103-104 k at the 129 VGPRs = 3 waves of an otherwise identical build);
 // 32x32 float rows are loaded where they are consumed and need a few more; 64x64 holds 128 + 66 + temporaries
 // (two waves, 254 VGPRs)
-#ifndef LSPIV_WALK_WAVES
-#define LSPIV_WALK_WAVES 3
-#endif
-#ifndef LSPIV_WAVES_MID
-#define LSPIV_WAVES_MID 3
-#endif
-#ifndef LSPIV_WAVES_32F
-#define LSPIV_WAVES_32F 4
-#endif
-#ifndef LSPIV_WAVES_32U8
-#define LSPIV_WAVES_32U8 4
-#endif
-#ifndef LSPIV_WALK_WAVES_MID
-#define LSPIV_WALK_WAVES_MID 3
-#endif
+template <typename T, int N>
+constexpr int kWavesPerSimd = N <= 16 ? 4 : N <= 24 ? 3 : (N == 32 && sizeof(T) < 8) ? 4 : 2;
 // walking kernels: the carried spectrum costs 32 x 32 one wave per SIMD
-#ifndef LSPIV_WALK_WAVES_64
-#define LSPIV_WALK_WAVES_64 2
-#endif
 template <typename T, int N>
-constexpr int kWalkWaves = N <= 16 ? 4 : (N < 32 && sizeof(T) < 8) ? LSPIV_WALK_WAVES_MID : (N == 32 && sizeof(T) < 8) ? LSPIV_WALK_WAVES : N == 64 ? LSPIV_WALK_WAVES_64 : 2;
-template <typename T, int N>
-constexpr int kWavesPerSimd = N <= 16 ? 4 : N <= 24 ? LSPIV_WAVES_MID : (N == 32 && sizeof(T) == 1) ? LSPIV_WAVES_32U8 : (N == 32 && sizeof(T) == 4) ? LSPIV_WAVES_32F : 2;
+constexpr int kWalkWaves = N <= 16 ? 4 : (N <= 32 && sizeof(T) < 8) ? 3 : 2;
 
 // ---- per-timestep kernel: one job (two neighbouring windows of one pair) per lane group ---------
 template <typename T, int N, bool PLANES, bool WANT_NZ>
@@ -1436,8 +1409,9 @@ __device__ __forceinline__ void prepare_one(const RowRaw<T, N>& raw, float (&x)[
 // transpose | FFT | epilogue): they stop the scheduler from stretching live ranges across phases.  32 x 32: removed the
 // last spills at 3 waves/SIMD (+7 %); 64 x 64 (256 VGPRs, 2 waves/SIMD, the carried spectrum is spilled across the
 // inverse transform either way): 50 -> 44 spilled registers and +2.8 %, +3.7 % together with the barriers inside fft64
-// (LSPIV_FFT64_SB; interleaved A/B on one box, 1080p 64 x 64 @ 75 %: 28.7 k -> 29.8 k pairs/s).  The other sizes were
-// measured without and are left alone.
+// (fft_regs.h; interleaved A/B on one box, 1080p 64 x 64 @ 75 %: 28.7 k -> 29.8 k pairs/s).  The other sizes were
+// measured without and are left alone.  RELAX (walk_iteration) drops them: only the 32 x 32 ensemble kernel does (kEnsRelax).
+#define LSPIV_WALK_SB do { if constexpr ((N == 32 || N == 64) && !RELAX) __builtin_amdgcn_sched_barrier(0); } while (0)
 // VALU arbitration priority per phase of a walking iteration (s_setprio; the arbiter serves priority first, then age).  The
 // register FFTs are long runs of independent VALU work; the epilogue (reductions, LDS round trips, logarithms), the loads +
 // row conversion at the top of the next iteration, the transposes and the un-packing are short dependent chains that wait for
@@ -1447,37 +1421,14 @@ __device__ __forceinline__ void prepare_one(const RowRaw<T, N>& raw, float (&x)[
 // rescue off): 32 x 32 6.34 -> 5.95-6.06 ms (-4.5 ... -6 %), 64 x 64 18.0 -> 16.9-17.1 ms (-5.9 %).  Which phases: epilogue +
 // conversion alone bring the same on one box and 1.3 % less on the other; transposes alone or un-packing alone are SLOWER
 // than no priorities (6.52 / 6.44 ms); conversion left at 0 costs 1.5 %; levels 2 / 3 change nothing (docs/history.md).
-// T / U / E / P = priority of transposes / un-packing / epilogue / loads + conversion; the FFTs run at 0.
-#ifndef LSPIV_PRIO_T
-#define LSPIV_PRIO_T 1
-#endif
-#ifndef LSPIV_PRIO_U
-#define LSPIV_PRIO_U 1
-#endif
-#ifndef LSPIV_PRIO_E
-#define LSPIV_PRIO_E 1
-#endif
-#ifndef LSPIV_PRIO_P
-#define LSPIV_PRIO_P LSPIV_PRIO_E   // loads + row conversion at the top of an iteration
-#endif
-#define LSPIV_PRIO_ANY (LSPIV_PRIO_T || LSPIV_PRIO_U || LSPIV_PRIO_E || LSPIV_PRIO_P)
-#define LSPIV_SETPRIO(x) do { if constexpr (LSPIV_PRIO_ANY) __builtin_amdgcn_s_setprio(x); } while (0)
-#ifndef LSPIV_WALK_RELAX
-#define LSPIV_WALK_RELAX 0   // experiment: the per-timestep walking kernels without the barriers (bit mask: 1 = 32 x 32, 2 = 64 x 64)
-#endif
-template <typename T, int N> constexpr bool kWalkRelax = ((LSPIV_WALK_RELAX & 1) && N == 32) || ((LSPIV_WALK_RELAX & 2) && N == 64);
-#ifndef LSPIV_WALK_SB
-#define LSPIV_WALK_SB do { if constexpr ((N == 32 || N == 64) && !RELAX) __builtin_amdgcn_sched_barrier(0); } while (0)
-#endif
+// So: transposes, un-packing, epilogue and loads + conversion run at 1, the FFTs at 0.
+#define LSPIV_SETPRIO(x) __builtin_amdgcn_s_setprio(x)
 
 // float32 rows: every lane reads its own 4 N-byte row 16 bytes at a time.  (Fetching the rows coalesced -- N / 4 consecutive
 // lanes per row -- and staging them through the job's transpose tile was measured and dropped: 104.9 k against 107.5 k pairs/s
 // at 1080p 32 x 32, the 16 extra LDS instructions per frame and 6 spilled registers cost more than the strided loads, which
 // hit L2; DESIGN.md section 4, git history.)
-#ifndef LSPIV_F32_EARLY
-#define LSPIV_F32_EARLY 1
-#endif
-template <int N> constexpr bool kF32Early = LSPIV_F32_EARLY && Geo<N>::FULL;
+template <int N> constexpr bool kF32Early = Geo<N>::FULL;
 
 // Un-pack phase of a walking iteration in batches of B ky steps (walk_iteration, UB): the two incoming exchanges (ds_bpermute) of all
 // B steps are issued first, then the steps run in ascending ky.  Written one ky at a time, the compiler waits for each step's
@@ -1487,6 +1438,7 @@ template <int N> constexpr bool kF32Early = LSPIV_F32_EARLY && Geo<N>::FULL;
 // The value is chosen PER KERNEL from the compiler's resource report (tools/kres.py): a batch must cost
 // no VGPR, no scratch and no wave against B = 1, otherwise the kernel keeps 1 -- as do all sizes that were not looked at.
 // -DLSPIV_UNPACK_BATCH=b forces b for every walking kernel (A/B builds; 1 = the former order everywhere).
+// (override kept: tools/kres.py tries the candidates through it when the resource rule is applied to a new compiler)
 #ifndef LSPIV_UNPACK_BATCH
 #define LSPIV_UNPACK_BATCH -1
 #endif
@@ -1510,6 +1462,7 @@ constexpr int kEnsUnpackBatch = LSPIV_UNPACK_BATCH >= 0 ? LSPIV_UNPACK_BATCH : k
 // behind the two fetches; left alone, the compiler sinks the second frame's address arithmetic and loads below the wait for the
 // first frame's row -- so an iteration waits for memory once instead of twice, as the float32 path does (kF32Early).  Per kernel
 // by the same rule as the batch.  -DLSPIV_U8_EARLY=0 / 1 forces it off / on for every uint8 walking kernel.
+// (override kept: tools/kres.py applies the resource rule through it)
 #ifndef LSPIV_U8_EARLY
 #define LSPIV_U8_EARLY -1
 #endif
@@ -1534,13 +1487,6 @@ template <int N, bool WANT_NZ> constexpr bool kEnsU8Early = LSPIV_U8_EARLY >= 0 
 // (No-return float atomics into lane-major slots were measured first: 44.6 ms -- the L2 atomic units take ~3.5 TB/s, 61 GB of
 // adds per 1000 pairs do not hide behind the arithmetic; at 32 x 32 the same scheme LOSES to the register accumulator, 11.6
 // against 7.0 ms.  docs/history.md, round 4.)
-#ifndef LSPIV_XCD_ORDER_DEFAULT
-#define LSPIV_XCD_ORDER_DEFAULT 1
-#endif
-#ifndef LSPIV_ENS_LDS_RMW
-#define LSPIV_ENS_LDS_RMW 1
-#endif
-template <int N> constexpr bool kEnsLdsRmw = LSPIV_ENS_LDS_RMW && N == 64;
 // ... and HALF of the partial sum stays in LDS for the whole segment: with the half-tile transposes above a wave's LDS is a 9.3 KB tile
 // + 8 KB = the 17.4 KB it had, so columns 0 .. 31 of every lane's row (the first 8 KB of the lane-ordered slot) are accumulated in
 // LDS and written to the slot ONCE per segment; columns 32 .. 63 keep the round trip through the tile (now 8 KB per iteration each way).
@@ -1553,27 +1499,24 @@ template <int N> constexpr bool kEnsLdsRmw = LSPIV_ENS_LDS_RMW && N == 64;
 // the counts are identical): the additions are the same in the same order, but the compiler contracts the symmetric a b + c d
 // products of the un-packing step the other way round in the re-shaped iteration, so the planes themselves move by an ulp.  Across
 // chunkings and job orders the kernel agrees with itself bit for bit (tests/test_gpu_strip_order.py, the ensemble chunking tests).
-#ifndef LSPIV_ENS_HALF_ACC
-#define LSPIV_ENS_HALF_ACC 1
-#endif
-template <int N> constexpr bool kEnsHalfAcc = LSPIV_ENS_HALF_ACC && kEnsLdsRmw<N>;
+// The two full-slot forms it replaced (the whole slot through the tile; the row-major slot of round 3) are retired to
+// docs/experiments/ens64_full_slot_forms.patch.txt.
+template <int N> constexpr bool kEnsHalfAcc = N == 64;
 // Round 6: why do ~27 GB of stores per 1000 pairs reach HBM when the hot halves of an XCD's ~256 live slots are
 // 2 MB in a 4 MB L2?  What was established (tools/ubench/l2_rmw.hip + rocprofv3 WRITE_SIZE; A/B builds of this kernel):
 //   * the L2 IS write-back: 2 MB per XCD re-written 500 times reach HBM once (0.017 GB for 8.4 GB stored), also with 55 us between
 //     two passes (no ageing of dirty lines) and also when the read is a global_load_lds_dwordx4 like here;
 //   * a stream of plain loads next to the slots evicts them (7.0 GB written back at 2 stream bytes per slot byte, 0.018 GB at 1/8),
-//     non-temporal loads do not (0.35 GB) -- but in THIS kernel non-temporal frame loads (LSPIV_ENS64_NT) save 20 % of the written
-//     bytes and quintuple the fetched ones (26.9 -> 21.4 GB, 3.3 -> 15.4 GB, 28.7 -> 31.5 ms): the frames are not what evicts;
+//     non-temporal loads do not (0.35 GB) -- but in THIS kernel non-temporal frame loads save 20 % of the written bytes and
+//     quintuple the fetched ones (26.9 -> 21.4 GB, 3.3 -> 15.4 GB, 28.7 -> 31.5 ms; the 75 % overlap of the windows lives on L2 hits
+//     of the frame lines): the frames are not what evicts;
 //   * hot bytes that are the upper 8 KB of every 16 KB (address bit 13 set: half the sets) are written back 78 x as often in the
-//     micro-benchmark as contiguous ones -- but the split layout below (all cold halves, then all hot halves) moves nothing here:
-//     27.26 vs 27.48 GB written, 30.18 vs 30.19 ms, same bits (tools/sessions_ens64_ab.sh).
+//     micro-benchmark as contiguous ones -- but a split layout (all cold halves, then all hot halves) moves nothing here:
+//     27.26 vs 27.48 GB written, 30.18 vs 30.19 ms, same bits.
 // So: neither a write-through L2, nor the frame stream, nor the slots' address pattern, nor the LDS-direct loads.  Every store of the
 // hot half still reaches the fabric although its line is re-read from the L2 an iteration later (hit rate 95 %); the kernel does not
-// wait for those bytes (VALU-bound).  Dead end recorded; both switches stay for whoever looks next.
-#ifndef LSPIV_ENS_SPLIT_HALVES
-#define LSPIV_ENS_SPLIT_HALVES 0
-#endif
-template <int N> constexpr bool kEnsSplitHalves = LSPIV_ENS_SPLIT_HALVES && kEnsHalfAcc<N>;
+// wait for those bytes (VALU-bound).  Dead end recorded; both experiments are retired to
+// docs/experiments/ens64_nt_split_slots.patch.txt for whoever looks next.
 constexpr int kEnsHalfAccWaveDwords = kHalfTileDwords + 2048;   // tile | half accumulator (lane-ordered: (j / 4) * 256 + lane * 4 + j % 4, j < 32)
 typedef float __attribute__((address_space(1))) * GlobalF32;
 typedef float __attribute__((address_space(3))) * LdsF32;
@@ -1585,32 +1528,14 @@ __device__ __forceinline__ GlobalF32 uniform_global_ptr(const float* p) {   // v
 // Addressing of the slot: SGPR base + the lane's 32-bit byte offset + an immediate (written out: left to the compiler the 16
 // store addresses and 4 prefetch bases become loop-invariant VGPR pairs that are spilled and re-loaded every iteration -- 30 of
 // the kernel's 43 scratch loads per iteration, ~40 GB of the 109 GB it fetched per 1000 pairs, profiles/r04_ens64).
-template <int N>
-__device__ __forceinline__ void slot_prefetch_lds(GlobalF32 slot, float* buf) {   // slot: wave-uniform (uniform_global_ptr)
-  static_assert(N == 64 && Geo<N>::GROUPS == 1 && Geo<N>::LDS_JOB >= N * N, "one job per wave, the tile holds a plane");
+// The slot's second 8 KB (columns 32 .. 63) come in, to the start of the (half) tile
+// (`slot`: the address of the slot's UPPER half, slot + 8 KB; wave-uniform, uniform_global_ptr)
+__device__ __forceinline__ void slot_prefetch_lds_upper(GlobalF32 slot, float* buf) {
   const uint32_t voff = (threadIdx.x & 63u) * 16u;
   const uint32_t lds = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uintptr_t)(LdsF32)buf);
   __builtin_amdgcn_s_waitcnt(0xC07F);   // lgkmcnt(0): the transpose's own reads of the tile have returned
   // M0 = LDS base of the piece (the hardware adds lane * 16), four immediates move the global AND the LDS address by 1 KB each.
   // (The compiler reserves M0 and rejects it in a clobber list: the block saves and restores it.)
-#pragma unroll
-  for (int qq = 0; qq < N / 16; ++qq) {
-    const uint64_t base = reinterpret_cast<uint64_t>(slot) + (uint64_t)qq * 4096u;
-    const uint32_t l = lds + qq * 4096u;
-    uint32_t m0_saved;
-    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %3\n\ts_nop 0\n\t"
-                 "global_load_lds_dwordx4 %1, %2\n\tglobal_load_lds_dwordx4 %1, %2 offset:1024\n\t"
-                 "global_load_lds_dwordx4 %1, %2 offset:2048\n\tglobal_load_lds_dwordx4 %1, %2 offset:3072\n\t"
-                 "s_mov_b32 m0, %0"
-                 : "=&s"(m0_saved) : "v"(voff), "s"(base), "s"(l) : "memory");
-  }
-}
-// the half-accumulator variant: only the slot's second 8 KB (columns 32 .. 63) come in, to the start of the (half) tile
-// (`slot`: the address of the slot's UPPER half -- slot + 8 KB in the interleaved layout, the slot's entry of the hot array in the split one)
-__device__ __forceinline__ void slot_prefetch_lds_upper(GlobalF32 slot, float* buf) {
-  const uint32_t voff = (threadIdx.x & 63u) * 16u;
-  const uint32_t lds = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uintptr_t)(LdsF32)buf);
-  __builtin_amdgcn_s_waitcnt(0xC07F);   // lgkmcnt(0): the transpose's own reads of the tile have returned
 #pragma unroll
   for (int qq = 0; qq < 2; ++qq) {
     const uint64_t base = reinterpret_cast<uint64_t>(slot) + (uint64_t)qq * 4096u;
@@ -1629,41 +1554,13 @@ __device__ __forceinline__ void slot_store4(uint64_t base, uint32_t voff, const 
                :: "v"(voff), "s"(base), "v"(v[0]), "v"(v[1]), "v"(v[2]), "v"(v[3]) : "memory");
 }
 // acc <- (acc + m0 c0) + m1 c1, m in {0, 1} (exact products: the additions of the masked planes in pair order); `init`: the
-// slot holds nothing yet (no prefetch was issued)
-template <int N>
-__device__ __forceinline__ void slot_accumulate(GlobalF32 slot, const float* buf, const float (&c0)[N], bool keep0, const float (&c1)[N],
-                                                bool keep1, bool init_) {
-  const int lane = threadIdx.x & 63;
-  const bool init = __builtin_amdgcn_readfirstlane((int)init_) != 0;   // one job per wave: uniform, and the compiler may know it
-  const bool any = __builtin_amdgcn_readfirstlane((int)(keep0 || keep1)) != 0;
-  if (!init) __builtin_amdgcn_s_waitcnt(0x0F70);   // vmcnt(0): the slot has landed in the tile -- and nothing of it arrives later
-  if (!init && !any) return;
-  const float m0 = keep0 ? 1.0f : 0.0f, m1 = keep1 ? 1.0f : 0.0f;
-  const float* lsrc = buf + lane * 4;
-  const uint32_t voff = (uint32_t)lane * 16u;
-#pragma unroll
-  for (int qq = 0; qq < N / 16; ++qq) {
-    f32x4 a[4];
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-      const int q = 4 * qq + k;
-      if (init) a[k] = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
-      else a[k] = *reinterpret_cast<const f32x4*>(lsrc + q * 256);
-#pragma unroll
-      for (int e = 0; e < 4; ++e) a[k][e] = fmaf(c1[4 * q + e], m1, fmaf(c0[4 * q + e], m0, a[k][e]));
-    }
-    slot_store4(reinterpret_cast<uint64_t>(slot) + (uint64_t)qq * 4096u, voff, a);
-    __builtin_amdgcn_sched_barrier(0);   // sixteen registers of sums at a time
-  }
-}
-
-// the half-accumulator variant of slot_accumulate: columns 0 .. 31 read-modify-write `hacc` (LDS, stays), columns 32 .. 63 take the
+// slot holds nothing yet (no prefetch was issued).  Columns 0 .. 31 read-modify-write `hacc` (LDS, stays), columns 32 .. 63 take the
 // prefetched upper half of the slot from the tile and go back to HBM
 // (`slot`: the slot's UPPER half, as for slot_prefetch_lds_upper)
 __device__ __forceinline__ void slot_accumulate_half(GlobalF32 slot, const float* buf, float* hacc, const float (&c0)[64], bool keep0,
                                                      const float (&c1)[64], bool keep1, bool init_) {
   const int lane = threadIdx.x & 63;
-  const bool init = __builtin_amdgcn_readfirstlane((int)init_) != 0;
+  const bool init = __builtin_amdgcn_readfirstlane((int)init_) != 0;   // one job per wave: uniform, and the compiler may know it
   const bool any = __builtin_amdgcn_readfirstlane((int)(keep0 || keep1)) != 0;
   if (!init && !any) { __builtin_amdgcn_s_waitcnt(0x0F70); return; }   // nothing to add; the prefetch still has to land before the tile is reused
   const float m0 = keep0 ? 1.0f : 0.0f, m1 = keep1 ? 1.0f : 0.0f;
@@ -1764,9 +1661,9 @@ static inline uint32_t walk_blocks(uint32_t n_seg, uint32_t n_win, uint32_t jobs
   }
   return (uint32_t)(((uint64_t)n_seg * n_win + jobs_per_block - 1) / jobs_per_block);
 }
-// LSPIV_XCD_ORDER: 0 / 1 = by_windows above (A/B; read once per process)
+// LSPIV_XCD_ORDER: 0 / 1 = by_windows above (A/B; read once per process; unset = 1)
 static inline uint32_t walk_xcd_by_windows() {
-  static const int env = getenv("LSPIV_XCD_ORDER") ? atoi(getenv("LSPIV_XCD_ORDER")) : LSPIV_XCD_ORDER_DEFAULT;
+  static const int env = getenv("LSPIV_XCD_ORDER") ? atoi(getenv("LSPIV_XCD_ORDER")) : 1;
   return env != 0 ? 1u : 0u;
 }
 
@@ -1835,7 +1732,6 @@ __device__ __forceinline__ void walk_iteration(const PivParams& p, const T* row,
   constexpr int H = N / 2;
   bool dead0, dead1, fin0 = true, fin1 = true;
   int nz0 = G::NN, nz1 = G::NN;
-  if constexpr (LSPIV_PRIO_P != LSPIV_PRIO_E) LSPIV_SETPRIO(LSPIV_PRIO_P);
   if constexpr (sizeof(T) == 4 && kF32Early<N>) {
     // float32 rows: the loads of BOTH frames are in flight before the first is consumed (they land in xr / xi, the registers
     // they are converted in), so an iteration waits for memory once instead of twice
@@ -1857,10 +1753,7 @@ __device__ __forceinline__ void walk_iteration(const PivParams& p, const T* row,
     dead1 = inv1 == 0.0f;
   } else {
     RowRaw<T, N> raw0, raw1;
-    if constexpr (sizeof(T) == 1 && HALF_TILE && LSPIV_ENS64_NT) {   // the 64 x 64 ensemble kernel: frames past the L2-resident slots
-      raw0.template fetch<true>(row);
-      raw1.template fetch<true>(has2 ? row + p.frame_elems : row);
-    } else if constexpr (U8_EARLY && sizeof(T) == 1) {
+    if constexpr (U8_EARLY && sizeof(T) == 1) {
       const T* row1 = has2 ? row + p.frame_elems : row;
       __builtin_amdgcn_sched_barrier(0);   // the second address is formed before the first load ...
       raw0.fetch(row);
@@ -1874,7 +1767,7 @@ __device__ __forceinline__ void walk_iteration(const PivParams& p, const T* row,
     LSPIV_WALK_SB;
     prepare_one<T, N, WANT_NZ, S16>(raw1, xi, p.nz_positive != 0, p.std_gain, nz1, fin1, dead1);
   }
-  if constexpr (kEnsLdsRmw<N>) {
+  if constexpr (kEnsHalfAcc<N>) {
     if (one_job_per_wave_ens) {   // (compile-time false in the per-timestep kernel)
       // 64 x 64 ensemble kernel: the two "zero-variance window" flags as scalars now -- left as they are, the compiler keeps the
       // two 1 / std in VGPRs across all four transforms (spilled and re-loaded) to compare them with zero at the very end
@@ -1886,13 +1779,13 @@ __device__ __forceinline__ void walk_iteration(const PivParams& p, const T* row,
   LSPIV_SETPRIO(0);
   fft_walk<false, false, FOLD, SR>(xr, xi);   // along x
   LSPIV_WALK_SB;
-  LSPIV_SETPRIO(LSPIV_PRIO_T);
+  LSPIV_SETPRIO(1);
   transpose2<N, HALF_TILE, UDPP ? ColMap::kToPaired : ColMap::kNatural>(buf, lg, xr, xi);    // lane = kx (UDPP: unpack_col(lane)), regs = y
   LSPIV_WALK_SB;
   LSPIV_SETPRIO(0);
   fft_walk<false, false, FOLD, SR>(xr, xi);   // along y -> Z[ky][kx]
   LSPIV_WALK_SB;
-  LSPIV_SETPRIO(LSPIV_PRIO_U);
+  LSPIV_SETPRIO(1);
   // un-pack the two spectra, form both cross spectra and pack them for the shared inverse, one ky at a time (a
   // step only touches registers ky and N - ky of this lane and of the mirrored lane, so it can run in place)
   if constexpr (UDPP && UG > 2) {
@@ -1963,12 +1856,12 @@ __device__ __forceinline__ void walk_iteration(const PivParams& p, const T* row,
   LSPIV_SETPRIO(0);
   fft_walk<true, false, FOLD, SR>(xr, xi);    // along ky
   LSPIV_WALK_SB;
-  LSPIV_SETPRIO(LSPIV_PRIO_T);
+  LSPIV_SETPRIO(1);
   transpose2<N, HALF_TILE, UDPP ? ColMap::kFromPaired : ColMap::kNatural>(buf, lg, xr, xi);      // lane = y, regs = kx
-  if constexpr (kEnsLdsRmw<N>) {
-    // 64 x 64 ensemble kernel: the job's tile is free from here to the next iteration's first transpose -- the running partial
-    // sum of the job starts its way from HBM into it now (asynchronously, no registers) and is there when the planes are final
-    if (acc_slot) { if constexpr (HALF_TILE) slot_prefetch_lds_upper(acc_slot, buf); else slot_prefetch_lds<N>(acc_slot, buf); }
+  if constexpr (kEnsHalfAcc<N>) {
+    // 64 x 64 ensemble kernel: the job's tile is free from here to the next iteration's first transpose -- the upper half of the job's
+    // running partial sum starts its way from HBM into it now (asynchronously, no registers) and is there when the planes are final
+    if (acc_slot) slot_prefetch_lds_upper(acc_slot, buf);
   }
   LSPIV_WALK_SB;
   LSPIV_SETPRIO(0);
@@ -1990,7 +1883,7 @@ __device__ __forceinline__ void walk_iteration(const PivParams& p, const T* row,
       xi[j] = __builtin_amdgcn_fmed3f(xi[j], 0.0f, hi_b);
     }
   }
-  LSPIV_SETPRIO(LSPIV_PRIO_E);         // epilogue, and the next iteration's loads + row conversion
+  LSPIV_SETPRIO(1);         // epilogue, and the next iteration's loads + row conversion
   skip_a = !(c.prev_finite && fin0);
   skip_b = !(fin0 && fin1);
   if (WANT_NZ) {
@@ -2014,6 +1907,7 @@ __device__ __forceinline__ void walk_iteration(const PivParams& p, const T* row,
 // count, never on one group's frame index: the two groups of a wave can sit in segments of different lengths.
 // Per kernel by the resource rule of the un-pack batch above (no VGPR above the three-wave step, no scratch, no wave lost against the
 // kernel without it; tools/kres.py); the "defer_fit" option picks the form at launch.  -DLSPIV_WALK_DEFER=0 / 1 forces it off / on.
+// (override kept: tools/kres.py applies the resource rule through it; the GPU tests compare both forms bit for bit through the option)
 #ifndef LSPIV_WALK_DEFER
 #define LSPIV_WALK_DEFER -1
 #endif
@@ -2023,14 +1917,14 @@ constexpr bool kWalkDefer32[3][2][2] = {{{true, true}, {true, true}}, {{true, tr
 template <typename T, int N, bool PLANES, bool WANT_NZ>
 constexpr bool kWalkDefer = N == 32 && (LSPIV_WALK_DEFER >= 0 ? LSPIV_WALK_DEFER != 0 : kWalkDefer32[kSampleKind<T>][PLANES][WANT_NZ]);
 // The un-packing through DPP (UDPP, unpack_col): per kernel by the same resource rule, the "unpack_dpp" option picks the form at launch;
-// -DLSPIV_UNPACK_DPP=0 / 1 forces it off / on for every per-pair 32 x 32 walking kernel.  [sample type][PLANES][WANT_NZ]; all twelve, in
+// -DLSPIV_UNPACK_DPP=0 / 1 forces it off / on for every per-pair 32 x 32 walking kernel.  All twelve ([sample type][PLANES][WANT_NZ]), in
 // both forms of the fit, need no more VGPRs than the LDS form (up to 8 fewer: the batch's transient registers go), no scratch, no wave lost
+// (override kept: tools/kres.py applies the resource rule through it; the GPU tests compare both forms bit for bit through the option)
 #ifndef LSPIV_UNPACK_DPP
 #define LSPIV_UNPACK_DPP -1
 #endif
-constexpr bool kWalkUnpackDpp32[3][2][2] = {{{true, true}, {true, true}}, {{true, true}, {true, true}}, {{true, true}, {true, true}}};
 template <typename T, int N, bool PLANES, bool WANT_NZ>
-constexpr bool kWalkUnpackDpp = N == 32 && (LSPIV_UNPACK_DPP >= 0 ? LSPIV_UNPACK_DPP != 0 : kWalkUnpackDpp32[kSampleKind<T>][PLANES][WANT_NZ]);
+constexpr bool kWalkUnpackDpp = N == 32 && LSPIV_UNPACK_DPP != 0;   // (left alone: on)
 // "LDS-light" form of the per-pair 32 x 32 walking kernels (LITE, option "lds_light"), on top of the shipped DEFER / UDPP choices only:
 //  * kWalkSwap16: the ten 32-lane reductions of an iteration (sums and sums of squares of the two frames; plane maximum, peak row and
 //    peak column of the two planes) join their two 16-lane rows with v_permlane16_swap instead of ds_swizzle(SWAP,16) + s_waitcnt
@@ -2042,20 +1936,20 @@ constexpr bool kWalkUnpackDpp = N == 32 && (LSPIV_UNPACK_DPP >= 0 ? LSPIV_UNPACK
 //    the former form.  -DLSPIV_UNPACK_GROUP=n forces n (2, 4, 8 or 16).
 // Per kernel by the resource rule of the un-pack batch above (tools/kres.py): no more VGPRs than the three-wave step allows, no scratch
 // byte, no wave lost; of the admissible group sizes the one with the fewest scalar instructions in the un-pack segment.
-// [sample type][PLANES][WANT_NZ].  A kernel with neither (all switches off) has no LITE instantiation.
+// All twelve 32 x 32 kernels take kWalkSwap16.  A kernel with neither (all switches off) has no LITE instantiation.
+// (overrides kept: tools/kres.py applies the resource rule through them, tests/test_walk_lds_light_host.py builds with -DLSPIV_UNPACK_GROUP=16;
+// the GPU tests compare the forms bit for bit through the option)
 #ifndef LSPIV_SWAP16
 #define LSPIV_SWAP16 -1
 #endif
 #ifndef LSPIV_UNPACK_GROUP
 #define LSPIV_UNPACK_GROUP -1
 #endif
-constexpr bool kWalkSwap16_32[3][2][2] = {{{true, true}, {true, true}}, {{true, true}, {true, true}}, {{true, true}, {true, true}}};
-// (16 is admissible for all twelve and measured -0.2 ... -0.4 % on top of kWalkSwap16 with overlapping runs: not a gain, so every entry is 2)
-constexpr int kWalkUnpackGroup32[3][2][2] = {{{2, 2}, {2, 2}}, {{2, 2}, {2, 2}}, {{2, 2}, {2, 2}}};
 template <typename T, int N, bool PLANES, bool WANT_NZ>
-constexpr bool kWalkSwap16 = N == 32 && (LSPIV_SWAP16 >= 0 ? LSPIV_SWAP16 != 0 : kWalkSwap16_32[kSampleKind<T>][PLANES][WANT_NZ]);
+constexpr bool kWalkSwap16 = N == 32 && LSPIV_SWAP16 != 0;   // (left alone: on)
+// (16 is admissible for all twelve and measured -0.2 ... -0.4 % on top of kWalkSwap16 with overlapping runs: not a gain, so every kernel keeps 2)
 template <typename T, int N, bool PLANES, bool WANT_NZ>
-constexpr int kWalkUnpackGroup = N != 32 ? 2 : LSPIV_UNPACK_GROUP >= 0 ? LSPIV_UNPACK_GROUP : kWalkUnpackGroup32[kSampleKind<T>][PLANES][WANT_NZ];
+constexpr int kWalkUnpackGroup = (N == 32 && LSPIV_UNPACK_GROUP >= 0) ? LSPIV_UNPACK_GROUP : 2;
 template <typename T, int N, bool PLANES, bool WANT_NZ>
 constexpr bool kWalkLite = kWalkUnpackDpp<T, N, PLANES, WANT_NZ> && (kWalkSwap16<T, N, PLANES, WANT_NZ> || kWalkUnpackGroup<T, N, PLANES, WANT_NZ> > 2);
 // "Scalar epilogue" form (SCAL, option "scalar_epilogue"), on top of DEFER + UDPP + LITE (kWalkSwap16) only.  What the peak search computes
@@ -2066,6 +1960,7 @@ constexpr bool kWalkLite = kWalkUnpackDpp<T, N, PLANES, WANT_NZ> && (kWalkSwap16
 // arithmetic: the bits stay.  Per kernel by the resource rule of the un-pack batch above (tools/kres.py); -DLSPIV_WALK_SCALAR=0 / 1
 // forces it off / on.  [sample type][PLANES][WANT_NZ]; all ten kernels with a batched fit stay inside the step (147 ... 166 VGPRs, no
 // scratch, three waves); float64 with the score has no batched fit to sit on
+// (override kept: tools/kres.py applies the resource rule through it; the GPU tests compare both forms bit for bit through the option)
 #ifndef LSPIV_WALK_SCALAR
 #define LSPIV_WALK_SCALAR -1
 #endif
@@ -2073,16 +1968,13 @@ constexpr bool kWalkScalar32[3][2][2] = {{{true, true}, {true, true}}, {{true, t
 template <typename T, int N, bool PLANES, bool WANT_NZ>
 constexpr bool kWalkScalar = kWalkLite<T, N, PLANES, WANT_NZ> && kWalkSwap16<T, N, PLANES, WANT_NZ> && kWalkDefer<T, N, PLANES, WANT_NZ> &&
                              (LSPIV_WALK_SCALAR >= 0 ? LSPIV_WALK_SCALAR != 0 : kWalkScalar32[kSampleKind<T>][PLANES][WANT_NZ]);
-// The first iteration of a wave has no pair f - 1 in either group (f == p0): with LSPIV_SKIP_FIRST_A the 32 x 32 kernels leave out the
-// maximum, the search and the fit of its plane a -- nothing of it is stored, and a record slot that is not written stays invalid.
-#ifndef LSPIV_SKIP_FIRST_A
-#define LSPIV_SKIP_FIRST_A 1
-#endif
+// The first iteration of a wave has no pair f - 1 in either group (f == p0): the 32 x 32 kernels leave out the maximum, the search
+// and the fit of its plane a -- nothing of it is stored, and a record slot that is not written stays invalid.
 // Per kernel by the resource rule again: the branch keeps plane a's registers live across plane b's maximum, and without PLANES (where they
 // are live up to the plane stores anyway) only the uint8 kernels without the score stay free of scratch (149 -> 167 VGPRs); the float32
 // ones spill 8 - 32 bytes, the float64 one loses its third wave (167 -> 178).
 template <typename T, int N, bool PLANES, bool WANT_NZ>
-constexpr bool kWalkSkipFirstA = LSPIV_SKIP_FIRST_A && N == 32 && (PLANES || (sizeof(T) == 1 && !WANT_NZ));
+constexpr bool kWalkSkipFirstA = N == 32 && (PLANES || (sizeof(T) == 1 && !WANT_NZ));
 // the packed word of a record: ip | jp << 8 | flags
 constexpr uint32_t kDeferNearTie = 1u << 16, kDeferDead = 1u << 17, kDeferSkip = 1u << 18, kDeferValid = 1u << 19, kDeferNote = 1u << 20;
 
@@ -2313,7 +2205,7 @@ __global__ __launch_bounds__(BLOCK, (kWalkWaves<T, N>)) void piv_fft_walk_kernel
     const bool has2 = f + 1 <= p1;
     float xr[N], xi[N], mean_a, mean_b;
     bool skip_a, skip_b, dead_a, dead_b;
-    walk_iteration<T, N, WANT_NZ, kWalkRelax<T, N>, false, kWalkUnpackBatch<T, N, PLANES, WANT_NZ>, kWalkU8Early<N, PLANES, WANT_NZ>, kFftFoldWalk<N>, kFftSrWalk<N>, UDPP, S16, UG, SCAL>(
+    walk_iteration<T, N, WANT_NZ, false, false, kWalkUnpackBatch<T, N, PLANES, WANT_NZ>, kWalkU8Early<N, PLANES, WANT_NZ>, kFftFoldWalk<N>, kFftSrWalk<N>, UDPP, S16, UG, SCAL>(
         p, row, has2, buf, lg, partner_byte, lane0_byte, carry, xr, xi, mean_a, mean_b, skip_a, skip_b, dead_a, dead_b);
     if (WANT_NZ && win_dropped) skip_a = skip_b = true;
     const bool with_a = !kWalkSkipFirstA<T, N, PLANES, WANT_NZ> || it != 0;   // wave-uniform: no group has a pair f - 1 in the wave's first iteration
@@ -3000,22 +2892,15 @@ static hipError_t launch_shift_ensemble(const PivParams& p, int dtype, hipStream
 // job's partial sum instead of being searched for a peak.  A job = (time segment, window); each segment has its own
 // partial sum in HBM (zeroed by the caller), merged afterwards in segment order (ensemble_merge_kernel): fixed
 // summation order, no atomics, and ~3 rounds of jobs on the chip where one job per window would leave it 2/3 idle.
-// LSPIV_ENS_REGACC: the job's partial sum lives in N VGPRs per lane for the whole segment (lane = row y, register =
+// kEnsRegAcc: the job's partial sum lives in N VGPRs per lane for the whole segment (lane = row y, register =
 // column x, the layout the planes come out of the inverse transform in) and is stored once at the end, instead of a
 // read-modify-write of its HBM slot every iteration.  Same sequence of float additions per element => same bits.
-#ifndef LSPIV_ENS_REGACC
-#define LSPIV_ENS_REGACC 1
-#endif
-template <int N> constexpr bool kEnsRegAcc = LSPIV_ENS_REGACC && N <= 32;
-#ifndef LSPIV_WALK_ENS_WAVES_32
-#define LSPIV_WALK_ENS_WAVES_32 2
-#endif
-#ifndef LSPIV_ENS32_RELAX
-#define LSPIV_ENS32_RELAX 1   // measured: 6.78 -> 6.02 ms per 1000 pairs (147 k -> 166 k pairs/s): without the barriers the allocator needs 168 VGPRs instead of 194 and a third wave fits
-#endif
-template <typename T, int N> constexpr bool kEnsRelax = LSPIV_ENS32_RELAX && N == 32 && kEnsRegAcc<N> && sizeof(T) < 8;
+template <int N> constexpr bool kEnsRegAcc = N <= 32;
+// 32 x 32 without the scheduling barriers, measured: 6.78 -> 6.02 ms per 1000 pairs (147 k -> 166 k pairs/s): the allocator needs 168
+// VGPRs instead of 194 and a third wave fits
+template <typename T, int N> constexpr bool kEnsRelax = N == 32 && sizeof(T) < 8;
 template <typename T, int N>
-constexpr int kWalkEnsWaves = (kEnsRegAcc<N> && N == 32 && sizeof(T) < 8) ? LSPIV_WALK_ENS_WAVES_32 : kWalkWaves<T, N>;
+constexpr int kWalkEnsWaves = (N == 32 && sizeof(T) < 8) ? 2 : kWalkWaves<T, N>;
 // Relaxed (no barriers), the uint8 kernel without a signal threshold allocates 168 VGPRs by itself: a third wave fits although the
 // bound says two (166 k pairs/s; bounded at three it spills 28 bytes: 163 k).  The variants that count non-zero samples and the
 // float32 ones come out at 173 - 174 and would run two waves: they are bounded at three (168 VGPRs + 28 ... 44 bytes of scratch).
@@ -3053,11 +2938,10 @@ __global__ __launch_bounds__(BLOCK, (kWalkEnsBound<T, N, WANT_NZ>)) void piv_fft
   // the job's partial-sum slot is that of its (segment, WINDOW): ensemble_merge_kernel adds the segments' slots of a window in
   // segment order, whatever order the jobs ran in (strip_order permutes the windows of a segment)
   const uint32_t pslot = seg * p.n_win + win;
-  float* part = p.part_sum + (size_t)pslot * (kEnsSplitHalves<N> ? G::NN / 2 : G::NN);      // split: the slot's entry of the cold array
-  const GlobalF32 part_u = kEnsLdsRmw<N> ? uniform_global_ptr(part) : nullptr;   // one job per wave: the slot pointer lives in SGPRs
-  // the half that is re-written every iteration: the slot's entry of the hot array (split layout), or its second 8 KB
-  const GlobalF32 part_hi = !kEnsHalfAcc<N> ? part_u
-                            : uniform_global_ptr(kEnsSplitHalves<N> ? p.part_sum + ((size_t)p.n_seg * p.n_win + pslot) * (G::NN / 2) : part + G::NN / 2);
+  float* part = p.part_sum + (size_t)pslot * G::NN;
+  const GlobalF32 part_u = kEnsHalfAcc<N> ? uniform_global_ptr(part) : nullptr;   // one job per wave: the slot pointer lives in SGPRs
+  // the half that is re-written every iteration: the slot's second 8 KB
+  const GlobalF32 part_hi = kEnsHalfAcc<N> ? uniform_global_ptr(part + G::NN / 2) : nullptr;
   const bool win_dropped = WANT_NZ && p.win_keep && !p.win_keep[win];
   float cnt = 0.0f;
   float acc[kEnsRegAcc<N> ? N : 1];
@@ -3074,11 +2958,11 @@ __global__ __launch_bounds__(BLOCK, (kWalkEnsBound<T, N, WANT_NZ>)) void piv_fft
     bool skip[2], keep[2], dead[2];
     walk_iteration<T, N, WANT_NZ, kEnsRelax<T, N>, kEnsHalfAcc<N>, kEnsUnpackBatch<T, N, WANT_NZ>, kEnsU8Early<N, WANT_NZ>>(
         p, row, has2, buf, lg, partner_byte, lane0_byte, carry, xr, xi, mean[0], mean[1], skip[0], skip[1], dead[0], dead[1],
-        (kEnsLdsRmw<N> && !first) ? part_hi : nullptr, kEnsLdsRmw<N>);
+        (kEnsHalfAcc<N> && !first) ? part_hi : nullptr, kEnsHalfAcc<N>);
     if (WANT_NZ && win_dropped) skip[0] = skip[1] = true;
     const bool valid[2] = {job_valid && f > p0, job_valid && has2};
     float vmaxs[2];
-    if constexpr (kEnsLdsRmw<N>) {
+    if constexpr (kEnsHalfAcc<N>) {
       // 256 VGPRs, both planes and the carry live: four running maxima per plane instead of the 22-wide first level of plane_max's tree
       float ma[4] = {xr[0], xr[1], xr[2], xr[3]}, mb[4] = {xi[0], xi[1], xi[2], xi[3]};
 #pragma unroll
@@ -3113,11 +2997,8 @@ __global__ __launch_bounds__(BLOCK, (kWalkEnsBound<T, N, WANT_NZ>)) void piv_fft
         acc[j] += keep[0] ? xr[j] : 0.0f;   // pair f-1 first, then f: the reference's summation order
         acc[j] += keep[1] ? xi[j] : 0.0f;
       }
-    } else if constexpr (kEnsLdsRmw<N>) {
-      if constexpr (kEnsHalfAcc<N>) {
-        if (job_valid) slot_accumulate_half(part_hi, buf, hacc, xr, keep[0], xi, keep[1], first);
-        else __builtin_amdgcn_s_waitcnt(0x0F70);
-      } else if (job_valid) slot_accumulate<N>(part_u, buf, xr, keep[0], xi, keep[1], first);
+    } else if constexpr (kEnsHalfAcc<N>) {
+      if (job_valid) slot_accumulate_half(part_hi, buf, hacc, xr, keep[0], xi, keep[1], first);
       else __builtin_amdgcn_s_waitcnt(0x0F70);   // (a job past the end stores nothing, but its prefetch still has to land before the tile is reused)
       first = false;
     } else {
@@ -3152,12 +3033,12 @@ static hipError_t launch_t(const PivParams& p, bool ensemble, hipStream_t s) {
     PivParams q = p;
     q.strip_w = walk_strip_width<T, N>();
     q.xcd_by_windows = walk_xcd_by_windows();
-    constexpr size_t ens_lds = kEnsHalfAcc<N> ? (size_t)WAVES_PER_BLOCK * kEnsHalfAccWaveDwords * 4 : (size_t)G::LDS_BYTES;
+    constexpr size_t ens_lds = kEnsHalfAcc<N> ? (size_t)WAVES_PER_BLOCK * kEnsHalfAccWaveDwords * 4 : (size_t)G::LDS_BYTES;   // (64 x 64: tile + half accumulator per wave)
     hipLaunchKernelGGL((piv_fft_walk_ensemble_kernel<T, N, WANT_NZ>), dim3(walk_blocks(p.n_seg, p.n_win, jobs_per_block, q.xcd_by_windows)),
                        dim3(BLOCK), ens_lds, s, q);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess || !p.corr_sum) return e;   // no corr_sum: the per-segment slots are what the caller wants (sliding ensemble)
-    return launch_ensemble_merge(p.part_sum, p.part_cnt, p.n_seg, p.n_win, G::NN, p.corr_sum, p.corr_count, s, kEnsLdsRmw<N> ? N : 0, kEnsSplitHalves<N>);
+    return launch_ensemble_merge(p.part_sum, p.part_cnt, p.n_seg, p.n_win, G::NN, p.corr_sum, p.corr_count, s, kEnsHalfAcc<N> ? N : 0);
   }
   if (ensemble) {
     const uint32_t jobs = p.n_win;
